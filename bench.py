@@ -12,14 +12,21 @@ deblocking wavefront of one overlaps the throughput-bound motion search of the o
 Closed GOPs are independent under fixed QP and concatenate to the serial stream.
 N GPUs = N independent streams, one process per GPU, no data-path collective (weak
 scaling); torch.distributed is used only for the barrier and the max-over-ranks clock.
-G = 1 is measured too (single_gop_in_flight_fps), and the kernels of one instance running
-alone (roofline_exclusive / kernels_exclusive).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0): the headline
+(`value`, `ms_per_step`, ...) and the figures read off the timed steps' own per-kernel HIP events
+(`kernels`, `roofline` for the transform kernel k_tq, `roofline_me`, `roofline_pipeline`).
 
-Prints ONE JSON line (rank 0) carrying `roofline` for the transform kernel (k_tq) and
-`cpu_baseline` (the CPU oracle timed on this box's host cores, rank 0, N=1 only), plus `plugin`:
+`--full` adds everything that takes runs of its own: G = 1 (single_gop_in_flight_fps,
+roofline_isolated), the kernels of one instance running alone (roofline_exclusive /
+kernels_exclusive), the batch-vs-single self-check, the VALU issue bound of the committed profiles,
+`cpu_baseline` (the CPU oracle timed on this box's host cores, rank 0, N=1 only), and `plugin`:
 the same engine measured through the actual drop-in boundary in the reference's operating mode
 (CreateVideoEncoder -> EncodeOneFrame on HOST I420 pictures, bitrate rate control, one picture at a
 time per stream, S streams side by side; PCIe included) - never the headline, always beside it.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0): DIR/gop_bytes.npy and
+DIR/picture_bytes.npy (sizes of every GOP and access unit), DIR/bitstream.npy (the bytes of a fixed,
+seeded selection of whole GOPs, at most 48 MiB as float32) and DIR/bitstream_gops.npy (which GOPs).
 
 `python bench.py --gpus N` without a launcher (no RANK in the environment) starts N child
 processes itself, one per GPU, BEFORE anything touches a GPU, and relays rank 0's line.
@@ -53,6 +60,9 @@ ME_BYTES_PER_MB = 384 + 384 + 384 + 32
 # whole pipeline, P picture: 2 720 B per macroblock
 PIPE_BYTES_PER_MB = 2720
 HBM_PEAK_GBS = 8000.0
+# --dump-outputs: at most this many bitstream bytes (one float32 each), whole GOPs picked in a seeded order
+DUMP_BITSTREAM_VALUES = 12 << 20
+DUMP_SEED = 0
 
 
 def cpu_limits():
@@ -385,6 +395,29 @@ def valu_issue_bound(nmb):
         return None
 
 
+def dump_outputs(path, outs, cap, sizes, gop_bytes):
+    """What the last step handed its caller, per GOP g = instance * batch + index: the access unit sizes, the GOP sizes and
+    the bytes of whole GOPs taken in a seeded order while they fit DUMP_BITSTREAM_VALUES (the first one cut there if it alone
+    does not), concatenated in GOP order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    B = len(gop_bytes[0])
+    gb = np.concatenate(gop_bytes).astype(np.int64)
+    streams = [outs[g // B][(g % B) * cap:(g % B) * cap + int(gb[g])] for g in range(len(gb))]
+    chosen, total = [], 0
+    for g in np.random.default_rng(DUMP_SEED).permutation(len(gb)):
+        if total + gb[g] > DUMP_BITSTREAM_VALUES and chosen:
+            continue
+        chosen.append(int(g))
+        total += int(gb[g])
+    chosen.sort()
+    bits = np.concatenate([streams[g] for g in chosen])[:DUMP_BITSTREAM_VALUES]
+    np.save(os.path.join(path, "gop_bytes.npy"), gb.astype(np.float64))
+    np.save(os.path.join(path, "picture_bytes.npy"), np.concatenate(sizes).astype(np.float64).reshape(len(gb), -1))
+    np.save(os.path.join(path, "bitstream.npy"), bits.astype(np.float32))
+    np.save(os.path.join(path, "bitstream_gops.npy"), np.asarray(chosen, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -414,8 +447,15 @@ def main():
     ap.add_argument("--streams", default="1,4,16,64", help="plugin measurement: numbers of concurrent streams (encoder objects), comma separated")
     ap.add_argument("--plugin-frames", type=int, default=300, help="plugin measurement: pictures per stream (10 s at 30 Hz)")
     ap.add_argument("--bitrate", type=int, default=5000000, help="plugin measurement: target bitrate (the reference accepts 1..10 Mbps)")
-    ap.add_argument("--no-plugin", action="store_true", help="leave the plugin measurement out of the default line")
+    ap.add_argument("--no-plugin", action="store_true", help="leave the plugin measurement out of the --full line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks: one GOP in flight, one instance alone, the batch-vs-single self-check, "
+                         "the VALU issue bound, the plugin measurement and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (gops mode, rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "gops":
+        ap.error("--dump-outputs applies to --mode gops")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher: start one child per GPU ourselves - before this process has touched a GPU (nothing below this
@@ -512,7 +552,7 @@ def main():
     outs = [np.zeros(B * cap, np.uint8) for _ in range(I)]
     sizes = [np.zeros(B * FRAMES_PER_STEP, np.uint32) for _ in range(I)]
     gop_bytes = [np.zeros(B, np.uint64) for _ in range(I)]
-    enc1 = capi.Encoder(WIDTH, HEIGHT, **enc_kw) if G > 1 else None
+    enc1 = capi.Encoder(WIDTH, HEIGHT, **enc_kw) if G > 1 and args.full else None
     out1 = np.zeros(cap, np.uint8)
     sizes1 = np.zeros(FRAMES_PER_STEP, np.uint32)
 
@@ -580,34 +620,36 @@ def main():
                 st["kernels"][name][key] += v[key]
         for key in ("p_mbs", "me_searched_mbs", "tq_coded_mbs"):
             st[key] += o[key]
-    if enc1 is not None:
-        enc1.stats(reset=True)
-    # the same kernels with the chip to themselves: instance 0 alone, one step (only when instances overlap)
-    st_ex = None
-    if I > 1:
-        run_inst(0)
-        torch.cuda.synchronize()
-        st_ex = enc.stats(reset=True)
-    # latency mode for reference: one GOP in flight, kernels alone on the GPU (also gives the
-    # MC+DCT kernel's duration without other streams' kernels sharing the chip)
-    fence()
-    t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs, cap, sizes, gop_bytes)
+    st_ex = st1 = lat_dt = selfcheck = None
     lat_steps = 2
-    for _ in range(lat_steps):
-        one_gop(0)
-    fence()
-    lat_dt = time.perf_counter() - t1
-    st1 = (enc1 if enc1 is not None else enc).stats(reset=True)
-    # self-check of the measured path: GOP 0 as the lockstep batch coded it == the same 30 pictures through the
-    # batch-1 encoder (a different launch geometry of the same kernels); both are bit-exact against the CPU oracle
-    # in tests/test_gpu_parity.py at sizes the oracle finishes quickly
-    selfcheck = None
-    if enc1 is not None:
-        calls0 = args.warmup + args.steps + (1 if I > 1 else 0)      # encode_gops_device calls instance 0 has made
-        enc1.set_idr_pic_id(((calls0 - 1) * B) & 255, 1)             # idr_pic_id its GOP 0 carried in the last one
-        n1 = one_gop(0)
-        a = outs[0][:int(gop_bytes[0][0])]
-        selfcheck = bool(int(gop_bytes[0][0]) == n1 and np.array_equal(a, out1[:n1]))
+    if args.full:
+        if enc1 is not None:
+            enc1.stats(reset=True)
+        # the same kernels with the chip to themselves: instance 0 alone, one step (only when instances overlap)
+        if I > 1:
+            run_inst(0)
+            torch.cuda.synchronize()
+            st_ex = enc.stats(reset=True)
+        # latency mode for reference: one GOP in flight, kernels alone on the GPU (also gives the
+        # MC+DCT kernel's duration without other streams' kernels sharing the chip)
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(lat_steps):
+            one_gop(0)
+        fence()
+        lat_dt = time.perf_counter() - t1
+        st1 = (enc1 if enc1 is not None else enc).stats(reset=True)
+        # self-check of the measured path: GOP 0 as the lockstep batch coded it == the same 30 pictures through the
+        # batch-1 encoder (a different launch geometry of the same kernels); both are bit-exact against the CPU oracle
+        # in tests/test_gpu_parity.py at sizes the oracle finishes quickly
+        if enc1 is not None:
+            calls0 = args.warmup + args.steps + (1 if I > 1 else 0)      # encode_gops_device calls instance 0 has made
+            enc1.set_idr_pic_id(((calls0 - 1) * B) & 255, 1)             # idr_pic_id its GOP 0 carried in the last one
+            n1 = one_gop(0)
+            a = outs[0][:int(gop_bytes[0][0])]
+            selfcheck = bool(int(gop_bytes[0][0]) == n1 and np.array_equal(a, out1[:n1]))
     for e_ in encs:
         e_.close()
 
@@ -671,8 +713,9 @@ def main():
                                 "(HIP events on the launching stream); pricing every macroblock at 1952 B would read %.4f" %
                                 (PMB_BYTES_PER_MB * nmb * B / (pmb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if pmb_ms > 0 else 0.0)},
             "kernels": per_kernel,
-            "single_gop_in_flight_fps": round(lat_steps * FRAMES_PER_STEP / lat_dt, 2),
         }
+        if lat_dt is not None:
+            res["single_gop_in_flight_fps"] = round(lat_steps * FRAMES_PER_STEP / lat_dt, 2)
         me = k["me"]
         if me["launches"]:
             me_ms = me["ms"] / me["launches"]
@@ -696,24 +739,24 @@ def main():
                                          "unit": "GB/s", "frac": round(a_e / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ms_e, 5), "coded_fraction": round(cf_e, 4)}
             res["kernels_exclusive"] = {name: {"ms_per_launch": round(v["ms"] / v["launches"], 4)}
                                         for name, v in st_ex["kernels"].items() if v["launches"]}
-        p1 = st1["kernels"]["tq"]
-        if p1["launches"]:
+        p1 = st1["kernels"]["tq"] if st1 is not None else None
+        if p1 is not None and p1["launches"]:
             ms1 = p1["ms"] / p1["launches"]
             cf1 = st1["tq_coded_mbs"] / max(1, st1["p_mbs"])
             a1 = tq_bytes(nmb, cf1) / (ms1 * 1e-3) / 1e9
             res["roofline_isolated"] = {"kernel": "k_tq, one GOP in flight (no other kernels on the chip)",
                                         "achieved": round(a1, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                         "frac": round(a1 / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ms1, 5), "coded_fraction": round(cf1, 4)}
-        ib = valu_issue_bound(nmb)
+        ib = valu_issue_bound(nmb) if args.full else None
         if ib is not None and args.content == "s1" and args.slices < 2:
             ib["achieved_frac"] = round(fps / world / ib["bound_fps"], 3)
             res["valu_issue"] = ib
-        if world == 1 and not args.no_plugin and args.content == "s1" and args.slices < 2 and args.input == "i420":
+        if args.full and world == 1 and not args.no_plugin and args.content == "s1" and args.slices < 2 and args.input == "i420":
             try:
                 res["plugin"] = plugin_bench(plugin_streams, args.plugin_frames, args.bitrate, local_rank)
             except SystemExit as exc:   # never let the side measurement take the headline line down
                 res["plugin"] = {"error": str(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # N independent encoder instances on N host threads.  The sweep shows where the box's CPU
             # share saturates (a cgroup quota makes more threads than that share SLOWER); the best row is the baseline.
             lim = cpu_limits()

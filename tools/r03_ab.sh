@@ -6,8 +6,8 @@ mkdir -p $O
 cd $R
 tag=$1; shift
 for rep in 1 2 3; do
-  timeout -k 10 300 python bench.py --no-plugin --no-cpu-baseline --steps 6 "$@" > $O/ab_${tag}_A$rep.json 2> /dev/null
-  MI355X_H264_LIB=$R/media_amd/lib/libmi355x_h264_ab.so timeout -k 10 300 python bench.py --no-plugin --no-cpu-baseline --steps 6 "$@" > $O/ab_${tag}_B$rep.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --no-plugin --no-cpu-baseline --steps 6 "$@" > $O/ab_${tag}_A$rep.json 2> /dev/null
+  MI355X_H264_LIB=$R/media_amd/lib/libmi355x_h264_ab.so timeout -k 10 300 python bench.py --full --no-plugin --no-cpu-baseline --steps 6 "$@" > $O/ab_${tag}_B$rep.json 2> /dev/null
 done
 python - <<PY
 import json

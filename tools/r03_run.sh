@@ -7,9 +7,9 @@ cd $R
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/gpu_tests_$1.log 2>&1; echo "tests rc=$?"; tail -3 $O/gpu_tests_$1.log
 timeout -k 10 600 python bench.py --mode plugin --streams 1,4,16,64 > $O/plugin_hub_$1.json 2> $O/plugin_hub_$1.err; echo "plugin hub rc=$?"
 MI355X_H264_HUB=0 timeout -k 10 600 python bench.py --mode plugin --streams 1,4,16,64 > $O/plugin_nohub_$1.json 2> $O/plugin_nohub_$1.err; echo "plugin nohub rc=$?"
-timeout -k 10 600 python bench.py --no-plugin --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; echo "bench rc=$?"
-timeout -k 10 600 python bench.py --no-plugin --no-cpu-baseline --search exhaustive > $O/bench_exh_$1.json 2> $O/bench_exh_$1.err; echo "bench exhaustive rc=$?"
-for c in scroll s2 s3; do timeout -k 10 300 python bench.py --no-plugin --no-cpu-baseline --steps 4 --content $c > $O/bench_${c}_$1.json 2> /dev/null; timeout -k 10 300 python bench.py --no-plugin --no-cpu-baseline --steps 4 --content $c --search exhaustive > $O/bench_${c}_exh_$1.json 2> /dev/null; done
+timeout -k 10 600 python bench.py --full --no-plugin --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --no-plugin --no-cpu-baseline --search exhaustive > $O/bench_exh_$1.json 2> $O/bench_exh_$1.err; echo "bench exhaustive rc=$?"
+for c in scroll s2 s3; do timeout -k 10 300 python bench.py --full --no-plugin --no-cpu-baseline --steps 4 --content $c > $O/bench_${c}_$1.json 2> /dev/null; timeout -k 10 300 python bench.py --full --no-plugin --no-cpu-baseline --steps 4 --content $c --search exhaustive > $O/bench_${c}_exh_$1.json 2> /dev/null; done
 python - <<PY
 import json
 for n in ("plugin_hub_$1", "plugin_nohub_$1"):

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r03
 mkdir -p $O
 cd $R
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/gpu_tests_$1.log 2>&1; echo "tests rc=$?"; tail -3 $O/gpu_tests_$1.log
-timeout -k 10 600 python bench.py --no-plugin --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --no-plugin --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; echo "bench rc=$?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_$1.json"))

@@ -37,7 +37,7 @@ def pmc(path, name):
 
 fetch, write = pmc(src + "/pmc_fetch/*/*counter_collection.csv", "FETCH_SIZE"), pmc(src + "/pmc_write/*/*counter_collection.csv", "WRITE_SIZE")
 out = {"what": "BASELINE.json configs[2]: 1080p60 NV12, main profile, CAVLC (CABAC off), one instance x 32 GOPs in lockstep; rocprofv3 --kernel-trace --stats and "
-               "separate --pmc FETCH_SIZE / WRITE_SIZE passes of `python3 bench.py --input nv12 --profile main --fps 60 --instances 1 --gops-in-flight 32 "
+               "separate --pmc FETCH_SIZE / WRITE_SIZE passes of `python3 bench.py --full --input nv12 --profile main --fps 60 --instances 1 --gops-in-flight 32 "
                "--no-cpu-baseline --no-plugin` (tools/prof_cfg2.sh %s, tools/summarize_cfg2.py)" % tag,
        "fps_under_profiler": fps, "fps_unprofiled_two_instances": float(sys.argv[2]) if len(sys.argv) > 2 else None, "kernels": {}}
 for k in sorted(dur):

@@ -26,7 +26,7 @@ def pmc(path, name):
         if r["Counter_Name"] == name:
             d[(r["Kernel_Name"].split("(")[0].replace("void ", "").replace("h264::", ""), int(r["Grid_Size"]))].append(float(r["Counter_Value"]))
     return d
-out = {"tag": tag, "command": "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline (stats); --steps 1 (each --pmc pass)",
+out = {"tag": tag, "command": "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline (stats); --steps 1 (each --pmc pass)",
        "kernel_avg_by_batch": split, "pmc": {}}
 fetch = pmc(src + "/pmc_fetch/*/*counter_collection.csv", "FETCH_SIZE")
 write = pmc(src + "/pmc_write/*/*counter_collection.csv", "WRITE_SIZE")
@@ -67,7 +67,7 @@ if tq:
            "fetch_ratio_calibrated": "1.0 for 64-byte segments, 0.5 for the luma passes' 128-byte segments", "write_ratio_calibrated": 1.0,
            "calibration": "profiles/r03b_ubench_fetch.json (rd4_tq 1.0, rd4_tq8 0.5, wr4_tq / wr4_tq8 / wr32_lv 1.0)",
            "traffic_bytes_per_launch": int(v["FETCH_SIZE_KB_raw"] * 1024 + v["WRITE_SIZE_KB"] * 1024) + half_counted,
-           "note": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-plugin` "
+           "note": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-plugin` "
                    "(profiles/%s_summary.json).  traffic = WRITE_SIZE + FETCH_SIZE + the half of the luma reads the counter leaves out (measured "
                    "ratio 0.5 for that access shape).  bench.py compares this with coded x 1952 + settled x 2 bytes of the same launch" % tag}
     json.dump(tr_, open("profiles/%s_traffic.json" % tag, "w"), indent=1)
