@@ -61,7 +61,8 @@ enum {
 enum { MI355X_H264_FRAME_IDR = 1, MI355X_H264_FRAME_P = 3 }; /* EVideoFrameType values, codec_def.h:70,72 */
 
 enum { MI355X_H264_RC_FIXED_QP = 0, MI355X_H264_RC_BITRATE = 1 };
-enum { MI355X_H264_INPUT_I420 = 0, MI355X_H264_INPUT_NV12 = 1 };
+enum { MI355X_H264_INPUT_I420 = 0, MI355X_H264_INPUT_NV12 = 1,
+       MI355X_H264_INPUT_RGBA = 2 /* mi355x_h264_stream_open only; mi355x_h264_create refuses it */ };
 enum { MI355X_H264_SEARCH_EXHAUSTIVE = 0, MI355X_H264_SEARCH_SEEDED = 1 };
 
 typedef struct mi355x_h264_config {
@@ -78,7 +79,8 @@ typedef struct mi355x_h264_config {
     int32_t batch;           /* closed GOPs (or independent streams) encoded in lockstep by one instance,
                               * 1..64; > 1 is driven through mi355x_h264_encode_gops_device only      */
     int32_t input_format;    /* layout of pictures handed over in DEVICE memory (encode_device, encode_batch_device,
-                              * encode_gops_device): MI355X_H264_INPUT_I420 (default) or MI355X_H264_INPUT_NV12     */
+                              * encode_gops_device): MI355X_H264_INPUT_I420 (default) or MI355X_H264_INPUT_NV12; streams: the
+                              * layout of every picture of the stream, MI355X_H264_INPUT_RGBA included (see "streams")   */
     int32_t slices;          /* 0 / 1: one slice per picture (the reference preset, SM_SINGLE_SLICE, ref :247).  n > 1:
                               * n bands of ceil(rows / n) macroblock rows (at least two rows each), one slice NAL
                               * unit per band, disable_deblocking_filter_idc = 2: the bands of a picture
@@ -214,7 +216,7 @@ int64_t mi355x_h264_debug_read(mi355x_h264_encoder *enc, int what, void *dst, si
  * device) deliver at about the same time: ONE lockstep launch sequence per step instead of one per stream, every picture with
  * its own QP, picture type, frame_num and reference pictures.  mi355x_h264_stream_encode is synchronous and may be called from
  * one thread per stream concurrently; the output is bit-for-bit what mi355x_h264_create / mi355x_h264_encode with the same
- * config and the same QP sequence produce (tests/test_gpu_streams.py).  One reference picture (refs <= 1), host I420 input.
+ * config and the same QP sequence produce (tests/test_gpu_streams.py).  One reference picture (refs <= 1).
  * *out stays valid until the stream's next encode / close.  MI355X_H264_HUB_ITEMS (default 32) streams share an engine;
  * MI355X_H264_HUB_WINDOW_US (default 200): how long a step waits for pictures that are already being uploaded. */
 typedef struct mi355x_h264_stream mi355x_h264_stream;
@@ -222,6 +224,28 @@ int mi355x_h264_stream_open(const mi355x_h264_config *cfg, mi355x_h264_stream **
 void mi355x_h264_stream_close(mi355x_h264_stream *s);
 int mi355x_h264_stream_encode(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *u, int u_stride,
                               const uint8_t *v, int v_stride, uint8_t **out, uint32_t *out_len, int *frame_type);
+/* Layouts and device-resident pictures (tests/test_gpu_stream_inputs.py).  config.input_format names the layout of EVERY picture of
+ * the stream - MI355X_H264_INPUT_I420, _NV12 or _RGBA - and streams share an engine only with streams of the same layout.
+ * mi355x_h264_stream_encode takes host I420 planes, _encode_nv12 host NV12 (arguments as mi355x_h264_encode_nv12), _encode_rgba
+ * host RGBA (as mi355x_h264_encode_rgba; the conversion is the one stated there, one launch for all RGBA pictures of a step).
+ * mi355x_h264_stream_encode_device takes ONE tight picture in the stream's layout (I420: Y, U, V; NV12: Y, UV; RGBA: 4 * width
+ * bytes per row) in device memory of the stream's device.  Host and device calls may alternate freely on one stream; the output is
+ * the same bytes either way.  A call whose form is not the stream's layout (host I420 planes to an NV12 stream, ...) returns
+ * MI355X_H264_E_ARG, sets the stream's error text and leaves the stream as it was.
+ * Contract of the device form:
+ *   - the picture is only read, and only during the call.  I420 and NV12 pictures are read where they lie by the encoder kernels
+ *     themselves (no copy is made); an RGBA picture is read once, by the conversion kernel;
+ *   - the call does not synchronise with the caller's own HIP streams: whatever writes the picture must have completed;
+ *   - alignment: an RGBA picture must start on a multiple of 8 bytes (the conversion loads 8 bytes per lane; less is refused with
+ *     MI355X_H264_E_ARG).  I420 and NV12 pictures may start on any byte - every source load of the kernels tests its own address
+ *     and takes single bytes when it is not a multiple of 4 (NV12 chroma: 8) - but only pictures that start on a multiple of 8
+ *     bytes and whose width is a multiple of 4 are read at full speed.  These are the requirements of mi355x_h264_encode_device
+ *     and mi355x_h264_encode_rgba_device as well. */
+int mi355x_h264_stream_encode_device(mi355x_h264_stream *s, const void *d_pic, uint8_t **out, uint32_t *out_len, int *frame_type);
+int mi355x_h264_stream_encode_nv12(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride,
+                                   uint8_t **out, uint32_t *out_len, int *frame_type);
+int mi355x_h264_stream_encode_rgba(mi355x_h264_stream *s, const uint8_t *rgba, int stride, uint8_t **out, uint32_t *out_len,
+                                   int *frame_type);
 int mi355x_h264_stream_set_qp(mi355x_h264_stream *s, int qp);            /* as mi355x_h264_set_qp            */
 int mi355x_h264_stream_force_idr(mi355x_h264_stream *s);                 /* as mi355x_h264_force_idr         */
 int mi355x_h264_stream_set_idr_pic_id(mi355x_h264_stream *s, int next);  /* idr_pic_id of the next IDR       */

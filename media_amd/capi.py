@@ -30,7 +30,9 @@ EXPORTS = [
     "mi355x_h264_stream_open", "mi355x_h264_stream_close", "mi355x_h264_stream_encode", "mi355x_h264_stream_set_qp",
     "mi355x_h264_stream_force_idr", "mi355x_h264_stream_set_idr_pic_id", "mi355x_h264_stream_last_me_cost",
     "mi355x_h264_stream_last_error", "mi355x_h264_stream_debug_read", "mi355x_h264_stream_hub_stats",
+    "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
 ]
+INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
 
 
 class Config(C.Structure):
@@ -88,6 +90,9 @@ def lib():
         L.mi355x_h264_stream_close.argtypes = [vp]
         L.mi355x_h264_stream_close.restype = None
         L.mi355x_h264_stream_encode.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.mi355x_h264_stream_encode_device.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.mi355x_h264_stream_encode_nv12.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.mi355x_h264_stream_encode_rgba.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_set_qp.argtypes = [vp, C.c_int]
         L.mi355x_h264_stream_force_idr.argtypes = [vp]
         L.mi355x_h264_stream_set_idr_pic_id.argtypes = [vp, C.c_int]
@@ -263,14 +268,17 @@ class Encoder:
 
 class Stream:
     """a stream of the shared engine (include/mi355x_h264.h, "streams"): one picture per call, coded together with the pictures
-    other streams of the same geometry deliver at about the same time; thread-safe across streams (one thread per stream)"""
+    other streams of the same geometry deliver at about the same time; thread-safe across streams (one thread per stream).
+    input_format (INPUT_I420 / INPUT_NV12 / INPUT_RGBA) is the layout of every picture of the stream, from host or device memory"""
 
-    def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1):
+    def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
+                 input_format=0):
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
         cfg.width, cfg.height, cfg.qp, cfg.gop, cfg.fps = width, height, qp, gop, fps
         cfg.profile_idc, cfg.device, cfg.disable_deblock, cfg.slices, cfg.search = profile_idc, device, disable_deblock, slices, search
+        cfg.input_format = input_format
         self.h = C.c_void_p()
         rc = L.mi355x_h264_stream_open(C.byref(cfg), C.byref(self.h))
         if rc != 0:
@@ -290,6 +298,28 @@ class Stream:
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
         self._check(lib().mi355x_h264_stream_encode(self.h, base, w, base + w * h, w // 2, base + w * h * 5 // 4, w // 2,
                                                     C.byref(out), C.byref(n), C.byref(ft)))
+        return C.string_at(out.value, n.value), ft.value
+
+    def encode_device(self, dev_ptr):
+        """one tight picture in the stream's layout, in device memory of the stream's device; read in place"""
+        out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
+        self._check(lib().mi355x_h264_stream_encode_device(self.h, C.c_void_p(dev_ptr), C.byref(out), C.byref(n), C.byref(ft)))
+        return C.string_at(out.value, n.value), ft.value
+
+    def encode_nv12(self, nv12):
+        """host NV12 (Y plane then interleaved UV)"""
+        w, h = self.width, self.height
+        f = np.ascontiguousarray(nv12, dtype=np.uint8)
+        out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
+        self._check(lib().mi355x_h264_stream_encode_nv12(self.h, f.ctypes.data, w, f.ctypes.data + w * h, w,
+                                                         C.byref(out), C.byref(n), C.byref(ft)))
+        return C.string_at(out.value, n.value), ft.value
+
+    def encode_rgba(self, rgba, stride=None):
+        """host RGBA (height x width x 4 bytes, or rows `stride` bytes apart)"""
+        f = np.ascontiguousarray(rgba, dtype=np.uint8)
+        out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
+        self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.width), C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
     def set_qp(self, qp):

@@ -119,8 +119,11 @@ struct FrameParams {
     // one lockstep step).  gridDim.y counts POSITIONS; itemtab[position] names the batch item, the ring slot its picture is
     // reconstructed into and its QP.  rec[] then holds the BASE of the reconstruction planes, which lie [item][ring slot]
     // (st_y / st_c bytes between items, st_ring_y / st_ring_c between the nbuf slots of one item); qtab is the table of
-    // quantiser constants by QP.  Direct launches leave itemtab null and never read these.
+    // quantiser constants by QP.  srctab[position] is the address of the position's source picture - a slot of the hub's
+    // staging array, or the caller's own device picture, read where it lies (src / st_src are not used).  Direct launches leave
+    // itemtab and srctab null and never read these.
     const uint32_t* itemtab;
+    const unsigned long long* srctab;
     const QpEntry* qtab;
     size_t st_ring_y, st_ring_c;
     int nbuf;
@@ -132,6 +135,14 @@ __device__ __forceinline__ ItemRef item_ref(const uint32_t* itemtab, int pos)
 {
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)itemtab[pos]);   // uniform: a scalar load
     return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 16) & 63u)};
+}
+// srctab entry of a position: wave-uniform like the itemtab word, a scalar load of its own (it depends on the position alone, so
+// it is issued beside the itemtab word, not behind it)
+__device__ __forceinline__ const uint8_t* item_src(const unsigned long long* srctab, int pos)
+{
+    const unsigned long long a = srctab[pos];
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+    return (const uint8_t*)(((unsigned long long)hi << 32) | lo);
 }
 // the parameter block of batch item g (pointers advanced by g strides)
 __device__ __forceinline__ FrameParams batch_view(FrameParams P, int g)
@@ -157,6 +168,7 @@ __device__ __forceinline__ FrameParams batch_view(FrameParams P, int pos)
 {
     if constexpr (!IND) return batch_view(P, pos);
     else {
+        const uint8_t* const src = item_src(P.srctab, pos);
         const ItemRef it = item_ref(P.itemtab, pos);
         uint8_t* const by = P.rec[0] + (size_t)it.item * P.st_y;
         uint8_t* const bu = P.rec[1] + (size_t)it.item * P.st_c;
@@ -170,7 +182,7 @@ __device__ __forceinline__ FrameParams batch_view(FrameParams P, int pos)
         }
         P.ref[0] = P.refs[0][0]; P.ref[1] = P.refs[0][1]; P.ref[2] = P.refs[0][2];
         const int g = it.item;
-        P.src += (size_t)g * P.st_src;
+        P.src = src;
         P.mb += (size_t)g * P.st_mb;
         P.levels += (size_t)g * P.st_mb * LV_STRIDE;
         P.mvd += (size_t)g * P.st_mb * 8;

@@ -239,6 +239,7 @@ struct CavlcParams {
     size_t st_src;
     const uint8_t* aux;   // 16 bytes per macroblock: Intra4x4PredMode of the blocks of MB_I4 macroblocks (blkIdx order)
     const uint32_t* itemtab;   // indirect launches (IND = true): position -> batch item (dev_common.h item_ref); null otherwise
+    const unsigned long long* srctab;   // indirect launches: position -> address of its source picture (dev_common.h item_src)
 };
 __device__ __forceinline__ CavlcParams batch_view(CavlcParams C, int g)
 {
@@ -251,7 +252,16 @@ __device__ __forceinline__ CavlcParams batch_view(CavlcParams C, int g)
     return C;
 }
 template <bool IND>
-__device__ __forceinline__ CavlcParams batch_view(CavlcParams C, int pos) { return batch_view(C, batch_item<IND>(C.itemtab, pos)); }
+__device__ __forceinline__ CavlcParams batch_view(CavlcParams C, int pos)
+{
+    if constexpr (!IND) return batch_view(C, pos);
+    else {
+        const uint8_t* const src = item_src(C.srctab, pos);   // by position: the picture may lie in the caller's own memory
+        C = batch_view(C, item_ref(C.itemtab, pos).item);
+        C.src = src;
+        return C;
+    }
+}
 enum { MAX_BATCH = 64 };
 // One limit for both halves of the overflow guard: a slice is accepted by k_bit_scan only when header + data +
 // tail end at least SLICE_GUARD_BITS before the end of its share of the payload buffer, and k_cavlc<true> drops a slot

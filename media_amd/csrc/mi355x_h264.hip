@@ -383,13 +383,16 @@ struct StatScope {
 // Direct (items == nullptr): the n = e->G batch items of the encoder, one QP, one ring position, consecutive idr_pic_ids - the
 // closed-GOP batch of mi355x_h264_encode_gops_device and the single-picture calls.  Indirect (the stream hub below): position k
 // of the grid is picture items[k] - its own batch item, ring slot, QP, frame_num and idr_pic_id; the kernels are the IND = true
-// instantiations and read d_itemtab.  A step holds pictures of ONE type (IDR or P): the two run different kernels.
+// instantiations and read d_itemtab, and the source picture of position k lies at d_srctab[k] (d_src is not used) - wherever that is: a
+// slot of the hub's staging array or the caller's own device memory.  A step holds pictures of ONE type (IDR or P): the two run
+// different kernels.
 struct ItemPic { int item, cur, qp, frame_num, idr_id; };
 struct Step {
     const uint8_t* d_src = nullptr; size_t src_item_stride = 0; bool nv12 = false; bool idr = false;
     int n = 1;
     const ItemPic* items = nullptr;
     const uint32_t* d_itemtab = nullptr;
+    const unsigned long long* d_srctab = nullptr;
     hipStream_t st = nullptr, ec = nullptr;
     hipEvent_t recon_ready = nullptr, entropy_done = nullptr, done = nullptr;
     unsigned* h_err = nullptr;
@@ -419,7 +422,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         for (int r = 0; r < mi355x_h264_encoder::MAX_REFS; r++) P.refs[r][p] = e->d_planes[(cur + e->nbuf - 1 - std::min(r, e->nrefs - 1)) % e->nbuf][p];
         P.ref[p] = P.refs[0][p];
     }
-    P.itemtab = T.d_itemtab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
+    P.itemtab = T.d_itemtab; P.srctab = T.d_srctab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
     P.mb = e->d_mb; P.levels = e->d_levels; P.mvd = e->d_mvd; P.mvq = e->d_mvq; P.aux = e->d_aux; P.me_cost = e->d_me_cost; P.me_total = e->d_me_total; P.pmv = e->d_pmv;
     P.st_src = T.src_item_stride; P.st_y = e->st_y; P.st_c = e->st_c; P.st_mb = e->nmb; P.sl = e->sl;
     P.band.row0 = e->b_row0; P.band.rows = e->b_rows;
@@ -508,7 +511,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
     C.st_mb = e->nmb; C.st_bitbuf = e->st_bitbuf_bytes / 4;
     C.aux = e->d_aux; C.mvq = e->d_mvq;
     C.src = T.d_src; C.w = e->cfg.width; C.h = e->cfg.height; C.src_nv12 = T.nv12 ? 1 : 0; C.st_src = T.src_item_stride;
-    C.itemtab = T.d_itemtab;
+    C.itemtab = T.d_itemtab; C.srctab = T.d_srctab;
     const int cavlc_grid = (e->b_nmb + 1) / 2;
     unsigned db_serial = 0;
     if (!e->cfg.disable_deblock) {   // (the diagonal debug form of the filter reads the strengths too)
@@ -1021,10 +1024,8 @@ int mi355x_h264_encode_nv12(mi355x_h264_encoder* e, const uint8_t* y, int ys, co
 
 // RGBA ingest: one conversion pass into the I420 staging picture (include/mi355x_h264.h states the arithmetic;
 // oracle/h264_rgba.c is its CPU restatement).  Thread = one 2x2 block: two 8-byte loads, two 2-byte luma stores, one Cb, one Cr.
-__global__ __launch_bounds__(256) void k_rgba_to_i420(const uint8_t* __restrict__ rgba, size_t stride, uint8_t* __restrict__ i420, int w, int h)
+__device__ __forceinline__ void rgba_block_to_i420(const uint8_t* __restrict__ rgba, size_t stride, uint8_t* __restrict__ i420, int w, int h, int bx, int by)
 {
-    const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y;
-    if (bx >= w / 2) return;
     uint8_t* const Y = i420;
     uint8_t* const U = i420 + (size_t)w * h;
     uint8_t* const V = U + (size_t)(w / 2) * (h / 2);
@@ -1041,6 +1042,24 @@ __global__ __launch_bounds__(256) void k_rgba_to_i420(const uint8_t* __restrict_
     const int r = (sr + 2) >> 2, g = (sg + 2) >> 2, b = (sb + 2) >> 2;
     U[(size_t)by * (w / 2) + bx] = (uint8_t)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
     V[(size_t)by * (w / 2) + bx] = (uint8_t)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
+}
+__global__ __launch_bounds__(256) void k_rgba_to_i420(const uint8_t* __restrict__ rgba, size_t stride, uint8_t* __restrict__ i420, int w, int h)
+{
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y;
+    if (bx >= w / 2) return;
+    rgba_block_to_i420(rgba, stride, i420, w, h, bx, by);
+}
+// The stream hub's form: ONE launch converts every picture of a step.  blockIdx.z = position; tab[position] = where the RGBA picture
+// lies (the caller's device memory or the hub's RGBA staging) and its row stride, srctab[position] = the I420 staging slot the
+// encoder kernels of the step then read.  Eight bytes per lane and row, as above: rows start on 8 bytes for every even width, so
+// widths that are not multiples of 4 take the same path.
+struct RgbaSrc { unsigned long long addr, stride; };
+__global__ __launch_bounds__(256) void k_rgba_to_i420_step(const RgbaSrc* __restrict__ tab, const unsigned long long* __restrict__ srctab, int w, int h)
+{
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y;
+    if (bx >= w / 2) return;
+    const RgbaSrc t = tab[blockIdx.z];
+    rgba_block_to_i420((const uint8_t*)t.addr, (size_t)t.stride, (uint8_t*)srctab[blockIdx.z], w, h, bx, by);
 }
 
 static int encode_rgba_from_device(mi355x_h264_encoder* e, const uint8_t* d_rgba, size_t stride, uint8_t** out, uint32_t* out_len, int* frame_type)
@@ -1320,7 +1339,13 @@ struct HubItem {
     long frames = 0;
     int last_cur = 0;                // ring slot of the last finished picture
     hipEvent_t copied = nullptr;     // the picture's upload has finished
-    // the request in flight
+    // the request in flight: where its picture lies.  staged: it was uploaded to the item's staging slot (`copied` says when it has
+    // arrived); else d_in is the caller's own device picture, read in place.  RGBA pictures (rgba_src, rgba_stride: the caller's
+    // device picture or the item's RGBA staging slot) are converted into the I420 staging slot by the step's leader.
+    bool staged = true;
+    const uint8_t* d_in = nullptr;
+    const uint8_t* rgba_src = nullptr;
+    size_t rgba_stride = 0;
     bool pending = false, done = false;
     int rc = 0, frame_type = 0;
     uint8_t* out = nullptr;
@@ -1332,8 +1357,11 @@ struct HubCtx {
     hipStream_t st = nullptr, ec = nullptr;
     hipEvent_t recon_ready = nullptr, entropy_done = nullptr, done = nullptr;
     unsigned* h_err = nullptr;       // pinned: hand-off time-out flag of the wavefront kernels
-    uint32_t* h_itemtab = nullptr;   // pinned, MAX_BATCH words
-    uint32_t* d_itemtab = nullptr;
+    // the step's tables, one pinned block and one transfer: [source address per position][itemtab word per position][RGBA hubs:
+    // {address, row stride} of the RGBA picture per position]
+    enum { TAB_SRC = 0, TAB_ITEM = MAX_BATCH * 8, TAB_RGBA = TAB_ITEM + MAX_BATCH * 4, TAB_BYTES = TAB_RGBA + MAX_BATCH * 16 };
+    uint8_t* h_tab = nullptr;        // pinned
+    uint8_t* d_tab = nullptr;
     bool busy = false;
 };
 
@@ -1354,9 +1382,13 @@ struct Hub {
     bool collecting = false;         // a leader is gathering a P step
     HubCtx ctx[MAX_CTX];
     bool any_busy() const { for (int i = 0; i <= nctx_p; i++) if (ctx[i].busy) return true; return false; }
-    uint8_t* d_stage = nullptr;      // [cap] pictures as the callers hand them over (tight I420)
-    uint8_t* h_stage = nullptr;      // pinned
+    int fmt = MI355X_H264_INPUT_I420;   // layout of every picture of this hub's streams (config.input_format)
+    uint8_t* d_stage = nullptr;      // [cap] pictures the kernels read when the caller's are not read in place: host pictures as handed
+    uint8_t* h_stage = nullptr;      // over (tight I420 / NV12; pinned h_stage on their way), RGBA pictures after the conversion (I420)
     size_t st_stage = 0;
+    uint8_t* d_rgba = nullptr;       // [cap] host RGBA pictures on their way to the conversion kernel: allocated with the hub's
+    uint8_t* h_rgba = nullptr;       // first one (pinned)
+    size_t st_rgba = 0;
     // uploads: item k on copy stream k % NCOPY.  Two streams fill most of the link (tools/ubench_h2d.hip: 1 stream 32 GB/s, 2: 46-51,
     // 4+: 52-57); HIP streams are a scarce resource on this runtime - beyond about a dozen live streams in the process every launch
     // gets slower (measured: 8 copy streams per hub halved the throughput at 64 streams)
@@ -1377,7 +1409,7 @@ std::atomic<int> g_streams_open{0};   // over all hubs of the process
 bool same_geometry(const mi355x_h264_config& a, const mi355x_h264_config& b)
 {
     return a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
-           a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search;
+           a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
 }
 
 void hub_free(Hub* h)
@@ -1393,13 +1425,15 @@ void hub_free(Hub* h)
         if (c.entropy_done) (void)hipEventDestroy(c.entropy_done);
         if (c.done) (void)hipEventDestroy(c.done);
         if (c.h_err) (void)hipHostFree(c.h_err);
-        if (c.h_itemtab) (void)hipHostFree(c.h_itemtab);
-        (void)hipFree(c.d_itemtab);
+        if (c.h_tab) (void)hipHostFree(c.h_tab);
+        (void)hipFree(c.d_tab);
     }
     for (auto& cs : h->copy_st) if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); }
     for (auto& it : h->items) if (it.copied) (void)hipEventDestroy(it.copied);
     (void)hipFree(h->d_stage);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
+    (void)hipFree(h->d_rgba);
+    if (h->h_rgba) (void)hipHostFree(h->h_rgba);
     if (h->verbose && h->pictures)
         fprintf(stderr, "mi355x_h264 hub %dx%d: %llu pictures in %llu steps (%.2f per step, largest %llu); per picture: upload %.0f us, queued %.0f us, "
                         "whole call %.0f us; per step: launch %.0f us, GPU wait %.0f us, finish %.0f us\n", h->cfg.width, h->cfg.height,
@@ -1415,6 +1449,7 @@ int hub_create(const mi355x_h264_config& cfg, Hub** out)
     Hub* h = new (std::nothrow) Hub();
     if (!h) return MI355X_H264_E_NOMEM;
     h->cfg = cfg;
+    h->fmt = cfg.input_format;
     const char* ci = getenv("MI355X_H264_HUB_ITEMS");
     h->cap = std::min((int)MAX_BATCH, std::max(1, ci ? atoi(ci) : 32));
     const char* wu = getenv("MI355X_H264_HUB_WINDOW_US");
@@ -1430,6 +1465,7 @@ int hub_create(const mi355x_h264_config& cfg, Hub** out)
     if (rc != MI355X_H264_OK) { h->e = nullptr; hub_free(h); return rc; }
     const size_t fb = (size_t)cfg.width * cfg.height * 3 / 2;
     h->st_stage = (fb + 255) & ~(size_t)255;
+    h->st_rgba = ((size_t)cfg.width * cfg.height * 4 + 255) & ~(size_t)255;
 #define HK(call) do { if ((call) != hipSuccess) { hub_free(h); return MI355X_H264_E_HIP; } } while (0)
     HK(hipSetDevice(cfg.device));
     HK(hipMalloc((void**)&h->d_stage, h->st_stage * h->cap));
@@ -1446,8 +1482,8 @@ int hub_create(const mi355x_h264_config& cfg, Hub** out)
         HK(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
         HK(hipHostMalloc((void**)&c.h_err, sizeof(unsigned), hipHostMallocDefault));
         *c.h_err = 0;
-        HK(hipHostMalloc((void**)&c.h_itemtab, MAX_BATCH * sizeof(uint32_t), hipHostMallocDefault));
-        HK(hipMalloc((void**)&c.d_itemtab, MAX_BATCH * sizeof(uint32_t)));
+        HK(hipHostMalloc((void**)&c.h_tab, HubCtx::TAB_BYTES, hipHostMallocDefault));
+        HK(hipMalloc((void**)&c.d_tab, HubCtx::TAB_BYTES));
     }
     for (int i = 0; i < h->cap; i++) HK(hipEventCreateWithFlags(&h->items[i].copied, hipEventDisableTiming));
 #undef HK
@@ -1477,14 +1513,29 @@ void hub_run_step(Hub* h, HubCtx& c, const std::vector<int>& batch, bool idr)
     const uint64_t t0 = now_us();
     {
         std::lock_guard<std::mutex> lk(h->launch_mu);
+        const bool rgba = h->fmt == MI355X_H264_INPUT_RGBA;
+        unsigned long long* const h_src = (unsigned long long*)(c.h_tab + HubCtx::TAB_SRC);
+        uint32_t* const h_itemtab = (uint32_t*)(c.h_tab + HubCtx::TAB_ITEM);
+        RgbaSrc* const h_rgbatab = (RgbaSrc*)(c.h_tab + HubCtx::TAB_RGBA);
         for (int k = 0; k < n; k++) {
-            c.h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].qp << 16);
-            if (hipStreamWaitEvent(c.st, h->items[pics[k].item].copied, 0) != hipSuccess) rc = MI355X_H264_E_HIP;
+            const HubItem& it = h->items[pics[k].item];
+            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].qp << 16);
+            // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
+            h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
+            if (rgba) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)it.rgba_src, (unsigned long long)it.rgba_stride};
+            if (it.staged && hipStreamWaitEvent(c.st, it.copied, 0) != hipSuccess) rc = MI355X_H264_E_HIP;
         }
-        if (hipMemcpyAsync(c.d_itemtab, c.h_itemtab, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c.st) != hipSuccess) rc = MI355X_H264_E_HIP;
+        const size_t tab_bytes = rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
+        if (hipMemcpyAsync(c.d_tab, c.h_tab, tab_bytes, hipMemcpyHostToDevice, c.st) != hipSuccess) rc = MI355X_H264_E_HIP;
+        const unsigned long long* const d_srctab = (const unsigned long long*)(c.d_tab + HubCtx::TAB_SRC);
+        if (rc == MI355X_H264_OK && rgba) {   // one conversion launch for the step, in front of the first kernel that reads samples
+            const int w = h->cfg.width, hh = h->cfg.height;
+            hipLaunchKernelGGL(k_rgba_to_i420_step, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(hh / 2), (unsigned)n), dim3(256), 0, c.st,
+                               (const RgbaSrc*)(c.d_tab + HubCtx::TAB_RGBA), d_srctab, w, hh);
+        }
         if (rc == MI355X_H264_OK) {
-            T.d_src = h->d_stage; T.src_item_stride = h->st_stage; T.nv12 = false; T.idr = idr; T.n = n;
-            T.items = pics; T.d_itemtab = c.d_itemtab;
+            T.d_src = nullptr; T.src_item_stride = 0; T.nv12 = h->fmt == MI355X_H264_INPUT_NV12; T.idr = idr; T.n = n;
+            T.items = pics; T.d_itemtab = (const uint32_t*)(c.d_tab + HubCtx::TAB_ITEM); T.d_srctab = d_srctab;
             // entropy coding beside the loop filter shortens a picture's latency; with many streams open the second HIP stream
             // costs more than the overlap brings (64 streams: 10.9 k -> 12.1 k fps on one stream per step)
             T.st = c.st; T.ec = g_streams_open.load(std::memory_order_relaxed) > 40 ? c.st : c.ec; T.recon_ready = c.recon_ready; T.entropy_done = c.entropy_done; T.done = c.done; T.h_err = c.h_err;
@@ -1534,7 +1585,9 @@ int mi355x_h264_stream_open(const mi355x_h264_config* cfg, mi355x_h264_stream** 
 {
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
     *out = nullptr;
-    if (cfg->refs > 1 || cfg->band_count > 1 || cfg->batch > 1 || cfg->input_format != MI355X_H264_INPUT_I420) return MI355X_H264_E_ARG;
+    if (cfg->refs > 1 || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
+    if (cfg->input_format != MI355X_H264_INPUT_I420 && cfg->input_format != MI355X_H264_INPUT_NV12 && cfg->input_format != MI355X_H264_INPUT_RGBA)
+        return MI355X_H264_E_ARG;
     if (cfg->qp < 10 || cfg->qp > 51 || cfg->gop < 1) return MI355X_H264_E_ARG;
     mi355x_h264_stream* s = new (std::nothrow) mi355x_h264_stream();
     if (!s) return MI355X_H264_E_NOMEM;
@@ -1584,52 +1637,105 @@ void mi355x_h264_stream_close(mi355x_h264_stream* s)
     delete s;
 }
 
-int mi355x_h264_stream_encode(mi355x_h264_stream* s, const uint8_t* y, int ys, const uint8_t* u, int us, const uint8_t* v, int vs,
-                              uint8_t** out, uint32_t* out_len, int* frame_type)
+// What a stream call was handed: host planes in one of the three layouts, or one tight device picture in the stream's layout.
+enum { HUB_IN_I420 = 0, HUB_IN_NV12 = 1, HUB_IN_RGBA = 2, HUB_IN_DEVICE = 3 };
+struct HubInput { int form; const uint8_t* p[3]; int stride[3]; };
+
+// A host picture into the stream's staging slot: pinned copy, then the transfer on the item's copy stream; it.copied says when it
+// has arrived.  (The reference's tight I420 layout, InitSrcPic ref :354-365, goes as it is; other layouts row by row.)
+static bool hub_upload(Hub* h, HubItem& it, int item, const HubInput& in, int nopen)
 {
-    if (!s || !y || !u || !v || !out || !out_len) return MI355X_H264_E_ARG;
+    const int w = h->cfg.width, hh = h->cfg.height;
+    uint8_t* hs = h->h_stage + (size_t)item * h->st_stage;
+    uint8_t* ds = h->d_stage + (size_t)item * h->st_stage;
+    hipStream_t cs = h->copy_st[item % Hub::NCOPY];
+    const size_t ysz = (size_t)w * hh, fb = ysz * 3 / 2;
+    const uint8_t* const y = in.p[0];
+    bool ok = true;
+    if (in.form == HUB_IN_RGBA) {   // to the RGBA staging slot; the step's conversion launch writes the I420 slot
+        uint8_t* hr = h->h_rgba + (size_t)item * h->st_rgba;
+        uint8_t* dr = h->d_rgba + (size_t)item * h->st_rgba;
+        const size_t row = (size_t)w * 4, n = row * hh;
+        if ((size_t)in.stride[0] == row) memcpy(hr, y, n);
+        else for (int r = 0; r < hh; r++) memcpy(hr + (size_t)r * row, y + (size_t)r * in.stride[0], row);
+        ok = hipMemcpyAsync(dr, hr, n, hipMemcpyHostToDevice, cs) == hipSuccess;
+        it.rgba_src = dr; it.rgba_stride = row;
+    } else if (in.form == HUB_IN_NV12) {
+        const uint8_t* const uv = in.p[1];
+        const int ys = in.stride[0], uvs = in.stride[1];
+        if (ys == w && uvs == w && uv == y + ysz) memcpy(hs, y, fb);
+        else {
+            for (int r = 0; r < hh; r++) memcpy(hs + (size_t)r * w, y + (size_t)r * ys, (size_t)w);
+            for (int r = 0; r < hh / 2; r++) memcpy(hs + ysz + (size_t)r * w, uv + (size_t)r * uvs, (size_t)w);
+        }
+        ok = hipMemcpyAsync(ds, hs, fb, hipMemcpyHostToDevice, cs) == hipSuccess;
+    } else {
+        const uint8_t* const u = in.p[1], * const v = in.p[2];
+        const int ys = in.stride[0], us = in.stride[1], vs = in.stride[2];
+        if (ys == w && us == w / 2 && vs == w / 2 && u == y + ysz && v == u + ysz / 4) {
+            // few streams: four pieces, so that the copy of piece k + 1 runs while piece k is on the bus (latency); many streams: one
+            // transfer per picture (every queued command costs, and other streams' transfers fill the bus anyway: 16 / 32 / 64 streams
+            // went from 7.3 / 8.0 / 8.6 k to 8.8 / 11.5 / 10.9 k fps with this alone, profiles/r03_hub_sweep_*.log)
+            const size_t piece = nopen > 4 ? fb : (((fb / 4) + 255) & ~(size_t)255);
+            for (size_t o = 0; o < fb && ok; o += piece) {
+                const size_t len = std::min(piece, fb - o);
+                memcpy(hs + o, y + o, len);
+                ok = hipMemcpyAsync(ds + o, hs + o, len, hipMemcpyHostToDevice, cs) == hipSuccess;
+            }
+        } else {
+            uint8_t* d = hs;
+            for (int r = 0; r < hh; r++) memcpy(d + (size_t)r * w, y + (size_t)r * ys, (size_t)w);
+            d += ysz;
+            for (int r = 0; r < hh / 2; r++) memcpy(d + (size_t)r * (w / 2), u + (size_t)r * us, (size_t)(w / 2));
+            d += ysz / 4;
+            for (int r = 0; r < hh / 2; r++) memcpy(d + (size_t)r * (w / 2), v + (size_t)r * vs, (size_t)(w / 2));
+            ok = hipMemcpyAsync(ds, hs, fb, hipMemcpyHostToDevice, cs) == hipSuccess;
+        }
+    }
+    return ok && hipEventRecord(it.copied, cs) == hipSuccess;
+}
+
+static int hub_encode(mi355x_h264_stream* s, const HubInput& in, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
     Hub* h = s->hub;
     HubItem& it = h->items[s->item];
-    const int w = h->cfg.width, hh = h->cfg.height;
-    if (ys < w || us < w / 2 || vs < w / 2) { snprintf(it.err, sizeof(it.err), "stride smaller than width"); return MI355X_H264_E_ARG; }
+    const int w = h->cfg.width;
+    const bool rgba = h->fmt == MI355X_H264_INPUT_RGBA;
+    // whatever is refused is refused here, on the host, before anything is queued or launched; the stream stays usable
+    auto refuse = [&](const char* why) { snprintf(it.err, sizeof(it.err), "%s", why); return (int)MI355X_H264_E_ARG; };
+    if (in.form != HUB_IN_DEVICE && in.form != h->fmt) return refuse("the host picture's layout is not the one the stream was opened with");
+    if (in.form == HUB_IN_I420 && (in.stride[0] < w || in.stride[1] < w / 2 || in.stride[2] < w / 2)) return refuse("stride smaller than width");
+    if (in.form == HUB_IN_NV12 && (in.stride[0] < w || in.stride[1] < w)) return refuse("stride smaller than width");
+    if (in.form == HUB_IN_RGBA && in.stride[0] < 4 * w) return refuse("stride smaller than 4 * width");
+    if (in.form == HUB_IN_DEVICE && rgba && ((uintptr_t)in.p[0] & 7) != 0) return refuse("RGBA picture not aligned to 8 bytes");
     if (hipSetDevice(h->cfg.device) != hipSuccess) { snprintf(it.err, sizeof(it.err), "hipSetDevice"); return MI355X_H264_E_HIP; }
     const uint64_t t_in = now_us();
-    int nopen;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->uploading++;   // a step that is being gathered waits (briefly) for this picture
-        nopen = h->nopen;
-    }
-    // 1. the picture into the stream's staging slot: pinned copy, then the transfer - in pieces, so that the copy of piece k + 1
-    // runs while piece k is on the bus (the reference's tight layout, InitSrcPic ref :354-365; other layouts row by row)
-    uint8_t* hs = h->h_stage + (size_t)s->item * h->st_stage;
-    uint8_t* ds = h->d_stage + (size_t)s->item * h->st_stage;
-    hipStream_t cs = h->copy_st[s->item % Hub::NCOPY];
-    const size_t ysz = (size_t)w * hh, fb = ysz * 3 / 2;
+    const bool staged = in.form != HUB_IN_DEVICE;
     bool ok = true;
-    if (ys == w && us == w / 2 && vs == w / 2 && u == y + ysz && v == u + ysz / 4) {
-        // few streams: four pieces, so that the copy of piece k + 1 runs while piece k is on the bus (latency); many streams: one
-        // transfer per picture (every queued command costs, and other streams' transfers fill the bus anyway: 16 / 32 / 64 streams
-        // went from 7.3 / 8.0 / 8.6 k to 8.8 / 11.5 / 10.9 k fps with this alone, profiles/r03_hub_sweep_*.log)
-        const size_t piece = nopen > 4 ? fb : (((fb / 4) + 255) & ~(size_t)255);
-        for (size_t o = 0; o < fb && ok; o += piece) {
-            const size_t len = std::min(piece, fb - o);
-            memcpy(hs + o, y + o, len);
-            ok = hipMemcpyAsync(ds + o, hs + o, len, hipMemcpyHostToDevice, cs) == hipSuccess;
+    if (staged) {
+        // 1. a host picture goes to the stream's staging slot
+        int nopen;
+        {
+            std::lock_guard<std::mutex> lk(h->mu);
+            if (in.form == HUB_IN_RGBA && (!h->d_rgba || !h->h_rgba)) {   // RGBA staging comes with the hub's first host RGBA picture; whichever half is missing
+                if (!h->d_rgba && hipMalloc((void**)&h->d_rgba, h->st_rgba * h->cap) != hipSuccess) h->d_rgba = nullptr;
+                if (h->d_rgba && !h->h_rgba && hipHostMalloc((void**)&h->h_rgba, h->st_rgba * h->cap, hipHostMallocDefault) != hipSuccess) h->h_rgba = nullptr;
+                if (!h->d_rgba || !h->h_rgba) { snprintf(it.err, sizeof(it.err), "no memory for the RGBA staging pictures"); return MI355X_H264_E_NOMEM; }
+            }
+            h->uploading++;   // a step that is being gathered waits (briefly) for this picture
+            nopen = h->nopen;
         }
-    } else {
-        uint8_t* d = hs;
-        for (int r = 0; r < hh; r++) memcpy(d + (size_t)r * w, y + (size_t)r * ys, (size_t)w);
-        d += ysz;
-        for (int r = 0; r < hh / 2; r++) memcpy(d + (size_t)r * (w / 2), u + (size_t)r * us, (size_t)(w / 2));
-        d += ysz / 4;
-        for (int r = 0; r < hh / 2; r++) memcpy(d + (size_t)r * (w / 2), v + (size_t)r * vs, (size_t)(w / 2));
-        ok = hipMemcpyAsync(ds, hs, fb, hipMemcpyHostToDevice, cs) == hipSuccess;
-    }
-    ok = ok && hipEventRecord(it.copied, cs) == hipSuccess;
+        it.d_in = nullptr;
+        ok = hub_upload(h, it, s->item, in, nopen);
+    } else if (rgba) {
+        // a device picture is read where it lies: nothing is copied and nothing waited for.  RGBA: by the step's conversion launch,
+        // which writes the item's I420 staging slot; I420 / NV12: by the encoder kernels themselves
+        it.d_in = nullptr; it.rgba_src = in.p[0]; it.rgba_stride = (size_t)w * 4;
+    } else it.d_in = in.p[0];
+    it.staged = staged;
     // 2. queue the picture; lead a step or wait for the one that takes it
     std::unique_lock<std::mutex> lk(h->mu);
-    h->uploading--;
+    if (staged) h->uploading--;
     if (!ok) { h->cv.notify_all(); snprintf(it.err, sizeof(it.err), "upload of the picture failed"); return MI355X_H264_E_HIP; }
     it.pending = true; it.done = false;
     const uint64_t t_q = now_us();
@@ -1672,6 +1778,33 @@ int mi355x_h264_stream_encode(mi355x_h264_stream* s, const uint8_t* y, int ys, c
     *out = it.out; *out_len = it.out_len;
     if (frame_type) *frame_type = it.frame_type;
     return it.rc;
+}
+
+
+int mi355x_h264_stream_encode(mi355x_h264_stream* s, const uint8_t* y, int ys, const uint8_t* u, int us, const uint8_t* v, int vs,
+                              uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !y || !u || !v || !out || !out_len) return MI355X_H264_E_ARG;
+    return hub_encode(s, HubInput{HUB_IN_I420, {y, u, v}, {ys, us, vs}}, out, out_len, frame_type);
+}
+
+int mi355x_h264_stream_encode_nv12(mi355x_h264_stream* s, const uint8_t* y, int ys, const uint8_t* uv, int uvs, uint8_t** out, uint32_t* out_len,
+                                   int* frame_type)
+{
+    if (!s || !y || !uv || !out || !out_len) return MI355X_H264_E_ARG;
+    return hub_encode(s, HubInput{HUB_IN_NV12, {y, uv, nullptr}, {ys, uvs, 0}}, out, out_len, frame_type);
+}
+
+int mi355x_h264_stream_encode_rgba(mi355x_h264_stream* s, const uint8_t* rgba, int stride, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !rgba || !out || !out_len) return MI355X_H264_E_ARG;
+    return hub_encode(s, HubInput{HUB_IN_RGBA, {rgba, nullptr, nullptr}, {stride, 0, 0}}, out, out_len, frame_type);
+}
+
+int mi355x_h264_stream_encode_device(mi355x_h264_stream* s, const void* d_pic, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !d_pic || !out || !out_len) return MI355X_H264_E_ARG;
+    return hub_encode(s, HubInput{HUB_IN_DEVICE, {(const uint8_t*)d_pic, nullptr, nullptr}, {0, 0, 0}}, out, out_len, frame_type);
 }
 
 int mi355x_h264_stream_set_qp(mi355x_h264_stream* s, int qp)

@@ -127,6 +127,7 @@ EncoderRetCode PropertyDrivenEncoder::InitEncoder()
         ERR("InitEncoder: the %s engine could not be opened", BackendName());
         return VIDEO_ENCODER_INIT_FAIL;
     }
+    m_frameBytes = EnginePictureBytes();
     INFO("InitEncoder (%s): %ux%u @%u, %u bps, gop %u, %s", BackendName(), m_active.width, m_active.height, m_active.fps,
          m_active.bitrate, m_active.gop, m_active.profile.c_str());
     return VIDEO_ENCODER_SUCCESS;

@@ -54,9 +54,13 @@ protected:
     virtual bool EngineOpen(const Settings &s) = 0;          // create + configure; false -> InitEncoder fails
     virtual void EngineClose() = 0;                          // idempotent
     virtual bool EngineReady() const = 0;
-    // one tight I420 picture (Y w*h, U, V) -> access unit in ENGINE-owned memory, valid until the next call
+    // one tight picture (I420: Y w*h, U, V - unless the backend was opened for another layout or for device memory by an
+    // extension key) -> access unit in ENGINE-owned memory, valid until the next call
     virtual bool EngineEncode(const uint8_t *i420, uint8_t **out, uint32_t *outLen) = 0;
     virtual bool EngineForceIdr() = 0;
+    // bytes of one input picture in the layout the engine was opened for (asked after EngineOpen); the size guard of
+    // EncodeOneFrame.  The reference's layout is tight I420 (videoFormatI420, VideoEncoderOpenH264.cpp:307)
+    virtual uint32_t EnginePictureBytes() const { return m_lumaBytes * 3 / 2; }
 
     const Settings &Active() const { return m_active; }
     uint32_t LumaBytes() const { return m_lumaBytes; }

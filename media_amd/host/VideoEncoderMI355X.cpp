@@ -62,6 +62,10 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     if (GetStrEncParam("persist.vmi.video.encode.search") == "0") {
         cfg.search = MI355X_H264_SEARCH_EXHAUSTIVE;
     }
+    // extensions: the layout of the pictures ("nv12", "rgba"; else the reference's tight I420) and where they lie ("device":
+    // inputData is an address in this device's memory, read in place; else host memory).  include/mi355x_h264.h, "streams"
+    m_input = ParseInputLayout(GetStrEncParam("persist.vmi.video.encode.input"));
+    m_inputDevice = ParseInputDevice(GetStrEncParam("persist.vmi.video.encode.inputmem"));
     // One engine per object (mi355x_h264_create) costs every picture its own launch sequence.  The default is a STREAM of the
     // shared engine: the pictures that the encoder objects of one process hand over at about the same time are coded in one
     // lockstep step (include/mi355x_h264.h, "streams"; same bitstream).  persist.vmi.video.encode.shared = 0 (or the environment
@@ -69,6 +73,7 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     const char *hubEnv = getenv("MI355X_H264_HUB");
     const bool shared = GetStrEncParam("persist.vmi.video.encode.shared") != "0" && !(hubEnv != nullptr && hubEnv[0] == '0');
     if (shared) {
+        cfg.input_format = m_input;
         const int rc = mi355x_h264_stream_open(&cfg, &m_stream);
         if (rc != MI355X_H264_OK) {
             ERR("mi355x_h264_stream_open returned %d", rc);
@@ -77,6 +82,8 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
         }
         return true;
     }
+    // (an engine of its own takes RGBA through entry points of their own; its input_format names the layout of device I420 / NV12)
+    cfg.input_format = m_input == MI355X_H264_INPUT_NV12 ? MI355X_H264_INPUT_NV12 : MI355X_H264_INPUT_I420;
     const int rc = mi355x_h264_create(&cfg, &m_engine);
     if (rc != MI355X_H264_OK) {
         ERR("mi355x_h264_create returned %d", rc);
@@ -149,8 +156,32 @@ int32_t VideoEncoderMI355X::StartQp(uint32_t bitrate, uint32_t fps, uint32_t wid
     return 42;
 }
 
+int32_t VideoEncoderMI355X::ParseInputLayout(const std::string &value)
+{
+    return value == "nv12" ? MI355X_H264_INPUT_NV12 : value == "rgba" ? MI355X_H264_INPUT_RGBA : MI355X_H264_INPUT_I420;
+}
+
+bool VideoEncoderMI355X::ParseInputDevice(const std::string &value) { return value == "device"; }
+
 int VideoEncoderMI355X::EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType)
 {
+    if (m_inputDevice) {   // one tight picture in device memory, in the object's layout
+        if (m_stream != nullptr) {
+            return mi355x_h264_stream_encode_device(m_stream, i420, out, outLen, frameType);
+        }
+        return m_input == MI355X_H264_INPUT_RGBA ? mi355x_h264_encode_rgba_device(m_engine, i420, out, outLen, frameType)
+                                                 : mi355x_h264_encode_device(m_engine, i420, out, outLen, frameType);
+    }
+    if (m_input == MI355X_H264_INPUT_RGBA) {
+        const int stride = static_cast<int>(Active().width) * 4;
+        return m_stream != nullptr ? mi355x_h264_stream_encode_rgba(m_stream, i420, stride, out, outLen, frameType)
+                                   : mi355x_h264_encode_rgba(m_engine, i420, stride, out, outLen, frameType);
+    }
+    if (m_input == MI355X_H264_INPUT_NV12) {
+        const int w = static_cast<int>(Active().width);
+        return m_stream != nullptr ? mi355x_h264_stream_encode_nv12(m_stream, i420, w, i420 + LumaBytes(), w, out, outLen, frameType)
+                                   : mi355x_h264_encode_nv12(m_engine, i420, w, i420 + LumaBytes(), w, out, outLen, frameType);
+    }
     // tight I420 exactly as the reference's InitSrcPic lays the planes out (ref :354-365)
     const int pitch = static_cast<int>(Active().width);
     const uint8_t *u = i420 + LumaBytes();

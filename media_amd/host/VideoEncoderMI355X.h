@@ -27,6 +27,10 @@ public:
     // measurement hook (bench.py reads the reconstruction for PSNR): luma reconstruction of the last picture, coded size
     int64_t ReadReconY(void *dst, size_t cap, int32_t *codedWidth, int32_t *codedHeight);
     bool Shared() const { return m_stream != nullptr; }
+    // extension keys persist.vmi.video.encode.input / .inputmem: "nv12" / "rgba" -> MI355X_H264_INPUT_NV12 / _RGBA, anything else
+    // (or unset) -> MI355X_H264_INPUT_I420, the reference's videoFormatI420; "device" -> true, anything else -> host memory
+    static int32_t ParseInputLayout(const std::string &value);
+    static bool ParseInputDevice(const std::string &value);
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -35,6 +39,7 @@ protected:
     bool EngineReady() const override { return m_engine != nullptr || m_stream != nullptr; }
     bool EngineEncode(const uint8_t *i420, uint8_t **out, uint32_t *outLen) override;
     bool EngineForceIdr() override;
+    uint32_t EnginePictureBytes() const override { return m_input == MI355X_H264_INPUT_RGBA ? LumaBytes() * 4 : LumaBytes() * 3 / 2; }
 
 private:
     int EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType);
@@ -50,6 +55,8 @@ private:
     int64_t m_gopLeft = 0, m_picsLeft = 0, m_meanP = 0;   // GOP budget left, P pictures left in the GOP, running mean of the P pictures' bits
     bool m_sceneDetect = true;         // bEnableSceneChangeDetect = 1 in the reference preset (ref :283)
     uint32_t m_sceneCuts = 0;
+    int32_t m_input = MI355X_H264_INPUT_I420;   // layout of the pictures EncodeOneFrame is handed (persist.vmi.video.encode.input)
+    bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
 };
 
 #endif  // VIDEO_ENCODER_MI355X_H

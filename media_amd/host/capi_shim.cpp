@@ -16,6 +16,14 @@ uint32_t vc_encode(void *enc, const uint8_t *in, uint32_t inSize, uint8_t **out,
 {
     return static_cast<VideoEncoder *>(enc)->EncodeOneFrame(in, inSize, out, outSize);
 }
+// inputData as an address (persist.vmi.video.encode.inputmem = device: a picture in device memory)
+uint32_t vc_encode_addr(void *enc, uint64_t addr, uint32_t inSize, uint8_t **out, uint32_t *outSize)
+{
+    return static_cast<VideoEncoder *>(enc)->EncodeOneFrame(reinterpret_cast<const uint8_t *>(static_cast<uintptr_t>(addr)), inSize, out, outSize);
+}
+// how the two input extension keys read a value (host logic, no device)
+int32_t vc_parse_input_layout(const char *value) { return VideoEncoderMI355X::ParseInputLayout(value != nullptr ? value : ""); }
+int32_t vc_parse_input_device(const char *value) { return VideoEncoderMI355X::ParseInputDevice(value != nullptr ? value : "") ? 1 : 0; }
 uint32_t vc_stop(void *enc) { return static_cast<VideoEncoder *>(enc)->StopEncoder(); }
 void vc_destroy(void *enc) { static_cast<VideoEncoder *>(enc)->DestroyEncoder(); }
 uint32_t vc_reset(void *enc) { return static_cast<VideoEncoder *>(enc)->ResetEncoder(); }

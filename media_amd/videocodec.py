@@ -30,6 +30,10 @@ def lib():
         L.vc_destroy.restype = None
         L.vc_encode.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32)]
         L.vc_encode.restype = C.c_uint32
+        L.vc_encode_addr.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32)]
+        L.vc_encode_addr.restype = C.c_uint32
+        L.vc_parse_input_layout.argtypes = [C.c_char_p]
+        L.vc_parse_input_device.argtypes = [C.c_char_p]
         L.vc_last_qp.argtypes = [vp]
         L.vc_scene_cuts.argtypes = [vp]
         L.vc_scene_cuts.restype = C.c_uint32
@@ -53,7 +57,18 @@ def prop_get(key):
     return buf.value.decode()
 
 
-def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None):
+def parse_input_layout(value):
+    """what persist.vmi.video.encode.input = value selects: 0 I420, 1 NV12, 2 RGBA"""
+    return lib().vc_parse_input_layout(str(value).encode())
+
+
+def parse_input_device(value):
+    """does persist.vmi.video.encode.inputmem = value select device memory?"""
+    return bool(lib().vc_parse_input_device(str(value).encode()))
+
+
+def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
+                   inputmem=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -68,6 +83,8 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.qp", "" if qp is None else qp)
     prop_set("persist.vmi.video.encode.scenedetect", "1")
     prop_set("persist.vmi.video.encode.slices", "" if slices is None else slices)
+    prop_set("persist.vmi.video.encode.input", "" if input is None else input)        # nv12 | rgba; else I420
+    prop_set("persist.vmi.video.encode.inputmem", "" if inputmem is None else inputmem)   # device; else host memory
 
 
 class VideoEncoder:
@@ -88,6 +105,12 @@ class VideoEncoder:
         a = np.ascontiguousarray(data, dtype=np.uint8)
         out, n = C.c_void_p(), C.c_uint32()
         rc = lib().vc_encode(self.h, a.ctypes.data, a.size if size is None else size, C.byref(out), C.byref(n))
+        return rc, (C.string_at(out.value, n.value) if rc == SUCCESS else b"")
+
+    def encode_addr(self, addr, size):
+        """inputData = an address (a picture in device memory, persist.vmi.video.encode.inputmem = device), inputSize = size"""
+        out, n = C.c_void_p(), C.c_uint32()
+        rc = lib().vc_encode_addr(self.h, addr, size, C.byref(out), C.byref(n))
         return rc, (C.string_at(out.value, n.value) if rc == SUCCESS else b"")
 
     def stop(self):

@@ -5,14 +5,19 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...>
+// usage: plugin_bench <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
+// input (optional; without it everything is as above): i420 | nv12 | rgba, with ":device" behind it for pictures in device
+// memory - the extension keys persist.vmi.video.encode.input / .inputmem.  The pictures of the file are converted to the layout
+// on the host before the clock starts; for device memory they are uploaded once, before the clock, and every stream cycles
+// through them in place (the HIP runtime is reached through dlopen: this tool is built with the host compiler alone).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <dlfcn.h>
 #include <string>
 #include <thread>
 #include <vector>
@@ -20,13 +25,56 @@
 
 int main(int argc, char **argv)
 {
-    if (argc != 7) { fprintf(stderr, "usage: %s in.i420 w h pictures frames_per_stream S1,S2,...\n", argv[0]); return 2; }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     const int w = atoi(argv[2]), h = atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
-    const size_t fsz = (size_t)w * h * 3 / 2;
+    size_t fsz = (size_t)w * h * 3 / 2;
     std::vector<uint8_t> pics(fsz * npic);
     FILE *in = fopen(argv[1], "rb");
     if (in == nullptr || fread(pics.data(), 1, pics.size(), in) != pics.size()) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
     fclose(in);
+    const uint8_t *base = pics.data();   // where the pictures lie: fsz bytes apart, in host or in device memory
+    std::string layout = argc == 8 ? argv[7] : "i420";
+    bool device = false;
+    if (layout.size() > 7 && layout.compare(layout.size() - 7, 7, ":device") == 0) { device = true; layout.resize(layout.size() - 7); }
+    if (layout != "i420" && layout != "nv12" && layout != "rgba") { fprintf(stderr, "unknown input %s\n", argv[7]); return 2; }
+    if (argc == 8) {
+        setenv("PERSIST_VMI_VIDEO_ENCODE_INPUT", layout.c_str(), 1);
+        setenv("PERSIST_VMI_VIDEO_ENCODE_INPUTMEM", device ? "device" : "", 1);
+    }
+    if (layout != "i420") {   // the same pictures in the other layout (RGBA: BT.601 back to RGB, any mapping will do for a measurement)
+        const size_t ysz = (size_t)w * h, nsz = layout == "rgba" ? ysz * 4 : fsz;
+        std::vector<uint8_t> conv(nsz * npic);
+        for (int p = 0; p < npic; p++) {
+            const uint8_t *Y = pics.data() + fsz * p, *U = Y + ysz, *V = U + ysz / 4;
+            uint8_t *o = conv.data() + nsz * p;
+            if (layout == "nv12") {
+                memcpy(o, Y, ysz);
+                for (size_t i = 0; i < ysz / 4; i++) { o[ysz + 2 * i] = U[i]; o[ysz + 2 * i + 1] = V[i]; }
+            } else {
+                auto clip = [](int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); };
+                for (int y = 0; y < h; y++)
+                    for (int x = 0; x < w; x++) {
+                        const int l = Y[(size_t)y * w + x], cb = U[(size_t)(y / 2) * (w / 2) + x / 2] - 128, cr = V[(size_t)(y / 2) * (w / 2) + x / 2] - 128;
+                        uint8_t *q = o + ((size_t)y * w + x) * 4;
+                        q[0] = clip(l + ((359 * cr) >> 8)); q[1] = clip(l - ((88 * cb + 183 * cr) >> 8)); q[2] = clip(l + ((454 * cb) >> 8)); q[3] = 255;
+                    }
+            }
+        }
+        pics.swap(conv);
+        fsz = nsz;
+        base = pics.data();
+    }
+    if (device) {   // upload once, before the clock
+        void *hip = dlopen("libamdhip64.so", RTLD_NOW | RTLD_GLOBAL);
+        auto dmalloc = hip ? reinterpret_cast<int (*)(void **, size_t)>(dlsym(hip, "hipMalloc")) : nullptr;
+        auto dcopy = hip ? reinterpret_cast<int (*)(void *, const void *, size_t, int)>(dlsym(hip, "hipMemcpy")) : nullptr;
+        void *d = nullptr;
+        if (!dmalloc || !dcopy || dmalloc(&d, pics.size()) != 0 || dcopy(d, pics.data(), pics.size(), 1 /* hipMemcpyHostToDevice */) != 0) {
+            fprintf(stderr, "cannot put the pictures into device memory\n");
+            return 2;
+        }
+        base = static_cast<const uint8_t *>(d);
+    }
     std::vector<int> counts;
     for (char *tok = strtok(argv[6], ","); tok != nullptr; tok = strtok(nullptr, ",")) counts.push_back(atoi(tok));
     for (int S : counts) {
@@ -38,7 +86,7 @@ int main(int argc, char **argv)
             if (ok) {   // warm-up outside the clock: first IDR, allocations
                 uint8_t *au = nullptr;
                 uint32_t n = 0;
-                ok = encs[k]->EncodeOneFrame(pics.data() + fsz * (size_t)(k % npic), (uint32_t)fsz, &au, &n) == VIDEO_ENCODER_SUCCESS;
+                ok = encs[k]->EncodeOneFrame(base + fsz * (size_t)(k % npic), (uint32_t)fsz, &au, &n) == VIDEO_ENCODER_SUCCESS;
             }
         }
         if (!ok) { printf("{\"streams\":%d,\"error\":\"an encoder could not be opened\"}\n", S); continue; }
@@ -48,7 +96,7 @@ int main(int argc, char **argv)
         auto work = [&](int k) {
             lat[k].reserve(frames);
             for (int i = 0; i < frames; i++) {
-                const uint8_t *f = pics.data() + fsz * (size_t)((k + 1 + i) % npic);   // (the pool holds frames + S + 1 pictures: no wrap)
+                const uint8_t *f = base + fsz * (size_t)((k + 1 + i) % npic);   // (the pool holds frames + S + 1 pictures: no wrap)
                 uint8_t *au = nullptr;
                 uint32_t n = 0;
                 const auto t0 = std::chrono::steady_clock::now();
