@@ -209,6 +209,24 @@ int mi355x_h264_debug_keep_pre(mi355x_h264_encoder *enc, int on);
 /* copies the named device buffer of the last encoded picture (batch item 0) to dst; returns bytes or <0 */
 int64_t mi355x_h264_debug_read(mi355x_h264_encoder *enc, int what, void *dst, size_t cap);
 
+/* Codes ONE picture (every batch item's) from GIVEN decisions: the inverse of mi355x_h264_debug_read, the way into the entropy stage
+ * for syntax the decision kernels never choose (tests/test_gpu_entropy_random.py).  mbinfo, levels, mvq, mbaux: host arrays in the
+ * layouts of MI355X_H264_DBG_MBINFO / _LEVELS / _MVQ / _MBAUX, config.batch items one after the other (an item = all macroblocks of
+ * the coded picture); src_i420: config.batch tight I420 pictures of the display size, one after the other - the samples of I_PCM
+ * macroblocks are read from there.  The picture goes the way of every other picture - picture type by the same rule (forced IDR,
+ * first picture, GOP length), frame_num, idr_pic_id, ring slot and reference count kept the same way - except that the arrays are
+ * uploaded where the decision, transform and reconstruction kernels would have run, and that nothing is loop-filtered: boundary
+ * strengths, vector prediction and P_Skip, skip runs, both CAVLC passes, the bit scan, packing and the host's finishing run as in
+ * mi355x_h264_encode.  An inter macroblock is given as P_L0_16x16 / 16x8 / 8x16 / 8x8 with its vectors in mvq; whether it is written
+ * as P_Skip is decided on the device, as always.  What the arrays must respect is what the encoder's own pictures do: one QP (set_qp),
+ * ref_idx_l0 of a macroblock in chroma_mode and below the picture's reference count, tc consistent with levels.
+ * out / out_len: config.batch entries; item g's access unit, exactly as mi355x_h264_encode returns it, valid until the next call on
+ * the handle.  An item that fails (MI355X_H264_E_OVERFLOW: one of its slices outgrew its payload share - there is no I_PCM fallback
+ * here) gets out[g] = NULL, out_len[g] = 0, the other items are still delivered, and the first error is returned.
+ * The reconstruction ring holds nothing meaningful afterwards: the next mi355x_h264_encode* (or injected) picture is an IDR. */
+int mi355x_h264_debug_code_syntax(mi355x_h264_encoder *enc, const void *mbinfo, const void *levels, const void *mvq,
+                                  const void *mbaux, const uint8_t *src_i420, uint8_t **out, uint32_t *out_len, int *frame_type);
+
 /* ---- streams (ABI 3): many encoders of one geometry, one picture per call each, sharing one engine ----
  * The reference's operating mode is one VideoEncoder object per cloud-phone stream, each driven by its own thread with one
  * EncodeOneFrame per tick (/root/reference/video_codec/VideoEncoderOpenH264.cpp:304-352).  A stream is such an encoder whose

@@ -31,7 +31,9 @@ EXPORTS = [
     "mi355x_h264_stream_force_idr", "mi355x_h264_stream_set_idr_pic_id", "mi355x_h264_stream_last_me_cost",
     "mi355x_h264_stream_last_error", "mi355x_h264_stream_debug_read", "mi355x_h264_stream_hub_stats",
     "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
+    "mi355x_h264_debug_code_syntax",
 ]
+E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
 
 
@@ -86,6 +88,7 @@ def lib():
         L.mi355x_h264_debug_keep_pre.argtypes = [vp, C.c_int]
         L.mi355x_h264_debug_read.argtypes = [vp, C.c_int, vp, C.c_size_t]
         L.mi355x_h264_debug_read.restype = C.c_int64
+        L.mi355x_h264_debug_code_syntax.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_open.argtypes = [C.POINTER(Config), C.POINTER(vp)]
         L.mi355x_h264_stream_close.argtypes = [vp]
         L.mi355x_h264_stream_close.restype = None
@@ -111,7 +114,20 @@ def lib():
 
 
 class EncoderError(RuntimeError):
-    pass
+    rc = 0   # the MI355X_H264_E_* code, where a call returned one
+
+
+def _planes(f, w, h, strides, nv12=False):
+    """(address, stride) of every plane for the host entry points.  f: one tight picture (numpy uint8) - or, with `strides`, a
+    sequence of separate plane arrays (Y, U, V; NV12: Y, UV) whose rows lie strides[k] bytes apart; also returns what to keep alive"""
+    if strides is None:
+        f = np.ascontiguousarray(f, dtype=np.uint8)
+        base = f.ctypes.data
+        if nv12:
+            return [(base, w), (base + w * h, w)], f
+        return [(base, w), (base + w * h, w // 2), (base + w * h * 5 // 4, w // 2)], f
+    keep = [np.ascontiguousarray(p, dtype=np.uint8) for p in f]
+    return [(p.ctypes.data, int(st)) for p, st in zip(keep, strides)], keep
 
 
 class Encoder:
@@ -142,26 +158,41 @@ class Encoder:
 
     def _check(self, rc):
         if rc != 0:
-            raise EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_last_error(self.h).decode()))
+            err = EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_last_error(self.h).decode()))
+            err.rc = rc
+            raise err
 
-    def encode(self, i420):
-        """host I420 (numpy uint8, width*height*3/2) -> (bytes, frame_type)"""
-        w, h = self.width, self.height
-        f = np.ascontiguousarray(i420, dtype=np.uint8)
-        base = f.ctypes.data
+    def encode(self, i420, strides=None):
+        """host I420 (numpy uint8, width*height*3/2) -> (bytes, frame_type); with strides = (y, u, v) in bytes, i420 is the
+        three planes as separate arrays"""
+        ((y, ys), (u, us), (v, vs)), keep = _planes(i420, self.width, self.height, strides)   # keep: alive during the call
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_encode(self.h, base, w, base + w * h, w // 2, base + w * h * 5 // 4, w // 2,
-                                             C.byref(out), C.byref(n), C.byref(ft)))
+        self._check(lib().mi355x_h264_encode(self.h, y, ys, u, us, v, vs, C.byref(out), C.byref(n), C.byref(ft)))
+        del keep
         return C.string_at(out.value, n.value), ft.value
 
-    def encode_nv12(self, nv12):
-        """host NV12 (Y plane then interleaved UV) -> (bytes, frame_type)"""
-        w, h = self.width, self.height
-        f = np.ascontiguousarray(nv12, dtype=np.uint8)
+    def encode_nv12(self, nv12, strides=None):
+        """host NV12 (Y plane then interleaved UV) -> (bytes, frame_type); with strides = (y, uv), nv12 is the two planes"""
+        ((y, ys), (uv, uvs)), keep = _planes(nv12, self.width, self.height, strides, nv12=True)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_encode_nv12(self.h, f.ctypes.data, w, f.ctypes.data + w * h, w,
-                                                  C.byref(out), C.byref(n), C.byref(ft)))
+        self._check(lib().mi355x_h264_encode_nv12(self.h, y, ys, uv, uvs, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
+
+    def code_syntax(self, mbinfo, levels, mvq, mbaux, src_i420):
+        """mi355x_h264_debug_code_syntax: one picture per batch item from given decisions (arrays in the debug_read layouts, `batch`
+        items one after the other; src_i420: `batch` tight pictures).  Returns (rc, [access unit or None per item], frame_type):
+        the error code is returned, not raised - the items that did not fail are still delivered"""
+        a = [np.ascontiguousarray(x) for x in (mbinfo, levels, mvq, mbaux, src_i420)]
+        sizes = (self.nmb * 32, self.nmb * LV_STRIDE * 2, self.nmb * 16, self.nmb * 16, self.width * self.height * 3 // 2)
+        for x, n in zip(a, sizes):
+            if x.nbytes != n * self.batch:
+                raise ValueError("array of %d bytes where %d x %d are expected" % (x.nbytes, self.batch, n))
+        out, n, ft = (C.c_void_p * self.batch)(), (C.c_uint32 * self.batch)(), C.c_int()
+        rc = lib().mi355x_h264_debug_code_syntax(self.h, *[x.ctypes.data for x in a], out, n, C.byref(ft))
+        return rc, [C.string_at(out[g], n[g]) if out[g] else None for g in range(self.batch)], ft.value
+
+    def last_error(self):
+        return lib().mi355x_h264_last_error(self.h).decode()
 
     def encode_rgba(self, rgba, stride=None):
         """host RGBA (height x width x 4 bytes, or rows `stride` bytes apart) -> (bytes, frame_type)"""
@@ -289,15 +320,15 @@ class Stream:
 
     def _check(self, rc):
         if rc != 0:
-            raise EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_stream_last_error(self.h).decode()))
+            err = EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_stream_last_error(self.h).decode()))
+            err.rc = rc
+            raise err
 
-    def encode(self, i420):
-        w, h = self.width, self.height
-        f = np.ascontiguousarray(i420, dtype=np.uint8)
-        base = f.ctypes.data
+    def encode(self, i420, strides=None):
+        """host I420; with strides = (y, u, v) in bytes, i420 is the three planes as separate arrays"""
+        ((y, ys), (u, us), (v, vs)), keep = _planes(i420, self.width, self.height, strides)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode(self.h, base, w, base + w * h, w // 2, base + w * h * 5 // 4, w // 2,
-                                                    C.byref(out), C.byref(n), C.byref(ft)))
+        self._check(lib().mi355x_h264_stream_encode(self.h, y, ys, u, us, v, vs, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
     def encode_device(self, dev_ptr):
@@ -306,13 +337,11 @@ class Stream:
         self._check(lib().mi355x_h264_stream_encode_device(self.h, C.c_void_p(dev_ptr), C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
-    def encode_nv12(self, nv12):
-        """host NV12 (Y plane then interleaved UV)"""
-        w, h = self.width, self.height
-        f = np.ascontiguousarray(nv12, dtype=np.uint8)
+    def encode_nv12(self, nv12, strides=None):
+        """host NV12 (Y plane then interleaved UV); with strides = (y, uv), nv12 is the two planes as separate arrays"""
+        ((y, ys), (uv, uvs)), keep = _planes(nv12, self.width, self.height, strides, nv12=True)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode_nv12(self.h, f.ctypes.data, w, f.ctypes.data + w * h, w,
-                                                         C.byref(out), C.byref(n), C.byref(ft)))
+        self._check(lib().mi355x_h264_stream_encode_nv12(self.h, y, ys, uv, uvs, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
     def encode_rgba(self, rgba, stride=None):

@@ -216,6 +216,7 @@ struct mi355x_h264_encoder {
     uint8_t* d_stage = nullptr;              // device copy of a host-supplied picture
     uint8_t* h_stage = nullptr;              // pinned staging for strided host input
     uint8_t* d_rgba = nullptr, *h_rgba = nullptr;   // RGBA pictures on their way to the conversion kernel (allocated with the first)
+    uint8_t* d_inject_src = nullptr;         // mi355x_h264_debug_code_syntax: the batch items' source pictures (allocated with the first call)
     size_t frame_bytes = 0, bitbuf_cap = 0, au_cap = 0;
     Slot slots[NSLOT];
     int next_slot = 0;
@@ -223,6 +224,7 @@ struct mi355x_h264_encoder {
     std::vector<std::vector<uint8_t>> esc_buf;  // slow path: escaped access unit, per batch item
     long frames = 0;
     int frame_in_gop = 0, frame_num = 0, idr_id = 0, idr_step = 1, force_idr = 0;
+    bool after_injected = false;             // the last picture came through mi355x_h264_debug_code_syntax
     int qp = 26;
     bool keep_pre = false, stats_on = false;
     std::vector<hipEvent_t> ev_pool;
@@ -334,6 +336,7 @@ void build_parameter_sets(mi355x_h264_encoder* e)
 // slice_header() of 7.3.3 for this build's fixed choices, from slice_type on (first_mb_in_slice differs per slice and
 // is written by k_bit_scan); returns bit count (< 64)
 int avail_refs(const mi355x_h264_encoder* e, bool idr) { return idr ? 0 : std::min(e->nrefs, e->frame_in_gop); }
+inline bool mb_is_intra_host(int type) { return type == MB_I16 || type == MB_IPCM || type == MB_I4; }
 
 // frame_num, qp, nact (num_ref_idx_l0_active of a P slice): the picture's own - one per batch item in the stream hub's steps
 int build_slice_header(const mi355x_h264_encoder* e, bool idr, int idr_id, bool no_filter, int frame_num, int qp, int nact, uint64_t* bits)
@@ -387,6 +390,9 @@ struct StatScope {
 // slot of the hub's staging array or the caller's own device memory.  A step holds pictures of ONE type (IDR or P): the two run
 // different kernels.
 struct ItemPic { int item, cur, qp, frame_num, idr_id; };
+// mi355x_h264_debug_code_syntax: the decisions of the step's pictures come from the host (arrays of n items) instead of the
+// decision and reconstruction kernels
+struct Injected { const void* mbinfo; const void* levels; const void* mvq; const void* mbaux; };
 struct Step {
     const uint8_t* d_src = nullptr; size_t src_item_stride = 0; bool nv12 = false; bool idr = false;
     int n = 1;
@@ -397,6 +403,7 @@ struct Step {
     hipEvent_t recon_ready = nullptr, entropy_done = nullptr, done = nullptr;
     unsigned* h_err = nullptr;
     Slot* slot = nullptr;   // payload / access-unit buffers (laid out by batch item) and, with stats on, the event list
+    const Injected* inj = nullptr;   // test hook (direct steps only): upload these instead of deciding and reconstructing; no loop filter
     // out: where the access units lie in slot->h_au
     size_t au_start = 0, payload_off = 0;
     int nal_hdr = 0;
@@ -438,7 +445,26 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
 
     // (the payload buffers of the items were left zeroed by the k_pack of their previous use)
 
-    if (idr) {
+    if (T.inj) {
+        // the arrays k_i4_decide / k_intra_rows / k_me / k_tq / k_pintra_rows would have left, and the flags they would have raised
+        const size_t n = (size_t)T.n * e->nmb;
+        HIPCHK(e, hipMemcpyAsync(e->d_mb, T.inj->mbinfo, n * sizeof(MbInfo), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_levels, T.inj->levels, n * LV_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_mvq, T.inj->mvq, n * 8 * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_aux, T.inj->mbaux, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemsetAsync(e->d_me_cost, 0, n * sizeof(uint16_t), st));
+        unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {};
+        const MbInfo* m = (const MbInfo*)T.inj->mbinfo;
+        for (int g = 0; g < T.n; g++)
+            for (int i = 0; i < e->nmb; i++) {
+                const int type = m[(size_t)g * e->nmb + i].type;
+                if (type == MB_IPCM) anypcm[g] = pic_serial;
+                if (!idr && mb_is_intra_host(type)) anyintra[g] = pic_serial;
+            }
+        HIPCHK(e, hipMemcpyAsync(e->d_anypcm, anypcm, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_anyintra, anyintra, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipStreamSynchronize(st));   // (the flag arrays live on this stack)
+    } else if (idr) {
         StatScope sc(e, &S, MI355X_H264_K_INTRA, (uint32_t)(e->diag_mode ? e->mbw + e->mbh - 1 : 1), (uint32_t)(e->b_nmb * T.n), st);
         LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3((e->b_nmb + 3) / 4, G), dim3(64), st, P, 0);   // Intra4x4 or Intra16x16, and the block modes: from the source alone
         if (e->diag_mode && !ind) {
@@ -545,12 +571,12 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
                 (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
     }
     if (fork) HIPCHK(e, hipEventRecord(T.entropy_done, ec));
-    if (e->keep_pre && !ind)
+    if (e->keep_pre && !ind && !T.inj)
         for (int p = 0; p < 3; p++) {   // (the items' planes lie nbuf ring slots apart: one row of the 2-D copy per item)
             const size_t ring = p ? e->st_ring_c : e->st_ring_y;
             HIPCHK(e, hipMemcpy2DAsync(e->d_pre[p], ring, e->d_planes[cur][p], p ? e->st_c : e->st_y, ring, (size_t)e->G, hipMemcpyDeviceToDevice, st));
         }
-    if (!e->cfg.disable_deblock) {
+    if (!e->cfg.disable_deblock && !T.inj) {
         const int steps = e->mbw + 2 * (e->mbh - 1);
         StatScope sc(e, &S, MI355X_H264_K_DEBLOCK, (uint32_t)(e->diag_mode ? steps : 1), (uint32_t)(e->b_nmb * T.n), st);
         DbParams D{};
@@ -599,16 +625,19 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
 }
 
 // enqueue everything for one picture (every batch item's) whose I420 samples are at d_src: the direct form
-int submit(mi355x_h264_encoder* e, const uint8_t* d_src, size_t src_item_stride, int slot_idx, bool nv12)
+int submit(mi355x_h264_encoder* e, const uint8_t* d_src, size_t src_item_stride, int slot_idx, bool nv12, const Injected* inj = nullptr)
 {
     Slot& S = e->slots[slot_idx];
-    const bool idr = e->force_idr || e->frames == 0 || e->frame_in_gop >= e->cfg.gop;
+    // (after an injected picture, mi355x_h264_debug_code_syntax, nothing was reconstructed: a real picture has no reference then)
+    const bool idr = e->force_idr || (e->after_injected && !inj) || e->frames == 0 || e->frame_in_gop >= e->cfg.gop;
     if (idr) { e->frame_in_gop = 0; e->frame_num = 0; }
     e->force_idr = 0;
+    e->after_injected = inj != nullptr;
     Step T;
     T.d_src = d_src; T.src_item_stride = src_item_stride; T.nv12 = nv12; T.idr = idr; T.n = e->G;
     T.st = e->stream; T.ec = e->stream_ec; T.recon_ready = S.recon_ready; T.entropy_done = S.entropy_done; T.done = S.done; T.h_err = S.h_err;
     T.slot = &S;
+    T.inj = inj;
     const int rc = submit_step(e, T);
     if (rc) return rc;
     S.au_start = T.au_start; S.payload_off = T.payload_off; S.idr = idr; S.nal_hdr = T.nal_hdr;
@@ -936,6 +965,7 @@ void mi355x_h264_destroy(mi355x_h264_encoder* e)
     (void)hipFree(e->d_handoff); (void)hipFree(e->d_bs); (void)hipFree(e->d_me_cost);
     if (e->h_stage) (void)hipHostFree(e->h_stage);
     (void)hipFree(e->d_rgba);
+    (void)hipFree(e->d_inject_src);
     if (e->h_rgba) (void)hipHostFree(e->h_rgba);
     for (auto& S : e->slots) {
         (void)hipFree(S.d_bitbuf); (void)hipFree(S.d_info);
@@ -1113,7 +1143,10 @@ int mi355x_h264_encode_batch_device(mi355x_h264_encoder* e, const void* d_frames
         if (rc) return rc;
         const int idx = head;
         head++; npend--;
-        if (pos + n > out_cap) return fail(e, MI355X_H264_E_OVERFLOW, "batch output buffer too small");
+        if (pos + n > out_cap) {
+            e->force_idr = 1;   // this picture (and those in flight behind it) never reach the caller: the next one must not refer to them
+            return fail(e, MI355X_H264_E_OVERFLOW, "batch output buffer too small");
+        }
         memcpy(host_out + pos, p, n);
         sizes[idx] = n;
         pos += n;
@@ -1301,6 +1334,33 @@ int64_t mi355x_h264_debug_read(mi355x_h264_encoder* e, int what, void* dst, size
     if (hipStreamSynchronize(e->stream) != hipSuccess) return MI355X_H264_E_HIP;
     if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return MI355X_H264_E_HIP;
     return (int64_t)n;
+}
+
+int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, const void* levels, const void* mvq, const void* mbaux,
+                                  const uint8_t* src_i420, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!e || !mbinfo || !levels || !mvq || !mbaux || !src_i420 || !out || !out_len) return fail(e, MI355X_H264_E_ARG, "null argument");
+    if (e->cfg.band_count > 1) return fail(e, MI355X_H264_E_ARG, "not for slice bands over several instances");
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t src_bytes = e->frame_bytes * (size_t)e->G;
+    if (!e->d_inject_src) HIPCHK(e, hipMalloc((void**)&e->d_inject_src, src_bytes + 256));
+    HIPCHK(e, hipMemcpy(e->d_inject_src, src_i420, src_bytes, hipMemcpyHostToDevice));   // k_cavlc reads the I_PCM samples from the source
+    const int slot = e->next_slot;
+    e->next_slot = (e->next_slot + 1) % NSLOT;
+    const Injected inj{mbinfo, levels, mvq, mbaux};
+    int rc = submit(e, e->d_inject_src, e->frame_bytes, slot, false, &inj);
+    if (rc) return rc;
+    rc = wait_slot(e, slot);
+    if (rc) return rc;
+    char first[sizeof(e->err)] = {0};
+    for (int g = 0; g < e->G; g++) {   // every item is finished, whatever became of the ones before it
+        out[g] = nullptr; out_len[g] = 0;
+        const int r = finish_item(e, slot, g, &out[g], &out_len[g], frame_type);
+        if (r) { out[g] = nullptr; out_len[g] = 0; }
+        if (r && !rc) { rc = r; memcpy(first, e->err, sizeof(first)); }
+    }
+    if (rc) memcpy(e->err, first, sizeof(first));
+    return rc;
 }
 
 int mi355x_h264_stats_enable(mi355x_h264_encoder* e, int on)

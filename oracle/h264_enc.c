@@ -87,16 +87,28 @@ static int se_len(int v)
 }
 
 /* ------------------------------------------------------------ CAVLC 9.2 */
+/* hit counters of the writer (h264o_enc_hits): the encoder whose slice data is being written, NULL for the stand-alone helpers */
+static __thread h264o_hits *g_hits;
+#define HIT(expr) do { if (g_hits) { g_hits->expr; } } while (0)
+static void cavlc_block_body(bitw *b, const int16_t *lv, int max_coeff, int nC);
 static void cavlc_block(bitw *b, const int16_t *lv, int max_coeff, int nC)
+{
+    const uint64_t at = b->bits;
+    cavlc_block_body(b, lv, max_coeff, nC);
+    if (b->bits - at > 64) HIT(long_residual_slots++);
+}
+static void cavlc_block_body(bitw *b, const int16_t *lv, int max_coeff, int nC)
 {
     int level[16], idx[16], tc = 0, t1 = 0;
     for (int i = max_coeff - 1; i >= 0; i--)
         if (lv[i]) { level[tc] = lv[i]; idx[tc] = i; tc++; }
     while (t1 < tc && t1 < 3 && abs(level[t1]) == 1) t1++;
     if (nC == -1) {
+        HIT(cdc_token[tc][t1]++);
         bw_put(b, o_chroma_dc_token_len[4 * tc + t1], o_chroma_dc_token_bits[4 * tc + t1]);
     } else {
         int tab = nC < 2 ? 0 : nC < 4 ? 1 : nC < 8 ? 2 : 3;
+        HIT(coeff_token[tab][tc][t1]++);
         bw_put(b, o_coeff_token_len[tab][4 * tc + t1], o_coeff_token_bits[tab][4 * tc + t1]);
     }
     if (!tc) return;
@@ -106,6 +118,12 @@ static void cavlc_block(bitw *b, const int16_t *lv, int max_coeff, int nC)
         int lvl = level[k];
         int code = lvl > 0 ? 2 * lvl - 2 : -2 * lvl - 1;
         if (k == t1 && t1 < 3) code -= 2;
+        HIT(suffix_len[suffix_len]++);
+        {   /* level_prefix of this level (9.2.2.1), counted for the two greatest the generator may use */
+            const int pre = suffix_len == 0 ? (code < 14 ? code : code < 30 ? 14 : 15) : (code < (15 << suffix_len) ? code >> suffix_len : 15);
+            if (pre == 14) HIT(prefix14[suffix_len]++);
+            if (pre == 15) HIT(prefix15[suffix_len]++);
+        }
         if (suffix_len == 0) {
             if (code < 14) {
                 bw_put(b, code + 1, 1);
@@ -137,12 +155,14 @@ static void cavlc_block(bitw *b, const int16_t *lv, int max_coeff, int nC)
     }
     if (tc < max_coeff) {
         int tz = idx[0] + 1 - tc;
+        if (nC == -1) HIT(cdc_total_zeros[tc][tz]++); else HIT(total_zeros[tc][tz]++);
         if (nC == -1) bw_put(b, o_cdc_total_zeros_len[tc - 1][tz], o_cdc_total_zeros_bits[tc - 1][tz]);
         else bw_put(b, o_total_zeros_len[tc - 1][tz], o_total_zeros_bits[tc - 1][tz]);
         int zl = tz;
         for (int k = 0; k < tc - 1 && zl > 0; k++) {
             int run = idx[k] - idx[k + 1] - 1;
             int t = (zl > 7 ? 7 : zl) - 1;
+            HIT(run_before[t + 1][run]++);
             bw_put(b, o_run_len[t][run], o_run_bits[t][run]);
             zl -= run;
         }
@@ -199,6 +219,11 @@ struct h264o_enc {
     uint8_t *rbsp;
     size_t rbsp_cap;
     int64_t last_slice_bits;
+    int64_t slice_bits_all[256];   /* every slice of the last picture: bits of its RBSP up to and including rbsp_stop_one_bit */
+    int nslices_last;
+    uint32_t *mb_bitpos;   /* per macroblock of the last picture: bit position in its slice's RBSP where its syntax starts (a P_Skip
+                            * macroblock: where the run that holds it is written) */
+    h264o_hits hits;
     uint32_t me_cost; /* scene-change statistic of the last picture */
     int any_pcm;      /* the picture being coded holds an I_PCM macroblock: it is not loop-filtered */
     uint8_t *aux;          /* 16 bytes per macroblock: Intra4x4PredMode of the 16 blocks (blkIdx order) */
@@ -265,6 +290,7 @@ h264o_enc *h264o_enc_create(const h264o_config *cfg)
     e->aux = (uint8_t *)calloc((size_t)e->mbw * e->mbh, 16);
     e->mvq = (int16_t *)calloc((size_t)e->mbw * e->mbh, 8 * sizeof(int16_t));
     e->pshape = (uint8_t *)calloc((size_t)e->mbw * e->mbh, 1);
+    e->mb_bitpos = (uint32_t *)calloc((size_t)e->mbw * e->mbh, sizeof(uint32_t));
     for (int i = 0; i < e->mbw * e->mbh; i++) e->slice_of[i] = (int16_t)(i / e->mbw / e->slice_rows);
     e->rbsp_cap = ysz * 4 + 65536;
     e->rbsp = (uint8_t *)malloc(e->rbsp_cap);
@@ -282,6 +308,7 @@ void h264o_enc_destroy(h264o_enc *e)
     free(e->aux);
     free(e->mvq);
     free(e->pshape);
+    free(e->mb_bitpos);
     free(e->rbsp);
     free(e);
 }
@@ -335,6 +362,15 @@ const uint8_t *h264o_enc_mbaux(const h264o_enc *e) { return e->aux; }
 const int16_t *h264o_enc_mvq(const h264o_enc *e) { return e->mvq; }
 const int16_t *h264o_enc_levels(const h264o_enc *e) { return e->levels; }
 int64_t h264o_enc_last_slice_bits(const h264o_enc *e) { return e->last_slice_bits; }
+int h264o_enc_slice_bits_all(const h264o_enc *e, int64_t *bits, int cap)
+{
+    for (int i = 0; i < e->nslices_last && i < cap; i++) bits[i] = e->slice_bits_all[i];
+    return e->nslices_last;
+}
+const uint32_t *h264o_enc_mb_bitpos(const h264o_enc *e) { return e->mb_bitpos; }
+const uint8_t *h264o_enc_source(const h264o_enc *e, int p) { return e->src[p]; }
+const h264o_hits *h264o_enc_hits(const h264o_enc *e) { return &e->hits; }
+void h264o_enc_hits_reset(h264o_enc *e) { memset(&e->hits, 0, sizeof(e->hits)); }
 uint32_t h264o_enc_last_me_cost(const h264o_enc *e) { return e->me_cost; }
 
 /* ------------------------------------------------------------ headers 7.3.2 */
@@ -1202,9 +1238,12 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
     const int16_t *lv = e->levels + (size_t)(my * e->mbw + mx) * H264O_LV_STRIDE;
     int cbpl = mb->cbp & 15, cbpc = mb->cbp >> 4;
     const int qpd = e->rs ? e->rs->qpd[my * e->mbw + mx] : 0;   /* mb_qp_delta: 0 for every macroblock the encoder codes */
+    const uint64_t mb_at = b->bits;
+    e->hits.mb_kind[mb->type]++;
     if (mb->type == H264O_MB_IPCM) {   /* 7.3.5: mb_type I_PCM, alignment, 256 + 2 x 64 samples */
         int cw = e->cw, cs = cw / 2;
         bw_ue(b, (uint32_t)(p_slice ? 5 + 25 : 25));
+        e->hits.mb_type[p_slice][p_slice ? 30 : 25]++;
         while (b->bits & 7) bw_put(b, 1, 0);
         for (int y = 0; y < 16; y++)
             for (int x = 0; x < 16; x++) bw_put(b, 8, e->src[0][(16 * my + y) * cw + 16 * mx + x]);
@@ -1216,6 +1255,8 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
     if (mb->type == H264O_MB_I4) {   /* I_NxN: 7.3.5.1 mb_pred with the sixteen Intra4x4 modes, then the residual by coded_block_pattern */
         const uint8_t *am = e->aux + (size_t)(my * e->mbw + mx) * 16;
         bw_ue(b, (uint32_t)(p_slice ? 5 : 0));
+        e->hits.mb_type[p_slice][p_slice ? 5 : 0]++;
+        e->hits.cbp_intra[mb->cbp]++;
         if (e->cfg.profile_idc == 100) bw_put(b, 1, 0);   /* transform_size_8x8_flag: Intra4x4, not Intra8x8 */
         for (int k = 0; k < 16; k++) {   /* 8.3.1.1: predicted mode = the smaller of the left and upper blocks' modes */
             int x = o_blk_x[k], y = o_blk_y[k], mA, mB, dc_only = 0;
@@ -1226,6 +1267,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
             else if (!intra_avail(e, mx, my, mx, my - 1)) { dc_only = 1; mB = 2; }
             else mB = (mb - e->mbw)->type == H264O_MB_I4 ? (am - 16 * e->mbw)[xy2blk[12 + x]] : 2;
             int pm = dc_only ? 2 : (mA < mB ? mA : mB), m = am[k];
+            e->hits.i4_mode[k][m]++;
             if (m == pm) bw_put(b, 1, 1);
             else { bw_put(b, 1, 0); bw_put(b, 3, (uint32_t)(m < pm ? m : m - 1)); }
         }
@@ -1238,8 +1280,11 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
     if (mb->type == H264O_MB_I16) {
         int t = 1 + mb->i16_mode + 4 * cbpc + (cbpl ? 12 : 0);
         bw_ue(b, (uint32_t)(p_slice ? 5 + t : t));
+        e->hits.mb_type[p_slice][p_slice ? 5 + t : t]++;
         bw_ue(b, mb->chroma_mode);
         bw_se(b, qpd); /* mb_qp_delta */
+        if (b->bits - mb_at > 64) e->hits.long_header_slots++;
+        g_hits = &e->hits;
         cavlc_block(b, lv + H264O_LV_LUMA_DC, 16, nc_luma(e, mx, my, 0));
     } else {
         /* 7.3.5.1 / 7.3.5.2: mb_type (P_L0_16x16, P_L0_L0_16x8, P_L0_L0_8x16, P_8x8 with four sub_mb_type P_L0_8x8), then
@@ -1247,6 +1292,8 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
         const int shape = mb->type >= H264O_MB_P16X8 ? mb->type - H264O_MB_P16X8 + 1 : 0, nparts = shape == 0 ? 1 : shape == 3 ? 4 : 2;
         const int16_t *qv = e->mvq + (size_t)(my * e->mbw + mx) * 8;
         bw_ue(b, (uint32_t)shape);
+        e->hits.mb_type[1][shape]++;
+        e->hits.cbp_inter[mb->cbp]++;
         if (e->rs && e->rs->direct) {   /* random-stream generator, every inter macroblock of the picture */
             uint32_t *rng = &e->rs->rng;
             int sub[4] = {0, 0, 0, 0}, all8x8 = 1;
@@ -1285,6 +1332,8 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
             mv_t p = predict_mv_part(e, mx, my, x0, y0, w, h, mb->chroma_mode, NULL);
             bw_se(b, qv[2 * (2 * y0 + x0)] - p.x);
             bw_se(b, qv[2 * (2 * y0 + x0) + 1] - p.y);
+            if ((uint32_t)abs(qv[2 * (2 * y0 + x0)] - p.x) > e->hits.max_mvd) e->hits.max_mvd = (uint32_t)abs(qv[2 * (2 * y0 + x0)] - p.x);
+            if ((uint32_t)abs(qv[2 * (2 * y0 + x0) + 1] - p.y) > e->hits.max_mvd) e->hits.max_mvd = (uint32_t)abs(qv[2 * (2 * y0 + x0) + 1] - p.y);
         }
         int code = 0;
         while (o_cbp_code2inter[code] != mb->cbp) code++;
@@ -1293,6 +1342,8 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
         if (mb->cbp) bw_se(b, qpd); /* mb_qp_delta */
     }
 residual:
+    if (mb->type != H264O_MB_I16 && b->bits - mb_at > 64) e->hits.long_header_slots++;
+    g_hits = &e->hits;
     for (int b8 = 0; b8 < 4; b8++)
         if (cbpl & (1 << b8))
             for (int k = 0; k < 4; k++) {
@@ -1308,6 +1359,17 @@ residual:
         for (int pl = 0; pl < 2; pl++)
             for (int k = 0; k < 4; k++)
                 cavlc_block(b, lv + H264O_LV_CHROMA_AC + (pl * 4 + k) * 16 + 1, 15, nc_chroma(e, mx, my, pl, k));
+    g_hits = NULL;
+}
+
+/* mb_skip_run as written (hit counters): its length, whether it ends the slice, whether an I_PCM macroblock follows it */
+static void hit_skip_run(h264o_enc *e, int run, int ends_slice, const h264o_mbinfo *next)
+{
+    if (!run) return;
+    if ((uint32_t)run > e->hits.max_skip_run) e->hits.max_skip_run = (uint32_t)run;
+    if (run > e->mbw) e->hits.skip_runs_over_a_row++;
+    if (ends_slice) e->hits.skip_run_ends_slice++;
+    if (next && next->type == H264O_MB_IPCM) e->hits.pcm_after_skip_run++;
 }
 
 /* ------------------------------------------------------------ picture driver */
@@ -1418,6 +1480,7 @@ int64_t h264o_enc_encode(h264o_enc *e, const uint8_t *y, int ys, const uint8_t *
     }
     /* stage 2: entropy coding, one NAL unit per slice */
     e->last_slice_bits = 0;
+    e->nslices_last = 0;
     memset(e->rbsp, 0, e->rbsp_cap);
     for (int row0 = e->band_row0; row0 < e->band_row1; row0 += e->slice_rows) {
         int row1 = row0 + e->slice_rows < e->mbh ? row0 + e->slice_rows : e->mbh;
@@ -1428,15 +1491,19 @@ int64_t h264o_enc_encode(h264o_enc *e, const uint8_t *y, int ys, const uint8_t *
         for (int my = row0; my < row1; my++)
             for (int mx = 0; mx < e->mbw; mx++) {
                 const h264o_mbinfo *mb = &e->mb[my * e->mbw + mx];
+                e->mb_bitpos[my * e->mbw + mx] = (uint32_t)b.bits;
                 if (!idr) {
-                    if (mb->type == H264O_MB_PSKIP) { skip_run++; continue; }
+                    if (mb->type == H264O_MB_PSKIP) { skip_run++; e->hits.mb_kind[H264O_MB_PSKIP]++; continue; }
+                    hit_skip_run(e, skip_run, 0, mb);
                     bw_ue(&b, (uint32_t)skip_run);
                     skip_run = 0;
                 }
                 write_mb(e, &b, mx, my, !idr);
             }
+        hit_skip_run(e, skip_run, 1, NULL);
         if (skip_run) bw_ue(&b, (uint32_t)skip_run);
         e->last_slice_bits += (int64_t)(b.bits - hdr_bits);
+        if (e->nslices_last < 256) e->slice_bits_all[e->nslices_last++] = (int64_t)b.bits + 1;
         bw_trailing(&b);
         if ((b.bits >> 3) > e->rbsp_cap) return -3;
         pos = emit_nal(out, out_cap, pos, idr ? 3 : 2, idr ? 5 : 1, e->rbsp, (size_t)(b.bits >> 3));
@@ -1488,6 +1555,83 @@ static int rs_levels(uint32_t *s, int16_t *lv, int first, int n, int density, in
         }
     }
     return tc;
+}
+
+/* feature 2048: one block of a shape the quantised transform of a picture hardly ever makes (h264_oracle.h lists them).
+ * Levels are laid down in coding order, from the highest scan position down; level_prefix stays <= 15. */
+static int rs_dense_block(uint32_t *s, int16_t *lv, int first, int n)
+{
+    static const int16_t ramp[6] = {2, 4, 7, 13, 25, 49};   /* each is the smallest magnitude that raises suffixLength once more */
+    const int room = n - first;
+    int16_t seq[16];   /* magnitudes in coding order */
+    int cnt = 0, spread = 1;
+    for (int i = first; i < n; i++) lv[i] = 0;
+    switch (rs_below(s, 8)) {
+    case 0:   /* every position non-zero */
+        for (int i = 0; i < room; i++) seq[cnt++] = (int16_t)(1 + (rs_below(s, 4) == 0));
+        break;
+    case 1:   /* one late coefficient after a long run of zeros; now and then one more at the very start (run_before up to 14) */
+        lv[n - 1 - rs_below(s, room < 3 ? room : 3)] = (int16_t)(rs_below(s, 2) ? -1 - rs_below(s, 3) : 1 + rs_below(s, 3));
+        if (rs_below(s, 2)) {
+            const int i = first + rs_below(s, room < 2 ? room : 2);
+            if (!lv[i]) lv[i] = (int16_t)(rs_below(s, 2) ? -1 - rs_below(s, 2) : 1 + rs_below(s, 2));
+        }
+        break;
+    case 2: {   /* 0..3 trailing ones, a level of exactly 2 or 3 (levelCode -= 2 when there are fewer than three), more ones */
+        const int t1 = rs_below(s, 4), more = rs_below(s, 6);
+        for (int i = 0; i < t1 + 1 + more && cnt < room; i++) seq[cnt++] = (int16_t)(i == t1 ? 2 + rs_below(s, 2) : 1);
+        break; }
+    case 3: case 4: {   /* a ramp up to suffixLength sl; then (4) a level of level_prefix 14 or 15 at that suffixLength */
+        const int esc = rs_below(s, 2);
+        int sl = rs_below(s, 7), t1 = rs_below(s, 3);
+        if (sl > room - 1) sl = room - 1;
+        if (t1 + sl + 2 > room) t1 = 0;
+        for (int i = 0; i < t1; i++) seq[cnt++] = 1;
+        for (int i = 0; i < sl; i++) seq[cnt++] = ramp[i];
+        if (esc) {
+            const int p15 = rs_below(s, 2);
+            if (sl == 0) seq[cnt++] = (int16_t)(p15 ? 18 + rs_below(s, 500) : 9 + rs_below(s, 7));
+            else seq[cnt++] = (int16_t)(p15 ? 15 * (1 << (sl - 1)) + 1 + rs_below(s, 200) : 7 * (1 << sl) + 1 + rs_below(s, 1 << (sl - 1)));
+        } else seq[cnt++] = (int16_t)(1 + rs_below(s, sl ? 3 << (sl - 1) : 2));
+        if (cnt < room && rs_below(s, 2)) seq[cnt++] = (int16_t)(1 + rs_below(s, 4));
+        break; }
+    default: {  /* (three in eight) TotalCoeff drawn evenly from 1 .. all, TrailingOnes from 0 .. 3, positions evenly */
+        const int tc = 1 + rs_below(s, room), t1 = rs_below(s, 4);
+        for (int i = 0; i < tc; i++) seq[cnt++] = (int16_t)(i < t1 ? 1 : i == t1 && t1 < 3 ? 2 + rs_below(s, 2) : 1 + rs_below(s, 3));
+        spread = rs_below(s, 3) ? 0 : 2;
+        break; }
+    }
+    if (spread == 2) {   /* packed at the low end: total_zeros 0 .. 2 whatever TotalCoeff is */
+        const int slack = room - cnt, start = first + rs_below(s, slack < 2 ? slack + 1 : 3);
+        for (int k = 0; k < cnt; k++) lv[start + cnt - 1 - k] = (int16_t)(rs_below(s, 2) ? -seq[k] : seq[k]);
+        cnt = 0;
+    }
+    /* seq[] onto scan positions, highest first: evenly drawn positions, or (spread 1) mostly adjacent with a zero now and then */
+    for (int i = n - 1, k = 0; i >= first && k < cnt; i--) {
+        const int left = i - first + 1, need = cnt - k;
+        const int take = left <= need ? 1 : spread ? rs_below(s, 4) != 0 : rs_below(s, left) < need;
+        if (take) { lv[i] = (int16_t)(rs_below(s, 2) ? -seq[k] : seq[k]); k++; }
+    }
+    int tc = 0;
+    for (int i = first; i < n; i++) tc += lv[i] != 0;
+    return tc;
+}
+/* a generous estimate of the bits of one block (the budget of feature 2048) */
+static int rs_block_cost(const int16_t *lv, int first, int n)
+{
+    int bits = 26;
+    for (int i = first; i < n; i++) bits += lv[i] == 0 ? 0 : abs(lv[i]) <= 1 ? 2 : abs(lv[i]) < 9 ? 8 : 30;
+    return bits;
+}
+/* one residual block of the random picture: an ordinary one, or - while the macroblock's budget (feature 2048, else 0) lasts - a dense one */
+static int rs_block(uint32_t *s, int16_t *lv, int first, int n, int density, int mag, int *dense_left)
+{
+    if (*dense_left >= 300 && rs_below(s, 3) == 0) {
+        const int tc = rs_dense_block(s, lv, first, n);
+        *dense_left -= rs_block_cost(lv, first, n);
+        return tc;
+    }
+    return rs_levels(s, lv, first, n, density, mag);
 }
 
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
@@ -1549,6 +1693,23 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         size_t n = (size_t)e->cw * e->ch / (p ? 4 : 1);
         for (size_t i = 0; i < n; i++) e->src[p][i] = (uint8_t)(rs_next(&rng) >> 11);
     }
+    int skip_from = -1, skip_to = -1;   /* feature 4096: macroblocks skip_from .. skip_to - 1 of a P picture are P_Skip */
+    if (features & 4096) {
+        if (rs_below(&rng, 4) == 0) memset(e->src[0] + (size_t)rs_below(&rng, e->mbh) * 16 * e->cw, 0, (size_t)16 * e->cw);   /* a macroblock row of zero luma */
+        for (int p = 0; p < 3; p++) {   /* outside the display size: the edge repeated, as the encoder reads its source */
+            const int w = p ? e->cfg.width / 2 : e->cfg.width, h = p ? e->cfg.height / 2 : e->cfg.height, cw = p ? e->cw / 2 : e->cw, ch = p ? e->ch / 2 : e->ch;
+            for (int r = 0; r < ch; r++) {
+                uint8_t *d = e->src[p] + (size_t)r * cw;
+                if (r >= h) memcpy(d, e->src[p] + (size_t)(h - 1) * cw, (size_t)cw);
+                else for (int c = w; c < cw; c++) d[c] = d[w - 1];
+            }
+        }
+        if (!idr && rs_below(&rng, 3) == 0) {
+            skip_from = rs_below(&rng, nmb);
+            skip_to = skip_from + e->mbw + 1 + rs_below(&rng, 2 * e->mbw);
+        }
+    }
+    int any_pcm = 0;
     memset(e->levels, 0, (size_t)nmb * H264O_LV_STRIDE * sizeof(int16_t));
     memset(e->aux, 0, (size_t)nmb * 16);
     memset(e->mvq, 0, (size_t)nmb * 8 * sizeof(int16_t));
@@ -1573,6 +1734,10 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             else type = kind < 22 ? H264O_MB_PSKIP : kind < 44 ? H264O_MB_P16 : kind < 54 ? H264O_MB_P16X8 : kind < 64 ? H264O_MB_P8X16
                       : kind < 76 ? H264O_MB_P8X8 : kind < 85 ? H264O_MB_I16 : kind < 94 ? H264O_MB_I4 : H264O_MB_IPCM;
             if (type == H264O_MB_IPCM && !(features & 8)) type = H264O_MB_I16;
+            if (mbi >= skip_from && mbi < skip_to) type = H264O_MB_PSKIP;
+            const int saturate = (features & 8192) && my < e->slice_rows && mbi % 8 < 3;
+            if (saturate) type = idr ? H264O_MB_I4 : H264O_MB_P16;
+            int dense_left = (features & 2048) ? 2000 : 0;
             mb->type = (uint8_t)type;
             /* residual density / magnitude of this macroblock (kept small at high QP: 16-bit intermediates of 8.5) */
             /* feature 512: at QP_Y <= 14 an eighth of the levels is 128 .. 427 (scaled coefficients stay below 2^15) */
@@ -1581,6 +1746,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 mb->cbp = 0x2F;
                 memset(mb->tc, 16, 24);
                 if (mbqp_out) mbqp_out[mbi] = 0;   /* 8.7.2.2: qP of an I_PCM macroblock */
+                any_pcm = 1;
                 continue;
             }
             if (type == H264O_MB_PSKIP && rs.direct) {   /* (its vector is the decoder's business) */
@@ -1608,9 +1774,9 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 mb->i16_mode = (uint8_t)m;
                 const int cbpl = rs_below(&rng, 2) ? 15 : 0, cbpc = rs_below(&rng, 3);
                 mb->cbp = (uint8_t)(cbpl | (cbpc << 4));
-                rs_levels(&rng, lv + H264O_LV_LUMA_DC, 0, 16, dens + 2, mag);
+                rs_block(&rng, lv + H264O_LV_LUMA_DC, 0, 16, dens + 2, mag, &dense_left);
                 if (cbpl)
-                    for (int b = 0; b < 16; b++) mb->tc[b] = (uint8_t)rs_levels(&rng, lv + H264O_LV_LUMA + b * 16, 1, 16, dens, mag);
+                    for (int b = 0; b < 16; b++) mb->tc[b] = (uint8_t)rs_block(&rng, lv + H264O_LV_LUMA + b * 16, 1, 16, dens, mag, &dense_left);
                 carries_delta = 1;
             } else if (type == H264O_MB_I4) {
                 for (int k = 0; k < 16; k++) {
@@ -1646,16 +1812,38 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 mb->mvx = qv[0]; mb->mvy = qv[1];
                 mb->cbp = (uint8_t)(rs_below(&rng, 3) == 0 ? 0 : (rs_below(&rng, 16) | (rs_below(&rng, 3) << 4)));
                 mb->i16_mode = (uint8_t)(high && (mb->cbp & 15) ? rs_below(&rng, 2) : 0);   /* transform_size_8x8_flag */
+                if ((features & 4096) && type == H264O_MB_P16 && mb->cbp == 0 && mb->chroma_mode == 0) {
+                    mv_t skip;   /* the encoder writes this macroblock as P_Skip when its vector is the P_Skip one: move it */
+                    predict_mv_part(e, mx, my, 0, 0, 2, 2, 0, &skip);
+                    if (skip.x == mb->mvx && skip.y == mb->mvy) {
+                        mb->mvx = (int16_t)(mb->mvx + (mb->mvx < 0 ? 1 : -1));
+                        for (int q = 0; q < 4; q++) qv[2 * q] = mb->mvx;
+                    }
+                }
             }
             if (type != H264O_MB_I16) {
                 for (int b = 0; b < 16; b++)
-                    if (mb->cbp & (1 << (b >> 2))) mb->tc[b] = (uint8_t)rs_levels(&rng, lv + H264O_LV_LUMA + b * 16, 0, 16, dens, mag);
+                    if (mb->cbp & (1 << (b >> 2))) mb->tc[b] = (uint8_t)rs_block(&rng, lv + H264O_LV_LUMA + b * 16, 0, 16, dens, mag, &dense_left);
                 carries_delta = mb->cbp != 0;
             }
             if (mb->cbp >> 4) {
+                if (features & 2048) {
+                    rs_block(&rng, lv + H264O_LV_CHROMA_DC, 0, 4, dens + 3, mag, &dense_left);
+                    rs_block(&rng, lv + H264O_LV_CHROMA_DC + 4, 0, 4, dens + 3, mag, &dense_left);
+                } else
                 rs_levels(&rng, lv + H264O_LV_CHROMA_DC, 0, 8, dens + 3, mag);
                 if ((mb->cbp >> 4) == 2)
-                    for (int b = 0; b < 8; b++) mb->tc[16 + b] = (uint8_t)rs_levels(&rng, lv + H264O_LV_CHROMA_AC + b * 16, 1, 16, dens, mag);
+                    for (int b = 0; b < 8; b++) mb->tc[16 + b] = (uint8_t)rs_block(&rng, lv + H264O_LV_CHROMA_AC + b * 16, 1, 16, dens, mag, &dense_left);
+            }
+            if (saturate) {   /* feature 8192: every coefficient of the macroblock a level of level_prefix 15 */
+                mb->cbp = 0x2F;
+                for (int i = H264O_LV_LUMA; i < H264O_LV_STRIDE; i++) {
+                    const int a = 500 + rs_below(&rng, 100);
+                    lv[i] = (int16_t)(rs_below(&rng, 2) ? -a : a);
+                }
+                for (int b = 0; b < 8; b++) lv[H264O_LV_CHROMA_AC + b * 16] = 0;   /* (the DC positions of the AC blocks are not coded) */
+                memset(mb->tc, 16, 16);
+                memset(mb->tc + 16, 15, 8);
             }
             if (carries_delta && (features & 1) && rs_below(&rng, 2)) {
                 int d = rs_below(&rng, 4) ? rs_below(&rng, 9) - 4 : rs_below(&rng, 52) - 26;
@@ -1668,6 +1856,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             }
             if (mbqp_out) mbqp_out[mbi] = (uint8_t)qp;
         }
+    if ((features & 4096) && any_pcm) rs.idc = 1;   /* the encoder does not filter a picture that holds an I_PCM macroblock */
     /* headers and slices, as h264o_enc_encode writes them */
     size_t pos = 0;
     bitw b;
@@ -1684,6 +1873,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         if (pos != (size_t)-1) pos = emit_nal(out, out_cap, pos, 3, 8, e->rbsp, (size_t)(b.bits >> 3));
     }
     memset(e->rbsp, 0, e->rbsp_cap);
+    e->nslices_last = 0;
     int slice_no = 0;
     for (int a0 = 0; a0 < nmb && pos != (size_t)-1; slice_no++) {
         int a1;   /* the slice is macroblocks a0 .. a1 - 1 */
@@ -1696,15 +1886,19 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         for (int a = a0; a < a1; a++) {
                 const int mx = a % e->mbw, my = a / e->mbw;
                 const h264o_mbinfo *mb = &e->mb[a];
+                e->mb_bitpos[a] = (uint32_t)b.bits;
                 if (!idr) {
-                    if (mb->type == H264O_MB_PSKIP) { skip_run++; continue; }
+                    if (mb->type == H264O_MB_PSKIP) { skip_run++; e->hits.mb_kind[H264O_MB_PSKIP]++; continue; }
+                    hit_skip_run(e, skip_run, 0, mb);
                     bw_ue(&b, (uint32_t)skip_run);
                     skip_run = 0;
                 }
                 write_mb(e, &b, mx, my, !idr);
             }
         a0 = a1;
+        hit_skip_run(e, skip_run, 1, NULL);
         if (skip_run) bw_ue(&b, (uint32_t)skip_run);
+        if (e->nslices_last < 256) e->slice_bits_all[e->nslices_last++] = (int64_t)b.bits + 1;
         bw_trailing(&b);
         if ((b.bits >> 3) > e->rbsp_cap) { pos = (size_t)-1; break; }
         pos = emit_nal(out, out_cap, pos, idr ? 3 : 2, idr ? 5 : 1, e->rbsp, (size_t)(b.bits >> 3));

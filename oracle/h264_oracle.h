@@ -104,6 +104,36 @@ int h264o_pred4x4(const uint8_t *rec, int stride, int mode, int avail, uint8_t p
 const int16_t *h264o_enc_levels(const h264o_enc *e);
 /* bits of slice_data() of the last slice, before trailing bits (for tests) */
 int64_t h264o_enc_last_slice_bits(const h264o_enc *e);
+/* every slice of the last picture: bits of its RBSP from first_mb_in_slice up to and including rbsp_stop_one_bit; returns the
+ * number of slices (at most `cap` entries are written) */
+int h264o_enc_slice_bits_all(const h264o_enc *e, int64_t *bits, int cap);
+/* per macroblock of the last picture: the bit of its slice's RBSP at which its syntax starts (a P_Skip macroblock: where the
+ * mb_skip_run that holds it is written) - lets a test name the macroblock a differing byte falls in */
+const uint32_t *h264o_enc_mb_bitpos(const h264o_enc *e);
+/* source planes (coded size, pitch as the reconstruction's): of the last encoded picture, or the samples
+ * h264o_enc_random_picture drew for its I_PCM macroblocks */
+const uint8_t *h264o_enc_source(const h264o_enc *e, int plane);
+/* What the slice data writer has written since the last reset, per syntax element (tests: is an input worth running?).
+ * Counted for h264o_enc_encode and h264o_enc_random_picture alike; every field is a plain count unless named max_. */
+typedef struct {
+    uint32_t coeff_token[4][17][4];     /* Table 9-5 by [nC class: 0-1, 2-3, 4-7, 8+][TotalCoeff][TrailingOnes] */
+    uint32_t cdc_token[5][4];           /* ... its chroma DC column (nC = -1) */
+    uint32_t total_zeros[16][16];       /* Tables 9-7 / 9-8 by [TotalCoeff 1..15][total_zeros] */
+    uint32_t cdc_total_zeros[4][4];     /* Table 9-9 (a) by [TotalCoeff 1..3][total_zeros] */
+    uint32_t run_before[8][15];         /* Table 9-10 by [min(zerosLeft, 7)][run_before] */
+    uint32_t suffix_len[7];             /* levels coded with suffixLength 0..6 */
+    uint32_t prefix14[7], prefix15[7];  /* levels of level_prefix 14 / 15, by the suffixLength they were coded with */
+    uint32_t mb_kind[8];                /* by H264O_MB_* */
+    uint32_t mb_type[2][32];            /* mb_type as written, [0] in I slices, [1] in P slices */
+    uint32_t cbp_intra[48], cbp_inter[48];   /* coded_block_pattern of Intra4x4 / inter macroblocks, by value */
+    uint32_t i4_mode[16][9];            /* Intra4x4PredMode by [blkIdx][mode] */
+    uint32_t max_mvd;                   /* greatest |mvd_l0| component, quarter samples */
+    uint32_t max_skip_run, skip_runs_over_a_row, skip_run_ends_slice, pcm_after_skip_run;
+    uint32_t long_header_slots;         /* macroblock headers (mb_type .. mb_qp_delta) of more than 64 bits */
+    uint32_t long_residual_slots;       /* residual blocks of more than 64 bits */
+} h264o_hits;
+const h264o_hits *h264o_enc_hits(const h264o_enc *e);
+void h264o_enc_hits_reset(h264o_enc *e);
 /* scene-change statistic (mirrors mi355x_h264_last_me_cost) */
 uint32_t h264o_enc_last_me_cost(const h264o_enc *e);
 
@@ -114,7 +144,19 @@ uint32_t h264o_enc_last_me_cost(const h264o_enc *e);
  * 64 (with 32) slices cut at random macroblocks instead of bands of rows, 128 ref_pic_list_modification commands in P slices,
  * 256 parameter sets and slice headers laid out the way OpenH264 writes them (15-bit frame_num, POC type 0, VUI, a list modification
  * in every P slice; the same for every picture of a stream), 512 levels of 128 .. 427 at QP_Y <= 14 (use with 1: QPs are then drawn from 4 .. 48),
- * 1024 constrained_intra_pred_flag = 1.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
+ * 1024 constrained_intra_pred_flag = 1,
+ * 2048 dense residual: blocks of shapes the quantised transform of a picture hardly ever makes - every position non-zero, one late
+ * coefficient after a long run of zeros, runs of +-1 with 0..3 trailing ones in front of a level of exactly +-2 / +-3, magnitude ramps
+ * that walk suffixLength from 0 to 6, levels of level_prefix 14 and 15 at every suffixLength, TotalCoeff and TrailingOnes drawn
+ * evenly - beside the ordinary ones, within a budget per macroblock (level_prefix stays <= 15),
+ * 4096 encoder-shaped: what mi355x_h264_debug_code_syntax turns into the same bytes.  A P_L0_16x16 macroblock that k_mvpred would
+ * turn into P_Skip (no coefficients, ref_idx 0, the P_Skip vector) gets its vector moved by a quarter sample; a picture with an
+ * I_PCM macroblock says disable_deblocking_filter_idc 1; the I_PCM samples outside the display size repeat the edge (the
+ * encoder reads a display-size source); and - what the decision kernels' pictures have and independent draws never do - now and
+ * then a run of P_Skip macroblocks longer than a row, and I_PCM samples that are all zero (emulation prevention),
+ * 8192 (tests of the refusal path only, NOT conforming: macroblocks far beyond the 3200 bits of A.3.1) two macroblocks in five of
+ * the first slice carry escape levels in every position.
+ * 2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
  * macroblock (0 for I_PCM, the value the loop filter uses).  Side information: h264o_enc_mbinfo / _mvq / _mbaux / _levels. */
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
                                  int *is_idr, uint8_t *mbqp_out);

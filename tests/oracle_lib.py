@@ -22,6 +22,23 @@ MBINFO_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("type", "u1"), ("i16_m
 assert MBINFO_DTYPE.itemsize == 32
 
 
+class Hits(C.Structure):
+    """h264o_hits: what the oracle's slice data writer has written since the last reset, per syntax element"""
+    _fields_ = [("coeff_token", C.c_uint32 * 4 * 17 * 4), ("cdc_token", C.c_uint32 * 4 * 5), ("total_zeros", C.c_uint32 * 16 * 16),
+                ("cdc_total_zeros", C.c_uint32 * 4 * 4), ("run_before", C.c_uint32 * 15 * 8), ("suffix_len", C.c_uint32 * 7),
+                ("prefix14", C.c_uint32 * 7), ("prefix15", C.c_uint32 * 7), ("mb_kind", C.c_uint32 * 8), ("mb_type", C.c_uint32 * 32 * 2),
+                ("cbp_intra", C.c_uint32 * 48), ("cbp_inter", C.c_uint32 * 48), ("i4_mode", C.c_uint32 * 9 * 16),
+                ("max_mvd", C.c_uint32), ("max_skip_run", C.c_uint32), ("skip_runs_over_a_row", C.c_uint32),
+                ("skip_run_ends_slice", C.c_uint32), ("pcm_after_skip_run", C.c_uint32), ("long_header_slots", C.c_uint32),
+                ("long_residual_slots", C.c_uint32)]
+    MAX_FIELDS = ("max_mvd", "max_skip_run")
+
+    def arrays(self):
+        """{field: numpy uint64 array (a copy)}"""
+        return {n: np.array(np.ctypeslib.as_array(getattr(self, n)) if not isinstance(getattr(self, n), int) else getattr(self, n), dtype=np.uint64)
+                for n, _ in self._fields_}
+
+
 def _build():
     srcs = [os.path.join(_ODIR, f) for f in os.listdir(_ODIR) if f.endswith((".c", ".h"))]
     if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs):
@@ -70,6 +87,15 @@ def lib():
         L.h264o_enc_random_picture.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_int), vp]
         L.h264o_enc_last_slice_bits.restype = C.c_int64
         L.h264o_enc_last_slice_bits.argtypes = [vp]
+        L.h264o_enc_slice_bits_all.argtypes = [vp, vp, C.c_int]
+        L.h264o_enc_mb_bitpos.restype = vp
+        L.h264o_enc_mb_bitpos.argtypes = [vp]
+        L.h264o_enc_source.restype = vp
+        L.h264o_enc_source.argtypes = [vp, C.c_int]
+        L.h264o_enc_hits.restype = C.POINTER(Hits)
+        L.h264o_enc_hits.argtypes = [vp]
+        L.h264o_enc_hits_reset.restype = None
+        L.h264o_enc_hits_reset.argtypes = [vp]
         L.h264o_dec_create.restype = vp
         L.h264o_dec_destroy.argtypes = [vp]
         L.h264o_dec_decode.argtypes = [vp, vp, C.c_size_t]
@@ -148,6 +174,9 @@ class OracleEncoder:
         return bytes(self.out[:n]), bool(idr.value)
 
     RAND_QP, RAND_CHROMA_OFF, RAND_FILTER_OFF, RAND_PCM, RAND_IDC, RAND_SUBPARTS, RAND_SLICES, RAND_REORDER, RAND_OPENH264_HEADERS, RAND_BIG_LEVELS, RAND_CONSTRAINED_INTRA, RAND_ALL = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2047
+    # not part of RAND_ALL (the decoder-peer tests): dense residual blocks; syntax the encoder's entropy stage codes to the same bytes
+    # (mi355x_h264_debug_code_syntax); a first slice that outgrows its payload share (refusal path only, not conforming)
+    RAND_DENSE, RAND_ENCODER_SHAPED, RAND_SATURATE_FIRST_SLICE = 2048, 4096, 8192
 
     def random_picture(self, seed, force_idr=False, features=31):
         """one picture of random conforming syntax (h264o_enc_random_picture): (access unit, is_idr, QP_Y per macroblock);
@@ -215,7 +244,31 @@ class OracleEncoder:
         return lib().h264o_enc_last_me_cost(self.h)
 
     def slice_bits(self):
+        """bits of every slice of the last picture, first_mb_in_slice up to and including rbsp_stop_one_bit"""
+        a = np.zeros(256, np.int64)
+        n = lib().h264o_enc_slice_bits_all(self.h, _ptr(a), a.size)
+        return [int(v) for v in a[:n]]
+
+    def last_slice_data_bits(self):
+        """bits of slice_data() of the last picture (all its slices), headers and trailing bits not counted"""
         return lib().h264o_enc_last_slice_bits(self.h)
+
+    def mb_bitpos(self):
+        """per macroblock of the last picture: the bit of its slice's RBSP at which its syntax starts"""
+        n = (self.cw // 16) * (self.ch // 16)
+        addr = lib().h264o_enc_mb_bitpos(self.h)
+        return np.ctypeslib.as_array(C.cast(addr, C.POINTER(C.c_uint32)), shape=(n,)).copy()
+
+    def source_i420(self):
+        """the source picture as a tight display-size I420 array (after random_picture: the samples drawn for I_PCM macroblocks)"""
+        w, h = self.width, self.height
+        return np.concatenate([self._plane(lib().h264o_enc_source, p)[: (h // 2 if p else h), : (w // 2 if p else w)].ravel() for p in range(3)])
+
+    def hits(self):
+        return lib().h264o_enc_hits(self.h).contents.arrays()
+
+    def hits_reset(self):
+        lib().h264o_enc_hits_reset(self.h)
 
     def close(self):
         if self.h:

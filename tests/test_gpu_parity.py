@@ -131,10 +131,41 @@ def test_forced_idr_qp_change_and_strided_input():
         if i == 4:
             enc.set_qp(37)
             orc.set_qp(37)
-        a, ft = enc.encode(f)
+        if i % 2:   # rows padded to a different stride per plane, random bytes in the padding, planes in separate buffers
+            a, ft = enc.encode(*_padded_planes(f, w, h, (w + 7, w // 2 + 3, w // 2 + 16), seed=i))
+        else:
+            a, ft = enc.encode(f)
         b, idr = orc.encode(f, force_idr=(i == 2))
         assert a == b and (ft == capi.FRAME_IDR) == idr
+    planes, _ = _padded_planes(f, w, h, (w, w // 2, w // 2), seed=0)
+    for bad in ((w - 1, w // 2, w // 2), (w, w // 2 - 1, w // 2), (w, w // 2, w // 2 - 1)):   # a stride below the width
+        with pytest.raises(capi.EncoderError) as ei:
+            enc.encode(planes, bad)
+        assert ei.value.rc == capi.E_ARG
     enc.close()
+    # the NV12 form: padded Y and UV rows
+    enc, orc = capi.Encoder(w, h, qp=30), OracleEncoder(w, h, qp=30)
+    for i, f in enumerate(synth.sequence("s1", w, h, 2)):
+        (y, u, v), _ = _padded_planes(f, w, h, (w + 5, w // 2, w // 2), seed=20 + i)
+        uv = np.random.default_rng(30 + i).integers(0, 256, (h // 2, w + 12), dtype=np.uint8)
+        uv[:, 0:w:2], uv[:, 1:w:2] = u.reshape(h // 2, -1)[:, : w // 2], v.reshape(h // 2, -1)[:, : w // 2]
+        assert enc.encode_nv12((y, uv), (w + 5, w + 12))[0] == orc.encode(f)[0]
+    with pytest.raises(capi.EncoderError) as ei:
+        enc.encode_nv12((y, uv), (w + 5, w - 2))
+    assert ei.value.rc == capi.E_ARG
+    enc.close()
+
+
+def _padded_planes(f, w, h, strides, seed):
+    """a tight I420 picture as three separate planes with rows strides[k] bytes apart and random bytes behind every row"""
+    rng = np.random.default_rng(seed)
+    tight = [f[: w * h].reshape(h, w), f[w * h: w * h * 5 // 4].reshape(h // 2, w // 2), f[w * h * 5 // 4:].reshape(h // 2, w // 2)]
+    out = []
+    for t, st in zip(tight, strides):
+        p = rng.integers(0, 256, (t.shape[0], st), dtype=np.uint8)
+        p[:, : t.shape[1]] = t
+        out.append(p)
+    return out, strides
 
 
 def test_nv12_ingest_main_profile_1080p60():

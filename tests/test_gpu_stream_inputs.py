@@ -261,3 +261,30 @@ def test_plugin_input_properties_shared_engine_and_own_engine(mode):
         vc.set_video_mode(w, h)
         vc.prop_set("persist.vmi.video.encode.shared", "")
     assert dev is None or dev.untouched()
+
+
+def test_host_pictures_with_padded_rows_equal_the_oracle_on_the_tight_picture():
+    """the row-copy branches of the stream hub's host forms: every plane its own stride, random bytes in the padding"""
+    w, h = 178, 98
+    for nv12 in (False, True):
+        st = capi.Stream(w, h, qp=27, gop=4, input_format=capi.INPUT_NV12 if nv12 else capi.INPUT_I420)
+        orc = OracleEncoder(w, h, qp=27, gop=4)
+        try:
+            for i, f in enumerate(synth.sequence("s1", w, h, 5)):
+                rng = np.random.default_rng(100 + i)
+                y, u, v = f[: w * h].reshape(h, w), f[w * h: w * h * 5 // 4].reshape(h // 2, w // 2), f[w * h * 5 // 4:].reshape(h // 2, w // 2)
+                strides = (w + 9, w + 14) if nv12 else (w + 9, w // 2 + 1, w // 2 + 6)
+                src = [y, np.stack([u, v], axis=2).reshape(h // 2, w)] if nv12 else [y, u, v]
+                planes = []
+                for t, s_ in zip(src, strides):
+                    p = rng.integers(0, 256, (t.shape[0], s_), dtype=np.uint8)
+                    p[:, : t.shape[1]] = t
+                    planes.append(p)
+                got = (st.encode_nv12 if nv12 else st.encode)(planes, strides)[0]
+                assert got == orc.encode(f)[0], "picture %d (%s)" % (i, "NV12" if nv12 else "I420")
+            with pytest.raises(capi.EncoderError) as ei:
+                (st.encode_nv12 if nv12 else st.encode)(planes, (w - 1,) + tuple(strides[1:]))
+            assert ei.value.rc == capi.E_ARG
+        finally:
+            st.close()
+            orc.close()
