@@ -1,0 +1,882 @@
+// media_amd/csrc/engine.h -- the encoder engine behind include/mi355x_h264.h: device memory, streams, access-unit
+// slots, one lockstep step of launches (submit_step), the wait for it and the host's finish of every access unit.  The
+// stream hub (hub.h) and the decoder peer (decoder.h) each drive one engine.  Part of the one translation unit
+// mi355x_h264.hip, which includes the kernels before this file.
+#pragma once
+
+#define HIPCHK(err, call)                                                                                    \
+    do {                                                                                                     \
+        hipError_t _r = (call);                                                                              \
+        if (_r != hipSuccess) return set_err((err), MI355X_H264_E_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
+    } while (0)
+// for the set-up functions that hand the hipError_t on (their callers undo and translate): the call that failed, for the report
+namespace { thread_local const char* t_failed_call = ""; }
+#define HIPTRY(call)                                                      \
+    do {                                                                  \
+        hipError_t _r = (call);                                           \
+        if (_r != hipSuccess) { t_failed_call = #call; return _r; }       \
+    } while (0)
+
+namespace {
+
+// Every device or pinned allocation of an owner (engine, hub, decoder) is registered where it is made and freed in one loop.
+struct DevMem {
+    struct Block { void* p; bool pinned; };
+    std::vector<Block> blocks;
+    template <class T> hipError_t dev(T** p, size_t bytes, bool zero = false)
+    {
+        HIPTRY(hipMalloc((void**)p, bytes));
+        blocks.push_back({*p, false});
+        if (zero) HIPTRY(hipMemset(*p, 0, bytes));
+        return hipSuccess;
+    }
+    template <class T> hipError_t pinned(T** p, size_t bytes)
+    {
+        HIPTRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
+        blocks.push_back({*p, true});
+        return hipSuccess;
+    }
+    // both halves of a staging pair that comes with its first use: whichever is still missing
+    template <class T> bool pair(T** d, T** h, size_t bytes)
+    {
+        if (!*d && dev(d, bytes) != hipSuccess) *d = nullptr;
+        if (*d && !*h && pinned(h, bytes) != hipSuccess) *h = nullptr;
+        return *d && *h;
+    }
+    void free_all() { for (const Block& b : blocks) { if (b.pinned) (void)hipHostFree(b.p); else (void)hipFree(b.p); } blocks.clear(); }
+};
+
+// What one step in flight needs to be launched and waited for: its stream pair (entropy coding forks to ec), the fork /
+// join events, the event behind its last command and the wavefront kernels' time-out flag (pinned).  An engine slot and
+// a hub context each hold one.
+struct StepSync {
+    hipStream_t st = nullptr, ec = nullptr;
+    hipEvent_t recon_ready = nullptr, entropy_done = nullptr, done = nullptr;
+    unsigned* h_err = nullptr;
+    bool own_streams = false;
+};
+// st == nullptr: a stream pair of its own (one stream for both when one_stream); else the caller's pair
+hipError_t sync_create(StepSync& y, hipStream_t st, hipStream_t ec, bool one_stream)
+{
+    if (!st) {
+        y.own_streams = true;
+        HIPTRY(hipStreamCreateWithFlags(&y.st, hipStreamNonBlocking));
+        if (one_stream) y.ec = y.st;
+        else HIPTRY(hipStreamCreateWithFlags(&y.ec, hipStreamNonBlocking));
+    } else { y.st = st; y.ec = ec; }
+    for (hipEvent_t* ev : {&y.done, &y.recon_ready, &y.entropy_done}) HIPTRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    HIPTRY(hipHostMalloc((void**)&y.h_err, sizeof(unsigned), hipHostMallocDefault));
+    *y.h_err = 0;
+    return hipSuccess;
+}
+void sync_destroy(StepSync& y)
+{
+    if (y.own_streams && y.st) {
+        (void)hipStreamSynchronize(y.st);
+        if (y.ec && y.ec != y.st) { (void)hipStreamSynchronize(y.ec); (void)hipStreamDestroy(y.ec); }
+        (void)hipStreamDestroy(y.st);
+    }
+    for (hipEvent_t ev : {y.done, y.recon_ready, y.entropy_done}) if (ev) (void)hipEventDestroy(ev);
+    if (y.h_err) (void)hipHostFree(y.h_err);
+    y = StepSync();
+}
+// the wavefront kernels' time-out flag of a finished step: read, cleared (it is per report) and put into words
+int handoff_timeout(StepSync& y, char (&err)[256])
+{
+    const unsigned flag = *y.h_err;
+    if (!flag) return MI355X_H264_OK;
+    *y.h_err = 0;
+    return set_err(err, MI355X_H264_E_INTERNAL, "wavefront kernel hand-off timed out (flag %u)", flag);
+}
+
+constexpr int NSLOT = 3;          // access-unit slots in flight
+
+// where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
+struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0; };
+
+struct Slot {
+    uint32_t* d_bitbuf = nullptr;   // device slice payload (zeroed before use)
+    SliceInfo* d_info = nullptr;
+    SliceInfo* h_info = nullptr;    // pinned
+    uint8_t* h_au = nullptr;        // pinned access unit buffer
+    AuLayout lay;                   // of the picture in flight
+    bool busy = false;
+    StepSync sync;                  // on the engine's stream pair
+    // stats events of this frame: pairs (start, stop, kernel id, launches, mbs)
+    struct Ev { hipEvent_t a, b; int k; uint32_t launches, mbs; };
+    std::vector<Ev> evs;
+};
+
+}  // namespace
+
+struct mi355x_h264_encoder {
+    mi355x_h264_config cfg{};
+    int mbw = 0, mbh = 0, cw = 0, ch = 0, nmb = 0, level_idc = 0;
+    int device = 0;
+    int G = 1;                               // lockstep batch: closed GOPs / streams encoded together
+    int nsl = 1;                             // slices per picture: bands of sl.rows macroblock rows
+    SliceRows sl{};
+    size_t slice_cap = 0;                    // bytes of payload buffer per slice (multiple of 16)
+    // slice bands over several GPUs: this instance codes slices b_sl0 .. b_sl0 + b_nsl - 1 = rows b_row0 .. b_row0 + b_rows - 1
+    int b_sl0 = 0, b_nsl = 1, b_row0 = 0, b_rows = 0, b_nmb = 0;
+    size_t st_y = 0, st_c = 0, st_bitbuf_bytes = 0, st_au = 0, st_handoff = 0;  // per-item strides
+    hipStream_t stream = nullptr;
+    hipStream_t stream_ec = nullptr;         // entropy coding runs here, beside the deblocking wavefront (= stream when the process holds many engines)
+    std::atomic<int>* counted_live = nullptr;
+    enum { MAX_REFS = 3 };
+    int nrefs = 1, nbuf = 2;                 // reference frames searched (config.refs) and reconstruction buffers (nrefs + 1)
+    uint8_t* d_planes[MAX_REFS + 1][3] = {{nullptr}};  // ring: [index][plane]; `cur` is written, cur - 1 - r (mod nbuf) is ref_idx_l0 r
+    // the planes lie [batch item][ring slot]: d_planes[b][p] = d_plane_base[p] + b * st_ring, st_y / st_c (the item strides) = nbuf
+    // ring strides - so that an indirect launch (stream hub) can address every item's OWN ring slot from one base pointer
+    uint8_t* d_plane_base[3] = {nullptr, nullptr, nullptr};
+    size_t st_ring_y = 0, st_ring_c = 0;
+    QpEntry* d_qtab = nullptr;               // [52] quantiser constants by QP (indirect launches)
+    int nslots = NSLOT;                      // access-unit slots allocated (the hub's engine needs one)
+    uint8_t* d_pre[3] = {nullptr};           // copy of the reconstruction before the loop filter (debug)
+    PicSeq seq;                              // seq.cur: index written by the picture being encoded
+    bool pair_filter = true;                 // two macroblock rows per wave in the loop filter for lockstep batches of pair_min_batch pictures or more
+    int pair_min_batch = 8;                  // (MI355X_H264_PAIR_FILTER=N sets it, 0 turns the pair form off)
+    MbInfo* d_mb = nullptr;
+    int16_t* d_levels = nullptr;
+    int16_t* d_mvd = nullptr;
+    uint8_t* d_aux = nullptr;                // [G][nmb][16] Intra4x4 modes
+    int16_t* d_mvq = nullptr;                // [G][nmb][8] vectors of the four 8x8 quadrants of inter macroblocks
+    uint32_t* d_me_total = nullptr;          // [G][nmb] best motion cost so far over the reference pictures (k_me, one launch each)
+    int* d_pmv = nullptr;                    // [G][nmb] the previous picture's vectors, parked for the later launches
+    uint16_t* d_slotbits = nullptr;
+    unsigned long long* d_slotcode = nullptr;
+    uint32_t* d_mbbits = nullptr;
+    unsigned* d_anybs = nullptr;             // [G] picture serial when any boundary strength is non-zero
+    unsigned* d_anypcm = nullptr;            // [G] == pic_serial: the picture holds an I_PCM macroblock (not loop-filtered)
+    unsigned* d_anyintra = nullptr;          // [G] == pic_serial: P picture with macroblocks for the intra pass
+    unsigned pic_serial = 0;                 // changes every picture, never 0
+    int32_t* d_prevcoded = nullptr;          // [G][nmb + 1] skip-run helper (k_skip_scan)
+    unsigned long long* d_handoff = nullptr; // row-to-row hand-off of the wavefront kernels
+    uint32_t* d_bs = nullptr;                // boundary strengths, 32 B per macroblock
+    uint16_t* d_me_cost = nullptr;           // [G][nmb] per-macroblock motion cost (scene-change statistic)
+    std::vector<uint32_t> last_me_cost;      // of the last finished picture, per batch item
+    unsigned serial = 0;
+    bool diag_mode = false;                  // debug: one launch per wavefront step instead
+    uint8_t* d_stage = nullptr;              // device copy of a host-supplied picture
+    uint8_t* h_stage = nullptr;              // pinned staging for strided host input
+    uint8_t* d_rgba = nullptr, *h_rgba = nullptr;   // RGBA pictures on their way to the conversion kernel (allocated with the first)
+    uint8_t* d_inject_src = nullptr;         // mi355x_h264_debug_code_syntax: the batch items' source pictures (allocated with the first call)
+    size_t frame_bytes = 0, bitbuf_cap = 0, au_cap = 0;
+    Slot slots[NSLOT];
+    int next_slot = 0;
+    StreamShape shape{};                     // what the parameter sets and slice headers are written from
+    std::vector<uint8_t> sps_pps;            // Annex-B SPS + PPS NALs
+    DevMem mem;                              // every hipMalloc / hipHostMalloc of this engine
+    std::vector<std::vector<uint8_t>> esc_buf;  // slow path: escaped access unit, per batch item
+    int idr_step = 1;                        // idr_pic_id stride between the batch items
+    bool after_injected = false;             // the last picture came through mi355x_h264_debug_code_syntax
+    int qp = 26;
+    bool keep_pre = false, stats_on = false;
+    std::vector<hipEvent_t> ev_pool;
+    int me_turn = 0;                         // this engine's id at the GPU's motion-search lock (0: takes no part)
+    uint32_t p_intra_x16 = 0;                // intra macroblocks per P picture, recent pictures (x 16, a running mean): sizes k_pintra_rows' grid
+    mi355x_h264_stats stats{};
+    char err[256] = {0};
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// One motion search of a lockstep batch at a time per GPU.
+// Two instances beside each other are worth more than one because the dependency-bound kernels of one (loop filter, entropy
+// coding, row wavefronts) run in the issue slots the other's motion search leaves.  Left to themselves the instances settle in
+// whatever phase their first steps put them - search beside filter (good), or search beside search and filter beside filter (2 - 5 %
+// less, run by run: section 7 of DESIGN.md).  A lock word in device memory per GPU keeps the searches apart: a one-wave kernel in
+// front of a search takes it (compare-and-swap, sleeping between tries), a one-thread kernel behind the search gives it back.
+// Whoever comes first goes first - no order is imposed, so an engine in its IDR step, or gone, holds nobody up (an ORDER between the
+// engines' searches, by events or by counters, follows the order in which the host threads happened to queue them and left one
+// instance idle for 1.4 ms of every step) - and the holder's search is already queued behind its acquire, so the lock is always given
+// back; the wait gives up after TURN_TIMEOUT_US all the same.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void k_turn_acquire(unsigned* lock, unsigned id, int timeout_us)
+{
+    if (threadIdx.x) return;
+    const long long t0 = wall_clock64();   // 100 MHz
+    for (;;) {
+        unsigned expect = 0u;
+        if (__hip_atomic_compare_exchange_strong(lock, &expect, id, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if (wall_clock64() - t0 > (long long)timeout_us * 100) { __hip_atomic_store(lock, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+        __builtin_amdgcn_s_sleep(16);
+    }
+}
+__global__ void k_turn_release(unsigned* lock, unsigned id)
+{
+    unsigned expect = id;
+    (void)__hip_atomic_compare_exchange_strong(lock, &expect, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+namespace {
+enum { TURN_MIN_BATCH = 16, TURN_DEVICES = 16, TURN_TIMEOUT_US = 3000 };
+struct MeTurns {
+    std::mutex mu;
+    unsigned* d_lock[TURN_DEVICES] = {};   // allocated with the first engine of the device, kept for the life of the process
+    unsigned next_id = 1;
+};
+MeTurns g_turns;
+const bool g_turns_on = !(getenv("MI355X_H264_ME_TURNS") && atoi(getenv("MI355X_H264_ME_TURNS")) == 0);
+
+enum { PINTRA_SPARSE_MBS = 8 };   // intra macroblocks per P picture up to which k_pintra_rows takes the step's pictures one after the other
+}  // namespace
+
+namespace {
+
+int avail_refs(const mi355x_h264_encoder* e, bool idr) { return idr ? 0 : std::min(e->nrefs, e->seq.frame_in_gop); }
+inline bool mb_is_intra_host(int type) { return type == MB_I16 || type == MB_IPCM || type == MB_I4; }
+
+hipEvent_t get_event(mi355x_h264_encoder* e)
+{
+    if (!e->ev_pool.empty()) { hipEvent_t ev = e->ev_pool.back(); e->ev_pool.pop_back(); return ev; }
+    hipEvent_t ev = nullptr;
+    if (hipEventCreate(&ev) != hipSuccess) return nullptr;
+    return ev;
+}
+
+struct StatScope {
+    mi355x_h264_encoder* e; Slot* s; int k; uint32_t launches, mbs; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
+    StatScope(mi355x_h264_encoder* e_, Slot* s_, int k_, uint32_t l, uint32_t m, hipStream_t st_ = nullptr)
+        : e(e_), s(s_), k(k_), launches(l), mbs(m), st(st_ ? st_ : e_->stream)
+    {
+        if (e->stats_on) { a = get_event(e); b = get_event(e); if (a) (void)hipEventRecord(a, st); }
+    }
+    ~StatScope()
+    {
+        if (e->stats_on && a && b) { (void)hipEventRecord(b, st); s->evs.push_back({a, b, k, launches, mbs}); }
+    }
+};
+
+// ---- one lockstep step: which pictures, where from, on which streams ----
+// Direct (items == nullptr): the n = e->G batch items of the encoder, one QP, one ring position, consecutive idr_pic_ids - the
+// closed-GOP batch of mi355x_h264_encode_gops_device and the single-picture calls.  Indirect (the stream hub below): position k
+// of the grid is picture items[k] - its own batch item, ring slot, QP, frame_num and idr_pic_id; the kernels are the IND = true
+// instantiations and read d_itemtab, and the source picture of position k lies at d_srctab[k] (d_src is not used) - wherever that is: a
+// slot of the hub's staging array or the caller's own device memory.  A step holds pictures of ONE type (IDR or P): the two run
+// different kernels.
+// mi355x_h264_debug_code_syntax: the decisions of the step's pictures come from the host (arrays of n items) instead of the
+// decision and reconstruction kernels
+struct Injected { const void* mbinfo; const void* levels; const void* mvq; const void* mbaux; };
+struct Step {
+    const uint8_t* d_src = nullptr; size_t src_item_stride = 0; bool nv12 = false; bool idr = false;
+    int n = 1;
+    const ItemPic* items = nullptr;
+    const uint32_t* d_itemtab = nullptr;
+    const unsigned long long* d_srctab = nullptr;
+    const StepSync* sync = nullptr;   // streams, events and the time-out flag of the step
+    bool one_stream = false;          // entropy coding stays on sync->st
+    Slot* slot = nullptr;   // payload / access-unit buffers (laid out by batch item) and, with stats on, the event list
+    const Injected* inj = nullptr;   // test hook (direct steps only): upload these instead of deciding and reconstructing; no loop filter
+    AuLayout lay;   // out: where the access units lie in slot->h_au
+};
+
+#define LAUNCH2(ind, KT, KF, grid, block, stream, ...)                                   \
+    do {                                                                                 \
+        if (ind) hipLaunchKernelGGL(KT, grid, block, 0, stream, __VA_ARGS__);            \
+        else hipLaunchKernelGGL(KF, grid, block, 0, stream, __VA_ARGS__);                \
+    } while (0)
+
+// ---- the parameter blocks of the kernels, as far as they come from the engine alone (submit_step and the decoder's dec_submit
+// add what is theirs) ----
+inline unsigned next_nonzero(unsigned& serial) { serial = serial == 0xFFFFFFFFu ? 1u : serial + 1u; return serial; }   // changes every time, never 0
+
+FrameParams frame_params(mi355x_h264_encoder* e)   // takes the next picture serial
+{
+    FrameParams P{};
+    P.cw = e->cw; P.ch = e->ch; P.mbw = e->mbw; P.mbh = e->mbh;
+    P.mb = e->d_mb; P.levels = e->d_levels; P.mvd = e->d_mvd; P.mvq = e->d_mvq; P.aux = e->d_aux; P.me_cost = e->d_me_cost; P.me_total = e->d_me_total; P.pmv = e->d_pmv;
+    P.st_y = e->st_y; P.st_c = e->st_c; P.st_mb = e->nmb;
+    P.mbdiv.inv = recip32(e->mbw);
+    P.anypcm = e->d_anypcm; P.anyintra = e->d_anyintra; P.pic_serial = next_nonzero(e->pic_serial);
+    return P;
+}
+IntraRowParams intra_row_params(mi355x_h264_encoder* e, const FrameParams& P, unsigned* h_err, int npic)   // takes the next wavefront serial
+{
+    IntraRowParams R{};
+    R.p = P; R.handoff = e->d_handoff; R.st_handoff = e->st_handoff; R.err = h_err;
+    R.serial = next_nonzero(e->serial);
+    R.npic = npic;
+    return R;
+}
+// pl: the planes being filtered (or their base: indirect launches); qp: the picture's (thresholds of every edge unless the launch reads mbqp)
+DbParams db_params(const mi355x_h264_encoder* e, uint8_t* const pl[3], const SliceRows& sl, int qp)
+{
+    DbParams D{};
+    for (int p = 0; p < 3; p++) D.pl[p] = pl[p];
+    D.mb = e->d_mb; D.cw = e->cw; D.ch = e->ch; D.mbw = e->mbw; D.mbh = e->mbh; D.sl = sl; D.bs = (const uint8_t*)e->d_bs;
+    fill_filter_thresholds(D, qp);
+    return D;
+}
+DbRowParams db_row_params(const mi355x_h264_encoder* e, const DbParams& D, unsigned* h_err, unsigned serial, unsigned pic_serial, int row0, int npic)
+{
+    DbRowParams R{};
+    R.d = D; R.handoff = e->d_handoff; R.err = h_err;
+    R.st_y = e->st_y; R.st_c = e->st_c; R.st_handoff = e->st_handoff; R.st_mb = e->nmb;
+    R.serial = serial; R.row0 = row0;
+    R.bs = e->d_bs; R.anybs = e->d_anybs;
+    R.anypcm = e->d_anypcm; R.anyintra = e->d_anyintra; R.pic_serial = pic_serial;
+    R.npic = npic;
+    return R;
+}
+
+int submit_step(mi355x_h264_encoder* e, Step& T)
+{
+    Slot& S = *T.slot;
+    const bool idr = T.idr, ind = T.items != nullptr;
+    const int cur = e->seq.cur;
+    FrameParams P = frame_params(e);
+    P.src = T.d_src; P.src_nv12 = T.nv12 ? 1 : 0; P.w = e->cfg.width; P.h = e->cfg.height;
+    P.nref = ind ? 1 : std::max(1, avail_refs(e, idr));
+    for (int p = 0; p < 3; p++) {
+        P.rec[p] = ind ? e->d_plane_base[p] : e->d_planes[cur][p];
+        for (int r = 0; r < mi355x_h264_encoder::MAX_REFS; r++) P.refs[r][p] = e->d_planes[(cur + e->nbuf - 1 - std::min(r, e->nrefs - 1)) % e->nbuf][p];
+        P.ref[p] = P.refs[0][p];
+    }
+    P.itemtab = T.d_itemtab; P.srctab = T.d_srctab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
+    P.st_src = T.src_item_stride; P.sl = e->sl;
+    P.band.row0 = e->b_row0; P.band.rows = e->b_rows;
+    const unsigned pic_serial = P.pic_serial;
+    const unsigned G = (unsigned)T.n;
+    fill_qp(P.qy, P.qc, P.lambda, P.sad_nz, e->qp);   // (indirect launches take these from qtab by the item's own QP)
+    P.search = e->cfg.search;
+    const StepSync& Y = *T.sync;
+    hipStream_t st = Y.st;
+
+    // (the payload buffers of the items were left zeroed by the k_pack of their previous use)
+
+    if (T.inj) {
+        // the arrays k_i4_decide / k_intra_rows / k_me / k_tq / k_pintra_rows would have left, and the flags they would have raised
+        const size_t n = (size_t)T.n * e->nmb;
+        HIPCHK(e->err, hipMemcpyAsync(e->d_mb, T.inj->mbinfo, n * sizeof(MbInfo), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemcpyAsync(e->d_levels, T.inj->levels, n * LV_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemcpyAsync(e->d_mvq, T.inj->mvq, n * 8 * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemcpyAsync(e->d_aux, T.inj->mbaux, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemsetAsync(e->d_me_cost, 0, n * sizeof(uint16_t), st));
+        unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {};
+        const MbInfo* m = (const MbInfo*)T.inj->mbinfo;
+        for (int g = 0; g < T.n; g++)
+            for (int i = 0; i < e->nmb; i++) {
+                const int type = m[(size_t)g * e->nmb + i].type;
+                if (type == MB_IPCM) anypcm[g] = pic_serial;
+                if (!idr && mb_is_intra_host(type)) anyintra[g] = pic_serial;
+            }
+        HIPCHK(e->err, hipMemcpyAsync(e->d_anypcm, anypcm, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemcpyAsync(e->d_anyintra, anyintra, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipStreamSynchronize(st));   // (the flag arrays live on this stack)
+    } else if (idr) {
+        StatScope sc(e, &S, MI355X_H264_K_INTRA, (uint32_t)(e->diag_mode ? e->mbw + e->mbh - 1 : 1), (uint32_t)(e->b_nmb * T.n), st);
+        LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3((e->b_nmb + 3) / 4, G), dim3(64), st, P, 0);   // Intra4x4 or Intra16x16, and the block modes: from the source alone
+        if (e->diag_mode && !ind) {
+            for (int s = 0; s < e->mbw + e->mbh - 1; s++) {
+                const int ymin = std::max(0, s - e->mbw + 1), ymax = std::min(e->mbh - 1, s);
+                hipLaunchKernelGGL(k_intra_diag, dim3(ymax - ymin + 1, G), dim3(64), 0, st, P, s);
+            }
+        } else {
+            const IntraRowParams R = intra_row_params(e, P, Y.h_err, (int)G);
+            {   // MI355X_H264_INTRA_SLOTS: pictures the row wavefront holds at a time (k_intra_rows)
+                static const int slots = getenv("MI355X_H264_INTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_INTRA_SLOTS"))) : 24;
+                LAUNCH2(ind, k_intra_rows<true>, k_intra_rows<false>, dim3(e->b_rows, std::min(G, (unsigned)slots)), dim3(128), st, R);
+            }
+        }
+    } else {
+        { const bool turns = g_turns_on && !ind && e->me_turn > 0 && T.n >= TURN_MIN_BATCH;
+          if (turns) hipLaunchKernelGGL(k_turn_acquire, dim3(1), dim3(64), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn, (int)TURN_TIMEOUT_US);
+          { StatScope sc(e, &S, MI355X_H264_K_ME, (uint32_t)P.nref, (uint32_t)(e->b_nmb * T.n), st);
+            FrameParams Q = P;   // one launch per reference picture (config.refs): Q.ref = the planes of ref_idx_l0 = Q.rf
+            Q.rf_last = P.nref - 1;
+            for (int r = 0; r < P.nref; r++) {
+                Q.rf = r;
+                for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
+                LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, G), dim3(64), st, Q);
+            } }
+          if (turns) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
+        }
+        { StatScope sc(e, &S, MI355X_H264_K_PMB, 1, (uint32_t)(e->b_nmb * T.n), st);
+          if (e->cfg.profile_idc == 100) LAUNCH2(ind, k_tq8<true>, k_tq8<false>, dim3((e->b_nmb + 15) / 16, G), dim3(64), st, P);   // High: 8x8 transform, sixteen macroblocks per wave
+          else LAUNCH2(ind, k_tq<true>, k_tq<false>, dim3((e->b_nmb + 7) / 8, G), dim3(64), st, P); }   // one wave per eight macroblocks
+        {   // macroblocks the motion search handed to the intra pass (returns at once when there are none)
+            const IntraRowParams R = intra_row_params(e, P, Y.h_err, (int)G);
+            // Their grids hold ONE picture at a time (the workgroups walk the step's pictures) while the recent P pictures had next to
+            // no intra macroblocks, all of them once they have: see k_pintra_rows.  MI355X_H264_PINTRA_SLOTS fixes the number.
+            static const int pslots_env = getenv("MI355X_H264_PINTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_PINTRA_SLOTS"))) : 0;
+            const unsigned pslots = std::min(G, pslots_env ? (unsigned)pslots_env : (e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u));
+            LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3(std::min((e->b_nmb + 3) / 4, (int)I4_MARKED_WAVES), pslots), dim3(64), st, P, (int)G);
+            LAUNCH2(ind, (k_pintra_rows<false, true>), (k_pintra_rows<false, false>), dim3(e->b_rows, pslots), dim3(64), st, R);
+        }
+    }
+    // entropy coding: slice headers per position
+    HdrBatch H{}, Hpcm{};
+    for (int g = 0; g < T.n; g++) {
+        uint64_t hdr = 0;
+        const int fn = ind ? T.items[g].frame_num : e->seq.frame_num, qp = ind ? T.items[g].qp : e->qp;
+        const int id = ind ? T.items[g].idr_id : ((e->seq.idr_id + g * e->idr_step) & 0xFF);
+        const int nact = ind ? (idr ? 0 : 1) : avail_refs(e, idr);
+        H.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, false, fn, qp, nact, &hdr);
+        H.bits[g] = hdr;
+        Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, true, fn, qp, nact, &hdr);
+        Hpcm.bits[g] = hdr;
+    }
+    // entropy coding needs only levels / MbInfo, the loop filter the reconstruction and the boundary strengths
+    // (a small launch of its own on this stream): the two run side by side and the filter never waits for the coder
+    hipStream_t ec = T.one_stream ? st : Y.ec;
+    CavlcParams C{};
+    C.mb = e->d_mb; C.levels = e->d_levels; C.mvd = e->d_mvd; C.mbw = e->mbw; C.nmb = e->nmb; C.p_slice = idr ? 0 : 1; C.t8x8 = e->cfg.profile_idc == 100 ? 1 : 0;
+    C.nref = ind ? (idr ? 0 : 1) : avail_refs(e, idr); C.sl = e->sl;
+    C.mb_first = e->b_row0 * e->mbw; C.mb_end = C.mb_first + e->b_nmb;
+    C.slice_cap = (unsigned)e->slice_cap;
+    C.mbdiv = P.mbdiv;
+    C.slotbits = e->d_slotbits; C.slotcode = e->d_slotcode; C.mbbits = e->d_mbbits; C.bitbuf = S.d_bitbuf;
+    C.bs = (uint8_t*)e->d_bs; C.prevcoded = e->d_prevcoded;
+    C.st_mb = e->nmb; C.st_bitbuf = e->st_bitbuf_bytes / 4;
+    C.aux = e->d_aux; C.mvq = e->d_mvq;
+    C.src = T.d_src; C.w = e->cfg.width; C.h = e->cfg.height; C.src_nv12 = T.nv12 ? 1 : 0; C.st_src = T.src_item_stride;
+    C.itemtab = T.d_itemtab; C.srctab = T.d_srctab;
+    const int cavlc_grid = (e->b_nmb + 1) / 2;
+    unsigned db_serial = 0;
+    if (!e->cfg.disable_deblock) {   // (the diagonal debug form of the filter reads the strengths too)
+        db_serial = next_nonzero(e->serial);   // the serial the loop filter of this picture will run under
+        LAUNCH2(ind, k_bs<true>, k_bs<false>, dim3(std::min(cavlc_grid, (int)BS_WAVES), G), dim3(64), st, C, e->d_anybs, db_serial);
+    }
+    const bool fork = ec != st;
+    if (fork) {
+        HIPCHK(e->err, hipEventRecord(Y.recon_ready, st));
+        HIPCHK(e->err, hipStreamWaitEvent(ec, Y.recon_ready, 0));
+    }
+    {
+        StatScope sc(e, &S, MI355X_H264_K_CAVLC, 4, (uint32_t)(e->b_nmb * T.n), ec);
+        const int grid = cavlc_grid;
+        if (!idr) {
+            LAUNCH2(ind, k_mvpred<true>, k_mvpred<false>, dim3((e->b_nmb + 63) / 64, G), dim3(64), ec, P);   // vectors + coded_block_pattern are final: mvd, P_Skip
+            LAUNCH2(ind, k_skip_scan<true>, k_skip_scan<false>, dim3(G), dim3(256), ec, C);
+        }
+        LAUNCH2(ind, (k_cavlc<false, true>), (k_cavlc<false, false>), dim3(grid, G), dim3(64), ec, C);
+        LAUNCH2(ind, k_bit_scan<true>, k_bit_scan<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, C, H, Hpcm, (const unsigned*)e->d_anypcm, pic_serial, S.d_info, e->d_me_cost,
+                e->b_nsl, e->b_sl0, (unsigned)e->slice_cap);
+        LAUNCH2(ind, (k_cavlc<true, true>), (k_cavlc<true, false>), dim3(grid, G), dim3(64), ec, C);
+        // access unit layout in the pinned buffer: [pad][SPS PPS (IDR only)][00 00 00 01 hdr][payload...];
+        // with several slices: the payload of slice s at s * slice_cap, the access unit is put together by finish_item
+        const size_t pre = (idr ? e->sps_pps.size() : 0) + 5;
+        const size_t pad = (16 - (pre & 15)) & 15;
+        T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr, idr ? ((3 << 5) | 5) : ((2 << 5) | 1)};
+        LAUNCH2(ind, k_pack<true>, k_pack<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, (uint8_t*)S.d_bitbuf, e->st_bitbuf_bytes, S.h_au + T.lay.payload_off, e->st_au,
+                (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
+    }
+    if (fork) HIPCHK(e->err, hipEventRecord(Y.entropy_done, ec));
+    if (e->keep_pre && !ind && !T.inj)
+        for (int p = 0; p < 3; p++) {   // (the items' planes lie nbuf ring slots apart: one row of the 2-D copy per item)
+            const size_t ring = p ? e->st_ring_c : e->st_ring_y;
+            HIPCHK(e->err, hipMemcpy2DAsync(e->d_pre[p], ring, e->d_planes[cur][p], p ? e->st_c : e->st_y, ring, (size_t)e->G, hipMemcpyDeviceToDevice, st));
+        }
+    if (!e->cfg.disable_deblock && !T.inj) {
+        const int steps = e->mbw + 2 * (e->mbh - 1);
+        StatScope sc(e, &S, MI355X_H264_K_DEBLOCK, (uint32_t)(e->diag_mode ? steps : 1), (uint32_t)(e->b_nmb * T.n), st);
+        const DbParams D = db_params(e, ind ? e->d_plane_base : e->d_planes[cur], e->sl, e->qp);   // (indirect launches look the item's own QP up on the device)
+        if (e->diag_mode && !ind) {
+            for (int s = 0; s < steps; s++) {
+                const int ymin = std::max(0, (s - (e->mbw - 1) + 1) >> 1), ymax = std::min(e->mbh - 1, s >> 1);
+                if (ymax < ymin) continue;
+                hipLaunchKernelGGL(k_deblock_diag, dim3(ymax - ymin + 1), dim3(64), 0, st, D, s);
+            }
+        } else {
+            DbRowParams R = db_row_params(e, D, Y.h_err, db_serial, pic_serial, e->b_row0, (int)G);
+            R.itemtab = T.d_itemtab; R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c;
+            // two macroblock rows per wave (k_deblock_pairs) for lockstep batches of pictures of one slice; else one row per wave
+            const bool pairs = e->pair_filter && T.n >= e->pair_min_batch && e->nsl == 1 && e->b_rows == e->mbh;
+            const unsigned grid_x = pairs ? (unsigned)((e->b_rows + 1) / 2) : (unsigned)e->b_rows;
+            auto filter = [&](bool bs4, unsigned at_a_time) {
+                const dim3 grid(grid_x, std::min(G, at_a_time));
+                if (pairs) { if (bs4) LAUNCH2(ind, (k_deblock_pairs<true, true>), (k_deblock_pairs<true, false>), grid, dim3(64), st, R);
+                             else LAUNCH2(ind, (k_deblock_pairs<false, true>), (k_deblock_pairs<false, false>), grid, dim3(64), st, R); }
+                else { if (bs4) LAUNCH2(ind, (k_deblock_rows<true, false, true>), (k_deblock_rows<true, false, false>), grid, dim3(64), st, R);
+                       else LAUNCH2(ind, (k_deblock_rows<false, false, true>), (k_deblock_rows<false, false, false>), grid, dim3(64), st, R); }
+            };
+            if (idr) { R.need_intra = 0; filter(true, G); }
+            else {   // P pictures: the form without the bS 4 filter, or - when the picture has intra macroblocks - the one with it
+                // (while the recent P pictures had next to none, the second launch holds one picture at a time: see k_deblock_rows)
+                R.need_intra = -1; filter(false, G);
+                R.need_intra = 1; filter(true, e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u);
+            }
+        }
+    }
+    if (fork) HIPCHK(e->err, hipStreamWaitEvent(st, Y.entropy_done, 0));   // join: the next picture rewrites MbInfo / levels
+    HIPCHK(e->err, hipEventRecord(Y.done, st));
+    HIPCHK(e->err, hipGetLastError());
+    return MI355X_H264_OK;
+}
+
+// enqueue everything for one picture (every batch item's) whose I420 samples are at d_src: the direct form
+int submit(mi355x_h264_encoder* e, const uint8_t* d_src, size_t src_item_stride, int slot_idx, bool nv12, const Injected* inj = nullptr)
+{
+    Slot& S = e->slots[slot_idx];
+    // (after an injected picture, mi355x_h264_debug_code_syntax, nothing was reconstructed: a real picture has no reference then)
+    const bool idr = e->seq.next_is_idr(e->cfg.gop) || (e->after_injected && !inj);
+    e->seq.begin(idr);
+    e->after_injected = inj != nullptr;
+    Step T;
+    T.d_src = d_src; T.src_item_stride = src_item_stride; T.nv12 = nv12; T.idr = idr; T.n = e->G;
+    T.sync = &S.sync;
+    T.slot = &S;
+    T.inj = inj;
+    const int rc = submit_step(e, T);
+    if (rc) return rc;
+    S.lay = T.lay;
+    S.busy = true;
+    e->seq.advance(idr, e->nbuf, e->idr_step * e->G);   // bookkeeping for the next picture
+    return MI355X_H264_OK;
+}
+
+// wait for a slot (all batch items of one lockstep picture); stats are folded in once
+int wait_slot(mi355x_h264_encoder* e, int slot_idx)
+{
+    Slot& S = e->slots[slot_idx];
+    if (!S.busy) return set_err(e->err, MI355X_H264_E_INTERNAL, "collect on an idle slot");
+    HIPCHK(e->err, hipEventSynchronize(S.sync.done));
+    S.busy = false;
+    for (auto& ev : S.evs) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
+            e->stats.ms[ev.k] += ms; e->stats.launches[ev.k] += ev.launches; e->stats.mbs[ev.k] += ev.mbs;
+        }
+        e->ev_pool.push_back(ev.a); e->ev_pool.push_back(ev.b);
+    }
+    S.evs.clear();
+    e->stats.frames += (uint64_t)e->G;
+    const int rc = handoff_timeout(S.sync, e->err);
+    if (rc) e->seq.force_idr = 1;   // the picture's reconstruction is not to be trusted: it must not become a reference
+    return rc;
+}
+
+// finish the access unit of batch item g on the host: S = the buffers it was written to, L = where and of which type
+int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    uint8_t* base = S.h_au + (size_t)g * e->st_au;
+    const SliceInfo* const info = S.h_info + (size_t)g * e->b_nsl;   // one per slice of this instance's band
+    for (int sl = 0; sl < e->b_nsl; sl++)
+        if (info[sl].error) {
+            e->seq.force_idr = 1;   // the refused picture is missing from the stream: the next one must not refer to it
+            const int code = info[sl].error == 1 ? MI355X_H264_E_OVERFLOW : MI355X_H264_E_INTERNAL;
+            if (e->nsl > 1) return set_err(e->err, code, "device reported error %u (slice %d)", info[sl].error, sl);
+            return set_err(e->err, code, "device reported error %u", info[sl].error);
+        }
+    // what the picture tells the statistics, the scene-change measure and the sizing of the next P pictures' intra pass
+    uint32_t cost = 0, searched = 0, tq_coded = 0;
+    size_t need = e->sps_pps.size() + 16;
+    for (int sl = 0; sl < e->b_nsl; sl++) {
+        cost += info[sl].me_cost; searched += info[sl].searched; tq_coded += info[sl].tq_coded;
+        need += 5 + (size_t)info[sl].total_bytes * 3 / 2 + 16;
+    }
+    e->last_me_cost[g] = cost;
+    if (!L.idr) {
+        e->stats.p_mbs += (uint64_t)e->b_nmb; e->stats.me_searched_mbs += searched; e->stats.tq_coded_mbs += tq_coded;
+        e->p_intra_x16 = (3 * e->p_intra_x16 + 16 * (searched - tq_coded)) / 4;
+    }
+    if (frame_type) *frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
+    std::vector<uint8_t>& eb = e->esc_buf[g];
+    if (e->nsl > 1) {
+        // several slices: one NAL unit each, put together here (the payloads lie slice_cap apart in the pinned buffer)
+        eb.resize(need);
+        size_t pos = 0;
+        if (L.idr && e->b_sl0 == 0) { memcpy(eb.data(), e->sps_pps.data(), e->sps_pps.size()); pos = e->sps_pps.size(); }   // parameter sets go with the first band
+        for (int sl = 0; sl < e->b_nsl; sl++) {
+            const SliceInfo& si = info[sl];
+            const uint8_t* pay = base + (size_t)(e->b_sl0 + sl) * e->slice_cap;
+            uint8_t* o = eb.data() + pos;
+            o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 1; o[4] = (uint8_t)L.nal_hdr;
+            pos += 5;
+            if (si.epb_count == 0) { memcpy(eb.data() + pos, pay, si.total_bytes); pos += si.total_bytes; }
+            else pos += nal_escape(pay, si.total_bytes, eb.data() + pos);
+        }
+        *out = eb.data();
+        *out_len = (uint32_t)pos;
+        return MI355X_H264_OK;
+    }
+    // one slice: the kernels wrote the payload behind the room left for parameter sets and NAL header
+    uint8_t* au = base + L.au_start;
+    size_t pos = 0;
+    if (L.idr) { memcpy(au, e->sps_pps.data(), e->sps_pps.size()); pos = e->sps_pps.size(); }
+    au[pos++] = 0; au[pos++] = 0; au[pos++] = 0; au[pos++] = 1; au[pos++] = (uint8_t)L.nal_hdr;
+    if (info->epb_count == 0) {
+        *out = au;
+        *out_len = (uint32_t)(pos + info->total_bytes);
+    } else {  // rare: some 00 00 0x pattern needs an emulation prevention byte
+        eb.resize(pos + (size_t)info->total_bytes * 3 / 2 + 16);
+        memcpy(eb.data(), au, pos);
+        const size_t n = nal_escape(base + L.payload_off, info->total_bytes, eb.data() + pos);
+        *out = eb.data();
+        *out_len = (uint32_t)(pos + n);
+    }
+    return MI355X_H264_OK;
+}
+
+int collect(mi355x_h264_encoder* e, int slot_idx, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    const int rc = wait_slot(e, slot_idx);
+    return rc ? rc : finish_item(e, e->slots[slot_idx], e->slots[slot_idx].lay, 0, out, out_len, frame_type);
+}
+
+void destroy_engine(mi355x_h264_encoder* e)
+{
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    if (e->stream_ec && e->stream_ec != e->stream) (void)hipStreamSynchronize(e->stream_ec);
+    e->mem.free_all();
+    for (auto& S : e->slots) {
+        sync_destroy(S.sync);
+        for (auto& ev : S.evs) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
+    }
+    for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
+    if (e->stream_ec && e->stream_ec != e->stream) (void)hipStreamDestroy(e->stream_ec);
+    if (e->counted_live) e->counted_live->fetch_sub(1);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+}
+
+// streams, device and pinned memory of a configured engine
+hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
+{
+    DevMem& M = e->mem;
+    HIPTRY(hipSetDevice(e->device));
+    HIPTRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    // Entropy coding normally runs on a stream of its own beside the loop filter (shorter picture latency).  A process that
+    // holds many engines (the plugin surface with many streams: one engine per VideoEncoder object) would then ask for more
+    // hardware queues than the device has, and the runtime's multiplexing costs more than the overlap gains (16 plugin streams: 3.8 k -> 6.0 k fps; 4 streams: p99 8 -> 4 ms): from the third
+    // live engine on (or with MI355X_H264_ONE_STREAM=1) an engine uses its one stream for everything.
+    {
+        static std::atomic<int> live{0};
+        const char* one = getenv("MI355X_H264_ONE_STREAM");
+        const int n = live.fetch_add(1) + 1;
+        e->counted_live = &live;
+        if ((one && one[0] == '1') || (n > 2 && !(one && one[0] == '0'))) e->stream_ec = e->stream;
+        else HIPTRY(hipStreamCreateWithFlags(&e->stream_ec, hipStreamNonBlocking));
+    }
+    const size_t ysz = (size_t)e->cw * e->ch;
+    const size_t Gn = (size_t)e->G, nmb = Gn * e->nmb;   // (nmb: macroblocks of all batch items)
+    e->st_ring_y = ysz + 256; e->st_ring_c = ysz / 4 + 256;
+    e->st_y = e->st_ring_y * e->nbuf; e->st_c = e->st_ring_c * e->nbuf;
+    for (int p = 0; p < 3; p++) {
+        HIPTRY(M.dev(&e->d_plane_base[p], (p ? e->st_c : e->st_y) * Gn, true));
+        for (int b = 0; b < e->nbuf; b++) e->d_planes[b][p] = e->d_plane_base[p] + (size_t)b * (p ? e->st_ring_c : e->st_ring_y);
+    }
+    for (int p = 0; p < 3; p++) HIPTRY(M.dev(&e->d_pre[p], (p ? e->st_ring_c : e->st_ring_y) * Gn));
+    {
+        std::vector<QpEntry> qt(52);
+        for (int q = 0; q < 52; q++) fill_qp(qt[q].qy, qt[q].qc, qt[q].lambda, qt[q].sad_nz, q);
+        HIPTRY(M.dev(&e->d_qtab, 52 * sizeof(QpEntry)));
+        HIPTRY(hipMemcpy(e->d_qtab, qt.data(), 52 * sizeof(QpEntry), hipMemcpyHostToDevice));
+    }
+    HIPTRY(M.dev(&e->d_mb, nmb * sizeof(MbInfo), true));
+    HIPTRY(M.dev(&e->d_levels, nmb * LV_STRIDE * sizeof(int16_t)));
+    HIPTRY(M.dev(&e->d_mvd, nmb * 8 * sizeof(int16_t)));
+    HIPTRY(M.dev(&e->d_mvq, nmb * 8 * sizeof(int16_t), true));
+    HIPTRY(M.dev(&e->d_me_total, nmb * sizeof(uint32_t)));
+    HIPTRY(M.dev(&e->d_pmv, nmb * sizeof(int)));
+    HIPTRY(M.dev(&e->d_aux, nmb * 16, true));
+    HIPTRY(M.dev(&e->d_slotbits, nmb * 32 * sizeof(uint16_t)));
+    HIPTRY(M.dev(&e->d_slotcode, nmb * 32 * sizeof(unsigned long long)));
+    HIPTRY(M.dev(&e->d_mbbits, nmb * sizeof(uint32_t)));
+    for (unsigned** flag : {&e->d_anybs, &e->d_anypcm, &e->d_anyintra}) HIPTRY(M.dev(flag, Gn * sizeof(unsigned), true));
+    HIPTRY(M.dev(&e->d_prevcoded, Gn * (e->nmb + 1) * sizeof(int32_t)));
+    e->st_handoff = (size_t)e->nmb * 24;
+    HIPTRY(M.dev(&e->d_handoff, Gn * e->st_handoff * sizeof(unsigned long long), true));
+    HIPTRY(M.dev(&e->d_bs, nmb * 32));
+    HIPTRY(M.dev(&e->d_me_cost, nmb * sizeof(uint16_t), true));
+    e->frame_bytes = (size_t)e->cfg.width * e->cfg.height * 3 / 2;
+    HIPTRY(M.dev(&e->d_stage, e->frame_bytes + 256));
+    HIPTRY(M.pinned(&e->h_stage, e->frame_bytes + 256));
+    e->bitbuf_cap = ysz * 2 + (1 << 16);
+    e->slice_cap = e->bitbuf_cap;
+    if (e->nsl > 1) {   // every slice gets room for twice its luma bytes (CAVLC's worst case is about 1.6 times)
+        e->slice_cap = ((size_t)e->sl.rows * 256 * e->mbw * 2 + 4096 + 15) & ~(size_t)15;
+        e->bitbuf_cap = e->slice_cap * e->nsl;
+    }
+    e->st_bitbuf_bytes = (e->bitbuf_cap + 256 + 255) & ~(size_t)255;
+    e->au_cap = e->bitbuf_cap + e->sps_pps.size() + 64;
+    e->st_au = (e->au_cap + 256 + 255) & ~(size_t)255;
+    e->nslots = hub_engine ? 1 : NSLOT;
+    if (!hub_engine && e->G >= TURN_MIN_BATCH && e->device >= 0 && e->device < TURN_DEVICES) {   // takes part in the turn-taking of the motion searches
+        std::lock_guard<std::mutex> tl(g_turns.mu);
+        if (!g_turns.d_lock[e->device]) {
+            HIPTRY(hipMalloc((void**)&g_turns.d_lock[e->device], sizeof(unsigned)));
+            HIPTRY(hipMemset(g_turns.d_lock[e->device], 0, sizeof(unsigned)));
+        }
+        e->me_turn = (int)g_turns.next_id++;
+    }
+    for (int si = 0; si < e->nslots; si++) {
+        Slot& S = e->slots[si];
+        HIPTRY(M.dev(&S.d_bitbuf, e->st_bitbuf_bytes * Gn, true));
+        HIPTRY(M.dev(&S.d_info, sizeof(SliceInfo) * Gn * e->nsl));
+        HIPTRY(M.pinned(&S.h_info, sizeof(SliceInfo) * Gn * e->nsl));
+        HIPTRY(M.pinned(&S.h_au, e->st_au * Gn));
+        HIPTRY(sync_create(S.sync, e->stream, e->stream_ec, false));
+    }
+    HIPTRY(hipDeviceSynchronize());
+    return hipSuccess;
+}
+
+// hub_engine: the engine of a stream hub (hub.h) - one set of output buffers instead of NSLOT, never more than one HIP stream
+// pair of its own (the hub's step contexts bring theirs)
+int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool hub_engine)
+{
+    if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
+    {   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): an engine has two streams, a stream hub seven, and
+        // a host process runs several.  Ask for more before the runtime comes up - unless the host has chosen (measured: 64
+        // plugin streams 7.4 k fps on 4 queues, 10.4 k on 32).  Has no effect once another HIP user has initialised the runtime.
+        static std::once_flag once;
+        std::call_once(once, [] { setenv("GPU_MAX_HW_QUEUES", "16", 0); });
+    }
+    *out = nullptr;
+    if (cfg->width < 16 || cfg->height < 16 || cfg->width > 4096 || cfg->height > 4096 || ((cfg->width | cfg->height) & 1) ||
+        cfg->qp < 10 || cfg->qp > 51 || cfg->gop < 1 || (cfg->profile_idc != 66 && cfg->profile_idc != 77 && cfg->profile_idc != 100) ||
+        (cfg->input_format != MI355X_H264_INPUT_I420 && cfg->input_format != MI355X_H264_INPUT_NV12) || cfg->slices < 0 || cfg->slices > 64 ||
+        cfg->refs < 0 || cfg->refs > mi355x_h264_encoder::MAX_REFS || (cfg->search != MI355X_H264_SEARCH_EXHAUSTIVE && cfg->search != MI355X_H264_SEARCH_SEEDED))
+        return MI355X_H264_E_ARG;
+    if (cfg->band_count < 0 || cfg->band_index < 0 || (cfg->band_count > 1 && (cfg->band_index >= cfg->band_count || cfg->batch > 1))) return MI355X_H264_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return MI355X_H264_E_NODEVICE;
+    mi355x_h264_encoder* e = new (std::nothrow) mi355x_h264_encoder();
+    if (!e) return MI355X_H264_E_NOMEM;
+    e->cfg = *cfg;
+    e->device = cfg->device;
+    e->qp = cfg->qp;
+    e->mbw = (cfg->width + 15) / 16; e->mbh = (cfg->height + 15) / 16;
+    e->cw = e->mbw * 16; e->ch = e->mbh * 16; e->nmb = e->mbw * e->mbh;
+    e->level_idc = std::max(32, pick_level(e->nmb, cfg->fps > 0 ? cfg->fps : 30));
+    {   // slices: bands of ceil(rows / slices) macroblock rows, at least two rows each
+        const int n = std::min(std::max(cfg->slices, 1), std::max(1, e->mbh / 2));
+        e->sl.rows = (e->mbh + n - 1) / n;
+        e->sl.inv = recip32(e->sl.rows);   // (one row: my is always 0)
+        e->nsl = (e->mbh + e->sl.rows - 1) / e->sl.rows;
+    }
+    e->b_sl0 = 0; e->b_nsl = e->nsl;
+    if (cfg->band_count > 1) {   // this instance codes its share of the slices; the others belong to the neighbours
+        if (cfg->band_count > e->nsl) { delete e; return MI355X_H264_E_ARG; }
+        e->b_sl0 = (int)((long)cfg->band_index * e->nsl / cfg->band_count);
+        e->b_nsl = (int)((long)(cfg->band_index + 1) * e->nsl / cfg->band_count) - e->b_sl0;
+    }
+    e->b_row0 = e->b_sl0 * e->sl.rows;
+    e->b_rows = std::min(e->mbh, (e->b_sl0 + e->b_nsl) * e->sl.rows) - e->b_row0;
+    e->b_nmb = e->b_rows * e->mbw;
+    e->nrefs = cfg->refs > 1 ? cfg->refs : 1;
+    e->nbuf = e->nrefs + 1;
+    e->G = cfg->batch > 1 ? cfg->batch : 1;
+    if (e->G > MAX_BATCH) { delete e; return MI355X_H264_E_ARG; }
+    e->esc_buf.resize((size_t)e->G);
+    e->last_me_cost.assign((size_t)e->G, 0);
+    e->shape = StreamShape{cfg->profile_idc, e->level_idc, e->nrefs, e->mbw, e->mbh, cfg->width, cfg->height, e->nsl, cfg->disable_deblock};
+    e->sps_pps = build_parameter_sets(e->shape);
+    e->diag_mode = getenv("MI355X_H264_DIAG") != nullptr && e->G == 1 && e->b_nsl == e->nsl;
+    {
+        // The loop filter takes two macroblock rows per wave (k_deblock_pairs) from a lockstep batch of 8 pictures on (pictures of one
+        // slice): measured on the bench workload with the filter's edge skip in place, same box, row form / pair form: batch 4
+        // 8 837 / 8 851 fps, batch 8 15.0 / 15.3 k, batch 16 21.2 / 22.1 k, batch 32 24.0 / 25.0 k; one GOP in flight 1 230 / 1 209 fps -
+        // so small batches and the latency mode keep one row per wave.  MI355X_H264_PAIR_FILTER=N moves the threshold, 0 turns the
+        // pair form off.
+        const char* pf = getenv("MI355X_H264_PAIR_FILTER");
+        e->pair_filter = !(pf && pf[0] == '0');
+        e->pair_min_batch = (pf && pf[0] >= '1' && pf[0] <= '9') ? atoi(pf) : 8;
+    }
+    const hipError_t r = engine_alloc(e, hub_engine);
+    if (r != hipSuccess) {
+        fprintf(stderr, "mi355x_h264_create: %s: %s\n", t_failed_call, hipGetErrorString(r));
+        destroy_engine(e);
+        return r == hipErrorOutOfMemory ? MI355X_H264_E_NOMEM : MI355X_H264_E_HIP;
+    }
+    *out = e;
+    return MI355X_H264_OK;
+}
+
+int take_slot(mi355x_h264_encoder* e) { const int slot = e->next_slot; e->next_slot = (slot + 1) % NSLOT; return slot; }
+
+// one picture already in device memory, in the given layout
+int encode_one_device(mi355x_h264_encoder* e, const void* d_pic, bool nv12, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    HIPCHK(e->err, hipSetDevice(e->device));
+    const int slot = take_slot(e);
+    if (e->G != 1) return set_err(e->err, MI355X_H264_E_ARG, "single-picture calls need a batch-1 encoder");
+    int rc = submit(e, (const uint8_t*)d_pic, 0, slot, nv12);
+    if (rc) return rc;
+    return collect(e, slot, out, out_len, frame_type);
+}
+
+// A host picture on its way to the device: tight in pinned memory (h_dst), then the transfer to d_dst on st.  A picture that is
+// tight where it lies (the reference's own layout, InitSrcPic ref :354-365: no per-row work) goes in `pieces` pieces, the copy
+// of piece k + 1 overlapping the transfer of piece k; any other in one transfer.
+hipError_t stage_picture(const HostPicture& in, int w, int h, uint8_t* h_dst, uint8_t* d_dst, hipStream_t st, int pieces)
+{
+    const size_t n = picture_bytes(in.layout, w, h);
+    if (!picture_is_tight(in, w, h)) {
+        pack_picture(in, w, h, h_dst);
+        return hipMemcpyAsync(d_dst, h_dst, n, hipMemcpyHostToDevice, st);
+    }
+    const size_t piece = pieces > 1 ? ((n / pieces) + 255) & ~(size_t)255 : n;
+    for (size_t o = 0; o < n; o += piece) {
+        const size_t len = std::min(piece, n - o);
+        memcpy(h_dst + o, in.p[0] + o, len);
+        HIPTRY(hipMemcpyAsync(d_dst + o, h_dst + o, len, hipMemcpyHostToDevice, st));
+    }
+    return hipSuccess;
+}
+
+// a host I420 / NV12 picture through the engine's staging pair (the previous picture's use of it has completed: encode is synchronous)
+int encode_one_host(mi355x_h264_encoder* e, const HostPicture& in, int pieces, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    HIPCHK(e->err, hipSetDevice(e->device));
+    HIPCHK(e->err, stage_picture(in, e->cfg.width, e->cfg.height, e->h_stage, e->d_stage, e->stream, pieces));
+    return encode_one_device(e, e->d_stage, in.layout == PIC_NV12, out, out_len, frame_type);
+}
+
+// an RGBA picture in device memory: one conversion pass into the I420 staging picture
+int encode_rgba_from_device(mi355x_h264_encoder* e, const uint8_t* d_rgba, size_t stride, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    const int w = e->cfg.width, h = e->cfg.height;
+    hipLaunchKernelGGL(k_rgba_to_i420, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(h / 2)), dim3(256), 0, e->stream, d_rgba, stride, e->d_stage, w, h);
+    HIPCHK(e->err, hipGetLastError());
+    return encode_one_device(e, e->d_stage, false, out, out_len, frame_type);
+}
+
+// `count` lockstep pictures with NSLOT - 1 of them in flight: submit_pic(i, slot) queues picture i, consume(i, slot) waits for
+// the slot and takes what it holds.  On an error the pictures still in flight are waited for (and dropped) before returning -
+// no slot stays busy - and the first error's text stays.
+template <class SubmitPic, class Consume>
+int run_pipeline(mi355x_h264_encoder* e, int count, SubmitPic&& submit_pic, Consume&& consume)
+{
+    int pending[NSLOT], npend = 0, head = 0;
+    auto drain_one = [&]() -> int { const int rc = consume(head, pending[head % NSLOT]); if (rc == 0) { head++; npend--; } return rc; };
+    auto bail = [&](int rc) -> int {
+        char first[sizeof(e->err)];
+        memcpy(first, e->err, sizeof(first));
+        for (; npend > 0; head++, npend--) (void)wait_slot(e, pending[head % NSLOT]);   // (an idle slot says so and is passed over)
+        memcpy(e->err, first, sizeof(first));
+        return rc;
+    };
+    for (int i = 0; i < count; i++) {
+        if (npend == NSLOT - 1) { int rc = drain_one(); if (rc) return bail(rc); }
+        pending[i % NSLOT] = take_slot(e);
+        int rc = submit_pic(i, pending[i % NSLOT]);
+        if (rc) return bail(rc);
+        npend++;
+    }
+    while (npend) { int rc = drain_one(); if (rc) return bail(rc); }
+    return MI355X_H264_OK;
+}
+
+// ---- slice bands over several GPUs: the rows next to a band in the reference picture come from the neighbours ----
+enum { HALO_MB_ROWS = 2 };   // 32 luma rows: the search reaches 16 rows + 0.75 + the 6-tap filter's 3, chroma half of that
+// rows [r0, r1) of the newest reconstruction <-> a packed block (Y rows, then U rows, then V rows)
+int halo_copy(mi355x_h264_encoder* e, int r0, int r1, void* d_blk, bool to_block)
+{
+    const int last = (e->seq.cur + e->nbuf - 1) % e->nbuf;
+    uint8_t* blk = (uint8_t*)d_blk;
+    for (int p = 0; p < 3; p++) {
+        const size_t pitch = p ? e->cw / 2 : e->cw, rows_per_mb = p ? 8 : 16;
+        const size_t off = (size_t)r0 * rows_per_mb * pitch, n = (size_t)(r1 - r0) * rows_per_mb * pitch;
+        uint8_t* pl = e->d_planes[last][p] + off;
+        if (n) HIPCHK(e->err, hipMemcpyAsync(to_block ? (void*)blk : (void*)pl, to_block ? (const void*)pl : (const void*)blk, n, hipMemcpyDefault, e->stream));   // the block may be device or host memory
+        blk += (size_t)HALO_MB_ROWS * rows_per_mb * pitch;   // fixed layout, whatever the number of rows present
+    }
+    HIPCHK(e->err, hipStreamSynchronize(e->stream));
+    return MI355X_H264_OK;
+}
+
+}  // namespace

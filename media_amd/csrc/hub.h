@@ -1,0 +1,257 @@
+// media_amd/csrc/hub.h -- the stream hub's HIP side (include/mi355x_h264.h, "streams"): streams of one geometry share an engine
+// whose batch items are the streams; the pictures that calls deliver while the engine is busy leave together as ONE lockstep
+// step (the IND = true kernels).  Who gathers, leads and waits is hub_sched.h; here: staging memory, uploads, the step itself.
+#pragma once
+
+namespace {
+
+static_assert(HUB_MAX_ITEMS == MAX_BATCH, "a hub's streams are the batch items of its engine");
+
+enum { HUB_IN_DEVICE = 3 };   // HostPicture.layout of a stream call that was handed one tight device picture in the stream's layout
+static_assert(PIC_I420 == MI355X_H264_INPUT_I420 && PIC_NV12 == MI355X_H264_INPUT_NV12 && PIC_RGBA == MI355X_H264_INPUT_RGBA, "layouts");
+
+// the device side of a stream: its request in flight and the answer
+struct HubItem {
+    hipEvent_t copied = nullptr;     // the picture's upload has finished
+    // where the picture lies.  staged: it was uploaded to the item's staging slot (`copied` says when it has arrived); else d_in is
+    // the caller's own device picture, read in place.  RGBA pictures (rgba_src, rgba_stride: the caller's device picture or the
+    // item's RGBA staging slot) are converted into the I420 staging slot by the step's leader.
+    bool staged = true;
+    const uint8_t* d_in = nullptr;
+    const uint8_t* rgba_src = nullptr;
+    size_t rgba_stride = 0;
+    int rc = 0, frame_type = 0;
+    uint8_t* out = nullptr;
+    uint32_t out_len = 0;
+    char err[256] = {0};
+};
+
+struct HubCtx {
+    StepSync sync;                   // a stream pair of its own
+    // the step's tables, one pinned block and one transfer: [source address per position][itemtab word per position][RGBA hubs:
+    // {address, row stride} of the RGBA picture per position]
+    enum { TAB_SRC = 0, TAB_ITEM = MAX_BATCH * 8, TAB_RGBA = TAB_ITEM + MAX_BATCH * 4, TAB_BYTES = TAB_RGBA + MAX_BATCH * 16 };
+    uint8_t* h_tab = nullptr;        // pinned
+    uint8_t* d_tab = nullptr;
+};
+
+struct Hub {
+    HubSched sched;                  // queue, item states, step contexts: sched.mu guards them
+    std::mutex launch_mu;            // one leader at a time touches the engine's host state (serials, statistics)
+    mi355x_h264_encoder* e = nullptr;
+    mi355x_h264_config cfg{};
+    DevMem mem;
+    HubItem items[MAX_BATCH];
+    HubCtx ctx[HUB_MAX_CTX];         // ctx[0 .. nctx_p - 1] take the P steps, ctx[nctx_p] the IDR steps
+    int fmt = MI355X_H264_INPUT_I420;   // layout of every picture of this hub's streams (config.input_format)
+    uint8_t* d_stage = nullptr;      // [cap] pictures the kernels read when the caller's are not read in place: host pictures as handed
+    uint8_t* h_stage = nullptr;      // over (tight I420 / NV12; pinned h_stage on their way), RGBA pictures after the conversion (I420)
+    size_t st_stage = 0;
+    uint8_t* d_rgba = nullptr;       // [cap] host RGBA pictures on their way to the conversion kernel: allocated with the hub's
+    uint8_t* h_rgba = nullptr;       // first one (pinned)
+    size_t st_rgba = 0;
+    // uploads: item k on copy stream k % NCOPY.  Two streams fill most of the link (tools/ubench_h2d.hip: 1 stream 32 GB/s, 2: 46-51,
+    // 4+: 52-57); HIP streams are a scarce resource on this runtime - beyond about a dozen live streams in the process every launch
+    // gets slower (measured: 8 copy streams per hub halved the throughput at 64 streams)
+    enum { NCOPY = 2 };
+    hipStream_t copy_st[NCOPY] = {nullptr};
+    // where a picture's time goes (microseconds, summed; MI355X_H264_HUB_VERBOSE=1 prints them when the hub is freed)
+    std::atomic<uint64_t> us_upload{0}, us_launch{0}, us_gpu{0}, us_finish{0}, us_total{0};
+    bool verbose = false;
+};
+
+std::mutex g_hubs_mu;
+std::vector<Hub*> g_hubs;
+std::atomic<int> g_streams_open{0};   // over all hubs of the process
+
+bool same_geometry(const mi355x_h264_config& a, const mi355x_h264_config& b)
+{
+    return a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
+           a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
+}
+
+void hub_free(Hub* h)
+{
+    if (!h) return;
+    HubSched& S = h->sched;
+    (void)hipSetDevice(h->cfg.device);
+    for (auto& c : h->ctx) sync_destroy(c.sync);
+    for (auto& cs : h->copy_st) if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); }
+    for (auto& it : h->items) if (it.copied) (void)hipEventDestroy(it.copied);
+    h->mem.free_all();
+    if (h->verbose && S.pictures)
+        fprintf(stderr, "mi355x_h264 hub %dx%d: %llu pictures in %llu steps (%.2f per step, largest %llu); per picture: upload %.0f us, queued %.0f us, "
+                        "whole call %.0f us; per step: launch %.0f us, GPU wait %.0f us, finish %.0f us\n", h->cfg.width, h->cfg.height,
+                (unsigned long long)S.pictures, (unsigned long long)S.steps, (double)S.pictures / S.steps, (unsigned long long)S.max_batch,
+                (double)h->us_upload / S.pictures, (double)S.us_queue / S.pictures, (double)h->us_total / S.pictures,
+                (double)h->us_launch / S.steps, (double)h->us_gpu / S.steps, (double)h->us_finish / S.steps);
+    if (h->e) destroy_engine(h->e);
+    delete h;
+}
+
+hipError_t hub_alloc(Hub* h)
+{
+    HIPTRY(hipSetDevice(h->cfg.device));
+    HIPTRY(h->mem.dev(&h->d_stage, h->st_stage * h->sched.cap));
+    HIPTRY(h->mem.pinned(&h->h_stage, h->st_stage * h->sched.cap));
+    for (auto& cs : h->copy_st) HIPTRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    const char* one = getenv("MI355X_H264_ONE_STREAM");
+    for (int ci = 0; ci <= h->sched.nctx_p; ci++) {
+        HubCtx& c = h->ctx[ci];
+        // (the IDR context has one stream: its row wavefront dominates, nothing to overlap)
+        HIPTRY(sync_create(c.sync, nullptr, nullptr, (one && one[0] == '1') || ci == h->sched.nctx_p));
+        HIPTRY(h->mem.pinned(&c.h_tab, HubCtx::TAB_BYTES));
+        HIPTRY(h->mem.dev(&c.d_tab, HubCtx::TAB_BYTES));
+    }
+    for (int i = 0; i < h->sched.cap; i++) HIPTRY(hipEventCreateWithFlags(&h->items[i].copied, hipEventDisableTiming));
+    return hipSuccess;
+}
+
+int hub_create(const mi355x_h264_config& cfg, Hub** out)
+{
+    Hub* h = new (std::nothrow) Hub();
+    if (!h) return MI355X_H264_E_NOMEM;
+    h->cfg = cfg;
+    h->fmt = cfg.input_format;
+    const char* ci = getenv("MI355X_H264_HUB_ITEMS");
+    h->sched.cap = std::min((int)MAX_BATCH, std::max(1, ci ? atoi(ci) : 32));
+    const char* wu = getenv("MI355X_H264_HUB_WINDOW_US");
+    if (wu) h->sched.window_us = std::max(0, atoi(wu));
+    h->verbose = getenv("MI355X_H264_HUB_VERBOSE") != nullptr;
+    // MI355X_H264_HUB_CTX = contexts for P steps (default 2, 1..8): one step's loop filter overlaps the other's motion search.  More
+    // contexts mean more HIP streams, and those cost more than they bring (measured: 4 contexts -5 %, 6 contexts -50 %)
+    const char* nc = getenv("MI355X_H264_HUB_CTX");
+    h->sched.nctx_p = std::min((int)HUB_MAX_CTX - 1, std::max(1, nc ? atoi(nc) : 2));
+    mi355x_h264_config ec = cfg;
+    ec.batch = h->sched.cap; ec.refs = 1; ec.band_index = 0; ec.band_count = 0; ec.input_format = MI355X_H264_INPUT_I420;
+    int rc = create_engine(&ec, &h->e, true);
+    if (rc != MI355X_H264_OK) { h->e = nullptr; hub_free(h); return rc; }
+    h->sched.nbuf = h->e->nbuf;
+    h->st_stage = (picture_bytes(PIC_I420, cfg.width, cfg.height) + 255) & ~(size_t)255;
+    h->st_rgba = (picture_bytes(PIC_RGBA, cfg.width, cfg.height) + 255) & ~(size_t)255;
+    if (hub_alloc(h) != hipSuccess) { hub_free(h); return MI355X_H264_E_HIP; }
+    *out = h;
+    return MI355X_H264_OK;
+}
+
+// one lockstep step for the gathered pictures T (all of one type) on context T.ctx: launch, wait, finish; rc[k] answers
+void hub_run_step(Hub* h, HubStep& T)
+{
+    mi355x_h264_encoder* e = h->e;
+    HubCtx& c = h->ctx[T.ctx];
+    StepSync& Y = c.sync;
+    (void)hipSetDevice(h->cfg.device);
+    const int n = T.n; const bool idr = T.idr;
+    const ItemPic* const pics = T.picks;
+    Step St;
+    int rc = MI355X_H264_OK;
+    char errtxt[256] = {0};
+    const uint64_t t0 = now_us();
+    {
+        std::lock_guard<std::mutex> lk(h->launch_mu);
+        const bool rgba = h->fmt == MI355X_H264_INPUT_RGBA;
+        unsigned long long* const h_src = (unsigned long long*)(c.h_tab + HubCtx::TAB_SRC);
+        uint32_t* const h_itemtab = (uint32_t*)(c.h_tab + HubCtx::TAB_ITEM);
+        RgbaSrc* const h_rgbatab = (RgbaSrc*)(c.h_tab + HubCtx::TAB_RGBA);
+        for (int k = 0; k < n; k++) {
+            const HubItem& it = h->items[pics[k].item];
+            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].qp << 16);
+            // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
+            h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
+            if (rgba) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)it.rgba_src, (unsigned long long)it.rgba_stride};
+            if (it.staged && hipStreamWaitEvent(Y.st, it.copied, 0) != hipSuccess) rc = MI355X_H264_E_HIP;
+        }
+        const size_t tab_bytes = rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
+        if (hipMemcpyAsync(c.d_tab, c.h_tab, tab_bytes, hipMemcpyHostToDevice, Y.st) != hipSuccess) rc = MI355X_H264_E_HIP;
+        const unsigned long long* const d_srctab = (const unsigned long long*)(c.d_tab + HubCtx::TAB_SRC);
+        if (rc == MI355X_H264_OK && rgba) {   // one conversion launch for the step, in front of the first kernel that reads samples
+            const int w = h->cfg.width, hh = h->cfg.height;
+            hipLaunchKernelGGL(k_rgba_to_i420_step, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(hh / 2), (unsigned)n), dim3(256), 0, Y.st,
+                               (const RgbaSrc*)(c.d_tab + HubCtx::TAB_RGBA), d_srctab, w, hh);
+        }
+        if (rc == MI355X_H264_OK) {
+            St.d_src = nullptr; St.src_item_stride = 0; St.nv12 = h->fmt == MI355X_H264_INPUT_NV12; St.idr = idr; St.n = n;
+            St.items = pics; St.d_itemtab = (const uint32_t*)(c.d_tab + HubCtx::TAB_ITEM); St.d_srctab = d_srctab;
+            // entropy coding beside the loop filter shortens a picture's latency; with many streams open the second HIP stream
+            // costs more than the overlap brings (64 streams: 10.9 k -> 12.1 k fps on one stream per step)
+            St.sync = &Y; St.one_stream = g_streams_open.load(std::memory_order_relaxed) > 40;
+            St.slot = &e->slots[0];
+            rc = submit_step(e, St);
+        }
+        if (rc != MI355X_H264_OK) snprintf(errtxt, sizeof(errtxt), "%s", e->err);
+    }
+    const uint64_t t1 = now_us();
+    if (rc == MI355X_H264_OK) {
+        if (hipEventSynchronize(Y.done) != hipSuccess) rc = set_err(errtxt, MI355X_H264_E_HIP, "hipEventSynchronize failed");
+    } else (void)hipStreamSynchronize(Y.st);
+    if (rc == MI355X_H264_OK) rc = handoff_timeout(Y, errtxt);
+    const uint64_t t2 = now_us();
+    std::lock_guard<std::mutex> lk(h->launch_mu);   // (finish_item touches the engine's statistics and error text)
+    for (int k = 0; k < n; k++) {
+        HubItem& it = h->items[pics[k].item];
+        it.rc = rc;
+        if (rc == MI355X_H264_OK) {
+            it.rc = finish_item(e, e->slots[0], St.lay, pics[k].item, &it.out, &it.out_len, &it.frame_type);
+            if (it.rc != MI355X_H264_OK) snprintf(it.err, sizeof(it.err), "%s", e->err);
+        } else snprintf(it.err, sizeof(it.err), "%s", errtxt);
+        T.rc[k] = it.rc;
+    }
+    h->us_launch += t1 - t0; h->us_gpu += t2 - t1; h->us_finish += now_us() - t2;
+}
+
+}  // namespace
+
+struct mi355x_h264_stream { Hub* hub; int item; };
+
+namespace {
+
+int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    Hub* h = s->hub;
+    HubItem& it = h->items[s->item];
+    const int w = h->cfg.width, hh = h->cfg.height, item = s->item;
+    const bool rgba = h->fmt == MI355X_H264_INPUT_RGBA;
+    // whatever is refused is refused here, on the host, before anything is queued or launched; the stream stays usable
+    auto refuse = [&](const char* why) { return set_err(it.err, MI355X_H264_E_ARG, "%s", why); };
+    if (in.layout != HUB_IN_DEVICE && in.layout != h->fmt) return refuse("the host picture's layout is not the one the stream was opened with");
+    if (in.layout == PIC_I420 && (in.stride[0] < w || in.stride[1] < w / 2 || in.stride[2] < w / 2)) return refuse("stride smaller than width");
+    if (in.layout == PIC_NV12 && (in.stride[0] < w || in.stride[1] < w)) return refuse("stride smaller than width");
+    if (in.layout == PIC_RGBA && in.stride[0] < 4 * w) return refuse("stride smaller than 4 * width");
+    if (in.layout == HUB_IN_DEVICE && rgba && ((uintptr_t)in.p[0] & 7) != 0) return refuse("RGBA picture not aligned to 8 bytes");
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return set_err(it.err, MI355X_H264_E_HIP, "hipSetDevice");
+    const uint64_t t_in = now_us();
+    const bool staged = in.layout != HUB_IN_DEVICE;
+    bool ok = true;
+    if (staged) {
+        // 1. a host picture goes to the stream's staging slot (RGBA: to its RGBA staging slot, which comes with the hub's first host
+        // RGBA picture; the step's conversion launch writes the I420 slot): pinned copy, then the transfer on the item's copy
+        // stream; it.copied says when it has arrived
+        const int nopen = h->sched.begin_upload([&] { return in.layout != PIC_RGBA || h->mem.pair(&h->d_rgba, &h->h_rgba, h->st_rgba * h->sched.cap); });
+        if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the RGBA staging pictures");
+        const size_t off = (size_t)item * (in.layout == PIC_RGBA ? h->st_rgba : h->st_stage);
+        uint8_t* const hs = (in.layout == PIC_RGBA ? h->h_rgba : h->h_stage) + off, * const ds = (in.layout == PIC_RGBA ? h->d_rgba : h->d_stage) + off;
+        hipStream_t cs = h->copy_st[item % Hub::NCOPY];
+        // few streams: four pieces, so that the copy of piece k + 1 runs while piece k is on the bus (latency); many streams: one
+        // transfer per picture (every queued command costs, and other streams' transfers fill the bus anyway: 16 / 32 / 64 streams
+        // went from 7.3 / 8.0 / 8.6 k to 8.8 / 11.5 / 10.9 k fps with this alone, profiles/r03_hub_sweep_*.log)
+        const int pieces = in.layout == PIC_I420 && nopen <= 4 ? 4 : 1;
+        it.d_in = nullptr;
+        if (in.layout == PIC_RGBA) { it.rgba_src = ds; it.rgba_stride = (size_t)w * 4; }
+        ok = stage_picture(in, w, hh, hs, ds, cs, pieces) == hipSuccess && hipEventRecord(it.copied, cs) == hipSuccess;
+    } else if (rgba) {
+        // a device picture is read where it lies: nothing is copied and nothing waited for.  RGBA: by the step's conversion launch,
+        // which writes the item's I420 staging slot; I420 / NV12: by the encoder kernels themselves
+        it.d_in = nullptr; it.rgba_src = in.p[0]; it.rgba_stride = (size_t)w * 4;
+    } else it.d_in = in.p[0];
+    it.staged = staged;
+    const uint64_t t_q = now_us();
+    // 2. queue the picture; lead a step or wait for the one that takes it
+    h->us_upload += t_q - t_in;
+    if (!h->sched.encode(item, staged, ok, [&](HubStep& T) { hub_run_step(h, T); })) return set_err(it.err, MI355X_H264_E_HIP, "upload of the picture failed");
+    h->us_total += now_us() - t_in;
+    *out = it.out; *out_len = it.out_len;
+    if (frame_type) *frame_type = it.frame_type;
+    return it.rc;
+}
+
+}  // namespace
