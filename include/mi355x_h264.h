@@ -271,8 +271,21 @@ int mi355x_h264_stream_last_me_cost(const mi355x_h264_stream *s, uint32_t *cost)
 const char *mi355x_h264_stream_last_error(const mi355x_h264_stream *s);
 int mi355x_h264_stream_coded_width(const mi355x_h264_stream *s);
 int mi355x_h264_stream_coded_height(const mi355x_h264_stream *s);
-/* reconstruction plane (MI355X_H264_DBG_RECON_Y / _U / _V) of the stream's last picture; returns bytes or < 0 */
+/* Test hooks.  mi355x_h264_stream_debug_read: what mi355x_h264_debug_read gives for an encoder (every MI355X_H264_DBG_* value), of the
+ * stream's own batch item after the stream's last picture; returns bytes or < 0.  The stream's calls are synchronous and nothing
+ * rewrites a stream's arrays before its next call, so other streams may go on encoding meanwhile.
+ * MI355X_H264_DBG_PRE_Y / _U / _V need mi355x_h264_stream_debug_keep_pre(s, 1) before the picture: the switch belongs to the shared
+ * engine, so it holds for EVERY stream of s's geometry that shares it (and ends with the engine, when its last stream closes).
+ * On: every step copies its pictures' planes aside in front of the loop filter (device-to-device copies on the step's HIP
+ * stream, into memory every engine owns anyway).  Off (the default): no launch, no copy and no allocation differs. */
 int64_t mi355x_h264_stream_debug_read(mi355x_h264_stream *s, int what, void *dst, size_t cap);
+int mi355x_h264_stream_debug_keep_pre(mi355x_h264_stream *s, int on);
+/* Which lockstep step coded the stream's last picture: the step's serial number on the stream's engine (1, 2, ..; steps of
+ * one engine are numbered in the order they were gathered), the number of pictures the step carried, this picture's position
+ * among them (0 .. pictures - 1: the grid index the indirect kernels saw, not the batch item) and whether it was an IDR
+ * step.  Two streams of one geometry (and at most 32 open) that report the same serial were coded by the same launches.
+ * Any out-pointer may be null.  serial 0: no picture yet. */
+int mi355x_h264_stream_debug_last_step(const mi355x_h264_stream *s, uint64_t *serial, int *pictures, int *position, int *idr);
 /* how the stream's engine has been batching: steps launched, pictures coded, largest step, streams open on it */
 int mi355x_h264_stream_hub_stats(const mi355x_h264_stream *s, uint64_t *steps, uint64_t *pictures, uint64_t *max_batch,
                                  int *open_streams);

@@ -31,7 +31,7 @@ EXPORTS = [
     "mi355x_h264_stream_force_idr", "mi355x_h264_stream_set_idr_pic_id", "mi355x_h264_stream_last_me_cost",
     "mi355x_h264_stream_last_error", "mi355x_h264_stream_debug_read", "mi355x_h264_stream_hub_stats",
     "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
-    "mi355x_h264_debug_code_syntax",
+    "mi355x_h264_debug_code_syntax", "mi355x_h264_stream_debug_keep_pre", "mi355x_h264_stream_debug_last_step",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
@@ -106,6 +106,8 @@ def lib():
         L.mi355x_h264_stream_coded_height.argtypes = [vp]
         L.mi355x_h264_stream_debug_read.argtypes = [vp, C.c_int, vp, C.c_size_t]
         L.mi355x_h264_stream_debug_read.restype = C.c_int64
+        L.mi355x_h264_stream_debug_keep_pre.argtypes = [vp, C.c_int]
+        L.mi355x_h264_stream_debug_last_step.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_hub_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mi355x_h264_stats_enable.argtypes = [vp, C.c_int]
         L.mi355x_h264_stats_read.argtypes = [vp, C.POINTER(Stats), C.c_int]
@@ -128,6 +130,28 @@ def _planes(f, w, h, strides, nv12=False):
         return [(base, w), (base + w * h, w // 2), (base + w * h * 5 // 4, w // 2)], f
     keep = [np.ascontiguousarray(p, dtype=np.uint8) for p in f]
     return [(p.ctypes.data, int(st)) for p, st in zip(keep, strides)], keep
+
+
+def _debug_read(obj, fn, what):
+    """one MI355X_H264_DBG_* buffer of an Encoder's or a Stream's last picture as a numpy array in its natural shape"""
+    if what in (DBG_RECON_Y, DBG_PRE_Y):
+        a = np.empty((obj.ch, obj.cw), np.uint8)
+    elif what in (DBG_RECON_U, DBG_RECON_V, DBG_PRE_U, DBG_PRE_V):
+        a = np.empty((obj.ch // 2, obj.cw // 2), np.uint8)
+    elif what == DBG_MBINFO:
+        a = np.empty(obj.nmb, MBINFO_DTYPE)
+    elif what == DBG_MBAUX:
+        a = np.empty((obj.nmb, 16), np.uint8)
+    elif what == DBG_MVQ:
+        a = np.empty((obj.nmb, 8), np.int16)
+    elif what == DBG_LEVELS:
+        a = np.empty((obj.nmb, LV_STRIDE), np.int16)
+    else:
+        raise ValueError("debug_read(%r)" % (what,))
+    n = fn(obj.h, what, a.ctypes.data, a.nbytes)
+    if n != a.nbytes:
+        raise EncoderError("debug_read(%d) -> %d" % (what, n))
+    return a
 
 
 class Encoder:
@@ -258,23 +282,7 @@ class Encoder:
         self._check(lib().mi355x_h264_debug_keep_pre(self.h, int(on)))
 
     def debug_read(self, what):
-        ysz = self.cw * self.ch
-        if what in (DBG_RECON_Y, DBG_PRE_Y):
-            a = np.empty((self.ch, self.cw), np.uint8)
-        elif what in (DBG_RECON_U, DBG_RECON_V, DBG_PRE_U, DBG_PRE_V):
-            a = np.empty((self.ch // 2, self.cw // 2), np.uint8)
-        elif what == DBG_MBINFO:
-            a = np.empty(self.nmb, MBINFO_DTYPE)
-        elif what == DBG_MBAUX:
-            a = np.empty((self.nmb, 16), np.uint8)
-        elif what == DBG_MVQ:
-            a = np.empty((self.nmb, 8), np.int16)
-        else:
-            a = np.empty((self.nmb, LV_STRIDE), np.int16)
-        n = lib().mi355x_h264_debug_read(self.h, what, a.ctypes.data, a.nbytes)
-        if n != a.nbytes:
-            raise EncoderError("debug_read(%d) -> %d" % (what, n))
-        return a
+        return _debug_read(self, lib().mi355x_h264_debug_read, what)
 
     def stats_enable(self, on=True):
         self._check(lib().mi355x_h264_stats_enable(self.h, int(on)))
@@ -317,6 +325,7 @@ class Stream:
             raise EncoderError("mi355x_h264_stream_open failed: %d" % rc)
         self.width, self.height = width, height
         self.cw, self.ch = L.mi355x_h264_stream_coded_width(self.h), L.mi355x_h264_stream_coded_height(self.h)
+        self.nmb = (self.cw // 16) * (self.ch // 16)
 
     def _check(self, rc):
         if rc != 0:
@@ -369,6 +378,20 @@ class Stream:
         if got != n:
             raise EncoderError("stream_debug_read -> %d" % got)
         return a.reshape(self.ch // (2 if p else 1), self.cw // (2 if p else 1))
+
+    def debug_read(self, what):
+        """as Encoder.debug_read, of this stream's last picture (DBG_PRE_* after keep_pre)"""
+        return _debug_read(self, lib().mi355x_h264_stream_debug_read, what)
+
+    def keep_pre(self, on=True):
+        """keep the pre-filter planes of every stream of this stream's engine (mi355x_h264_stream_debug_keep_pre)"""
+        self._check(lib().mi355x_h264_stream_debug_keep_pre(self.h, int(on)))
+
+    def last_step(self):
+        """the lockstep step that coded this stream's last picture (mi355x_h264_stream_debug_last_step)"""
+        ser, n, pos, idr = C.c_uint64(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().mi355x_h264_stream_debug_last_step(self.h, C.byref(ser), C.byref(n), C.byref(pos), C.byref(idr)))
+        return {"serial": ser.value, "pictures": n.value, "position": pos.value, "idr": bool(idr.value)}
 
     def hub_stats(self):
         st, pc, mx, op = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()

@@ -467,6 +467,14 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             const size_t ring = p ? e->st_ring_c : e->st_ring_y;
             HIPCHK(e->err, hipMemcpy2DAsync(e->d_pre[p], ring, e->d_planes[cur][p], p ? e->st_c : e->st_y, ring, (size_t)e->G, hipMemcpyDeviceToDevice, st));
         }
+    if (e->keep_pre && ind)   // (mi355x_h264_stream_debug_keep_pre: every position's picture, from its item's own ring slot to its item's copy)
+        for (int k = 0; k < T.n; k++)
+            for (int p = 0; p < 3; p++) {
+                const size_t ring = p ? e->st_ring_c : e->st_ring_y;
+                HIPCHK(e->err, hipMemcpyAsync(e->d_pre[p] + (size_t)T.items[k].item * ring,
+                                              e->d_plane_base[p] + (size_t)T.items[k].item * (p ? e->st_c : e->st_y) + (size_t)T.items[k].cur * ring, ring,
+                                              hipMemcpyDeviceToDevice, st));
+            }
     if (!e->cfg.disable_deblock && !T.inj) {
         const int steps = e->mbw + 2 * (e->mbh - 1);
         StatScope sc(e, &S, MI355X_H264_K_DEBLOCK, (uint32_t)(e->diag_mode ? steps : 1), (uint32_t)(e->b_nmb * T.n), st);

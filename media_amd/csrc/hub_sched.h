@@ -43,6 +43,9 @@ struct HubSched {
         PicSeq seq;                  // coding state of the stream (what the engine keeps for its one stream)
         int qp = 26, gop = 30;
         int last_cur = 0;            // ring slot of the last finished picture
+        uint64_t step_serial = 0;    // the step that took the stream's last picture: its number on this hub (1, 2, ..), how many
+        int step_n = 0, step_pos = 0;   // pictures it carried, this picture's position in it, and its type (test hook:
+        bool step_idr = false;       // mi355x_h264_stream_debug_last_step)
     } items[HUB_MAX_ITEMS];
     uint64_t steps = 0, pictures = 0, max_batch = 0;
     std::atomic<uint64_t> us_queue{0};
@@ -77,6 +80,15 @@ struct HubSched {
     void force_idr(int item) { std::lock_guard<std::mutex> lk(mu); items[item].seq.force_idr = 1; }
     void set_idr_pic_id(int item, int next) { std::lock_guard<std::mutex> lk(mu); items[item].seq.idr_id = next & 0xFF; }
     int last_cur(int item) { std::lock_guard<std::mutex> lk(mu); return items[item].last_cur; }
+    void last_step(int item, uint64_t* serial, int* n, int* pos, int* idr)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        const Item& it = items[item];
+        if (serial) *serial = it.step_serial;
+        if (n) *n = it.step_n;
+        if (pos) *pos = it.step_pos;
+        if (idr) *idr = it.step_idr ? 1 : 0;
+    }
 
     // A picture is about to be uploaded: a step that is being gathered waits (briefly) for it.  ready() runs under the lock (what
     // the upload needs and is shared, allocated once); false refuses the picture.  Returns the streams open, -1 when refused.
@@ -124,6 +136,7 @@ struct HubSched {
             for (int k = 0; k < T.n; k++) {
                 Item& b = items[q[k]];
                 b.seq.begin(idr);
+                b.step_serial = steps + 1; b.step_n = T.n; b.step_pos = k; b.step_idr = idr;
                 T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id};
                 T.rc[k] = 0;
             }

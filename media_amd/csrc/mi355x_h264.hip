@@ -362,19 +362,50 @@ const char* mi355x_h264_stream_last_error(const mi355x_h264_stream* s) { return 
 int mi355x_h264_stream_coded_width(const mi355x_h264_stream* s) { return s ? s->hub->e->cw : 0; }
 int mi355x_h264_stream_coded_height(const mi355x_h264_stream* s) { return s ? s->hub->e->ch : 0; }
 
-// reconstruction planes of the stream's last picture (MI355X_H264_DBG_RECON_Y / _U / _V); the stream's calls are synchronous, so
-// the picture is complete
+// test hooks: what mi355x_h264_debug_read gives for an engine, for the stream's own batch item after its last picture; the stream's
+// calls are synchronous, so the picture is complete, and nothing rewrites the item's arrays before the stream's next call
 int64_t mi355x_h264_stream_debug_read(mi355x_h264_stream* s, int what, void* dst, size_t cap)
 {
-    if (!s || !dst || what < MI355X_H264_DBG_RECON_Y || what > MI355X_H264_DBG_RECON_V) return MI355X_H264_E_ARG;
+    if (!s || !dst) return MI355X_H264_E_ARG;
     Hub* h = s->hub;
     const mi355x_h264_encoder* e = h->e;
     if (hipSetDevice(h->cfg.device) != hipSuccess) return MI355X_H264_E_HIP;
-    const size_t ysz = (size_t)e->cw * e->ch, n = what ? ysz / 4 : ysz;
+    const size_t ysz = (size_t)e->cw * e->ch, item = (size_t)s->item, mb0 = item * e->nmb;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (what) {
+        case MI355X_H264_DBG_RECON_Y: case MI355X_H264_DBG_RECON_U: case MI355X_H264_DBG_RECON_V:
+            src = e->d_plane_base[what] + item * (what ? e->st_c : e->st_y) + (size_t)h->sched.last_cur(s->item) * (what ? e->st_ring_c : e->st_ring_y);
+            n = what ? ysz / 4 : ysz; break;
+        case MI355X_H264_DBG_PRE_Y: case MI355X_H264_DBG_PRE_U: case MI355X_H264_DBG_PRE_V: {
+            const int p = what - MI355X_H264_DBG_PRE_Y;
+            src = e->d_pre[p] + item * (p ? e->st_ring_c : e->st_ring_y); n = p ? ysz / 4 : ysz; break;
+        }
+        case MI355X_H264_DBG_MBINFO: src = e->d_mb + mb0; n = (size_t)e->nmb * sizeof(MbInfo); break;
+        case MI355X_H264_DBG_LEVELS: src = e->d_levels + mb0 * LV_STRIDE; n = (size_t)e->nmb * LV_STRIDE * 2; break;
+        case MI355X_H264_DBG_MBAUX: src = e->d_aux + mb0 * 16; n = (size_t)e->nmb * 16; break;
+        case MI355X_H264_DBG_MVQ: src = e->d_mvq + mb0 * 8; n = (size_t)e->nmb * 16; break;
+        default: return MI355X_H264_E_ARG;
+    }
     if (cap < n) return MI355X_H264_E_ARG;
-    const uint8_t* src = e->d_plane_base[what] + (size_t)s->item * (what ? e->st_c : e->st_y) + (size_t)h->sched.last_cur(s->item) * (what ? e->st_ring_c : e->st_ring_y);
     if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return MI355X_H264_E_HIP;
     return (int64_t)n;
+}
+
+// keeps a copy of every picture's reconstruction before the loop filter, for all streams of this stream's engine (engine.h, submit_step)
+int mi355x_h264_stream_debug_keep_pre(mi355x_h264_stream* s, int on)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    std::lock_guard<std::mutex> lk(s->hub->launch_mu);   // (a step's leader reads it while it launches)
+    s->hub->e->keep_pre = on != 0;
+    return MI355X_H264_OK;
+}
+
+int mi355x_h264_stream_debug_last_step(const mi355x_h264_stream* s, uint64_t* serial, int* pictures, int* position, int* idr)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    s->hub->sched.last_step(s->item, serial, pictures, position, idr);
+    return MI355X_H264_OK;
 }
 
 // how the hub of this stream has been batching: steps launched, pictures coded, the largest step

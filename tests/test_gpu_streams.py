@@ -34,8 +34,9 @@ def test_one_stream_equals_the_oracle_through_qp_changes_and_forced_idr():
 @pytest.mark.parametrize("w,h,prof,slices,nstreams,npic", [(320, 240, 66, 0, 6, 12), (176, 144, 100, 3, 5, 9), (176, 144, 66, 0, 12, 8), (640, 368, 77, 0, 4, 7),
                                                            (64, 48, 66, 0, 44, 5)])   # 44 streams: two engines (32 streams each at most), one HIP stream per step
 def test_streams_on_threads_each_equal_their_oracle(w, h, prof, slices, nstreams, npic):
-    """every stream has its own content, its own GOP length (IDR pictures fall on different ticks: steps mix picture types), its
-    own QP walk; twelve streams make steps of eight pictures or more (the pair form of the loop filter, indirect)"""
+    """every stream has its own content, its own GOP length (IDR pictures fall on different ticks: IDR steps and P steps are in
+    flight beside each other - a step itself holds pictures of one type, hub_sched.h), its own QP walk; twelve streams make steps
+    of eight pictures or more (the pair form of the loop filter, indirect)"""
     kinds = ["s1", "scroll", "split", "cut", "s3", "ramp"]
     streams, want, got = [], [], [[] for _ in range(nstreams)]
     seqs = []
