@@ -118,43 +118,37 @@ __device__ __forceinline__ void put_level(S& s, int code, int suffix_len)
     s.put(2 * prefix - 2, (1u << (prefix - 3)) | (unsigned)c);
 }
 
-// residual_block_cavlc(): lv points at scan position 0 of this block's list
+// residual_block_cavlc(): lv points at scan position 0 of this block's list.  maxc (4, 15 or 16) and nC (-1: chroma DC) are
+// RUN-TIME values: code_slot has one call site, so the lanes of a wave that hold an Intra16x16 DC, a luma, a chroma DC and a
+// chroma AC block walk this code together instead of one block kind after the other.
+// All 16 entries from lv on are read whatever maxc is (they lie inside the macroblock's own levels row for every block kind:
+// the last one is LV_CHROMA_AC + 7 * 16 + 1 + 15 < LV_STRIDE) and the ones from maxc on are masked out.
 template <class S>
 __device__ __forceinline__ void cavlc_block(S& s, const int16_t* lv, int maxc, int nC)
 {
-    unsigned nzm = 0, one = 0;
+    unsigned nzm = 0;
 #pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const int v = i < maxc ? (int)lv[i] : 0;
-        nzm |= (unsigned)(v != 0) << i;
-        one |= (unsigned)(v == 1 || v == -1) << i;
-    }
+    for (int i = 0; i < 16; i++) nzm |= (unsigned)(lv[i] != 0) << i;
+    nzm &= (1u << maxc) - 1u;
+    const bool cdc = nC == -1;
     const int tc = __popc(nzm);
+    // the (up to three) trailing ones, highest frequency first, and their trailing_ones_sign_flags: one walk, one put
+    unsigned m = nzm, signs = 0;
     int t1 = 0;
-    {
-        unsigned m = nzm;
-        while (m && t1 < 3) {
-            const int i = 31 - __clz((int)m);
-            if (!((one >> i) & 1)) break;
-            t1++; m &= ~(1u << i);
-        }
+    while (m && t1 < 3) {
+        const int i = 31 - __clz((int)m), v = lv[i];
+        if (v != 1 && v != -1) break;
+        signs = (signs << 1) | (v < 0 ? 1u : 0u);
+        t1++; m &= ~(1u << i);
     }
-    if (nC == -1) s.put(c_cdc_len[4 * tc + t1], c_cdc_bits[4 * tc + t1]);
-    else {
+    {   // coeff_token: Table 9-5, the column by nC (one load from the selected table, not a branch per table)
         const int tab = nC < 2 ? 0 : nC < 4 ? 1 : nC < 8 ? 2 : 3;
-        s.put(c_ct_len[tab][4 * tc + t1], c_ct_bits[tab][4 * tc + t1]);
+        const uint8_t* const tl = cdc ? c_cdc_len : c_ct_len[tab];
+        const uint8_t* const tb = cdc ? c_cdc_bits : c_ct_bits[tab];
+        s.put(tl[4 * tc + t1], tb[4 * tc + t1]);
     }
     if (!tc) return;
-    unsigned m = nzm;
-    {   // trailing_ones_sign_flag of the (up to three) trailing ones, highest frequency first: one put
-        unsigned signs = 0;
-        for (int k = 0; k < t1; k++) {
-            const int i = 31 - __clz((int)m);
-            signs = (signs << 1) | (lv[i] < 0 ? 1u : 0u);
-            m &= ~(1u << i);
-        }
-        s.put(t1, signs);
-    }
+    s.put(t1, signs);
     int suffix_len = (tc > 10 && t1 < 3) ? 1 : 0;
     bool first = true;
     while (m) {
@@ -171,8 +165,12 @@ __device__ __forceinline__ void cavlc_block(S& s, const int16_t* lv, int maxc, i
     const int top = 31 - __clz((int)nzm);
     if (tc < maxc) {
         const int tz = top + 1 - tc;
-        if (nC == -1) s.put(c_ctz_len[tc - 1][tz], c_ctz_bits[tc - 1][tz]);
-        else s.put(c_tz_len[tc - 1][tz], c_tz_bits[tc - 1][tz]);
+        {   // total_zeros: Table 9-9 (a) for chroma DC (tc <= 3 here), Tables 9-7 / 9-8 otherwise
+            const int e = cdc ? 4 * (tc - 1) + tz : 16 * (tc - 1) + tz;
+            const uint8_t* const tl = cdc ? &c_ctz_len[0][0] : &c_tz_len[0][0];
+            const uint8_t* const tb = cdc ? &c_ctz_bits[0][0] : &c_tz_bits[0][0];
+            s.put(tl[e], tb[e]);
+        }
         int zl = tz;
         m = nzm;
         int hi = top;
@@ -189,26 +187,14 @@ __device__ __forceinline__ void cavlc_block(S& s, const int16_t* lv, int maxc, i
     }
 }
 
-// nC of a luma 4x4 block (bx4,by4 in 0..3) / chroma block (2x2 grid), 9.2.1
-// (top: the macroblock above is in this slice)
-__device__ __forceinline__ int nc_luma(const MbInfo* m, int mx, bool top, int mbw, int x, int y)
+// nC of a block (9.2.1) from the TotalCoeff of the block to its left (nA) and above it (nB).  The caller names each of them as
+// an entry of tc[]: `in` when the neighbour lies in this macroblock (x > 0 / y > 0), `out` in the macroblock to the left /
+// above otherwise (top: the macroblock above is in this slice).  One body for luma and chroma blocks.
+__device__ __forceinline__ int nc_block(const MbInfo* m, int mx, bool top, int mbw, bool a_in, int ia_in, int ia_out, bool b_in, int ib_in, int ib_out)
 {
     int nA = -1, nB = -1;
-    if (x > 0) nA = m->tc[xy2blk(x - 1, y)];
-    else if (mx > 0) nA = (m - 1)->tc[xy2blk(3, y)];
-    if (y > 0) nB = m->tc[xy2blk(x, y - 1)];
-    else if (top) nB = (m - mbw)->tc[xy2blk(x, 3)];
-    if (nA >= 0 && nB >= 0) return (nA + nB + 1) >> 1;
-    return nA >= 0 ? nA : (nB >= 0 ? nB : 0);
-}
-__device__ __forceinline__ int nc_chroma(const MbInfo* m, int mx, bool top, int mbw, int pl, int x, int y)
-{
-    const int base = 16 + pl * 4;
-    int nA = -1, nB = -1;
-    if (x > 0) nA = m->tc[base + 2 * y];
-    else if (mx > 0) nA = (m - 1)->tc[base + 2 * y + 1];
-    if (y > 0) nB = m->tc[base + x];
-    else if (top) nB = (m - mbw)->tc[base + 2 + x];
+    if (a_in || mx > 0) nA = (a_in ? m : m - 1)->tc[a_in ? ia_in : ia_out];
+    if (b_in || top) nB = (b_in ? m : m - mbw)->tc[b_in ? ib_in : ib_out];
     if (nA >= 0 && nB >= 0) return (nA + nB + 1) >> 1;
     return nA >= 0 ? nA : (nB >= 0 ? nB : 0);
 }
@@ -393,21 +379,30 @@ __device__ __forceinline__ void code_slot(S& s, const CavlcParams& C, int mbi, i
             if (C.t8x8 && cbpl) s.put(1, m->i16_mode & 1u);   // transform_size_8x8_flag (High profile, luma coefficients present)
             if (m->cbp) put_se(s, 0);
         }
-    } else if (slot == 1) {
-        if (i16) cavlc_block(s, lv + LV_LUMA_DC, 16, nc_luma(m, mx, top, C.mbw, 0, 0));
-    } else if (slot < 18) {
-        const int b = slot - 2;
-        if (cbpl & (1 << (b >> 2))) {
-            const int nC = nc_luma(m, mx, top, C.mbw, blk_x(b), blk_y(b));
-            if (i16) cavlc_block(s, lv + LV_LUMA + b * 16 + 1, 15, nC);
-            else cavlc_block(s, lv + LV_LUMA + b * 16, 16, nC);
-        }
-    } else if (slot < 20) {
-        if (cbpc) cavlc_block(s, lv + LV_CHROMA_DC + (slot - 18) * 4, 4, -1);
-    } else if (slot < 28) {
-        const int k = slot - 20, pl = k >> 2, b = k & 3;
-        if (cbpc == 2) cavlc_block(s, lv + LV_CHROMA_AC + k * 16 + 1, 15, nc_chroma(m, mx, top, C.mbw, pl, b & 1, b >> 1));
     }
+    // Slots 1..27: what this lane's block is - nothing is coded here.  Lanes of one wave hold all four block kinds, and a wave
+    // runs divergent paths one after the other, so the coder itself follows once, after the branches have rejoined.
+    bool has_block = false;
+    const int16_t* blk = lv;
+    int maxc = 16, nC = 0;
+    if (slot >= 1 && slot < 18) {
+        // slot 1: Intra16x16 DC (nC of blkIdx 0); slots 2..17: blkIdx 0..15, Intra16x16 AC (scan positions 1..15) or a whole luma block
+        const int b = slot == 1 ? 0 : slot - 2, x = blk_x(b), y = blk_y(b);
+        has_block = slot == 1 ? i16 : (cbpl & (1 << (b >> 2))) != 0;
+        const bool ac = i16 && slot != 1;
+        blk = lv + (slot == 1 ? LV_LUMA_DC : LV_LUMA + b * 16 + (ac ? 1 : 0));
+        maxc = ac ? 15 : 16;
+        if (has_block) nC = nc_block(m, mx, top, C.mbw, x > 0, xy2blk(x - 1, y), xy2blk(3, y), y > 0, xy2blk(x, y - 1), xy2blk(x, 3));
+    } else if (slot < 20) {
+        if (slot >= 18) { has_block = cbpc != 0; blk = lv + LV_CHROMA_DC + (slot - 18) * 4; maxc = 4; nC = -1; }
+    } else if (slot < 28) {
+        const int k = slot - 20, base = 16 + (k >> 2) * 4, x = k & 1, y = (k >> 1) & 1;
+        has_block = cbpc == 2;
+        blk = lv + LV_CHROMA_AC + k * 16 + 1;
+        maxc = 15;
+        if (has_block) nC = nc_block(m, mx, top, C.mbw, x > 0, base + 2 * y, base + 2 * y + 1, y > 0, base + x, base + 2 + x);
+    }
+    if (has_block) cavlc_block(s, blk, maxc, nC);
 }
 
 // boundary strengths of every macroblock for the loop filter (lane = macroblock, edge segment).  Its own small
