@@ -26,29 +26,66 @@ enum { ME_R = 16, ME_AP = 4, ME_WS = 16 + 2 * ME_R + 2 * ME_AP, ME_WDW = ME_WS /
 
 // two-tap description of every quarter-sample position: pred = (T0 + T1 + 1) >> 1
 // with Tk read from plane pk at grid offset (dxk, dyk); planes 0 G, 1 b, 2 h, 3 j
-__device__ __forceinline__ void qpel_taps(int fx, int fy, int& o0, int& o1)
+struct QpelTap { int o0, o1; };
+constexpr QpelTap qpel_tap(int i)   // i = fy * 4 + fx
 {
     const int PL = ME_PLS;
     const int G = 0, B = PL, H = 2 * PL, J = 3 * PL, R = 1, D = ME_GP;
-    switch (fy * 4 + fx) {
-        case 0: o0 = G; o1 = G; break;
-        case 1: o0 = G; o1 = B; break;
-        case 2: o0 = B; o1 = B; break;
-        case 3: o0 = G + R; o1 = B; break;
-        case 4: o0 = G; o1 = H; break;
-        case 5: o0 = B; o1 = H; break;
-        case 6: o0 = B; o1 = J; break;
-        case 7: o0 = B; o1 = H + R; break;
-        case 8: o0 = H; o1 = H; break;
-        case 9: o0 = H; o1 = J; break;
-        case 10: o0 = J; o1 = J; break;
-        case 11: o0 = H + R; o1 = J; break;
-        case 12: o0 = G + D; o1 = H; break;
-        case 13: o0 = B + D; o1 = H; break;
-        case 14: o0 = B + D; o1 = J; break;
-        default: o0 = B + D; o1 = H + R; break;
+    switch (i) {
+        case 0: return {G, G};
+        case 1: return {G, B};
+        case 2: return {B, B};
+        case 3: return {G + R, B};
+        case 4: return {G, H};
+        case 5: return {B, H};
+        case 6: return {B, J};
+        case 7: return {B, H + R};
+        case 8: return {H, H};
+        case 9: return {H, J};
+        case 10: return {J, J};
+        case 11: return {H + R, J};
+        case 12: return {G + D, H};
+        case 13: return {B + D, H};
+        case 14: return {B + D, J};
+        default: return {B + D, H + R};
     }
 }
+// a wave-uniform position: the selection stays on the scalar unit
+__device__ __forceinline__ void qpel_taps(int fx, int fy, int& o0, int& o1)
+{
+    const QpelTap t = qpel_tap(fy * 4 + fx);
+    o0 = t.o0; o1 = t.o1;
+}
+// The same as data, o0 | o1 << 16, for positions that differ between lanes (as a switch they compile to two select chains
+// of fifteen links each).  The kernel copies the table into LDS once; a lookup is one ds_read_b32.
+#define ME_QT(i) ((uint32_t)qpel_tap(i).o0 | ((uint32_t)qpel_tap(i).o1 << 16))
+__constant__ const uint32_t c_qpel_tap[16] = {ME_QT(0), ME_QT(1), ME_QT(2), ME_QT(3), ME_QT(4), ME_QT(5), ME_QT(6), ME_QT(7),
+                                              ME_QT(8), ME_QT(9), ME_QT(10), ME_QT(11), ME_QT(12), ME_QT(13), ME_QT(14), ME_QT(15)};
+#undef ME_QT
+__device__ __forceinline__ void qpel_taps_lds(const uint32_t* s_tap, int ox, int oy, int& o0, int& o1)
+{
+    const uint32_t t = s_tap[((oy & 3) << 2) | (ox & 3)];
+    o0 = (int)(t & 0xFFFFu); o1 = (int)(t >> 16);
+}
+
+// Measurement builds only (Makefile target `ab`, AB_FLAGS=-DME_AB_REPEAT=<mask>): every phase of the sub-sample stage whose
+// bit is set runs TWICE - bit 0 the plane build, 1 the centre, 2 round 0, 3 round 1, 4 the write-out.  Results stay what
+// they are (so the pictures that follow see the same content), and SQ_INSTS_VALU per wave rises by what the phase costs.
+#ifndef ME_AB_REPEAT
+#define ME_AB_REPEAT 0
+#endif
+#if ME_AB_REPEAT
+__device__ __forceinline__ int me_ab_reps(int bit)
+{
+    int n = ((ME_AB_REPEAT >> bit) & 1) ? 2 : 1;
+    asm volatile("" : "+s"(n));   // opaque: the repetition is not folded away
+    return n;
+}
+__device__ __forceinline__ int me_ab_next() { asm volatile("" ::: "memory"); return 1; }
+#define ME_AB_PHASE(bit) for (int ab_n = me_ab_reps(bit), ab_i = 0; ab_i < ab_n; ab_i += me_ab_next())
+#else
+#define ME_AB_PHASE(bit) if constexpr (true)
+#endif
 
 
 // four chroma prediction samples (8.4.2.2.2) of plane cp (pitch cs2, chh rows): integer position (x0, y0), eighth-sample
@@ -472,35 +509,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
 
     // ---- 3. half-sample planes on an 18x18 grid, origin (ix-1, iy-1); four samples per lane-task ----
     const int oo = (iy + ME_R + ME_AP - 1) * ME_WS + ix + ME_R + ME_AP - 1;   // window byte offset of grid (0,0)
+    // (the integer search is done with s_ytab: until the intra estimate it holds the tap table of qpel_taps_lds)
+    uint32_t* const s_tap = s_ytab;
+    if (lane < 16) s_tap[lane] = c_qpel_tap[lane];
+    ME_AB_PHASE(0) {
+    // i / 5 for i < 128 as a 24-bit multiply and a shift (exact up to 1 023)
     for (int i = lane; i < (ME_GS + 5) * 5; i += 64) {
-        const int rr = i / 5, seg = (i - rr * 5) * 4;                          // b1 row rr <-> grid row rr - 2
+        const int rr = (i * 205) >> 10, seg = (i - rr * 5) * 4;                // b1 row rr <-> grid row rr - 2
         *(uint2*)(s_b1 + rr * ME_GP + seg) = htap4_pk(winb, oo + (rr - 2) * ME_WS + seg - 2);
     }
     __syncthreads();
-    for (int i = lane; i < ME_GS * 5; i += 64) {
-        const int y = i / 5, seg = (i - y * 5) * 4;
-        const uint32_t Gv = lds_ld4(winb, oo + y * ME_WS + seg);
-        uint2 rw[6];
+    // lane = (pair of grid rows, segment): 45 lanes, one trip.  The seven rows of horizontal sums and the seven window rows
+    // that two neighbouring grid rows need are read and realigned once (one row at a time took twelve of each, and a
+    // second trip with 26 lanes busy); the G samples are window row 2 + r of the seven.
+    if (lane < (ME_GS / 2) * 5) {
+        const int yp = (lane * 205) >> 10, seg = (lane - yp * 5) * 4, y0 = 2 * yp;
+        uint2 rw[7];
 #pragma unroll
-        for (int k = 0; k < 6; k++) rw[k] = *(const uint2*)(s_b1 + (y + k) * ME_GP + seg);
-        const uint32_t Bv = round5_pk(rw[2]);                                   // b: the horizontal sums of this row, rounded
-        uint32_t Hv;                                                            // h: vertical 6-tap on the integer samples
+        for (int k = 0; k < 7; k++) rw[k] = *(const uint2*)(s_b1 + (y0 + k) * ME_GP + seg);
+        uint32_t c[7];
         {
-            uint32_t c[6];
-            const int o = oo + (y - 2) * ME_WS + seg;
+            const int o = oo + (y0 - 2) * ME_WS + seg;
             lds_u32p pc = (lds_u32p)(winb + (o & ~3));   // window rows are ME_WS = 56 bytes apart
             asm("" : "+v"(pc));
 #pragma unroll
-            for (int k = 0; k < 6; k++) c[k] = __builtin_amdgcn_alignbyte(pc[k * ME_WDW + 1], pc[k * ME_WDW], o & 3);
-            Hv = round5_pk(vtap4_pk(c));
+            for (int k = 0; k < 7; k++) c[k] = __builtin_amdgcn_alignbyte(pc[k * ME_WDW + 1], pc[k * ME_WDW], o & 3);
         }
-        const uint32_t Jv = jtap4(rw);                                          // j: vertical 6-tap on the unclipped horizontal sums
-        *(uint32_t*)(s_pl + y * ME_GP + seg) = Gv;
-        *(uint32_t*)(s_pl + ME_PLS + y * ME_GP + seg) = Bv;
-        *(uint32_t*)(s_pl + 2 * ME_PLS + y * ME_GP + seg) = Hv;
-        *(uint32_t*)(s_pl + 3 * ME_PLS + y * ME_GP + seg) = Jv;
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            uint8_t* const q = s_pl + (y0 + r) * ME_GP + seg;
+            *(uint32_t*)q = c[2 + r];                                           // G: the integer samples
+            *(uint32_t*)(q + ME_PLS) = round5_pk(rw[2 + r]);                    // b: the horizontal sums of this row, rounded
+            *(uint32_t*)(q + 2 * ME_PLS) = round5_pk(vtap4_pk(c + r));          // h: vertical 6-tap on the integer samples
+            *(uint32_t*)(q + 3 * ME_PLS) = jtap4(rw + r);                       // j: vertical 6-tap on the unclipped horizontal sums
+        }
     }
     __syncthreads();
+    }
 
     // ---- 4. sub-pel refinement: 8 candidates per round; lane = (candidate, pair of 4x4 blocks).  The two
     // blocks of a lane (b and b+8) ride in the low / high 16 bits of every register: differences, the 4x4
@@ -522,7 +567,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     // has no seven companions to share a round with: it is costed apart, quad-mapped - lane = (4x4 block, row), the
     // Hadamard's rows in the lane, its columns as two butterflies over the DPP quad - for a third of a round's price.
     unsigned centre_key;
-    {
+    ME_AB_PHASE(1) {
         const int r = lane & 3, b4 = lane >> 2;
         const uint32_t sy = *(const uint32_t*)(s_src + ((b4 >> 2) * 4 + r) * 16 + (b4 & 3) * 4);
         const uint32_t ry = lds_ld4(winb, (ME_R + ME_AP + (b4 >> 2) * 4 + r + iy) * ME_WS + ME_R + ME_AP + (b4 & 3) * 4 + ix);
@@ -542,37 +587,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
         const int tot = __builtin_amdgcn_readlane(s16, 0) + __builtin_amdgcn_readlane(s16, 16) + __builtin_amdgcn_readlane(s16, 32) + __builtin_amdgcn_readlane(s16, 48);
         centre_key = ((unsigned)(tot >> 1) + (unsigned)(P.lambda * (se_len(cx - pmx) + se_len(cy - pmy)))) << 4;   // order 0
     }
-    unsigned best_cost_r = 0, bestk = 0xFFFFFFFFu;
-#pragma unroll 1
-    for (int round = 0; round < 2; round++) {
-        // round 0: the 8 half-sample neighbours (then the centre joins the comparison); round 1: the 8 quarter-sample neighbours
-        const int step = round == 1 ? 1 : 2;
-        const int ord = cand + 1;                         // 0 = centre
-        // neighbour order (-1,-1)(0,-1)(1,-1)(-1,0)(1,0)(-1,1)(0,1)(1,1)
-        const int nn = cand >= 4 ? cand + 1 : cand;
-        const int ddx = (nn % 3) - 1, ddy = (nn / 3) - 1;
-        const int qx = cx + step * ddx, qy = cy + step * ddy;
-        const int ox = qx - 4 * ix, oy = qy - 4 * iy;
-        const int gx = 1 + (ox >> 2), gy = 1 + (oy >> 2);
-        int t0, t1;
-        qpel_taps(ox & 3, oy & 3, t0, t1);
-        const int gb = (gy + b4y) * ME_GP + gx + b4x;
-        // plane rows are ME_GP = 20 bytes apart: one dword base pointer and byte shift per tap, rows by constant index
-        lds_u32p pa = (lds_u32p)(s_pl + ((t0 + gb) & ~3));
-        lds_u32p pb = (lds_u32p)(s_pl + ((t1 + gb) & ~3));
-        asm("" : "+v"(pa));   // keep the array's own LDS offset in the register, so that the row offsets fit the ds_read2 fields
-        asm("" : "+v"(pb));
-        const int sa = (t0 + gb) & 3, sb = (t1 + gb) & 3;
+    // neighbour order (-1,-1)(0,-1)(1,-1)(-1,0)(1,0)(-1,1)(0,1)(1,1); order 0 = the centre
+    const int nn = cand >= 4 ? cand + 1 : cand;
+    const int ddx = (nn % 3) - 1, ddy = (nn / 3) - 1;
+    // the lane's two blocks against the prediction rows pl[y] (low block) / ph[y] (high block): differences, 4x4 Hadamard,
+    // absolute sum over the eight lanes of the candidate
+    auto satd8 = [&](const uint32_t pl[4], const uint32_t ph[4]) -> int {
         pk16 d[16];
 #pragma unroll
-        for (int y = 0; y < 4; y++) {
-            const int rl = (ME_GP / 4) * y, rh = (ME_GP / 4) * (y + 8);
-            const uint32_t pl = avg4(__builtin_amdgcn_alignbyte(pa[rl + 1], pa[rl], sa), __builtin_amdgcn_alignbyte(pb[rl + 1], pb[rl], sb));
-            const uint32_t ph = avg4(__builtin_amdgcn_alignbyte(pa[rh + 1], pa[rh], sa), __builtin_amdgcn_alignbyte(pb[rh + 1], pb[rh], sb));
+        for (int y = 0; y < 4; y++)
 #pragma unroll
             for (int x = 0; x < 4; x++)
-                d[4 * y + x] = S[4 * y + x] - __builtin_bit_cast(pk16, __builtin_amdgcn_perm(ph, pl, sel0 + 0x00010001u * x));
-        }
+                d[4 * y + x] = S[4 * y + x] - __builtin_bit_cast(pk16, __builtin_amdgcn_perm(ph[y], pl[y], sel0 + 0x00010001u * x));
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const pk16 s0 = d[4 * i] + d[4 * i + 3], s1 = d[4 * i + 1] + d[4 * i + 2];
@@ -589,20 +615,72 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
             sum = __builtin_amdgcn_sad_u16(__builtin_bit_cast(uint32_t, s0 - s1), 0x80008000u, sum);
             sum = __builtin_amdgcn_sad_u16(__builtin_bit_cast(uint32_t, d0 - d1), 0x80008000u, sum);
         }
-        const int s = group_sum8_dpp((int)sum);
-        const unsigned cost = (unsigned)(s >> 1) + (unsigned)(P.lambda * (se_len(qx - pmx) + se_len(qy - pmy)));
-        const unsigned key = (cost << 4) | (unsigned)ord;
-        bestk = key < bestk ? key : bestk;
-        if (round == 0) bestk = centre_key < bestk ? centre_key : bestk;
-        bestk = wave_min_u32_dpp(bestk);
+        return group_sum8_dpp((int)sum);
+    };
+    // lambda * bits(mv - pmv) of the lane's neighbour.  (The three lengths per axis worked out on the scalar unit, the lane
+    // picking its own, measured 5 VALU per wave MORE than this: DESIGN.md section 11.)
+    auto mv_rate = [&](int step) -> unsigned {
+        return (unsigned)(P.lambda * (se_len(cx + step * ddx - pmx) + se_len(cy + step * ddy - pmy)));
+    };
+    // the round's winner among `key` of every lane and `stay` (order 0): the centre moves there; returns its cost
+    auto take_winner = [&](unsigned key, unsigned stay, int step) -> unsigned {
+        const unsigned bestk = wave_min_u32_dpp(key < stay ? key : stay);
         const int w = (int)(bestk & 15);
-        best_cost_r = bestk >> 4;
         if (w) {
             const int n = w - 1, wn = n >= 4 ? n + 1 : n;
             cx += step * ((wn % 3) - 1);
             cy += step * ((wn / 3) - 1);
         }
-        bestk = best_cost_r << 4;                        // the next pass starts from "stay" (order 0)
+        return bestk >> 4;
+    };
+    unsigned best_cost_r;
+    // Round 0: the 8 half-sample neighbours of the integer position, then the centre joins the comparison.  Every one of
+    // them is a sample of ONE plane (qpel_tap entries 0, 2, 8, 10 have o0 == o1: G, b, h, j), and which plane and where
+    // depends on the lane alone: one tap, no table, no average.
+    {
+        int s;
+        ME_AB_PHASE(2) {
+            const int go = ME_PLS * ((ddx != 0) + 2 * (ddy != 0)) + ((ddy >= 0) + b4y) * ME_GP + (ddx >= 0) + b4x;
+            // plane rows are ME_GP = 20 bytes apart: one dword base pointer and byte shift, rows by constant index
+            lds_u32p pa = (lds_u32p)(s_pl + (go & ~3));
+            asm("" : "+v"(pa));   // keep the array's own LDS offset in the register, so that the row offsets fit the ds_read2 fields
+            const int sa = go & 3;
+            uint32_t pl[4], ph[4];
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                const int rl = (ME_GP / 4) * y, rh = (ME_GP / 4) * (y + 8);
+                pl[y] = __builtin_amdgcn_alignbyte(pa[rl + 1], pa[rl], sa);
+                ph[y] = __builtin_amdgcn_alignbyte(pa[rh + 1], pa[rh], sa);
+            }
+            s = satd8(pl, ph);
+        }
+        const unsigned cost = (unsigned)(s >> 1) + mv_rate(2);
+        best_cost_r = take_winner((cost << 4) | (unsigned)(cand + 1), centre_key, 2);
+    }
+    // Round 1: the 8 quarter-sample neighbours of round 0's winner, two taps each
+    {
+        int s;
+        ME_AB_PHASE(3) {
+            const int ox = cx + ddx - 4 * ix, oy = cy + ddy - 4 * iy;
+            int t0, t1;
+            qpel_taps_lds(s_tap, ox, oy, t0, t1);
+            const int gb = (1 + (oy >> 2) + b4y) * ME_GP + 1 + (ox >> 2) + b4x;
+            lds_u32p pa = (lds_u32p)(s_pl + ((t0 + gb) & ~3));
+            lds_u32p pb = (lds_u32p)(s_pl + ((t1 + gb) & ~3));
+            asm("" : "+v"(pa));
+            asm("" : "+v"(pb));
+            const int sa = (t0 + gb) & 3, sb = (t1 + gb) & 3;
+            uint32_t pl[4], ph[4];
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                const int rl = (ME_GP / 4) * y, rh = (ME_GP / 4) * (y + 8);
+                pl[y] = avg4(__builtin_amdgcn_alignbyte(pa[rl + 1], pa[rl], sa), __builtin_amdgcn_alignbyte(pb[rl + 1], pb[rl], sb));
+                ph[y] = avg4(__builtin_amdgcn_alignbyte(pa[rh + 1], pa[rh], sa), __builtin_amdgcn_alignbyte(pb[rh + 1], pb[rh], sb));
+            }
+            s = satd8(pl, ph);
+        }
+        const unsigned cost = (unsigned)(s >> 1) + mv_rate(1);
+        best_cost_r = take_winner((cost << 4) | (unsigned)(cand + 1), best_cost_r << 4, 1);   // "stay" is order 0
     }
     const int rbits = P.nref <= 1 ? 0 : (P.nref == 2 ? 1 : (rf == 0 ? 1 : 3));   // te(v) of ref_idx_l0 (9.1)
     // ---- 4b. partitions (oracle/h264_enc.c motion_search): a macroblock whose 16x16 cost reaches PART_TEST_MIN is also costed
@@ -617,8 +695,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
         auto eval = [&](int qlx, int qly, int qhx, int qhy) -> uint32_t {
             const int oxl = qlx - 4 * ix, oyl = qly - 4 * iy, oxh = qhx - 4 * ix, oyh = qhy - 4 * iy;
             int t0, t1, u0, u1;
-            qpel_taps(oxl & 3, oyl & 3, t0, t1);
-            qpel_taps(oxh & 3, oyh & 3, u0, u1);
+            qpel_taps_lds(s_tap, oxl, oyl, t0, t1);
+            qpel_taps_lds(s_tap, oxh, oyh, u0, u1);
             const int gbl = (1 + (oyl >> 2) + b4y) * ME_GP + 1 + (oxl >> 2) + b4x;
             const int gbh = (1 + (oyh >> 2) + b4y + 8) * ME_GP + 1 + (oxh >> 2) + b4x;
             lds_u32p pal = (lds_u32p)(s_pl + ((t0 + gbl) & ~3)), pbl = (lds_u32p)(s_pl + ((t1 + gbl) & ~3));
@@ -681,7 +759,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
             return min(k, (unsigned)__shfl_xor((int)k, 32));
         };
         const uint32_t acc0 = eval(4 * ix, 4 * iy, 4 * ix, 4 * iy);   // the common starting point of every partition
-        const int nn = cand >= 4 ? cand + 1 : cand, ddx = (nn % 3) - 1, ddy = (nn / 3) - 1;
         unsigned best_all = best_cost_r;
 #pragma unroll 1
         for (int sh = 1; sh <= 3; sh++) {
@@ -725,12 +802,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     // this reference picture against the best so far
     const unsigned total = best_cost_r + (unsigned)(P.lambda * rbits);
     const bool better = total < prev_total;   // wave-uniform; rf == 0: always
-    if (better) {
+    if (better) ME_AB_PHASE(4) {
         // the prediction goes to the reconstruction planes (k_tq turns it into the reconstruction in place): luma from the
         // half-sample planes still in LDS, lane = (row, 4-sample segment); chroma by 8.4.2.2.2; every sample by the vector of
         // its quadrant
-        const int y = lane >> 2, seg = (lane & 3) * 4;
-        const int pl = lane >> 4, cyy = (lane >> 1) & 7, cxx = (lane & 1) * 4;   // chroma: lanes < 32
+        // (the zero tests use the same lane mapping; worked out again from an opaque copy of the lane number, it is not kept
+        // in registers - or spilled - across the whole search.  This steers one compiler's register allocation: with another
+        // compiler version, check scratch = 0 again as profiles/me_subsample_kernel_resources.txt was made)
+        int wl = lane;
+        asm volatile("" : "+v"(wl));
+        const int y = wl >> 2, seg = (wl & 3) * 4;
+        const int pl = wl >> 4, cyy = (wl >> 1) & 7, cxx = (wl & 1) * 4;   // chroma: lanes < 32
         if (shape == 0) {   // one vector: the tap selection stays on the scalar unit
             const int ox = cx - 4 * ix, oy = cy - 4 * iy;
             int t0, t1;
@@ -746,7 +828,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 const int vx = lowq ? (leftq ? qvx0 : qvx1) : (leftq ? qvx2 : qvx3), vy = lowq ? (leftq ? qvy0 : qvy1) : (leftq ? qvy2 : qvy3);
                 const int ox = vx - 4 * ix, oy = vy - 4 * iy;
                 int t0, t1;
-                qpel_taps(ox & 3, oy & 3, t0, t1);
+                qpel_taps_lds(s_tap, ox, oy, t0, t1);
                 const int gb = (1 + (oy >> 2) + y) * ME_GP + 1 + (ox >> 2) + seg;
                 *(uint32_t*)(P.rec[0] + (size_t)(by + y) * P.cw + bx + seg) = avg4(lds_ld4(s_pl, t0 + gb), lds_ld4(s_pl, t1 + gb));
             }
