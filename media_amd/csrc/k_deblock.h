@@ -167,10 +167,14 @@ __global__ __launch_bounds__(64) void k_deblock_diag(DbParams D, int s)
 
 // ===========================================================================
 // Persistent form: ONE launch, one wavefront per macroblock row.  Row r walks its
-// macroblocks left to right; macroblock mx needs the bottom four luma / two chroma
-// sample rows of macroblock (mx, r-1), which row r-1 PUBLISHES once it has
-// finished macroblock mx+1 (whose left-edge filter is the last thing that touches
-// them).  That is exactly the 8.7 raster-order dependency (left, top, top-right).
+// macroblocks left to right; the HORIZONTAL edges of macroblock mx need the bottom
+// four luma / two chroma sample rows of macroblock (mx, r-1), which row r-1
+// PUBLISHES as soon as it has filtered the LEFT edge of macroblock mx+1 (the last
+// thing that touches them: its columns 13..15).  The vertical edges of (mx, r)
+// touch rows 0..15 of their own row only, so row r waits BETWEEN its two phases,
+// not before the first.  That is the 8.7 raster-order dependency (left, top,
+// top-right) and no more: a row runs about three quarters of a macroblock step
+// plus the hand-off latency behind the one above it.
 //
 // Hand-off (cdna_hip_programming.md Guideline 16, form R2 "the data is the flag"):
 // 24 granules per macroblock, each ONE aligned 8-byte agent-scope relaxed atomic
@@ -361,10 +365,11 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     uint4 b0 = pf_b0, b1 = pf_b1;
     u64 g = pf_g;
 
-    // 7. the previous macroblock is final with respect to this row once the current one's left edge has been filtered
-    // (the horizontal edges of the current macroblock do not touch it): store / publish it.  Issued right after the
-    // vertical-edge phase, so that the stores' acknowledgements (the agent-scope granule stores go all the way to the
-    // memory side; vmcnt retires in order) have the rest of the iteration to come back before the next wait for loads.
+    // the previous macroblock is final with respect to this row once the current one's LEFT edge has been filtered (its
+    // other vertical edges and its horizontal edges do not touch it): store / publish it.  Issued between the left edge and
+    // edges 1..3, so that the row below gets it as early as 8.7 allows and the stores' acknowledgements (the agent-scope
+    // granule stores go all the way to the memory side; vmcnt retires in order) have the rest of the iteration to come
+    // back before the next wait for loads.
     auto store_prev = [&](const int mx, const bool have_cur) {
         if (mx > 0) {
             const int pmx = mx - 1;
@@ -393,7 +398,56 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             // 2. current macroblock into LDS
             *(uint32_t*)&SY(yr, yc4) = cur_y;
             if (lane < 32) *(uint32_t*)&SC(cpl_l, cr_l, cc4) = cur_c;
-            // 3. top apron: wait until every granule carries this picture's tag
+            // requests for the next macroblock leave now and are collected after the filter
+            if (mx + 1 < D.mbw) prefetch(mx + 1);
+            if (PERMB) {
+                const int qc = (int)(cur_q & 255u), qt = (int)(cur_q >> 8);
+                thresholds(qc, qc, al, be, t1, t2, t3);
+                thresholds(mx > 0 ? qp_left : qc, qc, alL, beL, t1L, t2L, t3L);
+                thresholds(qt, qc, alT, beT, t1T, t2T, t3T);
+                qp_left = qc;
+            }
+            wave_sync();
+            const bool any_v = (b0.x | b0.y | b0.z | b0.w) != 0, any_h = (b1.x | b1.y | b1.z | b1.w) != 0;
+            // 3. vertical edges: lane = one line of samples, four edges in registers.
+            //    chroma lines take part in steps 0 and 1 (chroma edges 0 and 4 <-> luma edges 0 and 8).
+            //    The left edge goes first and its p side (the one tile dword of the previous macroblock it can change) is
+            //    written back at once: the previous macroblock is final from here, and the row below is waiting for it.
+            const bool v_on = any_v && lane < 32;
+            int px[20];
+            int e1 = 0, e2 = 0, e3 = 0;
+            if (v_on) {
+#pragma unroll
+                for (int w = 0; w < 5; w++) {
+                    const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
+#pragma unroll
+                    for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
+                }
+                const int e0 = (int)((b0.x >> seg8) & 255);
+                e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
+                e2 = isC ? 0 : (int)((b0.z >> seg8) & 255); e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
+                // an edge no line of which is filtered (bS 0 in every segment, luma and chroma: three of four inner edges on
+                // ordinary P pictures) is skipped by ONE wave-uniform branch - not a branch inside the filter, see filt_uni
+                if (__ballot(e0 != 0) != 0ull) {
+                    filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, alL, beL, t1L, t2L, t3L);
+                    *(uint32_t*)vrow = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+                }
+            }
+            wave_sync();
+            // 4. publish the previous macroblock (the row below needs nothing else of this one), then edges 1..3 from
+            //    the registers already held
+            store_prev(mx, true);
+            if (v_on) {
+                if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
+                if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
+                if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
+#pragma unroll
+                for (int w = 1; w < 5; w++)
+                    if (w < 3 || !isC)
+                        *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
+            }
+            // the top apron is needed from here on and not before (the vertical edges touch rows 0..15 only): wait until
+            // every granule of the macroblock above carries this picture's tag
             if (!first_row) {
                 unsigned spins = 0;
                 while (!timed_out) {
@@ -406,42 +460,7 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
                 if (lane < 16) *(uint32_t*)&SY(-4 + (gk >> 2), (gk & 3) * 4) = (uint32_t)g;
                 else if (lane < 24) *(uint32_t*)&SC((gk - 16) >> 2, -2 + (((gk - 16) >> 1) & 1), ((gk - 16) & 1) * 4) = (uint32_t)g;
             }
-            // requests for the next macroblock leave now and are collected after the filter
-            if (mx + 1 < D.mbw) prefetch(mx + 1);
-            if (PERMB) {
-                const int qc = (int)(cur_q & 255u), qt = (int)(cur_q >> 8);
-                thresholds(qc, qc, al, be, t1, t2, t3);
-                thresholds(mx > 0 ? qp_left : qc, qc, alL, beL, t1L, t2L, t3L);
-                thresholds(qt, qc, alT, beT, t1T, t2T, t3T);
-                qp_left = qc;
-            }
             wave_sync();
-            const bool any_v = (b0.x | b0.y | b0.z | b0.w) != 0, any_h = (b1.x | b1.y | b1.z | b1.w) != 0;
-            // 4. vertical edges: lane = one line of samples, four edges in registers.
-            //    chroma lines take part in steps 0 and 1 (chroma edges 0 and 4 <-> luma edges 0 and 8)
-            if (any_v && lane < 32) {
-                int px[20];
-#pragma unroll
-                for (int w = 0; w < 5; w++) {
-                    const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
-#pragma unroll
-                    for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
-                }
-                const int e0 = (int)(((isC ? b0.x : b0.x) >> seg8) & 255), e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
-                const int e2 = isC ? 0 : (int)((b0.z >> seg8) & 255), e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
-                // an edge no line of which is filtered (bS 0 in every segment, luma and chroma: three of four inner edges on
-                // ordinary P pictures) is skipped by ONE wave-uniform branch - not a branch inside the filter, see filt_uni
-                if (__ballot(e0 != 0) != 0ull) filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, alL, beL, t1L, t2L, t3L);
-                if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-                if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-                if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-#pragma unroll
-                for (int w = 0; w < 5; w++)
-                    if (w < 3 || !isC)
-                        *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
-            }
-            wave_sync();
-            store_prev(mx, true);
             // 5. horizontal edges: lane = one column of samples (rows -4..15; chroma uses rows -4..7 of its tile)
             if (any_h && lane < 32) {
                 int px[20];
@@ -493,11 +512,16 @@ __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 
 // ===========================================================================
 // Pair form of the persistent loop filter: ONE wave filters TWO macroblock rows - lanes 0..31 row 2p
-// (macroblock t in iteration t), lanes 32..63 row 2p + 1 two macroblocks behind (macroblock t - 2), which is exactly the lag
-// 8.7 demands (left, top, top-right).  Both rows run the SAME instruction stream: every phase of the row form used lanes
-// 0..31 only for the filter arithmetic, so a lockstep batch needs half the waves and half the filter instructions per
-// macroblock, and the upper row hands its bottom sample rows to the lower one through LDS (a two-slot ring: written in
-// iteration t - 1, read in iteration t) instead of 24 global granules and their latency.  Between pairs the hand-off is
+// (macroblock t in iteration t), lanes 32..63 row 2p + 1 ONE macroblock behind (macroblock t - 1).  Both rows run the SAME
+// instruction stream: every phase of the row form used lanes 0..31 only for the filter arithmetic, so a lockstep batch needs
+// half the waves and half the filter instructions per macroblock, and the upper row hands its bottom sample rows to the lower
+// one through LDS instead of 24 global granules and their latency.  Inside an iteration the order is the dependency of 8.7
+// itself: left edge of V(t) above and of V(t - 1) below; the upper row publishes macroblock t - 1 (final now) into the ring
+// slot (t - 1) & 1, the lower row macroblock t - 2 to the next pair; edges 1..3; the lower row takes that slot as its top apron
+// (the upper row waits for the previous pair's granules at the same point); horizontal edges of t above and t - 1 below.  A
+// slot is written and read in the same iteration, so of the two slots the one not being written is simply idle; the
+// upper row's closing publish (t == mbw: no macroblock of its own, no shift) sits at the same point of the iteration, because
+// the lower row's last macroblock takes it a few instructions later.  Between pairs the hand-off is
 // the row form's ({tag, 4 samples} granules in global memory), and so is everything else: tile layout, the branch-free
 // filter, prefetch one macroblock ahead, one writer per picture sample, bounded spins.
 // MEASURED (bench workload, 32 pictures per launch): at first the launch got 7 % shorter and the pipeline 1 % slower (each step of
@@ -604,8 +628,8 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
             }
         }
     };
-    for (int t = 0; t <= D.mbw + 2; t++) {
-        const int mx = t - 2 * half;                              // this lane's macroblock
+    for (int t = 0; t <= D.mbw + 1; t++) {
+        const int mx = t - half;                                  // this lane's macroblock
         const bool in_range = mx >= 0 && mx <= D.mbw && live;     // (mx == mbw: the closing store of the row)
         const bool have_cur = in_range && mx < D.mbw;
         if (have_cur) {
@@ -621,7 +645,47 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
             *(uint32_t*)&SY(yr0 + 8, yc4) = cur_y1;
             *(uint32_t*)&SC(cpl_l, cr_l, cc4) = cur_c;
         }
-        // top apron: the upper row waits for the previous pair's granules, the lower row takes the ring slot of its macroblock
+        {   // requests for this lane's next macroblock (clamped: the loads of a finished or not yet started row are harmless)
+            const int nx = mx + 1 < 0 ? 0 : (mx + 1 > last_mx ? last_mx : mx + 1);
+            prefetch(nx);
+        }
+        wave_sync();
+        const bool any_v = have_cur && (b0.x | b0.y | b0.z | b0.w) != 0, any_h = have_cur && (b1.x | b1.y | b1.z | b1.w) != 0;
+        // vertical edges, left edge first; its p side (the one tile dword of the previous macroblock it can change) goes back at once
+        int px[20];
+        int e1 = 0, e2 = 0, e3 = 0;
+        if (any_v) {
+#pragma unroll
+            for (int w = 0; w < 5; w++) {
+                const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
+#pragma unroll
+                for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
+            }
+            const int e0 = (int)((b0.x >> seg8) & 255);
+            e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
+            e2 = isC ? 0 : (int)((b0.z >> seg8) & 255); e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
+            if (__ballot(e0 != 0) != 0ull) {
+                filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, al, be, t1, t2, t3);
+                *(uint32_t*)vrow = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+            }
+        }
+        wave_sync();
+        // the previous macroblock of each row is final now: the upper row's goes into the ring slot the lower row reads further
+        // down in this same iteration, the lower row's to the next pair.  mx == mbw is the closing publish of a row (no shift,
+        // no left edge) - at this point too, because the lower row's last macroblock is waiting for it.
+        if (in_range) store_prev(mx, have_cur);
+        if (any_v) {
+            if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
+            if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
+            if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
+#pragma unroll
+            for (int w = 1; w < 5; w++)
+                if (w < 3 || !isC)
+                    *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
+        }
+        wave_sync();   // (the ring slot written above is read by the other half's lanes)
+        // top apron, needed by the horizontal edges only: the upper row waits for the previous pair's granules, the lower row
+        // takes the ring slot the upper row has just filled
         {
             const bool need_g = have_cur && !from_lds && !first_row;   // lanes of the upper half
             unsigned spins = 0;
@@ -638,33 +702,7 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
                 else *(uint32_t*)&SC((gk - 16) >> 2, -2 + (((gk - 16) >> 1) & 1), ((gk - 16) & 1) * 4) = v;
             }
         }
-        {   // requests for this lane's next macroblock (clamped: the loads of a finished or not yet started row are harmless)
-            const int nx = mx + 1 < 0 ? 0 : (mx + 1 > last_mx ? last_mx : mx + 1);
-            prefetch(nx);
-        }
         wave_sync();
-        const bool any_v = have_cur && (b0.x | b0.y | b0.z | b0.w) != 0, any_h = have_cur && (b1.x | b1.y | b1.z | b1.w) != 0;
-        if (any_v) {
-            int px[20];
-#pragma unroll
-            for (int w = 0; w < 5; w++) {
-                const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
-#pragma unroll
-                for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
-            }
-            const int e0 = (int)((b0.x >> seg8) & 255), e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
-            const int e2 = isC ? 0 : (int)((b0.z >> seg8) & 255), e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
-            if (__ballot(e0 != 0) != 0ull) filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, al, be, t1, t2, t3);
-            if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-            if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-            if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-#pragma unroll
-            for (int w = 0; w < 5; w++)
-                if (w < 3 || !isC)
-                    *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
-        }
-        wave_sync();
-        if (have_cur) store_prev(mx, true);
         if (any_h) {
             int px[20];
 #pragma unroll
@@ -691,7 +729,6 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
                 *(uint32_t*)((pl ? D.pl[2] : D.pl[1]) + (size_t)(8 * my - 2 + r) * cs + 8 * mx + c4) = *(const uint32_t*)&SC(pl, -2 + r, c4);
             }
         }
-        if (in_range && !have_cur) store_prev(mx, false);   // after the last macroblock of this lane's row
         if (mx + 1 >= 0 && mx + 1 <= last_mx) { cur_y0 = pf_y0; cur_y1 = pf_y1; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; }
         wave_sync();
     }
