@@ -372,6 +372,7 @@ const uint8_t *h264o_enc_source(const h264o_enc *e, int p) { return e->src[p]; }
 const h264o_hits *h264o_enc_hits(const h264o_enc *e) { return &e->hits; }
 void h264o_enc_hits_reset(h264o_enc *e) { memset(&e->hits, 0, sizeof(e->hits)); }
 uint32_t h264o_enc_last_me_cost(const h264o_enc *e) { return e->me_cost; }
+const uint8_t *h264o_enc_p_decision(const h264o_enc *e) { return e->want_intra; }
 
 /* ------------------------------------------------------------ headers 7.3.2 */
 static void write_sps(h264o_enc *e, bitw *b)

@@ -136,6 +136,10 @@ const h264o_hits *h264o_enc_hits(const h264o_enc *e);
 void h264o_enc_hits_reset(h264o_enc *e);
 /* scene-change statistic (mirrors mi355x_h264_last_me_cost) */
 uint32_t h264o_enc_last_me_cost(const h264o_enc *e);
+/* one byte per macroblock of the last P picture (stale after an IDR picture): what the motion stage decided before anything was
+ * coded - 0 searched and coded as an inter macroblock, 1 searched and handed to the intra pass, 2 settled without a search by one
+ * of the "nothing left to code" tests (mirrors the searched / tq_coded counters of mi355x_h264_stats) */
+const uint8_t *h264o_enc_p_decision(const h264o_enc *e);
 
 /* One picture of RANDOM conforming syntax (decoder-peer tests; nothing is reconstructed - oracle/h264_dec.c says what the
  * stream decodes to).  features: 1 mb_qp_delta + slice QPs, 2 chroma_qp_index_offsets, 4 filter offsets, 8 I_PCM macroblocks,

@@ -76,6 +76,8 @@ def lib():
         L.h264o_enc_set_qp.argtypes = [vp, C.c_int]
         L.h264o_enc_last_me_cost.argtypes = [vp]
         L.h264o_enc_last_me_cost.restype = C.c_uint32
+        L.h264o_enc_p_decision.restype = vp
+        L.h264o_enc_p_decision.argtypes = [vp]
         L.h264o_enc_set_idr_id.argtypes = [vp, C.c_int, C.c_int]
         L.h264o_enc_halo_bytes.argtypes = [vp]
         L.h264o_enc_halo_bytes.restype = C.c_size_t
@@ -242,6 +244,15 @@ class OracleEncoder:
 
     def me_cost(self):
         return lib().h264o_enc_last_me_cost(self.h)
+
+    P_CODED, P_TO_INTRA, P_SETTLED = 0, 1, 2
+
+    def p_decision(self):
+        """per macroblock of the last P picture: P_CODED (searched, coded as an inter macroblock), P_TO_INTRA (searched, handed to
+        the intra pass) or P_SETTLED (one of the "nothing left to code" tests: no search, nothing coded)"""
+        n = (self.cw // 16) * (self.ch // 16)
+        addr = lib().h264o_enc_p_decision(self.h)
+        return np.ctypeslib.as_array(C.cast(addr, C.POINTER(C.c_uint8)), shape=(n,)).copy()
 
     def slice_bits(self):
         """bits of every slice of the last picture, first_mb_in_slice up to and including rbsp_stop_one_bit"""

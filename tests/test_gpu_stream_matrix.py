@@ -31,11 +31,10 @@ class Job(C.Structure):   # StreamTickJob of tools/stream_tick.cpp
                 ("out", C.c_void_p), ("len", C.c_uint32), ("frame_type", C.c_int32)]
 
 
-@pytest.fixture(scope="module")
-def tick(tmp_path_factory):
+def build_tick(directory):
     """tools/stream_tick.cpp: one picture of every stream of a group handed in by native threads that start together (Python
     threads arrive an interpreter-lock hand-over apart, longer than a step of small pictures takes)"""
-    so = str(tmp_path_factory.mktemp("stream_tick") / "libstream_tick.so")
+    so = os.path.join(str(directory), "libstream_tick.so")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-pthread", os.path.join(ROOT, "tools", "stream_tick.cpp"), "-o", so])
     L = C.CDLL(so)
     L.stream_tick.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int]
@@ -45,6 +44,11 @@ def tick(tmp_path_factory):
     def run(jobs):
         assert L.stream_tick(host, dev, jobs, len(jobs)) == 0, "the helper's threads could not be started"
     return run
+
+
+@pytest.fixture(scope="module")
+def tick(tmp_path_factory):
+    return build_tick(tmp_path_factory.mktemp("stream_tick"))
 
 
 def _open(s):
