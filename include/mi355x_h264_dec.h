@@ -68,7 +68,8 @@ const char *mi355x_h264_parser_error(const mi355x_h264_parser *p);
  * of any other shape), deblocking idc, num_ref_idx_active,
  * transform_8x8_mode, has I_PCM, bit 0 has intra | bit 1 has inter; with n >= 17 also: chroma_qp_index_offset,
  * second_chroma_qp_index_offset, FilterOffsetA, FilterOffsetB, 1 = every macroblock has that one QP and no offset applies;
- * with n >= 20 also RefPicList0 entries 0..2 as "reference pictures ago" (0 = the one decoded last; default 0, 1, 2).
+ * with n >= 20 also RefPicList0 entries 0..2 as "reference pictures ago" (0 = the one decoded last; default 0, 1, 2);
+ * with n >= 21 also 1 = a reference picture (nal_ref_idc != 0), 0 = a non-reference picture.
  * Returns the number of values written */
 int mi355x_h264_parser_info(const mi355x_h264_parser *p, int32_t *out, int n);
 /* what: 0 MbInfo (32 B / macroblock, layout of mi355x_h264.h), 1 quadrant vectors (8 int16), 2 Intra4x4 modes (16 B), 3 levels (416 int16),

@@ -544,9 +544,9 @@ int mi355x_h264_parser_info(const mi355x_h264_parser* p, int32_t* out, int n)
 {
     if (!p || !out || n < 12) return -1;
     const h264dec::Picture& c = p->p.picture();
-    const int32_t v[20] = {c.mbw, c.mbh, c.width, c.height, c.idr, c.qp, c.slice_rows, c.deblock_idc, c.num_ref_active, c.t8x8_mode, c.has_pcm, c.has_intra | (c.has_inter << 1),
-                           c.cqo[0], c.cqo[1], c.filter_oa, c.filter_ob, c.one_qp, c.ref_age[0], c.ref_age[1], c.ref_age[2]};
-    const int m = n < 17 ? 12 : (n < 20 ? 17 : 20);   // (a caller with an earlier layout's slots gets those)
+    const int32_t v[21] = {c.mbw, c.mbh, c.width, c.height, c.idr, c.qp, c.slice_rows, c.deblock_idc, c.num_ref_active, c.t8x8_mode, c.has_pcm, c.has_intra | (c.has_inter << 1),
+                           c.cqo[0], c.cqo[1], c.filter_oa, c.filter_ob, c.one_qp, c.ref_age[0], c.ref_age[1], c.ref_age[2], c.is_ref};
+    const int m = n < 17 ? 12 : (n < 20 ? 17 : (n < 21 ? 20 : 21));   // (a caller with an earlier layout's slots gets those)
     memcpy(out, v, (size_t)m * sizeof(int32_t));
     return m;
 }

@@ -246,12 +246,20 @@ typedef struct {
 
 typedef struct { uint8_t *pl[3]; int frame_num; int32_t id; } dpic;
 
+/* parameter sets as parsed, kept by id (7.4.1.2.1: a set is activated by the slice header that names it) */
+typedef struct { int valid, profile, level, log2_max_frame_num, poc_type, log2_max_poc_lsb, max_refs, mbw, mbh, crop_l, crop_r, crop_t, crop_b; } dsps;
+typedef struct { int valid, sps_id, init_qp, cqp_off[2], dbf_ctrl, num_ref_default, t8x8_mode, constrained_intra; } dpps;
+
 struct h264o_dec {
-    /* SPS */
+    dsps sps_tab[32];
+    dpps pps_tab[256];
+    /* the active SPS */
     int have_sps, profile, level, log2_max_frame_num, poc_type, log2_max_poc_lsb, max_refs;
-    int mbw, mbh, crop_r, crop_b;
-    /* PPS */
+    int mbw, mbh, crop_l, crop_r, crop_t, crop_b;
+    /* the active PPS (one per picture in the streams read here; re-read from the table at every slice) */
     int have_pps, init_qp, cqp_off[2], dbf_ctrl, num_ref_default, t8x8_mode, constrained_intra;
+    int prev_ref_frame_num;    /* PrevRefFrameNum (7.4.3); -1: no reference picture decoded yet */
+    int last_list0[3];         /* RefPicList0 of the last P slice as indices into refs[] (0 = the newest reference picture) */
     /* picture */
     int cw, ch;
     dpic cur, out;             /* `out`: last finished picture (returned by h264o_dec_plane) */
@@ -265,12 +273,17 @@ struct h264o_dec {
     int dbf_idc_pic, dbf_a_pic, dbf_b_pic;   /* filter parameters (the streams read here use one set per picture) */
     int8_t *slice_dbf;         /* per slice: idc | (alpha offset + 6) << 2 | ... kept simple: arrays below */
     int slice_idc[256], slice_oa[256], slice_ob[256];
-    int cur_is_ref, cur_frame_num, cur_is_idr;
+    int cur_is_ref, cur_frame_num, cur_is_idr, cur_pps_id;
     int max_mb_bits, max_level_prefix;
     char err[200];
 };
 
-h264o_dec *h264o_dec_create(void) { return (h264o_dec *)calloc(1, sizeof(h264o_dec)); }
+h264o_dec *h264o_dec_create(void)
+{
+    h264o_dec *d = (h264o_dec *)calloc(1, sizeof(h264o_dec));
+    if (d) d->prev_ref_frame_num = -1;
+    return d;
+}
 static void free_pic(dpic *p) { for (int i = 0; i < 3; i++) { free(p->pl[i]); p->pl[i] = NULL; } }
 void h264o_dec_destroy(h264o_dec *d)
 {
@@ -280,8 +293,15 @@ void h264o_dec_destroy(h264o_dec *d)
     free(d->mb);
     free(d);
 }
-int h264o_dec_width(const h264o_dec *d) { return d->cw - 2 * d->crop_r; }
-int h264o_dec_height(const h264o_dec *d) { return d->ch - 2 * d->crop_b; }
+int h264o_dec_width(const h264o_dec *d) { return d->cw - 2 * (d->crop_l + d->crop_r); }
+int h264o_dec_height(const h264o_dec *d) { return d->ch - 2 * (d->crop_t + d->crop_b); }
+/* frame_crop_left_offset / frame_crop_top_offset in luma samples: where the cropped picture starts inside plane() */
+int h264o_dec_crop_left(const h264o_dec *d) { return 2 * d->crop_l; }
+int h264o_dec_crop_top(const h264o_dec *d) { return 2 * d->crop_t; }
+/* the last decoded picture: was a reference picture; entry idx (0..2) of the RefPicList0 of its last P slice as the number of
+ * reference pictures decoded since that one (0 = the newest; -1 = no picture) */
+int h264o_dec_last_is_ref(const h264o_dec *d) { return d->cur_is_ref; }
+int h264o_dec_ref_age(const h264o_dec *d, int idx) { return idx >= 0 && idx < 3 ? d->last_list0[idx] : -1; }
 int h264o_dec_coded_width(const h264o_dec *d) { return d->cw; }
 int h264o_dec_coded_height(const h264o_dec *d) { return d->ch; }
 const uint8_t *h264o_dec_plane(const h264o_dec *d, int p) { return d->out.pl[p]; }
@@ -323,41 +343,59 @@ static int alloc_pic(const h264o_dec *d, dpic *p)
 }
 
 /* ------------------------------------------------------------------ 7.3.2.1 / 7.3.2.2 parameter sets */
-static int parse_sps(h264o_dec *d, bitr *b)
+static int parse_sps(h264o_dec *dec, bitr *b)
 {
+    dsps sps, *d = &sps;
+    memset(d, 0, sizeof(*d));
     d->profile = (int)rd_u(b, 8);
     rd_u(b, 8); /* constraint flags + reserved */
     d->level = (int)rd_u(b, 8);
-    if (rd_ue(b) != 0) return fail(d, "seq_parameter_set_id != 0");
+    const uint32_t id = rd_ue(b);
+    if (id > 31) return fail(dec, "seq_parameter_set_id > 31");
     if (d->profile == 100 || d->profile == 110 || d->profile == 122 || d->profile == 244 || d->profile == 44 ||
         d->profile == 83 || d->profile == 86 || d->profile == 118 || d->profile == 128) {
-        if (rd_ue(b) != 1) return fail(d, "chroma_format_idc != 1");
-        if (rd_ue(b) || rd_ue(b)) return fail(d, "bit depth != 8");
+        if (rd_ue(b) != 1) return fail(dec, "chroma_format_idc != 1");
+        if (rd_ue(b) || rd_ue(b)) return fail(dec, "bit depth != 8");
         rd_bit(b); /* qpprime_y_zero_transform_bypass_flag */
-        if (rd_bit(b)) return fail(d, "seq_scaling_matrix_present_flag unsupported");
+        if (rd_bit(b)) return fail(dec, "seq_scaling_matrix_present_flag unsupported");
     }
     d->log2_max_frame_num = (int)rd_ue(b) + 4;
     d->poc_type = (int)rd_ue(b);
     if (d->poc_type == 0) d->log2_max_poc_lsb = (int)rd_ue(b) + 4;
-    else if (d->poc_type == 1) return fail(d, "pic_order_cnt_type 1 unsupported");
+    else if (d->poc_type == 1) return fail(dec, "pic_order_cnt_type 1 unsupported");
     d->max_refs = (int)rd_ue(b);
-    if (d->max_refs > D_MAXREF) return fail(d, "max_num_ref_frames > 16");
+    if (d->max_refs > D_MAXREF) return fail(dec, "max_num_ref_frames > 16");
     rd_bit(b); /* gaps_in_frame_num_value_allowed_flag */
     int mbw = (int)rd_ue(b) + 1, mbh = (int)rd_ue(b) + 1;
-    if (!rd_bit(b)) return fail(d, "frame_mbs_only_flag = 0 unsupported");
+    if (!rd_bit(b)) return fail(dec, "frame_mbs_only_flag = 0 unsupported");
     rd_bit(b); /* direct_8x8_inference_flag */
-    d->crop_r = d->crop_b = 0;
-    if (rd_bit(b)) {
-        if (rd_ue(b)) return fail(d, "frame_crop_left_offset unsupported");
+    if (rd_bit(b)) {   /* frame_cropping_flag: offsets in units of two luma samples (4:2:0 frames, 7-19 .. 7-22) */
+        d->crop_l = (int)rd_ue(b);
         d->crop_r = (int)rd_ue(b);
-        if (rd_ue(b)) return fail(d, "frame_crop_top_offset unsupported");
+        d->crop_t = (int)rd_ue(b);
         d->crop_b = (int)rd_ue(b);
+        if (d->crop_l < 0 || d->crop_r < 0 || d->crop_l + d->crop_r >= 8 * mbw || d->crop_t < 0 || d->crop_b < 0 || d->crop_t + d->crop_b >= 8 * mbh)
+            return fail(dec, "frame cropping larger than the picture");
     }
-    if (b->err) return fail(d, "sps truncated");
-    if (mbw != d->mbw || mbh != d->mbh || !d->mb) {
-        d->mbw = mbw; d->mbh = mbh; d->cw = 16 * mbw; d->ch = 16 * mbh;
+    if (b->err) return fail(dec, "sps truncated");
+    if (mbw > 1024 || mbh > 1024) return fail(dec, "picture size");
+    d->mbw = mbw; d->mbh = mbh;
+    d->valid = 1;
+    dec->sps_tab[id] = sps;
+    return 0;
+}
+
+/* the SPS a slice header names through its PPS becomes the active one (a new picture size: new buffers, no references) */
+static int activate_sps(h264o_dec *d, const dsps *s)
+{
+    d->profile = s->profile; d->level = s->level; d->log2_max_frame_num = s->log2_max_frame_num; d->poc_type = s->poc_type;
+    d->log2_max_poc_lsb = s->log2_max_poc_lsb; d->max_refs = s->max_refs;
+    d->crop_l = s->crop_l; d->crop_r = s->crop_r; d->crop_t = s->crop_t; d->crop_b = s->crop_b;
+    if (s->mbw != d->mbw || s->mbh != d->mbh || !d->mb) {
+        if (d->pic_open) return fail(d, "the picture size changes inside a picture");
+        d->mbw = s->mbw; d->mbh = s->mbh; d->cw = 16 * s->mbw; d->ch = 16 * s->mbh;
         free(d->mb);
-        d->mb = (dmb *)calloc((size_t)mbw * mbh, sizeof(dmb));
+        d->mb = (dmb *)calloc((size_t)s->mbw * s->mbh, sizeof(dmb));
         if (!d->mb || alloc_pic(d, &d->cur) || alloc_pic(d, &d->out)) return fail(d, "out of memory");
         for (int i = 0; i < D_MAXREF; i++) free_pic(&d->refs[i]);
         d->nrefs = 0;
@@ -366,31 +404,36 @@ static int parse_sps(h264o_dec *d, bitr *b)
     return 0;
 }
 
-static int parse_pps(h264o_dec *d, bitr *b)
+static int parse_pps(h264o_dec *dec, bitr *b)
 {
-    if (rd_ue(b) || rd_ue(b)) return fail(d, "pic/seq_parameter_set_id != 0");
-    if (rd_bit(b)) return fail(d, "entropy_coding_mode_flag = 1 (CABAC) unsupported by the test decoder");
+    dpps pps, *d = &pps;
+    memset(d, 0, sizeof(*d));
+    const uint32_t id = rd_ue(b), sid = rd_ue(b);
+    if (id > 255 || sid > 31) return fail(dec, "pic_parameter_set_id > 255 or seq_parameter_set_id > 31");
+    d->sps_id = (int)sid;
+    if (rd_bit(b)) return fail(dec, "entropy_coding_mode_flag = 1 (CABAC) unsupported by the test decoder");
     rd_bit(b); /* bottom_field_pic_order_in_frame_present_flag */
-    if (rd_ue(b)) return fail(d, "slice groups unsupported");
+    if (rd_ue(b)) return fail(dec, "slice groups unsupported");
     d->num_ref_default = (int)rd_ue(b) + 1;
     rd_ue(b); /* num_ref_idx_l1_default_active_minus1 */
-    if (rd_bit(b)) return fail(d, "weighted_pred_flag unsupported");
+    if (rd_bit(b)) return fail(dec, "weighted_pred_flag unsupported");
     rd_u(b, 2);
     d->init_qp = 26 + rd_se(b);
     rd_se(b); /* pic_init_qs */
     d->cqp_off[0] = d->cqp_off[1] = rd_se(b);
     d->dbf_ctrl = (int)rd_bit(b);
     d->constrained_intra = (int)rd_bit(b);   /* constrained_intra_pred_flag */
-    if (rd_bit(b)) return fail(d, "redundant_pic_cnt_present_flag unsupported");
+    if (rd_bit(b)) return fail(dec, "redundant_pic_cnt_present_flag unsupported");
     d->t8x8_mode = 0;
-    if (b->err) return fail(d, "pps truncated");
+    if (b->err) return fail(dec, "pps truncated");
     if (more_rbsp_data(b)) {
         d->t8x8_mode = (int)rd_bit(b);
-        if (rd_bit(b)) return fail(d, "pic_scaling_matrix_present_flag unsupported");
+        if (rd_bit(b)) return fail(dec, "pic_scaling_matrix_present_flag unsupported");
         d->cqp_off[1] = rd_se(b);
-        if (b->err) return fail(d, "pps truncated");
+        if (b->err) return fail(dec, "pps truncated");
     }
-    d->have_pps = 1;
+    d->valid = 1;
+    dec->pps_tab[id] = pps;
     return 0;
 }
 
@@ -1291,7 +1334,12 @@ static int finish_picture(h264o_dec *d)
     {
         dpic t = d->out; d->out = d->cur; d->cur = t;   /* out now holds the finished picture; cur gets a scratch buffer */
     }
-    if (d->cur_is_ref) {
+    if (d->cur_is_ref) d->prev_ref_frame_num = d->cur_frame_num;
+    int enters = d->cur_is_ref;   /* 8.2.5.1: only a picture of nal_ref_idc != 0 is marked "used for short-term reference" */
+#ifdef H264O_DEC_MUTATE_NONREF_ENTERS_LIST
+    enters = 1;
+#endif
+    if (enters) {
         if (d->cur_is_idr) { for (int i = 0; i < d->nrefs; i++) { /* all reference pictures become unused */ } d->nrefs = 0; }
         const int cap = d->max_refs > 0 ? d->max_refs : 1;
         /* make room: drop the oldest */
@@ -1357,11 +1405,27 @@ static int build_list0(h264o_dec *d, bitr *b, int frame_num, int nactive, int mo
 
 static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
 {
-    if (!d->have_sps || !d->have_pps) return fail(d, "slice before parameter sets");
     const int first_mb = (int)rd_ue(b);
-    const int st = (int)rd_ue(b) % 5;
+    const uint32_t st_raw = rd_ue(b);
+    if (st_raw > 9) return fail(d, "slice_type out of range");
+    int st = (int)st_raw % 5;   /* 7.4.3: values 5..9 say the same as 0..4, and that every slice of the picture has the type */
+#ifdef H264O_DEC_MUTATE_SLICE_TYPE_7_IS_P
+    if (st_raw == 7 && nal_type != 5) st = 0;   /* (in an IDR picture the planted error would be refused at once: it has to reach the all-I non-IDR pictures) */
+#endif
     if (st != 0 && st != 2) return fail(d, "only I and P slices supported");
-    if (rd_ue(b)) return fail(d, "pic_parameter_set_id != 0");
+    uint32_t pps_id = rd_ue(b);
+#ifdef H264O_DEC_MUTATE_PPS_ID_IGNORED
+    pps_id = 0;
+#endif
+    if (b->err || pps_id > 255 || !d->pps_tab[pps_id].valid) return fail(d, "slice names a picture parameter set that was not sent");
+    {   /* 7.4.1.2.1: the PPS the slice names, and through it the SPS, are the active ones */
+        const dpps *p = &d->pps_tab[pps_id];
+        if (!d->sps_tab[p->sps_id].valid) return fail(d, "slice names a sequence parameter set that was not sent");
+        if (activate_sps(d, &d->sps_tab[p->sps_id])) return -1;
+        d->init_qp = p->init_qp; d->cqp_off[0] = p->cqp_off[0]; d->cqp_off[1] = p->cqp_off[1]; d->dbf_ctrl = p->dbf_ctrl;
+        d->num_ref_default = p->num_ref_default; d->t8x8_mode = p->t8x8_mode; d->constrained_intra = p->constrained_intra;
+        d->have_pps = 1;
+    }
     const int frame_num = (int)rd_u(b, d->log2_max_frame_num);
     if (nal_type == 5) rd_ue(b); /* idr_pic_id */
     if (d->poc_type == 0) rd_u(b, d->log2_max_poc_lsb);
@@ -1371,6 +1435,7 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
         if (nactive > D_MAXREF) return fail(d, "num_ref_idx_l0_active > 16");
         if (nal_type == 5) return fail(d, "P slice in an IDR picture");
         if (build_list0(d, b, frame_num, nactive, rd_bit(b))) return -1;   /* ref_pic_list_modification_flag_l0 */
+        for (int i = 0; i < 3; i++) d->last_list0[i] = d->list0[i];
     }
     if (nal_ref_idc) {
         if (nal_type == 5) { rd_bit(b); if (rd_bit(b)) return fail(d, "long_term_reference_flag unsupported"); }
@@ -1388,12 +1453,27 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
     const int nmb = d->mbw * d->mbh;
     if (first_mb == 0) {
         if (d->pic_open) return fail(d, "new picture before the previous one was complete");
+        /* 7.4.3 (no gaps_in_frame_num here): frame_num is 0 in an IDR picture and PrevRefFrameNum + 1 in every other picture -
+         * a non-reference picture (nal_ref_idc 0) may not repeat PrevRefFrameNum, and leaves it where it was */
+        if (nal_type == 5 && frame_num != 0) return fail(d, "frame_num != 0 in an IDR picture");
+        if (nal_type != 5 && d->prev_ref_frame_num >= 0 && frame_num != ((d->prev_ref_frame_num + 1) & ((1 << d->log2_max_frame_num) - 1)))
+            return fail(d, "frame_num does not follow PrevRefFrameNum");
+        if (nal_type == 5 && !nal_ref_idc) return fail(d, "nal_ref_idc 0 in an IDR picture");
         d->slice_count = 0;
         for (int i = 0; i < nmb; i++) d->mb[i].kind = DMB_NONE;
         d->max_mb_bits = 0; d->max_level_prefix = 0;
         d->cur_is_ref = nal_ref_idc != 0; d->cur_frame_num = frame_num; d->cur_is_idr = nal_type == 5;
         if (nal_type == 5) d->nrefs = 0;   /* 8.2.1: an IDR picture marks all reference pictures unused before it is decoded */
-    } else if (first_mb != d->pic_open) return fail(d, "first_mb_in_slice does not continue the picture (ASO unsupported)");
+        d->cur_pps_id = (int)pps_id;
+    } else {
+        if (first_mb != d->pic_open) return fail(d, "first_mb_in_slice does not continue the picture (ASO unsupported)");
+        /* 7.4.3 / 7.4.1.2.4: frame_num, nal_unit_type and "nal_ref_idc is 0" are the same in every slice of a picture.  The PPS
+         * may legally differ between slices; the streams read here name one per picture, and the per-picture use of its fields
+         * (chroma offsets in the loop filter) relies on that, so another id inside a picture is refused rather than half-applied */
+        if (frame_num != d->cur_frame_num) return fail(d, "frame_num differs between the slices of a picture");
+        if ((nal_ref_idc != 0) != d->cur_is_ref || (nal_type == 5) != d->cur_is_idr) return fail(d, "nal_ref_idc / nal_unit_type differ between the slices of a picture");
+        if ((int)pps_id != d->cur_pps_id) return fail(d, "slices of one picture name different picture parameter sets (unsupported by the test decoder)");
+    }
     if (d->slice_count >= 256) return fail(d, "more than 256 slices");
     const int sl = d->slice_count++;
     d->slice_idc[sl] = idc; d->slice_oa[sl] = oa; d->slice_ob[sl] = ob;

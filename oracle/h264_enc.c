@@ -195,7 +195,15 @@ struct randsyn {
     int direct;          /* inter macroblocks are written from random draws at writing time: sub_mb_types down to 4x4, a
                           * ref_idx_l0 per partition, mvd_l0 values as such (whatever they add up to IS the vector) */
     uint32_t rng;
+    /* picture level (features 16384 / 32768 / 65536; the values of a stream without them: a reference picture, slices all of the
+     * picture's own type written as 7 / 5, PPS 0 with pic_init_qp 26, the configured reference count, deblocking control present) */
+    int is_ref;          /* nal_ref_idc != 0: the slice headers carry dec_ref_pic_marking() */
+    int cur_p, cur_st;   /* the slice whose header is being written: a P slice; slice_type as written */
+    int pps_id, init_qp, nref_default, dbf_ctrl;   /* of the picture parameter set every slice of the picture names */
+    int no_t8x8;         /* High profile: that PPS says transform_8x8_mode_flag = 0 */
 };
+/* one picture parameter set of a random stream (feature 65536 keeps up to four in play) */
+struct rs_pps { int id, init_qp, cqo[2], nref_default, dbf_ctrl, constrained, t8x8; };
 static uint32_t rs_next(uint32_t *s)
 {
     uint32_t x = *s;
@@ -230,6 +238,13 @@ struct h264o_enc {
     int16_t *mvq;          /* 8 int16 per macroblock: vectors of the four 8x8 quadrants of an inter macroblock */
     uint8_t *pshape;       /* P pictures: partition shape the motion search chose (0 16x16, 1 16x8, 2 8x16, 3 8x8) */
     int rs_cqo[2], rs_constrained;   /* what the last parameter sets of h264o_enc_random_picture said (they travel with IDR pictures only) */
+    /* picture-level state of h264o_enc_random_picture (features 16384 / 32768 / 65536); all zero for every other stream */
+    struct rs_pps rs_pps[4];
+    int rs_npps, rs_pps_last;   /* parameter sets in play (0: the single PPS 0); the one the previous picture used */
+    int rs_sps_id, rs_crop_l, rs_crop_t;   /* drawn once per stream; crops in units of two luma samples */
+    int nonref_in_gop, nonref_run;   /* non-reference pictures since the IDR picture; length of the run that is being written */
+    int rs_alt, rs_prev_idr;         /* single-slice pictures alternate I / P; the previous picture was an IDR picture */
+    int32_t rs_last[8];              /* h264o_enc_random_last */
     struct randsyn *rs;   /* h264o_enc_random_picture (decoder-peer tests): syntax the encoder itself never uses; NULL while encoding */
     uint8_t *want_intra;   /* P pictures: 1 = the motion search handed the macroblock to the intra pass; 2 = one of the "nothing
                             * left to code" tests hit: the prediction is the reconstruction, no transform is run (the tests use
@@ -372,6 +387,7 @@ const uint8_t *h264o_enc_source(const h264o_enc *e, int p) { return e->src[p]; }
 const h264o_hits *h264o_enc_hits(const h264o_enc *e) { return &e->hits; }
 void h264o_enc_hits_reset(h264o_enc *e) { memset(&e->hits, 0, sizeof(e->hits)); }
 uint32_t h264o_enc_last_me_cost(const h264o_enc *e) { return e->me_cost; }
+void h264o_enc_random_last(const h264o_enc *e, int32_t out[8]) { memcpy(out, e->rs_last, sizeof(e->rs_last)); }
 const uint8_t *h264o_enc_p_decision(const h264o_enc *e) { return e->want_intra; }
 
 /* ------------------------------------------------------------ headers 7.3.2 */
@@ -382,7 +398,7 @@ static void write_sps(h264o_enc *e, bitw *b)
     /* constraint_set0..5 + 2 reserved bits */
     bw_put(b, 8, prof == 66 ? 0xC0 : prof == 77 ? 0x40 : 0x00);
     bw_put(b, 8, (uint32_t)e->level_idc);
-    bw_ue(b, 0); /* seq_parameter_set_id */
+    bw_ue(b, (uint32_t)e->rs_sps_id); /* seq_parameter_set_id (0 but for the random streams of feature 65536) */
     if (prof == 100) {
         bw_ue(b, 1);     /* chroma_format_idc 4:2:0 */
         bw_ue(b, 0);     /* bit_depth_luma_minus8 */
@@ -405,11 +421,11 @@ static void write_sps(h264o_enc *e, bitw *b)
     bw_put(b, 1, 1); /* frame_mbs_only_flag */
     bw_put(b, 1, 1); /* direct_8x8_inference_flag */
     int cr = (e->cw - e->cfg.width) / 2, cb = (e->ch - e->cfg.height) / 2;
-    if (cr || cb) {
+    if (cr || cb || e->rs_crop_l || e->rs_crop_t) {
         bw_put(b, 1, 1);
-        bw_ue(b, 0);
+        bw_ue(b, (uint32_t)e->rs_crop_l);
         bw_ue(b, (uint32_t)cr);
-        bw_ue(b, 0);
+        bw_ue(b, (uint32_t)e->rs_crop_t);
         bw_ue(b, (uint32_t)cb);
     } else {
         bw_put(b, 1, 0);
@@ -437,27 +453,27 @@ static void write_sps(h264o_enc *e, bitw *b)
     bw_trailing(b);
 }
 
-static void write_pps(h264o_enc *e, bitw *b)
+static void write_pps(h264o_enc *e, bitw *b, const struct rs_pps *p)
 {
-    bw_ue(b, 0);     /* pic_parameter_set_id */
-    bw_ue(b, 0);     /* seq_parameter_set_id */
+    bw_ue(b, (uint32_t)p->id);        /* pic_parameter_set_id */
+    bw_ue(b, (uint32_t)e->rs_sps_id); /* seq_parameter_set_id */
     bw_put(b, 1, 0); /* entropy_coding_mode_flag: CAVLC */
     bw_put(b, 1, 0); /* bottom_field_pic_order_in_frame_present_flag */
     bw_ue(b, 0);     /* num_slice_groups_minus1 */
-    bw_ue(b, (uint32_t)e->nrefs - 1); /* num_ref_idx_l0_default_active_minus1 */
+    bw_ue(b, (uint32_t)p->nref_default - 1); /* num_ref_idx_l0_default_active_minus1 */
     bw_ue(b, 0);     /* num_ref_idx_l1_default_active_minus1 */
     bw_put(b, 1, 0); /* weighted_pred_flag */
     bw_put(b, 2, 0); /* weighted_bipred_idc */
-    bw_se(b, 0);     /* pic_init_qp_minus26 */
+    bw_se(b, p->init_qp - 26);   /* pic_init_qp_minus26 */
     bw_se(b, 0);     /* pic_init_qs_minus26 */
-    bw_se(b, e->rs ? e->rs->cqo[0] : 0);     /* chroma_qp_index_offset */
-    bw_put(b, 1, 1); /* deblocking_filter_control_present_flag */
-    bw_put(b, 1, e->rs && e->rs->constrained ? 1 : 0); /* constrained_intra_pred_flag */
+    bw_se(b, p->cqo[0]);         /* chroma_qp_index_offset */
+    bw_put(b, 1, (uint32_t)p->dbf_ctrl);    /* deblocking_filter_control_present_flag */
+    bw_put(b, 1, (uint32_t)p->constrained); /* constrained_intra_pred_flag */
     bw_put(b, 1, 0); /* redundant_pic_cnt_present_flag */
     if (e->cfg.profile_idc == 100) {
-        bw_put(b, 1, 1); /* transform_8x8_mode_flag: inter macroblocks use the 8x8 transform */
+        bw_put(b, 1, (uint32_t)p->t8x8); /* transform_8x8_mode_flag: inter macroblocks use the 8x8 transform */
         bw_put(b, 1, 0); /* pic_scaling_matrix_present_flag */
-        bw_se(b, e->rs ? e->rs->cqo[1] : 0);     /* second_chroma_qp_index_offset */
+        bw_se(b, p->cqo[1]);     /* second_chroma_qp_index_offset */
     }
     bw_trailing(b);
 }
@@ -465,16 +481,17 @@ static void write_pps(h264o_enc *e, bitw *b)
 static void write_slice_header(h264o_enc *e, bitw *b, int idr, int first_mb)
 {
     bw_ue(b, (uint32_t)first_mb); /* first_mb_in_slice */
-    bw_ue(b, idr ? 7 : 5);    /* slice_type: all slices of the picture I / P */
-    bw_ue(b, 0);              /* pic_parameter_set_id */
+    const int p_slice = e->rs ? e->rs->cur_p : !idr;
+    bw_ue(b, e->rs ? (uint32_t)e->rs->cur_st : idr ? 7 : 5);   /* slice_type: all slices of the picture I / P (the generator: or 2 / 0) */
+    bw_ue(b, e->rs ? (uint32_t)e->rs->pps_id : 0);             /* pic_parameter_set_id */
     if (e->rs && e->rs->ohstyle) bw_put(b, 15, (uint32_t)e->frame_num);
     else
     bw_put(b, 8, (uint32_t)e->frame_num);
     if (idr) bw_ue(b, (uint32_t)e->idr_id);
     if (e->rs && e->rs->ohstyle) bw_put(b, 16, (uint32_t)(2 * e->frame_in_gop) & 0xFFFFu);   /* pic_order_cnt_lsb */
-    if (!idr) {
+    if (p_slice) {
         /* the first pictures after an IDR have fewer reference pictures than the PPS default announces */
-        if (e->avail_refs != e->nrefs) { bw_put(b, 1, 1); bw_ue(b, (uint32_t)e->avail_refs - 1); }
+        if (e->avail_refs != (e->rs ? e->rs->nref_default : e->nrefs)) { bw_put(b, 1, 1); bw_ue(b, (uint32_t)e->avail_refs - 1); }
         else bw_put(b, 1, 0); /* num_ref_idx_active_override_flag */
         if (e->rs && e->rs->reorder) {   /* 7.3.3.1: short-term commands by differences of picture numbers (frame_num never wraps here) */
             int pred = e->frame_num;
@@ -492,11 +509,12 @@ static void write_slice_header(h264o_enc *e, bitw *b, int idr, int first_mb)
     if (idr) {
         bw_put(b, 1, 0); /* no_output_of_prior_pics_flag */
         bw_put(b, 1, 0); /* long_term_reference_flag */
-    } else {
+    } else if (!e->rs || e->rs->is_ref) {   /* (a picture of nal_ref_idc 0 carries no dec_ref_pic_marking()) */
         bw_put(b, 1, 0); /* adaptive_ref_pic_marking_mode_flag */
     }
     if (e->rs) {   /* random-stream generator: its own QP and filter parameters */
-        bw_se(b, (e->rs->slice_first ? e->rs->cur_slice_qp : e->rs->slice_qp[(first_mb / e->mbw / e->slice_rows) & 255]) - 26);
+        bw_se(b, (e->rs->slice_first ? e->rs->cur_slice_qp : e->rs->slice_qp[(first_mb / e->mbw / e->slice_rows) & 255]) - e->rs->init_qp);
+        if (!e->rs->dbf_ctrl) return;   /* no deblocking_filter_control: idc 0 and zero offsets are inferred */
         bw_ue(b, (uint32_t)e->rs->idc);
         if (e->rs->idc != 1) { bw_se(b, e->rs->oa); bw_se(b, e->rs->ob); }
         return;
@@ -1233,6 +1251,8 @@ static int nc_chroma(const h264o_enc *e, int mx, int my, int pl, int b)
     return nA >= 0 ? nA : nB >= 0 ? nB : 0;
 }
 
+/* transform_8x8_mode_flag of the picture parameter set in use: 1 under High, but for a PPS of the generator that says 0 */
+static int t8x8_mode(const h264o_enc *e) { return e->cfg.profile_idc == 100 && !(e->rs && e->rs->no_t8x8); }
 static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
 {
     const h264o_mbinfo *mb = &e->mb[my * e->mbw + mx];
@@ -1258,7 +1278,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
         bw_ue(b, (uint32_t)(p_slice ? 5 : 0));
         e->hits.mb_type[p_slice][p_slice ? 5 : 0]++;
         e->hits.cbp_intra[mb->cbp]++;
-        if (e->cfg.profile_idc == 100) bw_put(b, 1, 0);   /* transform_size_8x8_flag: Intra4x4, not Intra8x8 */
+        if (t8x8_mode(e)) bw_put(b, 1, 0);   /* transform_size_8x8_flag: Intra4x4, not Intra8x8 */
         for (int k = 0; k < 16; k++) {   /* 8.3.1.1: predicted mode = the smaller of the left and upper blocks' modes */
             int x = o_blk_x[k], y = o_blk_y[k], mA, mB, dc_only = 0;
             if (x > 0) mA = am[xy2blk[4 * y + x - 1]];
@@ -1318,7 +1338,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
             int code = 0;
             while (o_cbp_code2inter[code] != mb->cbp) code++;
             bw_ue(b, (uint32_t)code);
-            if (e->cfg.profile_idc == 100 && (mb->cbp & 15) && all8x8) bw_put(b, 1, mb->i16_mode);
+            if (t8x8_mode(e) && (mb->cbp & 15) && all8x8) bw_put(b, 1, mb->i16_mode);
             if (mb->cbp) bw_se(b, qpd);
             goto residual;
         }
@@ -1339,7 +1359,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
         int code = 0;
         while (o_cbp_code2inter[code] != mb->cbp) code++;
         bw_ue(b, (uint32_t)code);
-        if (e->cfg.profile_idc == 100 && (mb->cbp & 15)) bw_put(b, 1, mb->i16_mode); /* transform_size_8x8_flag */
+        if (t8x8_mode(e) && (mb->cbp & 15)) bw_put(b, 1, mb->i16_mode); /* transform_size_8x8_flag */
         if (mb->cbp) bw_se(b, qpd); /* mb_qp_delta */
     }
 residual:
@@ -1410,7 +1430,8 @@ int64_t h264o_enc_encode(h264o_enc *e, const uint8_t *y, int ys, const uint8_t *
         if (pos == (size_t)-1) return -2;
         memset(e->rbsp, 0, 256);
         b = (bitw){e->rbsp, e->rbsp_cap, 0};
-        write_pps(e, &b);
+        const struct rs_pps plain = {0, 26, {0, 0}, e->nrefs, 1, 0, 1};
+        write_pps(e, &b, &plain);
         pos = emit_nal(out, out_cap, pos, 3, 8, e->rbsp, (size_t)(b.bits >> 3));
         if (pos == (size_t)-1) return -2;
     }
@@ -1646,22 +1667,101 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
     memset(&rs, 0, sizeof(rs));
     int *cqo_sticky = e->rs_cqo;   /* the PPS travels with IDR pictures only: its offsets hold until the next one */
     int idr = force_idr || e->frames == 0 || e->frame_in_gop >= e->cfg.gop;
-    if (idr) { e->frame_in_gop = 0; e->frame_num = 0; }
+    if (idr) { e->frame_in_gop = 0; e->frame_num = 0; e->nonref_in_gop = 0; }
     if (is_idr) *is_idr = idr;
-    e->avail_refs = idr ? 0 : (e->frame_in_gop < e->nrefs ? e->frame_in_gop : e->nrefs);
+    /* (reference pictures since the IDR picture: non-reference pictures of feature 16384 do not count) */
+    e->avail_refs = idr ? 0 : (e->frame_in_gop - e->nonref_in_gop < e->nrefs ? e->frame_in_gop - e->nonref_in_gop : e->nrefs);
     rs.qpd = (int8_t *)calloc((size_t)nmb, 1);
+    /* ---- picture level (features 16384, 32768, 65536): drawn from a generator of their own, so that the draws of every other
+     * feature - and with them the streams of every case without these bits - stay what they were.  This block is the one place
+     * that says which parameter set, reference marking and slice types the picture has; the writers read it from rs. */
+    uint32_t prng = (seed ^ 0x5bd1e995u) * 2246822519u + 0x3C6EF372u;
+    rs_next(&prng);
+    rs.is_ref = 1;
+    if (e->frames == 0) {   /* once per stream */
+        e->rs_npps = 0; e->rs_pps_last = -1; e->rs_sps_id = 0; e->rs_crop_l = e->rs_crop_t = 0; e->nonref_run = 0; e->rs_alt = 0;
+        if (features & 65536) {
+            static const int sps_ids[3] = {0, 5, 31};
+            const int k = rs_below(&prng, 3);
+            e->rs_sps_id = sps_ids[k];
+            e->hits.sps_id_used[k]++;
+            /* left / top cropping by 2 or 4 luma samples where the picture stays at least 8 samples wide and high */
+            e->rs_crop_l = e->cfg.width >= 12 ? 1 + rs_below(&prng, 2) : 0;
+            e->rs_crop_t = e->cfg.height >= 12 ? 1 + rs_below(&prng, 2) : 0;
+            if (e->rs_crop_l || e->rs_crop_t) e->hits.crop_lt_streams++;
+        }
+    }
+    int resend = -1;   /* a PPS sent again, with new content, in front of this non-IDR picture */
+    static const int pps_ids[4] = {0, 1, 7, 255};
+    if (features & 65536) {
+        if (idr) {   /* all parameter sets in play travel with the IDR picture: two to four of the four ids, each with its own draw */
+            int order[4] = {0, 1, 2, 3};
+            for (int i = 3; i > 0; i--) { const int j = rs_below(&prng, i + 1), t = order[i]; order[i] = order[j]; order[j] = t; }
+            e->rs_npps = 2 + rs_below(&prng, 3);
+            for (int i = 0; i < e->rs_npps; i++) e->rs_pps[i].id = pps_ids[order[i]];
+        } else if (rs_below(&prng, 3) == 0) resend = rs_below(&prng, e->rs_npps);
+        for (int i = 0; i < e->rs_npps; i++) {
+            if (!idr && i != resend) continue;
+            struct rs_pps *p = &e->rs_pps[i], old = *p;
+            p->init_qp = 26 + rs_below(&prng, 25) - 12;
+            p->cqo[0] = rs_below(&prng, 25) - 12;
+            p->cqo[1] = high ? rs_below(&prng, 25) - 12 : p->cqo[0];
+            p->nref_default = 1 + rs_below(&prng, 3);
+            p->dbf_ctrl = rs_below(&prng, 3) != 0;
+            p->constrained = (features & 1024) ? 1 : rs_below(&prng, 2);
+            p->t8x8 = high ? rs_below(&prng, 4) != 0 : 0;
+            if (!idr && memcmp(&old, p, sizeof(old)) != 0) e->hits.pps_resent++;
+        }
+    }
+    const struct rs_pps plain = {0, 26, {0, 0}, e->nrefs, 1, 0, 1};
+    const struct rs_pps *pps = &plain;   /* (cqo / constrained of the plain PPS are filled from features 2 / 1024 below) */
+    int pps_k = -1;
+    if (features & 65536) {
+        pps_k = rs_below(&prng, e->rs_npps);
+        if (resend >= 0 && rs_below(&prng, 2)) pps_k = resend;   /* often the one that has just changed */
+        pps = &e->rs_pps[pps_k];
+        for (int i = 0; i < 4; i++) if (pps->id == pps_ids[i]) e->hits.pps_id_used[i]++;
+        if (!idr && e->rs_pps_last >= 0 && e->rs_pps[e->rs_pps_last].id != pps->id) e->hits.pps_switches++;
+        if (!pps->dbf_ctrl) e->hits.pics_no_dbf_ctrl++;
+        e->rs_pps_last = pps_k;
+    }
+    rs.pps_id = pps->id; rs.init_qp = pps->init_qp; rs.nref_default = pps->nref_default; rs.dbf_ctrl = pps->dbf_ctrl;
+    rs.no_t8x8 = high && !pps->t8x8;
+    /* feature 16384: a non-IDR picture of nal_ref_idc 0.  POC type 2 (the generator's own header) allows no two in a row
+     * (8.2.1.3); POC type 0 (feature 256) does: runs of up to three */
+    if (features & 16384) {
+        const int most = (features & 256) ? 3 : 1;
+        if (!idr && e->nonref_run < most && rs_below(&prng, 5) < 3) rs.is_ref = 0;
+        if (!rs.is_ref) {
+            e->hits.nonref_pics++;
+            if (e->rs_prev_idr) e->hits.nonref_after_idr++;
+            e->nonref_run++;
+        } else {
+            if (e->nonref_run) { e->hits.nonref_run[e->nonref_run]++; if (idr) e->hits.nonref_before_idr++; }
+            e->nonref_run = 0;
+        }
+    }
+    /* feature 32768: every slice of a non-IDR picture is an I or a P slice; slice_is_i[] by slice number */
+    uint8_t slice_is_i[256];
+    memset(slice_is_i, idr ? 1 : 0, sizeof(slice_is_i));
+    int shape_drawn = -1;   /* 0 all I, 1 an I slice first and a P slice later, 2 a P slice first and an I slice later, 3 all P */
+    if ((features & 32768) && !idr) {
+        shape_drawn = rs_below(&prng, 4);
+        for (int i = 0; i < 256; i++) slice_is_i[i] = (uint8_t)rs_below(&prng, 2);
+    }
     if (idr) {
         cqo_sticky[0] = (features & 2) ? rs_below(&rng, 25) - 12 : 0;
         cqo_sticky[1] = (features & 2) && high ? rs_below(&rng, 25) - 12 : cqo_sticky[0];
     }
     rs.cqo[0] = cqo_sticky[0]; rs.cqo[1] = cqo_sticky[1];
+    if (features & 65536) { rs.cqo[0] = pps->cqo[0]; rs.cqo[1] = pps->cqo[1]; }
     rs.idc = (features & 16) ? rs_below(&rng, 3) : (e->cfg.disable_deblock ? 1 : e->slice_rows < e->mbh ? 2 : 0);
     rs.direct = (features & 32) != 0;
     /* feature 128: reference list modification - up to avail_refs commands naming distinct reference pictures, never the same
      * picture as the command before (a difference of 0 cannot be written) */
     rs.ohstyle = (features & 256) != 0;
     if (idr) e->rs_constrained = (features & 1024) != 0;   /* (the PPS travels with IDR pictures only) */
-    rs.constrained = e->rs_constrained;
+    rs.constrained = (features & 65536) ? pps->constrained : e->rs_constrained;
     rs.reorder = 0; rs.nreorder = 0;
     if (rs.ohstyle && !idr) { rs.reorder = 1; rs.nreorder = 1; rs.reorder_age[0] = 1; }
     if ((features & 128) && !idr && e->frame_num >= e->avail_refs) {
@@ -1685,8 +1785,30 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             rs.slice_first[i] = first;
         }
     }
+    int shape = idr ? 0 : 3;
+    if (shape_drawn >= 0) {   /* feature 32768, now that the number of slices is known */
+        int nsl = (e->mbh + e->slice_rows - 1) / e->slice_rows;
+        if (rs.slice_first) { nsl = 0; for (int i = 0; i < nmb; i++) nsl += rs.slice_first[i] == i; }
+        if (nsl > 256) nsl = 256;
+        if (nsl == 1) {   /* one slice per picture: I and P take turns */
+            if (!(features & 64) && e->cfg.slices <= 1) { slice_is_i[0] = (uint8_t)!e->rs_alt; e->rs_alt = !e->rs_alt; }
+            shape = slice_is_i[0] ? 0 : 3;
+        } else {
+            shape = shape_drawn;
+            if (shape == 0 || shape == 3) memset(slice_is_i, shape == 0, sizeof(slice_is_i));
+            else {   /* mixed: the first slice's type is the shape's, and at least one slice of the other type follows */
+                int other = 0;
+                slice_is_i[0] = (uint8_t)(shape == 1);
+                for (int i = 1; i < nsl; i++) other |= slice_is_i[i] != slice_is_i[0];
+                if (!other) slice_is_i[1 + rs_below(&prng, nsl - 1)] = (uint8_t)!slice_is_i[0];
+            }
+        }
+        e->hits.slice_shape[shape]++;
+        e->hits.slice_type_form[shape == 0 || shape == 3]++;
+    }
     rs.oa = (features & 4) ? rs_below(&rng, 13) - 6 : 0;
     rs.ob = (features & 4) ? rs_below(&rng, 13) - 6 : 0;
+    if (!rs.dbf_ctrl) { rs.idc = 0; rs.oa = rs.ob = 0; }   /* what a slice header without the filter fields means (7.4.3) */
     const int qlo = 4, qhi = 48;   /* QP_Y range drawn from: wide enough for every row of Tables 8-15 / 8-16 that filters */
     for (int i = 0; i < 256; i++) rs.slice_qp[i] = (features & 1) ? qlo + rs_below(&rng, qhi - qlo + 1) : e->cfg.qp;
     /* samples of the I_PCM macroblocks */
@@ -1727,17 +1849,18 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 nslice++;
                 qp = rs.slice_qp[(rs.slice_first ? nslice - 1 : my / e->slice_rows) & 255];
             }
+            const int islice = slice_is_i[(nslice - 1) & 255];   /* the macroblock lies in an I slice */
             const int left = intra_avail(e, mx, my, mx - 1, my), top = intra_avail(e, mx, my, mx, my - 1), topleft = intra_avail(e, mx, my, mx - 1, my - 1);
             int kind = rs_below(&rng, 100);
             /* I picture: I4 45 %, I16 45 %, I_PCM 10 %; P picture: skip 22, 16x16 22, 16x8 10, 8x16 10, 8x8 12, I16 9, I4 9, PCM 6 */
             int type;
-            if (idr) type = kind < 45 ? H264O_MB_I4 : kind < 90 ? H264O_MB_I16 : H264O_MB_IPCM;
+            if (islice) type = kind < 45 ? H264O_MB_I4 : kind < 90 ? H264O_MB_I16 : H264O_MB_IPCM;
             else type = kind < 22 ? H264O_MB_PSKIP : kind < 44 ? H264O_MB_P16 : kind < 54 ? H264O_MB_P16X8 : kind < 64 ? H264O_MB_P8X16
                       : kind < 76 ? H264O_MB_P8X8 : kind < 85 ? H264O_MB_I16 : kind < 94 ? H264O_MB_I4 : H264O_MB_IPCM;
             if (type == H264O_MB_IPCM && !(features & 8)) type = H264O_MB_I16;
-            if (mbi >= skip_from && mbi < skip_to) type = H264O_MB_PSKIP;
+            if (mbi >= skip_from && mbi < skip_to && !islice) type = H264O_MB_PSKIP;
             const int saturate = (features & 8192) && my < e->slice_rows && mbi % 8 < 3;
-            if (saturate) type = idr ? H264O_MB_I4 : H264O_MB_P16;
+            if (saturate) type = islice ? H264O_MB_I4 : H264O_MB_P16;
             int dense_left = (features & 2048) ? 2000 : 0;
             mb->type = (uint8_t)type;
             /* residual density / magnitude of this macroblock (kept small at high QP: 16-bit intermediates of 8.5) */
@@ -1812,7 +1935,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 }
                 mb->mvx = qv[0]; mb->mvy = qv[1];
                 mb->cbp = (uint8_t)(rs_below(&rng, 3) == 0 ? 0 : (rs_below(&rng, 16) | (rs_below(&rng, 3) << 4)));
-                mb->i16_mode = (uint8_t)(high && (mb->cbp & 15) ? rs_below(&rng, 2) : 0);   /* transform_size_8x8_flag */
+                mb->i16_mode = (uint8_t)(high && !rs.no_t8x8 && (mb->cbp & 15) ? rs_below(&rng, 2) : 0);   /* transform_size_8x8_flag */
                 if ((features & 4096) && type == H264O_MB_P16 && mb->cbp == 0 && mb->chroma_mode == 0) {
                     mv_t skip;   /* the encoder writes this macroblock as P_Skip when its vector is the P_Skip one: move it */
                     predict_mv_part(e, mx, my, 0, 0, 2, 2, 0, &skip);
@@ -1857,7 +1980,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             }
             if (mbqp_out) mbqp_out[mbi] = (uint8_t)qp;
         }
-    if ((features & 4096) && any_pcm) rs.idc = 1;   /* the encoder does not filter a picture that holds an I_PCM macroblock */
+    if ((features & 4096) && any_pcm && rs.dbf_ctrl) rs.idc = 1;   /* the encoder does not filter a picture that holds an I_PCM macroblock */
     /* headers and slices, as h264o_enc_encode writes them */
     size_t pos = 0;
     bitw b;
@@ -1870,8 +1993,24 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         pos = emit_nal(out, out_cap, pos, 3, 7, e->rbsp, (size_t)(b.bits >> 3));
         memset(e->rbsp, 0, 256);
         b = (bitw){e->rbsp, e->rbsp_cap, 0};
-        write_pps(e, &b);
+        if (features & 65536) {
+            for (int i = 0; i < e->rs_npps && pos != (size_t)-1; i++) {
+                memset(e->rbsp, 0, 256);
+                b = (bitw){e->rbsp, e->rbsp_cap, 0};
+                write_pps(e, &b, &e->rs_pps[i]);
+                pos = emit_nal(out, out_cap, pos, 3, 8, e->rbsp, (size_t)(b.bits >> 3));
+            }
+        } else {
+        struct rs_pps one = plain;
+        one.cqo[0] = rs.cqo[0]; one.cqo[1] = rs.cqo[1]; one.constrained = rs.constrained;
+        write_pps(e, &b, &one);
         if (pos != (size_t)-1) pos = emit_nal(out, out_cap, pos, 3, 8, e->rbsp, (size_t)(b.bits >> 3));
+        }
+    } else if (resend >= 0) {
+        memset(e->rbsp, 0, 256);
+        b = (bitw){e->rbsp, e->rbsp_cap, 0};
+        write_pps(e, &b, &e->rs_pps[resend]);
+        pos = emit_nal(out, out_cap, pos, 3, 8, e->rbsp, (size_t)(b.bits >> 3));
     }
     memset(e->rbsp, 0, e->rbsp_cap);
     e->nslices_last = 0;
@@ -1882,19 +2021,22 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         else { a1 = a0 + e->slice_rows * e->mbw; if (a1 > nmb) a1 = nmb; }
         b = (bitw){e->rbsp, e->rbsp_cap, 0};
         rs.cur_slice_qp = rs.slice_qp[slice_no & 255];
+        const int p_slice = !slice_is_i[slice_no & 255];
+        rs.cur_p = p_slice;
+        rs.cur_st = (shape == 0 || shape == 3 ? 5 : 0) + (p_slice ? 0 : 2);
         write_slice_header(e, &b, idr, a0);
         int skip_run = 0;
         for (int a = a0; a < a1; a++) {
                 const int mx = a % e->mbw, my = a / e->mbw;
                 const h264o_mbinfo *mb = &e->mb[a];
                 e->mb_bitpos[a] = (uint32_t)b.bits;
-                if (!idr) {
+                if (p_slice) {
                     if (mb->type == H264O_MB_PSKIP) { skip_run++; e->hits.mb_kind[H264O_MB_PSKIP]++; continue; }
                     hit_skip_run(e, skip_run, 0, mb);
                     bw_ue(&b, (uint32_t)skip_run);
                     skip_run = 0;
                 }
-                write_mb(e, &b, mx, my, !idr);
+                write_mb(e, &b, mx, my, p_slice);
             }
         a0 = a1;
         hit_skip_run(e, skip_run, 1, NULL);
@@ -1902,17 +2044,21 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         if (e->nslices_last < 256) e->slice_bits_all[e->nslices_last++] = (int64_t)b.bits + 1;
         bw_trailing(&b);
         if ((b.bits >> 3) > e->rbsp_cap) { pos = (size_t)-1; break; }
-        pos = emit_nal(out, out_cap, pos, idr ? 3 : 2, idr ? 5 : 1, e->rbsp, (size_t)(b.bits >> 3));
+        pos = emit_nal(out, out_cap, pos, idr ? 3 : rs.is_ref ? 2 : 0, idr ? 5 : 1, e->rbsp, (size_t)(b.bits >> 3));
         memset(e->rbsp, 0, (size_t)(b.bits >> 3) + 8);
     }
     e->rs = NULL;
+    e->rs_prev_idr = idr;
+    e->rs_last[0] = rs.is_ref; e->rs_last[1] = rs.pps_id; e->rs_last[2] = e->rs_sps_id; e->rs_last[3] = 2 * e->rs_crop_l;
+    e->rs_last[4] = 2 * e->rs_crop_t; e->rs_last[5] = rs.init_qp; e->rs_last[6] = shape; e->rs_last[7] = rs.dbf_ctrl;
     free(rs.qpd);
     rs.qpd = NULL;
     free(rs.slice_first);
     rs.slice_first = NULL;
     if (pos == (size_t)-1) return -2;
     if (idr) e->idr_id = (e->idr_id + e->idr_step) & 0xFF;
-    e->frame_num = (e->frame_num + 1) & 255;
+    if (rs.is_ref) e->frame_num = (e->frame_num + 1) & 255;   /* (a non-reference picture leaves PrevRefFrameNum where it was) */
+    else e->nonref_in_gop++;
     e->frame_in_gop++;
     e->frames++;
     return (int64_t)pos;

@@ -131,6 +131,18 @@ typedef struct {
     uint32_t max_skip_run, skip_runs_over_a_row, skip_run_ends_slice, pcm_after_skip_run;
     uint32_t long_header_slots;         /* macroblock headers (mb_type .. mb_qp_delta) of more than 64 bits */
     uint32_t long_residual_slots;       /* residual blocks of more than 64 bits */
+    /* picture level, h264o_enc_random_picture with features 16384 / 32768 / 65536 */
+    uint32_t nonref_pics;               /* pictures of nal_ref_idc 0 */
+    uint32_t nonref_run[4];             /* runs of 1, 2, 3 of them (counted when the next reference picture is written; [0] unused) */
+    uint32_t nonref_before_idr, nonref_after_idr;   /* such a picture directly before / directly after an IDR picture */
+    uint32_t slice_shape[4];            /* non-IDR pictures: all slices I, an I slice first and a P slice later, a P slice first and an I slice later, all P */
+    uint32_t slice_type_form[2];        /* ... with slice_type written as 0..4 / as 5..9 */
+    uint32_t pps_switches;              /* pictures that name another PPS than the picture before */
+    uint32_t pps_resent;                /* PPS sent again with changed content in front of a non-IDR picture */
+    uint32_t pics_no_dbf_ctrl;          /* pictures under a PPS with deblocking_filter_control_present_flag = 0 */
+    uint32_t pps_id_used[4];            /* pictures by pic_parameter_set_id 0, 1, 7, 255 */
+    uint32_t sps_id_used[3];            /* streams by seq_parameter_set_id 0, 5, 31 */
+    uint32_t crop_lt_streams;           /* streams whose SPS crops on the left / top */
 } h264o_hits;
 const h264o_hits *h264o_enc_hits(const h264o_enc *e);
 void h264o_enc_hits_reset(h264o_enc *e);
@@ -160,10 +172,21 @@ const uint8_t *h264o_enc_p_decision(const h264o_enc *e);
  * then a run of P_Skip macroblocks longer than a row, and I_PCM samples that are all zero (emulation prevention),
  * 8192 (tests of the refusal path only, NOT conforming: macroblocks far beyond the 3200 bits of A.3.1) two macroblocks in five of
  * the first slice carry escape levels in every position.
- * 2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
+ * 16384 non-reference pictures (nal_ref_idc 0, no dec_ref_pic_marking, frame_num = PrevRefFrameNum + 1; one between reference
+ * pictures, with 256 - POC type 0 - runs of up to three), 32768 every slice of a non-IDR picture is an I or a P slice (all-I non-IDR
+ * pictures, I before P, P before I, all-P; slice_type 7 / 5 only when all slices share the type; one slice per picture: I and P
+ * take turns), 65536 parameter sets: seq_parameter_set_id from {0, 5, 31}, two to four PPS with ids from {0, 1, 7, 255}, each
+ * with its own pic_init_qp, chroma offsets, num_ref_idx_l0_default_active, deblocking_filter_control_present_flag,
+ * constrained_intra_pred_flag and (High) transform_8x8_mode_flag, all sent with the IDR picture, one sent again with new content
+ * before some non-IDR pictures, one PPS per picture; and frame cropping on the left and top by 2 or 4 luma samples.
+ * These three draw from a generator of their own.  2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
  * macroblock (0 for I_PCM, the value the loop filter uses).  Side information: h264o_enc_mbinfo / _mvq / _mbaux / _levels. */
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
                                  int *is_idr, uint8_t *mbqp_out);
+
+/* the last picture of h264o_enc_random_picture: is a reference picture, pic_parameter_set_id, seq_parameter_set_id, left crop and
+ * top crop in luma samples, pic_init_qp, slice-type shape (h264o_hits.slice_shape; an IDR picture: 0), deblocking control present */
+void h264o_enc_random_last(const h264o_enc *e, int32_t out[8]);
 
 /* ---- stand-alone stage functions (kernel-level parity, known-answer tests) ---- */
 void h264o_fdct4x4(const int16_t in[16], int16_t out[16]);
@@ -215,6 +238,10 @@ void h264o_dec_destroy(h264o_dec *d);
 int h264o_dec_decode(h264o_dec *d, const uint8_t *data, size_t len);
 int h264o_dec_width(const h264o_dec *d);         /* cropped */
 int h264o_dec_height(const h264o_dec *d);
+int h264o_dec_crop_left(const h264o_dec *d);     /* frame_crop_left_offset / _top_offset in luma samples: the cropped picture starts there in plane() */
+int h264o_dec_crop_top(const h264o_dec *d);
+int h264o_dec_last_is_ref(const h264o_dec *d);   /* the last picture had nal_ref_idc != 0 */
+int h264o_dec_ref_age(const h264o_dec *d, int idx);   /* RefPicList0[idx] of its last P slice: reference pictures decoded since that one (-1 none) */
 int h264o_dec_coded_width(const h264o_dec *d);
 int h264o_dec_coded_height(const h264o_dec *d);
 const uint8_t *h264o_dec_plane(const h264o_dec *d, int plane); /* coded size, pitch = coded w */

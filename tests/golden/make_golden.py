@@ -71,6 +71,10 @@ RANDOM_CASES = [
     ("rand_qcif_everything", 176, 144, 100, 0, 3, 511, 6),                       # + slices of any shape, list modification, OpenH264-style headers
     ("rand_qcif_openh264_shape", 176, 144, 66, 0, 1, 256 | 1 | 2 | 4 | 32, 6),  # one reference, QP per macroblock, offsets, sub-partitions
     ("rand_qcif_all_features", 176, 144, 100, 0, 3, 2047, 6),                    # + levels beyond a byte, constrained_intra_pred_flag
+    # picture level: non-reference pictures, I / P slices in any non-IDR picture, several parameter sets with left / top cropping
+    ("rand_96x80_nonref_slice_types", 96, 80, 66, 2, 3, 16384 | 32768 | 1 | 128, 8),
+    ("rand_112x64_parameter_sets_high", 112, 64, 100, 3, 2, 65536 | 32768 | 1 | 4 | 32, 8),
+    ("rand_96x80_picture_level_all", 96, 80, 100, 0, 3, 16384 | 32768 | 65536 | 63 | 128 | 256 | 1024, 8),
 ]
 
 

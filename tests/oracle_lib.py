@@ -30,7 +30,11 @@ class Hits(C.Structure):
                 ("cbp_intra", C.c_uint32 * 48), ("cbp_inter", C.c_uint32 * 48), ("i4_mode", C.c_uint32 * 9 * 16),
                 ("max_mvd", C.c_uint32), ("max_skip_run", C.c_uint32), ("skip_runs_over_a_row", C.c_uint32),
                 ("skip_run_ends_slice", C.c_uint32), ("pcm_after_skip_run", C.c_uint32), ("long_header_slots", C.c_uint32),
-                ("long_residual_slots", C.c_uint32)]
+                ("long_residual_slots", C.c_uint32),
+                # picture level (random_picture with RAND_NONREF / RAND_SLICE_TYPES / RAND_PARAMETER_SETS)
+                ("nonref_pics", C.c_uint32), ("nonref_run", C.c_uint32 * 4), ("nonref_before_idr", C.c_uint32), ("nonref_after_idr", C.c_uint32),
+                ("slice_shape", C.c_uint32 * 4), ("slice_type_form", C.c_uint32 * 2), ("pps_switches", C.c_uint32), ("pps_resent", C.c_uint32),
+                ("pics_no_dbf_ctrl", C.c_uint32), ("pps_id_used", C.c_uint32 * 4), ("sps_id_used", C.c_uint32 * 3), ("crop_lt_streams", C.c_uint32)]
     MAX_FIELDS = ("max_mvd", "max_skip_run")
 
     def arrays(self):
@@ -98,11 +102,13 @@ def lib():
         L.h264o_enc_hits.argtypes = [vp]
         L.h264o_enc_hits_reset.restype = None
         L.h264o_enc_hits_reset.argtypes = [vp]
+        L.h264o_enc_random_last.restype = None
+        L.h264o_enc_random_last.argtypes = [vp, vp]
         L.h264o_dec_create.restype = vp
         L.h264o_dec_destroy.argtypes = [vp]
         L.h264o_dec_decode.argtypes = [vp, vp, C.c_size_t]
         for n in ("h264o_dec_width", "h264o_dec_height", "h264o_dec_coded_width", "h264o_dec_coded_height",
-                  "h264o_dec_last_slice_type", "h264o_dec_last_nal_type"):
+                  "h264o_dec_last_slice_type", "h264o_dec_last_nal_type", "h264o_dec_crop_left", "h264o_dec_crop_top", "h264o_dec_last_is_ref"):
             getattr(L, n).argtypes = [vp]
         L.h264o_dec_plane.restype = vp
         L.h264o_dec_plane.argtypes = [vp, C.c_int]
@@ -110,6 +116,7 @@ def lib():
         L.h264o_dec_error.argtypes = [vp]
         for n in ("h264o_dec_max_mb_bits", "h264o_dec_max_level_prefix"):
             getattr(L, n).argtypes = [vp]
+        L.h264o_dec_ref_age.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_kind.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_qp.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_mv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -179,6 +186,9 @@ class OracleEncoder:
     # not part of RAND_ALL (the decoder-peer tests): dense residual blocks; syntax the encoder's entropy stage codes to the same bytes
     # (mi355x_h264_debug_code_syntax); a first slice that outgrows its payload share (refusal path only, not conforming)
     RAND_DENSE, RAND_ENCODER_SHAPED, RAND_SATURATE_FIRST_SLICE = 2048, 4096, 8192
+    # picture level: non-reference pictures; I and P slices in any non-IDR picture; several parameter sets, left / top cropping
+    RAND_NONREF, RAND_SLICE_TYPES, RAND_PARAMETER_SETS = 16384, 32768, 65536
+    SHAPE_ALL_I, SHAPE_I_THEN_P, SHAPE_P_THEN_I, SHAPE_ALL_P = 0, 1, 2, 3
 
     def random_picture(self, seed, force_idr=False, features=31):
         """one picture of random conforming syntax (h264o_enc_random_picture): (access unit, is_idr, QP_Y per macroblock);
@@ -191,6 +201,13 @@ class OracleEncoder:
         if n < 0:
             raise RuntimeError("oracle random picture failed %d" % n)
         return bytes(self.out[:n]), bool(idr.value), mbqp
+
+    def random_last(self):
+        """picture level of the last random_picture: is_ref, pps_id, sps_id, crop_left, crop_top (luma samples), pic_init_qp,
+        shape (SHAPE_*), deblock_control"""
+        a = np.zeros(8, np.int32)
+        lib().h264o_enc_random_last(self.h, _ptr(a))
+        return dict(zip(("is_ref", "pps_id", "sps_id", "crop_left", "crop_top", "pic_init_qp", "shape", "deblock_control"), (int(v) for v in a)))
 
     def _plane(self, fn, p):
         cw, ch = (self.cw, self.ch) if p == 0 else (self.cw // 2, self.ch // 2)
@@ -311,6 +328,25 @@ class OracleDecoder:
     @property
     def size(self):
         return lib().h264o_dec_width(self.h), lib().h264o_dec_height(self.h)
+
+    @property
+    def crop(self):
+        """(left, top) in luma samples: where the cropped picture of `size` starts inside plane(0)"""
+        return lib().h264o_dec_crop_left(self.h), lib().h264o_dec_crop_top(self.h)
+
+    def cropped(self, p):
+        """plane p cut to the display size by the decoder's own crop offsets"""
+        (w, h), (x, y) = self.size, self.crop
+        s = 2 if p else 1
+        return self.plane(p)[y // s:(y + h) // s, x // s:(x + w) // s]
+
+    @property
+    def last_is_ref(self):
+        return bool(lib().h264o_dec_last_is_ref(self.h))
+
+    def ref_ages(self):
+        """RefPicList0 of the last P slice: per entry, the number of reference pictures decoded since that one"""
+        return tuple(lib().h264o_dec_ref_age(self.h, i) for i in range(3))
 
     # statistics of the last decoded picture
     KIND_I4, KIND_I16, KIND_IPCM, KIND_INTER, KIND_SKIP = 1, 2, 3, 4, 5

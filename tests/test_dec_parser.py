@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 from media_amd import synth, h264dec
 from oracle_lib import OracleEncoder, OracleDecoder
+import picture_level
+from picture_level import PICTURE_LEVEL_CASES
 
 CASES = [("s1", 176, 144, 26, 66, 0, 0), ("cut", 208, 160, 28, 66, 0, 0), ("split", 176, 144, 26, 66, 0, 0), ("s3", 96, 80, 30, 66, 0, 0),
          ("s3", 64, 48, 10, 66, 0, 0), ("split", 208, 160, 30, 100, 2, 0), ("cut", 176, 144, 22, 77, 3, 3), ("scroll", 130, 98, 30, 100, 0, 2),
@@ -74,6 +76,8 @@ def test_parser_survives_damaged_streams():
     for (kind, w, h, qp, prof, refs, slices) in (("cut", 96, 80, 28, 66, 0, 0), ("split", 96, 80, 26, 100, 2, 0), ("s3", 64, 48, 12, 77, 3, 2), ("s1", 48, 32, 40, 66, 0, 0)):
         enc = OracleEncoder(w, h, qp=qp, gop=3, profile_idc=prof, refs=refs, slices=slices)
         streams.append([enc.encode(f)[0] for f in synth.sequence(kind, w, h, 4)])
+    # and one random-syntax stream with non-reference pictures, mixed slice types and several parameter sets
+    streams.append([au for au, _, _ in picture_level.pictures((48, 32, 100, 2, 2, 16384 | 32768 | 65536 | 1 | 32), 8, 4)[0]])
     par = h264dec.Parser()
     ok = bad = 0
     for case in range(3000):
@@ -265,7 +269,8 @@ def test_parser_under_address_sanitizer(tmp_path):
         pytest.skip("sanitizer build not available: " + r.stderr[-200:])
     rng = random.Random(5)
     units = []
-    for (w, h, prof, sl, refs, feat) in ((96, 80, 66, 0, 3, 511), (112, 64, 100, 2, 2, 255), (48, 32, 77, 0, 1, 256 | 1 | 2 | 32)):
+    for (w, h, prof, sl, refs, feat) in ((96, 80, 66, 0, 3, 511), (112, 64, 100, 2, 2, 255), (48, 32, 77, 0, 1, 256 | 1 | 2 | 32),
+                                         (48, 32, 100, 2, 2, 16384 | 32768 | 65536 | 1 | 32 | 256)):
         enc = OracleEncoder(w, h, qp=30, gop=4, profile_idc=prof, slices=sl, refs=refs)
         aus = [enc.random_picture(rng.getrandbits(30), features=feat)[0] for _ in range(10)]
         for rep in range(50):
@@ -434,4 +439,169 @@ def test_a_dropped_reference_picture_is_noticed():
     with pytest.raises(h264dec.StreamError, match="without a reference"):
         par.parse(aus[9])                                  # ... and the picture after it is not decoded against a stale list
     assert par.parse(aus[10]) and par.parse(aus[11])       # picture 10 is an IDR picture
+    par.close()
+
+
+# ---- picture level: non-reference pictures, I / P slices in any non-IDR picture, parameter sets by id, left / top cropping ----
+_COUNTERS = ("nonref_pics", "nonref_run", "nonref_before_idr", "nonref_after_idr", "slice_shape", "slice_type_form", "pps_switches",
+             "pps_resent", "pics_no_dbf_ctrl", "pps_id_used", "sps_id_used", "crop_lt_streams")
+
+
+def test_picture_level_cases_cover_what_they_claim():
+    """PICTURE_LEVEL_CASES by the generator's own counters: non-reference pictures in runs of one, two and three, directly before
+    and directly after an IDR picture; the four slice-type shapes (all I in a non-IDR picture, I then P, P then I, all P) with
+    slice_type written as 0..4 and as 5..9; PPS switches between consecutive pictures, PPS sent again with changed content,
+    pictures under a PPS without deblocking control; every PPS id and SPS id; left / top cropping.  Every counter is non-zero
+    over the list, and each shape and each run length occurs in at least three different cases."""
+    total = None
+    shape_cases, run_cases = np.zeros(4, int), np.zeros(4, int)
+    bits = {16384: False, 32768: False, 65536: False}
+    for case in PICTURE_LEVEL_CASES:
+        _, hits = picture_level.pictures(case)
+        h = {k: hits[k].astype(np.int64) for k in _COUNTERS}
+        total = h if total is None else {k: total[k] + h[k] for k in _COUNTERS}
+        shape_cases += h["slice_shape"] > 0
+        run_cases += h["nonref_run"] > 0
+        print(case, {k: h[k].tolist() for k in _COUNTERS})
+    print("total", {k: total[k].tolist() for k in _COUNTERS})
+    for k in _COUNTERS:
+        v = total[k][1:] if k == "nonref_run" else total[k]
+        assert np.all(v > 0), (k, total[k])
+    assert np.all(shape_cases >= 3), shape_cases
+    assert np.all(run_cases[1:] >= 3), run_cases
+    feats = [c[5] for c in PICTURE_LEVEL_CASES]
+    for want in (16384, 32768, 65536, 16384 | 32768, 16384 | 65536, 32768 | 65536, 114688):
+        assert any(f & 114688 == want for f in feats), want
+    assert any(f & (114688 | 63 | 128 | 256 | 1024) == (114688 | 63 | 128 | 256 | 1024) for f in feats)
+    assert {c[4] for c in PICTURE_LEVEL_CASES} >= {1, 2, 3} and {c[3] for c in PICTURE_LEVEL_CASES} >= {0, 2, 3}
+    assert {c[2] for c in PICTURE_LEVEL_CASES} == {66, 77, 100} and sum(bool(c[5] & 64) for c in PICTURE_LEVEL_CASES) >= 2
+
+
+_KIND_OF = {0: 2, 4: 1, 3: 3, 1: 4, 5: 4, 6: 4, 7: 4, 2: 5}   # product type -> oracle decoder kind (I16, I4, I_PCM, inter, skip)
+
+
+@pytest.mark.parametrize("case", PICTURE_LEVEL_CASES, ids=["%dx%d_p%d_s%d_r%d_f%d" % c for c in PICTURE_LEVEL_CASES])
+def test_parser_reads_picture_level_streams(case):
+    """Every picture of every PICTURE_LEVEL_CASES stream: the product parser reads back what was written (the side information of
+    test_parser_reads_random_streams), and besides: is_ref, QP_Y per macroblock under the PPS the picture names (pic_init_qp
+    differs between them), the display size after left / top cropping, and the reference list as ages.  The oracle's independent
+    decoder accepts every access unit and agrees on macroblock kinds, on the vector and reference index of every 4x4 block, on the
+    QPs, on is_ref, on the size and on the list.  Neither may refuse an access unit."""
+    w, h, prof, slices, refs, features = case
+    enc = picture_level.encoder(case)
+    par, dec = h264dec.Parser(), OracleDecoder()
+    refs_held = 0
+    for i in range(picture_level.PICTURES):
+        au, idr, mbqp = enc.random_picture(picture_level.seed(case, i), features=features)
+        last = enc.random_last()
+        label = "picture %d (%s)" % (i, last)
+        assert dec.decode(au) == 1, label
+        assert par.parse(au), label
+        _compare_side_information(par, enc, label, vectors=not (features & 32))
+        mb = par.arrays()[0]
+        assert [_KIND_OF[int(t)] for t in mb["type"]] == list(dec.mb_kinds()), label
+        mv4, refq = par.vectors4()
+        for a in np.nonzero(np.isin(mb["type"], (1, 2, 5, 6, 7)))[0]:
+            for b in range(16):
+                got = (int(mv4[a, b, 0]), int(mv4[a, b, 1]), int(refq[a, 2 * (b >> 3) + ((b >> 1) & 1)]))
+                assert got == dec.mb_mv(int(a), b), "%s macroblock %d block %d" % (label, a, b)
+        assert np.array_equal(par.mbqp(), mbqp), label + ": QP_Y"
+        assert np.array_equal(dec.mb_qps(), mbqp.astype(np.int32)), label + ": QP_Y (oracle decoder)"
+        info = par.info()
+        assert bool(info["idr"]) == idr and bool(info["is_ref"]) == bool(last["is_ref"]) == dec.last_is_ref, label
+        assert (info["width"], info["height"]) == (w - last["crop_left"], h - last["crop_top"]) == dec.size, label
+        assert dec.crop == (last["crop_left"], last["crop_top"])
+        if idr:
+            refs_held = 0
+        assert (info["num_ref_active"] == 0) == (last["shape"] == 0), label + ": a list where, and only where, a P slice was written"
+        if info["num_ref_active"]:   # a P slice in the picture: its list, entry by entry, as "reference pictures ago"
+            assert info["num_ref_active"] <= refs_held, label
+            ages = dec.ref_ages()
+            for r in range(info["num_ref_active"]):
+                assert info["ref_age%d" % r] == ages[r] and 0 <= ages[r] < refs_held, "%s: list entry %d" % (label, r)
+        refs_held = min(refs_held + int(last["is_ref"]), max(refs, 1))
+    par.close()
+
+
+def _oracle_reference_pictures(aus):
+    dec, out = OracleDecoder(), []
+    for au in aus:
+        assert dec.decode(au) == 1
+        out.append((dec.last_is_ref, [dec.plane(p) for p in range(3)]))
+    return out
+
+
+@pytest.mark.parametrize("case", [c for c in PICTURE_LEVEL_CASES if c[5] & 16384], ids=lambda c: "%dx%d_f%d" % (c[0], c[1], c[5]))
+def test_dropping_non_reference_pictures_changes_no_reference_picture(case):
+    """A non-reference picture is one that nothing is predicted from: the stream without its nal_ref_idc 0 pictures must decode
+    to the same reference pictures, sample for sample.  Checked on the oracle's independent decoder by itself (a decoder that lets
+    a non-reference picture into its list fails this without a second opinion) and on the product parser (it accepts the
+    thinned stream: frame_num still follows PrevRefFrameNum)."""
+    aus = [au for au, _, _ in picture_level.pictures(case)[0]]
+    full = _oracle_reference_pictures(aus)
+    thin, index = picture_level.thinned(aus)
+    assert 0 < len(thin) < len(aus) and index == [i for i, (is_ref, _) in enumerate(full) if is_ref]
+    par = h264dec.Parser()
+    for (is_ref, planes), i, au in zip(_oracle_reference_pictures(thin), index, thin):
+        assert is_ref and par.parse(au) and par.info()["is_ref"] == 1
+        for p in range(3):
+            assert np.array_equal(planes[p], full[i][1][p]), "picture %d plane %d" % (i, p)
+    par.close()
+
+
+def _sets_and_idr():
+    """an intact IDR picture of the oracle encoder at 48x32 (six macroblocks; 8-bit frame_num, POC type 2, PPS 0 with deblocking
+    control), the stream the crafted units below belong to"""
+    enc = OracleEncoder(48, 32, qp=30, gop=30)
+    return enc.encode(synth.sequence("s1", 48, 32, 1)[0])[0]
+
+
+def _skip_slice(first_mb, run, pps_id=0, frame_num=1, hdr=0x41, slice_type=5):
+    """a P slice of nothing but one mb_skip_run"""
+    b = _Bits().ue(first_mb).ue(slice_type).ue(pps_id).u(8, frame_num)
+    b.u(1, 0).u(1, 0)                # num_ref_idx_active_override_flag, ref_pic_list_modification_flag_l0
+    if hdr >> 5:
+        b.u(1, 0)                    # adaptive_ref_pic_marking_mode_flag (reference pictures only)
+    return b.se(0).ue(1).ue(run).nal(hdr)
+
+
+def test_picture_level_refusals_stay_refusals():
+    """Four units the parser must refuse, each with a message that names the reason, and after each the next IDR picture decodes:
+    a picture whose slices name PPS with different chroma offsets (the documented limit: one PPS's chroma offsets per picture), a
+    slice naming a PPS id that was never sent, a non-reference picture whose frame_num equals PrevRefFrameNum (7.4.3), a P slice
+    inside an IDR picture.  The crafted slices are sound: their conforming forms parse."""
+    idr = _sets_and_idr()
+    # PPS 1: as the encoder's PPS 0 (CAVLC, one reference, pic_init_qp 26, deblocking control) with chroma_qp_index_offset 3
+    pps1 = _Bits().ue(1).ue(0).u(1, 0).u(1, 0).ue(0).ue(0).ue(0).u(1, 0).u(2, 0).se(0).se(0).se(3).u(1, 1).u(1, 0).u(1, 0).nal(0x68)
+    par = h264dec.Parser()
+    assert par.parse(idr)
+    assert par.parse(_skip_slice(0, 3, slice_type=0) + _skip_slice(3, 3, slice_type=0)), "two slices under one PPS: a conforming picture"
+    assert par.parse(idr) and par.parse(pps1 + _skip_slice(0, 6, pps_id=1)) and par.info()["cqo_cb"] == 3, "PPS 1 by itself is usable"
+    assert par.parse(idr) and par.parse(_skip_slice(0, 6, hdr=0x01)) and par.info()["is_ref"] == 0, "a non-reference picture, frame_num 1"
+    assert par.parse(_skip_slice(0, 6)), "... and the reference picture after it has the same frame_num"
+    for unit, reason in ((pps1 + _skip_slice(0, 3, slice_type=0) + _skip_slice(3, 3, pps_id=1, slice_type=0), "chroma QP offsets differ"),
+                         (_skip_slice(0, 6, pps_id=9), "missing parameter set"),
+                         (_skip_slice(0, 6, frame_num=0, hdr=0x01), "does not follow"),
+                         (_Bits().ue(0).ue(0).ue(0).u(8, 0).ue(0).u(1, 0).u(1, 0).u(1, 0).u(1, 0).se(0).ue(1).ue(6).nal(0x65), "P slice in an IDR picture")):
+        assert par.parse(idr)
+        with pytest.raises(h264dec.StreamError, match=reason):
+            par.parse(unit)
+        assert par.parse(idr), "the next IDR picture decodes"
+    # the independent decoder refuses, each by its reason, the three that are not a limit of the product
+    p_in_idr = _Bits().ue(0).ue(0).ue(0).u(8, 0).ue(0).u(1, 0).u(1, 0).u(1, 0).u(1, 0).se(0).ue(1).ue(6).nal(0x65)
+    for unit, reason in ((_skip_slice(0, 6, pps_id=9), "parameter set that was not sent"),
+                         (_skip_slice(0, 6, frame_num=0, hdr=0x01), "does not follow PrevRefFrameNum"),
+                         (p_in_idr, "P slice in an IDR picture")):
+        dec = OracleDecoder()
+        assert dec.decode(idr) == 1
+        with pytest.raises(RuntimeError, match=reason):
+            dec.decode(unit)
+        assert dec.decode(idr) == 1
+    # ... and what may not change inside a picture (7.4.3): frame_num, the reference marking
+    for unit, reason in ((_skip_slice(0, 3, slice_type=0) + _skip_slice(3, 3, slice_type=0, frame_num=2), "frame_num differs between the slices"),
+                         (_skip_slice(0, 3, slice_type=0) + _skip_slice(3, 3, slice_type=0, hdr=0x01), "nal_ref_idc / nal_unit_type differ")):
+        dec = OracleDecoder()
+        assert dec.decode(idr) == 1
+        with pytest.raises(RuntimeError, match=reason):
+            dec.decode(unit)
     par.close()

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 from media_amd import capi, synth, h264dec
 from oracle_lib import OracleEncoder, OracleDecoder
+import picture_level
+from picture_level import PICTURE_LEVEL_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -160,16 +162,124 @@ def test_decoder_against_the_committed_random_stream_vectors():
         dec.close()
 
 
-def test_decoder_long_stream_across_frame_num_wraps():
+@pytest.mark.parametrize("features", [1 | 32 | 128, 16384 | 128 | 1], ids=["qp_subparts_reorder", "nonref_reorder_qp"])
+def test_decoder_long_stream_across_frame_num_wraps(features):
     """600 pictures of one GOP (8-bit frame_num: it wraps twice), three reference pictures, list modification in most P slices,
     QP per macroblock, sub-partitions: PicNum / FrameNumWrap arithmetic (8.2.4.1) and the reconstruction ring over a long run -
-    every picture equals the independent decoder's."""
+    every picture equals the independent decoder's.  Second form: non-reference pictures (feature 16384) hold frame_num back
+    while it wraps, and the list modifications name PicNums counted over the reference pictures only."""
     w = h = 48
     enc = OracleEncoder(w, h, qp=30, gop=1000, profile_idc=66, refs=3)
     ref_dec, dec = OracleDecoder(), h264dec.Decoder()
     for i in range(600):
-        au = enc.random_picture(7 * i + 1, features=1 | 32 | 128)[0]
+        au = enc.random_picture(7 * i + 1, features=features)[0]
         assert ref_dec.decode(au) == 1 and dec.decode(au), "picture %d" % i
         for p in range(3):
             assert np.array_equal(dec.plane(p), ref_dec.plane(p)), "picture %d plane %d" % (i, p)
     dec.close()
+
+
+# whole-row slice bands of a CIF picture run as parallel wavefronts, here with I and P slices side by side
+PICTURE_LEVEL_GPU_CASES = PICTURE_LEVEL_CASES + [(352, 288, 100, 3, 3, 16384 | 32768 | 65536 | 1 | 2 | 4)]
+
+
+def _i420_of(ref_dec):
+    return np.concatenate([ref_dec.cropped(p).ravel() for p in range(3)])
+
+
+@pytest.mark.parametrize("case", PICTURE_LEVEL_GPU_CASES, ids=["%dx%d_p%d_s%d_r%d_f%d" % c for c in PICTURE_LEVEL_GPU_CASES])
+def test_decoder_equals_the_independent_decoder_on_picture_level_streams(case):
+    """tests/picture_level.py PICTURE_LEVEL_CASES (tests/test_dec_parser.py proves what they hold): non-reference pictures - decoded
+    into the ring slot the next picture overwrites, so each is read right after its decode call -, I and P slices in any
+    non-IDR picture (all-I pictures that leave the ring running, either order inside a picture), parameter sets by id with
+    their own pic_init_qp / chroma offsets / default reference count / transform mode and absent deblocking control, and left /
+    top cropping.  Every picture, coded planes and cropped output, equals the oracle's independent decoder's: integer kernels,
+    no tolerance."""
+    w, h, prof, slices, refs, features = case
+    enc = picture_level.encoder(case)
+    ref_dec, dec = OracleDecoder(), h264dec.Decoder()
+    for i in range(picture_level.PICTURES):
+        au, idr, mbqp = enc.random_picture(picture_level.seed(case, i), features=features)
+        assert ref_dec.decode(au) == 1
+        assert dec.decode(au), "picture %d" % i
+        for p in range(3):
+            got, want = dec.plane(p), ref_dec.plane(p)
+            if not np.array_equal(got, want):
+                ys, xs = np.nonzero(got != want)
+                s = 16 if p == 0 else 8
+                k = (int(ys[0]) // s) * ((w + 15) // 16) + int(xs[0]) // s
+                raise AssertionError("picture %d (%s, %s) plane %d: %d samples differ, first in macroblock %d (type %d, QP %d)"
+                                     % (i, "IDR" if idr else "non-IDR", enc.random_last(), p, ys.size, k, int(enc.mbinfo()["type"][k]), int(mbqp[k])))
+        assert dec.info()[:2] == ref_dec.size == (w - enc.random_last()["crop_left"], h - enc.random_last()["crop_top"])
+        assert np.array_equal(dec.i420(), _i420_of(ref_dec)), "picture %d: cropped output" % i
+    dec.close()
+
+
+@pytest.mark.parametrize("case", [c for c in PICTURE_LEVEL_CASES if c[5] & 16384], ids=lambda c: "%dx%d_f%d" % (c[0], c[1], c[5]))
+def test_dropping_non_reference_pictures_changes_no_reference_picture_on_the_gpu(case):
+    """The stream in full into one Decoder, the stream without its nal_ref_idc 0 pictures into another: every reference picture
+    comes out the same.  A non-reference picture that rotated the reconstruction ring, or stayed in a slot a later picture
+    predicts from, would show here without any other decoder's opinion."""
+    aus = picture_level.pictures(case)[0]
+    thin, index = picture_level.thinned([au for au, _, _ in aus])
+    assert index == [i for i, (_, _, is_ref) in enumerate(aus) if is_ref] and len(thin) < len(aus)
+    full_dec, thin_dec = h264dec.Decoder(), h264dec.Decoder()
+    full = {}
+    for i, (au, _, is_ref) in enumerate(aus):
+        assert full_dec.decode(au)
+        if is_ref:
+            full[i] = [full_dec.plane(p) for p in range(3)]
+    for i, au in zip(index, thin):
+        assert thin_dec.decode(au), "picture %d of the thinned stream" % i
+        for p in range(3):
+            assert np.array_equal(thin_dec.plane(p), full[i][p]), "picture %d plane %d" % (i, p)
+    full_dec.close()
+    thin_dec.close()
+
+
+def reference_nonreference_reference():
+    """three pictures at 48x32 - an IDR picture, a non-reference P picture, a reference P picture - under parameter sets with
+    left / top cropping; (access units, the oracle decoder's coded planes, its cropped I420 pictures, display size)"""
+    feat = 16384 | 65536 | 1
+    for base in range(100):
+        enc, ref = OracleEncoder(48, 32, qp=30, gop=30, refs=2), OracleDecoder()
+        aus, flags, planes, out = [], [], [], []
+        for i in range(3):
+            aus.append(enc.random_picture(1000 * base + i, features=feat)[0])
+            flags.append(enc.random_last()["is_ref"])
+            assert ref.decode(aus[-1]) == 1
+            planes.append([ref.plane(p) for p in range(3)])
+            out.append(_i420_of(ref))
+        if flags == [1, 0, 1]:
+            assert ref.crop[0] > 0 and ref.crop[1] > 0
+            return aus, planes, out, ref.size
+    raise AssertionError("no seed gives reference, non-reference, reference")
+
+
+def test_look_ahead_keeps_the_last_good_picture_readable_after_a_refused_unit():
+    """decode() returns once a picture is launched, and a non-reference picture shares its ring slot with the picture after it.
+    Reference, non-reference, reference: each is read only after the FOLLOWING decode call was refused as damaged (a truncated
+    access unit, which the host parser refuses before anything is launched) - the refused unit must leave the last good picture,
+    its size and its crop in place.  The refusal costs the reference pictures, so each of the three is reached by a decoder of
+    its own: a refusal empties the parser's reference list (lose_refs) and PrevRefFrameNum, so decoding on with the stream's
+    next non-IDR picture on the same decoder is unreachable by design.  That is what is checked instead: the next P picture -
+    after the refusal that followed the IDR picture, and after the one that followed the non-reference picture - is refused by
+    the host parser for want of a reference, never predicted from the slot the non-reference picture was decoded into, the
+    last good picture still reads back, and the next IDR picture decodes."""
+    aus, planes, out, size = reference_nonreference_reference()
+    for k in range(3):
+        dec = h264dec.Decoder()
+        for au in aus[:k + 1]:
+            assert dec.decode(au)
+        with pytest.raises(h264dec.StreamError):
+            dec.decode(aus[k][: len(aus[k]) * 3 // 5])
+        for p in range(3):
+            assert np.array_equal(dec.plane(p), planes[k][p]), "picture %d plane %d" % (k, p)
+        assert dec.info()[:2] == size and np.array_equal(dec.i420(), out[k]), "picture %d" % k
+        if k < 2:
+            with pytest.raises(h264dec.StreamError, match="without a reference"):
+                dec.decode(aus[k + 1])
+            assert np.array_equal(dec.i420(), out[k]), "picture %d after the refused P picture" % k
+        assert dec.decode(aus[0])
+        assert np.array_equal(dec.i420(), out[0])
+        dec.close()

@@ -74,3 +74,18 @@ def test_plugin_decoder_on_streams_of_other_encoders():
         want = np.concatenate([ref.plane(0)[:h, :w].ravel(), ref.plane(1)[: h // 2, : w // 2].ravel(), ref.plane(2)[: h // 2, : w // 2].ravel()])
         assert rc == vd.SUCCESS and np.array_equal(out, want), "picture %d" % i
     assert d.stop() == vd.SUCCESS and d.delete() == vd.SUCCESS
+
+
+def test_plugin_decoder_crops_left_and_top_and_returns_non_reference_pictures():
+    """Reference, non-reference, reference picture (tests/test_gpu_decoder.py) through send / retrieve: the SPS crops on the left
+    and top, and what retrieve returns is the oracle decoder's planes cut by the oracle's own crop offsets."""
+    from test_gpu_decoder import reference_nonreference_reference
+    aus, _, out, (w, h) = reference_nonreference_reference()
+    d = vd.PluginDecoder()
+    assert d.create_decoder(vd.STREAM_AVC) == vd.SUCCESS and d.init() == vd.SUCCESS and d.install_hooks() == vd.SUCCESS
+    assert d.set_pic_info(w, h) == vd.SUCCESS and d.start() == vd.SUCCESS
+    for i, au in enumerate(aus):
+        assert d.send(au) == vd.SUCCESS, "picture %d" % i
+        rc, got = d.retrieve(w * h * 3 // 2)
+        assert rc == vd.SUCCESS and np.array_equal(got, out[i]), "picture %d" % i
+    assert d.stop() == vd.SUCCESS and d.delete() == vd.SUCCESS

@@ -3,6 +3,8 @@
 (a) it uses no function of h264_common.c / h264_enc.c and does not include h264_tables.h;
 (b) its tables, typed from the standard in the standard's printed layout (VLC tables as bit strings), agree entry by
     entry with the encoder's h264_tables.h, typed in (length, bits) form;
+(d) mutation tests on the DECODER side for the picture level (non-reference pictures, PPS by id, slice_type 5..9): one error
+    planted in oracle/h264_dec.c is caught by the checks the picture-level tests make, each by the mechanism expected of it.
 (c) mutation tests: an error planted in ONE normative formula or table entry on the encoder side (filter tap, rounding,
     dequantiser entry, tC0 entry, boundary-strength rule, intra plane coefficient, chroma weights) makes the round trip
     decode(encode(x)) == reconstruction FAIL.  With the round-1 decoder, which called the encoder's own functions, every
@@ -189,3 +191,108 @@ def test_encoder_side_error_breaks_the_round_trip(mut, tmp_path):
     name, fname, old, new = mut
     so = _build_mutant(str(tmp_path), fname, old, new)
     assert not _roundtrip_ok(so), "mutant %s survived: the decoder does not pin this stage" % name
+
+
+# ---- decoder-side mutants, picture level (tests/picture_level.py; the checks are those of tests/test_dec_parser.py) ------------
+def _picture_level_verdicts(so):
+    """Every PICTURE_LEVEL_CASES stream through the decoder of library `so`.  Per case: `first_bad` = (picture index, what the
+    generator says of that picture) of the first access unit that is refused or whose QP_Y per macroblock is not what was
+    written, else None; `thinned_bad` = the stream without its non-reference pictures decodes to other reference pictures
+    (None where the full stream already failed)."""
+    import picture_level
+    L = C.CDLL(so)
+    vp = C.c_void_p
+    L.h264o_dec_create.restype = vp
+    L.h264o_dec_decode.argtypes = [vp, vp, C.c_size_t]
+    L.h264o_dec_plane.restype = vp
+    L.h264o_dec_plane.argtypes = [vp, C.c_int]
+    L.h264o_dec_mb_qp.argtypes = [vp, C.c_int]
+    L.h264o_dec_destroy.argtypes = [vp]
+
+    def decode_all(aus, cw, ch):
+        d, out = L.h264o_dec_create(), []
+        for au in aus:
+            buf = np.frombuffer(au, np.uint8)
+            if L.h264o_dec_decode(d, ol._ptr(buf), buf.size) != 1:
+                out.append(None)
+                break
+            planes = [np.ctypeslib.as_array(C.cast(L.h264o_dec_plane(d, p), C.POINTER(C.c_uint8)), shape=(ch >> (p > 0), cw >> (p > 0))).copy() for p in range(3)]
+            out.append((planes, [L.h264o_dec_mb_qp(d, a) for a in range(cw * ch // 256)]))
+        L.h264o_dec_destroy(d)
+        return out
+
+    verdicts = []
+    for case in picture_level.PICTURE_LEVEL_CASES:
+        cw, ch = (case[0] + 15) // 16 * 16, (case[1] + 15) // 16 * 16
+        enc = picture_level.encoder(case)
+        aus, qps, what = [], [], []
+        for i in range(picture_level.PICTURES):
+            au, idr, mbqp = enc.random_picture(picture_level.seed(case, i), features=case[5])
+            aus.append(au); qps.append([int(q) for q in mbqp]); what.append(dict(enc.random_last(), idr=idr))
+        enc.close()
+        full = decode_all(aus, cw, ch)
+        first_bad = next(((i, what[i]) for i, f in enumerate(full) if f is None or f[1] != qps[i]), None)
+        thinned_bad = None
+        if first_bad is None:
+            thin, index = picture_level.thinned(aus)
+            got = decode_all(thin, cw, ch)
+            thinned_bad = any(g is None or any(not np.array_equal(g[0][p], full[i][0][p]) for p in range(3)) for g, i in zip(got, index))
+        verdicts.append({"case": case, "first_bad": first_bad, "thinned_bad": thinned_bad})
+    return verdicts
+
+
+def test_unmutated_decoder_passes_the_picture_level_checks(tmp_path):
+    """the control of the three mutants below: the same harness on the unchanged source finds nothing"""
+    so = _build_mutant(str(tmp_path), "h264_dec.c", "#ifdef H264O_DEC_MUTATE_NONREF_ENTERS_LIST", "#ifdef H264O_DEC_MUTATE_NONREF_ENTERS_LIST")
+    for v in _picture_level_verdicts(so):
+        assert v["first_bad"] is None and v["thinned_bad"] is False, v
+
+
+def test_decoder_mutant_non_reference_picture_enters_the_list(tmp_path):
+    """Without list modification every access unit still decodes and every QP is right - the error shows only in samples, and
+    the thinned-stream check pins it: with the non-reference pictures removed, reference pictures come out different.  Where P
+    slices carry list modifications (features 128 / 256) the extra list entry may also make a command name the wrong picture,
+    so a later access unit can be refused first - never before the first non-reference picture.  Streams without feature 16384
+    are untouched, every stream with it is caught."""
+    so = _build_mutant(str(tmp_path), "h264_dec.c", "#ifdef H264O_DEC_MUTATE_NONREF_ENTERS_LIST", "#if 1")
+    verdicts = _picture_level_verdicts(so)
+    import picture_level
+    for v in verdicts:
+        if not v["case"][5] & 16384:
+            assert v["first_bad"] is None and v["thinned_bad"] is False, v
+            continue
+        assert v["first_bad"] is not None or v["thinned_bad"], v
+        if not v["case"][5] & (128 | 256):
+            assert v["first_bad"] is None and v["thinned_bad"], v
+        if v["first_bad"] is not None:
+            flags = [is_ref for _, _, is_ref in picture_level.pictures(v["case"])[0]]
+            assert not all(flags[:v["first_bad"][0]]), v
+    assert sum(bool(v["thinned_bad"]) for v in verdicts) >= 2, "the case list holds two streams of feature 16384 without list modification"
+
+
+def test_decoder_mutant_pps_taken_from_id_0(tmp_path):
+    """Caught by QP_Y per macroblock (pic_init_qp differs between the PPS) or by a refusal (PPS 0 not in play, a default
+    reference count that is not the named PPS's): in every stream of feature 65536, first at a picture that names another PPS
+    than 0; streams without the feature pass."""
+    so = _build_mutant(str(tmp_path), "h264_dec.c", "#ifdef H264O_DEC_MUTATE_PPS_ID_IGNORED", "#if 1")
+    for v in _picture_level_verdicts(so):
+        if v["case"][5] & 65536:
+            assert v["first_bad"] is not None and v["first_bad"][1]["pps_id"] != 0, v
+        else:
+            assert v["first_bad"] is None and v["thinned_bad"] is False, v
+
+
+def test_decoder_mutant_slice_type_7_read_as_p(tmp_path):
+    """Planted outside IDR pictures (there it would be refused at the first picture of any stream and say nothing): caught at
+    the first all-I non-IDR picture of a stream of feature 32768, whose slices are written with slice_type 7 - as a refusal or
+    as QPs that are not the ones written; streams without the feature pass."""
+    so = _build_mutant(str(tmp_path), "h264_dec.c", "#ifdef H264O_DEC_MUTATE_SLICE_TYPE_7_IS_P", "#if 1")
+    caught = 0
+    for v in _picture_level_verdicts(so):
+        if v["case"][5] & 32768:
+            if v["first_bad"] is not None:
+                assert v["first_bad"][1]["shape"] == 0 and not v["first_bad"][1]["idr"], v
+                caught += 1
+        else:
+            assert v["first_bad"] is None and v["thinned_bad"] is False, v
+    assert caught >= 3, caught
