@@ -1,8 +1,10 @@
 // media_amd/csrc/k_deblock.h -- in-loop deblocking filter (H.264 8.7).  Macroblock (mx,my)
 // filters against samples already finished by its left, top and top-right neighbours, which
 // 8.7 orders strictly (vertical edges of a macroblock, then its horizontal edges, macroblocks
-// in raster order).  Two forms, same results:
-//   k_deblock_rows  (in use) one launch, one persistent wave per macroblock row (further down)
+// in raster order).  Three forms, same results:
+//   k_deblock_pairs one launch, one persistent wave per TWO macroblock rows: the default from a lockstep batch of 8 pictures on
+//   k_deblock_rows  one launch, one persistent wave per macroblock row: smaller batches, pictures of several slices, the
+//                   latency mode, the decoder peer.  Both are built from one set of per-macroblock steps (db_* further down).
 //   k_deblock_diag  (first form; MI355X_H264_DIAG=1) one wavefront per macroblock, one launch
 //                   per wavefront step mx + 2*my == s
 //
@@ -38,7 +40,7 @@ struct DbParams {
     int alpha_y, beta_y, alpha_c, beta_c;
     int tc0_y[3], tc0_c[3];  // by bS-1
     SliceRows sl;        // several slices: disable_deblocking_filter_idc 2, the edge between two slices is left alone
-    const uint8_t* bs;   // k_bs's boundary strengths, 32 per macroblock: [dir][edge][segment] (the diagonal form reads them here)
+    const uint8_t* bs;   // boundary strengths of k_bs / k_dec_bs, 32 per macroblock: [dir][edge][segment]; the diagonal form reads these bytes, the persistent forms the same array as words (DbRowParams::bs)
     // k_deblock_rows<.., PERMB = true> (decoder peer): thresholds per edge from the two macroblocks' own QPs (8.7.2.2)
     const uint8_t* mbqp; // QP_Y per macroblock (0 for I_PCM)
     int oa, ob;          // FilterOffsetA, FilterOffsetB
@@ -194,7 +196,7 @@ typedef unsigned long long u64;
 struct DbRowParams {
     DbParams d;
     u64* handoff;        // [mbh][mbw][24] granules: 16 luma dwords (rows 12..15), 8 chroma dwords (rows 6..7 of Cb, Cr)
-    const uint32_t* bs;  // [nmb][8]: boundary strengths (k_cavlc count pass), word dir*4+edge, byte = segment along the edge
+    const uint32_t* bs;  // [nmb][8]: d.bs as words, word dir*4+edge, byte = segment along the edge
     unsigned* err;
     unsigned serial;     // changes every picture, never 0
     const unsigned* anybs;   // [item] == serial when the picture has any non-zero boundary strength (k_bs)
@@ -258,60 +260,195 @@ enum { DR_LP = 40, DR_CP = 24 };  // LDS pitches; luma tile cols -16..15 (+4 pad
 // parity when the plane starts at an odd dword (DR_CB), and the second plane the remaining 8 when it lies 16 mod 32 dwords
 // after the first (DR_CPS) - 32 lanes, 32 banks.  (Separate arrays had put all 32 lines on the 16 odd banks, the two chroma
 // planes partly on each other's: 2- and 3-way conflicts on every access of the phase)
-#ifdef MI355X_AB_OLD_DB_TILE   // A/B builds only (media_amd/csrc/Makefile target `ab`): the layout before round 3, chroma straight behind luma
-enum { DR_CB = 4 * 200, DR_CPS = 4 * 120, DR_TILE = DR_CB + 2 * DR_CPS + 12 };
-#else
 enum { DR_CB = 4 * 201, DR_CPS = 4 * 144, DR_TILE = DR_CB + 2 * DR_CPS + 12 };
-#endif
+// sample (r, c) of a tile's luma / of its chroma plane pl; (0, 0) = first sample of the current macroblock, the previous one to its left
+__device__ __forceinline__ uint8_t* db_y(uint8_t* const tile, const int r, const int c) { return tile + (r + 4) * DR_LP + c + 16; }
+__device__ __forceinline__ uint8_t* db_c(uint8_t* const tile, const int pl, const int r, const int c) { return tile + DR_CB + pl * DR_CPS + (r + 4) * DR_CP + c + 8; }
+__device__ __forceinline__ uint32_t& dw(uint8_t* const p) { return *(uint32_t*)p; }   // the aligned dword at p
 
+// The steps of a macroblock, once for both persistent forms.  A form keeps what is its own - which lanes move the samples, where
+// the bottom rows go, the prefetch, the order of the steps and their wave_sync() points - and calls these for the rest.
+struct DbThr { int al, be, t1, t2, t3; };   // alpha, beta and tc0 by bS 1..3 of one edge, luma or chroma as the lane's line
+__device__ __forceinline__ DbThr db_picture_thr(const DbParams& D, const bool isC)
+{
+    return isC ? DbThr{D.alpha_c, D.beta_c, D.tc0_c[0], D.tc0_c[1], D.tc0_c[2]} : DbThr{D.alpha_y, D.beta_y, D.tc0_y[0], D.tc0_y[1], D.tc0_y[2]};
+}
+// The picture at position pos of the step (blockIdx.y, or the one this workgroup walks to).  false: this launch has nothing to do
+// on it and nobody waits.  Otherwise D is R.d moved to the picture (planes, macroblock records; IND: ring slot and thresholds)
+template <bool PERMB, bool IND>
+__device__ __forceinline__ bool db_picture_view(const DbRowParams& R, const int pos, DbParams& D, u64*& handoff, const uint32_t*& bsw)
+{
+    const int bitem = batch_item<IND>(R.itemtab, pos);
+    if (R.anybs[bitem] != R.serial) return false;   // no edge of this picture is filtered
+    if (R.anypcm[bitem] == R.pic_serial) return false;
+    if (R.need_intra != 0 && (R.anyintra[bitem] == R.pic_serial) != (R.need_intra > 0)) return false;
+    D = R.d;
+    const size_t g = (size_t)bitem;
+    D.pl[0] += g * R.st_y; D.pl[1] += g * R.st_c; D.pl[2] += g * R.st_c; D.mb += g * R.st_mb;
+    if constexpr (IND) {   // the item's own ring slot and its own QP's thresholds (Tables 8-16 / 8-17, chroma through Table 8-15)
+        const ItemRef it = item_ref(R.itemtab, pos);
+        D.pl[0] += (size_t)it.cur * R.st_ring_y; D.pl[1] += (size_t)it.cur * R.st_ring_c; D.pl[2] += (size_t)it.cur * R.st_ring_c;
+        const int qpc = c_chroma_qp[it.qp];
+        D.alpha_y = c_alpha[it.qp]; D.beta_y = c_beta[it.qp]; D.alpha_c = c_alpha[qpc]; D.beta_c = c_beta[qpc];
+#pragma unroll
+        for (int i = 0; i < 3; i++) { D.tc0_y[i] = c_tc0[it.qp][i]; D.tc0_c[i] = c_tc0[qpc][i]; }
+    }
+    if (PERMB) D.mbqp += g * R.st_mb;
+    handoff = R.handoff + g * R.st_handoff;
+    bsw = R.bs + g * R.st_mb * 8;
+    return true;
+}
+// Filter lane l of a row: 0..15 the luma lines, 16..31 the chroma lines (plane fpl, line).  V phase: the lane holds line fln of
+// its plane (vrow: 4-byte aligned, from column -4), H phase: column fln (hcol: from row -4).  seg8: shift to its segment's strength
+struct DbLane { bool isC; int fpl, seg8, hstride; uint8_t *vrow, *hcol; };
+__device__ __forceinline__ DbLane db_lane(const int l, uint8_t* const tile)
+{
+    DbLane L;
+    L.isC = l >= 16; L.fpl = (l >> 3) & 1;
+    const int fln = L.isC ? (l & 7) : l;
+    L.seg8 = 8 * (L.isC ? (fln >> 1) : (fln >> 2));
+    L.vrow = L.isC ? db_c(tile, L.fpl, fln, -4) : db_y(tile, fln, -4);
+    L.hcol = L.isC ? db_c(tile, L.fpl, -4, fln) : db_y(tile, -4, fln);
+    L.hstride = L.isC ? DR_CP : DR_LP;
+    return L;
+}
+// Edge E (0..3) of one direction on the line px[]: b = that direction's four strength words (byte = segment along the edge).
+// Chroma lines have edges 0 and 1 only, which are luma edges 0 and 2.  An edge no line of which is filtered (bS 0 in every
+// segment, luma and chroma: three of four inner edges on ordinary P pictures) is skipped by ONE wave-uniform branch - not a
+// branch inside the filter, see filt_uni.  Returns whether the edge was filtered.
+template <bool BS4, int E>
+__device__ __forceinline__ bool db_edge(const DbLane& L, int (&px)[20], const uint4 b, const DbThr& T)
+{
+    const uint32_t w = E == 0 ? b.x : E == 1 ? (L.isC ? b.z : b.y) : E == 2 ? b.z : b.w;
+    const int bS = (E >= 2 && L.isC) ? 0 : (int)((w >> L.seg8) & 255);
+    if (__ballot(bS != 0) == 0ull) return false;
+    filt_uni<BS4>(px[4 * E], px[4 * E + 1], px[4 * E + 2], px[4 * E + 3], px[4 * E + 4], px[4 * E + 5], px[4 * E + 6], px[4 * E + 7],
+                  bS, L.isC, T.al, T.be, T.t1, T.t2, T.t3);
+    return true;
+}
+template <int W>
+__device__ __forceinline__ uint32_t db_pack(const int (&px)[20])   // dword W of the line
+{
+    return (uint32_t)px[4 * W] | ((uint32_t)px[4 * W + 1] << 8) | ((uint32_t)px[4 * W + 2] << 16) | ((uint32_t)px[4 * W + 3] << 24);
+}
+// Vertical edges: lane = one line of samples, four edges in registers (px[] is the caller's: it lives across the publish).  The
+// left edge goes first and its p side (the one tile dword of the previous macroblock it can change) is written back at once:
+// the previous macroblock is final from here, and the row below is waiting for it.  Then edges 1..3 from the same registers.
+template <bool BS4>
+__device__ __forceinline__ void db_left_edge(const DbLane& L, int (&px)[20], const uint4 b0, const bool on, const DbThr& T)
+{
+    if (on) {
+#pragma unroll
+        for (int w = 0; w < 5; w++) {
+            const uint32_t v = dw(L.vrow + 4 * w);
+#pragma unroll
+            for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
+        }
+        if (db_edge<BS4, 0>(L, px, b0, T)) dw(L.vrow) = db_pack<0>(px);
+    }
+}
+template <bool BS4>
+__device__ __forceinline__ void db_inner_vertical(const DbLane& L, int (&px)[20], const uint4 b0, const bool on, const DbThr& T)
+{
+    if (on) {
+        db_edge<BS4, 1>(L, px, b0, T);
+        db_edge<BS4, 2>(L, px, b0, T);
+        db_edge<BS4, 3>(L, px, b0, T);
+        dw(L.vrow + 4) = db_pack<1>(px); dw(L.vrow + 8) = db_pack<2>(px);
+        if (!L.isC) { dw(L.vrow + 12) = db_pack<3>(px); dw(L.vrow + 16) = db_pack<4>(px); }
+    }
+}
+// Horizontal edges: lane = one column of samples (rows -4..15; chroma uses rows -4..7 of its tile); Ttop: the edge to the macroblock above
+template <bool BS4>
+__device__ __forceinline__ void db_horizontal(const DbLane& L, const uint4 b1, const bool on, const DbThr& Ttop, const DbThr& T)
+{
+    if (on) {
+        int px[20];
+#pragma unroll
+        for (int r = 0; r < 20; r++) px[r] = L.hcol[r * L.hstride];
+        db_edge<BS4, 0>(L, px, b1, Ttop);
+        db_edge<BS4, 1>(L, px, b1, T);
+        db_edge<BS4, 2>(L, px, b1, T);
+        db_edge<BS4, 3>(L, px, b1, T);
+        // samples an edge can change: p2..q2 around rows 0,4,8,12 -> rows -3..14; chroma: p0,q0 around rows 0,4
+#pragma unroll
+        for (int r = 1; r < 19; r++) {
+            const bool both = r == 3 || r == 4 || r == 7 || r == 8;
+            if (both || !L.isC) L.hcol[r * L.hstride] = (uint8_t)px[r];
+        }
+    }
+}
+// Granule k of a macroblock, one dword of its bottom sample rows: f(chroma, plane, row, byte column), position in the macroblock.
+// 0..15: luma row 12 + k/4, dword k%4; 16..23: chroma plane (k-16)/4, row 6 + ((k-16)/2)%2, dword (k-16)%2; lanes k >= 24 have none.
+template <class F>
+__device__ __forceinline__ void db_granule(const int k, F f)
+{
+    if (k < 16) f(false, 0, 12 + (k >> 2), (k & 3) * 4);
+    else if (k < 24) f(true, (k - 16) >> 2, 6 + (((k - 16) >> 1) & 1), ((k - 16) & 1) * 4);
+}
+// that position in the tile, in the macroblock (dmx, dmy) from the current one
+__device__ __forceinline__ uint8_t* db_tile_at(uint8_t* const tile, const bool c, const int pl, const int r, const int col, const int dmx, const int dmy)
+{
+    return c ? db_c(tile, pl, 8 * dmy + r, 8 * dmx + col) : db_y(tile, 16 * dmy + r, 16 * dmx + col);
+}
+// bottom dword k of the previous macroblock (shifted: it lies to the left of the current one) or of the current one
+__device__ __forceinline__ uint32_t db_bottom_dword(uint8_t* const tile, const int k, const bool shifted)
+{
+    uint32_t v = 0;
+    db_granule(k, [&](bool c, int pl, int r, int col) { v = dw(db_tile_at(tile, c, pl, r, col, shifted ? -1 : 0, 0)); });
+    return v;
+}
+// dword k of the macroblock above: into the tile's top apron, and from there (filtered, final) to the picture
+__device__ __forceinline__ void db_put_apron(uint8_t* const tile, const int k, const uint32_t v)
+{
+    db_granule(k, [&](bool c, int pl, int r, int col) { dw(db_tile_at(tile, c, pl, r, col, 0, -1)) = v; });
+}
+__device__ __forceinline__ void db_store_apron(const DbParams& D, uint8_t* const tile, const int k, const int mx, const int my)
+{
+    db_granule(k, [&](bool c, int pl, int r, int col) {
+        uint8_t* const p = c ? (pl ? D.pl[2] : D.pl[1]) + (size_t)(8 * (my - 1) + r) * (D.cw / 2) + 8 * mx + col
+                             : D.pl[0] + (size_t)(16 * (my - 1) + r) * D.cw + 16 * mx + col;
+        dw(p) = dw(db_tile_at(tile, c, pl, r, col, 0, -1));
+    });
+}
+// Wait until the granule g of every lane that needs one carries this picture's tag, re-reading it from addr.  Bounded: a timeout
+// sets timed_out, and no later wait of the wave spins at all.
+__device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64* const addr, const unsigned serial, bool& timed_out)
+{
+    unsigned spins = 0;
+    while (!timed_out) {
+        const bool bad = need && (unsigned)(g >> 32) != serial;
+        if (__ballot(bad) == 0ull) break;
+        if (++spins > (1u << 20)) { timed_out = true; break; }
+        __builtin_amdgcn_s_sleep(1);
+        if (need) g = AT_LOAD(addr);
+    }
+}
+
+// ===========================================================================
+// Row form: one wave per macroblock row; all 64 lanes move samples (one luma dword each), lanes 0..31 filter.
 // PERMB (the decoder peer, streams of other encoders): qPp / qPq are the two macroblocks' own QPs (mb_qp_delta, I_PCM = 0),
 // the chroma QPs go through chroma_qp_index_offset, indexA / indexB through the slice's filter offsets - three threshold
 // sets per macroblock (left edge, top edge, inner edges), looked up in LDS copies of Tables 8-15 / 8-16.  PERMB = false is
 // the encoder's form: one set per picture, prepared on the host.
+// ===========================================================================
 template <bool BS4, bool PERMB, bool IND>
-__device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const int pos)   // pos: the picture's position in the step (blockIdx.y, or the one this workgroup walks to)
+__device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const int pos)
 {
-    const int bitem = batch_item<IND>(R.itemtab, pos);
-    if (R.anybs[bitem] != R.serial) return;   // no edge of this picture is filtered: nothing to do, nobody waits
-    if (R.anypcm[bitem] == R.pic_serial) return;
-    if (R.need_intra != 0 && (R.anyintra[bitem] == R.pic_serial) != (R.need_intra > 0)) return;
-    DbParams D = R.d;
-    {
-        const size_t g = (size_t)bitem;
-        D.pl[0] += g * R.st_y; D.pl[1] += g * R.st_c; D.pl[2] += g * R.st_c; D.mb += g * R.st_mb;
-        if constexpr (IND) {   // the item's own ring slot and its own QP's thresholds (Tables 8-16 / 8-17, chroma through Table 8-15)
-            const ItemRef it = item_ref(R.itemtab, pos);
-            D.pl[0] += (size_t)it.cur * R.st_ring_y; D.pl[1] += (size_t)it.cur * R.st_ring_c; D.pl[2] += (size_t)it.cur * R.st_ring_c;
-            const int qpc = c_chroma_qp[it.qp];
-            D.alpha_y = c_alpha[it.qp]; D.beta_y = c_beta[it.qp]; D.alpha_c = c_alpha[qpc]; D.beta_c = c_beta[qpc];
-#pragma unroll
-            for (int i = 0; i < 3; i++) { D.tc0_y[i] = c_tc0[it.qp][i]; D.tc0_c[i] = c_tc0[qpc][i]; }
-        }
-        if (PERMB) D.mbqp += g * R.st_mb;
-    }
-    u64* const handoff = R.handoff + (size_t)bitem * R.st_handoff;
-    const uint32_t* const bsw = R.bs + (size_t)bitem * R.st_mb * 8;
+    DbParams D; u64* handoff; const uint32_t* bsw;
+    if (!db_picture_view<PERMB, IND>(R, pos, D, handoff, bsw)) return;
     const int lane = threadIdx.x, my = R.row0 + blockIdx.x, cs = D.cw / 2;   // (row0: first row of this instance's band)
     // a slice's rows form a wavefront of their own: its first row waits for nobody (no edge to the slice above is
     // filtered), its last row stores all sixteen sample rows itself
     const bool first_row = !D.sl.has_top(my);
     const bool last_row = my == D.mbh - 1 || !D.sl.has_top(my + 1);
-    __shared__ __attribute__((aligned(16))) uint8_t s_y[DR_TILE];        // luma [row+4][col+16], then the chroma planes [row+4][col+8] at DR_CB + plane * DR_CPS
-#define SY(r, c) s_y[((r) + 4) * DR_LP + (c) + 16]
-#define SC(pl, r, c) s_y[DR_CB + (pl) * DR_CPS + ((r) + 4) * DR_CP + (c) + 8]
+    __shared__ __attribute__((aligned(16))) uint8_t s_y[DR_TILE];
     bool timed_out = false;
     const int yr = lane >> 2, yc4 = (lane & 3) * 4;                                   // luma dword owned by this lane
     const int cpl_l = (lane >> 4) & 1, cr_l = (lane >> 1) & 7, cc4 = (lane & 1) * 4;  // chroma dword (lanes < 32)
-    // granule k (lane < 24): 0..15 luma row 12 + k/4, dword k%4; 16..23 chroma plane (k-16)/4, row 6 + ((k-16)/2)%2, dword (k-16)%2
-    const int gk = lane;
-    // filter lanes: 0..15 luma lines, 16..31 chroma lines (plane, line)
-    const bool isC = lane >= 16;
-    const int fpl = (lane >> 3) & 1, fln = isC ? (lane & 7) : lane;
-    const int seg8 = 8 * (isC ? (fln >> 1) : (fln >> 2));
+    const DbLane L = db_lane(lane, s_y);   // (lanes 32..63 get a role too and never act in it)
     // thresholds of the inner edges, of the left edge (L) and of the top edge (T); one set unless PERMB
-    int al = isC ? D.alpha_c : D.alpha_y, be = isC ? D.beta_c : D.beta_y;
-    int t1 = isC ? D.tc0_c[0] : D.tc0_y[0], t2 = isC ? D.tc0_c[1] : D.tc0_y[1], t3 = isC ? D.tc0_c[2] : D.tc0_y[2];
-    int alL = al, beL = be, t1L = t1, t2L = t2, t3L = t3, alT = al, beT = be, t1T = t1, t2T = t2, t3T = t3;
+    DbThr thr = db_picture_thr(D, L.isC), thrL = thr, thrT = thr;
     __shared__ uint32_t s_tA[PERMB ? 52 : 1];   // by indexA: alpha << 24 | tc0(bS 3) << 16 | tc0(bS 2) << 8 | tc0(bS 1)
     __shared__ uint8_t s_tB[PERMB ? 52 : 1], s_cq[PERMB ? 52 : 1];   // beta by indexB; QP_C by the offset luma QP
     if (PERMB) {
@@ -322,19 +459,15 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
         }
         wave_sync();
     }
-    const int cqo = fpl ? D.cqo_cr : D.cqo_cb;
-    auto thresholds = [&](const int qa, const int qb, int& A, int& B, int& T1, int& T2, int& T3) {
+    const int cqo = L.fpl ? D.cqo_cr : D.cqo_cb;
+    auto thresholds = [&](const int qa, const int qb) {
         const int ca = (int)s_cq[clip3(0, 51, qa + cqo)], cb = (int)s_cq[clip3(0, 51, qb + cqo)];
-        const int av = ((isC ? ca : qa) + (isC ? cb : qb) + 1) >> 1;           // qPav (8-461)
+        const int av = ((L.isC ? ca : qa) + (L.isC ? cb : qb) + 1) >> 1;           // qPav (8-461)
         const uint32_t w = s_tA[clip3(0, 51, av + D.oa)];
-        A = (int)(w >> 24); T1 = (int)(w & 255u); T2 = (int)((w >> 8) & 255u); T3 = (int)((w >> 16) & 255u);
-        B = (int)s_tB[clip3(0, 51, av + D.ob)];
+        return DbThr{(int)(w >> 24), (int)s_tB[clip3(0, 51, av + D.ob)], (int)(w & 255u), (int)((w >> 8) & 255u), (int)((w >> 16) & 255u)};
     };
     uint32_t pf_q = 0;   // QP_Y of the macroblock | of the one above << 8
     int qp_left = 0;
-    uint8_t* vrow = isC ? &SC(fpl, fln, -4) : &SY(fln, -4);                 // V phase: this lane's line, 4-byte aligned
-    uint8_t* hcol = isC ? &SC(fpl, -4, fln) : &SY(-4, fln);                 // H phase: top of this lane's column
-    const int hstride = isC ? DR_CP : DR_LP;
 
     // Software pipeline: the samples, boundary strengths and hand-off granules of macroblock mx+1 are
     // requested (straight-line, unconditional loads) after macroblock mx has been put into LDS, travel
@@ -375,15 +508,11 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             const int pmx = mx - 1;
             const int co = have_cur ? -16 : 0, cco = have_cur ? -8 : 0;  // after the last macroblock there was no shift
             const int nrow = last_row ? 16 : 12, ncrow = last_row ? 8 : 6;
-            if (yr < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr) * D.cw + 16 * pmx + yc4) = *(const uint32_t*)&SY(yr, co + yc4);
+            if (yr < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr, co + yc4));
             if (lane < 32 && cr_l < ncrow)
-                *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = *(const uint32_t*)&SC(cpl_l, cr_l, cco + cc4);
-            if (!last_row && lane < 24) {
-                uint32_t v;
-                if (lane < 16) v = *(const uint32_t*)&SY(12 + (gk >> 2), co + (gk & 3) * 4);
-                else v = *(const uint32_t*)&SC((gk - 16) >> 2, 6 + (((gk - 16) >> 1) & 1), cco + ((gk - 16) & 1) * 4);
-                AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + gk, ((u64)R.serial << 32) | v);
-            }
+                *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = dw(db_c(s_y, cpl_l, cr_l, cco + cc4));
+            if (!last_row && lane < 24)
+                AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + lane, ((u64)R.serial << 32) | db_bottom_dword(s_y, lane, have_cur));
         }
     };
     for (int mx = 0; mx <= D.mbw; mx++) {
@@ -391,112 +520,51 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
         if (have_cur) {
             // 1. previous macroblock moves to the left half of the tile
             if (mx > 0) {
-                *(uint32_t*)&SY(yr, yc4 - 16) = *(const uint32_t*)&SY(yr, yc4);
-                if (lane < 32) *(uint32_t*)&SC(cpl_l, cr_l, cc4 - 8) = *(const uint32_t*)&SC(cpl_l, cr_l, cc4);
+                dw(db_y(s_y, yr, yc4 - 16)) = dw(db_y(s_y, yr, yc4));
+                if (lane < 32) dw(db_c(s_y, cpl_l, cr_l, cc4 - 8)) = dw(db_c(s_y, cpl_l, cr_l, cc4));
             }
             wave_sync();
             // 2. current macroblock into LDS
-            *(uint32_t*)&SY(yr, yc4) = cur_y;
-            if (lane < 32) *(uint32_t*)&SC(cpl_l, cr_l, cc4) = cur_c;
+            dw(db_y(s_y, yr, yc4)) = cur_y;
+            if (lane < 32) dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
             // requests for the next macroblock leave now and are collected after the filter
             if (mx + 1 < D.mbw) prefetch(mx + 1);
             if (PERMB) {
                 const int qc = (int)(cur_q & 255u), qt = (int)(cur_q >> 8);
-                thresholds(qc, qc, al, be, t1, t2, t3);
-                thresholds(mx > 0 ? qp_left : qc, qc, alL, beL, t1L, t2L, t3L);
-                thresholds(qt, qc, alT, beT, t1T, t2T, t3T);
+                thr = thresholds(qc, qc);
+                thrL = thresholds(mx > 0 ? qp_left : qc, qc);
+                thrT = thresholds(qt, qc);
                 qp_left = qc;
             }
             wave_sync();
-            const bool any_v = (b0.x | b0.y | b0.z | b0.w) != 0, any_h = (b1.x | b1.y | b1.z | b1.w) != 0;
-            // 3. vertical edges: lane = one line of samples, four edges in registers.
-            //    chroma lines take part in steps 0 and 1 (chroma edges 0 and 4 <-> luma edges 0 and 8).
-            //    The left edge goes first and its p side (the one tile dword of the previous macroblock it can change) is
-            //    written back at once: the previous macroblock is final from here, and the row below is waiting for it.
-            const bool v_on = any_v && lane < 32;
+            const bool v_on = (b0.x | b0.y | b0.z | b0.w) != 0 && lane < 32, h_on = (b1.x | b1.y | b1.z | b1.w) != 0 && lane < 32;
+            // 3. vertical edges, the left one first
             int px[20];
-            int e1 = 0, e2 = 0, e3 = 0;
-            if (v_on) {
-#pragma unroll
-                for (int w = 0; w < 5; w++) {
-                    const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
-#pragma unroll
-                    for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
-                }
-                const int e0 = (int)((b0.x >> seg8) & 255);
-                e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
-                e2 = isC ? 0 : (int)((b0.z >> seg8) & 255); e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
-                // an edge no line of which is filtered (bS 0 in every segment, luma and chroma: three of four inner edges on
-                // ordinary P pictures) is skipped by ONE wave-uniform branch - not a branch inside the filter, see filt_uni
-                if (__ballot(e0 != 0) != 0ull) {
-                    filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, alL, beL, t1L, t2L, t3L);
-                    *(uint32_t*)vrow = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
-                }
-            }
+            db_left_edge<BS4>(L, px, b0, v_on, thrL);
             wave_sync();
             // 4. publish the previous macroblock (the row below needs nothing else of this one), then edges 1..3 from
             //    the registers already held
             store_prev(mx, true);
-            if (v_on) {
-                if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-                if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-                if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-#pragma unroll
-                for (int w = 1; w < 5; w++)
-                    if (w < 3 || !isC)
-                        *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
-            }
+            db_inner_vertical<BS4>(L, px, b0, v_on, thr);
             // the top apron is needed from here on and not before (the vertical edges touch rows 0..15 only): wait until
             // every granule of the macroblock above carries this picture's tag
             if (!first_row) {
-                unsigned spins = 0;
-                while (!timed_out) {
-                    const bool bad = lane < 24 && (unsigned)(g >> 32) != R.serial;
-                    if (__ballot(bad) == 0ull) break;
-                    if (++spins > (1u << 20)) { timed_out = true; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                    g = AT_LOAD(handoff + ((size_t)grow * D.mbw + mx) * 24 + glane);
-                }
-                if (lane < 16) *(uint32_t*)&SY(-4 + (gk >> 2), (gk & 3) * 4) = (uint32_t)g;
-                else if (lane < 24) *(uint32_t*)&SC((gk - 16) >> 2, -2 + (((gk - 16) >> 1) & 1), ((gk - 16) & 1) * 4) = (uint32_t)g;
+                db_wait_tags(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out);
+                db_put_apron(s_y, lane, (uint32_t)g);
             }
             wave_sync();
-            // 5. horizontal edges: lane = one column of samples (rows -4..15; chroma uses rows -4..7 of its tile)
-            if (any_h && lane < 32) {
-                int px[20];
-#pragma unroll
-                for (int r = 0; r < 20; r++) px[r] = hcol[r * hstride];
-                const int e0 = (int)((b1.x >> seg8) & 255), e1 = (int)(((isC ? b1.z : b1.y) >> seg8) & 255);
-                const int e2 = isC ? 0 : (int)((b1.z >> seg8) & 255), e3 = isC ? 0 : (int)((b1.w >> seg8) & 255);
-                if (__ballot(e0 != 0) != 0ull) filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, alT, beT, t1T, t2T, t3T);
-                if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-                if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-                if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-                // samples an edge can change: p2..q2 around rows 0,4,8,12 -> rows -3..14; chroma: p0,q0 around rows 0,4
-#pragma unroll
-                for (int r = 1; r < 19; r++) {
-                    const bool both = r == 3 || r == 4 || r == 7 || r == 8;
-                    if (both || !isC) hcol[r * hstride] = (uint8_t)px[r];
-                }
-            }
+            // 5. horizontal edges
+            db_horizontal<BS4>(L, b1, h_on, thrT, thr);
             wave_sync();
             consume();   // the next macroblock's data has arrived; nothing below waits for memory any more
             // 6. the top apron (rows 12..15 / 6..7 of the macroblock above) is final: store it
-            if (!first_row) {
-                if (lane < 16) *(uint32_t*)(D.pl[0] + (size_t)(16 * my - 4 + (gk >> 2)) * D.cw + 16 * mx + (gk & 3) * 4) = *(const uint32_t*)&SY(-4 + (gk >> 2), (gk & 3) * 4);
-                else if (lane < 24) {
-                    const int k = gk - 16, pl = k >> 2, r = (k >> 1) & 1, c4 = (k & 1) * 4;
-                    *(uint32_t*)((pl ? D.pl[2] : D.pl[1]) + (size_t)(8 * my - 2 + r) * cs + 8 * mx + c4) = *(const uint32_t*)&SC(pl, -2 + r, c4);
-                }
-            }
+            if (!first_row) db_store_apron(D, s_y, lane, mx, my);
         }
         if (!have_cur) store_prev(mx, false);   // after the last macroblock of the row
         cur_y = pf_y; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; cur_q = pf_q;
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;  // pinned host word, read after the picture's event
-#undef SY
-#undef SC
 }
 // The kernels: workgroup (row, y) filters its row of pictures y, y + gridDim.y, ... of the step's R.npic pictures.  A launch whose
 // pictures nearly all return at once - the bS 4 form on P steps of content without intra macroblocks - is made with gridDim.y = 1: placing
@@ -526,7 +594,7 @@ __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 // filter, prefetch one macroblock ahead, one writer per picture sample, bounded spins.
 // MEASURED (bench workload, 32 pictures per launch): at first the launch got 7 % shorter and the pipeline 1 % slower (each step of
 // the critical path carries the data movement of two macroblocks with 32 lanes per row instead of 64, and the waves the row form
-// had too many of were asleep in their hand-off spins, not contending for issue).  With the edge skip below (an edge no line of
+// had too many of were asleep in their hand-off spins, not contending for issue).  With the edge skip (an edge no line of
 // which is filtered costs one scalar branch) the instruction count decides: 152 VALU per macroblock here, 181 in the row form,
 // half the waves - 25.0 k fps against 24.0 k on one box.  So this form is the default from a lockstep batch of 8 pictures on
 // (pictures of one slice; MI355X_H264_PAIR_FILTER=N moves the threshold, 0 turns it off); smaller batches, the latency mode and
@@ -535,25 +603,8 @@ __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 template <bool BS4, bool IND>
 __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, const int pos)
 {
-    const int bitem = batch_item<IND>(R.itemtab, pos);
-    if (R.anybs[bitem] != R.serial) return;
-    if (R.anypcm[bitem] == R.pic_serial) return;
-    if (R.need_intra != 0 && (R.anyintra[bitem] == R.pic_serial) != (R.need_intra > 0)) return;
-    DbParams D = R.d;
-    {
-        const size_t g = (size_t)bitem;
-        D.pl[0] += g * R.st_y; D.pl[1] += g * R.st_c; D.pl[2] += g * R.st_c; D.mb += g * R.st_mb;
-        if constexpr (IND) {   // the item's own ring slot and its own QP's thresholds (Tables 8-16 / 8-17, chroma through Table 8-15)
-            const ItemRef it = item_ref(R.itemtab, pos);
-            D.pl[0] += (size_t)it.cur * R.st_ring_y; D.pl[1] += (size_t)it.cur * R.st_ring_c; D.pl[2] += (size_t)it.cur * R.st_ring_c;
-            const int qpc = c_chroma_qp[it.qp];
-            D.alpha_y = c_alpha[it.qp]; D.beta_y = c_beta[it.qp]; D.alpha_c = c_alpha[qpc]; D.beta_c = c_beta[qpc];
-#pragma unroll
-            for (int i = 0; i < 3; i++) { D.tc0_y[i] = c_tc0[it.qp][i]; D.tc0_c[i] = c_tc0[qpc][i]; }
-        }
-    }
-    u64* const handoff = R.handoff + (size_t)bitem * R.st_handoff;
-    const uint32_t* const bsw = R.bs + (size_t)bitem * R.st_mb * 8;
+    DbParams D; u64* handoff; const uint32_t* bsw;
+    if (!db_picture_view<false, IND>(R, pos, D, handoff, bsw)) return;
     const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31, cs = D.cw / 2;
     const int rowA = R.row0 + 2 * (int)blockIdx.x, rowB = rowA + 1;
     const bool hasB = rowB < D.mbh;                 // (an odd number of rows: the last wave has an upper row only)
@@ -565,21 +616,12 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
     __shared__ __attribute__((aligned(16))) uint8_t s_yy[2][(DR_TILE + 127) / 128 * 128];   // one tile per row of the pair (a multiple of 32 dwords apart: the same banks)
     __shared__ __attribute__((aligned(16))) uint32_t s_ring[2][24];   // bottom rows of the upper row's macroblock (parity of its index): 16 luma + 8 chroma dwords
     uint8_t* const s_y = s_yy[half];
-#define SY(r, c) s_y[((r) + 4) * DR_LP + (c) + 16]
-#define SC(pl, r, c) s_y[DR_CB + (pl) * DR_CPS + ((r) + 4) * DR_CP + (c) + 8]
     bool timed_out = false;
     // luma dwords owned by this lane: two of the 64 of a macroblock (rows yr0 and yr0 + 8); chroma dword as in the row form
     const int yr0 = hl >> 2, yc4 = (hl & 3) * 4;
     const int cpl_l = (hl >> 4) & 1, cr_l = (hl >> 1) & 7, cc4 = (hl & 1) * 4;
-    const int gk = hl;   // granule index (hl < 24)
-    const bool isC = hl >= 16;
-    const int fpl = (hl >> 3) & 1, fln = isC ? (hl & 7) : hl;
-    const int seg8 = 8 * (isC ? (fln >> 1) : (fln >> 2));
-    const int al = isC ? D.alpha_c : D.alpha_y, be = isC ? D.beta_c : D.beta_y;
-    const int t1 = isC ? D.tc0_c[0] : D.tc0_y[0], t2 = isC ? D.tc0_c[1] : D.tc0_y[1], t3 = isC ? D.tc0_c[2] : D.tc0_y[2];
-    uint8_t* vrow = isC ? &SC(fpl, fln, -4) : &SY(fln, -4);
-    uint8_t* hcol = isC ? &SC(fpl, -4, fln) : &SY(-4, fln);
-    const int hstride = isC ? DR_CP : DR_LP;
+    const DbLane L = db_lane(hl, s_y);
+    const DbThr thr = db_picture_thr(D, L.isC);   // one set for every edge of the picture
 
     uint32_t pf_y0 = 0, pf_y1 = 0, pf_c = 0;
     uint4 pf_b0 = {0, 0, 0, 0}, pf_b1 = pf_b0;
@@ -615,16 +657,14 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
             const int pmx = mx - 1;
             const int co = have_cur ? -16 : 0, cco = have_cur ? -8 : 0;
             const int nrow = last_row ? 16 : 12, ncrow = last_row ? 8 : 6;
-            *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0) * D.cw + 16 * pmx + yc4) = *(const uint32_t*)&SY(yr0, co + yc4);
-            if (yr0 + 8 < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0 + 8) * D.cw + 16 * pmx + yc4) = *(const uint32_t*)&SY(yr0 + 8, co + yc4);
+            *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0, co + yc4));
+            if (yr0 + 8 < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0 + 8) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0 + 8, co + yc4));
             if (cr_l < ncrow)
-                *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = *(const uint32_t*)&SC(cpl_l, cr_l, cco + cc4);
+                *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = dw(db_c(s_y, cpl_l, cr_l, cco + cc4));
             if (!last_row && hl < 24) {
-                uint32_t v;
-                if (hl < 16) v = *(const uint32_t*)&SY(12 + (gk >> 2), co + (gk & 3) * 4);
-                else v = *(const uint32_t*)&SC((gk - 16) >> 2, 6 + (((gk - 16) >> 1) & 1), cco + ((gk - 16) & 1) * 4);
-                if (half == 0) s_ring[pmx & 1][gk] = v;
-                else AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + gk, ((u64)R.serial << 32) | v);
+                const uint32_t v = db_bottom_dword(s_y, hl, have_cur);
+                if (half == 0) s_ring[pmx & 1][hl] = v;
+                else AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + hl, ((u64)R.serial << 32) | v);
             }
         }
     };
@@ -634,107 +674,46 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
         const bool have_cur = in_range && mx < D.mbw;
         if (have_cur) {
             if (mx > 0) {
-                *(uint32_t*)&SY(yr0, yc4 - 16) = *(const uint32_t*)&SY(yr0, yc4);
-                *(uint32_t*)&SY(yr0 + 8, yc4 - 16) = *(const uint32_t*)&SY(yr0 + 8, yc4);
-                *(uint32_t*)&SC(cpl_l, cr_l, cc4 - 8) = *(const uint32_t*)&SC(cpl_l, cr_l, cc4);
+                dw(db_y(s_y, yr0, yc4 - 16)) = dw(db_y(s_y, yr0, yc4));
+                dw(db_y(s_y, yr0 + 8, yc4 - 16)) = dw(db_y(s_y, yr0 + 8, yc4));
+                dw(db_c(s_y, cpl_l, cr_l, cc4 - 8)) = dw(db_c(s_y, cpl_l, cr_l, cc4));
             }
         }
         wave_sync();
         if (have_cur) {
-            *(uint32_t*)&SY(yr0, yc4) = cur_y0;
-            *(uint32_t*)&SY(yr0 + 8, yc4) = cur_y1;
-            *(uint32_t*)&SC(cpl_l, cr_l, cc4) = cur_c;
+            dw(db_y(s_y, yr0, yc4)) = cur_y0;
+            dw(db_y(s_y, yr0 + 8, yc4)) = cur_y1;
+            dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
         }
         {   // requests for this lane's next macroblock (clamped: the loads of a finished or not yet started row are harmless)
             const int nx = mx + 1 < 0 ? 0 : (mx + 1 > last_mx ? last_mx : mx + 1);
             prefetch(nx);
         }
         wave_sync();
-        const bool any_v = have_cur && (b0.x | b0.y | b0.z | b0.w) != 0, any_h = have_cur && (b1.x | b1.y | b1.z | b1.w) != 0;
-        // vertical edges, left edge first; its p side (the one tile dword of the previous macroblock it can change) goes back at once
+        const bool v_on = have_cur && (b0.x | b0.y | b0.z | b0.w) != 0, h_on = have_cur && (b1.x | b1.y | b1.z | b1.w) != 0;
         int px[20];
-        int e1 = 0, e2 = 0, e3 = 0;
-        if (any_v) {
-#pragma unroll
-            for (int w = 0; w < 5; w++) {
-                const uint32_t v = *(const uint32_t*)(vrow + 4 * w);
-#pragma unroll
-                for (int b = 0; b < 4; b++) px[4 * w + b] = (int)((v >> (8 * b)) & 255);
-            }
-            const int e0 = (int)((b0.x >> seg8) & 255);
-            e1 = (int)(((isC ? b0.z : b0.y) >> seg8) & 255);
-            e2 = isC ? 0 : (int)((b0.z >> seg8) & 255); e3 = isC ? 0 : (int)((b0.w >> seg8) & 255);
-            if (__ballot(e0 != 0) != 0ull) {
-                filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, al, be, t1, t2, t3);
-                *(uint32_t*)vrow = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
-            }
-        }
+        db_left_edge<BS4>(L, px, b0, v_on, thr);
         wave_sync();
         // the previous macroblock of each row is final now: the upper row's goes into the ring slot the lower row reads further
         // down in this same iteration, the lower row's to the next pair.  mx == mbw is the closing publish of a row (no shift,
         // no left edge) - at this point too, because the lower row's last macroblock is waiting for it.
         if (in_range) store_prev(mx, have_cur);
-        if (any_v) {
-            if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-            if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-            if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-#pragma unroll
-            for (int w = 1; w < 5; w++)
-                if (w < 3 || !isC)
-                    *(uint32_t*)(vrow + 4 * w) = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
-        }
+        db_inner_vertical<BS4>(L, px, b0, v_on, thr);
         wave_sync();   // (the ring slot written above is read by the other half's lanes)
         // top apron, needed by the horizontal edges only: the upper row waits for the previous pair's granules, the lower row
         // takes the ring slot the upper row has just filled
-        {
-            const bool need_g = have_cur && !from_lds && !first_row;   // lanes of the upper half
-            unsigned spins = 0;
-            while (!timed_out) {
-                const bool bad = need_g && hl < 24 && (unsigned)(g >> 32) != R.serial;
-                if (__ballot(bad) == 0ull) break;
-                if (++spins > (1u << 20)) { timed_out = true; break; }
-                __builtin_amdgcn_s_sleep(1);
-                if (need_g) g = AT_LOAD(handoff + ((size_t)grow * D.mbw + mx) * 24 + glane);
-            }
-            if (have_cur && !first_row && hl < 24) {
-                const uint32_t v = from_lds ? s_ring[mx & 1][gk] : (uint32_t)g;
-                if (hl < 16) *(uint32_t*)&SY(-4 + (gk >> 2), (gk & 3) * 4) = v;
-                else *(uint32_t*)&SC((gk - 16) >> 2, -2 + (((gk - 16) >> 1) & 1), ((gk - 16) & 1) * 4) = v;
-            }
-        }
+        db_wait_tags(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out);
+        if (have_cur && !first_row && hl < 24) db_put_apron(s_y, hl, from_lds ? s_ring[mx & 1][hl] : (uint32_t)g);
         wave_sync();
-        if (any_h) {
-            int px[20];
-#pragma unroll
-            for (int r = 0; r < 20; r++) px[r] = hcol[r * hstride];
-            const int e0 = (int)((b1.x >> seg8) & 255), e1 = (int)(((isC ? b1.z : b1.y) >> seg8) & 255);
-            const int e2 = isC ? 0 : (int)((b1.z >> seg8) & 255), e3 = isC ? 0 : (int)((b1.w >> seg8) & 255);
-            if (__ballot(e0 != 0) != 0ull) filt_uni<BS4>(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], e0, isC, al, be, t1, t2, t3);
-            if (__ballot(e1 != 0) != 0ull) filt_uni<BS4>(px[4], px[5], px[6], px[7], px[8], px[9], px[10], px[11], e1, isC, al, be, t1, t2, t3);
-            if (__ballot(e2 != 0) != 0ull) filt_uni<BS4>(px[8], px[9], px[10], px[11], px[12], px[13], px[14], px[15], e2, isC, al, be, t1, t2, t3);
-            if (__ballot(e3 != 0) != 0ull) filt_uni<BS4>(px[12], px[13], px[14], px[15], px[16], px[17], px[18], px[19], e3, isC, al, be, t1, t2, t3);
-#pragma unroll
-            for (int r = 1; r < 19; r++) {
-                const bool both = r == 3 || r == 4 || r == 7 || r == 8;
-                if (both || !isC) hcol[r * hstride] = (uint8_t)px[r];
-            }
-        }
+        db_horizontal<BS4>(L, b1, h_on, thr, thr);
         wave_sync();
         consume();
         // the top apron (rows 12..15 / 6..7 of the macroblock above) is final: store it
-        if (have_cur && !first_row) {
-            if (hl < 16) *(uint32_t*)(D.pl[0] + (size_t)(16 * my - 4 + (gk >> 2)) * D.cw + 16 * mx + (gk & 3) * 4) = *(const uint32_t*)&SY(-4 + (gk >> 2), (gk & 3) * 4);
-            else if (hl < 24) {
-                const int k = gk - 16, pl = k >> 2, r = (k >> 1) & 1, c4 = (k & 1) * 4;
-                *(uint32_t*)((pl ? D.pl[2] : D.pl[1]) + (size_t)(8 * my - 2 + r) * cs + 8 * mx + c4) = *(const uint32_t*)&SC(pl, -2 + r, c4);
-            }
-        }
+        if (have_cur && !first_row && hl < 24) db_store_apron(D, s_y, hl, mx, my);
         if (mx + 1 >= 0 && mx + 1 <= last_mx) { cur_y0 = pf_y0; cur_y1 = pf_y1; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; }
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;
-#undef SY
-#undef SC
 }
 template <bool BS4, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_pairs(DbRowParams R)
