@@ -16,6 +16,8 @@
  * (slice_qp_delta, mb_qp_delta), chroma QP index offsets, deblocking filter offsets and idc 0 / 1 / 2 (one set per picture),
  * slices of any shape in raster order (no FMO / ASO).  A stream outside that is refused with MI355X_H264_E_STREAM and a message naming the
  * syntax element; nothing is ever decoded approximately.
+ *
+ * Many streams on one GPU: mi355x_h264_dec_group_* below decodes the next pictures of up to 64 streams of one coded size in one step.
  */
 #ifndef MI355X_H264_DEC_H
 #define MI355X_H264_DEC_H
@@ -53,6 +55,37 @@ int mi355x_h264_dec_picture_info(const mi355x_h264_decoder *dec, int *width, int
  * (RetrieveFrameData, VideoDecoderNetint.cpp:640, PIXEL_FORMAT_YUV_420P) */
 int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder *dec, uint8_t *dst, size_t cap);
 int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder *dec, void *d_dst, size_t cap);
+
+/* ---- decoder groups: the next pictures of up to 64 streams reconstructed in ONE step ----
+ * One decoder object per stream costs each picture its own uploads and five to eight launches that fill a fraction of the GPU.  A
+ * group decodes the streams' next access units together: they are parsed side by side on a small pool of threads the group owns
+ * (min(streams, 8); MI355X_H264_DEC_PARSE_THREADS = 1..16), and the step then makes one set of transfers and one set of launches
+ * whatever the number of streams.  All streams of a group have one coded size - that of the first IDR picture any of them delivers;
+ * a stream of another size is refused with E_STREAM, the others go on.  Every stream keeps what a decoder keeps: its parser, its
+ * reference pictures and ring position, its crop, and the rule that after an error P pictures are refused until its next IDR
+ * picture.  A damaged or unsupported access unit fails its own stream only.  A group is driven by one thread at a time. */
+typedef struct mi355x_h264_dec_group mi355x_h264_dec_group;
+int mi355x_h264_dec_group_create(int device, int streams /* 1..64 */, mi355x_h264_dec_group **out);
+void mi355x_h264_dec_group_destroy(mi355x_h264_dec_group *g);
+/* one STEP: aus[i] / lens[i] = the next access unit of stream i, or aus[i] = NULL: stream i takes no part in this step.
+ * rc[i] = MI355X_H264_OK / E_STREAM / ... per stream, got[i] = 1 when stream i decoded a picture in this step (all four arrays have
+ * `streams` entries).  Returns < 0 only for what concerns the whole group (arguments, device, a timed-out wavefront - which leaves
+ * every picture of its step unusable as a reference: all its streams wait for an IDR picture).  The step is LAUNCHED on return, not
+ * necessarily finished: the next call parses while the GPU reconstructs, and waits for the step in flight before it launches its
+ * own.  read_*, debug_plane and sync wait first.  MI355X_H264_DEC_SYNC=1 waits inside every call, as for the single decoder. */
+int mi355x_h264_dec_group_decode(mi355x_h264_dec_group *g, const uint8_t *const *aus, const size_t *lens, int *got, int *rc);
+int mi355x_h264_dec_group_sync(mi355x_h264_dec_group *g);
+/* the message of stream's last refusal; stream = -1: of the group's own last failure */
+const char *mi355x_h264_dec_group_last_error(const mi355x_h264_dec_group *g, int stream);
+/* the stream's last decoded picture: as the single decoder's calls of these names */
+int mi355x_h264_dec_group_picture_info(const mi355x_h264_dec_group *g, int stream, int *w, int *h, int *cw, int *ch);
+int64_t mi355x_h264_dec_group_read_i420(mi355x_h264_dec_group *g, int stream, uint8_t *dst, size_t cap);
+int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group *g, int stream, void *d_dst, size_t cap);
+int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group *g, int stream, int plane, void *dst, size_t cap);
+/* what the last step was: out[0] its serial number, out[1] pictures it carried, out[2] kernel launches it made, out[3] host-to-device
+ * transfers it made, out[4] parse threads used; with n >= 7 also out[5] / out[6]: microseconds the host spent parsing / launching
+ * (and, with MI355X_H264_DEC_SYNC, waiting).  Returns the number of values written */
+int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group *g, int64_t *out, int n);
 
 /* ---- test / measurement hooks ---- */
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 */

@@ -1,0 +1,395 @@
+// media_amd/csrc/dec_group.h -- decoder groups (include/mi355x_h264_dec.h, mi355x_h264_dec_group_*): the next pictures of up to 64
+// streams reconstructed in ONE lockstep step on one engine with batch = streams, as the stream hub does for encoders.  A step is
+// one set of uploads and one set of launches whatever the number of streams: the streams' access units are parsed side by side on
+// a small pool of threads (dec_group_sched.h, which also rotates the two sets of pinned buffers), every parsed picture is copied
+// into its item's slice of group-wide pinned arrays laid [item][...], and each array then travels in one transfer that covers the
+// items from the lowest to the highest taking part (a stream that sits the step out inside that range has its stale slice sent
+// along: the per-macroblock arrays on the device are scratch of the step, nobody reads an absent item's).  What the pictures of a
+// step have of their own - ring slots, reference lists, offsets, filter controls, slice bands - is the step's position table
+// (dev_common.h DecPos); the kernels are k_dec_widen_pos / _inter_pos / _bs_pos, k_dec_resid<true>, k_pintra_rows<true, true> and
+// k_deblock_rows<BS4, true, true>.
+#pragma once
+#include "dec_group_sched.h"
+
+namespace {
+
+struct DecGroupStream {
+    h264dec::Parser parser;
+    int have_refs = 0, max_refs = 1;
+    int cur = 0;         // ring slot its next picture is written to
+    int last = -1;       // ring slot of its last decoded picture
+    int width = 0, height = 0, crop_x = 0, crop_y = 0;
+    uint64_t pictures = 0;
+    // the step in hand
+    const uint8_t* au = nullptr;
+    size_t len = 0;
+    int prc = 0;         // what the parser said: 1 picture, 0 none, -1 refused, -2 out of memory
+    bool copied = false; // its picture lies in the pinned set
+    char err[256] = {0};
+};
+
+// the per-macroblock arrays of a step: bytes per macroblock, and the arrays themselves (pinned: one per set; device: one)
+enum { DG_MB, DG_MVQ, DG_AUX, DG_LV8, DG_QP, DG_AVAIL, DG_MV4, DG_REFQ, DG_ARRAYS };
+constexpr size_t DG_BYTES[DG_ARRAYS] = {sizeof(MbInfo), 16, 16, LV_STRIDE, 1, 1, 64, 4};
+
+}  // namespace
+
+struct mi355x_h264_dec_group {
+    int device = 0, nstreams = 0;
+    mi355x_h264_encoder* eng = nullptr;
+    int mbw = 0, mbh = 0;
+    DecGroupStream* st = nullptr;        // [nstreams]
+    DecGroupSched sched;
+    uint8_t* h_arr[2][DG_ARRAYS] = {};   // pinned sets, [item][macroblock]
+    uint8_t* d_arr[DG_ARRAYS] = {};      // device (MbInfo, quadrant vectors and Intra4x4 modes are the engine's own arrays)
+    DecPos* h_tab[2] = {nullptr, nullptr};
+    DecPos* d_tab = nullptr;
+    DecBigLevel* h_big[2] = {nullptr, nullptr};
+    size_t h_big_cap[2] = {0, 0};
+    DecBigLevel* d_big = nullptr;
+    size_t d_big_cap = 0;
+    DevMem mem;
+    hipEvent_t up_done[2] = {nullptr, nullptr};
+    bool busy = false;                   // a step is in flight on the engine's stream
+    int flight[DEC_GROUP_MAX_STREAMS];   // its streams
+    int nflight = 0;
+    int intra_slots = 32, filter_slots = 32;   // pictures the row wavefronts hold at a time (the rest are walked to)
+    int64_t step_serial = 0, last[7] = {0, 0, 0, 0, 0, 0, 0};
+    char err[256] = {0};
+};
+
+namespace {
+
+int env_int(const char* name, int lo, int hi, int dflt)
+{
+    const char* v = getenv(name);
+    if (!v || !*v) return dflt;
+    return std::min(hi, std::max(lo, atoi(v)));
+}
+
+void dg_drop_refs(DecGroupStream& s) { s.have_refs = 0; s.parser.lose_refs(); }
+
+// the step in flight has finished; a wavefront that timed out leaves none of the step's pictures usable as a reference
+int dg_wait(mi355x_h264_dec_group* g)
+{
+    if (!g->busy) return MI355X_H264_OK;
+    g->busy = false;
+    mi355x_h264_encoder* e = g->eng;
+    HIPCHK(g->err, hipStreamSynchronize(e->stream));
+    const int rc = handoff_timeout(e->slots[0].sync, g->err);
+    if (rc) for (int k = 0; k < g->nflight; k++) dg_drop_refs(g->st[g->flight[k]]);
+    return rc;
+}
+
+void dg_free_geometry(mi355x_h264_dec_group* g)
+{
+    g->mem.free_all();
+    for (int k = 0; k < 2; k++) {
+        for (auto& p : g->h_arr[k]) p = nullptr;
+        g->h_tab[k] = nullptr;
+    }
+    for (auto& p : g->d_arr) p = nullptr;
+    g->d_tab = nullptr;
+}
+
+// engine and arrays for the group's geometry (that of the first IDR picture it meets)
+int dg_create_geometry(mi355x_h264_dec_group* g, int mbw, int mbh)
+{
+    mi355x_h264_config cfg;
+    mi355x_h264_default_config(&cfg);
+    cfg.width = 16 * mbw; cfg.height = 16 * mbh; cfg.refs = 3; cfg.device = g->device; cfg.batch = g->nstreams;
+    const int crc = create_engine(&cfg, &g->eng, false);
+    if (crc != MI355X_H264_OK) return set_err(g->err, crc, "engine for %d streams of %dx%d macroblocks could not be created", g->nstreams, mbw, mbh);
+    g->mbw = mbw; g->mbh = mbh;
+    const size_t n = (size_t)mbw * mbh * g->nstreams;
+    bool ok = true;
+    for (int a = 0; a < DG_ARRAYS && ok; a++) {
+        for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_arr[k][a], n * DG_BYTES[a]) == hipSuccess;
+        if (ok && a >= DG_LV8) ok = g->mem.dev(&g->d_arr[a], n * DG_BYTES[a]) == hipSuccess;
+    }
+    for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_tab[k], (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
+    ok = ok && g->mem.dev(&g->d_tab, (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
+    if (!ok) {
+        dg_free_geometry(g);
+        destroy_engine(g->eng); g->eng = nullptr;
+        return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the arrays of %d streams of %dx%d macroblocks", g->nstreams, mbw, mbh);
+    }
+    mi355x_h264_encoder* e = g->eng;
+    g->d_arr[DG_MB] = (uint8_t*)e->d_mb; g->d_arr[DG_MVQ] = (uint8_t*)e->d_mvq; g->d_arr[DG_AUX] = e->d_aux;
+    return MI355X_H264_OK;
+}
+
+// the parsed picture of stream i into its slice of pinned set k (run by the stream's parse job, or by the caller in the step that
+// fixes the geometry)
+void dg_copy_picture(mi355x_h264_dec_group* g, int i, int k)
+{
+    DecGroupStream& s = g->st[i];
+    const h264dec::Picture& pic = s.parser.picture();
+    const size_t n = (size_t)g->mbw * g->mbh;
+    static_assert(sizeof(h264dec::MbRec) == sizeof(MbInfo), "layout of the parser's macroblock records");
+    const void* src[DG_ARRAYS] = {pic.mb.data(), pic.mvq.data(), pic.aux.data(), pic.levels8.data(), pic.mbqp.data(), pic.mbavail.data(),
+                                  pic.mv4.data(), pic.refq.data()};
+    for (int a = 0; a < DG_ARRAYS; a++) {
+        if (a >= DG_MV4 && !pic.has_inter) continue;   // (not uploaded and not read: no inter macroblock)
+        memcpy(g->h_arr[k][a] + (size_t)i * n * DG_BYTES[a], src[a], n * DG_BYTES[a]);
+    }
+    s.copied = true;
+}
+
+int dg_stream_fail(DecGroupStream& s, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0)
+{
+    snprintf(s.err, sizeof(s.err), fmt, a, b, c, d);
+    dg_drop_refs(s);
+    return MI355X_H264_E_STREAM;
+}
+
+// one step.  rc[] / got[] per stream; the return value is what concerns the whole group
+int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* lens, int* got, int* rc)
+{
+    const int S = g->nstreams;
+    g->err[0] = 0;
+    for (int i = 0; i < S; i++) { got[i] = 0; rc[i] = MI355X_H264_OK; }
+    if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+    int jobs[DEC_GROUP_MAX_STREAMS], njobs = 0;
+    for (int i = 0; i < S; i++)
+        if (aus[i]) {
+            DecGroupStream& s = g->st[i];
+            s.au = aus[i]; s.len = lens[i]; s.prc = 0; s.copied = false; s.err[0] = 0;
+            jobs[njobs++] = i;
+        }
+    // the set whose uploads (two steps back) are out of the way; the step in flight reads the other
+    hipError_t werr = hipSuccess;
+    const int k = g->sched.begin_step([&](int set) { werr = hipEventSynchronize(g->up_done[set]); });
+    // (a failure between the first copy out of the set and the event behind the last: the set is handed out again by the next call
+    // with no event to wait for, so the copies already queued are waited for here)
+    struct EndStep {
+        DecGroupSched& s; hipStream_t queued_on = nullptr; bool launched = false;
+        ~EndStep() { if (queued_on && !launched) (void)hipStreamSynchronize(queued_on); s.end_step(launched); }
+    } end{g->sched};
+    if (werr != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipEventSynchronize: %s", hipGetErrorString(werr));
+    const double t0 = now_ms();
+    const DecGroupSched::ParseFn parse = [g](int i, int set) {
+        DecGroupStream& s = g->st[i];
+        try {
+            s.prc = s.parser.parse_access_unit(s.au, s.len, false);
+            if (s.prc > 0 && g->eng && s.parser.picture().mbw == g->mbw && s.parser.picture().mbh == g->mbh) dg_copy_picture(g, i, set);
+        } catch (const std::exception&) {
+            s.prc = -2;
+        }
+    };
+    g->sched.run(jobs, njobs, k, parse);
+    const double t1 = now_ms();
+    g->step_serial++;
+    g->last[0] = g->step_serial; g->last[1] = g->last[2] = g->last[3] = 0; g->last[4] = g->sched.last_threads;
+    g->last[5] = (int64_t)((t1 - t0) * 1e3); g->last[6] = 0;
+    // the step in flight must be out of the way before this one is launched; its time-out flag is looked at here
+    if (const int wrc = dg_wait(g)) {
+        for (int j = 0; j < njobs; j++) { dg_drop_refs(g->st[jobs[j]]); rc[jobs[j]] = wrc; snprintf(g->st[jobs[j]].err, sizeof(g->st[jobs[j]].err), "%s", g->err); }
+        return wrc;
+    }
+    // which of the parsed pictures this step takes, and the table row of each
+    int pos_stream[DEC_GROUP_MAX_STREAMS], npos = 0;
+    DecPos* tab = nullptr;
+    bool any_inter = false, any_intra = false, any_plain = false, any_bs4 = false;
+    size_t nbig = 0;
+    for (int j = 0; j < njobs; j++) {
+        const int i = jobs[j];
+        DecGroupStream& s = g->st[i];
+        if (s.prc == 0) continue;
+        if (s.prc == -2) { snprintf(s.err, sizeof(s.err), "out of host memory while parsing the access unit"); dg_drop_refs(s); rc[i] = MI355X_H264_E_NOMEM; continue; }
+        if (s.prc < 0) { snprintf(s.err, sizeof(s.err), "%s", s.parser.error().c_str()); dg_drop_refs(s); rc[i] = MI355X_H264_E_STREAM; continue; }
+        const h264dec::Picture& pic = s.parser.picture();
+        const h264dec::Sps& sps = s.parser.sps();
+        if (!g->eng) {
+            if (!pic.idr) { rc[i] = dg_stream_fail(s, "the stream must start with an IDR picture"); continue; }
+            if (const int crc = dg_create_geometry(g, pic.mbw, pic.mbh)) {
+                for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
+                return crc;
+            }
+        }
+        if (pic.mbw != g->mbw || pic.mbh != g->mbh) {
+            rc[i] = dg_stream_fail(s, "coded size %dx%d differs from the group's %dx%d", 16 * pic.mbw, 16 * pic.mbh, 16 * g->mbw, 16 * g->mbh);
+            continue;
+        }
+        mi355x_h264_encoder* e = g->eng;
+        if (pic.idr) s.have_refs = 0;
+        if (pic.has_inter && (s.have_refs < 1 || pic.num_ref_active > s.have_refs)) {
+            rc[i] = dg_stream_fail(s, "a P picture refers to %d reference pictures, %d are held", pic.num_ref_active, s.have_refs);
+            continue;
+        }
+        bool list_ok = true;
+        for (int r = 0; pic.has_inter && r < pic.num_ref_active && r < 3; r++)
+            if (pic.ref_age[r] < 0 || pic.ref_age[r] >= s.have_refs) { rc[i] = dg_stream_fail(s, "reference list entry %d is not a held picture", r); list_ok = false; break; }
+        if (!list_ok) continue;
+        try {
+            if (!s.copied) dg_copy_picture(g, i, k);
+        } catch (const std::exception&) { rc[i] = MI355X_H264_E_NOMEM; dg_drop_refs(s); continue; }
+        s.width = pic.width; s.height = pic.height; s.crop_x = 2 * sps.crop_l; s.crop_y = 2 * sps.crop_t;
+        s.max_refs = std::max(1, sps.max_refs);
+        // the table row (dev_common.h DecPos)
+        tab = g->h_tab[k];
+        DecPos& T = tab[npos];
+        memset(&T, 0, sizeof(T));
+        const bool filtered = pic.deblock_idc != 1;
+        uint32_t w0 = (uint32_t)i | ((uint32_t)s.cur << 8) | ((uint32_t)std::max(1, s.have_refs) << 16);
+        for (int r = 0; r < 3; r++) {
+            // RefPicList0 entry r = the reference picture decoded ref_age[r] + 1 reference pictures ago (ring slot cur - 1 - age)
+            const int age = std::min(r < pic.num_ref_active ? pic.ref_age[r] : r, std::max(0, s.have_refs - 1));
+            w0 |= (uint32_t)((s.cur + e->nbuf - 1 - age) % e->nbuf) << (10 + 2 * r);
+        }
+        w0 |= (pic.has_inter ? 1u << 24 : 0u) | (pic.has_intra ? 1u << 25 : 0u) | (filtered ? 1u << 26 : 0u) | (pic.deblock_idc == 0 ? 1u << 27 : 0u);
+        T.w[0] = w0;
+        T.w[1] = (uint32_t)(uint8_t)(int8_t)pic.cqo[0] | ((uint32_t)(uint8_t)(int8_t)pic.cqo[1] << 8) | ((uint32_t)(uint8_t)(int8_t)pic.filter_oa << 16) |
+                 ((uint32_t)(uint8_t)(int8_t)pic.filter_ob << 24);
+        // slices that are bands of whole rows run as independent wavefronts; any other shape: one wavefront over the picture.  The
+        // filter sees one slice with idc 0 (edges between slices are filtered) and with slices that are no bands (k_dec_bs has
+        // zeroed the strengths between them where idc 2 says so)
+        const int rows = pic.slice_rows > 0 ? pic.slice_rows : g->mbh;
+        const int frows = (pic.deblock_idc == 0 || pic.slice_rows < 0) ? g->mbh : rows;
+        T.w[2] = (uint32_t)rows; T.w[3] = recip32(rows);
+        T.w[4] = (uint32_t)frows; T.w[5] = recip32(frows);
+        any_inter |= pic.has_inter; any_intra |= pic.has_intra;
+        if (filtered) { if (pic.has_intra) any_bs4 = true; else any_plain = true; }
+        nbig += pic.big.size();
+        pos_stream[npos++] = i;
+    }
+    if (npos == 0) return MI355X_H264_OK;
+
+    mi355x_h264_encoder* e = g->eng;
+    hipStream_t st = e->stream;
+    const size_t nmb = (size_t)e->nmb;
+    int transfers = 0, launches = 0;
+    // one transfer per array: the items from the lowest to the highest taking part
+    end.queued_on = st;
+    const int i0 = pos_stream[0], i1 = pos_stream[npos - 1];   // (positions are in stream order)
+    for (int a = 0; a < DG_ARRAYS; a++) {
+        if (a >= DG_MV4 && !any_inter) continue;
+        const size_t off = (size_t)i0 * nmb * DG_BYTES[a], bytes = (size_t)(i1 - i0 + 1) * nmb * DG_BYTES[a];
+        HIPCHK(g->err, hipMemcpyAsync(g->d_arr[a] + off, g->h_arr[k][a] + off, bytes, hipMemcpyHostToDevice, st));
+        transfers++;
+    }
+    HIPCHK(g->err, hipMemcpyAsync(g->d_tab, tab, (size_t)npos * sizeof(DecPos), hipMemcpyHostToDevice, st));
+    transfers++;
+    if (nbig) {   // the streams' large levels as one list, the indices counted from item 0
+        static_assert(sizeof(h264dec::Picture::Big) == sizeof(DecBigLevel), "layout of the list of large levels");
+        if (nbig > g->h_big_cap[k]) {   // (no upload out of this set is in flight: begin_step has waited)
+            if (g->h_big[k]) (void)hipHostFree(g->h_big[k]);
+            g->h_big[k] = nullptr; g->h_big_cap[k] = 0;
+            const size_t cap = nbig * 2 + 1024;
+            HIPCHK(g->err, hipHostMalloc((void**)&g->h_big[k], cap * sizeof(DecBigLevel), hipHostMallocDefault));
+            g->h_big_cap[k] = cap;
+        }
+        if (nbig > g->d_big_cap) {
+            HIPCHK(g->err, hipStreamSynchronize(st));
+            if (g->d_big) (void)hipFree(g->d_big);
+            g->d_big = nullptr; g->d_big_cap = 0;
+            const size_t cap = nbig * 2 + 1024;
+            HIPCHK(g->err, hipMalloc((void**)&g->d_big, cap * sizeof(DecBigLevel)));
+            g->d_big_cap = cap;
+        }
+        size_t at = 0;
+        for (int p = 0; p < npos; p++) {
+            const auto& big = g->st[pos_stream[p]].parser.picture().big;
+            const uint32_t base = (uint32_t)((size_t)pos_stream[p] * nmb * LV_STRIDE);
+            for (const auto& b : big) g->h_big[k][at++] = DecBigLevel{b.idx + base, b.val};
+        }
+        HIPCHK(g->err, hipMemcpyAsync(g->d_big, g->h_big[k], nbig * sizeof(DecBigLevel), hipMemcpyHostToDevice, st));
+        transfers++;
+    }
+    HIPCHK(g->err, hipEventRecord(g->up_done[k], st));   // every copy out of the set has been queued
+    end.launched = true;
+
+    const dim3 wave(64);
+    const unsigned NP = (unsigned)npos;
+    {
+        const int words = (int)(nmb * (LV_STRIDE / 4));
+        hipLaunchKernelGGL(k_dec_widen_pos, dim3((words + 255) / 256, NP), dim3(256), 0, st, (const uint32_t*)g->d_arr[DG_LV8], (const MbInfo*)e->d_mb, e->d_levels, (int)nmb,
+                           (const DecPos*)g->d_tab);
+        launches++;
+        if (nbig) { hipLaunchKernelGGL(k_dec_patch, dim3(((int)nbig + 255) / 256), dim3(256), 0, st, (const DecBigLevel*)g->d_big, (int)nbig, e->d_levels); launches++; }
+    }
+    FrameParams P = frame_params(e);
+    P.w = e->cw; P.h = e->ch;
+    P.nref = 1;
+    for (int p = 0; p < 3; p++) P.rec[p] = e->d_plane_base[p];   // (the positions' planes and references: from the table)
+    P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
+    P.sl.rows = e->mbh; P.sl.inv = recip32(e->mbh);
+    P.band.row0 = 0; P.band.rows = e->mbh;
+    P.mbqp = g->d_arr[DG_QP]; P.mv4 = (const int16_t*)g->d_arr[DG_MV4]; P.refq = g->d_arr[DG_REFQ]; P.mbavail = g->d_arr[DG_AVAIL];
+    P.dectab = g->d_tab;
+    unsigned* const h_err = e->slots[0].sync.h_err;
+    if (any_inter) {
+        hipLaunchKernelGGL(k_dec_inter_pos, dim3(e->nmb, NP), wave, 0, st, P);
+        hipLaunchKernelGGL(k_dec_resid<true>, dim3((e->nmb + 3) / 4, NP), wave, 0, st, P);
+        launches += 2;
+    }
+    if (any_intra) {
+        const IntraRowParams R = intra_row_params(e, P, h_err, npos);
+        hipLaunchKernelGGL((k_pintra_rows<true, true>), dim3(e->mbh, std::min(NP, (unsigned)g->intra_slots)), wave, 0, st, R);
+        launches++;
+    }
+    if (any_plain || any_bs4) {
+        const unsigned db_serial = next_nonzero(e->serial);
+        DecBsParams B{};
+        B.mb = e->d_mb; B.mv4 = (const int16_t*)g->d_arr[DG_MV4]; B.refq = g->d_arr[DG_REFQ]; B.bs = (uint8_t*)e->d_bs; B.mbw = e->mbw; B.nmb = e->nmb; B.mbdiv = P.mbdiv;
+        B.mbavail = g->d_arr[DG_AVAIL];
+        hipLaunchKernelGGL(k_dec_bs_pos, dim3((e->nmb + 1) / 2, NP), wave, 0, st, B, e->d_anybs, db_serial, (const DecPos*)g->d_tab);
+        launches++;
+        // always the per-edge thresholds; the form with the bS 4 filter for the positions with intra macroblocks, the one without
+        // for the others (the pair of launches of the encoder's P steps, chosen by the table's flags)
+        DbParams D = db_params(e, e->d_plane_base, P.sl, 26);
+        D.mbqp = g->d_arr[DG_QP];
+        DbRowParams R = db_row_params(e, D, h_err, db_serial, P.pic_serial, 0, npos);
+        R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c; R.dectab = g->d_tab;
+        const dim3 grid(e->mbh, std::min(NP, (unsigned)g->filter_slots));
+        if (any_plain) { R.need_intra = -1; hipLaunchKernelGGL((k_deblock_rows<false, true, true>), grid, wave, 0, st, R); launches++; }
+        if (any_bs4) { R.need_intra = 1; hipLaunchKernelGGL((k_deblock_rows<true, true, true>), grid, wave, 0, st, R); launches++; }
+    }
+    HIPCHK(g->err, hipGetLastError());
+    g->busy = true;
+    g->nflight = npos;
+    for (int p = 0; p < npos; p++) g->flight[p] = pos_stream[p];
+    for (int p = 0; p < npos; p++) {   // parser and ring take the picture in together
+        const int i = pos_stream[p];
+        DecGroupStream& s = g->st[i];
+        const bool is_ref = s.parser.picture().is_ref;
+        s.last = s.cur;
+        s.parser.commit();
+        if (is_ref) {   // sliding window (8.2.5.3)
+            s.cur = (s.cur + 1) % e->nbuf;
+            s.have_refs = std::min(s.have_refs + 1, std::min(s.max_refs, e->nrefs));
+        }
+        s.pictures++;
+        got[i] = 1;
+    }
+    g->last[1] = npos; g->last[2] = launches; g->last[3] = transfers;
+    static const bool no_lookahead = getenv("MI355X_H264_DEC_SYNC") != nullptr;   // (measurements: wait for every step before returning)
+    int wrc = MI355X_H264_OK;
+    if (no_lookahead) wrc = dg_wait(g);
+    g->last[6] = (int64_t)((now_ms() - t1) * 1e3);
+    if (wrc) for (int p = 0; p < npos; p++) { got[pos_stream[p]] = 0; rc[pos_stream[p]] = wrc; }
+    return wrc;
+}
+
+int64_t dg_read(mi355x_h264_dec_group* g, int stream, void* dst, size_t cap, bool to_device)
+{
+    if (!g || !dst || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0) return MI355X_H264_E_ARG;
+    const DecGroupStream& s = g->st[stream];
+    const size_t w = (size_t)s.width, h = (size_t)s.height, need = w * h * 3 / 2;
+    if (cap < need) return MI355X_H264_E_ARG;
+    if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+    if (const int wrc = dg_wait(g)) return wrc;   // the picture asked for may still be in flight
+    const mi355x_h264_encoder* e = g->eng;
+    uint8_t* o = (uint8_t*)dst;
+    const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    for (int p = 0; p < 3; p++) {
+        const size_t pw = p ? w / 2 : w, ph = p ? h / 2 : h, pitch = p ? (size_t)e->cw / 2 : (size_t)e->cw;
+        const uint8_t* plane = e->d_plane_base[p] + (size_t)stream * (p ? e->st_c : e->st_y) + (size_t)s.last * (p ? e->st_ring_c : e->st_ring_y);
+        const uint8_t* src = plane + (size_t)(p ? s.crop_y / 2 : s.crop_y) * pitch + (size_t)(p ? s.crop_x / 2 : s.crop_x);
+        if (hipMemcpy2D(o, pw, src, pitch, pw, ph, kind) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipMemcpy2D");
+        o += pw * ph;
+    }
+    return (int64_t)need;
+}
+
+}  // namespace

@@ -116,7 +116,7 @@ int dec_submit(mi355x_h264_decoder* d, const h264dec::Picture& pic)
     unsigned* const h_err = e->slots[0].sync.h_err;
     if (pic.has_inter) {
         hipLaunchKernelGGL(k_dec_inter, dim3(e->nmb, 1), dim3(64), 0, st, P);
-        hipLaunchKernelGGL(k_dec_resid, dim3((e->nmb + 3) / 4, 1), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(k_dec_resid<false>, dim3((e->nmb + 3) / 4, 1), dim3(64), 0, st, P);
     }
     if (pic.has_intra) {
         const IntraRowParams R = intra_row_params(e, P, h_err, 1);

@@ -75,6 +75,8 @@ struct MbDiv {
 // macroblock rows row0 .. row0 + rows - 1, always whole slices.  One instance alone: row0 = 0, rows = mbh.
 struct Band { int row0, rows; };
 
+struct DecPos;   // decoder groups: the position table, below
+
 struct FrameParams {
     const uint8_t* src;  // tight picture in HBM: Y (w*h), then U, V planes (I420) or one interleaved UV plane (NV12)
     int src_nv12;        // 1: chroma is read straight from the interleaved plane (no conversion pass)
@@ -127,6 +129,10 @@ struct FrameParams {
     const QpEntry* qtab;
     size_t st_ring_y, st_ring_c;
     int nbuf;
+    // decoder groups (dec_group.h; kernels instantiated for DECODER positions): dectab[position] says what a decoder's picture has
+    // of its own - see DecPos below.  rec[] = the plane bases as for itemtab; mbqp / mv4 / refq / mbavail lie [item] with st_mb
+    // macroblocks between items.  Every other launch leaves it null.
+    const DecPos* dectab;
 };
 
 // itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 16..21 QP
@@ -202,6 +208,64 @@ __device__ __forceinline__ int batch_item(const uint32_t* itemtab, int pos)
 {
     if constexpr (!IND) return pos;
     else return item_ref(itemtab, pos).item;
+}
+
+// ---- decoder groups: pictures of DIFFERENT streams decoded in one lockstep step.  A decoder's picture differs from its neighbours
+// in more than the hub's itemtab word carries (reference lists change with list modification and non-reference pictures, every picture
+// parameter set has its offsets, every slice header its filter controls), so a decoder step has a table of its own: 32 bytes per
+// position in device memory, fetched with scalar loads that depend on blockIdx.y alone.
+//   w[0]  bits 0..7 batch item, 8..9 ring slot written, 10..15 ring slots of RefPicList0 entries 0..2, 16..17 nref,
+//         24 inter macroblocks present, 25 intra macroblocks present, 26 the picture is loop-filtered,
+//         27 edges between slices are filtered too (disable_deblocking_filter_idc 0)
+//   w[1]  four signed bytes: chroma_qp_index_offset, second_chroma_qp_index_offset, FilterOffsetA, FilterOffsetB
+//   w[2], w[3]  SliceRows of the intra wavefront (bands of whole rows, else the picture's height)
+//   w[4], w[5]  SliceRows of the loop filter (the picture's height with idc 0 or slices that are no bands)
+struct DecPos { uint32_t w[8]; };
+struct DecPosRef {
+    int item, cur, ref[3], nref;
+    bool inter, intra, filtered, across;
+    int cqo_cb, cqo_cr, oa, ob;
+    SliceRows sl, fsl;
+};
+__device__ __forceinline__ DecPosRef dec_pos(const DecPos* tab, int pos)
+{
+    const uint4 a = *(const uint4*)&tab[pos].w[0];
+    const uint2 b = *(const uint2*)&tab[pos].w[4];
+    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };   // wave-uniform: scalar loads
+    const uint32_t w0 = uni(a.x), w1 = uni(a.y);
+    DecPosRef d;
+    d.item = (int)(w0 & 0xFFu); d.cur = (int)((w0 >> 8) & 3u);
+    d.ref[0] = (int)((w0 >> 10) & 3u); d.ref[1] = (int)((w0 >> 12) & 3u); d.ref[2] = (int)((w0 >> 14) & 3u);
+    d.nref = (int)((w0 >> 16) & 3u);
+    d.inter = ((w0 >> 24) & 1u) != 0; d.intra = ((w0 >> 25) & 1u) != 0; d.filtered = ((w0 >> 26) & 1u) != 0; d.across = ((w0 >> 27) & 1u) != 0;
+    d.cqo_cb = (int)(int8_t)(w1 & 255u); d.cqo_cr = (int)(int8_t)((w1 >> 8) & 255u);
+    d.oa = (int)(int8_t)((w1 >> 16) & 255u); d.ob = (int)(int8_t)(w1 >> 24);
+    d.sl.rows = (int)uni(a.z); d.sl.inv = uni(a.w);
+    d.fsl.rows = (int)uni(b.x); d.fsl.inv = uni(b.y);
+    return d;
+}
+// the parameter block of a decoder position: the item's arrays, the ring slots of its picture and of ITS reference list, its offsets
+__device__ __forceinline__ FrameParams dec_view(FrameParams P, const DecPosRef& d)
+{
+    const size_t g = (size_t)d.item;
+    uint8_t* const by = P.rec[0] + g * P.st_y;
+    uint8_t* const bu = P.rec[1] + g * P.st_c;
+    uint8_t* const bv = P.rec[2] + g * P.st_c;
+    P.rec[0] = by + (size_t)d.cur * P.st_ring_y; P.rec[1] = bu + (size_t)d.cur * P.st_ring_c; P.rec[2] = bv + (size_t)d.cur * P.st_ring_c;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        P.refs[r][0] = by + (size_t)d.ref[r] * P.st_ring_y; P.refs[r][1] = bu + (size_t)d.ref[r] * P.st_ring_c; P.refs[r][2] = bv + (size_t)d.ref[r] * P.st_ring_c;
+    }
+    P.ref[0] = P.refs[0][0]; P.ref[1] = P.refs[0][1]; P.ref[2] = P.refs[0][2];
+    P.nref = d.nref;
+    P.mb += g * P.st_mb;
+    P.levels += g * P.st_mb * LV_STRIDE;
+    P.mvq += g * P.st_mb * 8;
+    P.aux += g * P.st_mb * 16;
+    P.mbqp += g * P.st_mb; P.mv4 += g * P.st_mb * 32; P.refq += g * P.st_mb * 4; P.mbavail += g * P.st_mb;
+    P.cqo_cb = d.cqo_cb; P.cqo_cr = d.cqo_cr;
+    P.sl = d.sl;
+    return P;
 }
 
 // Synchronisation inside a ONE-WAVE workgroup.  LDS instructions of one wave execute in program order,

@@ -213,6 +213,7 @@ struct DbRowParams {
     // indirect launches (IND = true, dev_common.h item_ref): position -> item, its ring slot and its QP; d.pl[] = plane bases
     const uint32_t* itemtab;
     size_t st_ring_y, st_ring_c;
+    const DecPos* dectab;    // decoder groups (PERMB && IND): position -> what the picture has of its own (dev_common.h)
 };
 
 // One edge, one line of samples held in registers, branch-free so that luma and
@@ -278,6 +279,22 @@ __device__ __forceinline__ DbThr db_picture_thr(const DbParams& D, const bool is
 template <bool PERMB, bool IND>
 __device__ __forceinline__ bool db_picture_view(const DbRowParams& R, const int pos, DbParams& D, u64*& handoff, const uint32_t*& bsw)
 {
+    if constexpr (PERMB && IND) {
+        // decoder groups: the position is a row of the decoder table (dev_common.h DecPos): item, ring slot, filter offsets, chroma QP
+        // offsets and the filter's slice bands are the picture's own; the thresholds come per edge from mbqp.  need_intra picks the
+        // form by the table's flag (a decoder's I_PCM macroblocks never switch the filter off: anypcm is not looked at)
+        const DecPosRef dp = dec_pos(R.dectab, pos);
+        if (!dp.filtered || R.anybs[dp.item] != R.serial) return false;
+        if (R.need_intra != 0 && dp.intra != (R.need_intra > 0)) return false;
+        D = R.d;
+        const size_t g = (size_t)dp.item;
+        D.pl[0] += g * R.st_y + (size_t)dp.cur * R.st_ring_y; D.pl[1] += g * R.st_c + (size_t)dp.cur * R.st_ring_c; D.pl[2] += g * R.st_c + (size_t)dp.cur * R.st_ring_c;
+        D.mb += g * R.st_mb; D.mbqp += g * R.st_mb;
+        D.oa = dp.oa; D.ob = dp.ob; D.cqo_cb = dp.cqo_cb; D.cqo_cr = dp.cqo_cr; D.sl = dp.fsl;
+        handoff = R.handoff + g * R.st_handoff;
+        bsw = R.bs + g * R.st_mb * 8;
+        return true;
+    } else {
     const int bitem = batch_item<IND>(R.itemtab, pos);
     if (R.anybs[bitem] != R.serial) return false;   // no edge of this picture is filtered
     if (R.anypcm[bitem] == R.pic_serial) return false;
@@ -297,6 +314,7 @@ __device__ __forceinline__ bool db_picture_view(const DbRowParams& R, const int 
     handoff = R.handoff + g * R.st_handoff;
     bsw = R.bs + g * R.st_mb * 8;
     return true;
+    }
 }
 // Filter lane l of a row: 0..15 the luma lines, 16..31 the chroma lines (plane fpl, line).  V phase: the lane holds line fln of
 // its plane (vrow: 4-byte aligned, from column -4), H phase: column fln (hcol: from row -4).  seg8: shift to its segment's strength

@@ -86,9 +86,9 @@ __device__ __forceinline__ const uint8_t* ref_plane(const FrameParams& P, int re
     return pl == 0 ? y : (pl == 1 ? u : v);
 }
 
-__global__ __launch_bounds__(64) void k_dec_inter(FrameParams P0)
+// (k_dec_inter: the batch item is blockIdx.y; k_dec_inter_pos, decoder groups: blockIdx.y is a position of the step's table)
+__device__ __forceinline__ void dec_inter_mb(const FrameParams& P)
 {
-    const FrameParams P = batch_view(P0, blockIdx.y);
     const int lane = threadIdx.x;
     const int mbi = P.band.row0 * P.mbw + (int)blockIdx.x, my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
     const uint32_t w1 = *(const uint32_t*)((const uint8_t*)(P.mb + mbi) + 4);
@@ -118,6 +118,18 @@ __global__ __launch_bounds__(64) void k_dec_inter(FrameParams P0)
         *(uint32_t*)(rec_chroma(P, pl) + (size_t)(8 * my + cyy) * (P.cw / 2) + 8 * mx + cxx) = o;
     }
 }
+__global__ __launch_bounds__(64) void k_dec_inter(FrameParams P0)
+{
+    const FrameParams P = batch_view(P0, blockIdx.y);
+    dec_inter_mb(P);
+}
+__global__ __launch_bounds__(64) void k_dec_inter_pos(FrameParams P0)
+{
+    const DecPosRef d = dec_pos(P0.dectab, blockIdx.y);
+    if (!d.inter) return;
+    const FrameParams P = dec_view(P0, d);
+    dec_inter_mb(P);
+}
 
 // lane = four consecutive levels of one macroblock (LV_STRIDE = 416 = 104 words per macroblock); an I_PCM macroblock's area holds
 // its 384 samples as bytes, which keep their place at the start of the int16 area (intra_mb_core<DEC> reads them there)
@@ -136,6 +148,26 @@ __global__ __launch_bounds__(256) void k_dec_widen(const uint32_t* lv8, const Mb
     o.x = ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
     o.y = ((uint32_t)c & 0xFFFFu) | ((uint32_t)d << 16);
     ((uint2*)(lv16 + (size_t)mbi * LV_STRIDE))[k] = o;
+}
+// decoder groups: blockIdx.y = position; the byte levels and the macroblock records lie [item] like the int16 lists.  (k_dec_patch
+// serves a group as it is: the step's large levels are one list whose indices count from item 0.)
+__global__ __launch_bounds__(256) void k_dec_widen_pos(const uint32_t* lv8, const MbInfo* mb, int16_t* lv16, int nmb, const DecPos* tab)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);   // word index inside the item
+    if (i >= nmb * (LV_STRIDE / 4)) return;
+    const size_t g = (size_t)dec_pos(tab, blockIdx.y).item * nmb;
+    const int mbi = i / (LV_STRIDE / 4), k = i - mbi * (LV_STRIDE / 4);
+    const uint32_t w = lv8[g * (LV_STRIDE / 4) + i];
+    int16_t* const o16 = lv16 + (g + mbi) * LV_STRIDE;
+    if (mb[g + mbi].type == MB_IPCM) {
+        if (k < 96) ((uint32_t*)o16)[k] = w;
+        return;
+    }
+    const int a = (int)(int8_t)(w & 255u), b = (int)(int8_t)((w >> 8) & 255u), c = (int)(int8_t)((w >> 16) & 255u), d = (int)(int8_t)(w >> 24);
+    uint2 o;
+    o.x = ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
+    o.y = ((uint32_t)c & 0xFFFFu) | ((uint32_t)d << 16);
+    ((uint2*)o16)[k] = o;
 }
 struct DecBigLevel { uint32_t idx; int32_t val; };
 __global__ __launch_bounds__(256) void k_dec_patch(const DecBigLevel* big, int n, int16_t* lv16)
@@ -156,7 +188,8 @@ struct DecBsParams {
     int across;        // disable_deblocking_filter_idc 0: edges between slices are filtered too
     MbDiv mbdiv;
 };
-__global__ __launch_bounds__(64) void k_dec_bs(DecBsParams C, unsigned* anybs, unsigned serial)
+// item: whose anybs word is raised (the batch item, which for a decoder group is not the grid's y)
+__device__ __forceinline__ void dec_bs_pair(const DecBsParams& C, unsigned* anybs, unsigned serial, int item)
 {
     const int lane = threadIdx.x, l = lane & 31, mbi = 2 * (int)blockIdx.x + (lane >> 5);
     int bs = 0;
@@ -188,12 +221,37 @@ __global__ __launch_bounds__(64) void k_dec_bs(DecBsParams C, unsigned* anybs, u
         }
         C.bs[(size_t)mbi * 32 + l] = (uint8_t)bs;
     }
-    if (__ballot(bs != 0) != 0ull && lane == 0) anybs[blockIdx.y] = serial;
+    if (__ballot(bs != 0) != 0ull && lane == 0) anybs[item] = serial;
+}
+__global__ __launch_bounds__(64) void k_dec_bs(DecBsParams C, unsigned* anybs, unsigned serial)
+{
+    dec_bs_pair(C, anybs, serial, (int)blockIdx.y);
+}
+// decoder groups: the arrays lie [item] (C.nmb macroblocks each), `across` is the position's own; a position that is not filtered
+// leaves its anybs word alone, and the loop filter then passes its picture by
+__global__ __launch_bounds__(64) void k_dec_bs_pos(DecBsParams C, unsigned* anybs, unsigned serial, const DecPos* tab)
+{
+    const DecPosRef d = dec_pos(tab, blockIdx.y);
+    if (!d.filtered) return;
+    const size_t g = (size_t)d.item * C.nmb;
+    C.mb += g; C.mv4 += g * 32; C.refq += g * 4; C.bs += g * 32; C.mbavail += g;
+    C.across = d.across ? 1 : 0;
+    dec_bs_pair(C, anybs, serial, d.item);
 }
 
+// IND (decoder groups): blockIdx.y is a position of the step's table; a position without inter macroblocks is passed by
+template <bool IND = false>
 __global__ __launch_bounds__(64) void k_dec_resid(FrameParams P0)
 {
-    const FrameParams P = batch_view(P0, blockIdx.y);
+    DecPosRef dp{};
+    if constexpr (IND) {
+        dp = dec_pos(P0.dectab, blockIdx.y);
+        if (!dp.inter) return;
+    }
+    const FrameParams P = [&] {
+        if constexpr (IND) return dec_view(P0, dp);
+        else return batch_view(P0, blockIdx.y);
+    }();
     const int lane = threadIdx.x, blk = lane & 15;
     const int first = P.band.row0 * P.mbw, end = first + P.band.rows * P.mbw;
     const int mbi = first + 4 * (int)blockIdx.x + (lane >> 4);
@@ -275,5 +333,6 @@ __global__ __launch_bounds__(64) void k_dec_resid(FrameParams P0)
         }
     }
 }
+
 
 }  // namespace h264

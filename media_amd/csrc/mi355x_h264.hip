@@ -37,6 +37,7 @@ using namespace h264;
 #include "hub_sched.h"
 #include "hub.h"
 #include "decoder.h"
+#include "dec_group.h"
 
 extern "C" {
 
@@ -522,6 +523,122 @@ int mi355x_h264_dec_timing(const mi355x_h264_decoder* d, uint64_t* pictures, dou
     if (parse_ms) *parse_ms = d->parse_ms;
     if (gpu_ms) *gpu_ms = d->gpu_ms;
     return MI355X_H264_OK;
+}
+
+// ---- decoder groups (dec_group.h) ----
+
+int mi355x_h264_dec_group_create(int device, int streams, mi355x_h264_dec_group** out)
+{
+    if (!out) return MI355X_H264_E_ARG;
+    *out = nullptr;
+    if (streams < 1 || streams > DEC_GROUP_MAX_STREAMS) return MI355X_H264_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return MI355X_H264_E_NODEVICE;
+    mi355x_h264_dec_group* g = new (std::nothrow) mi355x_h264_dec_group();
+    if (!g) return MI355X_H264_E_NOMEM;
+    g->device = device; g->nstreams = streams;
+    g->st = new (std::nothrow) DecGroupStream[streams];
+    if (!g->st) { delete g; return MI355X_H264_E_NOMEM; }
+    if (hipSetDevice(device) != hipSuccess || hipEventCreateWithFlags(&g->up_done[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->up_done[1], hipEventDisableTiming) != hipSuccess) {
+        for (hipEvent_t ev : g->up_done) if (ev) (void)hipEventDestroy(ev);
+        delete[] g->st;
+        delete g;
+        return MI355X_H264_E_HIP;
+    }
+    // pictures the row wavefronts hold at a time; a step of more walks to the rest (k_pintra_rows, k_deblock_rows)
+    g->intra_slots = env_int("MI355X_H264_DEC_INTRA_SLOTS", 1, DEC_GROUP_MAX_STREAMS, 32);
+    g->filter_slots = env_int("MI355X_H264_DEC_FILTER_SLOTS", 1, DEC_GROUP_MAX_STREAMS, 32);
+    // the parse threads: a number of the group's own, never the machine's
+    g->sched.start(env_int("MI355X_H264_DEC_PARSE_THREADS", 1, DEC_GROUP_MAX_THREADS, std::min(streams, 8)));
+    *out = g;
+    return MI355X_H264_OK;
+}
+
+void mi355x_h264_dec_group_destroy(mi355x_h264_dec_group* g)
+{
+    if (!g) return;
+    g->sched.stop();
+    (void)hipSetDevice(g->device);
+    if (g->eng) { (void)dg_wait(g); (void)hipStreamSynchronize(g->eng->stream); }
+    for (int k = 0; k < 2; k++) {
+        if (g->up_done[k]) (void)hipEventDestroy(g->up_done[k]);
+        if (g->h_big[k]) (void)hipHostFree(g->h_big[k]);
+    }
+    if (g->d_big) (void)hipFree(g->d_big);
+    g->mem.free_all();
+    if (g->eng) destroy_engine(g->eng);
+    delete[] g->st;
+    delete g;
+}
+
+// No exception leaves the C entry point; a failure that concerns the whole group (device, allocation, a timed-out wavefront) may have
+// cost any stream a reference picture, so all of them then wait for their next IDR picture.
+int mi355x_h264_dec_group_decode(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* lens, int* got, int* rc)
+{
+    if (!g || !aus || !lens || !got || !rc) return MI355X_H264_E_ARG;
+    int r;
+    try {
+        r = dg_step(g, aus, lens, got, rc);
+    } catch (const std::exception& ex) {
+        r = set_err(g->err, MI355X_H264_E_NOMEM, "step refused: %s", ex.what());
+    }
+    if (r != MI355X_H264_OK)
+        for (int i = 0; i < g->nstreams; i++) {
+            if (aus[i]) { got[i] = 0; if (rc[i] == MI355X_H264_OK) rc[i] = r; dg_drop_refs(g->st[i]); }
+        }
+    return r;
+}
+
+int mi355x_h264_dec_group_sync(mi355x_h264_dec_group* g)
+{
+    if (!g) return MI355X_H264_E_ARG;
+    if (!g->eng) return MI355X_H264_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+    return dg_wait(g);
+}
+
+// stream -1: the group's own report (what made a call return < 0)
+const char* mi355x_h264_dec_group_last_error(const mi355x_h264_dec_group* g, int stream)
+{
+    if (!g) return "no decoder group";
+    if (stream == -1) return g->err;
+    if (stream < 0 || stream >= g->nstreams) return "no such stream";
+    return g->st[stream].err;
+}
+
+int mi355x_h264_dec_group_picture_info(const mi355x_h264_dec_group* g, int stream, int* w, int* h, int* cw, int* ch)
+{
+    if (!g || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0) return MI355X_H264_E_ARG;
+    if (w) *w = g->st[stream].width;
+    if (h) *h = g->st[stream].height;
+    if (cw) *cw = 16 * g->mbw;
+    if (ch) *ch = 16 * g->mbh;
+    return MI355X_H264_OK;
+}
+
+int64_t mi355x_h264_dec_group_read_i420(mi355x_h264_dec_group* g, int stream, uint8_t* dst, size_t cap) { return dg_read(g, stream, dst, cap, false); }
+int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group* g, int stream, void* d_dst, size_t cap) { return dg_read(g, stream, d_dst, cap, true); }
+
+int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group* g, int stream, int plane, void* dst, size_t cap)
+{
+    if (!g || !dst || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0 || plane < 0 || plane > 2) return MI355X_H264_E_ARG;
+    const mi355x_h264_encoder* e = g->eng;
+    const size_t n = (size_t)e->cw * e->ch / (plane ? 4 : 1);
+    if (cap < n) return MI355X_H264_E_ARG;
+    if (hipSetDevice(g->device) != hipSuccess) return MI355X_H264_E_HIP;
+    if (const int wrc = dg_wait(g)) return wrc;
+    const uint8_t* src = e->d_plane_base[plane] + (size_t)stream * (plane ? e->st_c : e->st_y) + (size_t)g->st[stream].last * (plane ? e->st_ring_c : e->st_ring_y);
+    if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return MI355X_H264_E_HIP;
+    return (int64_t)n;
+}
+
+int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group* g, int64_t* out, int n)
+{
+    if (!g || !out || n < 1) return MI355X_H264_E_ARG;
+    const int m = std::min(n, 7);
+    for (int i = 0; i < m; i++) out[i] = g->last[i];
+    return m;
 }
 
 // ---- the host parser alone (no GPU): what it recovered from the last access unit, for the CPU tests ----

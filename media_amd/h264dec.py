@@ -1,5 +1,5 @@
 """ctypes binding of the decoder peer's C ABI (include/mi355x_h264_dec.h): `Decoder` (GPU reconstruction; fails loudly without
-a device) and `Parser` (the host-side CAVLC / header parser alone, usable without a GPU: the CPU tests compare what it
+a device), `DecoderGroup` (the next pictures of up to 64 streams of one coded size decoded in one step) and `Parser` (the host-side CAVLC / header parser alone, usable without a GPU: the CPU tests compare what it
 recovers from a stream with the side information of the encoder that wrote it)."""
 import ctypes as C
 import numpy as np
@@ -31,6 +31,16 @@ def _bind():
     L.mi355x_h264_parser_error.argtypes = [vp]; L.mi355x_h264_parser_error.restype = C.c_char_p
     L.mi355x_h264_parser_info.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
     L.mi355x_h264_parser_read.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_parser_read.restype = C.c_int64
+    L.mi355x_h264_dec_group_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
+    L.mi355x_h264_dec_group_destroy.argtypes = [vp]; L.mi355x_h264_dec_group_destroy.restype = None
+    L.mi355x_h264_dec_group_decode.argtypes = [vp, vp, vp, ip, ip]
+    L.mi355x_h264_dec_group_sync.argtypes = [vp]
+    L.mi355x_h264_dec_group_last_error.argtypes = [vp, C.c_int]; L.mi355x_h264_dec_group_last_error.restype = C.c_char_p
+    L.mi355x_h264_dec_group_picture_info.argtypes = [vp, C.c_int, ip, ip, ip, ip]
+    L.mi355x_h264_dec_group_read_i420.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_dec_group_read_i420.restype = C.c_int64
+    L.mi355x_h264_dec_group_read_i420_device.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_dec_group_read_i420_device.restype = C.c_int64
+    L.mi355x_h264_dec_group_debug_plane.argtypes = [vp, C.c_int, C.c_int, vp, sz]; L.mi355x_h264_dec_group_debug_plane.restype = C.c_int64
+    L.mi355x_h264_dec_group_last_step.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     _bound = True
     return L
 
@@ -104,6 +114,91 @@ class Decoder:
         n, a, b = C.c_uint64(0), C.c_double(0), C.c_double(0)
         lib().mi355x_h264_dec_timing(self.h, C.byref(n), C.byref(a), C.byref(b))
         return n.value, a.value, b.value
+
+
+class DecoderGroup:
+    """`streams` decoders behind one engine: decode() takes the next access unit of every stream (None: the stream sits this step
+    out) and reconstructs all their pictures in one set of transfers and launches"""
+    STEP = ("serial", "pictures", "launches", "transfers", "parse_threads", "parse_us", "launch_us")
+
+    def __init__(self, streams, device=0):
+        L = _bind()
+        self.h = C.c_void_p()
+        self.streams = streams
+        rc = L.mi355x_h264_dec_group_create(device, streams, C.byref(self.h))
+        if rc != 0:
+            raise EncoderError("mi355x_h264_dec_group_create(%d streams) -> %d" % (streams, rc))
+
+    def close(self):
+        if self.h:
+            lib().mi355x_h264_dec_group_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def error(self, stream=-1):
+        return lib().mi355x_h264_dec_group_last_error(self.h, stream).decode()
+
+    def decode(self, aus):
+        """aus: one entry per stream, bytes or None.  Returns [(rc, got)] per stream; raises when the step failed as a whole"""
+        if len(aus) != self.streams:
+            raise EncoderError("decode() takes %d access units (None for a stream that sits out), got %d" % (self.streams, len(aus)))
+        n = self.streams
+        keep = [None if a is None else (C.c_uint8 * max(1, len(a))).from_buffer_copy(a if len(a) else b"\0") for a in aus]
+        ptrs = (C.c_void_p * n)(*[None if b is None else C.addressof(b) for b in keep])
+        lens = (C.c_size_t * n)(*[0 if a is None else len(a) for a in aus])
+        got, rc = (C.c_int * n)(), (C.c_int * n)()
+        r = lib().mi355x_h264_dec_group_decode(self.h, ptrs, lens, got, rc)
+        if r != 0:
+            raise EncoderError("group decode -> %d: %s" % (r, self.error()))
+        return [(rc[i], got[i]) for i in range(n)]
+
+    def sync(self):
+        rc = lib().mi355x_h264_dec_group_sync(self.h)
+        if rc != 0:
+            raise EncoderError("group sync -> %d: %s" % (rc, self.error()))
+
+    def info(self, stream):
+        v = [C.c_int(0) for _ in range(4)]
+        if lib().mi355x_h264_dec_group_picture_info(self.h, stream, *[C.byref(x) for x in v]) != 0:
+            raise EncoderError("stream %d has decoded no picture yet" % stream)
+        return tuple(x.value for x in v)   # width, height, coded width, coded height
+
+    def read_i420(self, stream):
+        w, h, _, _ = self.info(stream)
+        a = np.empty(w * h * 3 // 2, np.uint8)
+        n = lib().mi355x_h264_dec_group_read_i420(self.h, stream, a.ctypes.data, a.nbytes)
+        if n != a.nbytes:
+            raise EncoderError("group read_i420 -> %d" % n)
+        return a
+
+    def read_i420_device(self, stream, tensor):
+        """into a torch uint8 tensor in device memory; returns the bytes written"""
+        n = lib().mi355x_h264_dec_group_read_i420_device(self.h, stream, tensor.data_ptr(), tensor.numel() * tensor.element_size())
+        if n < 0:
+            raise EncoderError("group read_i420_device -> %d" % n)
+        return n
+
+    def debug_planes(self, stream):
+        """the three coded-size planes of the stream's last picture"""
+        _, _, cw, ch = self.info(stream)
+        out = []
+        for p in range(3):
+            a = np.empty((ch // (2 if p else 1), cw // (2 if p else 1)), np.uint8)
+            n = lib().mi355x_h264_dec_group_debug_plane(self.h, stream, p, a.ctypes.data, a.nbytes)
+            if n != a.nbytes:
+                raise EncoderError("group debug_plane -> %d" % n)
+            out.append(a)
+        return out
+
+    def last_step(self):
+        v = (C.c_int64 * 7)()
+        n = lib().mi355x_h264_dec_group_last_step(self.h, v, 7)
+        return dict(zip(self.STEP[:n], list(v)[:n]))
 
 
 class Parser:

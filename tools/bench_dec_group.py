@@ -1,0 +1,101 @@
+"""Aggregate decode throughput of S 1080p streams: one DecoderGroup against S Decoder objects on S host threads.
+The content is what `bench.py --mode decode` decodes (S1, QP 26, GOP 30, written by the HIP encoder); every stream gets the same
+access units.  Both forms run interleaved, --repeat times each, in one process; with and without reading every picture back.
+Prints one JSON line per (S, form, read) with median and min / max fps, and for the group the host's parse / launch time per
+picture (mi355x_h264_dec_group_last_step).  Kernel times: run it once under `rocprofv3 --kernel-trace --stats -- python
+tools/bench_dec_group.py --streams 16 --repeat 1`.
+
+    python tools/bench_dec_group.py [--streams 1,4,16,32] [--pictures 60] [--repeat 3]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import threading
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+WIDTH, HEIGHT, QP, GOP = 1920, 1080, 26, 30
+
+
+def make_stream(n):
+    from media_amd import capi, synth
+    enc = capi.Encoder(WIDTH, HEIGHT, qp=QP, gop=GOP)
+    aus = [enc.encode(f)[0] for f in synth.sequence("s1", WIDTH, HEIGHT, n)]
+    enc.close()
+    return aus
+
+
+def run_group(aus, S, read):
+    from media_amd import h264dec
+    g = h264dec.DecoderGroup(S)
+    parse_us = launch_us = 0
+    t0 = time.perf_counter()
+    for au in aus:
+        res = g.decode([au] * S)
+        assert all(r == (0, 1) for r in res), res
+        st = g.last_step()
+        parse_us += st["parse_us"]; launch_us += st["launch_us"]
+        if read:
+            for k in range(S):
+                g.read_i420(k)
+    g.sync()
+    dt = time.perf_counter() - t0
+    g.close()
+    n = len(aus) * S
+    return n / dt, {"parse_ms_per_picture": parse_us / 1e3 / n, "launch_ms_per_picture": launch_us / 1e3 / n}
+
+
+def run_objects(aus, S, read):
+    from media_amd import h264dec
+    decs = [h264dec.Decoder() for _ in range(S)]
+    start = threading.Barrier(S + 1)
+
+    def work(d):
+        start.wait()
+        for au in aus:
+            assert d.decode(au)
+            if read:
+                d.i420()
+        d.sync()
+
+    th = [threading.Thread(target=work, args=(d,)) for d in decs]
+    for t in th:
+        t.start()
+    start.wait()
+    t0 = time.perf_counter()
+    for t in th:
+        t.join()
+    dt = time.perf_counter() - t0
+    out = {}
+    n, p, g = zip(*[d.timing() for d in decs])
+    out["parse_ms_per_picture"] = sum(p) / sum(n)
+    out["gpu_ms_per_picture"] = sum(g) / sum(n)
+    for d in decs:
+        d.close()
+    return len(aus) * S / dt, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", default="1,4,16,32")
+    ap.add_argument("--pictures", type=int, default=60)
+    ap.add_argument("--repeat", type=int, default=3)
+    a = ap.parse_args()
+    aus = make_stream(a.pictures)
+    for S in [int(x) for x in a.streams.split(",")]:
+        for read in (False, True):
+            runs = {"group": [], "objects": []}
+            extra = {}
+            for _ in range(a.repeat):
+                for form, fn in (("group", run_group), ("objects", run_objects)):
+                    fps, extra[form] = fn(aus, S, read)
+                    runs[form].append(fps)
+            for form in ("group", "objects"):
+                v = runs[form]
+                print(json.dumps(dict({"streams": S, "form": form, "read_back": read, "pictures_per_stream": a.pictures, "fps_median": round(statistics.median(v), 1),
+                                       "fps_min": round(min(v), 1), "fps_max": round(max(v), 1), "runs": [round(x, 1) for x in v]}, **extra[form])), flush=True)
+
+
+if __name__ == "__main__":
+    main()
