@@ -56,6 +56,34 @@ int mi355x_h264_dec_picture_info(const mi355x_h264_decoder *dec, int *width, int
 int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder *dec, uint8_t *dst, size_t cap);
 int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder *dec, void *d_dst, size_t cap);
 
+/* ---- output layouts: the last picture gathered out of the reconstruction ring by ONE kernel (media_amd/csrc/k_dec_out.h) ----
+ * Layouts: I420 = Y, U, V planes; NV12 = Y plane, then rows of U, V pairs; NV21 = Y plane, then rows of V, U pairs; RGBA = R, G, B, A
+ * bytes, A = 255 (VideoDecoder.h names them PIXEL_FORMAT_YUV_420P, _NV12, _NV21, _RGBA_8888).  RGBA is this build's own definition,
+ * integer BT.601 studio swing: c = 298 * (Y - 16), d = U - 128, e = V - 128, R = clip255((c + 409 * e + 128) >> 8),
+ * G = clip255((c - 100 * d - 208 * e + 128) >> 8), B = clip255((c + 516 * d + 128) >> 8), the shift arithmetic; the chroma sample
+ * of a 2x2 block serves its four pixels.
+ * The destination is packed: pictures in stream order, each at an offset rounded up to 256 bytes.  row_align is a power of two
+ * 1..256: a luma row, an NV12 / NV21 chroma row and an RGBA row have stride align_up(row bytes, row_align), an I420 chroma row
+ * align_up(width / 2, row_align); plane heights are tight; a picture ends with its last row's stride.  Into device memory no byte
+ * between a row's end and the next row's start is ever written; into host memory those bytes are unspecified. */
+#define MI355X_H264_PIX_I420 0
+#define MI355X_H264_PIX_NV12 1
+#define MI355X_H264_PIX_NV21 2
+#define MI355X_H264_PIX_RGBA 3
+typedef struct {
+    int64_t offset;                /* of the picture inside the output; -1: the stream has no picture in this output */
+    int32_t width, height;         /* cropped size */
+    int32_t stride, chroma_stride; /* bytes per row (chroma_stride: I420 U / V rows, NV12 / NV21 pair rows; 0 for RGBA) */
+    int32_t fresh;                 /* 1: decoded in the step the output belongs to */
+    int32_t reserved;
+    int64_t serial;                /* that step's serial number (mi355x_h264_dec_group_last_step out[0]; single decoder: pictures decoded) */
+} mi355x_h264_dec_out_pic;
+/* the last decoded picture in `layout`.  dst == NULL: fills *pic and returns the bytes needed without touching the GPU.  to_device:
+ * dst is device memory aligned to 16 bytes, written by a kernel on the decoder's own stream, which waits for no other stream: the
+ * caller's work on dst must be complete; the call returns when the picture is there.  Returns the bytes used or < 0 (E_ARG: layout, row_align, cap too small, no picture yet) */
+int64_t mi355x_h264_dec_read(mi355x_h264_decoder *dec, int layout, int row_align, void *dst, size_t cap, int to_device,
+                             mi355x_h264_dec_out_pic *pic);
+
 /* ---- decoder groups: the next pictures of up to 64 streams reconstructed in ONE step ----
  * One decoder object per stream costs each picture its own uploads and five to eight launches that fill a fraction of the GPU.  A
  * group decodes the streams' next access units together: they are parsed side by side on a small pool of threads the group owns
@@ -84,8 +112,31 @@ int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group *g, int str
 int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group *g, int stream, int plane, void *dst, size_t cap);
 /* what the last step was: out[0] its serial number, out[1] pictures it carried, out[2] kernel launches it made, out[3] host-to-device
  * transfers it made, out[4] parse threads used; with n >= 7 also out[5] / out[6]: microseconds the host spent parsing / launching
- * (and, with MI355X_H264_DEC_SYNC, waiting).  Returns the number of values written */
+ * (and, with MI355X_H264_DEC_SYNC, waiting); with n >= 9 also out[7] / out[8]: output launches / device-to-host output transfers the
+ * step made (set_output below; 0 / 0 for an unarmed group); with n >= 11 also out[9] / out[10]: launches / transfers of the last
+ * read_all call.  Returns the number of values written */
 int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group *g, int64_t *out, int n);
+
+/* every stream's last decoded picture in ONE call (layouts and packing: above): what read_i420 gives per stream, for all streams
+ * that have a picture, in stream order.  pics[streams] is filled: offset -1 for a stream without a picture; fresh = 1 for a stream
+ * that decoded in the last step, 0 for one that sat it out or was refused; serial = the last step's.  dst == NULL: sizes only
+ * (fills pics, returns the bytes needed, does not touch the GPU).  Waits for the step in flight, then makes one launch - straight into
+ * dst when to_device (device memory aligned to 16 bytes; no transfer), else into a device staging buffer followed by ONE
+ * device-to-host copy through a pinned buffer and a host copy to dst - whatever the number of streams.  The position table lies in
+ * pinned memory that the kernel reads in place.  Returns the bytes used or < 0 (E_ARG: layout, row_align, cap too small, no stream
+ * has a picture) */
+int64_t mi355x_h264_dec_group_read_all(mi355x_h264_dec_group *g, int layout, int row_align, void *dst, size_t cap, int to_device,
+                                       mi355x_h264_dec_out_pic *pics /* [streams] */);
+/* arm the group (layout -1: disarm): from the next step on every step that carries pictures is followed, on the engine's stream
+ * behind the loop filter, by one gather launch for exactly the step's positions and one asynchronous device-to-host copy into one
+ * of two pinned output sets, with an event of its own.  The sets take turns.  The step's table of output positions travels behind
+ * its position table in the same transfer: out[2] / out[3] of last_step count what they count for an unarmed group. */
+int mi355x_h264_dec_group_set_output(mi355x_h264_dec_group *g, int layout, int row_align);
+/* the output of an armed step.  back = 0: of the last step that carried pictures - waits for that step's event and reports a
+ * wavefront time-out of the step as sync does; back = 1: of the one before it, which is complete: never waits on the GPU.  *data
+ * points into the pinned set and stays valid until the second decode call after the step; pics[streams]: offset -1 for the streams
+ * that took no part in that step.  E_ARG: unarmed, or fewer than back + 1 armed steps so far */
+int mi355x_h264_dec_group_output(mi355x_h264_dec_group *g, int back, const uint8_t **data, mi355x_h264_dec_out_pic *pics);
 
 /* ---- test / measurement hooks ---- */
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 */

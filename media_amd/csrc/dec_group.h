@@ -20,6 +20,7 @@ struct DecGroupStream {
     int last = -1;       // ring slot of its last decoded picture
     int width = 0, height = 0, crop_x = 0, crop_y = 0;
     uint64_t pictures = 0;
+    int64_t last_serial = 0;   // serial number of the step that decoded its last picture
     // the step in hand
     const uint8_t* au = nullptr;
     size_t len = 0;
@@ -54,7 +55,22 @@ struct mi355x_h264_dec_group {
     int flight[DEC_GROUP_MAX_STREAMS];   // its streams
     int nflight = 0;
     int intra_slots = 32, filter_slots = 32;   // pictures the row wavefronts hold at a time (the rest are walked to)
-    int64_t step_serial = 0, last[7] = {0, 0, 0, 0, 0, 0, 0};
+    int64_t step_serial = 0, last[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // output (k_dec_out.h).  rd: read_all's table and staging; its device staging buffer also serves the armed steps (everything
+    // is ordered on the engine's stream).  Armed: the step's table of output positions lies behind its DecPos rows in tables of
+    // their own (h_tabx / d_tabx: DecPos [streams], then DecOutPos [streams]), so that one transfer carries both.
+    struct Out {
+        DecOutBuf rd;
+        bool armed = false, ready = false;
+        int layout = 0, row_align = 1;
+        uint8_t* h_tabx[2] = {nullptr, nullptr};
+        uint8_t* d_tabx = nullptr;
+        uint8_t* h_set[2] = {nullptr, nullptr};   // the two pinned output sets
+        size_t set_cap = 0;
+        hipEvent_t done[2] = {nullptr, nullptr};  // the copy into the set has finished
+        mi355x_h264_dec_out_pic pics[2][DEC_GROUP_MAX_STREAMS];
+        int cur = 0, count = 0;                   // the set of the last armed step; armed steps so far (0, 1, 2 = two or more)
+    } out;
     char err[256] = {0};
 };
 
@@ -90,6 +106,35 @@ void dg_free_geometry(mi355x_h264_dec_group* g)
     }
     for (auto& p : g->d_arr) p = nullptr;
     g->d_tab = nullptr;
+    hipEvent_t ev[2] = {g->out.done[0], g->out.done[1]};
+    const bool armed = g->out.armed;
+    const int layout = g->out.layout, row_align = g->out.row_align;
+    g->out = mi355x_h264_dec_group::Out();   // (its buffers were the geometry's: they come again with the next one)
+    g->out.done[0] = ev[0]; g->out.done[1] = ev[1]; g->out.armed = armed; g->out.layout = layout; g->out.row_align = row_align;
+}
+
+// the buffers of an armed group, for the geometry at hand and the layout armed: sized for every stream's picture at the coded size
+int dg_out_prepare(mi355x_h264_dec_group* g)
+{
+    mi355x_h264_dec_group::Out& o = g->out;
+    const size_t S = (size_t)g->nstreams;
+    const size_t need = S * out_align(out_geom(o.layout, 16 * g->mbw, 16 * g->mbh, o.row_align).bytes, 256);
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++) {
+        if (!o.done[k]) ok = hipEventCreateWithFlags(&o.done[k], hipEventDisableTiming) == hipSuccess;
+        if (ok && !o.h_tabx[k]) ok = g->mem.pinned(&o.h_tabx[k], S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
+    }
+    if (ok && !o.d_tabx) ok = g->mem.dev(&o.d_tabx, S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
+    if (ok && need > o.set_cap) {
+        for (int k = 0; k < 2; k++) { if (o.h_set[k]) g->mem.drop(o.h_set[k]); o.h_set[k] = nullptr; }
+        o.set_cap = 0;
+        for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&o.h_set[k], need) == hipSuccess;
+        if (ok) o.set_cap = need;
+    }
+    ok = ok && out_reserve(g->mem, o.rd, need, 0) == hipSuccess;
+    if (!ok) return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the output sets of %d streams", g->nstreams);
+    o.ready = true;
+    return MI355X_H264_OK;
 }
 
 // engine and arrays for the group's geometry (that of the first IDR picture it meets)
@@ -181,7 +226,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     const double t1 = now_ms();
     g->step_serial++;
     g->last[0] = g->step_serial; g->last[1] = g->last[2] = g->last[3] = 0; g->last[4] = g->sched.last_threads;
-    g->last[5] = (int64_t)((t1 - t0) * 1e3); g->last[6] = 0;
+    g->last[5] = (int64_t)((t1 - t0) * 1e3); g->last[6] = 0; g->last[7] = g->last[8] = 0;
     // the step in flight must be out of the way before this one is launched; its time-out flag is looked at here
     if (const int wrc = dg_wait(g)) {
         for (int j = 0; j < njobs; j++) { dg_drop_refs(g->st[jobs[j]]); rc[jobs[j]] = wrc; snprintf(g->st[jobs[j]].err, sizeof(g->st[jobs[j]].err), "%s", g->err); }
@@ -190,6 +235,10 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     // which of the parsed pictures this step takes, and the table row of each
     int pos_stream[DEC_GROUP_MAX_STREAMS], npos = 0;
     DecPos* tab = nullptr;
+    DecOutPos* otab = nullptr;          // armed: the output positions, behind the DecPos rows
+    const bool outp = g->out.armed;
+    const int oset = g->out.count ? g->out.cur ^ 1 : 0;
+    size_t obytes = 0;
     bool any_inter = false, any_intra = false, any_plain = false, any_bs4 = false;
     size_t nbig = 0;
     for (int j = 0; j < njobs; j++) {
@@ -205,6 +254,12 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             if (const int crc = dg_create_geometry(g, pic.mbw, pic.mbh)) {
                 for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
                 return crc;
+            }
+        }
+        if (outp && !g->out.ready) {   // (nothing is in flight: dg_wait above)
+            if (const int orc = dg_out_prepare(g)) {
+                for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
+                return orc;
             }
         }
         if (pic.mbw != g->mbw || pic.mbh != g->mbh) {
@@ -227,7 +282,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         s.width = pic.width; s.height = pic.height; s.crop_x = 2 * sps.crop_l; s.crop_y = 2 * sps.crop_t;
         s.max_refs = std::max(1, sps.max_refs);
         // the table row (dev_common.h DecPos)
-        tab = g->h_tab[k];
+        tab = outp ? (DecPos*)g->out.h_tabx[k] : g->h_tab[k];
         DecPos& T = tab[npos];
         memset(&T, 0, sizeof(T));
         const bool filtered = pic.deblock_idc != 1;
@@ -251,6 +306,16 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         any_inter |= pic.has_inter; any_intra |= pic.has_intra;
         if (filtered) { if (pic.has_intra) any_bs4 = true; else any_plain = true; }
         nbig += pic.big.size();
+        if (outp) {
+            if (npos == 0) for (int x = 0; x < S; x++) g->out.pics[oset][x] = out_no_pic(g->step_serial);
+            otab = (DecOutPos*)(g->out.h_tabx[k] + (size_t)S * sizeof(DecPos));
+            const OutGeom geo = out_geom(g->out.layout, s.width, s.height, g->out.row_align);
+            const size_t off = out_align(obytes, 256);
+            otab[npos] = DecOutPos{(uint32_t)i, (uint32_t)s.cur, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
+                                   (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, 0ull};
+            g->out.pics[oset][i] = out_pic((int64_t)off, s.width, s.height, geo, 1, g->step_serial);
+            obytes = off + geo.bytes;
+        }
         pos_stream[npos++] = i;
     }
     if (npos == 0) return MI355X_H264_OK;
@@ -268,7 +333,10 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         HIPCHK(g->err, hipMemcpyAsync(g->d_arr[a] + off, g->h_arr[k][a] + off, bytes, hipMemcpyHostToDevice, st));
         transfers++;
     }
-    HIPCHK(g->err, hipMemcpyAsync(g->d_tab, tab, (size_t)npos * sizeof(DecPos), hipMemcpyHostToDevice, st));
+    // (armed: the output positions lie behind the DecPos rows and travel with them)
+    const DecPos* const d_tab = outp ? (const DecPos*)g->out.d_tabx : g->d_tab;
+    const size_t tab_bytes = outp ? (size_t)S * sizeof(DecPos) + (size_t)npos * sizeof(DecOutPos) : (size_t)npos * sizeof(DecPos);
+    HIPCHK(g->err, hipMemcpyAsync((void*)d_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
     transfers++;
     if (nbig) {   // the streams' large levels as one list, the indices counted from item 0
         static_assert(sizeof(h264dec::Picture::Big) == sizeof(DecBigLevel), "layout of the list of large levels");
@@ -304,7 +372,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     {
         const int words = (int)(nmb * (LV_STRIDE / 4));
         hipLaunchKernelGGL(k_dec_widen_pos, dim3((words + 255) / 256, NP), dim3(256), 0, st, (const uint32_t*)g->d_arr[DG_LV8], (const MbInfo*)e->d_mb, e->d_levels, (int)nmb,
-                           (const DecPos*)g->d_tab);
+                           d_tab);
         launches++;
         if (nbig) { hipLaunchKernelGGL(k_dec_patch, dim3(((int)nbig + 255) / 256), dim3(256), 0, st, (const DecBigLevel*)g->d_big, (int)nbig, e->d_levels); launches++; }
     }
@@ -316,7 +384,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     P.sl.rows = e->mbh; P.sl.inv = recip32(e->mbh);
     P.band.row0 = 0; P.band.rows = e->mbh;
     P.mbqp = g->d_arr[DG_QP]; P.mv4 = (const int16_t*)g->d_arr[DG_MV4]; P.refq = g->d_arr[DG_REFQ]; P.mbavail = g->d_arr[DG_AVAIL];
-    P.dectab = g->d_tab;
+    P.dectab = d_tab;
     unsigned* const h_err = e->slots[0].sync.h_err;
     if (any_inter) {
         hipLaunchKernelGGL(k_dec_inter_pos, dim3(e->nmb, NP), wave, 0, st, P);
@@ -333,19 +401,28 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         DecBsParams B{};
         B.mb = e->d_mb; B.mv4 = (const int16_t*)g->d_arr[DG_MV4]; B.refq = g->d_arr[DG_REFQ]; B.bs = (uint8_t*)e->d_bs; B.mbw = e->mbw; B.nmb = e->nmb; B.mbdiv = P.mbdiv;
         B.mbavail = g->d_arr[DG_AVAIL];
-        hipLaunchKernelGGL(k_dec_bs_pos, dim3((e->nmb + 1) / 2, NP), wave, 0, st, B, e->d_anybs, db_serial, (const DecPos*)g->d_tab);
+        hipLaunchKernelGGL(k_dec_bs_pos, dim3((e->nmb + 1) / 2, NP), wave, 0, st, B, e->d_anybs, db_serial, d_tab);
         launches++;
         // always the per-edge thresholds; the form with the bS 4 filter for the positions with intra macroblocks, the one without
         // for the others (the pair of launches of the encoder's P steps, chosen by the table's flags)
         DbParams D = db_params(e, e->d_plane_base, P.sl, 26);
         D.mbqp = g->d_arr[DG_QP];
         DbRowParams R = db_row_params(e, D, h_err, db_serial, P.pic_serial, 0, npos);
-        R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c; R.dectab = g->d_tab;
+        R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c; R.dectab = d_tab;
         const dim3 grid(e->mbh, std::min(NP, (unsigned)g->filter_slots));
         if (any_plain) { R.need_intra = -1; hipLaunchKernelGGL((k_deblock_rows<false, true, true>), grid, wave, 0, st, R); launches++; }
         if (any_bs4) { R.need_intra = 1; hipLaunchKernelGGL((k_deblock_rows<true, true, true>), grid, wave, 0, st, R); launches++; }
     }
     HIPCHK(g->err, hipGetLastError());
+    if (outp) {
+        // behind the loop filter, and ahead of the next step on this stream, which may write the very ring slot (a non-reference
+        // picture leaves `cur` where it was): the step's pictures into the staging buffer, and that into the pinned set
+        HIPCHK(g->err, launch_dec_out(e, g->out.layout, otab, (const DecOutPos*)(g->out.d_tabx + (size_t)S * sizeof(DecPos)), npos, g->out.rd.d_stage, st));
+        HIPCHK(g->err, hipMemcpyAsync(g->out.h_set[oset], g->out.rd.d_stage, obytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(g->err, hipEventRecord(g->out.done[oset], st));
+        g->out.cur = oset; g->out.count = std::min(2, g->out.count + 1);
+        g->last[7] = 1; g->last[8] = 1;
+    }
     g->busy = true;
     g->nflight = npos;
     for (int p = 0; p < npos; p++) g->flight[p] = pos_stream[p];
@@ -354,6 +431,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         DecGroupStream& s = g->st[i];
         const bool is_ref = s.parser.picture().is_ref;
         s.last = s.cur;
+        s.last_serial = g->step_serial;
         s.parser.commit();
         if (is_ref) {   // sliding window (8.2.5.3)
             s.cur = (s.cur + 1) % e->nbuf;
@@ -390,6 +468,74 @@ int64_t dg_read(mi355x_h264_dec_group* g, int stream, void* dst, size_t cap, boo
         o += pw * ph;
     }
     return (int64_t)need;
+}
+
+// every stream's last picture in one launch (and, to the host, one transfer)
+int64_t dg_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* dst, size_t cap, bool to_device, mi355x_h264_dec_out_pic* pics)
+{
+    if (!g || !pics || !out_args_ok(layout, row_align)) return MI355X_H264_E_ARG;
+    DecOutPos rows[DEC_GROUP_MAX_STREAMS];
+    mi355x_h264_dec_out_pic desc[DEC_GROUP_MAX_STREAMS];
+    int n = 0;
+    size_t total = 0;
+    for (int i = 0; i < g->nstreams; i++) {
+        const DecGroupStream& s = g->st[i];
+        desc[i] = out_no_pic(g->step_serial);
+        if (s.last < 0) continue;
+        const OutGeom geo = out_geom(layout, s.width, s.height, row_align);
+        const size_t off = out_align(total, 256);
+        rows[n++] = DecOutPos{(uint32_t)i, (uint32_t)s.last, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
+                              (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, 0ull};
+        desc[i] = out_pic((int64_t)off, s.width, s.height, geo, s.last_serial == g->step_serial, g->step_serial);
+        total = off + geo.bytes;
+    }
+    if (n == 0) return MI355X_H264_E_ARG;
+    if (dst && (cap < total || (to_device && ((uintptr_t)dst & 15)))) return MI355X_H264_E_ARG;
+    memcpy(pics, desc, (size_t)g->nstreams * sizeof(desc[0]));
+    if (!dst) return (int64_t)total;
+    if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+    if (const int wrc = dg_wait(g)) return wrc;   // the pictures asked for may still be in flight
+    const mi355x_h264_encoder* e = g->eng;
+    HIPCHK(g->err, hipStreamSynchronize(e->stream));   // (an armed step's copy out of the staging buffer; nothing else is queued)
+    DecOutBuf& b = g->out.rd;
+    if (out_reserve(g->mem, b, to_device ? 0 : total, to_device ? 0 : total) != hipSuccess)
+        return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the output staging (%s)", t_failed_call);
+    memcpy(b.h_tab, rows, (size_t)n * sizeof(DecOutPos));
+    g->last[9] = g->last[10] = 0;
+    HIPCHK(g->err, launch_dec_out(e, layout, rows, b.d_tab, n, to_device ? (uint8_t*)dst : b.d_stage, e->stream));
+    g->last[9] = 1;
+    if (!to_device) { HIPCHK(g->err, hipMemcpyAsync(b.h_stage, b.d_stage, total, hipMemcpyDeviceToHost, e->stream)); g->last[10] = 1; }
+    HIPCHK(g->err, hipStreamSynchronize(e->stream));
+    if (!to_device) memcpy(dst, b.h_stage, total);
+    return (int64_t)total;
+}
+
+int dg_set_output(mi355x_h264_dec_group* g, int layout, int row_align)
+{
+    if (!g) return MI355X_H264_E_ARG;
+    if (layout == -1) { g->out.armed = false; g->out.count = 0; g->last[7] = g->last[8] = 0; return MI355X_H264_OK; }
+    if (!out_args_ok(layout, row_align)) return MI355X_H264_E_ARG;
+    if (g->eng) {   // the sets may be made anew for this layout by the next step: nothing may be on its way into them
+        if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+        if (const int wrc = dg_wait(g)) return wrc;
+        HIPCHK(g->err, hipStreamSynchronize(g->eng->stream));
+    }
+    g->out.armed = true; g->out.ready = false; g->out.layout = layout; g->out.row_align = row_align; g->out.count = 0;
+    return MI355X_H264_OK;
+}
+
+int dg_output(mi355x_h264_dec_group* g, int back, const uint8_t** data, mi355x_h264_dec_out_pic* pics)
+{
+    if (!g || !data || !pics || back < 0 || back > 1 || !g->out.armed || g->out.count <= back) return MI355X_H264_E_ARG;
+    const int o = back ? g->out.cur ^ 1 : g->out.cur;
+    if (back == 0) {   // (the step before it was waited for when the last one was launched)
+        if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
+        HIPCHK(g->err, hipEventSynchronize(g->out.done[o]));
+        if (const int wrc = dg_wait(g)) return wrc;
+    }
+    *data = g->out.h_set[o];
+    memcpy(pics, g->out.pics[o], (size_t)g->nstreams * sizeof(pics[0]));
+    return MI355X_H264_OK;
 }
 
 }  // namespace

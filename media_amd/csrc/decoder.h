@@ -3,6 +3,85 @@
 // per-macroblock arrays, hand-off granules, streams): decoding is the encoder's reconstruction path run from parsed decisions.
 #pragma once
 
+namespace {
+
+// ---- output in a layout (k_dec_out.h; include/mi355x_h264_dec.h states the packing) ----
+struct OutGeom { int stride, cstride; size_t bytes; };
+bool out_args_ok(int layout, int row_align) { return layout >= 0 && layout <= 3 && row_align >= 1 && row_align <= 256 && (row_align & (row_align - 1)) == 0; }
+size_t out_align(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+OutGeom out_geom(int layout, int w, int h, int row_align)
+{
+    const size_t a = (size_t)row_align;
+    OutGeom g{};
+    if (layout == DEC_OUT_RGBA) { g.stride = (int)out_align(4 * (size_t)w, a); g.bytes = (size_t)g.stride * h; }
+    else if (layout == DEC_OUT_I420) { g.stride = (int)out_align(w, a); g.cstride = (int)out_align(w / 2, a); g.bytes = (size_t)g.stride * h + 2 * (size_t)g.cstride * (h / 2); }
+    else { g.stride = g.cstride = (int)out_align(w, a); g.bytes = (size_t)g.stride * h + (size_t)g.cstride * (h / 2); }
+    return g;
+}
+mi355x_h264_dec_out_pic out_pic(int64_t off, int w, int h, const OutGeom& g, int fresh, int64_t serial)
+{
+    mi355x_h264_dec_out_pic p{};
+    p.offset = off; p.width = w; p.height = h; p.stride = g.stride; p.chroma_stride = g.cstride; p.fresh = fresh; p.serial = serial;
+    return p;
+}
+mi355x_h264_dec_out_pic out_no_pic(int64_t serial) { mi355x_h264_dec_out_pic p{}; p.offset = -1; p.serial = serial; return p; }
+
+// what the read calls of a decoder or a group own, made with the first call that needs it: the position table in pinned memory
+// (the kernel reads it in place: a read call makes no transfer for it) and the staging pair of the host form
+struct DecOutBuf {
+    DecOutPos* h_tab = nullptr;   // [DEC_GROUP_MAX_STREAMS]
+    const DecOutPos* d_tab = nullptr;   // the same memory as the device addresses it
+    uint8_t* d_stage = nullptr; size_t d_cap = 0;
+    uint8_t* h_stage = nullptr; size_t h_cap = 0;
+};
+// nothing on the GPU may be using the buffers (the callers have waited for their stream)
+hipError_t out_reserve(DevMem& mem, DecOutBuf& b, size_t dev_bytes, size_t host_bytes)
+{
+    if (!b.h_tab) {
+        HIPTRY(mem.pinned(&b.h_tab, 64 * sizeof(DecOutPos)));
+        HIPTRY(hipHostGetDevicePointer((void**)&b.d_tab, b.h_tab, 0));
+    }
+    if (dev_bytes > b.d_cap) {
+        if (b.d_stage) mem.drop(b.d_stage);
+        b.d_stage = nullptr; b.d_cap = 0;
+        HIPTRY(mem.dev(&b.d_stage, dev_bytes));
+        b.d_cap = dev_bytes;
+    }
+    if (host_bytes > b.h_cap) {
+        if (b.h_stage) mem.drop(b.h_stage);
+        b.h_stage = nullptr; b.h_cap = 0;
+        HIPTRY(mem.pinned(&b.h_stage, host_bytes));
+        b.h_cap = host_bytes;
+    }
+    return hipSuccess;
+}
+
+// ONE launch for the n pictures of rows[] (d_tab: the same rows as the device reads them) out of engine e's ring into dst
+hipError_t launch_dec_out(const mi355x_h264_encoder* e, int layout, const DecOutPos* rows, const DecOutPos* d_tab, int n, uint8_t* dst, hipStream_t st)
+{
+    int max_bytes = 0, max_rows = 0;
+    for (int i = 0; i < n; i++) {
+        const int w = (int)rows[i].width, h = (int)rows[i].height;
+        max_bytes = std::max(max_bytes, layout == DEC_OUT_RGBA ? 4 * w : w);
+        max_rows = std::max(max_rows, layout == DEC_OUT_RGBA ? h : (layout == DEC_OUT_I420 ? h + 2 * (h / 2) : h + h / 2));
+    }
+    DecOutParams P{};
+    P.y = e->d_plane_base[0]; P.u = e->d_plane_base[1]; P.v = e->d_plane_base[2];
+    P.st_y = e->st_y; P.st_c = e->st_c; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c;
+    P.pitch = e->cw; P.dst = dst; P.tab = d_tab;
+    // a row of b bytes that starts anywhere touches at most b / 16 + 2 chunks of 16 aligned bytes
+    const dim3 grid((unsigned)((max_bytes / 16 + 2 + 63) / 64), (unsigned)((max_rows + 4 * DEC_OUT_ROWS - 1) / (4 * DEC_OUT_ROWS)), (unsigned)n), block(64, 4);
+    switch (layout) {
+        case DEC_OUT_I420: hipLaunchKernelGGL(k_dec_out<DEC_OUT_I420>, grid, block, 0, st, P); break;
+        case DEC_OUT_NV12: hipLaunchKernelGGL(k_dec_out<DEC_OUT_NV12>, grid, block, 0, st, P); break;
+        case DEC_OUT_NV21: hipLaunchKernelGGL(k_dec_out<DEC_OUT_NV21>, grid, block, 0, st, P); break;
+        default: hipLaunchKernelGGL(k_dec_out<DEC_OUT_RGBA>, grid, block, 0, st, P); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
 struct mi355x_h264_decoder {
     h264dec::Parser parser;
     mi355x_h264_encoder* eng = nullptr;
@@ -22,6 +101,7 @@ struct mi355x_h264_decoder {
     DevMem mem;                     // the five per-macroblock arrays above (they change with the picture size)
     DecBigLevel* d_big = nullptr;   // levels that did not fit a byte (grows with the largest list met)
     size_t big_cap = 0;
+    DecOutBuf out;                  // read in a layout (k_dec_out.h): table and staging, in `mem`
     // One picture of look-ahead: decode() returns once picture n is LAUNCHED; the parse of access unit n + 1 then runs on the
     // host while the GPU reconstructs n.  The parser fills two picture buffers in turn (pinned memory: the uploads are
     // asynchronous); up_done[k] = the uploads out of buffer k have finished, so it may be parsed into again.
@@ -194,6 +274,7 @@ int dec_decode_unit(mi355x_h264_decoder* d, const uint8_t* au, size_t len, int* 
         d->mbw = pic.mbw; d->mbh = pic.mbh; d->have_refs = 0; d->last = -1;
         d->mem.free_all();   // (a picture after an allocation that failed below must meet null pointers, not the freed arrays)
         d->d_mbqp = d->d_refq = d->d_mbavail = nullptr; d->d_mv4 = nullptr; d->d_lv8 = nullptr;
+        d->out = DecOutBuf();
         const size_t n = (size_t)pic.mbw * pic.mbh;
         if (d->mem.dev(&d->d_mbqp, n) != hipSuccess || d->mem.dev(&d->d_mv4, n * 64) != hipSuccess || d->mem.dev(&d->d_refq, n * 4) != hipSuccess ||
             d->mem.dev(&d->d_mbavail, n) != hipSuccess || d->mem.dev(&d->d_lv8, n * LV_STRIDE) != hipSuccess)
@@ -239,6 +320,28 @@ int64_t dec_read(mi355x_h264_decoder* d, void* dst, size_t cap, bool to_device)
         o += pw * ph;
     }
     return (int64_t)need;
+}
+
+// the last picture in a layout: the group's kernel with one position (batch item 0, ring slot `last`)
+int64_t dec_read_out(mi355x_h264_decoder* d, int layout, int row_align, void* dst, size_t cap, bool to_device, mi355x_h264_dec_out_pic* pic)
+{
+    if (!d || !pic || !out_args_ok(layout, row_align) || d->last < 0) return MI355X_H264_E_ARG;
+    const OutGeom geo = out_geom(layout, d->width, d->height, row_align);
+    if (dst && (cap < geo.bytes || (to_device && ((uintptr_t)dst & 15)))) return MI355X_H264_E_ARG;
+    *pic = out_pic(0, d->width, d->height, geo, 1, (int64_t)d->pictures);
+    if (!dst) return (int64_t)geo.bytes;
+    if (hipSetDevice(d->device) != hipSuccess) return set_err(d->err, MI355X_H264_E_HIP, "hipSetDevice");
+    if (const int wrc = dec_wait(d)) return wrc;   // the picture asked for may still be in flight
+    const mi355x_h264_encoder* e = d->eng;
+    const size_t stage = to_device ? 0 : geo.bytes;
+    if (out_reserve(d->mem, d->out, stage, stage) != hipSuccess) return set_err(d->err, MI355X_H264_E_NOMEM, "memory for the output staging (%s)", t_failed_call);
+    d->out.h_tab[0] = DecOutPos{0u, (uint32_t)d->last, (uint32_t)d->crop_x, (uint32_t)d->crop_y, (uint32_t)d->width, (uint32_t)d->height,
+                                (uint32_t)geo.stride, (uint32_t)geo.cstride, 0ull, 0ull};
+    HIPCHK(d->err, launch_dec_out(e, layout, d->out.h_tab, d->out.d_tab, 1, to_device ? (uint8_t*)dst : d->out.d_stage, e->stream));
+    if (!to_device) HIPCHK(d->err, hipMemcpyAsync(d->out.h_stage, d->out.d_stage, geo.bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(d->err, hipStreamSynchronize(e->stream));
+    if (!to_device) memcpy(dst, d->out.h_stage, geo.bytes);
+    return (int64_t)geo.bytes;
 }
 
 }  // namespace

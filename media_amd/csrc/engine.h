@@ -43,6 +43,16 @@ struct DevMem {
         if (*d && !*h && pinned(h, bytes) != hipSuccess) *h = nullptr;
         return *d && *h;
     }
+    // one block back ahead of the others (a staging buffer that has to grow); nothing may be using it any more
+    void drop(void* p)
+    {
+        for (size_t i = 0; i < blocks.size(); i++)
+            if (blocks[i].p == p) {
+                if (blocks[i].pinned) (void)hipHostFree(p); else (void)hipFree(p);
+                blocks.erase(blocks.begin() + (long)i);
+                return;
+            }
+    }
     void free_all() { for (const Block& b : blocks) { if (b.pinned) (void)hipHostFree(b.p); else (void)hipFree(b.p); } blocks.clear(); }
 };
 

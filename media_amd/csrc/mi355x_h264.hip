@@ -33,6 +33,7 @@ using namespace h264;
 
 #include "host_framing.h"
 #include "rgba_kernels.h"
+#include "k_dec_out.h"
 #include "engine.h"
 #include "hub_sched.h"
 #include "hub.h"
@@ -503,6 +504,11 @@ int mi355x_h264_dec_picture_info(const mi355x_h264_decoder* d, int* width, int* 
 int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder* d, uint8_t* dst, size_t cap) { return dec_read(d, dst, cap, false); }
 int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder* d, void* d_dst, size_t cap) { return dec_read(d, d_dst, cap, true); }
 
+int64_t mi355x_h264_dec_read(mi355x_h264_decoder* d, int layout, int row_align, void* dst, size_t cap, int to_device, mi355x_h264_dec_out_pic* pic)
+{
+    return dec_read_out(d, layout, row_align, dst, cap, to_device != 0, pic);
+}
+
 // coded-size planes of the last picture (test hook: compared with the oracle decoder's planes)
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder* d, int plane, void* dst, size_t cap)
 {
@@ -563,6 +569,7 @@ void mi355x_h264_dec_group_destroy(mi355x_h264_dec_group* g)
     if (g->eng) { (void)dg_wait(g); (void)hipStreamSynchronize(g->eng->stream); }
     for (int k = 0; k < 2; k++) {
         if (g->up_done[k]) (void)hipEventDestroy(g->up_done[k]);
+        if (g->out.done[k]) (void)hipEventDestroy(g->out.done[k]);
         if (g->h_big[k]) (void)hipHostFree(g->h_big[k]);
     }
     if (g->d_big) (void)hipFree(g->d_big);
@@ -636,10 +643,17 @@ int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group* g, int stream, 
 int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group* g, int64_t* out, int n)
 {
     if (!g || !out || n < 1) return MI355X_H264_E_ARG;
-    const int m = std::min(n, 7);
+    const int m = n >= 11 ? 11 : (n >= 9 ? 9 : std::min(n, 7));   // (a caller with an earlier layout's slots gets those)
     for (int i = 0; i < m; i++) out[i] = g->last[i];
     return m;
 }
+
+int64_t mi355x_h264_dec_group_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* dst, size_t cap, int to_device, mi355x_h264_dec_out_pic* pics)
+{
+    return dg_read_all(g, layout, row_align, dst, cap, to_device != 0, pics);
+}
+int mi355x_h264_dec_group_set_output(mi355x_h264_dec_group* g, int layout, int row_align) { return dg_set_output(g, layout, row_align); }
+int mi355x_h264_dec_group_output(mi355x_h264_dec_group* g, int back, const uint8_t** data, mi355x_h264_dec_out_pic* pics) { return dg_output(g, back, data, pics); }
 
 // ---- the host parser alone (no GPU): what it recovered from the last access unit, for the CPU tests ----
 struct mi355x_h264_parser { h264dec::Parser p; };

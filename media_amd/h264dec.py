@@ -6,7 +6,17 @@ import numpy as np
 from .capi import lib, EncoderError, MBINFO_DTYPE, LV_STRIDE
 
 E_STREAM = -7
+PIX_I420, PIX_NV12, PIX_NV21, PIX_RGBA = 0, 1, 2, 3   # output layouts (MI355X_H264_PIX_*)
 _bound = False
+
+
+class OutPic(C.Structure):
+    """mi355x_h264_dec_out_pic: where a picture lies in an output (offset -1: the stream has none there)"""
+    _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("chroma_stride", C.c_int32),
+                ("fresh", C.c_int32), ("reserved", C.c_int32), ("serial", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 def _bind():
@@ -41,8 +51,26 @@ def _bind():
     L.mi355x_h264_dec_group_read_i420_device.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_dec_group_read_i420_device.restype = C.c_int64
     L.mi355x_h264_dec_group_debug_plane.argtypes = [vp, C.c_int, C.c_int, vp, sz]; L.mi355x_h264_dec_group_debug_plane.restype = C.c_int64
     L.mi355x_h264_dec_group_last_step.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+    op = C.POINTER(OutPic)
+    L.mi355x_h264_dec_read.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.c_int, op]; L.mi355x_h264_dec_read.restype = C.c_int64
+    L.mi355x_h264_dec_group_read_all.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.c_int, op]; L.mi355x_h264_dec_group_read_all.restype = C.c_int64
+    L.mi355x_h264_dec_group_set_output.argtypes = [vp, C.c_int, C.c_int]
+    L.mi355x_h264_dec_group_output.argtypes = [vp, C.c_int, C.POINTER(vp), op]
     _bound = True
     return L
+
+
+def _tensor_ready(tensor):
+    """the gather kernel runs on the engine's own stream, which does not wait for the default stream: whatever torch has queued
+    on the tensor's device (the fill that made the tensor, say) must be complete before the kernel writes into it"""
+    import torch
+    torch.cuda.synchronize(tensor.device)
+
+
+def _pic_bytes(p, layout):
+    """bytes of a picture of an output in `layout` from its descriptor (include/mi355x_h264_dec.h states the packing)"""
+    chroma_planes = {PIX_I420: 2, PIX_NV12: 1, PIX_NV21: 1, PIX_RGBA: 0}[layout]
+    return p["stride"] * p["height"] + chroma_planes * p["chroma_stride"] * (p["height"] // 2)
 
 
 class StreamError(EncoderError):
@@ -95,6 +123,24 @@ class Decoder:
     def i420_device(self, ptr, cap):
         return lib().mi355x_h264_dec_read_i420_device(self.h, ptr, cap)
 
+    def read(self, layout, row_align=1, device_tensor=None):
+        """the last picture in `layout` (PIX_*): (buffer, pic).  buffer is a numpy array of exactly the bytes used, or - with a
+        torch uint8 tensor in device memory - that tensor, written in place (bytes used: pic["bytes"])"""
+        pic = OutPic()
+        need = lib().mi355x_h264_dec_read(self.h, layout, row_align, None, 0, 0, C.byref(pic))
+        if need < 0:
+            raise EncoderError("dec_read(layout %d, row_align %d) -> %d" % (layout, row_align, need))
+        if device_tensor is None:
+            buf = np.empty(need, np.uint8)
+            n = lib().mi355x_h264_dec_read(self.h, layout, row_align, buf.ctypes.data, buf.nbytes, 0, C.byref(pic))
+        else:
+            buf = device_tensor
+            _tensor_ready(buf)
+            n = lib().mi355x_h264_dec_read(self.h, layout, row_align, buf.data_ptr(), buf.numel() * buf.element_size(), 1, C.byref(pic))
+        if n != need:
+            raise EncoderError("dec_read -> %d: %s" % (n, lib().mi355x_h264_dec_last_error(self.h).decode()))
+        return buf, dict(pic.as_dict(), bytes=n)
+
     def plane(self, p):
         """coded-size plane p of the last picture"""
         _, _, cw, ch = self.info()
@@ -119,7 +165,8 @@ class Decoder:
 class DecoderGroup:
     """`streams` decoders behind one engine: decode() takes the next access unit of every stream (None: the stream sits this step
     out) and reconstructs all their pictures in one set of transfers and launches"""
-    STEP = ("serial", "pictures", "launches", "transfers", "parse_threads", "parse_us", "launch_us")
+    STEP = ("serial", "pictures", "launches", "transfers", "parse_threads", "parse_us", "launch_us", "output_launches", "output_transfers",
+            "read_launches", "read_transfers")
 
     def __init__(self, streams, device=0):
         L = _bind()
@@ -196,9 +243,55 @@ class DecoderGroup:
         return out
 
     def last_step(self):
-        v = (C.c_int64 * 7)()
-        n = lib().mi355x_h264_dec_group_last_step(self.h, v, 7)
+        """the last step; output_launches / output_transfers: what an armed step added (set_output); read_launches /
+        read_transfers: what the last read_all call made"""
+        v = (C.c_int64 * 11)()
+        n = lib().mi355x_h264_dec_group_last_step(self.h, v, 11)
         return dict(zip(self.STEP[:n], list(v)[:n]))
+
+    def read_all(self, layout, row_align=1, device_tensor=None, out=None):
+        """every stream's last picture in one call: (buffer, pics).  buffer: a numpy array of exactly the bytes used (a view of
+        `out`, a numpy uint8 array of the caller's that is large enough, when one is given: a fresh array of tens of megabytes
+        per call costs more than the transfer), or the torch uint8 device tensor handed in, written in place; pics: one dict
+        per stream (offset -1: no picture yet), and the bytes used as self.read_bytes"""
+        pics = (OutPic * self.streams)()
+        need = lib().mi355x_h264_dec_group_read_all(self.h, layout, row_align, None, 0, 0, pics)
+        if need < 0:
+            raise EncoderError("group read_all(layout %d, row_align %d) -> %d" % (layout, row_align, need))
+        if device_tensor is None:
+            buf = np.empty(need, np.uint8) if out is None else out[:need]
+            if buf.size != need:
+                raise EncoderError("group read_all: `out` holds %d bytes, %d are needed" % (buf.size, need))
+            n = lib().mi355x_h264_dec_group_read_all(self.h, layout, row_align, buf.ctypes.data, buf.nbytes, 0, pics)
+        else:
+            buf = device_tensor
+            _tensor_ready(buf)
+            n = lib().mi355x_h264_dec_group_read_all(self.h, layout, row_align, buf.data_ptr(), buf.numel() * buf.element_size(), 1, pics)
+        if n != need:
+            raise EncoderError("group read_all -> %d: %s" % (n, self.error()))
+        self.read_bytes = n
+        return buf, [p.as_dict() for p in pics]
+
+    def set_output(self, layout, row_align=1):
+        """arm the group (layout -1: disarm): every step from the next one on also delivers its pictures in `layout` into one of
+        two pinned sets; output() hands them out"""
+        rc = lib().mi355x_h264_dec_group_set_output(self.h, layout, row_align)
+        if rc != 0:
+            raise EncoderError("group set_output(layout %d, row_align %d) -> %d" % (layout, row_align, rc))
+        self._armed = layout
+
+    def output(self, back=0):
+        """(numpy view of the pinned set, pics) of the last armed step (back = 0: waits for it) or of the one before (back = 1:
+        complete already).  The view is valid until the second decode() after that step"""
+        pics = (OutPic * self.streams)()
+        data = C.c_void_p()
+        rc = lib().mi355x_h264_dec_group_output(self.h, back, C.byref(data), pics)
+        if rc != 0:
+            raise EncoderError("group output(back %d) -> %d: %s" % (back, rc, self.error()))
+        out = [p.as_dict() for p in pics]
+        used = max([p["offset"] + _pic_bytes(p, self._armed) for p in out if p["offset"] >= 0] + [0])
+        view = np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint8)), shape=(max(used, 1),))[:used]
+        return view, out
 
 
 class Parser:

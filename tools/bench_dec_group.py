@@ -1,11 +1,15 @@
 """Aggregate decode throughput of S 1080p streams: one DecoderGroup against S Decoder objects on S host threads.
 The content is what `bench.py --mode decode` decodes (S1, QP 26, GOP 30, written by the HIP encoder); every stream gets the same
-access units.  Both forms run interleaved, --repeat times each, in one process; with and without reading every picture back.
-Prints one JSON line per (S, form, read) with median and min / max fps, and for the group the host's parse / launch time per
-picture (mi355x_h264_dec_group_last_step).  Kernel times: run it once under `rocprofv3 --kernel-trace --stats -- python
-tools/bench_dec_group.py --streams 16 --repeat 1`.
+access units.  Both forms run interleaved, --repeat times each, in one process, once per read mode of --read:
+    none   nothing is read back
+    each   every stream's picture with read_i420(k), one after the other (the objects: i420() on each stream's thread)
+    all    all pictures of a step with one read_all() (--layout, to the host)
+    armed  set_output() once; per step decode(t + 1), then output(back=1): the pictures of step t, copied while t + 1 was parsed
+The objects know `none` and read every picture back in all other modes.  Prints one JSON line per (S, form, read) with median and
+min / max fps, and for the group the host's parse / launch time per picture (mi355x_h264_dec_group_last_step).  Kernel times: run it
+once under `rocprofv3 --kernel-trace --stats -- python tools/bench_dec_group.py --streams 16 --repeat 1 --read armed`.
 
-    python tools/bench_dec_group.py [--streams 1,4,16,32] [--pictures 60] [--repeat 3]"""
+    python tools/bench_dec_group.py [--streams 1,4,16,32] [--pictures 60] [--repeat 3] [--read none,each] [--layout i420]"""
 import argparse
 import json
 import os
@@ -26,19 +30,34 @@ def make_stream(n):
     return aus
 
 
-def run_group(aus, S, read):
+LAYOUTS = {"i420": 0, "nv12": 1, "nv21": 2, "rgba": 3}
+
+
+def run_group(aus, S, read, layout=0):
     from media_amd import h264dec
     g = h264dec.DecoderGroup(S)
     parse_us = launch_us = 0
+    dst = None  # read_all's destination
+    taken = 0   # bytes looked at, so that no mode gets away with not touching its pictures
     t0 = time.perf_counter()
-    for au in aus:
+    if read == "armed":
+        g.set_output(layout)
+    for t, au in enumerate(aus):
         res = g.decode([au] * S)
         assert all(r == (0, 1) for r in res), res
         st = g.last_step()
         parse_us += st["parse_us"]; launch_us += st["launch_us"]
-        if read:
+        if read == "each":
             for k in range(S):
-                g.read_i420(k)
+                taken += g.read_i420(k).size
+        elif read == "all":
+            buf, _ = g.read_all(layout, out=dst)
+            dst = buf.base if buf.base is not None else buf   # (the first call's array serves the others)
+            taken += buf.size
+        elif read == "armed" and t > 0:
+            taken += g.output(1)[0].size
+    if read == "armed":
+        taken += g.output(0)[0].size
     g.sync()
     dt = time.perf_counter() - t0
     g.close()
@@ -55,7 +74,7 @@ def run_objects(aus, S, read):
         start.wait()
         for au in aus:
             assert d.decode(au)
-            if read:
+            if read != "none":
                 d.i420()
         d.sync()
 
@@ -81,19 +100,23 @@ def main():
     ap.add_argument("--streams", default="1,4,16,32")
     ap.add_argument("--pictures", type=int, default=60)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--read", default="none,each", help="read modes, comma-separated: none, each, all, armed")
+    ap.add_argument("--layout", default="i420", choices=sorted(LAYOUTS), help="of the modes all and armed")
     a = ap.parse_args()
+    modes = a.read.split(",")
+    assert all(m in ("none", "each", "all", "armed") for m in modes), modes
     aus = make_stream(a.pictures)
     for S in [int(x) for x in a.streams.split(",")]:
-        for read in (False, True):
+        for read in modes:
             runs = {"group": [], "objects": []}
             extra = {}
             for _ in range(a.repeat):
                 for form, fn in (("group", run_group), ("objects", run_objects)):
-                    fps, extra[form] = fn(aus, S, read)
+                    fps, extra[form] = fn(aus, S, read, LAYOUTS[a.layout]) if form == "group" else fn(aus, S, read)
                     runs[form].append(fps)
             for form in ("group", "objects"):
                 v = runs[form]
-                print(json.dumps(dict({"streams": S, "form": form, "read_back": read, "pictures_per_stream": a.pictures, "fps_median": round(statistics.median(v), 1),
+                print(json.dumps(dict({"streams": S, "form": form, "read_back": read != "none", "read": read, "layout": a.layout if read in ("all", "armed") else "i420", "pictures_per_stream": a.pictures, "fps_median": round(statistics.median(v), 1),
                                        "fps_min": round(min(v), 1), "fps_max": round(max(v), 1), "runs": [round(x, 1) for x in v]}, **extra[form])), flush=True)
 
 
