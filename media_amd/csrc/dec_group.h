@@ -6,10 +6,13 @@
 // items from the lowest to the highest taking part (a stream that sits the step out inside that range has its stale slice sent
 // along: the per-macroblock arrays on the device are scratch of the step, nobody reads an absent item's).  What the pictures of a
 // step have of their own - ring slots, reference lists, offsets, filter controls, slice bands - is the step's position table
-// (dev_common.h DecPos); the kernels are k_dec_widen_pos / _inter_pos / _bs_pos, k_dec_resid<true>, k_pintra_rows<true, true> and
-// k_deblock_rows<BS4, true, true>.
+// (dev_common.h DecPos); the kernels are k_dec_widen_pos / _inter_pos / _bs_pos, k_dec_resid, k_pintra_rows<true, true> and
+// k_deblock_rows<BS4, true, true>.  This is the project's ONE decoder: the decoder peer (decoder.h) is a group of one stream.  What
+// the general form costs such a group is the copy of the parsed picture into the pinned set, about 4.5 MB per 1080p picture; the
+// parse job makes it (a parser that writes into the set in place is the follow-up).
 #pragma once
 #include "dec_group_sched.h"
+#include "dec_out.h"
 
 namespace {
 
@@ -37,6 +40,9 @@ constexpr size_t DG_BYTES[DG_ARRAYS] = {sizeof(MbInfo), 16, 16, LV_STRIDE, 1, 1,
 
 struct mi355x_h264_dec_group {
     int device = 0, nstreams = 0;
+    bool resize = false;                 // an IDR picture of another coded size re-makes the geometry.  Honoured for a group of ONE
+                                         // stream only (a step of several has rows and copies in the arrays that would go); the
+                                         // decoder peer sets it: not in the public ABI, where a group keeps its first size
     mi355x_h264_encoder* eng = nullptr;
     int mbw = 0, mbh = 0;
     DecGroupStream* st = nullptr;        // [nstreams]
@@ -56,6 +62,7 @@ struct mi355x_h264_dec_group {
     int nflight = 0;
     int intra_slots = 32, filter_slots = 32;   // pictures the row wavefronts hold at a time (the rest are walked to)
     int64_t step_serial = 0, last[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double last_ms[2] = {0, 0};          // the last step's parse and launch time, untruncated (last[5] / last[6] are whole microseconds)
     // output (k_dec_out.h).  rd: read_all's table and staging; its device staging buffer also serves the armed steps (everything
     // is ordered on the engine's stream).  Armed: the step's table of output positions lies behind its DecPos rows in tables of
     // their own (h_tabx / d_tabx: DecPos [streams], then DecOutPos [streams]), so that one transfer carries both.
@@ -164,6 +171,21 @@ int dg_create_geometry(mi355x_h264_dec_group* g, int mbw, int mbh)
     return MI355X_H264_OK;
 }
 
+// `resize`: everything the old coded size owned goes, so that the IDR picture in hand finds the group as a new one does.  Nothing may
+// be in flight when the arrays are freed: the step (dg_wait, checked by the caller), whatever else is queued on the engine's stream
+// - an armed step's copy, the uploads out of BOTH pinned sets -, which the synchronize covers.  No stream keeps a picture.
+int dg_drop_geometry(mi355x_h264_dec_group* g)
+{
+    if (const int wrc = dg_wait(g)) return wrc;
+    HIPCHK(g->err, hipStreamSynchronize(g->eng->stream));
+    g->sched.in_flight[0] = g->sched.in_flight[1] = false;
+    dg_free_geometry(g);
+    destroy_engine(g->eng); g->eng = nullptr;
+    g->mbw = g->mbh = 0;
+    for (int i = 0; i < g->nstreams; i++) { dg_drop_refs(g->st[i]); g->st[i].cur = 0; g->st[i].last = -1; }
+    return MI355X_H264_OK;
+}
+
 // the parsed picture of stream i into its slice of pinned set k (run by the stream's parse job, or by the caller in the step that
 // fixes the geometry)
 void dg_copy_picture(mi355x_h264_dec_group* g, int i, int k)
@@ -226,6 +248,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     const double t1 = now_ms();
     g->step_serial++;
     g->last[0] = g->step_serial; g->last[1] = g->last[2] = g->last[3] = 0; g->last[4] = g->sched.last_threads;
+    g->last_ms[0] = t1 - t0; g->last_ms[1] = 0;
     g->last[5] = (int64_t)((t1 - t0) * 1e3); g->last[6] = 0; g->last[7] = g->last[8] = 0;
     // the step in flight must be out of the way before this one is launched; its time-out flag is looked at here
     if (const int wrc = dg_wait(g)) {
@@ -249,6 +272,12 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         if (s.prc < 0) { snprintf(s.err, sizeof(s.err), "%s", s.parser.error().c_str()); dg_drop_refs(s); rc[i] = MI355X_H264_E_STREAM; continue; }
         const h264dec::Picture& pic = s.parser.picture();
         const h264dec::Sps& sps = s.parser.sps();
+        if (S == 1 && g->eng && g->resize && pic.idr && (pic.mbw != g->mbw || pic.mbh != g->mbh)) {
+            if (const int drc = dg_drop_geometry(g)) {
+                for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
+                return drc;
+            }
+        }
         if (!g->eng) {
             if (!pic.idr) { rc[i] = dg_stream_fail(s, "the stream must start with an IDR picture"); continue; }
             if (const int crc = dg_create_geometry(g, pic.mbw, pic.mbh)) {
@@ -297,7 +326,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         T.w[1] = (uint32_t)(uint8_t)(int8_t)pic.cqo[0] | ((uint32_t)(uint8_t)(int8_t)pic.cqo[1] << 8) | ((uint32_t)(uint8_t)(int8_t)pic.filter_oa << 16) |
                  ((uint32_t)(uint8_t)(int8_t)pic.filter_ob << 24);
         // slices that are bands of whole rows run as independent wavefronts; any other shape: one wavefront over the picture.  The
-        // filter sees one slice with idc 0 (edges between slices are filtered) and with slices that are no bands (k_dec_bs has
+        // filter sees one slice with idc 0 (edges between slices are filtered) and with slices that are no bands (k_dec_bs_pos has
         // zeroed the strengths between them where idc 2 says so)
         const int rows = pic.slice_rows > 0 ? pic.slice_rows : g->mbh;
         const int frows = (pic.deblock_idc == 0 || pic.slice_rows < 0) ? g->mbh : rows;
@@ -388,7 +417,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     unsigned* const h_err = e->slots[0].sync.h_err;
     if (any_inter) {
         hipLaunchKernelGGL(k_dec_inter_pos, dim3(e->nmb, NP), wave, 0, st, P);
-        hipLaunchKernelGGL(k_dec_resid<true>, dim3((e->nmb + 3) / 4, NP), wave, 0, st, P);
+        hipLaunchKernelGGL(k_dec_resid, dim3((e->nmb + 3) / 4, NP), wave, 0, st, P);
         launches += 2;
     }
     if (any_intra) {
@@ -444,7 +473,8 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     static const bool no_lookahead = getenv("MI355X_H264_DEC_SYNC") != nullptr;   // (measurements: wait for every step before returning)
     int wrc = MI355X_H264_OK;
     if (no_lookahead) wrc = dg_wait(g);
-    g->last[6] = (int64_t)((now_ms() - t1) * 1e3);
+    g->last_ms[1] = now_ms() - t1;
+    g->last[6] = (int64_t)(g->last_ms[1] * 1e3);
     if (wrc) for (int p = 0; p < npos; p++) { got[pos_stream[p]] = 0; rc[pos_stream[p]] = wrc; }
     return wrc;
 }

@@ -4,8 +4,8 @@
 //
 // Parse jobs.  A step hands the pool one job per participating stream; job k is parse(stream[k], set).  Jobs are taken from a
 // counter under the lock, first come first served, by min(jobs, threads) threads - every job is run exactly once, by one thread.  A
-// step of ONE job is run by the caller itself: waking a thread for it costs more than it saves, and a group of one stream
-// then parses exactly as the single decoder does.  run() returns when every job of the step has finished, so a step's jobs never
+// step of ONE job is run by the caller itself: waking a thread for it costs more than it saves; a group of one stream - the decoder
+// peer is one - starts no thread at all.  run() returns when every job of the step has finished, so a step's jobs never
 // overlap the next step's, and what the jobs wrote is visible to the caller (the lock orders it).
 //
 // Buffer sets.  The streams parse into their slices of one SET of group-wide pinned arrays, laid [item][...], from which the step's

@@ -1,0 +1,89 @@
+// media_amd/csrc/dec_out.h -- host side of k_dec_out.h: the geometry of a picture in a layout (include/mi355x_h264_dec.h states the
+// packing), the table and staging buffers of the read calls, and the ONE launch that serves them (dec_group.h).
+#pragma once
+
+namespace {
+
+double now_ms()
+{
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+// ---- output in a layout (k_dec_out.h; include/mi355x_h264_dec.h states the packing) ----
+struct OutGeom { int stride, cstride; size_t bytes; };
+bool out_args_ok(int layout, int row_align) { return layout >= 0 && layout <= 3 && row_align >= 1 && row_align <= 256 && (row_align & (row_align - 1)) == 0; }
+size_t out_align(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+OutGeom out_geom(int layout, int w, int h, int row_align)
+{
+    const size_t a = (size_t)row_align;
+    OutGeom g{};
+    if (layout == DEC_OUT_RGBA) { g.stride = (int)out_align(4 * (size_t)w, a); g.bytes = (size_t)g.stride * h; }
+    else if (layout == DEC_OUT_I420) { g.stride = (int)out_align(w, a); g.cstride = (int)out_align(w / 2, a); g.bytes = (size_t)g.stride * h + 2 * (size_t)g.cstride * (h / 2); }
+    else { g.stride = g.cstride = (int)out_align(w, a); g.bytes = (size_t)g.stride * h + (size_t)g.cstride * (h / 2); }
+    return g;
+}
+mi355x_h264_dec_out_pic out_pic(int64_t off, int w, int h, const OutGeom& g, int fresh, int64_t serial)
+{
+    mi355x_h264_dec_out_pic p{};
+    p.offset = off; p.width = w; p.height = h; p.stride = g.stride; p.chroma_stride = g.cstride; p.fresh = fresh; p.serial = serial;
+    return p;
+}
+mi355x_h264_dec_out_pic out_no_pic(int64_t serial) { mi355x_h264_dec_out_pic p{}; p.offset = -1; p.serial = serial; return p; }
+
+// what the read calls of a decoder or a group own, made with the first call that needs it: the position table in pinned memory
+// (the kernel reads it in place: a read call makes no transfer for it) and the staging pair of the host form
+struct DecOutBuf {
+    DecOutPos* h_tab = nullptr;   // [DEC_GROUP_MAX_STREAMS]
+    const DecOutPos* d_tab = nullptr;   // the same memory as the device addresses it
+    uint8_t* d_stage = nullptr; size_t d_cap = 0;
+    uint8_t* h_stage = nullptr; size_t h_cap = 0;
+};
+// nothing on the GPU may be using the buffers (the callers have waited for their stream)
+hipError_t out_reserve(DevMem& mem, DecOutBuf& b, size_t dev_bytes, size_t host_bytes)
+{
+    if (!b.h_tab) {
+        HIPTRY(mem.pinned(&b.h_tab, 64 * sizeof(DecOutPos)));
+        HIPTRY(hipHostGetDevicePointer((void**)&b.d_tab, b.h_tab, 0));
+    }
+    if (dev_bytes > b.d_cap) {
+        if (b.d_stage) mem.drop(b.d_stage);
+        b.d_stage = nullptr; b.d_cap = 0;
+        HIPTRY(mem.dev(&b.d_stage, dev_bytes));
+        b.d_cap = dev_bytes;
+    }
+    if (host_bytes > b.h_cap) {
+        if (b.h_stage) mem.drop(b.h_stage);
+        b.h_stage = nullptr; b.h_cap = 0;
+        HIPTRY(mem.pinned(&b.h_stage, host_bytes));
+        b.h_cap = host_bytes;
+    }
+    return hipSuccess;
+}
+
+// ONE launch for the n pictures of rows[] (d_tab: the same rows as the device reads them) out of engine e's ring into dst
+hipError_t launch_dec_out(const mi355x_h264_encoder* e, int layout, const DecOutPos* rows, const DecOutPos* d_tab, int n, uint8_t* dst, hipStream_t st)
+{
+    int max_bytes = 0, max_rows = 0;
+    for (int i = 0; i < n; i++) {
+        const int w = (int)rows[i].width, h = (int)rows[i].height;
+        max_bytes = std::max(max_bytes, layout == DEC_OUT_RGBA ? 4 * w : w);
+        max_rows = std::max(max_rows, layout == DEC_OUT_RGBA ? h : (layout == DEC_OUT_I420 ? h + 2 * (h / 2) : h + h / 2));
+    }
+    DecOutParams P{};
+    P.y = e->d_plane_base[0]; P.u = e->d_plane_base[1]; P.v = e->d_plane_base[2];
+    P.st_y = e->st_y; P.st_c = e->st_c; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c;
+    P.pitch = e->cw; P.dst = dst; P.tab = d_tab;
+    // a row of b bytes that starts anywhere touches at most b / 16 + 2 chunks of 16 aligned bytes
+    const dim3 grid((unsigned)((max_bytes / 16 + 2 + 63) / 64), (unsigned)((max_rows + 4 * DEC_OUT_ROWS - 1) / (4 * DEC_OUT_ROWS)), (unsigned)n), block(64, 4);
+    switch (layout) {
+        case DEC_OUT_I420: hipLaunchKernelGGL(k_dec_out<DEC_OUT_I420>, grid, block, 0, st, P); break;
+        case DEC_OUT_NV12: hipLaunchKernelGGL(k_dec_out<DEC_OUT_NV12>, grid, block, 0, st, P); break;
+        case DEC_OUT_NV21: hipLaunchKernelGGL(k_dec_out<DEC_OUT_NV21>, grid, block, 0, st, P); break;
+        default: hipLaunchKernelGGL(k_dec_out<DEC_OUT_RGBA>, grid, block, 0, st, P); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace

@@ -1,6 +1,6 @@
 // media_amd/csrc/engine.h -- the encoder engine behind include/mi355x_h264.h: device memory, streams, access-unit
 // slots, one lockstep step of launches (submit_step), the wait for it and the host's finish of every access unit.  The
-// stream hub (hub.h) and the decoder peer (decoder.h) each drive one engine.  Part of the one translation unit
+// stream hub (hub.h) and the decoder groups (dec_group.h) each drive one engine.  Part of the one translation unit
 // mi355x_h264.hip, which includes the kernels before this file.
 #pragma once
 
@@ -286,7 +286,7 @@ struct Step {
         else hipLaunchKernelGGL(KF, grid, block, 0, stream, __VA_ARGS__);                \
     } while (0)
 
-// ---- the parameter blocks of the kernels, as far as they come from the engine alone (submit_step and the decoder's dec_submit
+// ---- the parameter blocks of the kernels, as far as they come from the engine alone (submit_step and the decoder groups' dg_step
 // add what is theirs) ----
 inline unsigned next_nonzero(unsigned& serial) { serial = serial == 0xFFFFFFFFu ? 1u : serial + 1u; return serial; }   // changes every time, never 0
 

@@ -40,7 +40,7 @@ struct DbParams {
     int alpha_y, beta_y, alpha_c, beta_c;
     int tc0_y[3], tc0_c[3];  // by bS-1
     SliceRows sl;        // several slices: disable_deblocking_filter_idc 2, the edge between two slices is left alone
-    const uint8_t* bs;   // boundary strengths of k_bs / k_dec_bs, 32 per macroblock: [dir][edge][segment]; the diagonal form reads these bytes, the persistent forms the same array as words (DbRowParams::bs)
+    const uint8_t* bs;   // boundary strengths of k_bs / k_dec_bs_pos, 32 per macroblock: [dir][edge][segment]; the diagonal form reads these bytes, the persistent forms the same array as words (DbRowParams::bs)
     // k_deblock_rows<.., PERMB = true> (decoder peer): thresholds per edge from the two macroblocks' own QPs (8.7.2.2)
     const uint8_t* mbqp; // QP_Y per macroblock (0 for I_PCM)
     int oa, ob;          // FilterOffsetA, FilterOffsetB
@@ -213,7 +213,7 @@ struct DbRowParams {
     // indirect launches (IND = true, dev_common.h item_ref): position -> item, its ring slot and its QP; d.pl[] = plane bases
     const uint32_t* itemtab;
     size_t st_ring_y, st_ring_c;
-    const DecPos* dectab;    // decoder groups (PERMB && IND): position -> what the picture has of its own (dev_common.h)
+    const DecPos* dectab;    // decoder groups (PERMB): position -> what the picture has of its own (dev_common.h)
 };
 
 // One edge, one line of samples held in registers, branch-free so that luma and
@@ -279,7 +279,7 @@ __device__ __forceinline__ DbThr db_picture_thr(const DbParams& D, const bool is
 template <bool PERMB, bool IND>
 __device__ __forceinline__ bool db_picture_view(const DbRowParams& R, const int pos, DbParams& D, u64*& handoff, const uint32_t*& bsw)
 {
-    if constexpr (PERMB && IND) {
+    if constexpr (PERMB) {
         // decoder groups: the position is a row of the decoder table (dev_common.h DecPos): item, ring slot, filter offsets, chroma QP
         // offsets and the filter's slice bands are the picture's own; the thresholds come per edge from mbqp.  need_intra picks the
         // form by the table's flag (a decoder's I_PCM macroblocks never switch the filter off: anypcm is not looked at)
@@ -310,7 +310,6 @@ __device__ __forceinline__ bool db_picture_view(const DbRowParams& R, const int 
 #pragma unroll
         for (int i = 0; i < 3; i++) { D.tc0_y[i] = c_tc0[it.qp][i]; D.tc0_c[i] = c_tc0[qpc][i]; }
     }
-    if (PERMB) D.mbqp += g * R.st_mb;
     handoff = R.handoff + g * R.st_handoff;
     bsw = R.bs + g * R.st_mb * 8;
     return true;
@@ -590,6 +589,7 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
 template <bool BS4, bool PERMB = false, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 {
+    static_assert(!PERMB || IND, "thresholds per edge: the pictures of a decoder group's step");
     // dependency-bound: when a throughput kernel of another stream shares the SIMD, this wave issues first
     __builtin_amdgcn_s_setprio(3);
     for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) deblock_rows_picture<BS4, PERMB, IND>(R, pos);

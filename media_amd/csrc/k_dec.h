@@ -1,18 +1,20 @@
 // media_amd/csrc/k_dec.h -- reconstruction kernels of the decoder peer (row f4 of SURVEY.md 8; the interface it serves is
 // /root/reference/video_decoder/include/VideoDecoder.h:83).  The host parser (h264_parse.h) has filled MbInfo, the quadrant
 // vectors, the Intra4x4 modes and the level lists - the very arrays the encoder's kernels exchange - so that decoding is the
-// encoder's own reconstruction path run from given decisions:
-//   k_dec_inter   motion-compensated prediction of every inter macroblock (8.4.2.2: luma by the 6-tap / bilinear quarter-
+// encoder's own reconstruction path run from given decisions.  Every launch is a decoder group's (dec_group.h; the single decoder
+// is a group of one stream): blockIdx.y is a POSITION of the step's table (dev_common.h DecPos), which names the batch item, the
+// ring slots and what else the picture has of its own; the per-macroblock arrays lie [item].
+//   k_dec_inter_pos  motion-compensated prediction of every inter macroblock (8.4.2.2: luma by the 6-tap / bilinear quarter-
 //                 sample rules straight from the reference plane, chroma by the 1/8-sample bilinear rule), written into the
 //                 picture; lane = (row, four samples), one wave per macroblock; a vector per 4x4 block and a reference
 //                 picture per 8x8 quadrant (the parser's mv4 / refq: partitions down to 4x4, 7.3.5.2)
-//   k_dec_widen   the levels arrive as one byte each (half the upload): widened into the int16 level lists the kernels read;
+//   k_dec_widen_pos  the levels arrive as one byte each (half the upload): widened into the int16 level lists the kernels read;
 //                 k_dec_patch puts the few values that did not fit a byte in place
-//   k_dec_bs      boundary strengths (8.7.2.1) from those arrays - the encoder's k_bs knows vectors per quadrant only
+//   k_dec_bs_pos  boundary strengths (8.7.2.1) from those arrays - the encoder's k_bs knows vectors per quadrant only
 //   k_dec_resid   scaling + inverse transform (4x4: 8.5.12, 8x8: 8.5.13, chroma DC: 8.5.11) of the inter macroblocks' levels,
 //                 added to the prediction in place; lane = one 4x4 block, four macroblocks per wave
-//   k_pintra_rows<true> (k_intra.h)  the intra macroblocks in row-wavefront order, intra_mb_core<true>
-//   k_deblock_rows (encoder)  the loop filter (PERMB = true when QPs or offsets differ inside the picture)
+//   k_pintra_rows<true, true> (k_intra.h)  the intra macroblocks in row-wavefront order, intra_mb_core<true>
+//   k_deblock_rows<BS4, true, true> (k_deblock.h)  the loop filter with thresholds per edge from the macroblocks' own QPs
 #pragma once
 #include "dev_common.h"
 #include "mc_filters.h"
@@ -86,9 +88,12 @@ __device__ __forceinline__ const uint8_t* ref_plane(const FrameParams& P, int re
     return pl == 0 ? y : (pl == 1 ? u : v);
 }
 
-// (k_dec_inter: the batch item is blockIdx.y; k_dec_inter_pos, decoder groups: blockIdx.y is a position of the step's table)
-__device__ __forceinline__ void dec_inter_mb(const FrameParams& P)
+// a position without inter macroblocks is passed by
+__global__ __launch_bounds__(64) void k_dec_inter_pos(FrameParams P0)
 {
+    const DecPosRef d = dec_pos(P0.dectab, blockIdx.y);
+    if (!d.inter) return;
+    const FrameParams P = dec_view(P0, d);
     const int lane = threadIdx.x;
     const int mbi = P.band.row0 * P.mbw + (int)blockIdx.x, my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
     const uint32_t w1 = *(const uint32_t*)((const uint8_t*)(P.mb + mbi) + 4);
@@ -118,39 +123,11 @@ __device__ __forceinline__ void dec_inter_mb(const FrameParams& P)
         *(uint32_t*)(rec_chroma(P, pl) + (size_t)(8 * my + cyy) * (P.cw / 2) + 8 * mx + cxx) = o;
     }
 }
-__global__ __launch_bounds__(64) void k_dec_inter(FrameParams P0)
-{
-    const FrameParams P = batch_view(P0, blockIdx.y);
-    dec_inter_mb(P);
-}
-__global__ __launch_bounds__(64) void k_dec_inter_pos(FrameParams P0)
-{
-    const DecPosRef d = dec_pos(P0.dectab, blockIdx.y);
-    if (!d.inter) return;
-    const FrameParams P = dec_view(P0, d);
-    dec_inter_mb(P);
-}
 
 // lane = four consecutive levels of one macroblock (LV_STRIDE = 416 = 104 words per macroblock); an I_PCM macroblock's area holds
-// its 384 samples as bytes, which keep their place at the start of the int16 area (intra_mb_core<DEC> reads them there)
-__global__ __launch_bounds__(256) void k_dec_widen(const uint32_t* lv8, const MbInfo* mb, int16_t* lv16, int nmb)
-{
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);   // word index
-    if (i >= nmb * (LV_STRIDE / 4)) return;
-    const int mbi = i / (LV_STRIDE / 4), k = i - mbi * (LV_STRIDE / 4);
-    const uint32_t w = lv8[i];
-    if (mb[mbi].type == MB_IPCM) {
-        if (k < 96) ((uint32_t*)(lv16 + (size_t)mbi * LV_STRIDE))[k] = w;
-        return;
-    }
-    const int a = (int)(int8_t)(w & 255u), b = (int)(int8_t)((w >> 8) & 255u), c = (int)(int8_t)((w >> 16) & 255u), d = (int)(int8_t)(w >> 24);
-    uint2 o;
-    o.x = ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
-    o.y = ((uint32_t)c & 0xFFFFu) | ((uint32_t)d << 16);
-    ((uint2*)(lv16 + (size_t)mbi * LV_STRIDE))[k] = o;
-}
-// decoder groups: blockIdx.y = position; the byte levels and the macroblock records lie [item] like the int16 lists.  (k_dec_patch
-// serves a group as it is: the step's large levels are one list whose indices count from item 0.)
+// its 384 samples as bytes, which keep their place at the start of the int16 area (intra_mb_core<DEC> reads them there).
+// blockIdx.y = position; the byte levels and the macroblock records lie [item] like the int16 lists.  (k_dec_patch knows no
+// positions: the step's large levels are one list whose indices count from item 0.)
 __global__ __launch_bounds__(256) void k_dec_widen_pos(const uint32_t* lv8, const MbInfo* mb, int16_t* lv16, int nmb, const DecPos* tab)
 {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);   // word index inside the item
@@ -188,7 +165,7 @@ struct DecBsParams {
     int across;        // disable_deblocking_filter_idc 0: edges between slices are filtered too
     MbDiv mbdiv;
 };
-// item: whose anybs word is raised (the batch item, which for a decoder group is not the grid's y)
+// item: whose anybs word is raised (the batch item, which is not the grid's y)
 __device__ __forceinline__ void dec_bs_pair(const DecBsParams& C, unsigned* anybs, unsigned serial, int item)
 {
     const int lane = threadIdx.x, l = lane & 31, mbi = 2 * (int)blockIdx.x + (lane >> 5);
@@ -223,11 +200,7 @@ __device__ __forceinline__ void dec_bs_pair(const DecBsParams& C, unsigned* anyb
     }
     if (__ballot(bs != 0) != 0ull && lane == 0) anybs[item] = serial;
 }
-__global__ __launch_bounds__(64) void k_dec_bs(DecBsParams C, unsigned* anybs, unsigned serial)
-{
-    dec_bs_pair(C, anybs, serial, (int)blockIdx.y);
-}
-// decoder groups: the arrays lie [item] (C.nmb macroblocks each), `across` is the position's own; a position that is not filtered
+// the arrays lie [item] (C.nmb macroblocks each), `across` is the position's own; a position that is not filtered
 // leaves its anybs word alone, and the loop filter then passes its picture by
 __global__ __launch_bounds__(64) void k_dec_bs_pos(DecBsParams C, unsigned* anybs, unsigned serial, const DecPos* tab)
 {
@@ -239,19 +212,12 @@ __global__ __launch_bounds__(64) void k_dec_bs_pos(DecBsParams C, unsigned* anyb
     dec_bs_pair(C, anybs, serial, d.item);
 }
 
-// IND (decoder groups): blockIdx.y is a position of the step's table; a position without inter macroblocks is passed by
-template <bool IND = false>
+// a position without inter macroblocks is passed by
 __global__ __launch_bounds__(64) void k_dec_resid(FrameParams P0)
 {
-    DecPosRef dp{};
-    if constexpr (IND) {
-        dp = dec_pos(P0.dectab, blockIdx.y);
-        if (!dp.inter) return;
-    }
-    const FrameParams P = [&] {
-        if constexpr (IND) return dec_view(P0, dp);
-        else return batch_view(P0, blockIdx.y);
-    }();
+    const DecPosRef dp = dec_pos(P0.dectab, blockIdx.y);
+    if (!dp.inter) return;
+    const FrameParams P = dec_view(P0, dp);
     const int lane = threadIdx.x, blk = lane & 15;
     const int first = P.band.row0 * P.mbw, end = first + P.band.rows * P.mbw;
     const int mbi = first + 4 * (int)blockIdx.x + (lane >> 4);

@@ -696,10 +696,11 @@ __global__ __launch_bounds__(128) void k_intra_rows(IntraRowParams R)
 // macroblocks of the row above, which are coded left to right: no cycle.  Pictures without marked macroblocks return at once.
 // ===========================================================================
 // DEC (the decoder peer): the intra macroblocks are those of intra type in the MbInfo the host parser filled (every macroblock
-// of an I picture); they are reconstructed from the given modes and levels.  DEC && IND: the pictures of a decoder group's step.
+// of an I picture); they are reconstructed from the given modes and levels, and the pictures are those of a decoder group's step.
 template <bool DEC, bool IND = false>
 __global__ __launch_bounds__(64) void k_pintra_rows(IntraRowParams R)
 {
+    static_assert(!DEC || IND, "the decoder's pictures are positions of a decoder group's table");
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x;
     __shared__ IntraLds S;
@@ -709,18 +710,18 @@ __global__ __launch_bounds__(64) void k_pintra_rows(IntraRowParams R)
     // step's chain, nearly all of its waves find nothing to do, and each needs ~200 registers to be placed - 2 176 of them per
     // step beside the other instance's motion search (80 registers a wave, six to a SIMD) cost 7 % of the throughput, 272 cost nothing.
     for (int pic = blockIdx.y; pic < R.npic; pic += gridDim.y) {
-    // DEC && IND (decoder groups): the position is a row of the decoder table (dev_common.h DecPos) - its item, ring slots, chroma QP
+    // DEC (decoder groups): the position is a row of the decoder table (dev_common.h DecPos) - its item, ring slots, chroma QP
     // offsets and slice bands; a position without intra macroblocks is passed by
     DecPosRef dp{};
-    if constexpr (DEC && IND) {
+    if constexpr (DEC) {
         dp = dec_pos(R.p.dectab, pic);
         if (!dp.intra) continue;
     }
     const FrameParams P = [&] {
-        if constexpr (DEC && IND) return dec_view(R.p, dp);
+        if constexpr (DEC) return dec_view(R.p, dp);
         else return batch_view<IND>(R.p, pic);
     }();
-    const int item = (DEC && IND) ? dp.item : batch_item<IND>(R.p.itemtab, pic);
+    const int item = DEC ? dp.item : batch_item<IND>(R.p.itemtab, pic);
     if (!DEC && *P.anyintra != P.pic_serial) continue;
     unsigned long long* const handoff = R.handoff + (size_t)item * R.st_handoff;
     const int my = P.band.row0 + blockIdx.x, cs = P.cw / 2;

@@ -1,7 +1,8 @@
 // media_amd/csrc/mi355x_h264.hip -- the C ABI of include/mi355x_h264.h and include/mi355x_h264_dec.h.  The library is this ONE
 // translation unit: the kernels (k_*.h, rgba_kernels.h), host_framing.h (parameter sets, slice header, NAL escaping, tables; no
-// HIP), engine.h (mi355x_h264_encoder), hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side), decoder.h
-// (the decoder peer).  Every entry point below checks its arguments and calls into one of them.  There is no CPU encode path:
+// HIP), engine.h (mi355x_h264_encoder), hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side), dec_group.h
+// (decoder groups) and decoder.h (the decoder peer: a group of one stream).  Every entry point below checks its arguments and
+// calls into one of them.  There is no CPU encode path:
 // without a HIP device create() fails.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -37,8 +38,8 @@ using namespace h264;
 #include "engine.h"
 #include "hub_sched.h"
 #include "hub.h"
-#include "decoder.h"
 #include "dec_group.h"
+#include "decoder.h"
 
 extern "C" {
 
@@ -423,114 +424,6 @@ int mi355x_h264_stream_hub_stats(const mi355x_h264_stream* s, uint64_t* steps, u
     return MI355X_H264_OK;
 }
 
-// ---- the decoder peer (decoder.h) ----
-
-int mi355x_h264_dec_create(int device, mi355x_h264_decoder** out)
-{
-    if (!out) return MI355X_H264_E_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return MI355X_H264_E_NODEVICE;
-    mi355x_h264_decoder* d = new (std::nothrow) mi355x_h264_decoder();
-    if (!d) return MI355X_H264_E_NOMEM;
-    d->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipEventCreateWithFlags(&d->up_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&d->up_done[1], hipEventDisableTiming) != hipSuccess) {
-        delete d;
-        return MI355X_H264_E_HIP;
-    }
-    // the parsers' per-macroblock arrays from now on: pinned (asynchronous uploads); MI355X_H264_DEC_PAGEABLE=1 keeps malloc (measurements)
-    if (!getenv("MI355X_H264_DEC_PAGEABLE")) h264dec::HostMem::use(pinned_alloc, pinned_free);
-    *out = d;
-    return MI355X_H264_OK;
-}
-
-void mi355x_h264_dec_destroy(mi355x_h264_decoder* d)
-{
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    if (d->eng) { (void)dec_wait(d); }
-    for (int k = 0; k < 2; k++)
-        if (d->up_done[k]) { if (d->up_pending[k]) (void)hipEventSynchronize(d->up_done[k]); (void)hipEventDestroy(d->up_done[k]); }
-    if (d->eng) destroy_engine(d->eng);
-    d->mem.free_all();
-    if (d->d_big) (void)hipFree(d->d_big);
-    delete d;
-}
-
-const char* mi355x_h264_dec_last_error(const mi355x_h264_decoder* d) { return d ? d->err : "no decoder"; }
-
-// The C entry point: no exception leaves it (the parser's arrays are std::vectors over pinned memory: an allocation failure
-// arrives as std::bad_alloc), and an access unit that is refused at ANY stage - parser, stream checks, allocation, launch, the
-// time-out of the picture in flight - may have been a reference picture: parser and ring then drop their reference pictures
-// together, so that every P picture is refused until the next IDR picture instead of being predicted from the wrong slot.
-int mi355x_h264_dec_decode(mi355x_h264_decoder* d, const uint8_t* au, size_t len, int* got_picture)
-{
-    if (!d || !au) return MI355X_H264_E_ARG;
-    int rc;
-    try {
-        rc = dec_decode_unit(d, au, len, got_picture);
-    } catch (const std::bad_alloc&) {
-        rc = set_err(d->err, MI355X_H264_E_NOMEM, "out of host memory while parsing the access unit");
-    } catch (const std::exception& ex) {
-        rc = set_err(d->err, MI355X_H264_E_NOMEM, "access unit refused: %s", ex.what());
-    }
-    if (rc != MI355X_H264_OK) {
-        d->have_refs = 0;
-        d->parser.lose_refs();
-        if (got_picture) *got_picture = 0;
-    }
-    return rc;
-}
-
-int mi355x_h264_dec_sync(mi355x_h264_decoder* d)
-{
-    if (!d) return MI355X_H264_E_ARG;
-    if (!d->eng) return MI355X_H264_OK;
-    if (hipSetDevice(d->device) != hipSuccess) return set_err(d->err, MI355X_H264_E_HIP, "hipSetDevice");
-    return dec_wait(d);
-}
-
-int mi355x_h264_dec_picture_info(const mi355x_h264_decoder* d, int* width, int* height, int* coded_width, int* coded_height)
-{
-    if (!d || d->last < 0) return MI355X_H264_E_ARG;
-    if (width) *width = d->width;
-    if (height) *height = d->height;
-    if (coded_width) *coded_width = 16 * d->mbw;
-    if (coded_height) *coded_height = 16 * d->mbh;
-    return MI355X_H264_OK;
-}
-
-int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder* d, uint8_t* dst, size_t cap) { return dec_read(d, dst, cap, false); }
-int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder* d, void* d_dst, size_t cap) { return dec_read(d, d_dst, cap, true); }
-
-int64_t mi355x_h264_dec_read(mi355x_h264_decoder* d, int layout, int row_align, void* dst, size_t cap, int to_device, mi355x_h264_dec_out_pic* pic)
-{
-    return dec_read_out(d, layout, row_align, dst, cap, to_device != 0, pic);
-}
-
-// coded-size planes of the last picture (test hook: compared with the oracle decoder's planes)
-int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder* d, int plane, void* dst, size_t cap)
-{
-    if (!d || !dst || d->last < 0 || plane < 0 || plane > 2) return MI355X_H264_E_ARG;
-    const mi355x_h264_encoder* e = d->eng;
-    const size_t n = (size_t)e->cw * e->ch / (plane ? 4 : 1);
-    if (cap < n) return MI355X_H264_E_ARG;
-    if (hipSetDevice(d->device) != hipSuccess) return MI355X_H264_E_HIP;
-    if (const int wrc = dec_wait(d)) return wrc;
-    if (hipMemcpy(dst, e->d_planes[d->last][plane], n, hipMemcpyDeviceToHost) != hipSuccess) return MI355X_H264_E_HIP;
-    return (int64_t)n;
-}
-
-int mi355x_h264_dec_timing(const mi355x_h264_decoder* d, uint64_t* pictures, double* parse_ms, double* gpu_ms)
-{
-    if (!d) return MI355X_H264_E_ARG;
-    if (pictures) *pictures = d->pictures;
-    if (parse_ms) *parse_ms = d->parse_ms;
-    if (gpu_ms) *gpu_ms = d->gpu_ms;
-    return MI355X_H264_OK;
-}
-
 // ---- decoder groups (dec_group.h) ----
 
 int mi355x_h264_dec_group_create(int device, int streams, mi355x_h264_dec_group** out)
@@ -555,8 +448,8 @@ int mi355x_h264_dec_group_create(int device, int streams, mi355x_h264_dec_group*
     // pictures the row wavefronts hold at a time; a step of more walks to the rest (k_pintra_rows, k_deblock_rows)
     g->intra_slots = env_int("MI355X_H264_DEC_INTRA_SLOTS", 1, DEC_GROUP_MAX_STREAMS, 32);
     g->filter_slots = env_int("MI355X_H264_DEC_FILTER_SLOTS", 1, DEC_GROUP_MAX_STREAMS, 32);
-    // the parse threads: a number of the group's own, never the machine's
-    g->sched.start(env_int("MI355X_H264_DEC_PARSE_THREADS", 1, DEC_GROUP_MAX_THREADS, std::min(streams, 8)));
+    // the parse threads: a number of the group's own, never the machine's; one stream is parsed by the caller (dec_group_sched.h)
+    if (streams > 1) g->sched.start(env_int("MI355X_H264_DEC_PARSE_THREADS", 1, DEC_GROUP_MAX_THREADS, std::min(streams, 8)));
     *out = g;
     return MI355X_H264_OK;
 }
@@ -633,10 +526,10 @@ int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group* g, int stream, 
     const mi355x_h264_encoder* e = g->eng;
     const size_t n = (size_t)e->cw * e->ch / (plane ? 4 : 1);
     if (cap < n) return MI355X_H264_E_ARG;
-    if (hipSetDevice(g->device) != hipSuccess) return MI355X_H264_E_HIP;
+    if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
     if (const int wrc = dg_wait(g)) return wrc;
     const uint8_t* src = e->d_plane_base[plane] + (size_t)stream * (plane ? e->st_c : e->st_y) + (size_t)g->st[stream].last * (plane ? e->st_ring_c : e->st_ring_y);
-    if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return MI355X_H264_E_HIP;
+    if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipMemcpy");
     return (int64_t)n;
 }
 
@@ -654,6 +547,81 @@ int64_t mi355x_h264_dec_group_read_all(mi355x_h264_dec_group* g, int layout, int
 }
 int mi355x_h264_dec_group_set_output(mi355x_h264_dec_group* g, int layout, int row_align) { return dg_set_output(g, layout, row_align); }
 int mi355x_h264_dec_group_output(mi355x_h264_dec_group* g, int back, const uint8_t** data, mi355x_h264_dec_out_pic* pics) { return dg_output(g, back, data, pics); }
+
+// ---- the decoder peer (decoder.h): a group of one stream, every call forwarded with stream 0 ----
+
+int mi355x_h264_dec_create(int device, mi355x_h264_decoder** out)
+{
+    if (!out) return MI355X_H264_E_ARG;
+    *out = nullptr;
+    mi355x_h264_decoder* d = new (std::nothrow) mi355x_h264_decoder();
+    if (!d) return MI355X_H264_E_NOMEM;
+    const int rc = mi355x_h264_dec_group_create(device, 1, &d->g);
+    if (rc != MI355X_H264_OK) { delete d; return rc; }
+    d->g->resize = true;   // an IDR picture of another coded size re-makes the geometry
+    *out = d;
+    return MI355X_H264_OK;
+}
+
+void mi355x_h264_dec_destroy(mi355x_h264_decoder* d)
+{
+    if (!d) return;
+    mi355x_h264_dec_group_destroy(d->g);
+    delete d;
+}
+
+const char* mi355x_h264_dec_last_error(const mi355x_h264_decoder* d) { return d ? d->err : "no decoder"; }
+
+// An access unit that is refused at ANY stage - parser, stream checks, allocation, launch, the time-out of the picture in flight -
+// may have been a reference picture: the group drops the parser's and the ring's reference pictures together (dg_drop_refs), so
+// that every P picture is refused until the next IDR picture instead of being predicted from the wrong slot.
+int mi355x_h264_dec_decode(mi355x_h264_decoder* d, const uint8_t* au, size_t len, int* got_picture)
+{
+    if (!d || !au) return MI355X_H264_E_ARG;
+    mi355x_h264_dec_group* g = d->g;
+    int got = 0, rc = MI355X_H264_OK;
+    const int64_t before = g->step_serial;
+    const int grc = mi355x_h264_dec_group_decode(g, &au, &len, &got, &rc);
+    if (g->step_serial != before) { d->parse_ms += g->last_ms[0]; d->gpu_ms += g->last_ms[1]; }
+    snprintf(d->err, sizeof(d->err), "%s", grc ? g->err : g->st[0].err);
+    if (got_picture) *got_picture = got;
+    return grc ? grc : rc;
+}
+
+int mi355x_h264_dec_sync(mi355x_h264_decoder* d) { return d ? dec_ret(d, mi355x_h264_dec_group_sync(d->g)) : MI355X_H264_E_ARG; }
+
+int mi355x_h264_dec_picture_info(const mi355x_h264_decoder* d, int* width, int* height, int* coded_width, int* coded_height)
+{
+    return d ? mi355x_h264_dec_group_picture_info(d->g, 0, width, height, coded_width, coded_height) : MI355X_H264_E_ARG;
+}
+
+int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder* d, uint8_t* dst, size_t cap) { return d ? dec_ret(d, dg_read(d->g, 0, dst, cap, false)) : MI355X_H264_E_ARG; }
+int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder* d, void* d_dst, size_t cap) { return d ? dec_ret(d, dg_read(d->g, 0, d_dst, cap, true)) : MI355X_H264_E_ARG; }
+
+// the last picture in a layout: the group's call with one stream; `serial` counts the decoder's pictures, and the picture is
+// always the one the last successful decode call produced
+int64_t mi355x_h264_dec_read(mi355x_h264_decoder* d, int layout, int row_align, void* dst, size_t cap, int to_device, mi355x_h264_dec_out_pic* pic)
+{
+    if (!d) return MI355X_H264_E_ARG;
+    const int64_t n = dec_ret(d, dg_read_all(d->g, layout, row_align, dst, cap, to_device != 0, pic));
+    if (n >= 0) { pic->fresh = 1; pic->serial = (int64_t)d->g->st[0].pictures; }
+    return n;
+}
+
+// coded-size planes of the last picture (test hook: compared with the oracle decoder's planes)
+int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder* d, int plane, void* dst, size_t cap)
+{
+    return d ? dec_ret(d, mi355x_h264_dec_group_debug_plane(d->g, 0, plane, dst, cap)) : MI355X_H264_E_ARG;
+}
+
+int mi355x_h264_dec_timing(const mi355x_h264_decoder* d, uint64_t* pictures, double* parse_ms, double* gpu_ms)
+{
+    if (!d) return MI355X_H264_E_ARG;
+    if (pictures) *pictures = d->g->st[0].pictures;
+    if (parse_ms) *parse_ms = d->parse_ms;
+    if (gpu_ms) *gpu_ms = d->gpu_ms;
+    return MI355X_H264_OK;
+}
 
 // ---- the host parser alone (no GPU): what it recovered from the last access unit, for the CPU tests ----
 struct mi355x_h264_parser { h264dec::Parser p; };
@@ -692,7 +660,7 @@ int64_t mi355x_h264_parser_read(const mi355x_h264_parser* p, int what, void* dst
         case 0: src = c.mb.data(); n = c.mb.size() * sizeof(h264dec::MbRec); break;
         case 1: src = c.mvq.data(); n = c.mvq.size() * sizeof(int16_t); break;
         case 2: src = c.aux.data(); n = c.aux.size(); break;
-        case 3: {   // the level lists as int16 (what k_dec_widen + k_dec_patch make of levels8 + big on the GPU)
+        case 3: {   // the level lists as int16 (what k_dec_widen_pos + k_dec_patch make of levels8 + big on the GPU)
             n = c.levels8.size() * sizeof(int16_t);
             if (cap < n) return -1;
             int16_t* o = (int16_t*)dst;
