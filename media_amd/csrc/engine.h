@@ -501,15 +501,19 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             // two macroblock rows per wave (k_deblock_pairs) for lockstep batches of pictures of one slice; else one row per wave
             const bool pairs = e->pair_filter && T.n >= e->pair_min_batch && e->nsl == 1 && e->b_rows == e->mbh;
             const unsigned grid_x = pairs ? (unsigned)((e->b_rows + 1) / 2) : (unsigned)e->b_rows;
-            auto filter = [&](bool bs4, unsigned at_a_time) {
+            auto filter = [&](bool bs4, unsigned at_a_time) {   // (bs4 = false: the stream hub's P steps only)
                 const dim3 grid(grid_x, std::min(G, at_a_time));
                 if (pairs) { if (bs4) LAUNCH2(ind, (k_deblock_pairs<true, true>), (k_deblock_pairs<true, false>), grid, dim3(64), st, R);
-                             else LAUNCH2(ind, (k_deblock_pairs<false, true>), (k_deblock_pairs<false, false>), grid, dim3(64), st, R); }
+                             else hipLaunchKernelGGL((k_deblock_pairs<false, true>), grid, dim3(64), 0, st, R); }
                 else { if (bs4) LAUNCH2(ind, (k_deblock_rows<true, false, true>), (k_deblock_rows<true, false, false>), grid, dim3(64), st, R);
-                       else LAUNCH2(ind, (k_deblock_rows<false, false, true>), (k_deblock_rows<false, false, false>), grid, dim3(64), st, R); }
+                       else hipLaunchKernelGGL((k_deblock_rows<false, false, true>), grid, dim3(64), 0, st, R); }
             };
             if (idr) { R.need_intra = 0; filter(true, G); }
-            else {   // P pictures: the form without the bS 4 filter, or - when the picture has intra macroblocks - the one with it
+            else if (!ind) {   // P pictures: ONE launch, every picture resident and taken in the form it needs (k_deblock_rows_p)
+                R.need_intra = 0;
+                if (pairs) hipLaunchKernelGGL(k_deblock_pairs_p, dim3(grid_x, G), dim3(64), 0, st, R);
+                else hipLaunchKernelGGL(k_deblock_rows_p, dim3(grid_x, G), dim3(64), 0, st, R);
+            } else {   // P pictures of the stream hub: the form without the bS 4 filter, or - when the picture has intra macroblocks - the one with it
                 // (while the recent P pictures had next to none, the second launch holds one picture at a time: see k_deblock_rows)
                 R.need_intra = -1; filter(false, G);
                 R.need_intra = 1; filter(true, e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u);

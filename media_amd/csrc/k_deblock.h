@@ -5,6 +5,7 @@
 //   k_deblock_pairs one launch, one persistent wave per TWO macroblock rows: the default from a lockstep batch of 8 pictures on
 //   k_deblock_rows  one launch, one persistent wave per macroblock row: smaller batches, pictures of several slices, the
 //                   latency mode, the decoder peer.  Both are built from one set of per-macroblock steps (db_* further down).
+//   k_deblock_pairs_p, k_deblock_rows_p  the encoder's P steps: the same two, each picture with or without the bS 4 filter
 //   k_deblock_diag  (first form; MI355X_H264_DIAG=1) one wavefront per macroblock, one launch
 //                   per wavefront step mx + 2*my == s
 //
@@ -204,8 +205,9 @@ struct DbRowParams {
     const unsigned* anyintra;   // [item] == pic_serial: a P picture with intra macroblocks (bS 3 / 4 edges)
     unsigned pic_serial;
     int npic;                // pictures of the step (gridDim.y of them at a time)
-    int need_intra;          // P pictures are launched in both forms: < 0 this form runs when the picture has no intra
-                             // macroblock, > 0 when it has, 0 = unconditional (IDR)
+    int need_intra;          // the stream hub and decoder groups launch P steps in both forms: < 0 this form runs when the picture
+                             // has no intra macroblock, > 0 when it has; 0 = unconditional (IDR steps, and k_deblock_*_p which
+                             // choose the form themselves)
     // lockstep batch strides (gridDim.y items)
     size_t st_y, st_c, st_handoff;   // bytes, bytes, u64 words
     int st_mb;
@@ -262,6 +264,7 @@ enum { DR_LP = 40, DR_CP = 24 };  // LDS pitches; luma tile cols -16..15 (+4 pad
 // after the first (DR_CPS) - 32 lanes, 32 banks.  (Separate arrays had put all 32 lines on the 16 odd banks, the two chroma
 // planes partly on each other's: 2- and 3-way conflicts on every access of the phase)
 enum { DR_CB = 4 * 201, DR_CPS = 4 * 144, DR_TILE = DR_CB + 2 * DR_CPS + 12 };
+enum { DR_PAIR_TILE = (DR_TILE + 127) / 128 * 128 };   // the pair form's two tiles lie a multiple of 32 dwords apart: the same banks
 // sample (r, c) of a tile's luma / of its chroma plane pl; (0, 0) = first sample of the current macroblock, the previous one to its left
 __device__ __forceinline__ uint8_t* db_y(uint8_t* const tile, const int r, const int c) { return tile + (r + 4) * DR_LP + c + 16; }
 __device__ __forceinline__ uint8_t* db_c(uint8_t* const tile, const int pl, const int r, const int c) { return tile + DR_CB + pl * DR_CPS + (r + 4) * DR_CP + c + 8; }
@@ -441,6 +444,18 @@ __device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64*
         if (need) g = AT_LOAD(addr);
     }
 }
+// The granule of the current macroblock was requested one macroblock ahead.  Where that copy is stale (the row above had not
+// published yet) it is requested again HERE, at the top of the iteration, so that the round trip runs beside the vertical edges
+// and not inside db_wait_tags behind them.  need: the wait's own predicate.  One ballot and a wave-uniform branch: nothing is
+// issued when every tag was fresh.  The load stays where it is written (the compiler barrier).
+__device__ __forceinline__ void db_rerequest(const bool need, u64& g, const u64* const addr, const unsigned serial)
+{
+    const bool bad = need && (unsigned)(g >> 32) != serial;
+    if (__ballot(bad) != 0ull) {
+        if (bad) g = AT_LOAD(addr);
+        asm volatile("" ::: "memory");
+    }
+}
 
 // ===========================================================================
 // Row form: one wave per macroblock row; all 64 lanes move samples (one luma dword each), lanes 0..31 filter.
@@ -450,16 +465,15 @@ __device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64*
 // the encoder's form: one set per picture, prepared on the host.
 // ===========================================================================
 template <bool BS4, bool PERMB, bool IND>
-__device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const int pos)
+__device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const int pos, const int lane, uint8_t* const s_y)
 {
     DbParams D; u64* handoff; const uint32_t* bsw;
     if (!db_picture_view<PERMB, IND>(R, pos, D, handoff, bsw)) return;
-    const int lane = threadIdx.x, my = R.row0 + blockIdx.x, cs = D.cw / 2;   // (row0: first row of this instance's band)
+    const int my = R.row0 + blockIdx.x, cs = D.cw / 2;   // (row0: first row of this instance's band)
     // a slice's rows form a wavefront of their own: its first row waits for nobody (no edge to the slice above is
     // filtered), its last row stores all sixteen sample rows itself
     const bool first_row = !D.sl.has_top(my);
     const bool last_row = my == D.mbh - 1 || !D.sl.has_top(my + 1);
-    __shared__ __attribute__((aligned(16))) uint8_t s_y[DR_TILE];
     bool timed_out = false;
     const int yr = lane >> 2, yc4 = (lane & 3) * 4;                                   // luma dword owned by this lane
     const int cpl_l = (lane >> 4) & 1, cr_l = (lane >> 1) & 7, cc4 = (lane & 1) * 4;  // chroma dword (lanes < 32)
@@ -544,6 +558,8 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             // 2. current macroblock into LDS
             dw(db_y(s_y, yr, yc4)) = cur_y;
             if (lane < 32) dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
+            // a granule that came stale is asked for again before anything else: it is the oldest request when the wait looks at it
+            if (!first_row) db_rerequest(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial);
             // requests for the next macroblock leave now and are collected after the filter
             if (mx + 1 < D.mbw) prefetch(mx + 1);
             if (PERMB) {
@@ -584,15 +600,36 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     if (timed_out && lane == 0) *R.err = 1u;  // pinned host word, read after the picture's event
 }
 // The kernels: workgroup (row, y) filters its row of pictures y, y + gridDim.y, ... of the step's R.npic pictures.  A launch whose
-// pictures nearly all return at once - the bS 4 form on P steps of content without intra macroblocks - is made with gridDim.y = 1: placing
-// a thousand 120-register waves beside the other instance's kernels for nothing is what costs, not the walk (see k_pintra_rows).
+// pictures nearly all return at once - the stream hub's bS 4 launch on P steps of content without intra macroblocks - is made with
+// gridDim.y = 1: placing a thousand 120-register waves beside the other instance's kernels for nothing is what costs, not the walk
+// (see k_pintra_rows).
 template <bool BS4, bool PERMB = false, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 {
     static_assert(!PERMB || IND, "thresholds per edge: the pictures of a decoder group's step");
+    __shared__ __attribute__((aligned(16))) uint8_t s_y[DR_TILE];   // (the kernel's, not the picture function's: k_deblock_rows_p inlines two of those)
     // dependency-bound: when a throughput kernel of another stream shares the SIMD, this wave issues first
     __builtin_amdgcn_s_setprio(3);
-    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) deblock_rows_picture<BS4, PERMB, IND>(R, pos);
+    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) deblock_rows_picture<BS4, PERMB, IND>(R, pos, (int)threadIdx.x, s_y);
+}
+// P steps of the encoder's own batches: ONE launch, every picture in the form it needs - with the bS 4 filter when the picture holds intra
+// macroblocks (k_pintra_rows' flag), without it otherwise.  The choice is a scalar compare per picture and both bodies are inlined;
+// R.need_intra is 0.  (Two launches, one per form, each returning at once from the other's pictures, were a kernel boundary and a
+// grid of waves to place on every P step for a launch that on ordinary content finds nothing.)
+__device__ __forceinline__ bool db_picture_has_intra(const DbRowParams& R, const int pos)
+{
+    return R.anyintra[batch_item<false>(R.itemtab, pos)] == R.pic_serial;
+}
+__global__ __launch_bounds__(64) void k_deblock_rows_p(DbRowParams R)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_y[DR_TILE];
+    __builtin_amdgcn_s_setprio(3);
+    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) {
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        if (db_picture_has_intra(R, pos)) deblock_rows_picture<true, false, false>(R, pos, lane, s_y);
+        else deblock_rows_picture<false, false, false>(R, pos, lane, s_y);
+    }
 }
 
 
@@ -619,11 +656,11 @@ __global__ __launch_bounds__(64) void k_deblock_rows(DbRowParams R)
 // the decoder use the row form.  tests/test_gpu_parity.py runs both forms at batch 8 and this one forced on single pictures.
 // ===========================================================================
 template <bool BS4, bool IND>
-__device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, const int pos)
+__device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, const int pos, const int lane, uint8_t (* const s_yy)[DR_PAIR_TILE], uint32_t (* const s_ring)[24])
 {
     DbParams D; u64* handoff; const uint32_t* bsw;
     if (!db_picture_view<false, IND>(R, pos, D, handoff, bsw)) return;
-    const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31, cs = D.cw / 2;
+    const int half = lane >> 5, hl = lane & 31, cs = D.cw / 2;
     const int rowA = R.row0 + 2 * (int)blockIdx.x, rowB = rowA + 1;
     const bool hasB = rowB < D.mbh;                 // (an odd number of rows: the last wave has an upper row only)
     const int my = half ? (hasB ? rowB : rowA) : rowA;
@@ -631,8 +668,6 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
     const bool first_row = half == 0 && rowA == 0;  // (one slice: only picture row 0 has nothing above)
     const bool last_row = my == D.mbh - 1;
     const bool from_lds = half == 1;                // the lower row's top apron comes from the upper row through LDS
-    __shared__ __attribute__((aligned(16))) uint8_t s_yy[2][(DR_TILE + 127) / 128 * 128];   // one tile per row of the pair (a multiple of 32 dwords apart: the same banks)
-    __shared__ __attribute__((aligned(16))) uint32_t s_ring[2][24];   // bottom rows of the upper row's macroblock (parity of its index): 16 luma + 8 chroma dwords
     uint8_t* const s_y = s_yy[half];
     bool timed_out = false;
     // luma dwords owned by this lane: two of the 64 of a macroblock (rows yr0 and yr0 + 8); chroma dword as in the row form
@@ -703,6 +738,8 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
             dw(db_y(s_y, yr0 + 8, yc4)) = cur_y1;
             dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
         }
+        // (upper row) a granule that came stale is asked for again before anything else
+        db_rerequest(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial);
         {   // requests for this lane's next macroblock (clamped: the loads of a finished or not yet started row are harmless)
             const int nx = mx + 1 < 0 ? 0 : (mx + 1 > last_mx ? last_mx : mx + 1);
             prefetch(nx);
@@ -736,8 +773,22 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
 template <bool BS4, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_pairs(DbRowParams R)
 {
+    __shared__ __attribute__((aligned(16))) uint8_t s_yy[2][DR_PAIR_TILE];   // one tile per row of the pair
+    __shared__ __attribute__((aligned(16))) uint32_t s_ring[2][24];   // bottom rows of the upper row's macroblock (parity of its index): 16 luma + 8 chroma dwords
     __builtin_amdgcn_s_setprio(3);
-    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) deblock_pairs_picture<BS4, IND>(R, pos);
+    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) deblock_pairs_picture<BS4, IND>(R, pos, (int)threadIdx.x, s_yy, s_ring);
+}
+__global__ __launch_bounds__(64) void k_deblock_pairs_p(DbRowParams R)   // P steps: see k_deblock_rows_p
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_yy[2][DR_PAIR_TILE];
+    __shared__ __attribute__((aligned(16))) uint32_t s_ring[2][24];
+    __builtin_amdgcn_s_setprio(3);
+    for (int pos = blockIdx.y; pos < R.npic; pos += gridDim.y) {
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        if (db_picture_has_intra(R, pos)) deblock_pairs_picture<true, false>(R, pos, lane, s_yy, s_ring);
+        else deblock_pairs_picture<false, false>(R, pos, lane, s_yy, s_ring);
+    }
 }
 
 }  // namespace h264

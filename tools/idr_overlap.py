@@ -7,7 +7,7 @@ f = glob.glob(sys.argv[1] + "/stats/*/*kernel_trace.csv")[-1]
 rows = list(csv.DictReader(open(f)))
 iv = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if "k_intra_rows" in r["Kernel_Name"] and r["Grid_Size_Y"] != "1"]
 print("IDR launches", len(iv), "avg %.1f us" % (sum(b - a for a, b in iv) / max(1, len(iv)) / 1e3))
-for name in ("k_me", "k_tq<", "k_mvpred", "k_cavlc<false", "k_cavlc<true", "k_deblock_pairs<false", "k_deblock_rows<false", "k_pintra_rows", "k_skip_scan", "k_bit_scan"):
+for name in ("k_me", "k_tq<", "k_mvpred", "k_cavlc<false", "k_cavlc<true", "k_deblock_pairs_p", "k_deblock_rows_p", "k_pintra_rows", "k_skip_scan", "k_bit_scan"):
     a, b = [], []
     for r in rows:
         if name in r["Kernel_Name"] and r["Grid_Size_Y"] != "1":

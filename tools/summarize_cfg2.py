@@ -51,5 +51,5 @@ out["note"] = ("FETCH_SIZE counts 64-byte requests at 64 B and larger ones at ha
                "kernel exists - every kernel reads the interleaved chroma plane itself; bytes and GB/s are given for the kernels whose launches all have one shape")
 json.dump(out, open("profiles/r03_cfg2_nv12_1080p60_main.json", "w"), indent=1)
 print(json.dumps({k: v for k, v in out.items() if k != "kernels"}, indent=1)[:600])
-for k in ("k_me<false>", "k_tq<false>", "k_intra_rows<false>", "k_deblock_pairs<false, false>"):
+for k in ("k_me<false>", "k_tq<false>", "k_intra_rows<false>", "k_deblock_pairs_p"):   # (k_deblock_pairs_p: the P steps' filter, before it k_deblock_pairs<false, false>)
     print(k, out["kernels"].get(k))
