@@ -431,30 +431,53 @@ __device__ __forceinline__ void db_store_apron(const DbParams& D, uint8_t* const
         dw(p) = dw(db_tile_at(tile, c, pl, r, col, 0, -1));
     });
 }
-// Wait until the granule g of every lane that needs one carries this picture's tag, re-reading it from addr.  Bounded: a timeout
-// sets timed_out, and no later wait of the wave spins at all.
-__device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64* const addr, const unsigned serial, bool& timed_out)
+// -DDB_AB_COUNT (measurement build, make ab): what the macroblock steps wait on.  Per wave in registers, added once at the wave's
+// end with vector atomic adds: iterations that have a wait, those whose prefetched tag was stale, those still stale at the first
+// look (the same number since the re-request left), spin passes.  The host reads and clears the four words with mi355x_h264_db_counts().
+struct DbCount { unsigned iters, stale, still_stale, spins; };
+#ifdef DB_AB_COUNT
+__device__ unsigned g_db_count[4];
+__device__ __forceinline__ void db_count_flush(const DbCount& c, const int lane)
 {
+    if (lane == 0 && c.iters) {
+        atomicAdd(&g_db_count[0], c.iters); atomicAdd(&g_db_count[1], c.stale);
+        atomicAdd(&g_db_count[2], c.still_stale); atomicAdd(&g_db_count[3], c.spins);
+    }
+}
+}  // namespace h264
+extern "C" __attribute__((visibility("default"))) int mi355x_h264_db_counts(unsigned out[4], int clear)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h264::g_db_count), 4 * sizeof(unsigned)) != hipSuccess) return -1;
+    const unsigned zero[4] = {0, 0, 0, 0};
+    if (clear && hipMemcpyToSymbol(HIP_SYMBOL(h264::g_db_count), zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+namespace h264 {
+#define DB_COUNT(x) x
+#else
+#define DB_COUNT(x)
+#endif
+// Wait until the granule g of every lane that needs one carries this picture's tag, re-reading it from addr.  The FIRST look
+// stands in front of the spin and is at the prefetched copy, which consume() has waited for an iteration ago: a wave whose
+// granules came fresh reaches the horizontal edges without any wait for memory - in particular without the one for this
+// iteration's own publish, whose write-through stores were issued a few dozen instructions earlier (a spin loop that starts
+// with the compare gets s_waitcnt vmcnt(0) at its head, because g may come from the reload, and every wave ran into it in
+// every iteration).  Only a wave that has to spin waits for everything (the reload's vmcnt(0)), and it is waiting anyway.
+// Bounded: a timeout sets timed_out, and no later wait of the wave spins at all.
+// (Asking again for a stale granule at the top of the iteration, ahead of the vertical edges, was measured beside this and
+// dropped: DESIGN.md section 11.)
+__device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64* const addr, const unsigned serial, bool& timed_out, DbCount& cnt)
+{
+    const bool stale = __ballot(need && (unsigned)(g >> 32) != serial) != 0ull;
+    DB_COUNT(cnt.iters++; if (stale) { cnt.stale++; cnt.still_stale++; })
+    if (timed_out || !stale) return;
     unsigned spins = 0;
-    while (!timed_out) {
-        const bool bad = need && (unsigned)(g >> 32) != serial;
-        if (__ballot(bad) == 0ull) break;
+    do {
         if (++spins > (1u << 20)) { timed_out = true; break; }
         __builtin_amdgcn_s_sleep(1);
         if (need) g = AT_LOAD(addr);
-    }
-}
-// The granule of the current macroblock was requested one macroblock ahead.  Where that copy is stale (the row above had not
-// published yet) it is requested again HERE, at the top of the iteration, so that the round trip runs beside the vertical edges
-// and not inside db_wait_tags behind them.  need: the wait's own predicate.  One ballot and a wave-uniform branch: nothing is
-// issued when every tag was fresh.  The load stays where it is written (the compiler barrier).
-__device__ __forceinline__ void db_rerequest(const bool need, u64& g, const u64* const addr, const unsigned serial)
-{
-    const bool bad = need && (unsigned)(g >> 32) != serial;
-    if (__ballot(bad) != 0ull) {
-        if (bad) g = AT_LOAD(addr);
-        asm volatile("" ::: "memory");
-    }
+    } while (__ballot(need && (unsigned)(g >> 32) != serial) != 0ull);
+    DB_COUNT(cnt.spins += spins;)
 }
 
 // ===========================================================================
@@ -501,15 +524,19 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     int qp_left = 0;
 
     // Software pipeline: the samples, boundary strengths and hand-off granules of macroblock mx+1 are
-    // requested (straight-line, unconditional loads) after macroblock mx has been put into LDS, travel
-    // while mx is filtered, and are waited for BEFORE this iteration's stores are issued, so no iteration
-    // ever waits for its own stores (vmcnt counts loads and stores together, in order).
+    // requested (straight-line, unconditional loads; past the end of the row the last macroblock's once more) after
+    // macroblock mx has been put into LDS, and travel while mx is filtered.  vmcnt counts loads and stores together, in
+    // order, and this iteration's publish is issued BEHIND them, between the vertical edges: so the one wait for memory in
+    // front of the horizontal edges (db_wait_tags) looks at a copy of the granule that is older than the publish, and the
+    // loads are collected after the horizontal edges (consume), by when the stores' acknowledgements have had that phase to
+    // come back.  No macroblock step waits for its own stores unless it has to spin for the row above anyway.
     uint32_t pf_y = 0, pf_c = 0;
     uint4 pf_b0 = {0, 0, 0, 0}, pf_b1 = pf_b0;
     u64 pf_g = 0;
     const int grow = first_row ? my : my - 1;      // a first row reads (and ignores) its own slots
     const int glane = lane < 24 ? lane : lane - 24 < 24 ? lane - 24 : lane - 48;
-    auto prefetch = [&](int mx) {
+    const int last_mx = D.mbw - 1;
+    auto prefetch = [&](int mx) {   // mx clamped by the caller into 0 .. mbw - 1
         pf_y = *(const uint32_t*)(D.pl[0] + (size_t)(16 * my + yr) * D.cw + 16 * mx + yc4);
         pf_c = *(const uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * mx + cc4);   // lanes >= 32 mirror lanes < 32
         const uint4* b = (const uint4*)(bsw + ((size_t)my * D.mbw + mx) * 8);
@@ -528,12 +555,13 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     uint32_t cur_y = pf_y, cur_c = pf_c, cur_q = pf_q;
     uint4 b0 = pf_b0, b1 = pf_b1;
     u64 g = pf_g;
+    DbCount cnt = {0, 0, 0, 0};
 
     // the previous macroblock is final with respect to this row once the current one's LEFT edge has been filtered (its
     // other vertical edges and its horizontal edges do not touch it): store / publish it.  Issued between the left edge and
-    // edges 1..3, so that the row below gets it as early as 8.7 allows and the stores' acknowledgements (the agent-scope
-    // granule stores go all the way to the memory side; vmcnt retires in order) have the rest of the iteration to come
-    // back before the next wait for loads.
+    // edges 1..3, so that the row below gets it as early as 8.7 allows.  The stores' acknowledgements (the agent-scope
+    // granule stores go all the way to the memory side; vmcnt retires in order) have edges 1..3 AND the horizontal edges to
+    // come back: db_wait_tags between the two does not wait for them (see there), the next full wait is consume().
     auto store_prev = [&](const int mx, const bool have_cur) {
         if (mx > 0) {
             const int pmx = mx - 1;
@@ -558,10 +586,9 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             // 2. current macroblock into LDS
             dw(db_y(s_y, yr, yc4)) = cur_y;
             if (lane < 32) dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
-            // a granule that came stale is asked for again before anything else: it is the oldest request when the wait looks at it
-            if (!first_row) db_rerequest(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial);
-            // requests for the next macroblock leave now and are collected after the filter
-            if (mx + 1 < D.mbw) prefetch(mx + 1);
+            // requests for the next macroblock leave now and are collected after the filter (clamped: the same loads
+            // whatever the position in the row; those of the last macroblock again are harmless)
+            prefetch(mx + 1 > last_mx ? last_mx : mx + 1);
             if (PERMB) {
                 const int qc = (int)(cur_q & 255u), qt = (int)(cur_q >> 8);
                 thr = thresholds(qc, qc);
@@ -582,7 +609,7 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             // the top apron is needed from here on and not before (the vertical edges touch rows 0..15 only): wait until
             // every granule of the macroblock above carries this picture's tag
             if (!first_row) {
-                db_wait_tags(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out);
+                db_wait_tags(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out, cnt);
                 db_put_apron(s_y, lane, (uint32_t)g);
             }
             wave_sync();
@@ -598,6 +625,7 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;  // pinned host word, read after the picture's event
+    DB_COUNT(db_count_flush(cnt, lane);)
 }
 // The kernels: workgroup (row, y) filters its row of pictures y, y + gridDim.y, ... of the step's R.npic pictures.  A launch whose
 // pictures nearly all return at once - the stream hub's bS 4 launch on P steps of content without intra macroblocks - is made with
@@ -702,6 +730,7 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
     uint32_t cur_y0 = pf_y0, cur_y1 = pf_y1, cur_c = pf_c;
     uint4 b0 = pf_b0, b1 = pf_b1;
     u64 g = pf_g;
+    DbCount cnt = {0, 0, 0, 0};
 
     // the previous macroblock of this lane's row is final for the row: rows 0..11 (all 16 of a last row) to the picture, rows
     // 12..15 handed down - the upper row into the LDS ring, the lower row as global granules for the next pair
@@ -738,8 +767,6 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
             dw(db_y(s_y, yr0 + 8, yc4)) = cur_y1;
             dw(db_c(s_y, cpl_l, cr_l, cc4)) = cur_c;
         }
-        // (upper row) a granule that came stale is asked for again before anything else
-        db_rerequest(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial);
         {   // requests for this lane's next macroblock (clamped: the loads of a finished or not yet started row are harmless)
             const int nx = mx + 1 < 0 ? 0 : (mx + 1 > last_mx ? last_mx : mx + 1);
             prefetch(nx);
@@ -757,7 +784,7 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
         wave_sync();   // (the ring slot written above is read by the other half's lanes)
         // top apron, needed by the horizontal edges only: the upper row waits for the previous pair's granules, the lower row
         // takes the ring slot the upper row has just filled
-        db_wait_tags(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out);
+        db_wait_tags(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out, cnt);
         if (have_cur && !first_row && hl < 24) db_put_apron(s_y, hl, from_lds ? s_ring[mx & 1][hl] : (uint32_t)g);
         wave_sync();
         db_horizontal<BS4>(L, b1, h_on, thr, thr);
@@ -769,6 +796,7 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;
+    DB_COUNT(db_count_flush(cnt, lane);)
 }
 template <bool BS4, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_pairs(DbRowParams R)
