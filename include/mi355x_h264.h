@@ -234,11 +234,23 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder *enc, const void *mbinfo, 
  * device) deliver at about the same time: ONE lockstep launch sequence per step instead of one per stream, every picture with
  * its own QP, picture type, frame_num and reference pictures.  mi355x_h264_stream_encode is synchronous and may be called from
  * one thread per stream concurrently; the output is bit-for-bit what mi355x_h264_create / mi355x_h264_encode with the same
- * config and the same QP sequence produce (tests/test_gpu_streams.py).  One reference picture (refs <= 1).
+ * config and the same QP sequence produce (tests/test_gpu_streams.py).
+ * Reference pictures: mi355x_h264_stream_open takes refs <= 1 and refuses more (its contract since ABI 3);
+ * mi355x_h264_stream_open_ex with MI355X_H264_STREAM_MULTIREF honours refs 2 / 3 (tests/test_gpu_stream_refs.py).  Streams share an
+ * engine only with streams of the same refs (0 and 1 are the same), and every position of a shared step has its own number of
+ * usable reference pictures, min(refs, pictures since ITS stream's IDR).  An engine holds refs + 1 reconstructions per stream slot:
+ * (refs + 1) * MI355X_H264_HUB_ITEMS * 1.5 * coded width * coded height bytes - at 1920x1088 and 32 slots 200 MB with one
+ * reference picture, 300 MB with two, 400 MB with three - allocated when the engine's first stream opens.
  * *out stays valid until the stream's next encode / close.  MI355X_H264_HUB_ITEMS (default 32) streams share an engine;
  * MI355X_H264_HUB_WINDOW_US (default 200): how long a step waits for pictures that are already being uploaded. */
 typedef struct mi355x_h264_stream mi355x_h264_stream;
 int mi355x_h264_stream_open(const mi355x_h264_config *cfg, mi355x_h264_stream **out);
+/* mi355x_h264_stream_open with flags.  flags 0: exactly mi355x_h264_stream_open.  MI355X_H264_STREAM_MULTIREF: cfg->refs 2 / 3 is
+ * honoured (with refs <= 1 the stream is an ordinary one and shares the engine of mi355x_h264_stream_open streams of its geometry).
+ * Unknown flag bits, refs > 3, band_count > 1 and batch > 1 return MI355X_H264_E_ARG before the device is touched.  Every other
+ * stream call works unchanged on the stream. */
+enum { MI355X_H264_STREAM_MULTIREF = 1 };   /* cfg->refs 2 / 3 is honoured */
+int mi355x_h264_stream_open_ex(const mi355x_h264_config *cfg, uint32_t flags, mi355x_h264_stream **out);
 void mi355x_h264_stream_close(mi355x_h264_stream *s);
 int mi355x_h264_stream_encode(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *u, int u_stride,
                               const uint8_t *v, int v_stride, uint8_t **out, uint32_t *out_len, int *frame_type);

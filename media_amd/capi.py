@@ -32,9 +32,11 @@ EXPORTS = [
     "mi355x_h264_stream_last_error", "mi355x_h264_stream_debug_read", "mi355x_h264_stream_hub_stats",
     "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
     "mi355x_h264_debug_code_syntax", "mi355x_h264_stream_debug_keep_pre", "mi355x_h264_stream_debug_last_step",
+    "mi355x_h264_stream_open_ex",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
+STREAM_MULTIREF = 1   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
 
 
 class Config(C.Structure):
@@ -90,6 +92,7 @@ def lib():
         L.mi355x_h264_debug_read.restype = C.c_int64
         L.mi355x_h264_debug_code_syntax.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_open.argtypes = [C.POINTER(Config), C.POINTER(vp)]
+        L.mi355x_h264_stream_open_ex.argtypes = [C.POINTER(Config), C.c_uint32, C.POINTER(vp)]
         L.mi355x_h264_stream_close.argtypes = [vp]
         L.mi355x_h264_stream_close.restype = None
         L.mi355x_h264_stream_encode.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
@@ -308,21 +311,31 @@ class Encoder:
 class Stream:
     """a stream of the shared engine (include/mi355x_h264.h, "streams"): one picture per call, coded together with the pictures
     other streams of the same geometry deliver at about the same time; thread-safe across streams (one thread per stream).
-    input_format (INPUT_I420 / INPUT_NV12 / INPUT_RGBA) is the layout of every picture of the stream, from host or device memory"""
+    input_format (INPUT_I420 / INPUT_NV12 / INPUT_RGBA) is the layout of every picture of the stream, from host or device memory.
+    refs 2 / 3: that many reference pictures are searched; the stream is opened with mi355x_h264_stream_open_ex (as it is whenever
+    `flags` is given: the flags of that call)"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
-                 input_format=0):
+                 input_format=0, refs=0, flags=None):
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
         cfg.width, cfg.height, cfg.qp, cfg.gop, cfg.fps = width, height, qp, gop, fps
         cfg.profile_idc, cfg.device, cfg.disable_deblock, cfg.slices, cfg.search = profile_idc, device, disable_deblock, slices, search
         cfg.input_format = input_format
+        cfg.refs = refs
+        if flags is None and refs > 1:
+            flags = STREAM_MULTIREF
         self.h = C.c_void_p()
-        rc = L.mi355x_h264_stream_open(C.byref(cfg), C.byref(self.h))
+        if flags is None:
+            rc = L.mi355x_h264_stream_open(C.byref(cfg), C.byref(self.h))
+        else:
+            rc = L.mi355x_h264_stream_open_ex(C.byref(cfg), flags, C.byref(self.h))
         if rc != 0:
             self.h = None
-            raise EncoderError("mi355x_h264_stream_open failed: %d" % rc)
+            err = EncoderError("mi355x_h264_stream_open%s failed: %d" % ("" if flags is None else "_ex", rc))
+            err.rc = rc
+            raise err
         self.width, self.height = width, height
         self.cw, self.ch = L.mi355x_h264_stream_coded_width(self.h), L.mi355x_h264_stream_coded_height(self.h)
         self.nmb = (self.cw // 16) * (self.ch // 16)

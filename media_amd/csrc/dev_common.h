@@ -85,8 +85,9 @@ struct FrameParams {
     uint8_t* rec[3];        // current picture reconstruction (pitch cw, cw/2, cw/2)
     const uint8_t* ref[3];  // previous deblocked picture (= refs[0])
     const uint8_t* refs[3][3];   // the reference pictures, ref_idx_l0 order (newest first); entries >= nref are not read
-    int nref;               // reference pictures available to this picture (1 .. config.refs)
+    int nref;               // reference pictures available to this picture (1 .. config.refs); indirect launches: the position's own
     int rf, rf_last;        // k_me runs once per reference picture: ref_idx_l0 of this launch (ref = its planes), and of the last launch
+                            // (indirect launches: of the position's last launch, nref - 1)
     uint32_t* me_total;     // per macroblock: best motion cost + lambda * bits(ref_idx_l0) so far, 0 = settled without a search
     int* pmv;               // per macroblock: the previous picture's vector (rate predictor), parked by the first launch
     MbInfo* mb;
@@ -119,7 +120,7 @@ struct FrameParams {
     const uint8_t* mbavail;   // per macroblock: neighbours (left, above, above-right, above-left) in this slice: bits 0..3; usable for intra prediction: bits 4..7
     // INDIRECT launches (kernels instantiated with IND = true; the stream hub of mi355x_h264.hip: pictures of DIFFERENT streams in
     // one lockstep step).  gridDim.y counts POSITIONS; itemtab[position] names the batch item, the ring slot its picture is
-    // reconstructed into and its QP.  rec[] then holds the BASE of the reconstruction planes, which lie [item][ring slot]
+    // reconstructed into, how many reference pictures it has and its QP.  rec[] then holds the BASE of the reconstruction planes, which lie [item][ring slot]
     // (st_y / st_c bytes between items, st_ring_y / st_ring_c between the nbuf slots of one item); qtab is the table of
     // quantiser constants by QP.  srctab[position] is the address of the position's source picture - a slot of the hub's
     // staging array, or the caller's own device picture, read where it lies (src / st_src are not used).  Direct launches leave
@@ -135,12 +136,13 @@ struct FrameParams {
     const DecPos* dectab;
 };
 
-// itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 16..21 QP
-struct ItemRef { int item, cur, qp; };
+// itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 10..11 the reference pictures the position's
+// picture has (1..3 in a P step: min(config.refs, pictures since the stream's IDR); 0 in an IDR step), 16..21 QP
+struct ItemRef { int item, cur, nref, qp; };
 __device__ __forceinline__ ItemRef item_ref(const uint32_t* itemtab, int pos)
 {
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)itemtab[pos]);   // uniform: a scalar load
-    return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 16) & 63u)};
+    return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 10) & 3u), (int)((w >> 16) & 63u)};
 }
 // srctab entry of a position: wave-uniform like the itemtab word, a scalar load of its own (it depends on the position alone, so
 // it is issued beside the itemtab word, not behind it)
@@ -168,7 +170,8 @@ __device__ __forceinline__ FrameParams batch_view(FrameParams P, int g)
     P.me_total += (size_t)g * P.st_mb; P.pmv += (size_t)g * P.st_mb;
     return P;
 }
-// IND = true: the view of POSITION pos of an indirect launch - the item's arrays, its own ring slots and its own QP's constants
+// IND = true: the view of POSITION pos of an indirect launch - the item's arrays, its own ring slots, its own QP's constants and
+// its own number of reference pictures (nref, rf_last; ref[] = the planes of ref_idx_l0 = P.rf, the launch's, in ITS ring)
 template <bool IND>
 __device__ __forceinline__ FrameParams batch_view(FrameParams P, int pos)
 {
@@ -186,7 +189,11 @@ __device__ __forceinline__ FrameParams batch_view(FrameParams P, int pos)
             rs = rs == 0 ? P.nbuf - 1 : rs - 1;
             P.refs[r][0] = by + (size_t)rs * P.st_ring_y; P.refs[r][1] = bu + (size_t)rs * P.st_ring_c; P.refs[r][2] = bv + (size_t)rs * P.st_ring_c;
         }
-        P.ref[0] = P.refs[0][0]; P.ref[1] = P.refs[0][1]; P.ref[2] = P.refs[0][2];
+        // (selects on the wave-uniform rf: indexing the argument struct would move it into scratch)
+        const int rf = P.rf;
+#pragma unroll
+        for (int p = 0; p < 3; p++) P.ref[p] = rf == 0 ? P.refs[0][p] : (rf == 1 ? P.refs[1][p] : P.refs[2][p]);
+        P.nref = it.nref; P.rf_last = it.nref - 1;
         const int g = it.item;
         P.src = src;
         P.mb += (size_t)g * P.st_mb;

@@ -233,7 +233,7 @@ enum { PINTRA_SPARSE_MBS = 8 };   // intra macroblocks per P picture up to which
 
 namespace {
 
-int avail_refs(const mi355x_h264_encoder* e, bool idr) { return idr ? 0 : std::min(e->nrefs, e->seq.frame_in_gop); }
+int avail_refs(const mi355x_h264_encoder* e, bool idr) { return e->seq.avail_refs(idr, e->nrefs); }
 inline bool mb_is_intra_host(int type) { return type == MB_I16 || type == MB_IPCM || type == MB_I4; }
 
 hipEvent_t get_event(mi355x_h264_encoder* e)
@@ -263,7 +263,8 @@ struct StatScope {
 // of the grid is picture items[k] - its own batch item, ring slot, QP, frame_num and idr_pic_id; the kernels are the IND = true
 // instantiations and read d_itemtab, and the source picture of position k lies at d_srctab[k] (d_src is not used) - wherever that is: a
 // slot of the hub's staging array or the caller's own device memory.  A step holds pictures of ONE type (IDR or P): the two run
-// different kernels.
+// different kernels.  A P step's positions are ordered by their pictures' number of reference pictures (ItemPic.nref, most
+// first): k_me's launch for reference picture r covers the positions that have it, the first ones.
 // mi355x_h264_debug_code_syntax: the decisions of the step's pictures come from the host (arrays of n items) instead of the
 // decision and reconstruction kernels
 struct Injected { const void* mbinfo; const void* levels; const void* mvq; const void* mbaux; };
@@ -336,7 +337,16 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
     const int cur = e->seq.cur;
     FrameParams P = frame_params(e);
     P.src = T.d_src; P.src_nv12 = T.nv12 ? 1 : 0; P.w = e->cfg.width; P.h = e->cfg.height;
-    P.nref = ind ? 1 : std::max(1, avail_refs(e, idr));
+    // indirect: me_pos[r] = positions that have reference picture r (the kernels take each position's own count from the itemtab word)
+    int me_pos[mi355x_h264_encoder::MAX_REFS] = {0, 0, 0};
+    if (ind)
+        for (int k = 0; k < T.n; k++) {
+            const int nr = T.items[k].nref;
+            if (nr < (idr ? 0 : 1) || nr > (idr ? 0 : e->nrefs) || (k > 0 && nr > T.items[k - 1].nref))
+                return set_err(e->err, MI355X_H264_E_INTERNAL, "step position %d: %d reference pictures (after %d)", k, nr, k ? T.items[k - 1].nref : 0);
+            for (int r = 0; r < nr; r++) me_pos[r]++;
+        }
+    P.nref = ind ? (idr ? 1 : T.items[0].nref) : std::max(1, avail_refs(e, idr));
     for (int p = 0; p < 3; p++) {
         P.rec[p] = ind ? e->d_plane_base[p] : e->d_planes[cur][p];
         for (int r = 0; r < mi355x_h264_encoder::MAX_REFS; r++) P.refs[r][p] = e->d_planes[(cur + e->nbuf - 1 - std::min(r, e->nrefs - 1)) % e->nbuf][p];
@@ -394,10 +404,10 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
           { StatScope sc(e, &S, MI355X_H264_K_ME, (uint32_t)P.nref, (uint32_t)(e->b_nmb * T.n), st);
             FrameParams Q = P;   // one launch per reference picture (config.refs): Q.ref = the planes of ref_idx_l0 = Q.rf
             Q.rf_last = P.nref - 1;
-            for (int r = 0; r < P.nref; r++) {
+            for (int r = 0; r < P.nref; r++) {   // (indirect: P.nref = the most any position has; no launch places a wave that has nothing to do)
                 Q.rf = r;
                 for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
-                LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, G), dim3(64), st, Q);
+                LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
             } }
           if (turns) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
         }
@@ -420,7 +430,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         uint64_t hdr = 0;
         const int fn = ind ? T.items[g].frame_num : e->seq.frame_num, qp = ind ? T.items[g].qp : e->qp;
         const int id = ind ? T.items[g].idr_id : ((e->seq.idr_id + g * e->idr_step) & 0xFF);
-        const int nact = ind ? (idr ? 0 : 1) : avail_refs(e, idr);
+        const int nact = ind ? T.items[g].nref : avail_refs(e, idr);
         H.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, false, fn, qp, nact, &hdr);
         H.bits[g] = hdr;
         Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, true, fn, qp, nact, &hdr);
@@ -431,7 +441,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
     hipStream_t ec = T.one_stream ? st : Y.ec;
     CavlcParams C{};
     C.mb = e->d_mb; C.levels = e->d_levels; C.mvd = e->d_mvd; C.mbw = e->mbw; C.nmb = e->nmb; C.p_slice = idr ? 0 : 1; C.t8x8 = e->cfg.profile_idc == 100 ? 1 : 0;
-    C.nref = ind ? (idr ? 0 : 1) : avail_refs(e, idr); C.sl = e->sl;
+    C.nref = ind ? 0 : avail_refs(e, idr); C.sl = e->sl;   // (indirect launches: the position's own, from the itemtab word)
     C.mb_first = e->b_row0 * e->mbw; C.mb_end = C.mb_first + e->b_nmb;
     C.slice_cap = (unsigned)e->slice_cap;
     C.mbdiv = P.mbdiv;

@@ -33,6 +33,9 @@ struct PicSeq {
     long frames = 0;
     bool next_is_idr(int gop) const { return force_idr || frames == 0 || frame_in_gop >= gop; }
     void begin(bool idr) { if (idr) { frame_in_gop = 0; frame_num = 0; force_idr = 0; } }
+    // reference pictures the picture begun has, of a stream that searches nrefs: those coded since the stream's last IDR picture
+    // (0, 1, 2, .. up to nrefs).  The one rule of the engine and the stream hub: a forced IDR restarts it with begin()
+    int avail_refs(bool idr, int nrefs) const { return idr ? 0 : std::min(nrefs, frame_in_gop); }
     // the picture went out: idr_step = what an IDR picture adds to idr_pic_id (the engine: its stride times the batch)
     void advance(bool idr, int nbuf, int idr_step)
     {
@@ -41,7 +44,8 @@ struct PicSeq {
     }
 };
 // one picture of an indirect step (engine.h, Step): the batch item it belongs to and that stream's state for the picture
-struct ItemPic { int item, cur, qp, frame_num, idr_id; };
+// (nref: PicSeq::avail_refs)
+struct ItemPic { int item, cur, qp, frame_num, idr_id, nref; };
 
 // ---- host tables (ITU-T H.264 Table 8-15, A-1; quantiser of the reference model) ----
 const uint8_t h_chroma_qp[52] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,

@@ -1,6 +1,8 @@
 // media_amd/csrc/hub.h -- the stream hub's HIP side (include/mi355x_h264.h, "streams"): streams of one geometry share an engine
 // whose batch items are the streams; the pictures that calls deliver while the engine is busy leave together as ONE lockstep
-// step (the IND = true kernels).  Who gathers, leads and waits is hub_sched.h; here: staging memory, uploads, the step itself.
+// step (the IND = true kernels).  The engine searches config.refs reference pictures and keeps refs + 1 reconstructions per stream
+// slot ((refs + 1) * cap * 1.5 * coded size bytes: at 1920x1088 with 32 slots 200 / 300 / 400 MB for refs 1 / 2 / 3); every position
+// of a step has its own number of usable ones (ItemPic.nref).  Who gathers, leads and waits is hub_sched.h; here: staging memory, uploads, the step itself.
 #pragma once
 
 namespace {
@@ -64,9 +66,10 @@ std::mutex g_hubs_mu;
 std::vector<Hub*> g_hubs;
 std::atomic<int> g_streams_open{0};   // over all hubs of the process
 
+// (refs: 0 and 1 are both one reference picture; streams that search more have rings of another size, so engines of their own)
 bool same_geometry(const mi355x_h264_config& a, const mi355x_h264_config& b)
 {
-    return a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
+    return std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
            a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
 }
 
@@ -123,10 +126,10 @@ int hub_create(const mi355x_h264_config& cfg, Hub** out)
     const char* nc = getenv("MI355X_H264_HUB_CTX");
     h->sched.nctx_p = std::min((int)HUB_MAX_CTX - 1, std::max(1, nc ? atoi(nc) : 2));
     mi355x_h264_config ec = cfg;
-    ec.batch = h->sched.cap; ec.refs = 1; ec.band_index = 0; ec.band_count = 0; ec.input_format = MI355X_H264_INPUT_I420;
+    ec.batch = h->sched.cap; ec.refs = std::max(cfg.refs, 1); ec.band_index = 0; ec.band_count = 0; ec.input_format = MI355X_H264_INPUT_I420;
     int rc = create_engine(&ec, &h->e, true);
     if (rc != MI355X_H264_OK) { h->e = nullptr; hub_free(h); return rc; }
-    h->sched.nbuf = h->e->nbuf;
+    h->sched.nrefs = h->e->nrefs; h->sched.nbuf = h->e->nbuf;   // (up to 4 ring slots: `cur` fits the itemtab word's two bits)
     h->st_stage = (picture_bytes(PIC_I420, cfg.width, cfg.height) + 255) & ~(size_t)255;
     h->st_rgba = (picture_bytes(PIC_RGBA, cfg.width, cfg.height) + 255) & ~(size_t)255;
     if (hub_alloc(h) != hipSuccess) { hub_free(h); return MI355X_H264_E_HIP; }
@@ -155,7 +158,7 @@ void hub_run_step(Hub* h, HubStep& T)
         RgbaSrc* const h_rgbatab = (RgbaSrc*)(c.h_tab + HubCtx::TAB_RGBA);
         for (int k = 0; k < n; k++) {
             const HubItem& it = h->items[pics[k].item];
-            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].qp << 16);
+            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].nref << 10) | ((uint32_t)pics[k].qp << 16);
             // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
             h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
             if (rgba) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)it.rgba_src, (unsigned long long)it.rgba_stride};

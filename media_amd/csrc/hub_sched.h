@@ -25,7 +25,7 @@ inline uint64_t now_us() { return (uint64_t)std::chrono::duration_cast<std::chro
 #endif
 
 // a gathered step: picks[k] = the stream (batch item) and what its slice header and the kernels need, as they stood when the step
-// was gathered with nopen streams open; rc[k] is the step runner's answer for it (0: the picture is in the stream)
+// was gathered with nopen streams open, ordered by the pictures' number of reference pictures (most first); rc[k] is the step runner's answer for it (0: the picture is in the stream)
 struct HubStep { int ctx; bool idr; int n, nopen; ItemPic picks[HUB_MAX_ITEMS]; int rc[HUB_MAX_ITEMS]; };
 
 struct HubSched {
@@ -34,7 +34,8 @@ struct HubSched {
     int cap = 0, nopen = 0, uploading = 0;
     int nctx_p = 2;                  // contexts for P steps
     int window_us = 200;             // how long a P step that is being gathered waits for pictures still being uploaded
-    int nbuf = 2;                    // reconstruction ring slots per stream
+    int nrefs = 1;                   // reference pictures every stream of the hub searches (config.refs)
+    int nbuf = 2;                    // reconstruction ring slots per stream: nrefs + 1
     bool collecting = false;         // a leader is gathering a P step
     bool busy[HUB_MAX_CTX] = {};
     std::vector<int> queue[2];       // [0] P pictures, [1] IDR pictures waiting for a step
@@ -136,9 +137,15 @@ struct HubSched {
             for (int k = 0; k < T.n; k++) {
                 Item& b = items[q[k]];
                 b.seq.begin(idr);
-                b.step_serial = steps + 1; b.step_n = T.n; b.step_pos = k; b.step_idr = idr;
-                T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id};
+                T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id, b.seq.avail_refs(idr, nrefs)};
                 T.rc[k] = 0;
+            }
+            // positions by their number of reference pictures, most first (queue order within a number): the motion search of
+            // reference picture r is then one launch over the first positions, those that have it
+            if (nrefs > 1) std::stable_sort(T.picks, T.picks + T.n, [](const ItemPic& a, const ItemPic& b) { return a.nref > b.nref; });
+            for (int k = 0; k < T.n; k++) {
+                Item& b = items[T.picks[k].item];
+                b.step_serial = steps + 1; b.step_n = T.n; b.step_pos = k; b.step_idr = idr;
             }
             q.erase(q.begin(), q.begin() + T.n);
             steps++; pictures += (uint64_t)T.n; max_batch = std::max<uint64_t>(max_batch, (uint64_t)T.n);

@@ -206,7 +206,7 @@ struct CavlcParams {
     const int16_t* mvq;   // 8 per macroblock: vectors of its four 8x8 quadrants
     int mbw, nmb, p_slice;
     int t8x8;             // PPS transform_8x8_mode_flag (High profile)
-    int nref;             // num_ref_idx_l0_active of the slice (ref_idx_l0 is coded when > 1)
+    int nref;             // num_ref_idx_l0_active of the slice (ref_idx_l0 is coded when > 1); indirect launches: from the itemtab word
     SliceRows sl;         // slices of the picture (bands of sl.rows macroblock rows)
     int mb_first, mb_end; // the macroblocks this instance codes (its band of whole slices; 0 .. nmb alone)
     MbDiv mbdiv;          // macroblock index / mbw
@@ -243,8 +243,10 @@ __device__ __forceinline__ CavlcParams batch_view(CavlcParams C, int pos)
     if constexpr (!IND) return batch_view(C, pos);
     else {
         const uint8_t* const src = item_src(C.srctab, pos);   // by position: the picture may lie in the caller's own memory
-        C = batch_view(C, item_ref(C.itemtab, pos).item);
+        const ItemRef it = item_ref(C.itemtab, pos);
+        C = batch_view(C, it.item);
         C.src = src;
+        C.nref = it.nref;   // num_ref_idx_l0_active of the position's own slice header
         return C;
     }
 }

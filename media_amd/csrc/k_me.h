@@ -128,6 +128,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
 {
     if (AB_PRIO_ME) __builtin_amdgcn_s_setprio(AB_PRIO_ME);
     const FrameParams P = batch_view<IND>(P0, blockIdx.y);
+    // indirect launches: every position has its own number of reference pictures.  The host orders a step's positions by that number
+    // and gives launch rf only the positions that have picture rf (engine.h), so this never holds; it keeps a position without
+    // the picture from reading a ring slot older than its stream's IDR
+    if constexpr (IND) { if (P.nref <= P.rf) return; }
     const int lane = threadIdx.x;
     const int mbi = P.band.row0 * P.mbw + xcd_mb_index(blockIdx.x, P.mbw * P.band.rows), my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
     const int bx = 16 * mx, by = 16 * my;

@@ -286,11 +286,15 @@ int mi355x_h264_stats_read(mi355x_h264_encoder* e, mi355x_h264_stats* out, int r
 
 // ---- streams (hub.h) ----
 
-int mi355x_h264_stream_open(const mi355x_h264_config* cfg, mi355x_h264_stream** out)
+int mi355x_h264_stream_open(const mi355x_h264_config* cfg, mi355x_h264_stream** out) { return mi355x_h264_stream_open_ex(cfg, 0, out); }
+
+int mi355x_h264_stream_open_ex(const mi355x_h264_config* cfg, uint32_t flags, mi355x_h264_stream** out)
 {
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
     *out = nullptr;
-    if (cfg->refs > 1 || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
+    if (flags & ~(uint32_t)MI355X_H264_STREAM_MULTIREF) return MI355X_H264_E_ARG;
+    const int max_refs = (flags & MI355X_H264_STREAM_MULTIREF) ? (int)mi355x_h264_encoder::MAX_REFS : 1;
+    if (cfg->refs > max_refs || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
     if (cfg->input_format != MI355X_H264_INPUT_I420 && cfg->input_format != MI355X_H264_INPUT_NV12 && cfg->input_format != MI355X_H264_INPUT_RGBA)
         return MI355X_H264_E_ARG;
     if (cfg->qp < 10 || cfg->qp > 51 || cfg->gop < 1) return MI355X_H264_E_ARG;

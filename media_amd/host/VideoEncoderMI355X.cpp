@@ -66,6 +66,9 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     // inputData is an address in this device's memory, read in place; else host memory).  include/mi355x_h264.h, "streams"
     m_input = ParseInputLayout(GetStrEncParam("persist.vmi.video.encode.input"));
     m_inputDevice = ParseInputDevice(GetStrEncParam("persist.vmi.video.encode.inputmem"));
+    // extension: "2" / "3" = that many reference pictures are searched and ref_idx_l0 is coded; anything else keeps the preset's
+    // one (iNumRefFrame = 1, ref :290).  Both paths below honour it
+    cfg.refs = ParseRefs(GetStrEncParam("persist.vmi.video.encode.refs"));
     // One engine per object (mi355x_h264_create) costs every picture its own launch sequence.  The default is a STREAM of the
     // shared engine: the pictures that the encoder objects of one process hand over at about the same time are coded in one
     // lockstep step (include/mi355x_h264.h, "streams"; same bitstream).  persist.vmi.video.encode.shared = 0 (or the environment
@@ -74,9 +77,9 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     const bool shared = GetStrEncParam("persist.vmi.video.encode.shared") != "0" && !(hubEnv != nullptr && hubEnv[0] == '0');
     if (shared) {
         cfg.input_format = m_input;
-        const int rc = mi355x_h264_stream_open(&cfg, &m_stream);
+        const int rc = mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
         if (rc != MI355X_H264_OK) {
-            ERR("mi355x_h264_stream_open returned %d", rc);
+            ERR("mi355x_h264_stream_open_ex returned %d", rc);
             m_stream = nullptr;
             return false;
         }
@@ -160,6 +163,8 @@ int32_t VideoEncoderMI355X::ParseInputLayout(const std::string &value)
 {
     return value == "nv12" ? MI355X_H264_INPUT_NV12 : value == "rgba" ? MI355X_H264_INPUT_RGBA : MI355X_H264_INPUT_I420;
 }
+
+int32_t VideoEncoderMI355X::ParseRefs(const std::string &value) { return value == "2" ? 2 : value == "3" ? 3 : 1; }
 
 bool VideoEncoderMI355X::ParseInputDevice(const std::string &value) { return value == "device"; }
 

@@ -31,6 +31,9 @@ public:
     // (or unset) -> MI355X_H264_INPUT_I420, the reference's videoFormatI420; "device" -> true, anything else -> host memory
     static int32_t ParseInputLayout(const std::string &value);
     static bool ParseInputDevice(const std::string &value);
+    // extension key persist.vmi.video.encode.refs: "2" / "3" -> that many reference pictures; anything else (or unset) -> 1, the
+    // reference preset's iNumRefFrame
+    static int32_t ParseRefs(const std::string &value);
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }

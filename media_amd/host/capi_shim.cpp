@@ -6,6 +6,10 @@
 #include "Property.h"
 #include "VideoCodecApi.h"
 #include "VideoEncoderMI355X.h"
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Wunused-function"
+#include "../csrc/host_framing.h"   // PicSeq (plain C++): vc_debug_ref_counts
+#pragma GCC diagnostic pop
 
 extern "C" {
 uint32_t vc_create(void **enc) { return CreateVideoEncoder(reinterpret_cast<VideoEncoder **>(enc)); }
@@ -24,6 +28,22 @@ uint32_t vc_encode_addr(void *enc, uint64_t addr, uint32_t inSize, uint8_t **out
 // how the two input extension keys read a value (host logic, no device)
 int32_t vc_parse_input_layout(const char *value) { return VideoEncoderMI355X::ParseInputLayout(value != nullptr ? value : ""); }
 int32_t vc_parse_input_device(const char *value) { return VideoEncoderMI355X::ParseInputDevice(value != nullptr ? value : "") ? 1 : 0; }
+// persist.vmi.video.encode.refs: 2 or 3 are taken, anything else is one reference picture
+int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
+// The one rule for a picture's number of reference pictures (PicSeq::avail_refs, shared by the engine and the stream hub), driven
+// as both drive it: n pictures of a stream that searches nrefs pictures with an IDR every gop; force[i] != 0 forces an IDR at
+// picture i.  out[i] = the count of picture i (0: an IDR picture).
+void vc_debug_ref_counts(int32_t nrefs, int32_t gop, const uint8_t *force, int32_t n, int32_t *out)
+{
+    PicSeq seq;
+    for (int32_t i = 0; i < n; i++) {
+        if (force != nullptr && force[i] != 0) seq.force_idr = 1;
+        const bool idr = seq.next_is_idr(gop);
+        seq.begin(idr);
+        out[i] = seq.avail_refs(idr, nrefs);
+        seq.advance(idr, nrefs + 1, 1);
+    }
+}
 uint32_t vc_stop(void *enc) { return static_cast<VideoEncoder *>(enc)->StopEncoder(); }
 void vc_destroy(void *enc) { static_cast<VideoEncoder *>(enc)->DestroyEncoder(); }
 uint32_t vc_reset(void *enc) { return static_cast<VideoEncoder *>(enc)->ResetEncoder(); }

@@ -34,6 +34,9 @@ def lib():
         L.vc_encode_addr.restype = C.c_uint32
         L.vc_parse_input_layout.argtypes = [C.c_char_p]
         L.vc_parse_input_device.argtypes = [C.c_char_p]
+        L.vc_parse_refs.argtypes = [C.c_char_p]
+        L.vc_debug_ref_counts.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.vc_debug_ref_counts.restype = None
         L.vc_last_qp.argtypes = [vp]
         L.vc_scene_cuts.argtypes = [vp]
         L.vc_scene_cuts.restype = C.c_uint32
@@ -67,8 +70,22 @@ def parse_input_device(value):
     return bool(lib().vc_parse_input_device(str(value).encode()))
 
 
+def parse_refs(value):
+    """what persist.vmi.video.encode.refs = value selects: 2 or 3 reference pictures, else 1"""
+    return lib().vc_parse_refs(str(value).encode())
+
+
+def ref_counts(nrefs, gop, n, forced=()):
+    """the number of reference pictures of each of n pictures of a stream that searches nrefs, IDR every gop pictures and at the
+    pictures in `forced` (the rule the engine and the stream hub share; 0 = an IDR picture)"""
+    force = bytes(1 if i in forced else 0 for i in range(n))
+    out = (C.c_int32 * n)()
+    lib().vc_debug_ref_counts(nrefs, gop, force, n, out)
+    return list(out)
+
+
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None):
+                   inputmem=None, refs=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -85,6 +102,7 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.slices", "" if slices is None else slices)
     prop_set("persist.vmi.video.encode.input", "" if input is None else input)        # nv12 | rgba; else I420
     prop_set("persist.vmi.video.encode.inputmem", "" if inputmem is None else inputmem)   # device; else host memory
+    prop_set("persist.vmi.video.encode.refs", "" if refs is None else refs)               # 2 | 3; else one reference picture
 
 
 class VideoEncoder:

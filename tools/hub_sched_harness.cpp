@@ -65,6 +65,10 @@ void fake_step(HubStep& T, std::mt19937& rng, long log_from)
         RULE(T.idr ? p.frame_num == 0 : p.frame_num == t.in_gop, "stream %d: frame_num %d in a %s step, %d pictures into the GOP", p.item, p.frame_num, T.idr ? "IDR" : "P", t.in_gop);
         RULE(T.idr || t.in_gop < GOP, "stream %d: GOP longer than %d", p.item, GOP);
         RULE(p.cur >= 0 && p.cur < S.nbuf, "ring slot");
+        // the picture's number of reference pictures: those coded since the stream's IDR, never one from before it (a failed picture
+        // is followed by an IDR picture); a step's positions are ordered by it, most first
+        RULE(p.nref == (T.idr ? 0 : std::min(S.nrefs, t.in_gop)), "stream %d: %d reference pictures, %d pictures into the GOP", p.item, p.nref, t.in_gop);
+        RULE(k == 0 || T.picks[k - 1].nref >= p.nref, "position %d has more reference pictures than the one before it", k);
         t.finished++;
         t.failed = all_fail || rng() % 16 == 0;
         T.rc[k] = t.failed ? 1 : 0;
@@ -122,6 +126,7 @@ int main(int argc, char** argv)
     const int rounds = argc > 1 ? atoi(argv[1]) : 20;
     const unsigned seed = argc > 2 ? (unsigned)atoi(argv[2]) : 1u;
     S.cap = HUB_MAX_ITEMS; S.nctx_p = NCTX_P; S.window_us = 50;
+    S.nrefs = seed % 2 == 0 ? 3 : 1; S.nbuf = S.nrefs + 1;   // even seeds: streams that search three reference pictures
     g_open_log.assign((size_t)THREADS * rounds * 2 + 1, 0);
     std::vector<std::thread> th;
     for (int i = 0; i < THREADS; i++) th.emplace_back(worker, i, rounds, seed);

@@ -5,8 +5,10 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--refs N] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
+// --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
+// (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
 // input (optional; without it everything is as above): i420 | nv12 | rgba, with ":device" behind it for pictures in device
 // memory - the extension keys persist.vmi.video.encode.input / .inputmem.  The pictures of the file are converted to the layout
 // on the host before the clock starts; for device memory they are uploaded once, before the clock, and every stream cycles
@@ -25,7 +27,14 @@
 
 int main(int argc, char **argv)
 {
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    for (int i = 1; i + 1 < argc; i++)   // --refs N: taken out of the line, the rest is positional
+        if (strcmp(argv[i], "--refs") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_REFS", argv[i + 1], 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     const int w = atoi(argv[2]), h = atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
     std::vector<uint8_t> pics(fsz * npic);
