@@ -114,7 +114,9 @@ int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group *g, int stream, 
  * transfers it made, out[4] parse threads used; with n >= 7 also out[5] / out[6]: microseconds the host spent parsing / launching
  * (and, with MI355X_H264_DEC_SYNC, waiting); with n >= 9 also out[7] / out[8]: output launches / device-to-host output transfers the
  * step made (set_output below; 0 / 0 for an unarmed group); with n >= 11 also out[9] / out[10]: launches / transfers of the last
- * read_all call.  Returns the number of values written */
+ * read_all call; with n >= 13 also out[11] / out[12]: bytes of device memory / of pinned host memory the group holds at the moment
+ * of the call (its picture store and its own arrays, tables and output buffers; not the parsers' heap).  Returns the number of
+ * values written */
 int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group *g, int64_t *out, int n);
 
 /* every stream's last decoded picture in ONE call (layouts and packing: above): what read_i420 gives per stream, for all streams
@@ -127,7 +129,7 @@ int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group *g, int64_t *out
  * has a picture) */
 int64_t mi355x_h264_dec_group_read_all(mi355x_h264_dec_group *g, int layout, int row_align, void *dst, size_t cap, int to_device,
                                        mi355x_h264_dec_out_pic *pics /* [streams] */);
-/* arm the group (layout -1: disarm): from the next step on every step that carries pictures is followed, on the engine's stream
+/* arm the group (layout -1: disarm): from the next step on every step that carries pictures is followed, on the group's one stream
  * behind the loop filter, by one gather launch for exactly the step's positions and one asynchronous device-to-host copy into one
  * of two pinned output sets, with an event of its own.  The sets take turns.  The step's table of output positions travels behind
  * its position table in the same transfer: out[2] / out[3] of last_step count what they count for an unarmed group. */
@@ -141,6 +143,8 @@ int mi355x_h264_dec_group_output(mi355x_h264_dec_group *g, int back, const uint8
 /* ---- test / measurement hooks ---- */
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 */
 int mi355x_h264_dec_timing(const mi355x_h264_decoder *dec, uint64_t *pictures, double *parse_ms, double *gpu_ms);
+/* mi355x_h264_dec_group_last_step of the group of one stream that the decoder is */
+int mi355x_h264_dec_last_step(const mi355x_h264_decoder *dec, int64_t *out, int n);
 
 /* the host parser alone (needs no GPU): parse one access unit and read back what it recovered */
 typedef struct mi355x_h264_parser mi355x_h264_parser;

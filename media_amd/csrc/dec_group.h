@@ -1,5 +1,6 @@
 // media_amd/csrc/dec_group.h -- decoder groups (include/mi355x_h264_dec.h, mi355x_h264_dec_group_*): the next pictures of up to 64
-// streams reconstructed in ONE lockstep step on one engine with batch = streams, as the stream hub does for encoders.  A step is
+// streams reconstructed in ONE lockstep step in one picture store (pic_store.h) with one item per stream, as the stream hub does
+// for encoders in its engine's.  A group owns that store, one stream and nothing of the encoder's.  A step is
 // one set of uploads and one set of launches whatever the number of streams: the streams' access units are parsed side by side on
 // a small pool of threads (dec_group_sched.h, which also rotates the two sets of pinned buffers), every parsed picture is copied
 // into its item's slice of group-wide pinned arrays laid [item][...], and each array then travels in one transfer that covers the
@@ -43,12 +44,12 @@ struct mi355x_h264_dec_group {
     bool resize = false;                 // an IDR picture of another coded size re-makes the geometry.  Honoured for a group of ONE
                                          // stream only (a step of several has rows and copies in the arrays that would go); the
                                          // decoder peer sets it: not in the public ABI, where a group keeps its first size
-    mi355x_h264_encoder* eng = nullptr;
-    int mbw = 0, mbh = 0;
+    PicStore store;                      // made for the group's geometry (that of the first IDR picture it meets): store.made()
+    StepSync sync;                       // the group's one stream; its h_err is the wavefront time-out flag
     DecGroupStream* st = nullptr;        // [nstreams]
     DecGroupSched sched;
     uint8_t* h_arr[2][DG_ARRAYS] = {};   // pinned sets, [item][macroblock]
-    uint8_t* d_arr[DG_ARRAYS] = {};      // device (MbInfo, quadrant vectors and Intra4x4 modes are the engine's own arrays)
+    uint8_t* d_arr[DG_ARRAYS] = {};      // device (MbInfo, quadrant vectors and Intra4x4 modes are the store's own arrays)
     DecPos* h_tab[2] = {nullptr, nullptr};
     DecPos* d_tab = nullptr;
     DecBigLevel* h_big[2] = {nullptr, nullptr};
@@ -57,14 +58,14 @@ struct mi355x_h264_dec_group {
     size_t d_big_cap = 0;
     DevMem mem;
     hipEvent_t up_done[2] = {nullptr, nullptr};
-    bool busy = false;                   // a step is in flight on the engine's stream
+    bool busy = false;                   // a step is in flight on the group's stream
     int flight[DEC_GROUP_MAX_STREAMS];   // its streams
     int nflight = 0;
     int intra_slots = 32, filter_slots = 32;   // pictures the row wavefronts hold at a time (the rest are walked to)
-    int64_t step_serial = 0, last[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t step_serial = 0, last[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (last_step's out[11] / out[12] are the DevMem totals)
     double last_ms[2] = {0, 0};          // the last step's parse and launch time, untruncated (last[5] / last[6] are whole microseconds)
     // output (k_dec_out.h).  rd: read_all's table and staging; its device staging buffer also serves the armed steps (everything
-    // is ordered on the engine's stream).  Armed: the step's table of output positions lies behind its DecPos rows in tables of
+    // is ordered on the group's stream).  Armed: the step's table of output positions lies behind its DecPos rows in tables of
     // their own (h_tabx / d_tabx: DecPos [streams], then DecOutPos [streams]), so that one transfer carries both.
     struct Out {
         DecOutBuf rd;
@@ -97,22 +98,25 @@ int dg_wait(mi355x_h264_dec_group* g)
 {
     if (!g->busy) return MI355X_H264_OK;
     g->busy = false;
-    mi355x_h264_encoder* e = g->eng;
-    HIPCHK(g->err, hipStreamSynchronize(e->stream));
-    const int rc = handoff_timeout(e->slots[0].sync, g->err);
+    HIPCHK(g->err, hipStreamSynchronize(g->sync.st));
+    const int rc = handoff_timeout(g->sync, g->err);
     if (rc) for (int k = 0; k < g->nflight; k++) dg_drop_refs(g->st[g->flight[k]]);
     return rc;
 }
 
+// store and arrays go (nothing in flight); the group's stream and events stay
 void dg_free_geometry(mi355x_h264_dec_group* g)
 {
+    pic_store_destroy(g->store);
     g->mem.free_all();
     for (int k = 0; k < 2; k++) {
         for (auto& p : g->h_arr[k]) p = nullptr;
         g->h_tab[k] = nullptr;
+        g->h_big[k] = nullptr; g->h_big_cap[k] = 0;
     }
     for (auto& p : g->d_arr) p = nullptr;
     g->d_tab = nullptr;
+    g->d_big = nullptr; g->d_big_cap = 0;
     hipEvent_t ev[2] = {g->out.done[0], g->out.done[1]};
     const bool armed = g->out.armed;
     const int layout = g->out.layout, row_align = g->out.row_align;
@@ -125,7 +129,7 @@ int dg_out_prepare(mi355x_h264_dec_group* g)
 {
     mi355x_h264_dec_group::Out& o = g->out;
     const size_t S = (size_t)g->nstreams;
-    const size_t need = S * out_align(out_geom(o.layout, 16 * g->mbw, 16 * g->mbh, o.row_align).bytes, 256);
+    const size_t need = S * out_align(out_geom(o.layout, g->store.cw, g->store.ch, o.row_align).bytes, 256);
     bool ok = true;
     for (int k = 0; k < 2 && ok; k++) {
         if (!o.done[k]) ok = hipEventCreateWithFlags(&o.done[k], hipEventDisableTiming) == hipSuccess;
@@ -144,44 +148,37 @@ int dg_out_prepare(mi355x_h264_dec_group* g)
     return MI355X_H264_OK;
 }
 
-// engine and arrays for the group's geometry (that of the first IDR picture it meets)
+// store (four ring slots: the picture being written and three reference pictures) and arrays for the group's geometry
 int dg_create_geometry(mi355x_h264_dec_group* g, int mbw, int mbh)
 {
-    mi355x_h264_config cfg;
-    mi355x_h264_default_config(&cfg);
-    cfg.width = 16 * mbw; cfg.height = 16 * mbh; cfg.refs = 3; cfg.device = g->device; cfg.batch = g->nstreams;
-    const int crc = create_engine(&cfg, &g->eng, false);
-    if (crc != MI355X_H264_OK) return set_err(g->err, crc, "engine for %d streams of %dx%d macroblocks could not be created", g->nstreams, mbw, mbh);
-    g->mbw = mbw; g->mbh = mbh;
     const size_t n = (size_t)mbw * mbh * g->nstreams;
-    bool ok = true;
+    bool ok = pic_store_create(g->store, g->device, mbw, mbh, g->nstreams, 4) == hipSuccess;
     for (int a = 0; a < DG_ARRAYS && ok; a++) {
         for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_arr[k][a], n * DG_BYTES[a]) == hipSuccess;
         if (ok && a >= DG_LV8) ok = g->mem.dev(&g->d_arr[a], n * DG_BYTES[a]) == hipSuccess;
     }
     for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_tab[k], (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
     ok = ok && g->mem.dev(&g->d_tab, (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
+    // the lists of large levels at their smallest size, so that the steps of an ordinary stream allocate nothing (dg_step grows them)
+    for (int k = 0; k < 2 && ok; k++) if ((ok = g->mem.pinned(&g->h_big[k], 1024 * sizeof(DecBigLevel)) == hipSuccess)) g->h_big_cap[k] = 1024;
+    if (ok && (ok = g->mem.dev(&g->d_big, 1024 * sizeof(DecBigLevel)) == hipSuccess)) g->d_big_cap = 1024;
     if (!ok) {
         dg_free_geometry(g);
-        destroy_engine(g->eng); g->eng = nullptr;
-        return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the arrays of %d streams of %dx%d macroblocks", g->nstreams, mbw, mbh);
+        return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the arrays of %d streams of %dx%d macroblocks (%s)", g->nstreams, mbw, mbh, t_failed_call);
     }
-    mi355x_h264_encoder* e = g->eng;
-    g->d_arr[DG_MB] = (uint8_t*)e->d_mb; g->d_arr[DG_MVQ] = (uint8_t*)e->d_mvq; g->d_arr[DG_AUX] = e->d_aux;
+    g->d_arr[DG_MB] = (uint8_t*)g->store.d_mb; g->d_arr[DG_MVQ] = (uint8_t*)g->store.d_mvq; g->d_arr[DG_AUX] = g->store.d_aux;
     return MI355X_H264_OK;
 }
 
 // `resize`: everything the old coded size owned goes, so that the IDR picture in hand finds the group as a new one does.  Nothing may
-// be in flight when the arrays are freed: the step (dg_wait, checked by the caller), whatever else is queued on the engine's stream
+// be in flight when the arrays are freed: the step (dg_wait, checked by the caller), whatever else is queued on the group's stream
 // - an armed step's copy, the uploads out of BOTH pinned sets -, which the synchronize covers.  No stream keeps a picture.
 int dg_drop_geometry(mi355x_h264_dec_group* g)
 {
     if (const int wrc = dg_wait(g)) return wrc;
-    HIPCHK(g->err, hipStreamSynchronize(g->eng->stream));
+    HIPCHK(g->err, hipStreamSynchronize(g->sync.st));
     g->sched.in_flight[0] = g->sched.in_flight[1] = false;
     dg_free_geometry(g);
-    destroy_engine(g->eng); g->eng = nullptr;
-    g->mbw = g->mbh = 0;
     for (int i = 0; i < g->nstreams; i++) { dg_drop_refs(g->st[i]); g->st[i].cur = 0; g->st[i].last = -1; }
     return MI355X_H264_OK;
 }
@@ -192,7 +189,7 @@ void dg_copy_picture(mi355x_h264_dec_group* g, int i, int k)
 {
     DecGroupStream& s = g->st[i];
     const h264dec::Picture& pic = s.parser.picture();
-    const size_t n = (size_t)g->mbw * g->mbh;
+    const size_t n = (size_t)g->store.nmb;
     static_assert(sizeof(h264dec::MbRec) == sizeof(MbInfo), "layout of the parser's macroblock records");
     const void* src[DG_ARRAYS] = {pic.mb.data(), pic.mvq.data(), pic.aux.data(), pic.levels8.data(), pic.mbqp.data(), pic.mbavail.data(),
                                   pic.mv4.data(), pic.refq.data()};
@@ -239,7 +236,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         DecGroupStream& s = g->st[i];
         try {
             s.prc = s.parser.parse_access_unit(s.au, s.len, false);
-            if (s.prc > 0 && g->eng && s.parser.picture().mbw == g->mbw && s.parser.picture().mbh == g->mbh) dg_copy_picture(g, i, set);
+            if (s.prc > 0 && g->store.made() && s.parser.picture().mbw == g->store.mbw && s.parser.picture().mbh == g->store.mbh) dg_copy_picture(g, i, set);
         } catch (const std::exception&) {
             s.prc = -2;
         }
@@ -272,13 +269,13 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         if (s.prc < 0) { snprintf(s.err, sizeof(s.err), "%s", s.parser.error().c_str()); dg_drop_refs(s); rc[i] = MI355X_H264_E_STREAM; continue; }
         const h264dec::Picture& pic = s.parser.picture();
         const h264dec::Sps& sps = s.parser.sps();
-        if (S == 1 && g->eng && g->resize && pic.idr && (pic.mbw != g->mbw || pic.mbh != g->mbh)) {
+        if (S == 1 && g->store.made() && g->resize && pic.idr && (pic.mbw != g->store.mbw || pic.mbh != g->store.mbh)) {
             if (const int drc = dg_drop_geometry(g)) {
                 for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
                 return drc;
             }
         }
-        if (!g->eng) {
+        if (!g->store.made()) {
             if (!pic.idr) { rc[i] = dg_stream_fail(s, "the stream must start with an IDR picture"); continue; }
             if (const int crc = dg_create_geometry(g, pic.mbw, pic.mbh)) {
                 for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
@@ -291,11 +288,11 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
                 return orc;
             }
         }
-        if (pic.mbw != g->mbw || pic.mbh != g->mbh) {
-            rc[i] = dg_stream_fail(s, "coded size %dx%d differs from the group's %dx%d", 16 * pic.mbw, 16 * pic.mbh, 16 * g->mbw, 16 * g->mbh);
+        const PicStore* const ps = &g->store;
+        if (pic.mbw != ps->mbw || pic.mbh != ps->mbh) {
+            rc[i] = dg_stream_fail(s, "coded size %dx%d differs from the group's %dx%d", 16 * pic.mbw, 16 * pic.mbh, ps->cw, ps->ch);
             continue;
         }
-        mi355x_h264_encoder* e = g->eng;
         if (pic.idr) s.have_refs = 0;
         if (pic.has_inter && (s.have_refs < 1 || pic.num_ref_active > s.have_refs)) {
             rc[i] = dg_stream_fail(s, "a P picture refers to %d reference pictures, %d are held", pic.num_ref_active, s.have_refs);
@@ -319,7 +316,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         for (int r = 0; r < 3; r++) {
             // RefPicList0 entry r = the reference picture decoded ref_age[r] + 1 reference pictures ago (ring slot cur - 1 - age)
             const int age = std::min(r < pic.num_ref_active ? pic.ref_age[r] : r, std::max(0, s.have_refs - 1));
-            w0 |= (uint32_t)((s.cur + e->nbuf - 1 - age) % e->nbuf) << (10 + 2 * r);
+            w0 |= (uint32_t)((s.cur + ps->nbuf - 1 - age) % ps->nbuf) << (10 + 2 * r);
         }
         w0 |= (pic.has_inter ? 1u << 24 : 0u) | (pic.has_intra ? 1u << 25 : 0u) | (filtered ? 1u << 26 : 0u) | (pic.deblock_idc == 0 ? 1u << 27 : 0u);
         T.w[0] = w0;
@@ -328,8 +325,8 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         // slices that are bands of whole rows run as independent wavefronts; any other shape: one wavefront over the picture.  The
         // filter sees one slice with idc 0 (edges between slices are filtered) and with slices that are no bands (k_dec_bs_pos has
         // zeroed the strengths between them where idc 2 says so)
-        const int rows = pic.slice_rows > 0 ? pic.slice_rows : g->mbh;
-        const int frows = (pic.deblock_idc == 0 || pic.slice_rows < 0) ? g->mbh : rows;
+        const int rows = pic.slice_rows > 0 ? pic.slice_rows : ps->mbh;
+        const int frows = (pic.deblock_idc == 0 || pic.slice_rows < 0) ? ps->mbh : rows;
         T.w[2] = (uint32_t)rows; T.w[3] = recip32(rows);
         T.w[4] = (uint32_t)frows; T.w[5] = recip32(frows);
         any_inter |= pic.has_inter; any_intra |= pic.has_intra;
@@ -349,9 +346,9 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     }
     if (npos == 0) return MI355X_H264_OK;
 
-    mi355x_h264_encoder* e = g->eng;
-    hipStream_t st = e->stream;
-    const size_t nmb = (size_t)e->nmb;
+    PicStore* const ps = &g->store;
+    hipStream_t st = g->sync.st;
+    const size_t nmb = (size_t)ps->nmb;
     int transfers = 0, launches = 0;
     // one transfer per array: the items from the lowest to the highest taking part
     end.queued_on = st;
@@ -370,18 +367,18 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     if (nbig) {   // the streams' large levels as one list, the indices counted from item 0
         static_assert(sizeof(h264dec::Picture::Big) == sizeof(DecBigLevel), "layout of the list of large levels");
         if (nbig > g->h_big_cap[k]) {   // (no upload out of this set is in flight: begin_step has waited)
-            if (g->h_big[k]) (void)hipHostFree(g->h_big[k]);
+            g->mem.drop(g->h_big[k]);
             g->h_big[k] = nullptr; g->h_big_cap[k] = 0;
             const size_t cap = nbig * 2 + 1024;
-            HIPCHK(g->err, hipHostMalloc((void**)&g->h_big[k], cap * sizeof(DecBigLevel), hipHostMallocDefault));
+            HIPCHK(g->err, g->mem.pinned(&g->h_big[k], cap * sizeof(DecBigLevel)));
             g->h_big_cap[k] = cap;
         }
         if (nbig > g->d_big_cap) {
             HIPCHK(g->err, hipStreamSynchronize(st));
-            if (g->d_big) (void)hipFree(g->d_big);
+            g->mem.drop(g->d_big);
             g->d_big = nullptr; g->d_big_cap = 0;
             const size_t cap = nbig * 2 + 1024;
-            HIPCHK(g->err, hipMalloc((void**)&g->d_big, cap * sizeof(DecBigLevel)));
+            HIPCHK(g->err, g->mem.dev(&g->d_big, cap * sizeof(DecBigLevel)));
             g->d_big_cap = cap;
         }
         size_t at = 0;
@@ -400,45 +397,45 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     const unsigned NP = (unsigned)npos;
     {
         const int words = (int)(nmb * (LV_STRIDE / 4));
-        hipLaunchKernelGGL(k_dec_widen_pos, dim3((words + 255) / 256, NP), dim3(256), 0, st, (const uint32_t*)g->d_arr[DG_LV8], (const MbInfo*)e->d_mb, e->d_levels, (int)nmb,
+        hipLaunchKernelGGL(k_dec_widen_pos, dim3((words + 255) / 256, NP), dim3(256), 0, st, (const uint32_t*)g->d_arr[DG_LV8], (const MbInfo*)ps->d_mb, ps->d_levels, (int)nmb,
                            d_tab);
         launches++;
-        if (nbig) { hipLaunchKernelGGL(k_dec_patch, dim3(((int)nbig + 255) / 256), dim3(256), 0, st, (const DecBigLevel*)g->d_big, (int)nbig, e->d_levels); launches++; }
+        if (nbig) { hipLaunchKernelGGL(k_dec_patch, dim3(((int)nbig + 255) / 256), dim3(256), 0, st, (const DecBigLevel*)g->d_big, (int)nbig, ps->d_levels); launches++; }
     }
-    FrameParams P = frame_params(e);
-    P.w = e->cw; P.h = e->ch;
+    FrameParams P = store_frame_params(ps);
+    P.w = ps->cw; P.h = ps->ch;
     P.nref = 1;
-    for (int p = 0; p < 3; p++) P.rec[p] = e->d_plane_base[p];   // (the positions' planes and references: from the table)
-    P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
-    P.sl.rows = e->mbh; P.sl.inv = recip32(e->mbh);
-    P.band.row0 = 0; P.band.rows = e->mbh;
+    for (int p = 0; p < 3; p++) P.rec[p] = ps->d_plane_base[p];   // (the positions' planes and references: from the table)
+    P.st_ring_y = ps->st_ring_y; P.st_ring_c = ps->st_ring_c; P.nbuf = ps->nbuf;
+    P.sl.rows = ps->mbh; P.sl.inv = recip32(ps->mbh);
+    P.band.row0 = 0; P.band.rows = ps->mbh;
     P.mbqp = g->d_arr[DG_QP]; P.mv4 = (const int16_t*)g->d_arr[DG_MV4]; P.refq = g->d_arr[DG_REFQ]; P.mbavail = g->d_arr[DG_AVAIL];
     P.dectab = d_tab;
-    unsigned* const h_err = e->slots[0].sync.h_err;
+    unsigned* const h_err = g->sync.h_err;
     if (any_inter) {
-        hipLaunchKernelGGL(k_dec_inter_pos, dim3(e->nmb, NP), wave, 0, st, P);
-        hipLaunchKernelGGL(k_dec_resid, dim3((e->nmb + 3) / 4, NP), wave, 0, st, P);
+        hipLaunchKernelGGL(k_dec_inter_pos, dim3(ps->nmb, NP), wave, 0, st, P);
+        hipLaunchKernelGGL(k_dec_resid, dim3((ps->nmb + 3) / 4, NP), wave, 0, st, P);
         launches += 2;
     }
     if (any_intra) {
-        const IntraRowParams R = intra_row_params(e, P, h_err, npos);
-        hipLaunchKernelGGL((k_pintra_rows<true, true>), dim3(e->mbh, std::min(NP, (unsigned)g->intra_slots)), wave, 0, st, R);
+        const IntraRowParams R = intra_row_params(ps, P, h_err, npos);
+        hipLaunchKernelGGL((k_pintra_rows<true, true>), dim3(ps->mbh, std::min(NP, (unsigned)g->intra_slots)), wave, 0, st, R);
         launches++;
     }
     if (any_plain || any_bs4) {
-        const unsigned db_serial = next_nonzero(e->serial);
+        const unsigned db_serial = next_nonzero(ps->serial);
         DecBsParams B{};
-        B.mb = e->d_mb; B.mv4 = (const int16_t*)g->d_arr[DG_MV4]; B.refq = g->d_arr[DG_REFQ]; B.bs = (uint8_t*)e->d_bs; B.mbw = e->mbw; B.nmb = e->nmb; B.mbdiv = P.mbdiv;
+        B.mb = ps->d_mb; B.mv4 = (const int16_t*)g->d_arr[DG_MV4]; B.refq = g->d_arr[DG_REFQ]; B.bs = (uint8_t*)ps->d_bs; B.mbw = ps->mbw; B.nmb = ps->nmb; B.mbdiv = P.mbdiv;
         B.mbavail = g->d_arr[DG_AVAIL];
-        hipLaunchKernelGGL(k_dec_bs_pos, dim3((e->nmb + 1) / 2, NP), wave, 0, st, B, e->d_anybs, db_serial, d_tab);
+        hipLaunchKernelGGL(k_dec_bs_pos, dim3((ps->nmb + 1) / 2, NP), wave, 0, st, B, ps->d_anybs, db_serial, d_tab);
         launches++;
         // always the per-edge thresholds; the form with the bS 4 filter for the positions with intra macroblocks, the one without
         // for the others (the pair of launches of the encoder's P steps, chosen by the table's flags)
-        DbParams D = db_params(e, e->d_plane_base, P.sl, 26);
+        DbParams D = db_params(ps, ps->d_plane_base, P.sl, 26);
         D.mbqp = g->d_arr[DG_QP];
-        DbRowParams R = db_row_params(e, D, h_err, db_serial, P.pic_serial, 0, npos);
-        R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c; R.dectab = d_tab;
-        const dim3 grid(e->mbh, std::min(NP, (unsigned)g->filter_slots));
+        DbRowParams R = db_row_params(ps, D, h_err, db_serial, P.pic_serial, 0, npos);
+        R.st_ring_y = ps->st_ring_y; R.st_ring_c = ps->st_ring_c; R.dectab = d_tab;
+        const dim3 grid(ps->mbh, std::min(NP, (unsigned)g->filter_slots));
         if (any_plain) { R.need_intra = -1; hipLaunchKernelGGL((k_deblock_rows<false, true, true>), grid, wave, 0, st, R); launches++; }
         if (any_bs4) { R.need_intra = 1; hipLaunchKernelGGL((k_deblock_rows<true, true, true>), grid, wave, 0, st, R); launches++; }
     }
@@ -446,7 +443,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     if (outp) {
         // behind the loop filter, and ahead of the next step on this stream, which may write the very ring slot (a non-reference
         // picture leaves `cur` where it was): the step's pictures into the staging buffer, and that into the pinned set
-        HIPCHK(g->err, launch_dec_out(e, g->out.layout, otab, (const DecOutPos*)(g->out.d_tabx + (size_t)S * sizeof(DecPos)), npos, g->out.rd.d_stage, st));
+        HIPCHK(g->err, launch_dec_out(ps, g->out.layout, otab, (const DecOutPos*)(g->out.d_tabx + (size_t)S * sizeof(DecPos)), npos, g->out.rd.d_stage, st));
         HIPCHK(g->err, hipMemcpyAsync(g->out.h_set[oset], g->out.rd.d_stage, obytes, hipMemcpyDeviceToHost, st));
         HIPCHK(g->err, hipEventRecord(g->out.done[oset], st));
         g->out.cur = oset; g->out.count = std::min(2, g->out.count + 1);
@@ -463,8 +460,8 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         s.last_serial = g->step_serial;
         s.parser.commit();
         if (is_ref) {   // sliding window (8.2.5.3)
-            s.cur = (s.cur + 1) % e->nbuf;
-            s.have_refs = std::min(s.have_refs + 1, std::min(s.max_refs, e->nrefs));
+            s.cur = (s.cur + 1) % ps->nbuf;
+            s.have_refs = std::min(s.have_refs + 1, std::min(s.max_refs, ps->nbuf - 1));
         }
         s.pictures++;
         got[i] = 1;
@@ -487,12 +484,12 @@ int64_t dg_read(mi355x_h264_dec_group* g, int stream, void* dst, size_t cap, boo
     if (cap < need) return MI355X_H264_E_ARG;
     if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
     if (const int wrc = dg_wait(g)) return wrc;   // the picture asked for may still be in flight
-    const mi355x_h264_encoder* e = g->eng;
+    const PicStore* const ps = &g->store;
     uint8_t* o = (uint8_t*)dst;
     const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     for (int p = 0; p < 3; p++) {
-        const size_t pw = p ? w / 2 : w, ph = p ? h / 2 : h, pitch = p ? (size_t)e->cw / 2 : (size_t)e->cw;
-        const uint8_t* plane = e->d_plane_base[p] + (size_t)stream * (p ? e->st_c : e->st_y) + (size_t)s.last * (p ? e->st_ring_c : e->st_ring_y);
+        const size_t pw = p ? w / 2 : w, ph = p ? h / 2 : h, pitch = p ? (size_t)ps->cw / 2 : (size_t)ps->cw;
+        const uint8_t* plane = ps->d_plane_base[p] + (size_t)stream * (p ? ps->st_c : ps->st_y) + (size_t)s.last * (p ? ps->st_ring_c : ps->st_ring_y);
         const uint8_t* src = plane + (size_t)(p ? s.crop_y / 2 : s.crop_y) * pitch + (size_t)(p ? s.crop_x / 2 : s.crop_x);
         if (hipMemcpy2D(o, pw, src, pitch, pw, ph, kind) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipMemcpy2D");
         o += pw * ph;
@@ -525,17 +522,18 @@ int64_t dg_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* d
     if (!dst) return (int64_t)total;
     if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
     if (const int wrc = dg_wait(g)) return wrc;   // the pictures asked for may still be in flight
-    const mi355x_h264_encoder* e = g->eng;
-    HIPCHK(g->err, hipStreamSynchronize(e->stream));   // (an armed step's copy out of the staging buffer; nothing else is queued)
+    const PicStore* const ps = &g->store;
+    hipStream_t st = g->sync.st;
+    HIPCHK(g->err, hipStreamSynchronize(st));   // (an armed step's copy out of the staging buffer; nothing else is queued)
     DecOutBuf& b = g->out.rd;
     if (out_reserve(g->mem, b, to_device ? 0 : total, to_device ? 0 : total) != hipSuccess)
         return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the output staging (%s)", t_failed_call);
     memcpy(b.h_tab, rows, (size_t)n * sizeof(DecOutPos));
     g->last[9] = g->last[10] = 0;
-    HIPCHK(g->err, launch_dec_out(e, layout, rows, b.d_tab, n, to_device ? (uint8_t*)dst : b.d_stage, e->stream));
+    HIPCHK(g->err, launch_dec_out(ps, layout, rows, b.d_tab, n, to_device ? (uint8_t*)dst : b.d_stage, st));
     g->last[9] = 1;
-    if (!to_device) { HIPCHK(g->err, hipMemcpyAsync(b.h_stage, b.d_stage, total, hipMemcpyDeviceToHost, e->stream)); g->last[10] = 1; }
-    HIPCHK(g->err, hipStreamSynchronize(e->stream));
+    if (!to_device) { HIPCHK(g->err, hipMemcpyAsync(b.h_stage, b.d_stage, total, hipMemcpyDeviceToHost, st)); g->last[10] = 1; }
+    HIPCHK(g->err, hipStreamSynchronize(st));
     if (!to_device) memcpy(dst, b.h_stage, total);
     return (int64_t)total;
 }
@@ -545,10 +543,10 @@ int dg_set_output(mi355x_h264_dec_group* g, int layout, int row_align)
     if (!g) return MI355X_H264_E_ARG;
     if (layout == -1) { g->out.armed = false; g->out.count = 0; g->last[7] = g->last[8] = 0; return MI355X_H264_OK; }
     if (!out_args_ok(layout, row_align)) return MI355X_H264_E_ARG;
-    if (g->eng) {   // the sets may be made anew for this layout by the next step: nothing may be on its way into them
+    if (g->store.made()) {   // the sets may be made anew for this layout by the next step: nothing may be on its way into them
         if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
         if (const int wrc = dg_wait(g)) return wrc;
-        HIPCHK(g->err, hipStreamSynchronize(g->eng->stream));
+        HIPCHK(g->err, hipStreamSynchronize(g->sync.st));
     }
     g->out.armed = true; g->out.ready = false; g->out.layout = layout; g->out.row_align = row_align; g->out.count = 0;
     return MI355X_H264_OK;

@@ -62,8 +62,8 @@ hipError_t out_reserve(DevMem& mem, DecOutBuf& b, size_t dev_bytes, size_t host_
     return hipSuccess;
 }
 
-// ONE launch for the n pictures of rows[] (d_tab: the same rows as the device reads them) out of engine e's ring into dst
-hipError_t launch_dec_out(const mi355x_h264_encoder* e, int layout, const DecOutPos* rows, const DecOutPos* d_tab, int n, uint8_t* dst, hipStream_t st)
+// ONE launch for the n pictures of rows[] (d_tab: the same rows as the device reads them) out of the store's ring into dst
+hipError_t launch_dec_out(const PicStore* s, int layout, const DecOutPos* rows, const DecOutPos* d_tab, int n, uint8_t* dst, hipStream_t st)
 {
     int max_bytes = 0, max_rows = 0;
     for (int i = 0; i < n; i++) {
@@ -72,9 +72,9 @@ hipError_t launch_dec_out(const mi355x_h264_encoder* e, int layout, const DecOut
         max_rows = std::max(max_rows, layout == DEC_OUT_RGBA ? h : (layout == DEC_OUT_I420 ? h + 2 * (h / 2) : h + h / 2));
     }
     DecOutParams P{};
-    P.y = e->d_plane_base[0]; P.u = e->d_plane_base[1]; P.v = e->d_plane_base[2];
-    P.st_y = e->st_y; P.st_c = e->st_c; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c;
-    P.pitch = e->cw; P.dst = dst; P.tab = d_tab;
+    P.y = s->d_plane_base[0]; P.u = s->d_plane_base[1]; P.v = s->d_plane_base[2];
+    P.st_y = s->st_y; P.st_c = s->st_c; P.st_ring_y = s->st_ring_y; P.st_ring_c = s->st_ring_c;
+    P.pitch = s->cw; P.dst = dst; P.tab = d_tab;
     // a row of b bytes that starts anywhere touches at most b / 16 + 2 chunks of 16 aligned bytes
     const dim3 grid((unsigned)((max_bytes / 16 + 2 + 63) / 64), (unsigned)((max_rows + 4 * DEC_OUT_ROWS - 1) / (4 * DEC_OUT_ROWS)), (unsigned)n), block(64, 4);
     switch (layout) {

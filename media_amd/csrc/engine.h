@@ -1,103 +1,11 @@
 // media_amd/csrc/engine.h -- the encoder engine behind include/mi355x_h264.h: device memory, streams, access-unit
-// slots, one lockstep step of launches (submit_step), the wait for it and the host's finish of every access unit.  The
-// stream hub (hub.h) and the decoder groups (dec_group.h) each drive one engine.  Part of the one translation unit
-// mi355x_h264.hip, which includes the kernels before this file.
+// slots, one lockstep step of launches (submit_step), the wait for it and the host's finish of every access unit.  An engine is
+// a picture store (pic_store.h: ring, per-macroblock arrays, hand-off granules, flags, serials) plus what coding a stream takes.
+// The stream hub (hub.h) drives one engine; the decoder groups (dec_group.h) own a store and no engine.  Part of the one
+// translation unit mi355x_h264.hip, which includes the kernels before this file.
 #pragma once
 
-#define HIPCHK(err, call)                                                                                    \
-    do {                                                                                                     \
-        hipError_t _r = (call);                                                                              \
-        if (_r != hipSuccess) return set_err((err), MI355X_H264_E_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
-    } while (0)
-// for the set-up functions that hand the hipError_t on (their callers undo and translate): the call that failed, for the report
-namespace { thread_local const char* t_failed_call = ""; }
-#define HIPTRY(call)                                                      \
-    do {                                                                  \
-        hipError_t _r = (call);                                           \
-        if (_r != hipSuccess) { t_failed_call = #call; return _r; }       \
-    } while (0)
-
 namespace {
-
-// Every device or pinned allocation of an owner (engine, hub, decoder) is registered where it is made and freed in one loop.
-struct DevMem {
-    struct Block { void* p; bool pinned; };
-    std::vector<Block> blocks;
-    template <class T> hipError_t dev(T** p, size_t bytes, bool zero = false)
-    {
-        HIPTRY(hipMalloc((void**)p, bytes));
-        blocks.push_back({*p, false});
-        if (zero) HIPTRY(hipMemset(*p, 0, bytes));
-        return hipSuccess;
-    }
-    template <class T> hipError_t pinned(T** p, size_t bytes)
-    {
-        HIPTRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
-        blocks.push_back({*p, true});
-        return hipSuccess;
-    }
-    // both halves of a staging pair that comes with its first use: whichever is still missing
-    template <class T> bool pair(T** d, T** h, size_t bytes)
-    {
-        if (!*d && dev(d, bytes) != hipSuccess) *d = nullptr;
-        if (*d && !*h && pinned(h, bytes) != hipSuccess) *h = nullptr;
-        return *d && *h;
-    }
-    // one block back ahead of the others (a staging buffer that has to grow); nothing may be using it any more
-    void drop(void* p)
-    {
-        for (size_t i = 0; i < blocks.size(); i++)
-            if (blocks[i].p == p) {
-                if (blocks[i].pinned) (void)hipHostFree(p); else (void)hipFree(p);
-                blocks.erase(blocks.begin() + (long)i);
-                return;
-            }
-    }
-    void free_all() { for (const Block& b : blocks) { if (b.pinned) (void)hipHostFree(b.p); else (void)hipFree(b.p); } blocks.clear(); }
-};
-
-// What one step in flight needs to be launched and waited for: its stream pair (entropy coding forks to ec), the fork /
-// join events, the event behind its last command and the wavefront kernels' time-out flag (pinned).  An engine slot and
-// a hub context each hold one.
-struct StepSync {
-    hipStream_t st = nullptr, ec = nullptr;
-    hipEvent_t recon_ready = nullptr, entropy_done = nullptr, done = nullptr;
-    unsigned* h_err = nullptr;
-    bool own_streams = false;
-};
-// st == nullptr: a stream pair of its own (one stream for both when one_stream); else the caller's pair
-hipError_t sync_create(StepSync& y, hipStream_t st, hipStream_t ec, bool one_stream)
-{
-    if (!st) {
-        y.own_streams = true;
-        HIPTRY(hipStreamCreateWithFlags(&y.st, hipStreamNonBlocking));
-        if (one_stream) y.ec = y.st;
-        else HIPTRY(hipStreamCreateWithFlags(&y.ec, hipStreamNonBlocking));
-    } else { y.st = st; y.ec = ec; }
-    for (hipEvent_t* ev : {&y.done, &y.recon_ready, &y.entropy_done}) HIPTRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    HIPTRY(hipHostMalloc((void**)&y.h_err, sizeof(unsigned), hipHostMallocDefault));
-    *y.h_err = 0;
-    return hipSuccess;
-}
-void sync_destroy(StepSync& y)
-{
-    if (y.own_streams && y.st) {
-        (void)hipStreamSynchronize(y.st);
-        if (y.ec && y.ec != y.st) { (void)hipStreamSynchronize(y.ec); (void)hipStreamDestroy(y.ec); }
-        (void)hipStreamDestroy(y.st);
-    }
-    for (hipEvent_t ev : {y.done, y.recon_ready, y.entropy_done}) if (ev) (void)hipEventDestroy(ev);
-    if (y.h_err) (void)hipHostFree(y.h_err);
-    y = StepSync();
-}
-// the wavefront kernels' time-out flag of a finished step: read, cleared (it is per report) and put into words
-int handoff_timeout(StepSync& y, char (&err)[256])
-{
-    const unsigned flag = *y.h_err;
-    if (!flag) return MI355X_H264_OK;
-    *y.h_err = 0;
-    return set_err(err, MI355X_H264_E_INTERNAL, "wavefront kernel hand-off timed out (flag %u)", flag);
-}
 
 constexpr int NSLOT = 3;          // access-unit slots in flight
 
@@ -119,53 +27,35 @@ struct Slot {
 
 }  // namespace
 
-struct mi355x_h264_encoder {
+struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed GOPs / streams encoded together; nbuf = nrefs + 1)
     mi355x_h264_config cfg{};
-    int mbw = 0, mbh = 0, cw = 0, ch = 0, nmb = 0, level_idc = 0;
-    int device = 0;
-    int G = 1;                               // lockstep batch: closed GOPs / streams encoded together
+    int level_idc = 0;
     int nsl = 1;                             // slices per picture: bands of sl.rows macroblock rows
     SliceRows sl{};
     size_t slice_cap = 0;                    // bytes of payload buffer per slice (multiple of 16)
     // slice bands over several GPUs: this instance codes slices b_sl0 .. b_sl0 + b_nsl - 1 = rows b_row0 .. b_row0 + b_rows - 1
     int b_sl0 = 0, b_nsl = 1, b_row0 = 0, b_rows = 0, b_nmb = 0;
-    size_t st_y = 0, st_c = 0, st_bitbuf_bytes = 0, st_au = 0, st_handoff = 0;  // per-item strides
+    size_t st_bitbuf_bytes = 0, st_au = 0;   // per-item strides
     hipStream_t stream = nullptr;
     hipStream_t stream_ec = nullptr;         // entropy coding runs here, beside the deblocking wavefront (= stream when the process holds many engines)
     std::atomic<int>* counted_live = nullptr;
-    enum { MAX_REFS = 3 };
-    int nrefs = 1, nbuf = 2;                 // reference frames searched (config.refs) and reconstruction buffers (nrefs + 1)
-    uint8_t* d_planes[MAX_REFS + 1][3] = {{nullptr}};  // ring: [index][plane]; `cur` is written, cur - 1 - r (mod nbuf) is ref_idx_l0 r
-    // the planes lie [batch item][ring slot]: d_planes[b][p] = d_plane_base[p] + b * st_ring, st_y / st_c (the item strides) = nbuf
-    // ring strides - so that an indirect launch (stream hub) can address every item's OWN ring slot from one base pointer
-    uint8_t* d_plane_base[3] = {nullptr, nullptr, nullptr};
-    size_t st_ring_y = 0, st_ring_c = 0;
+    enum { MAX_REFS = MAX_BUF - 1 };
+    int nrefs = 1;                           // reference frames searched (config.refs); in the ring `cur` is written, cur - 1 - r (mod nbuf) is ref_idx_l0 r
     QpEntry* d_qtab = nullptr;               // [52] quantiser constants by QP (indirect launches)
     int nslots = NSLOT;                      // access-unit slots allocated (the hub's engine needs one)
     uint8_t* d_pre[3] = {nullptr};           // copy of the reconstruction before the loop filter (debug)
     PicSeq seq;                              // seq.cur: index written by the picture being encoded
     bool pair_filter = true;                 // two macroblock rows per wave in the loop filter for lockstep batches of pair_min_batch pictures or more
     int pair_min_batch = 8;                  // (MI355X_H264_PAIR_FILTER=N sets it, 0 turns the pair form off)
-    MbInfo* d_mb = nullptr;
-    int16_t* d_levels = nullptr;
     int16_t* d_mvd = nullptr;
-    uint8_t* d_aux = nullptr;                // [G][nmb][16] Intra4x4 modes
-    int16_t* d_mvq = nullptr;                // [G][nmb][8] vectors of the four 8x8 quadrants of inter macroblocks
     uint32_t* d_me_total = nullptr;          // [G][nmb] best motion cost so far over the reference pictures (k_me, one launch each)
     int* d_pmv = nullptr;                    // [G][nmb] the previous picture's vectors, parked for the later launches
     uint16_t* d_slotbits = nullptr;
     unsigned long long* d_slotcode = nullptr;
     uint32_t* d_mbbits = nullptr;
-    unsigned* d_anybs = nullptr;             // [G] picture serial when any boundary strength is non-zero
-    unsigned* d_anypcm = nullptr;            // [G] == pic_serial: the picture holds an I_PCM macroblock (not loop-filtered)
-    unsigned* d_anyintra = nullptr;          // [G] == pic_serial: P picture with macroblocks for the intra pass
-    unsigned pic_serial = 0;                 // changes every picture, never 0
     int32_t* d_prevcoded = nullptr;          // [G][nmb + 1] skip-run helper (k_skip_scan)
-    unsigned long long* d_handoff = nullptr; // row-to-row hand-off of the wavefront kernels
-    uint32_t* d_bs = nullptr;                // boundary strengths, 32 B per macroblock
     uint16_t* d_me_cost = nullptr;           // [G][nmb] per-macroblock motion cost (scene-change statistic)
     std::vector<uint32_t> last_me_cost;      // of the last finished picture, per batch item
-    unsigned serial = 0;
     bool diag_mode = false;                  // debug: one launch per wavefront step instead
     uint8_t* d_stage = nullptr;              // device copy of a host-supplied picture
     uint8_t* h_stage = nullptr;              // pinned staging for strided host input
@@ -176,7 +66,6 @@ struct mi355x_h264_encoder {
     int next_slot = 0;
     StreamShape shape{};                     // what the parameter sets and slice headers are written from
     std::vector<uint8_t> sps_pps;            // Annex-B SPS + PPS NALs
-    DevMem mem;                              // every hipMalloc / hipHostMalloc of this engine
     std::vector<std::vector<uint8_t>> esc_buf;  // slow path: escaped access unit, per batch item
     int idr_step = 1;                        // idr_pic_id stride between the batch items
     bool after_injected = false;             // the last picture came through mi355x_h264_debug_code_syntax
@@ -287,47 +176,12 @@ struct Step {
         else hipLaunchKernelGGL(KF, grid, block, 0, stream, __VA_ARGS__);                \
     } while (0)
 
-// ---- the parameter blocks of the kernels, as far as they come from the engine alone (submit_step and the decoder groups' dg_step
-// add what is theirs) ----
-inline unsigned next_nonzero(unsigned& serial) { serial = serial == 0xFFFFFFFFu ? 1u : serial + 1u; return serial; }   // changes every time, never 0
-
+// the store's part of the frame parameters and what the encoder's kernels (motion search, entropy coding) take besides
 FrameParams frame_params(mi355x_h264_encoder* e)   // takes the next picture serial
 {
-    FrameParams P{};
-    P.cw = e->cw; P.ch = e->ch; P.mbw = e->mbw; P.mbh = e->mbh;
-    P.mb = e->d_mb; P.levels = e->d_levels; P.mvd = e->d_mvd; P.mvq = e->d_mvq; P.aux = e->d_aux; P.me_cost = e->d_me_cost; P.me_total = e->d_me_total; P.pmv = e->d_pmv;
-    P.st_y = e->st_y; P.st_c = e->st_c; P.st_mb = e->nmb;
-    P.mbdiv.inv = recip32(e->mbw);
-    P.anypcm = e->d_anypcm; P.anyintra = e->d_anyintra; P.pic_serial = next_nonzero(e->pic_serial);
+    FrameParams P = store_frame_params(e);
+    P.mvd = e->d_mvd; P.me_cost = e->d_me_cost; P.me_total = e->d_me_total; P.pmv = e->d_pmv;
     return P;
-}
-IntraRowParams intra_row_params(mi355x_h264_encoder* e, const FrameParams& P, unsigned* h_err, int npic)   // takes the next wavefront serial
-{
-    IntraRowParams R{};
-    R.p = P; R.handoff = e->d_handoff; R.st_handoff = e->st_handoff; R.err = h_err;
-    R.serial = next_nonzero(e->serial);
-    R.npic = npic;
-    return R;
-}
-// pl: the planes being filtered (or their base: indirect launches); qp: the picture's (thresholds of every edge unless the launch reads mbqp)
-DbParams db_params(const mi355x_h264_encoder* e, uint8_t* const pl[3], const SliceRows& sl, int qp)
-{
-    DbParams D{};
-    for (int p = 0; p < 3; p++) D.pl[p] = pl[p];
-    D.mb = e->d_mb; D.cw = e->cw; D.ch = e->ch; D.mbw = e->mbw; D.mbh = e->mbh; D.sl = sl; D.bs = (const uint8_t*)e->d_bs;
-    fill_filter_thresholds(D, qp);
-    return D;
-}
-DbRowParams db_row_params(const mi355x_h264_encoder* e, const DbParams& D, unsigned* h_err, unsigned serial, unsigned pic_serial, int row0, int npic)
-{
-    DbRowParams R{};
-    R.d = D; R.handoff = e->d_handoff; R.err = h_err;
-    R.st_y = e->st_y; R.st_c = e->st_c; R.st_handoff = e->st_handoff; R.st_mb = e->nmb;
-    R.serial = serial; R.row0 = row0;
-    R.bs = e->d_bs; R.anybs = e->d_anybs;
-    R.anypcm = e->d_anypcm; R.anyintra = e->d_anyintra; R.pic_serial = pic_serial;
-    R.npic = npic;
-    return R;
 }
 
 int submit_step(mi355x_h264_encoder* e, Step& T)
@@ -652,7 +506,7 @@ void destroy_engine(mi355x_h264_encoder* e)
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->stream_ec && e->stream_ec != e->stream) (void)hipStreamSynchronize(e->stream_ec);
-    e->mem.free_all();
+    pic_store_destroy(*e);   // (its list holds the engine's own allocations too)
     for (auto& S : e->slots) {
         sync_destroy(S.sync);
         for (auto& ev : S.evs) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -664,11 +518,11 @@ void destroy_engine(mi355x_h264_encoder* e)
     delete e;
 }
 
-// streams, device and pinned memory of a configured engine
+// the store, then what is the encoder's alone: streams, device and pinned memory of a configured engine
 hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
 {
     DevMem& M = e->mem;
-    HIPTRY(hipSetDevice(e->device));
+    HIPTRY(pic_store_create(*e, e->device, e->mbw, e->mbh, e->G, e->nbuf));
     HIPTRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     // Entropy coding normally runs on a stream of its own beside the loop filter (shorter picture latency).  A process that
     // holds many engines (the plugin surface with many streams: one engine per VideoEncoder object) would then ask for more
@@ -684,12 +538,6 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
     }
     const size_t ysz = (size_t)e->cw * e->ch;
     const size_t Gn = (size_t)e->G, nmb = Gn * e->nmb;   // (nmb: macroblocks of all batch items)
-    e->st_ring_y = ysz + 256; e->st_ring_c = ysz / 4 + 256;
-    e->st_y = e->st_ring_y * e->nbuf; e->st_c = e->st_ring_c * e->nbuf;
-    for (int p = 0; p < 3; p++) {
-        HIPTRY(M.dev(&e->d_plane_base[p], (p ? e->st_c : e->st_y) * Gn, true));
-        for (int b = 0; b < e->nbuf; b++) e->d_planes[b][p] = e->d_plane_base[p] + (size_t)b * (p ? e->st_ring_c : e->st_ring_y);
-    }
     for (int p = 0; p < 3; p++) HIPTRY(M.dev(&e->d_pre[p], (p ? e->st_ring_c : e->st_ring_y) * Gn));
     {
         std::vector<QpEntry> qt(52);
@@ -697,21 +545,13 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
         HIPTRY(M.dev(&e->d_qtab, 52 * sizeof(QpEntry)));
         HIPTRY(hipMemcpy(e->d_qtab, qt.data(), 52 * sizeof(QpEntry), hipMemcpyHostToDevice));
     }
-    HIPTRY(M.dev(&e->d_mb, nmb * sizeof(MbInfo), true));
-    HIPTRY(M.dev(&e->d_levels, nmb * LV_STRIDE * sizeof(int16_t)));
     HIPTRY(M.dev(&e->d_mvd, nmb * 8 * sizeof(int16_t)));
-    HIPTRY(M.dev(&e->d_mvq, nmb * 8 * sizeof(int16_t), true));
     HIPTRY(M.dev(&e->d_me_total, nmb * sizeof(uint32_t)));
     HIPTRY(M.dev(&e->d_pmv, nmb * sizeof(int)));
-    HIPTRY(M.dev(&e->d_aux, nmb * 16, true));
     HIPTRY(M.dev(&e->d_slotbits, nmb * 32 * sizeof(uint16_t)));
     HIPTRY(M.dev(&e->d_slotcode, nmb * 32 * sizeof(unsigned long long)));
     HIPTRY(M.dev(&e->d_mbbits, nmb * sizeof(uint32_t)));
-    for (unsigned** flag : {&e->d_anybs, &e->d_anypcm, &e->d_anyintra}) HIPTRY(M.dev(flag, Gn * sizeof(unsigned), true));
     HIPTRY(M.dev(&e->d_prevcoded, Gn * (e->nmb + 1) * sizeof(int32_t)));
-    e->st_handoff = (size_t)e->nmb * 24;
-    HIPTRY(M.dev(&e->d_handoff, Gn * e->st_handoff * sizeof(unsigned long long), true));
-    HIPTRY(M.dev(&e->d_bs, nmb * 32));
     HIPTRY(M.dev(&e->d_me_cost, nmb * sizeof(uint16_t), true));
     e->frame_bytes = (size_t)e->cfg.width * e->cfg.height * 3 / 2;
     HIPTRY(M.dev(&e->d_stage, e->frame_bytes + 256));
@@ -751,12 +591,7 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
 int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool hub_engine)
 {
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
-    {   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): an engine has two streams, a stream hub seven, and
-        // a host process runs several.  Ask for more before the runtime comes up - unless the host has chosen (measured: 64
-        // plugin streams 7.4 k fps on 4 queues, 10.4 k on 32).  Has no effect once another HIP user has initialised the runtime.
-        static std::once_flag once;
-        std::call_once(once, [] { setenv("GPU_MAX_HW_QUEUES", "16", 0); });
-    }
+    ask_for_hw_queues();   // (here, not only in the store's create: the device count below brings the runtime up)
     *out = nullptr;
     if (cfg->width < 16 || cfg->height < 16 || cfg->width > 4096 || cfg->height > 4096 || ((cfg->width | cfg->height) & 1) ||
         cfg->qp < 10 || cfg->qp > 51 || cfg->gop < 1 || (cfg->profile_idc != 66 && cfg->profile_idc != 77 && cfg->profile_idc != 100) ||

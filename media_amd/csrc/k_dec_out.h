@@ -25,7 +25,7 @@
 // A chunk that a row covers only in part (the row starts or ends inside it: widths that are no multiple of 16, tight rows) is
 // written sample by sample (byte, pair, pixel) by the same code path, so every even width is served by one kernel and no byte
 // outside a row is touched.  Reads stay inside the planes' allocation: a few bytes beyond the 16 asked for, and every ring slot
-// is followed by 256 spare bytes (engine.h, st_ring_y / st_ring_c).  No LDS, no scratch.
+// is followed by 256 spare bytes (pic_store.h, st_ring_y / st_ring_c).  No LDS, no scratch.
 #pragma once
 
 enum { DEC_OUT_I420 = 0, DEC_OUT_NV12 = 1, DEC_OUT_NV21 = 2, DEC_OUT_RGBA = 3, DEC_OUT_ROWS = 8 };
@@ -36,7 +36,7 @@ struct DecOutPos {
     unsigned long long reserved;
 };
 struct DecOutParams {
-    const uint8_t* y; const uint8_t* u; const uint8_t* v;   // the engine's plane bases (d_plane_base)
+    const uint8_t* y; const uint8_t* u; const uint8_t* v;   // the store's plane bases (d_plane_base)
     size_t st_y, st_c, st_ring_y, st_ring_c;               // bytes between items / between the ring slots of an item
     int pitch;                                              // coded width
     uint8_t* dst;

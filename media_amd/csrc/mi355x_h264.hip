@@ -1,6 +1,7 @@
 // media_amd/csrc/mi355x_h264.hip -- the C ABI of include/mi355x_h264.h and include/mi355x_h264_dec.h.  The library is this ONE
 // translation unit: the kernels (k_*.h, rgba_kernels.h), host_framing.h (parameter sets, slice header, NAL escaping, tables; no
-// HIP), engine.h (mi355x_h264_encoder), hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side), dec_group.h
+// HIP), pic_store.h (what encoder and decoder share: ring, per-macroblock arrays, flags), engine.h (mi355x_h264_encoder),
+// hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side), dec_group.h
 // (decoder groups) and decoder.h (the decoder peer: a group of one stream).  Every entry point below checks its arguments and
 // calls into one of them.  There is no CPU encode path:
 // without a HIP device create() fails.
@@ -35,6 +36,7 @@ using namespace h264;
 #include "host_framing.h"
 #include "rgba_kernels.h"
 #include "k_dec_out.h"
+#include "pic_store.h"
 #include "engine.h"
 #include "hub_sched.h"
 #include "hub.h"
@@ -443,8 +445,9 @@ int mi355x_h264_dec_group_create(int device, int streams, mi355x_h264_dec_group*
     g->st = new (std::nothrow) DecGroupStream[streams];
     if (!g->st) { delete g; return MI355X_H264_E_NOMEM; }
     if (hipSetDevice(device) != hipSuccess || hipEventCreateWithFlags(&g->up_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g->up_done[1], hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&g->up_done[1], hipEventDisableTiming) != hipSuccess || sync_create(g->sync, nullptr, nullptr, true) != hipSuccess) {
         for (hipEvent_t ev : g->up_done) if (ev) (void)hipEventDestroy(ev);
+        sync_destroy(g->sync);
         delete[] g->st;
         delete g;
         return MI355X_H264_E_HIP;
@@ -463,15 +466,14 @@ void mi355x_h264_dec_group_destroy(mi355x_h264_dec_group* g)
     if (!g) return;
     g->sched.stop();
     (void)hipSetDevice(g->device);
-    if (g->eng) { (void)dg_wait(g); (void)hipStreamSynchronize(g->eng->stream); }
+    (void)dg_wait(g);
+    (void)hipStreamSynchronize(g->sync.st);   // (an armed step's copy, the uploads out of both pinned sets)
+    dg_free_geometry(g);
     for (int k = 0; k < 2; k++) {
         if (g->up_done[k]) (void)hipEventDestroy(g->up_done[k]);
         if (g->out.done[k]) (void)hipEventDestroy(g->out.done[k]);
-        if (g->h_big[k]) (void)hipHostFree(g->h_big[k]);
     }
-    if (g->d_big) (void)hipFree(g->d_big);
-    g->mem.free_all();
-    if (g->eng) destroy_engine(g->eng);
+    sync_destroy(g->sync);
     delete[] g->st;
     delete g;
 }
@@ -497,7 +499,7 @@ int mi355x_h264_dec_group_decode(mi355x_h264_dec_group* g, const uint8_t* const*
 int mi355x_h264_dec_group_sync(mi355x_h264_dec_group* g)
 {
     if (!g) return MI355X_H264_E_ARG;
-    if (!g->eng) return MI355X_H264_OK;
+    if (!g->store.made()) return MI355X_H264_OK;
     if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
     return dg_wait(g);
 }
@@ -516,8 +518,8 @@ int mi355x_h264_dec_group_picture_info(const mi355x_h264_dec_group* g, int strea
     if (!g || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0) return MI355X_H264_E_ARG;
     if (w) *w = g->st[stream].width;
     if (h) *h = g->st[stream].height;
-    if (cw) *cw = 16 * g->mbw;
-    if (ch) *ch = 16 * g->mbh;
+    if (cw) *cw = g->store.cw;
+    if (ch) *ch = g->store.ch;
     return MI355X_H264_OK;
 }
 
@@ -527,12 +529,12 @@ int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group* g, int str
 int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group* g, int stream, int plane, void* dst, size_t cap)
 {
     if (!g || !dst || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0 || plane < 0 || plane > 2) return MI355X_H264_E_ARG;
-    const mi355x_h264_encoder* e = g->eng;
-    const size_t n = (size_t)e->cw * e->ch / (plane ? 4 : 1);
+    const PicStore* const ps = &g->store;
+    const size_t n = (size_t)ps->cw * ps->ch / (plane ? 4 : 1);
     if (cap < n) return MI355X_H264_E_ARG;
     if (hipSetDevice(g->device) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipSetDevice");
     if (const int wrc = dg_wait(g)) return wrc;
-    const uint8_t* src = e->d_plane_base[plane] + (size_t)stream * (plane ? e->st_c : e->st_y) + (size_t)g->st[stream].last * (plane ? e->st_ring_c : e->st_ring_y);
+    const uint8_t* src = ps->d_plane_base[plane] + (size_t)stream * (plane ? ps->st_c : ps->st_y) + (size_t)g->st[stream].last * (plane ? ps->st_ring_c : ps->st_ring_y);
     if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return set_err(g->err, MI355X_H264_E_HIP, "hipMemcpy");
     return (int64_t)n;
 }
@@ -540,8 +542,12 @@ int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group* g, int stream, 
 int mi355x_h264_dec_group_last_step(const mi355x_h264_dec_group* g, int64_t* out, int n)
 {
     if (!g || !out || n < 1) return MI355X_H264_E_ARG;
-    const int m = n >= 11 ? 11 : (n >= 9 ? 9 : std::min(n, 7));   // (a caller with an earlier layout's slots gets those)
-    for (int i = 0; i < m; i++) out[i] = g->last[i];
+    const int m = n >= 13 ? 13 : (n >= 11 ? 11 : (n >= 9 ? 9 : std::min(n, 7)));   // (a caller with an earlier layout's slots gets those)
+    for (int i = 0; i < std::min(m, 11); i++) out[i] = g->last[i];
+    if (m == 13) {   // what the group holds now: the store's and its own (the parsers' heap is not counted)
+        out[11] = (int64_t)(g->store.mem.dev_bytes + g->mem.dev_bytes);
+        out[12] = (int64_t)(g->store.mem.pinned_bytes + g->mem.pinned_bytes);
+    }
     return m;
 }
 
@@ -617,6 +623,8 @@ int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder* d, int plane, void* dst
 {
     return d ? dec_ret(d, mi355x_h264_dec_group_debug_plane(d->g, 0, plane, dst, cap)) : MI355X_H264_E_ARG;
 }
+
+int mi355x_h264_dec_last_step(const mi355x_h264_decoder* d, int64_t* out, int n) { return d ? mi355x_h264_dec_group_last_step(d->g, out, n) : MI355X_H264_E_ARG; }
 
 int mi355x_h264_dec_timing(const mi355x_h264_decoder* d, uint64_t* pictures, double* parse_ms, double* gpu_ms)
 {

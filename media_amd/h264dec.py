@@ -35,6 +35,7 @@ def _bind():
     L.mi355x_h264_dec_debug_plane.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_dec_debug_plane.restype = C.c_int64
     L.mi355x_h264_dec_sync.argtypes = [vp]
     L.mi355x_h264_dec_timing.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mi355x_h264_dec_last_step.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.mi355x_h264_parser_create.restype = vp
     L.mi355x_h264_parser_destroy.argtypes = [vp]; L.mi355x_h264_parser_destroy.restype = None
     L.mi355x_h264_parser_parse.argtypes = [vp, vp, sz]
@@ -61,7 +62,7 @@ def _bind():
 
 
 def _tensor_ready(tensor):
-    """the gather kernel runs on the engine's own stream, which does not wait for the default stream: whatever torch has queued
+    """the gather kernel runs on the decoder's own stream, which does not wait for the default stream: whatever torch has queued
     on the tensor's device (the fill that made the tensor, say) must be complete before the kernel writes into it"""
     import torch
     torch.cuda.synchronize(tensor.device)
@@ -156,6 +157,12 @@ class Decoder:
         if rc != 0:
             raise EncoderError("dec_sync -> %d: %s" % (rc, lib().mi355x_h264_dec_last_error(self.h).decode()))
 
+    def last_step(self):
+        """DecoderGroup.last_step() of the group of one stream behind this decoder"""
+        v = (C.c_int64 * len(DecoderGroup.STEP))()
+        n = lib().mi355x_h264_dec_last_step(self.h, v, len(v))
+        return dict(zip(DecoderGroup.STEP[:n], list(v)[:n]))
+
     def timing(self):
         n, a, b = C.c_uint64(0), C.c_double(0), C.c_double(0)
         lib().mi355x_h264_dec_timing(self.h, C.byref(n), C.byref(a), C.byref(b))
@@ -163,10 +170,10 @@ class Decoder:
 
 
 class DecoderGroup:
-    """`streams` decoders behind one engine: decode() takes the next access unit of every stream (None: the stream sits this step
+    """`streams` decoders on one picture store: decode() takes the next access unit of every stream (None: the stream sits this step
     out) and reconstructs all their pictures in one set of transfers and launches"""
     STEP = ("serial", "pictures", "launches", "transfers", "parse_threads", "parse_us", "launch_us", "output_launches", "output_transfers",
-            "read_launches", "read_transfers")
+            "read_launches", "read_transfers", "device_bytes", "pinned_bytes")
 
     def __init__(self, streams, device=0):
         L = _bind()
@@ -244,9 +251,9 @@ class DecoderGroup:
 
     def last_step(self):
         """the last step; output_launches / output_transfers: what an armed step added (set_output); read_launches /
-        read_transfers: what the last read_all call made"""
-        v = (C.c_int64 * 11)()
-        n = lib().mi355x_h264_dec_group_last_step(self.h, v, 11)
+        read_transfers: what the last read_all call made; device_bytes / pinned_bytes: device and pinned host memory the group holds now"""
+        v = (C.c_int64 * len(self.STEP))()
+        n = lib().mi355x_h264_dec_group_last_step(self.h, v, len(v))
         return dict(zip(self.STEP[:n], list(v)[:n]))
 
     def read_all(self, layout, row_align=1, device_tensor=None, out=None):
