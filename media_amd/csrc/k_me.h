@@ -86,16 +86,45 @@ __device__ __forceinline__ int me_ab_next() { asm volatile("" ::: "memory"); ret
 #else
 #define ME_AB_PHASE(bit) if constexpr (true)
 #endif
+// -DME_AB_COUNT (measurement build, make ab): which way every macroblock wave leaves section 1 and the integer search.  One bit
+// per event in a wave-uniform register, added at the wave's end (every return) with one vector atomic add; the host reads and
+// clears the ten words with mi355x_h264_me_counts().
+enum { MEC_T1_HIT, MEC_T1_REJ_SUMS, MEC_T1_REJ_LATER, MEC_T2_TRIED, MEC_T2_REJ_LUMA_SUMS, MEC_T2_REJ_CHROMA_DC, MEC_T2_REJ_TRANSFORM,
+       MEC_T2_HIT, MEC_SEEDED_WON, MEC_EXHAUSTIVE, MEC_N };
+#ifdef ME_AB_COUNT
+__device__ unsigned g_me_count[MEC_N];
+struct MeCount {
+    unsigned bits = 0;
+    __device__ __forceinline__ void operator()(int ev) { bits |= 1u << ev; }
+    __device__ __forceinline__ ~MeCount()
+    {
+        const int lane = threadIdx.x;
+        if (lane < MEC_N && ((bits >> lane) & 1u)) atomicAdd(&g_me_count[lane], 1u);
+    }
+};
+}  // namespace h264
+extern "C" __attribute__((visibility("default"))) int mi355x_h264_me_counts(unsigned out[h264::MEC_N], int clear)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h264::g_me_count), h264::MEC_N * sizeof(unsigned)) != hipSuccess) return -1;
+    const unsigned zero[h264::MEC_N] = {};
+    if (clear && hipMemcpyToSymbol(HIP_SYMBOL(h264::g_me_count), zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+namespace h264 {
+#define ME_COUNT(ev) me_count(ev)
+#else
+#define ME_COUNT(ev) ((void)0)
+#endif
 
 
 // four chroma prediction samples (8.4.2.2.2) of plane cp (pitch cs2, chh rows): integer position (x0, y0), eighth-sample
 // fraction (fx, fy); samples clamped at the picture edge exactly as motion compensation does.  Inside the picture the two
 // rows are read as aligned dwords and realigned (v_alignbyte), at the edge sample by sample.
-__device__ __forceinline__ uint32_t chroma_pred4(const uint8_t* cp, int cs2, int chh, int x0, int y0, int fx, int fy)
+// chroma_fetch4: the four samples at (x0, y0) in A, their right neighbours in B, the row below in C and D.
+__device__ __forceinline__ void chroma_fetch4(const uint8_t* cp, int cs2, int chh, int x0, int y0, uint32_t& A, uint32_t& B, uint32_t& C, uint32_t& D)
 {
     const uint8_t* r0 = cp + (size_t)clip3(0, chh - 1, y0) * cs2;
     const uint8_t* r1 = cp + (size_t)clip3(0, chh - 1, y0 + 1) * cs2;
-    uint32_t A, B, C, D;
     if (x0 >= 0 && (x0 & ~3) + 8 <= cs2) {
         const int xa = x0 & ~3, sh = x0 & 3;
         const uint32_t a0 = *(const uint32_t*)(r0 + xa), a1 = *(const uint32_t*)(r0 + xa + 4);
@@ -111,6 +140,11 @@ __device__ __forceinline__ uint32_t chroma_pred4(const uint8_t* cp, int cs2, int
             C |= (uint32_t)r1[xa] << (8 * k); D |= (uint32_t)r1[xb] << (8 * k);
         }
     }
+}
+__device__ __forceinline__ uint32_t chroma_pred4(const uint8_t* cp, int cs2, int chh, int x0, int y0, int fx, int fy)
+{
+    uint32_t A, B, C, D;
+    chroma_fetch4(cp, cs2, chh, x0, y0, A, B, C, D);
     if ((fx | fy) == 0) return A;
     const int w00 = (8 - fx) * (8 - fy), w10 = fx * (8 - fy), w01 = (8 - fx) * fy, w11 = fx * fy;
     uint32_t o = 0;
@@ -118,6 +152,20 @@ __device__ __forceinline__ uint32_t chroma_pred4(const uint8_t* cp, int cs2, int
     for (int k = 0; k < 4; k++)
         o |= (uint32_t)((w00 * byte_of(A, k) + w10 * byte_of(B, k) + w01 * byte_of(C, k) + w11 * byte_of(D, k) + 32) >> 6) << (8 * k);
     return o;
+}
+// The same for a vector of whole luma samples: fractions 0 or 4 (hx, hy: 4), wave-uniform.  The bilinear weights are then 64,
+// 32 + 32 or 4 x 16: a copy, (a + b + 1) >> 1 or (a + b + c + d + 2) >> 2, chosen on the scalar unit
+__device__ __forceinline__ uint32_t chroma_pred4_half(const uint8_t* cp, int cs2, int chh, int x0, int y0, bool hx, bool hy)
+{
+    uint32_t A, B, C, D;
+    chroma_fetch4(cp, cs2, chh, x0, y0, A, B, C, D);
+    if (!hx && !hy) return A;
+    if (!hy) return avg4(A, B);
+    if (!hx) return avg4(A, C);
+    const uint32_t m = 0x00FF00FFu;   // even and odd bytes apart, 16 bits each: 4 * 255 + 2 fits
+    const uint32_t e = (A & m) + (B & m) + (C & m) + (D & m) + 0x00020002u;
+    const uint32_t o = ((A >> 8) & m) + ((B >> 8) & m) + ((C >> 8) & m) + ((D >> 8) & m) + 0x00020002u;
+    return ((e >> 2) & m) | (((o >> 2) & m) << 8);
 }
 
 #ifndef ME_WAVES_MIN
@@ -133,6 +181,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     // the picture from reading a ring slot older than its stream's IDR
     if constexpr (IND) { if (P.nref <= P.rf) return; }
     const int lane = threadIdx.x;
+#ifdef ME_AB_COUNT
+    MeCount me_count;
+#endif
     const int mbi = P.band.row0 * P.mbw + xcd_mb_index(blockIdx.x, P.mbw * P.band.rows), my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
     const int bx = 16 * mx, by = 16 * my;
 
@@ -224,24 +275,64 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     // lane = (4x4 block, row); luma rides in the low and chroma (lanes 0..31) in the high 16 bits of every register,
     // so one packed forward transform (row pass in the lane, column pass over the DPP quad) serves both.  Tried at
     // the zero vector (static content) and, when that fails, at the macroblock's previous-picture vector rounded to
-    // integer samples, if non-zero (scrolling content); a hit fixes the vector and ends the search. ----
+    // integer samples, if non-zero (scrolling content); a hit fixes the vector and ends the search.
+    //
+    // Most waves fail, so every test asks the cheapest exact questions first, each a necessary condition of a hit:
+    //   (a) luma block sums: |sum of a 4x4 block's residual| >= thr_inter[0] (its coefficient (0, 0)) - two byte sums, two quad steps
+    //   (b) chroma DC: the chroma block sums through the 2x2 Hadamard against thr_dc_inter - fetched only behind (a)
+    //   (c) the packed transform, asked once after its first column
+    // Counted on one closed GOP of the bench content (1080p S1, QP 26, seeded search, 29 P pictures, 236 640 macroblocks;
+    // `make ab AB_FLAGS=-DME_AB_COUNT`, tools/me_counts.py; the same figures from the oracle's decisions restated on the CPU):
+    //   zero vector:      hits 0; turned down by (a) 236 640 (all); by (b) or (c) 0
+    //   previous vector:  tried 228 477; hits 81 949 (36 %); turned down by (a) 41 955, by (b) 95 184, by (c) 9 389
+    //   (of the 146 528 failures a luma coefficient of the first column decides 46 439, the chroma DC with luma passing
+    //   completely 88 911, a chroma AC coefficient 3 899; the luma SAD bound P.sad_nz decided none that (a) did not)
+    //   searched 154 691: the seeded test wins 136 141, the exhaustive pass runs 18 550 ----
     if (rf == 0) {
         typedef unsigned short pk16 __attribute__((ext_vector_type(2)));
         const int r = lane & 3, b4 = lane >> 2;
         const int cplz = lane >> 4, cyz = ((lane >> 3) & 1) * 4 + r, cxz = ((lane >> 2) & 1) * 4;   // chroma lane (lanes < 32)
         const uint32_t sy = *(const uint32_t*)(s_src + ((b4 >> 2) * 4 + r) * 16 + (b4 & 3) * 4);
-        const uint32_t sc = lane < 32 ? *(const uint32_t*)(s_srcc + cplz * 64 + cyz * 8 + cxz) : 0u;
-        const uint32_t one = 0x00010001u;
-        const pk16 sA = __builtin_bit_cast(pk16, (r & 1) ? 0xFFFFFFFFu : one);                          // +-1
-        const pk16 mA = __builtin_bit_cast(pk16, r == 1 ? 2u * one : one);
-        const pk16 mB = __builtin_bit_cast(pk16, r < 2 ? one : (r == 2 ? 0xFFFFFFFFu : 0xFFFEFFFEu));    // 1 1 -1 -2
-        // thresholds - 1 per position class (0 even/even, 1 odd/odd, 2 mixed), luma | chroma << 16
-        const uint32_t t0 = (uint32_t)(P.qy.thr_inter[0] - 1) | ((uint32_t)(P.qc.thr_inter[0] - 1) << 16);
-        const uint32_t t1 = (uint32_t)(P.qy.thr_inter[1] - 1) | ((uint32_t)(P.qc.thr_inter[1] - 1) << 16);
-        const uint32_t t2 = (uint32_t)(P.qy.thr_inter[2] - 1) | ((uint32_t)(P.qc.thr_inter[2] - 1) << 16);
-        const pk16 th_even = __builtin_bit_cast(pk16, (r & 1) ? t2 : t0), th_odd = __builtin_bit_cast(pk16, (r & 1) ? t1 : t2);
-        // ry / rc: this lane's four predicted luma / chroma samples (rc = 0 in lanes >= 32)
-        auto quantises_to_nothing = [&](uint32_t ry, uint32_t rc) -> bool {
+        // Cheap exact rejects, each a necessary condition of the transform test behind it.  Coefficient (0, 0) of a 4x4 block's core
+        // transform is the sum of its 16 residuals, so its level is non-zero exactly when |sum of source - sum of prediction| >=
+        // thr_inter[0]: a byte sum per lane (v_sad_u8 against 0) and the two quad steps give it without any transform.
+        const int sysum = (int)__builtin_amdgcn_sad_u8(sy, 0u, 0u);
+        auto quad_sum = [](int v) -> int {
+            v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
+            return v + __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+        };
+        const int tym1 = P.qy.thr_inter[0] - 1;
+        auto luma_sums_reject = [&](uint32_t ry) -> bool {   // wave-uniform: some luma block's coefficient (0, 0) does not vanish
+            const int d = quad_sum(sysum - (int)__builtin_amdgcn_sad_u8(ry, 0u, 0u));
+            return __ballot((unsigned)(d + tym1) > (unsigned)(2 * tym1)) != 0ull;   // |d| >= thr_inter[0]
+        };
+        // chroma DC (8.5.11.1): the four block sums of a plane through the 2x2 Hadamard, against thr_dc_inter.  The sums sit in
+        // every lane of the quads of lanes plane * 16 + block * 4
+        auto chroma_dc_reject = [&](uint32_t sc, uint32_t rc) -> bool {
+            const int dc = quad_sum((int)__builtin_amdgcn_sad_u8(sc, 0u, 0u) - (int)__builtin_amdgcn_sad_u8(rc, 0u, 0u));
+            bool dcnz = false;
+#pragma unroll
+            for (int pl = 0; pl < 2; pl++) {
+                const int d0 = __builtin_amdgcn_readlane(dc, pl * 16), d1 = __builtin_amdgcn_readlane(dc, pl * 16 + 4);
+                const int d2 = __builtin_amdgcn_readlane(dc, pl * 16 + 8), d3 = __builtin_amdgcn_readlane(dc, pl * 16 + 12);
+                const int t = P.qc.thr_dc_inter;
+                dcnz |= iabs(d0 + d1 + d2 + d3) >= t || iabs(d0 - d1 + d2 - d3) >= t || iabs(d0 + d1 - d2 - d3) >= t || iabs(d0 - d1 - d2 + d3) >= t;
+            }
+            return dcnz;
+        };
+        // ry / rc: this lane's four predicted luma / chroma samples, sc: its chroma source samples (both 0 in lanes >= 32).
+        // chroma_dc_reject has answered for the chroma DC already, and the transform leaves it out.  Everything
+        // the transform needs is set up in here, behind the rejects: most waves never come this far
+        auto quantises_to_nothing = [&](uint32_t ry, uint32_t sc, uint32_t rc) -> bool {
+            const uint32_t one = 0x00010001u;
+            const pk16 sA = __builtin_bit_cast(pk16, (r & 1) ? 0xFFFFFFFFu : one);                          // +-1
+            const pk16 mA = __builtin_bit_cast(pk16, r == 1 ? 2u * one : one);
+            const pk16 mB = __builtin_bit_cast(pk16, r < 2 ? one : (r == 2 ? 0xFFFFFFFFu : 0xFFFEFFFEu));    // 1 1 -1 -2
+            // thresholds - 1 per position class (0 even/even, 1 odd/odd, 2 mixed), luma | chroma << 16
+            const uint32_t t0 = (uint32_t)(P.qy.thr_inter[0] - 1) | ((uint32_t)(P.qc.thr_inter[0] - 1) << 16);
+            const uint32_t t1 = (uint32_t)(P.qy.thr_inter[1] - 1) | ((uint32_t)(P.qc.thr_inter[1] - 1) << 16);
+            const uint32_t t2 = (uint32_t)(P.qy.thr_inter[2] - 1) | ((uint32_t)(P.qc.thr_inter[2] - 1) << 16);
+            const pk16 th_even = __builtin_bit_cast(pk16, (r & 1) ? t2 : t0), th_odd = __builtin_bit_cast(pk16, (r & 1) ? t1 : t2);
             pk16 d[4];
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -253,11 +344,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 d[0] = s0 + s1; d[1] = d0 + d0 + d1; d[2] = s0 - s1; d[3] = d0 - d1 - d1;
             }
             uint32_t over = 0;
-            int dc = 0;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                // a residual that does not vanish shows in the first coefficient column (the DC column) nearly always:
-                // ask once after it and spare the other three
+                // a luma coefficient of the first column (the block sum among them) decides a third of the failures only
+                // (table above); the question after it is kept because it is one ballot and spares three columns
                 if (c == 1 && __ballot(over != 0) != 0ull) return false;
                 const pk16 q0 = __builtin_bit_cast(pk16, quad_bcast<0>(__builtin_bit_cast(int, d[c])));
                 const pk16 q1 = __builtin_bit_cast(pk16, quad_bcast<1>(__builtin_bit_cast(int, d[c])));
@@ -265,7 +355,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 const pk16 q3 = __builtin_bit_cast(pk16, quad_bcast<3>(__builtin_bit_cast(int, d[c])));
                 const pk16 A = q0 + sA * q3, B = q1 + sA * q2;
                 const pk16 w = mA * A + mB * B;                        // row r of the 4x4 core transform, column c
-                if (c == 0) dc = (int)(short)w.y;                     // chroma DC of the block where r == 0
                 typedef short spk16 __attribute__((ext_vector_type(2)));
                 const spk16 ws = __builtin_bit_cast(spk16, w);
                 const pk16 aw = __builtin_bit_cast(pk16, __builtin_elementwise_max(ws, -ws));
@@ -273,21 +362,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 if (c == 0 && r == 0) ov &= 0xFFFFu;                   // the chroma DC goes through the 2x2 Hadamard instead
                 over |= ov;
             }
-            // chroma DC: block DCs sit in lanes plane * 16 + block * 4
-            bool dcnz = false;
-#pragma unroll
-            for (int pl = 0; pl < 2; pl++) {
-                const int d0 = __builtin_amdgcn_readlane(dc, pl * 16), d1 = __builtin_amdgcn_readlane(dc, pl * 16 + 4);
-                const int d2 = __builtin_amdgcn_readlane(dc, pl * 16 + 8), d3 = __builtin_amdgcn_readlane(dc, pl * 16 + 12);
-                const int t = P.qc.thr_dc_inter;
-                dcnz |= iabs(d0 + d1 + d2 + d3) >= t || iabs(d0 - d1 + d2 - d3) >= t || iabs(d0 + d1 - d2 - d3) >= t || iabs(d0 - d1 - d2 + d3) >= t;
-            }
-            return !dcnz && __ballot(over != 0) == 0ull;
+            return __ballot(over != 0) == 0ull;
         };
         // Exact shortcut: if every luma coefficient stays below its threshold t_ij, then (the core transform's rows are
         // orthogonal with squared norms 4, 10, 4, 10) the residual energy of a 4x4 block is below E = sum t_ij^2 / (n_i n_j),
         // and by Cauchy-Schwarz the macroblock's SAD below 64 sqrt(E) = P.sad_nz.  A SAD at or above that (a moving
-        // macroblock tested at the zero vector) needs no transform to be turned down.
+        // macroblock tested at the zero vector) needs no transform to be turned down.  It stands behind the block sums and the
+        // chroma DC, which decide everything it decided on the contents counted and tested; taking it out raised
+        // the instructions per wave by 2.8 and was dropped.
         auto luma_sad = [&](uint32_t ry) -> unsigned {
             const int s = row_sum16_dpp((int)__builtin_amdgcn_sad_u8(sy, ry, 0u));
             return (unsigned)(__builtin_amdgcn_readlane(s, 0) + __builtin_amdgcn_readlane(s, 16) + __builtin_amdgcn_readlane(s, 32) + __builtin_amdgcn_readlane(s, 48));
@@ -307,19 +389,38 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 P.me_total[mbi] = 0u;   // settled: later reference pictures are not searched
             }
         };
+        // one test: 0 a hit, else the check that turned it down (1 luma block sums, 2 chroma DC, 3 SAD shortcut or transform)
+        auto test = [&](uint32_t ry, auto&& chroma) -> int {
+            if (luma_sums_reject(ry)) return 1;
+            const uint32_t rc = chroma();
+            const uint32_t sc = lane < 32 ? *(const uint32_t*)(s_srcc + cplz * 64 + cyz * 8 + cxz) : 0u;
+            if (chroma_dc_reject(sc, rc)) return 2;
+            if (luma_sad(ry) >= (unsigned)P.sad_nz) return 3;
+            return quantises_to_nothing(ry, sc, rc) ? 0 : 3;
+        };
         {   // the zero vector: co-located samples
             const uint32_t ry = s_win[(ME_R + ME_AP + (b4 >> 2) * 4 + r) * ME_WDW + (ME_R + ME_AP) / 4 + (b4 & 3)];
-            const uint32_t rc = lane < 32 ? *(const uint32_t*)(s_refc + cplz * 64 + cyz * 8 + cxz) : 0u;
-            if (luma_sad(ry) < (unsigned)P.sad_nz && quantises_to_nothing(ry, rc)) { settle(0, 0, ry, rc); return; }
+            uint32_t rc = 0;
+            const int why = test(ry, [&]() { return rc = lane < 32 ? *(const uint32_t*)(s_refc + cplz * 64 + cyz * 8 + cxz) : 0u; });
+            ME_COUNT(why == 0 ? MEC_T1_HIT : (why == 1 ? MEC_T1_REJ_SUMS : MEC_T1_REJ_LATER));
+            if (why == 0) { settle(0, 0, ry, rc); return; }
         }
         const int rvx = ((pmx + 2) >> 2) * 4, rvy = ((pmy + 2) >> 2) * 4;   // the previous vector rounded to integer samples
         if ((rvx | rvy) != 0) {   // wave-uniform
-            // luma: integer displacement inside the window; chroma: 1/8-sample bilinear (8.4.2.2.2) at fractions 0 or 4,
-            // samples clamped at the picture edge exactly as motion compensation does
+            // luma: integer displacement inside the window; chroma: 1/8-sample bilinear (8.4.2.2.2) at fractions 0 or 4 (averages),
+            // samples clamped at the picture edge exactly as motion compensation does - fetched (ten global loads) only once
+            // the luma block sums have let the wave through
             const uint32_t ry = lds_ld4(winb, (ME_R + ME_AP + (b4 >> 2) * 4 + r + (rvy >> 2)) * ME_WS + ME_R + ME_AP + (b4 & 3) * 4 + (rvx >> 2));
             uint32_t rc = 0;
-            if (lane < 32) rc = chroma_pred4(cplz ? P.ref[2] : P.ref[1], P.cw / 2, P.ch / 2, 8 * mx + cxz + (rvx >> 3), 8 * my + cyz + (rvy >> 3), rvx & 7, rvy & 7);
-            if (luma_sad(ry) < (unsigned)P.sad_nz && quantises_to_nothing(ry, rc)) { settle(rvx, rvy, ry, rc); return; }
+            const int why = test(ry, [&]() {
+                const uint8_t* const cp = cplz ? P.ref[2] : P.ref[1];
+                const int x0 = 8 * mx + cxz + (rvx >> 3), y0 = 8 * my + cyz + (rvy >> 3);
+                if (lane < 32) rc = chroma_pred4_half(cp, P.cw / 2, P.ch / 2, x0, y0, rvx & 4, rvy & 4);
+                return rc;
+            });
+            ME_COUNT(MEC_T2_TRIED);
+            ME_COUNT(why == 0 ? MEC_T2_HIT : (why == 1 ? MEC_T2_REJ_LUMA_SUMS : (why == 2 ? MEC_T2_REJ_CHROMA_DC : MEC_T2_REJ_TRANSFORM)));
+            if (why == 0) { settle(rvx, rvy, ry, rc); return; }
         }
     }
 
@@ -358,13 +459,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                     if (gy == 1 && k == 1) ckey = key;
                     else if (inr && key < nmin) nmin = key;
                 }
-            if (ckey < nmin) { best = ckey; seeded = true; }
+            if (ckey < nmin) { best = ckey; seeded = true; ME_COUNT(MEC_SEEDED_WON); }
         }
     }
 
     // ---- 2. integer full search: lane = (dx, half of the dy range); 16 SAD accumulators per lane, one pass over
     // 31 window rows, every row feeding up to 16 candidates (v_sad_u8, four samples per instruction) ----
     if (!seeded) {
+        ME_COUNT(MEC_EXHAUSTIVE);
         const int dxi = lane & 31, half = lane >> 5;
         const int col = dxi + ME_AP, cdw = col >> 2, sh = col & 3;
         // motion-vector cost and candidate index of every dy, shifted into key position: one table per macroblock
