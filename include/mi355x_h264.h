@@ -203,7 +203,15 @@ enum {
     MI355X_H264_DBG_PRE_U = 6,     /*  mi355x_h264_debug_keep_pre(enc, 1))                  */
     MI355X_H264_DBG_PRE_V = 7,
     MI355X_H264_DBG_MBAUX = 8,     /* 16 B per macroblock: Intra4x4PredMode of the blocks of type-4 macroblocks   */
-    MI355X_H264_DBG_MVQ = 9        /* 8 int16 per macroblock: (x, y) vectors of the four 8x8 quadrants of an inter macroblock */
+    MI355X_H264_DBG_MVQ = 9,       /* 8 int16 per macroblock: (x, y) vectors of the four 8x8 quadrants of an inter macroblock */
+    MI355X_H264_DBG_SRC = 10       /* the tight source picture of the last picture as it lies in the library's own staging memory, where the
+                                    * encoder kernels read it: width * height * 3 / 2 bytes, I420 for I420 and RGBA input (an RGBA
+                                    * picture is always converted into staging, from host or device memory: this is what the conversion
+                                    * wrote), NV12 for NV12 input.  MI355X_H264_E_ARG, with an error text and the handle as usable as
+                                    * before, when there is nothing to read: the last picture was read in place from the caller's device
+                                    * memory (I420 / NV12 device pictures, mi355x_h264_encode_batch_device / _gops_device, a picture of
+                                    * mi355x_h264_debug_code_syntax), or there has been no picture yet.  Reading it changes nothing
+                                    * on the encode path */
 };
 int mi355x_h264_debug_keep_pre(mi355x_h264_encoder *enc, int on);
 /* copies the named device buffer of the last encoded picture (batch item 0) to dst; returns bytes or <0 */

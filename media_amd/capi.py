@@ -17,7 +17,7 @@ LV_STRIDE = 416
 MBINFO_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("type", "u1"), ("i16_mode", "u1"),
                          ("chroma_mode", "u1"), ("cbp", "u1"), ("tc", "u1", (24,))])
 FRAME_IDR, FRAME_P = 1, 3
-DBG_RECON_Y, DBG_RECON_U, DBG_RECON_V, DBG_MBINFO, DBG_LEVELS, DBG_PRE_Y, DBG_PRE_U, DBG_PRE_V, DBG_MBAUX, DBG_MVQ = range(10)
+DBG_RECON_Y, DBG_RECON_U, DBG_RECON_V, DBG_MBINFO, DBG_LEVELS, DBG_PRE_Y, DBG_PRE_U, DBG_PRE_V, DBG_MBAUX, DBG_MVQ, DBG_SRC = range(11)
 K_NAMES = ["me", "tq", "intra", "cavlc", "deblock"]   # index = MI355X_H264_K_* (1: the id is still called K_PMB: k_tq / k_tq8 replaced k_pmb2)
 
 EXPORTS = [
@@ -149,11 +149,15 @@ def _debug_read(obj, fn, what):
         a = np.empty((obj.nmb, 8), np.int16)
     elif what == DBG_LEVELS:
         a = np.empty((obj.nmb, LV_STRIDE), np.int16)
+    elif what == DBG_SRC:   # the tight source picture in staging memory (I420; NV12 for NV12 input), display size, flat
+        a = np.empty(obj.width * obj.height * 3 // 2, np.uint8)
     else:
         raise ValueError("debug_read(%r)" % (what,))
     n = fn(obj.h, what, a.ctypes.data, a.nbytes)
     if n != a.nbytes:
-        raise EncoderError("debug_read(%d) -> %d" % (what, n))
+        err = EncoderError("debug_read(%d) -> %d%s" % (what, n, ": " + obj.last_error() if n == E_ARG else ""))
+        err.rc = n   # (E_ARG for DBG_SRC: the last picture was read in place, there is no staging picture)
+        raise err
     return a
 
 
@@ -372,6 +376,9 @@ class Stream:
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
         self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.width), C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
+
+    def last_error(self):
+        return lib().mi355x_h264_stream_last_error(self.h).decode()
 
     def set_qp(self, qp):
         self._check(lib().mi355x_h264_stream_set_qp(self.h, qp))

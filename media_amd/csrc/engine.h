@@ -59,6 +59,7 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     bool diag_mode = false;                  // debug: one launch per wavefront step instead
     uint8_t* d_stage = nullptr;              // device copy of a host-supplied picture
     uint8_t* h_stage = nullptr;              // pinned staging for strided host input
+    const uint8_t* last_src = nullptr;       // where the kernels read the last picture (MI355X_H264_DBG_SRC serves it when that is d_stage)
     uint8_t* d_rgba = nullptr, *h_rgba = nullptr;   // RGBA pictures on their way to the conversion kernel (allocated with the first)
     uint8_t* d_inject_src = nullptr;         // mi355x_h264_debug_code_syntax: the batch items' source pictures (allocated with the first call)
     size_t frame_bytes = 0, bitbuf_cap = 0, au_cap = 0;
@@ -400,6 +401,7 @@ int submit(mi355x_h264_encoder* e, const uint8_t* d_src, size_t src_item_stride,
     e->after_injected = inj != nullptr;
     Step T;
     T.d_src = d_src; T.src_item_stride = src_item_stride; T.nv12 = nv12; T.idr = idr; T.n = e->G;
+    e->last_src = d_src;
     T.sync = &S.sync;
     T.slot = &S;
     T.inj = inj;

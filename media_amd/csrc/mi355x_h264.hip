@@ -242,6 +242,10 @@ int64_t mi355x_h264_debug_read(mi355x_h264_encoder* e, int what, void* dst, size
         case MI355X_H264_DBG_LEVELS: src = e->d_levels; n = (size_t)e->nmb * LV_STRIDE * 2; break;
         case MI355X_H264_DBG_MBAUX: src = e->d_aux; n = (size_t)e->nmb * 16; break;
         case MI355X_H264_DBG_MVQ: src = e->d_mvq; n = (size_t)e->nmb * 16; break;
+        case MI355X_H264_DBG_SRC:   // the staging picture, where the kernels read the last picture from it
+            if (e->last_src != e->d_stage)
+                return set_err(e->err, MI355X_H264_E_ARG, "%s", e->last_src ? "the last picture was read in place from the caller's device memory: no staging picture" : "no picture yet");
+            src = e->d_stage; n = e->frame_bytes; break;
         default: return MI355X_H264_E_ARG;
     }
     if (cap < n) return MI355X_H264_E_ARG;
@@ -394,6 +398,14 @@ int64_t mi355x_h264_stream_debug_read(mi355x_h264_stream* s, int what, void* dst
         case MI355X_H264_DBG_LEVELS: src = e->d_levels + mb0 * LV_STRIDE; n = (size_t)e->nmb * LV_STRIDE * 2; break;
         case MI355X_H264_DBG_MBAUX: src = e->d_aux + mb0 * 16; n = (size_t)e->nmb * 16; break;
         case MI355X_H264_DBG_MVQ: src = e->d_mvq + mb0 * 8; n = (size_t)e->nmb * 16; break;
+        case MI355X_H264_DBG_SRC: {   // the stream's slot of the hub's staging pictures, where the step's kernels read the last picture from it
+            HubItem& it = h->items[s->item];
+            uint64_t serial = 0;
+            h->sched.last_step(s->item, &serial, nullptr, nullptr, nullptr);
+            if (!serial || it.d_in)
+                return set_err(it.err, MI355X_H264_E_ARG, "%s", serial ? "the last picture was read in place from the caller's device memory: no staging picture" : "no picture yet");
+            src = h->d_stage + item * h->st_stage; n = e->frame_bytes; break;
+        }
         default: return MI355X_H264_E_ARG;
     }
     if (cap < n) return MI355X_H264_E_ARG;
