@@ -337,6 +337,45 @@ typedef struct mi355x_h264_stats {
 int mi355x_h264_stats_enable(mi355x_h264_encoder *enc, int on);
 int mi355x_h264_stats_read(mi355x_h264_encoder *enc, mi355x_h264_stats *out, int reset);
 
+/* ---- quality report: the sum of squared errors (SSE) of every coded picture, per plane and per macroblock ----
+ * Definition.  Each of the three planes is compared sample by sample, Y, Cb and Cr reported in the order Y, U, V: the
+ * difference (src - rec) is squared and summed.
+ *   src  the picture the encoder kernels read: for I420 and NV12 input the caller's samples, for RGBA input the I420 staging
+ *        picture the conversion kernel (k_rgba_to_i420 / k_rgba_to_i420_step) wrote;
+ *   rec  the reconstruction that becomes the next reference, after the loop filter; a picture that is not filtered
+ *        (disable_deblock, or a picture with an I_PCM macroblock) is compared as it stands.
+ * Only display samples count: luma x < width, y < height; chroma x < width / 2, y < height / 2.  The replicated columns and rows of
+ * the coded size never count.  A band instance (band_count > 1) counts the macroblock rows of its own band only, so the sum over
+ * the instances equals what one instance reports.
+ * Per picture: sse[3], 64 bits per plane (32 are not enough: one 1080p picture of noise at QP 51 has a luma SSE above 2^32), and a
+ * map[rows][columns of macroblocks] of uint32_t, each entry the macroblock's SSE over its display samples, all three planes added
+ * (at most 384 * 65025); entries outside a band instance's band are 0, and the sum of the map is sse[0] + sse[1] + sse[2].
+ * All arithmetic on the device is integer: no float is computed, summed or returned, so the result is exact whatever the order of
+ * summation.  PSNR = 10 * log10(255^2 * samples / sse) is the caller's to compute (an SSE of 0: infinite).
+ * The switch only observes: access units, mi355x_h264_debug_read results and statistics are the same bytes with it on or off.  Off
+ * (the default): no launch, no copy and no allocation differs; the result arrays come with the first enable.  On: one kernel
+ * (k_sse) per step, beside the entropy coder and off the chain to the next picture's motion search; its results are complete when
+ * the call returns.  MI355X_H264_QUALITY=1 in the environment turns the switch on when an engine is created. */
+typedef struct mi355x_h264_quality {
+    uint64_t sse[3], samples[3];   /* Y, U, V; samples: what was compared (a band: its rows) */
+    uint32_t bytes, qp, frame_type, valid;   /* of the access unit; valid 0: nothing was compared */
+} mi355x_h264_quality;
+int mi355x_h264_quality_enable(mi355x_h264_encoder *enc, int on);   /* from the next picture on */
+/* records of every picture of the last call, in the order of sizes[]: config.batch entries after a one-picture call,
+ * count after encode_batch_device, batch * frames_per_gop after encode_gops_device; returns entries or < 0.  cap: entries dst has
+ * room for.  valid = 0 marks a picture refused with MI355X_H264_E_OVERFLOW and a picture of mi355x_h264_debug_code_syntax (whose
+ * ring holds nothing meaningful); the record is present.  Nothing to read (the switch was off for the last call, no picture yet):
+ * MI355X_H264_E_ARG with an error text, the handle as usable as before. */
+int64_t mi355x_h264_quality_read(mi355x_h264_encoder *enc, mi355x_h264_quality *dst, size_t cap);
+/* the map of the last picture of batch item `item`: coded height / 16 rows of coded width / 16 entries; cap: entries dst has room
+ * for; returns entries or < 0 */
+int64_t mi355x_h264_quality_map(mi355x_h264_encoder *enc, int item, uint32_t *dst, size_t cap);
+/* Streams: the switch belongs to the shared engine, as mi355x_h264_stream_debug_keep_pre's does - it holds for every stream that
+ * shares it and ends with the engine.  last_quality / quality_map: of the stream's own last picture. */
+int mi355x_h264_stream_quality_enable(mi355x_h264_stream *s, int on);
+int mi355x_h264_stream_last_quality(const mi355x_h264_stream *s, mi355x_h264_quality *out);
+int64_t mi355x_h264_stream_quality_map(mi355x_h264_stream *s, uint32_t *dst, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,8 @@ EXPORTS = [
     "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
     "mi355x_h264_debug_code_syntax", "mi355x_h264_stream_debug_keep_pre", "mi355x_h264_stream_debug_last_step",
     "mi355x_h264_stream_open_ex",
+    "mi355x_h264_quality_enable", "mi355x_h264_quality_read", "mi355x_h264_quality_map",
+    "mi355x_h264_stream_quality_enable", "mi355x_h264_stream_last_quality", "mi355x_h264_stream_quality_map",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
@@ -49,6 +51,27 @@ class Config(C.Structure):
 class Stats(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", C.c_uint64 * 5), ("mbs", C.c_uint64 * 5),
                 ("frames", C.c_uint64), ("p_mbs", C.c_uint64), ("me_searched_mbs", C.c_uint64), ("tq_coded_mbs", C.c_uint64)]
+
+
+class Quality(C.Structure):
+    """mi355x_h264_quality"""
+    _fields_ = [("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("bytes", C.c_uint32), ("qp", C.c_uint32),
+                ("frame_type", C.c_uint32), ("valid", C.c_uint32)]
+
+
+def psnr(sse, samples):
+    """10 * log10(255^2 * samples / sse) on the host; an SSE of 0 gives inf (nothing compared: nan)"""
+    import math
+    if not samples:
+        return float("nan")
+    return float("inf") if sse == 0 else 10.0 * math.log10(65025.0 * samples / sse)
+
+
+def _quality_record(q):
+    """a Quality as a dict, `psnr` (Y, U, V) added"""
+    sse, samples = [int(v) for v in q.sse], [int(v) for v in q.samples]
+    return {"sse": sse, "samples": samples, "bytes": int(q.bytes), "qp": int(q.qp), "frame_type": int(q.frame_type), "valid": bool(q.valid),
+            "psnr": [psnr(a, b) if q.valid else float("nan") for a, b in zip(sse, samples)]}
 
 
 _lib = None
@@ -112,6 +135,15 @@ def lib():
         L.mi355x_h264_stream_debug_keep_pre.argtypes = [vp, C.c_int]
         L.mi355x_h264_stream_debug_last_step.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_hub_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mi355x_h264_quality_enable.argtypes = [vp, C.c_int]
+        L.mi355x_h264_quality_read.argtypes = [vp, C.POINTER(Quality), C.c_size_t]
+        L.mi355x_h264_quality_read.restype = C.c_int64
+        L.mi355x_h264_quality_map.argtypes = [vp, C.c_int, vp, C.c_size_t]
+        L.mi355x_h264_quality_map.restype = C.c_int64
+        L.mi355x_h264_stream_quality_enable.argtypes = [vp, C.c_int]
+        L.mi355x_h264_stream_last_quality.argtypes = [vp, C.POINTER(Quality)]
+        L.mi355x_h264_stream_quality_map.argtypes = [vp, vp, C.c_size_t]
+        L.mi355x_h264_stream_quality_map.restype = C.c_int64
         L.mi355x_h264_stats_enable.argtypes = [vp, C.c_int]
         L.mi355x_h264_stats_read.argtypes = [vp, C.POINTER(Stats), C.c_int]
         _lib = L
@@ -291,6 +323,28 @@ class Encoder:
     def debug_read(self, what):
         return _debug_read(self, lib().mi355x_h264_debug_read, what)
 
+    def quality_enable(self, on=True):
+        """the quality report (mi355x_h264_quality_enable): SSE per plane and per macroblock of every picture from the next one on"""
+        self._check(lib().mi355x_h264_quality_enable(self.h, int(on)))
+
+    def quality(self, cap=None):
+        """the records of every picture of the last call, in the order of sizes[] (mi355x_h264_quality_read), as dicts with `psnr`
+        (Y, U, V; computed here) added; raises EncoderError (rc = E_ARG) when there is nothing to read"""
+        n = 4096 if cap is None else cap
+        a = (Quality * max(n, 1))()
+        got = lib().mi355x_h264_quality_read(self.h, a, n)
+        if got < 0:
+            self._check(int(got))
+        return [_quality_record(a[i]) for i in range(got)]
+
+    def quality_map(self, item=0):
+        """SSE per macroblock (all planes added) of the last picture of batch item `item`: uint32 (rows, columns)"""
+        m = np.zeros((self.ch // 16, self.cw // 16), np.uint32)
+        got = lib().mi355x_h264_quality_map(self.h, item, m.ctypes.data, m.size)
+        if got < 0:
+            self._check(int(got))
+        return m
+
     def stats_enable(self, on=True):
         self._check(lib().mi355x_h264_stats_enable(self.h, int(on)))
 
@@ -406,6 +460,24 @@ class Stream:
     def keep_pre(self, on=True):
         """keep the pre-filter planes of every stream of this stream's engine (mi355x_h264_stream_debug_keep_pre)"""
         self._check(lib().mi355x_h264_stream_debug_keep_pre(self.h, int(on)))
+
+    def quality_enable(self, on=True):
+        """the quality report for every stream of this stream's engine (mi355x_h264_stream_quality_enable)"""
+        self._check(lib().mi355x_h264_stream_quality_enable(self.h, int(on)))
+
+    def quality(self):
+        """the record of this stream's last picture, `psnr` added; raises EncoderError (rc = E_ARG) when there is none"""
+        q = Quality()
+        self._check(lib().mi355x_h264_stream_last_quality(self.h, C.byref(q)))
+        return _quality_record(q)
+
+    def quality_map(self):
+        """SSE per macroblock of this stream's last picture: uint32 (rows, columns)"""
+        m = np.zeros((self.ch // 16, self.cw // 16), np.uint32)
+        got = lib().mi355x_h264_stream_quality_map(self.h, m.ctypes.data, m.size)
+        if got < 0:
+            self._check(int(got))
+        return m
 
     def last_step(self):
         """the lockstep step that coded this stream's last picture (mi355x_h264_stream_debug_last_step)"""

@@ -10,7 +10,8 @@ namespace {
 constexpr int NSLOT = 3;          // access-unit slots in flight
 
 // where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
-struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0; };
+struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0;
+                  int quality = 0; };   // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
 
 struct Slot {
     uint32_t* d_bitbuf = nullptr;   // device slice payload (zeroed before use)
@@ -18,6 +19,8 @@ struct Slot {
     SliceInfo* h_info = nullptr;    // pinned
     uint8_t* h_au = nullptr;        // pinned access unit buffer
     AuLayout lay;                   // of the picture in flight
+    unsigned long long* h_qpart = nullptr;   // quality report (pinned, with the first enable): [G][mbh][SSE_SEGS][3] plane sums per wave of k_sse
+    uint32_t* h_qmap = nullptr;              //   and [G][nmb] sums per macroblock, stored by k_sse; rows outside the band stay 0
     bool busy = false;
     StepSync sync;                  // on the engine's stream pair
     // stats events of this frame: pairs (start, stop, kernel id, launches, mbs)
@@ -76,6 +79,16 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     int me_turn = 0;                         // this engine's id at the GPU's motion-search lock (0: takes no part)
     uint32_t p_intra_x16 = 0;                // intra macroblocks per P picture, recent pictures (x 16, a running mean): sizes k_pintra_rows' grid
     mi355x_h264_stats stats{};
+    // quality report (mi355x_h264_quality_enable; everything below comes with the first enable)
+    bool quality_on = false;
+    hipEvent_t q_ready = nullptr;            // the reconstruction of the step being launched is final: k_sse may start on the second stream
+    hipEvent_t q_done[MAX_BUF] = {nullptr};  // direct steps: behind the k_sse that compared ring slot b
+    bool q_done_set[MAX_BUF] = {false};
+    std::vector<mi355x_h264_quality> q_item; // [G] record of the item's last finished picture
+    std::vector<const uint32_t*> q_map;      // [G] its map, in the pinned memory of the slot that carried it (null: nothing compared)
+    std::vector<uint8_t> q_have;             // [G] the item has a record
+    std::vector<mi355x_h264_quality> q_recs; // the records of the last call, in the order of sizes[]: item g's goes to g * q_mul + q_add
+    size_t q_mul = 1, q_add = 0;
     char err[256] = {0};
 };
 
@@ -218,6 +231,15 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
     hipStream_t st = Y.st;
 
     // (the payload buffers of the items were left zeroed by the k_pack of their previous use)
+
+    // Quality report, hazard "ring slot": this picture's first kernels write ring slot `cur`, which the k_sse of the picture coded
+    // nbuf pictures ago read on the second stream.  In mi355x_h264_encode_gops_device / _batch_device no host wait lies between the
+    // two, so the rewrite is ordered behind that comparison by its event.  (Indirect steps: a stream's call returns only after the
+    // host has waited for its step's `done`, which lies behind the step's k_sse - the host wait is the order.)
+    if (!ind && e->q_done_set[cur]) {
+        HIPCHK(e->err, hipStreamWaitEvent(st, e->q_done[cur], 0));
+        e->q_done_set[cur] = false;
+    }
 
     if (T.inj) {
         // the arrays k_i4_decide / k_intra_rows / k_me / k_tq / k_pintra_rows would have left, and the flags they would have raised
@@ -385,8 +407,25 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             }
         }
     }
+    // Quality report: source against the reconstruction that is now final (behind the loop filter; behind the last reconstruction
+    // kernel when nothing is filtered).  On the second stream, beside the entropy coder and behind the filter's event: the chain to the
+    // next picture's k_me (this stream) does not wait for it.  An injected picture's ring holds nothing to compare.
+    T.lay.quality = !e->quality_on ? 0 : (T.inj ? 2 : 1);
+    const bool compare = T.lay.quality == 1;
+    if (compare) {
+        if (fork) {
+            HIPCHK(e->err, hipEventRecord(e->q_ready, st));
+            HIPCHK(e->err, hipStreamWaitEvent(ec, e->q_ready, 0));
+        }
+        LAUNCH2(ind, k_sse<true>, k_sse<false>, dim3((unsigned)e->b_rows * SSE_SEGS, G), dim3(64), ec, P, S.h_qpart, S.h_qmap);
+        if (!ind) { HIPCHK(e->err, hipEventRecord(e->q_done[cur], ec)); e->q_done_set[cur] = true; }   // (hazard "ring slot", above)
+    }
     if (fork) HIPCHK(e->err, hipStreamWaitEvent(st, Y.entropy_done, 0));   // join: the next picture rewrites MbInfo / levels
-    HIPCHK(e->err, hipEventRecord(Y.done, st));
+    // Hazard "source picture": a staging slot is handed to the next upload and a caller's device picture is valid only during the
+    // call, and both happen after the host has waited for `done`.  With a comparison in the step `done` is therefore recorded on the
+    // stream that runs it: that stream has waited for everything up to the filter on the other one and holds the entropy coder's
+    // work itself, so the event lies behind the whole step and the host's one wait covers k_sse's loads and its stores to pinned memory.
+    HIPCHK(e->err, hipEventRecord(Y.done, compare ? ec : st));
     HIPCHK(e->err, hipGetLastError());
     return MI355X_H264_OK;
 }
@@ -435,7 +474,7 @@ int wait_slot(mi355x_h264_encoder* e, int slot_idx)
 }
 
 // finish the access unit of batch item g on the host: S = the buffers it was written to, L = where and of which type
-int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
+int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
     uint8_t* base = S.h_au + (size_t)g * e->st_au;
     const SliceInfo* const info = S.h_info + (size_t)g * e->b_nsl;   // one per slice of this instance's band
@@ -496,6 +535,78 @@ int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8
     return MI355X_H264_OK;
 }
 
+// the quality record of item g's picture: the rows of the band added up (k_sse left one partial per wave and plane).  A
+// picture that was refused (E_OVERFLOW) or injected has a record with valid = 0
+void quality_record(mi355x_h264_encoder* e, const Slot& S, const AuLayout& L, int g, uint32_t bytes, bool compared)
+{
+    mi355x_h264_quality q{};
+    q.bytes = bytes; q.qp = (uint32_t)e->qp; q.frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
+    e->q_map[g] = nullptr;
+    if (compared) {
+        const unsigned long long* part = S.h_qpart + ((size_t)g * e->mbh + e->b_row0) * SSE_SEGS * 3;
+        for (int r = 0; r < e->b_rows * SSE_SEGS; r++)
+            for (int p = 0; p < 3; p++) q.sse[p] += part[(size_t)r * 3 + p];
+        // display samples of the band's rows
+        const int w = e->cfg.width, h = e->cfg.height;
+        const int y0 = std::min(h, 16 * e->b_row0), y1 = std::min(h, 16 * (e->b_row0 + e->b_rows));
+        const int c0 = std::min(h / 2, 8 * e->b_row0), c1 = std::min(h / 2, 8 * (e->b_row0 + e->b_rows));
+        q.samples[0] = (uint64_t)(y1 - y0) * w;
+        q.samples[1] = q.samples[2] = (uint64_t)(c1 - c0) * (w / 2);
+        q.valid = 1;
+        e->q_map[g] = S.h_qmap + (size_t)g * e->nmb;
+    }
+    e->q_item[g] = q;
+    e->q_have[g] = 1;
+    const size_t idx = (size_t)g * e->q_mul + e->q_add;
+    if (idx < e->q_recs.size()) e->q_recs[idx] = q;
+}
+
+int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    const int rc = finish_au(e, S, L, g, out, out_len, frame_type);
+    if (L.quality) quality_record(e, S, L, g, rc == MI355X_H264_OK ? *out_len : 0, rc == MI355X_H264_OK && L.quality == 1);
+    else if (!e->q_have.empty()) e->q_have[g] = 0;   // (coded with the switch off: nothing to read for this picture)
+    return rc;
+}
+
+// a call begins: room for the records of its n pictures (none while the switch is off); item g's record goes to g * mul + add
+void quality_begin(mi355x_h264_encoder* e, size_t n, size_t mul, size_t add)
+{
+    e->q_recs.clear();
+    if (e->quality_on) e->q_recs.resize(n);   // (valid = 0 until the picture is finished)
+    e->q_mul = mul; e->q_add = add;
+}
+
+// the switch of the quality report; the pinned result arrays of every slot and the events come with the first enable
+hipError_t quality_alloc(mi355x_h264_encoder* e)
+{
+    if (e->q_ready) return hipSuccess;
+    HIPTRY(hipSetDevice(e->device));
+    const size_t Gn = (size_t)e->G, part = Gn * e->mbh * SSE_SEGS * 3 * sizeof(unsigned long long), map = Gn * e->nmb * sizeof(uint32_t);
+    for (int si = 0; si < e->nslots; si++) {
+        Slot& S = e->slots[si];
+        HIPTRY(e->mem.pinned(&S.h_qpart, part));
+        HIPTRY(e->mem.pinned(&S.h_qmap, map));
+        memset(S.h_qpart, 0, part);
+        memset(S.h_qmap, 0, map);   // (a band instance's kernel stores its own rows only: the others stay 0)
+    }
+    for (int b = 0; b < e->nbuf; b++) HIPTRY(hipEventCreateWithFlags(&e->q_done[b], hipEventDisableTiming));
+    e->q_item.assign(Gn, mi355x_h264_quality{});
+    e->q_map.assign(Gn, nullptr);
+    e->q_have.assign(Gn, 0);
+    HIPTRY(hipEventCreateWithFlags(&e->q_ready, hipEventDisableTiming));
+    return hipSuccess;
+}
+int quality_set(mi355x_h264_encoder* e, bool on)
+{
+    if (on) {
+        const hipError_t r = quality_alloc(e);
+        if (r != hipSuccess) return set_err(e->err, r == hipErrorOutOfMemory ? MI355X_H264_E_NOMEM : MI355X_H264_E_HIP, "quality report: %s: %s", t_failed_call, hipGetErrorString(r));
+    }
+    e->quality_on = on;
+    return MI355X_H264_OK;
+}
+
 int collect(mi355x_h264_encoder* e, int slot_idx, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
     const int rc = wait_slot(e, slot_idx);
@@ -514,6 +625,8 @@ void destroy_engine(mi355x_h264_encoder* e)
         for (auto& ev : S.evs) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->q_done) if (ev) (void)hipEventDestroy(ev);
+    if (e->q_ready) (void)hipEventDestroy(e->q_ready);
     if (e->stream_ec && e->stream_ec != e->stream) (void)hipStreamDestroy(e->stream_ec);
     if (e->counted_live) e->counted_live->fetch_sub(1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -651,6 +764,14 @@ int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool
         destroy_engine(e);
         return r == hipErrorOutOfMemory ? MI355X_H264_E_NOMEM : MI355X_H264_E_HIP;
     }
+    {   // MI355X_H264_QUALITY=1: the quality report is on from the first picture (mi355x_h264_quality_enable)
+        const char* q = getenv("MI355X_H264_QUALITY");
+        if (q && q[0] == '1' && !q[1] && quality_set(e, true) != MI355X_H264_OK) {
+            fprintf(stderr, "mi355x_h264_create: %s\n", e->err);
+            destroy_engine(e);
+            return MI355X_H264_E_HIP;
+        }
+    }
     *out = e;
     return MI355X_H264_OK;
 }
@@ -663,6 +784,7 @@ int encode_one_device(mi355x_h264_encoder* e, const void* d_pic, bool nv12, uint
     HIPCHK(e->err, hipSetDevice(e->device));
     const int slot = take_slot(e);
     if (e->G != 1) return set_err(e->err, MI355X_H264_E_ARG, "single-picture calls need a batch-1 encoder");
+    quality_begin(e, 1, 1, 0);
     int rc = submit(e, (const uint8_t*)d_pic, 0, slot, nv12);
     if (rc) return rc;
     return collect(e, slot, out, out_len, frame_type);

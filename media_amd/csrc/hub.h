@@ -196,6 +196,7 @@ void hub_run_step(Hub* h, HubStep& T)
         if (rc == MI355X_H264_OK) {
             it.rc = finish_item(e, e->slots[0], St.lay, pics[k].item, &it.out, &it.out_len, &it.frame_type);
             if (it.rc != MI355X_H264_OK) snprintf(it.err, sizeof(it.err), "%s", e->err);
+            if (St.lay.quality) e->q_item[pics[k].item].qp = (uint32_t)pics[k].qp;   // (the position's own QP, not the engine's)
         } else snprintf(it.err, sizeof(it.err), "%s", errtxt);
         T.rc[k] = it.rc;
     }

@@ -28,6 +28,7 @@
 #include "k_me.h"
 #include "k_tq.h"
 #include "k_dec.h"
+#include "k_quality.h"
 #include "h264_parse.h"
 #include "../../include/mi355x_h264_dec.h"
 
@@ -123,10 +124,12 @@ int mi355x_h264_encode_batch_device(mi355x_h264_encoder* e, const void* d_frames
     HIPCHK(e->err, hipSetDevice(e->device));
     const bool nv12 = e->cfg.input_format == MI355X_H264_INPUT_NV12;
     size_t pos = 0;
+    quality_begin(e, (size_t)count, 0, 0);
     const int rc = run_pipeline(e, count,
         [&](int i, int slot) { return submit(e, (const uint8_t*)d_frames + (size_t)i * stride, 0, slot, nv12); },
         [&](int i, int slot) -> int {
             uint8_t* p = nullptr; uint32_t n = 0;
+            e->q_add = (size_t)i;
             const int r = collect(e, slot, &p, &n, nullptr);
             if (r) return r;
             if (pos + n > out_cap) {
@@ -152,9 +155,11 @@ int mi355x_h264_encode_gops_device(mi355x_h264_encoder* e, const void* d_frames,
     const bool nv12 = e->cfg.input_format == MI355X_H264_INPUT_NV12;
     for (int g = 0; g < G; g++) gop_bytes[g] = 0;
     e->seq.force_idr = 1;                     // every call starts closed GOPs
+    quality_begin(e, (size_t)G * frames_per_gop, (size_t)frames_per_gop, 0);
     return run_pipeline(e, frames_per_gop,
         [&](int i, int slot) { return submit(e, (const uint8_t*)d_frames + (size_t)i * frame_stride, gop_stride, slot, nv12); },
         [&](int i, int slot) -> int {
+            e->q_add = (size_t)i;
             int r = wait_slot(e, slot);
             for (int g = 0; g < G && !r; g++) {
                 uint8_t* p = nullptr; uint32_t n = 0;
@@ -265,6 +270,7 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, co
     HIPCHK(e->err, hipMemcpy(e->d_inject_src, src_i420, src_bytes, hipMemcpyHostToDevice));   // k_cavlc reads the I_PCM samples from the source
     const int slot = take_slot(e);
     const Injected inj{mbinfo, levels, mvq, mbaux};
+    quality_begin(e, (size_t)e->G, 1, 0);
     int rc = submit(e, e->d_inject_src, e->frame_bytes, slot, false, &inj);
     if (rc) return rc;
     rc = wait_slot(e, slot);
@@ -288,6 +294,32 @@ int mi355x_h264_stats_read(mi355x_h264_encoder* e, mi355x_h264_stats* out, int r
     *out = e->stats;
     if (reset) memset(&e->stats, 0, sizeof(e->stats));
     return MI355X_H264_OK;
+}
+
+// ---- quality report (engine.h: quality_record; k_quality.h) ----
+
+int mi355x_h264_quality_enable(mi355x_h264_encoder* e, int on)
+{
+    if (!e) return MI355X_H264_E_ARG;
+    return quality_set(e, on != 0);
+}
+
+int64_t mi355x_h264_quality_read(mi355x_h264_encoder* e, mi355x_h264_quality* dst, size_t cap)
+{
+    NEED(e, dst, "null argument");
+    NEED(e, !e->q_recs.empty(), "no quality records: the report was not enabled for the last call, or there has been no picture yet");
+    NEED(e, cap >= e->q_recs.size(), "room for fewer records than the last call made");
+    memcpy(dst, e->q_recs.data(), e->q_recs.size() * sizeof(mi355x_h264_quality));
+    return (int64_t)e->q_recs.size();
+}
+
+int64_t mi355x_h264_quality_map(mi355x_h264_encoder* e, int item, uint32_t* dst, size_t cap)
+{
+    NEED(e, dst && item >= 0 && item < e->G, "null argument or no such item");
+    NEED(e, !e->q_recs.empty() && e->q_have[item] && e->q_map[item], "no quality map: nothing was compared for the item's last picture");
+    NEED(e, cap >= (size_t)e->nmb, "room for fewer entries than the picture has macroblocks");
+    memcpy(dst, e->q_map[item], (size_t)e->nmb * sizeof(uint32_t));
+    return (int64_t)e->nmb;
 }
 
 // ---- streams (hub.h) ----
@@ -321,6 +353,7 @@ int mi355x_h264_stream_open_ex(const mi355x_h264_config* cfg, uint32_t flags, mi
     it = HubItem();
     it.copied = ev;
     g_streams_open.fetch_add(1);
+    if (!h->e->q_have.empty()) h->e->q_have[idx] = 0;   // (quality report: the item's record was the stream's before this one)
     s->hub = h; s->item = idx;
     *out = s;
     return MI355X_H264_OK;
@@ -420,6 +453,44 @@ int mi355x_h264_stream_debug_keep_pre(mi355x_h264_stream* s, int on)
     std::lock_guard<std::mutex> lk(s->hub->launch_mu);   // (a step's leader reads it while it launches)
     s->hub->e->keep_pre = on != 0;
     return MI355X_H264_OK;
+}
+
+// the quality report of all streams of this stream's engine (engine.h, submit_step), and this stream's last record and map
+int mi355x_h264_stream_quality_enable(mi355x_h264_stream* s, int on)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    if (hipSetDevice(s->hub->cfg.device) != hipSuccess) return set_err(s->hub->items[s->item].err, MI355X_H264_E_HIP, "hipSetDevice");
+    std::lock_guard<std::mutex> lk(s->hub->launch_mu);   // (a step's leader reads the switch while it launches, and the records when it finishes)
+    const int rc = quality_set(s->hub->e, on != 0);
+    if (rc != MI355X_H264_OK) snprintf(s->hub->items[s->item].err, sizeof(s->hub->items[s->item].err), "%s", s->hub->e->err);
+    return rc;
+}
+
+int mi355x_h264_stream_last_quality(const mi355x_h264_stream* s, mi355x_h264_quality* out)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    Hub* h = s->hub;
+    if (!out) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->launch_mu);
+    if (h->e->q_have.empty() || !h->e->q_have[s->item])
+        return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "no quality record: the report was not enabled for the stream's last picture, or there has been no picture yet");
+    *out = h->e->q_item[s->item];
+    return MI355X_H264_OK;
+}
+
+int64_t mi355x_h264_stream_quality_map(mi355x_h264_stream* s, uint32_t* dst, size_t cap)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    Hub* h = s->hub;
+    const mi355x_h264_encoder* e = h->e;
+    if (!dst) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->launch_mu);
+    if (e->q_have.empty() || !e->q_have[s->item] || !e->q_map[s->item])
+        return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "no quality map: nothing was compared for the stream's last picture");
+    if (cap < (size_t)e->nmb) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "room for fewer entries than the picture has macroblocks");
+    // (the stream's calls are synchronous and a step stores only its own items' part of the pinned arrays: nothing rewrites this before the stream's next picture)
+    memcpy(dst, e->q_map[s->item], (size_t)e->nmb * sizeof(uint32_t));
+    return (int64_t)e->nmb;
 }
 
 int mi355x_h264_stream_debug_last_step(const mi355x_h264_stream* s, uint64_t* serial, int* pictures, int* position, int* idr)

@@ -2,6 +2,7 @@
 #define LOG_TAG "VideoEncoderMI355X"
 #include "VideoEncoderMI355X.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include "MediaLog.h"
 #include "Property.h"
@@ -69,6 +70,12 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     // extension: "2" / "3" = that many reference pictures are searched and ref_idx_l0 is coded; anything else keeps the preset's
     // one (iNumRefFrame = 1, ref :290).  Both paths below honour it
     cfg.refs = ParseRefs(GetStrEncParam("persist.vmi.video.encode.refs"));
+    // extension: "1" = the library compares every picture with its source (SSE per plane; include/mi355x_h264.h, "quality report"):
+    // LastFrameQuality() and one log line per GOP.  The switch of a shared engine holds for all its streams and ends with it:
+    // an object without the key leaves it as it finds it and reads nothing
+    m_psnr = ParsePsnr(GetStrEncParam("persist.vmi.video.encode.psnr"));
+    m_haveQuality = false;
+    m_gopPictures = 0;
     // One engine per object (mi355x_h264_create) costs every picture its own launch sequence.  The default is a STREAM of the
     // shared engine: the pictures that the encoder objects of one process hand over at about the same time are coded in one
     // lockstep step (include/mi355x_h264.h, "streams"; same bitstream).  persist.vmi.video.encode.shared = 0 (or the environment
@@ -83,6 +90,12 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
             m_stream = nullptr;
             return false;
         }
+        if (m_psnr && mi355x_h264_stream_quality_enable(m_stream, 1) != MI355X_H264_OK) {
+            ERR("quality report: %s", mi355x_h264_stream_last_error(m_stream));
+            mi355x_h264_stream_close(m_stream);
+            m_stream = nullptr;
+            return false;
+        }
         return true;
     }
     // (an engine of its own takes RGBA through entry points of their own; its input_format names the layout of device I420 / NV12)
@@ -93,6 +106,65 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
         m_engine = nullptr;
         return false;
     }
+    if (m_psnr && mi355x_h264_quality_enable(m_engine, 1) != MI355X_H264_OK) {
+        ERR("quality report: %s", mi355x_h264_last_error(m_engine));
+        mi355x_h264_destroy(m_engine);
+        m_engine = nullptr;
+        return false;
+    }
+    return true;
+}
+
+// Quality report of the picture that went out (after a scene-change re-code: the IDR picture's, the last one the engine coded).
+// A GOP's line is written when the next IDR picture has been coded, and when the engine closes.
+void VideoEncoderMI355X::QualityAfterPicture(bool isIdr)
+{
+    mi355x_h264_quality q{};
+    const int rc = m_stream != nullptr ? mi355x_h264_stream_last_quality(m_stream, &q)
+                                       : (mi355x_h264_quality_read(m_engine, &q, 1) == 1 ? MI355X_H264_OK : MI355X_H264_E_ARG);
+    m_haveQuality = rc == MI355X_H264_OK;
+    if (!m_haveQuality) {
+        return;
+    }
+    m_lastQuality = q;
+    if (isIdr) {
+        QualityLogGop();
+    }
+    if (q.valid != 0) {
+        for (int p = 0; p < 3; p++) {
+            m_gopSse[p] += q.sse[p];
+            m_gopSamples[p] += q.samples[p];
+        }
+        m_gopBytes += q.bytes;
+        m_gopPictures++;
+    }
+}
+
+// pictures, mean bytes and mean PSNR Y / U / V of the GOP that has ended: the PSNR of the GOP's mean squared error per plane
+// (10 log10(255^2 samples / SSE) over the sums; computed here, on the host - the library reports integers only)
+void VideoEncoderMI355X::QualityLogGop()
+{
+    if (m_gopPictures != 0) {
+        double db[3];
+        for (int p = 0; p < 3; p++) {
+            db[p] = m_gopSse[p] != 0 ? 10.0 * std::log10(65025.0 * static_cast<double>(m_gopSamples[p]) / static_cast<double>(m_gopSse[p])) : INFINITY;
+        }
+        INFO("GOP of %u pictures: mean %llu bytes, mean PSNR Y %.2f U %.2f V %.2f dB", m_gopPictures,
+             static_cast<unsigned long long>(m_gopBytes / m_gopPictures), db[0], db[1], db[2]);
+    }
+    for (int p = 0; p < 3; p++) {
+        m_gopSse[p] = m_gopSamples[p] = 0;
+    }
+    m_gopBytes = 0;
+    m_gopPictures = 0;
+}
+
+bool VideoEncoderMI355X::LastFrameQuality(mi355x_h264_quality *out) const
+{
+    if (!m_psnr || !m_haveQuality || out == nullptr) {
+        return false;
+    }
+    *out = m_lastQuality;
     return true;
 }
 
@@ -166,6 +238,8 @@ int32_t VideoEncoderMI355X::ParseInputLayout(const std::string &value)
 
 int32_t VideoEncoderMI355X::ParseRefs(const std::string &value) { return value == "2" ? 2 : value == "3" ? 3 : 1; }
 
+bool VideoEncoderMI355X::ParsePsnr(const std::string &value) { return value == "1"; }
+
 bool VideoEncoderMI355X::ParseInputDevice(const std::string &value) { return value == "device"; }
 
 int VideoEncoderMI355X::EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType)
@@ -225,12 +299,18 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
             m_stream != nullptr ? mi355x_h264_stream_last_error(m_stream) : mi355x_h264_last_error(m_engine));
         return false;
     }
+    if (m_psnr) {
+        QualityAfterPicture(frameType == MI355X_H264_FRAME_IDR);
+    }
     RateControlUpdate(*outLen, frameType == MI355X_H264_FRAME_IDR);
     return true;
 }
 
 void VideoEncoderMI355X::EngineClose()
 {
+    if (m_psnr && (m_engine != nullptr || m_stream != nullptr)) {
+        QualityLogGop();
+    }
     if (m_engine != nullptr) {
         mi355x_h264_destroy(m_engine);
         m_engine = nullptr;

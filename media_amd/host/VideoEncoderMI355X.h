@@ -24,6 +24,9 @@ public:
     // test hooks
     int32_t LastFrameQp() const { return m_lastQp; }
     uint32_t SceneCuts() const { return m_sceneCuts; }
+    // quality report of the last picture that went out (extension key persist.vmi.video.encode.psnr = 1; after a scene-change
+    // re-code: of the IDR picture).  false: the key is off or there has been no picture
+    bool LastFrameQuality(mi355x_h264_quality *out) const;
     // measurement hook (bench.py reads the reconstruction for PSNR): luma reconstruction of the last picture, coded size
     int64_t ReadReconY(void *dst, size_t cap, int32_t *codedWidth, int32_t *codedHeight);
     bool Shared() const { return m_stream != nullptr; }
@@ -34,6 +37,9 @@ public:
     // extension key persist.vmi.video.encode.refs: "2" / "3" -> that many reference pictures; anything else (or unset) -> 1, the
     // reference preset's iNumRefFrame
     static int32_t ParseRefs(const std::string &value);
+    // extension key persist.vmi.video.encode.psnr: "1" -> the library's quality report is on (include/mi355x_h264.h, "quality
+    // report"), on the stream path and with an engine of its own alike; anything else (or unset) -> off
+    static bool ParsePsnr(const std::string &value);
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -48,6 +54,8 @@ private:
     int EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType);
     void RateControlUpdate(uint32_t frameBytes, bool isIdr);
     static int32_t StartQp(uint32_t bitrate, uint32_t fps, uint32_t width, uint32_t height);
+    void QualityAfterPicture(bool isIdr);
+    void QualityLogGop();
 
     mi355x_h264_encoder *m_engine = nullptr;   // an engine of its own (persist.vmi.video.encode.shared = 0), or
     mi355x_h264_stream *m_stream = nullptr;    // a stream of the process-wide shared engine (the default)
@@ -60,6 +68,11 @@ private:
     uint32_t m_sceneCuts = 0;
     int32_t m_input = MI355X_H264_INPUT_I420;   // layout of the pictures EncodeOneFrame is handed (persist.vmi.video.encode.input)
     bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
+    // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
+    bool m_psnr = false, m_haveQuality = false;
+    mi355x_h264_quality m_lastQuality{};
+    uint64_t m_gopSse[3] = {0, 0, 0}, m_gopSamples[3] = {0, 0, 0}, m_gopBytes = 0;
+    uint32_t m_gopPictures = 0;
 };
 
 #endif  // VIDEO_ENCODER_MI355X_H

@@ -30,6 +30,8 @@ int32_t vc_parse_input_layout(const char *value) { return VideoEncoderMI355X::Pa
 int32_t vc_parse_input_device(const char *value) { return VideoEncoderMI355X::ParseInputDevice(value != nullptr ? value : "") ? 1 : 0; }
 // persist.vmi.video.encode.refs: 2 or 3 are taken, anything else is one reference picture
 int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
+// persist.vmi.video.encode.psnr: "1" turns the quality report on, anything else leaves it off
+int32_t vc_parse_psnr(const char *value) { return VideoEncoderMI355X::ParsePsnr(value != nullptr ? value : "") ? 1 : 0; }
 // The one rule for a picture's number of reference pictures (PicSeq::avail_refs, shared by the engine and the stream hub), driven
 // as both drive it: n pictures of a stream that searches nrefs pictures with an IDR every gop; force[i] != 0 forces an IDR at
 // picture i.  out[i] = the count of picture i (0: an IDR picture).
@@ -51,6 +53,12 @@ int32_t vc_last_qp(void *enc)
 {
     auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
     return m != nullptr ? m->LastFrameQp() : -1;
+}
+// the quality record (mi355x_h264_quality) of the last picture that went out; 0, or -1 when there is none
+int32_t vc_last_quality(void *enc, mi355x_h264_quality *out)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    return m != nullptr && m->LastFrameQuality(out) ? 0 : -1;
 }
 uint32_t vc_scene_cuts(void *enc)
 {

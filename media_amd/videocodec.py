@@ -35,6 +35,8 @@ def lib():
         L.vc_parse_input_layout.argtypes = [C.c_char_p]
         L.vc_parse_input_device.argtypes = [C.c_char_p]
         L.vc_parse_refs.argtypes = [C.c_char_p]
+        L.vc_parse_psnr.argtypes = [C.c_char_p]
+        L.vc_last_quality.argtypes = [vp, vp]
         L.vc_debug_ref_counts.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
         L.vc_debug_ref_counts.restype = None
         L.vc_last_qp.argtypes = [vp]
@@ -75,6 +77,11 @@ def parse_refs(value):
     return lib().vc_parse_refs(str(value).encode())
 
 
+def parse_psnr(value):
+    """does persist.vmi.video.encode.psnr = value turn the quality report on?  "1" only"""
+    return bool(lib().vc_parse_psnr(str(value).encode()))
+
+
 def ref_counts(nrefs, gop, n, forced=()):
     """the number of reference pictures of each of n pictures of a stream that searches nrefs, IDR every gop pictures and at the
     pictures in `forced` (the rule the engine and the stream hub share; 0 = an IDR picture)"""
@@ -85,7 +92,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None, refs=None):
+                   inputmem=None, refs=None, psnr=None, shared=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -103,6 +110,9 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.input", "" if input is None else input)        # nv12 | rgba; else I420
     prop_set("persist.vmi.video.encode.inputmem", "" if inputmem is None else inputmem)   # device; else host memory
     prop_set("persist.vmi.video.encode.refs", "" if refs is None else refs)               # 2 | 3; else one reference picture
+    prop_set("persist.vmi.video.encode.psnr", "" if psnr is None else psnr)               # 1: quality report; else off
+    if shared is not None:
+        prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 
 
 class VideoEncoder:
@@ -142,6 +152,15 @@ class VideoEncoder:
 
     def last_qp(self):
         return lib().vc_last_qp(self.h)
+
+    def last_quality(self):
+        """the quality record of the last picture that went out (persist.vmi.video.encode.psnr = 1) as capi.Encoder.quality() gives
+        them, or None when there is none"""
+        from media_amd import capi
+        q = capi.Quality()
+        if lib().vc_last_quality(self.h, C.byref(q)) != 0:
+            return None
+        return capi._quality_record(q)
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)

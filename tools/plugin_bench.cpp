@@ -5,10 +5,13 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--refs N] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--refs N] [--psnr] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
+// --psnr (anywhere on the line): the extension key persist.vmi.video.encode.psnr = 1 - the library's quality report is on, every
+// picture's record is read after its call (outside the latency sample), and the JSON line carries psnr_y / psnr_u / psnr_v: the
+// PSNR of the mean squared error of all pictures of the run, per plane.
 // input (optional; without it everything is as above): i420 | nv12 | rgba, with ":device" behind it for pictures in device
 // memory - the extension keys persist.vmi.video.encode.input / .inputmem.  The pictures of the file are converted to the layout
 // on the host before the clock starts; for device memory they are uploaded once, before the clock, and every stream cycles
@@ -23,7 +26,11 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include <cmath>
 #include "VideoCodecApi.h"
+#include "mi355x_h264.h"
+
+extern "C" int32_t vc_last_quality(void *enc, mi355x_h264_quality *out);   // media_amd/host/capi_shim.cpp
 
 int main(int argc, char **argv)
 {
@@ -34,7 +41,16 @@ int main(int argc, char **argv)
             argc -= 2;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    bool psnr = false;
+    for (int i = 1; i < argc; i++)   // --psnr: taken out of the line
+        if (strcmp(argv[i], "--psnr") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_PSNR", "1", 1);
+            psnr = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     const int w = atoi(argv[2]), h = atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
     std::vector<uint8_t> pics(fsz * npic);
@@ -102,6 +118,7 @@ int main(int argc, char **argv)
         std::vector<std::vector<double>> lat(S);
         std::vector<uint64_t> bytes(S, 0);
         std::atomic<int> failures{0};
+        std::vector<uint64_t> sse((size_t)S * 3, 0), samples((size_t)S * 3, 0);
         auto work = [&](int k) {
             lat[k].reserve(frames);
             for (int i = 0; i < frames; i++) {
@@ -113,6 +130,9 @@ int main(int argc, char **argv)
                 lat[k].push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
                 if (rc != VIDEO_ENCODER_SUCCESS) failures++;
                 else bytes[k] += n;
+                mi355x_h264_quality q;
+                if (psnr && rc == VIDEO_ENCODER_SUCCESS && vc_last_quality(encs[k], &q) == 0 && q.valid)
+                    for (int p = 0; p < 3; p++) { sse[(size_t)k * 3 + p] += q.sse[p]; samples[(size_t)k * 3 + p] += q.samples[p]; }
             }
         };
         std::vector<std::thread> ths;
@@ -126,9 +146,19 @@ int main(int argc, char **argv)
         for (int k = 0; k < S; k++) { all.insert(all.end(), lat[k].begin(), lat[k].end()); total += bytes[k]; }
         std::sort(all.begin(), all.end());
         const size_t n = all.size();
+        char q[160] = "";
+        if (psnr) {
+            double db[3];
+            for (int p = 0; p < 3; p++) {
+                uint64_t e = 0, m = 0;
+                for (int k = 0; k < S; k++) { e += sse[(size_t)k * 3 + p]; m += samples[(size_t)k * 3 + p]; }
+                db[p] = m == 0 ? 0.0 : (e == 0 ? 999.0 : 10.0 * std::log10(65025.0 * (double)m / (double)e));   // (999: no error at all)
+            }
+            snprintf(q, sizeof(q), ",\"psnr_y\":%.3f,\"psnr_u\":%.3f,\"psnr_v\":%.3f", db[0], db[1], db[2]);
+        }
         printf("{\"streams\":%d,\"fps_aggregate\":%.1f,\"fps_per_stream\":%.1f,\"latency_ms_p50\":%.3f,\"latency_ms_p99\":%.3f,\"bytes_per_picture\":%.1f,"
-               "\"bitrate_achieved\":%.0f,\"pictures\":%zu,\"encode_failures\":%d}\n",
-               S, n / dt, n / dt / S, all[n / 2], all[std::min(n - 1, (size_t)(n * 0.99))], (double)total / n, (double)total * 8 * 30 / n, n, failures.load());
+               "\"bitrate_achieved\":%.0f,\"pictures\":%zu,\"encode_failures\":%d%s}\n",
+               S, n / dt, n / dt / S, all[n / 2], all[std::min(n - 1, (size_t)(n * 0.99))], (double)total / n, (double)total * 8 * 30 / n, n, failures.load(), q);
         fflush(stdout);
     }
     return 0;
