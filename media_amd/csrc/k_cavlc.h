@@ -17,20 +17,12 @@
 #pragma once
 #include "dev_common.h"
 #include "h264_vlc_tables.h"
+#include "h264_vlc_packed.h"
 
 namespace h264 {
 
-// ---- Table 9-5 .. 9-10 (ITU-T H.264): initialisers in h264_vlc_tables.h ----
-__constant__ const uint8_t c_ct_len[4][68] = H264_TAB_CT_LEN;
-__constant__ const uint8_t c_ct_bits[4][68] = H264_TAB_CT_BITS;
-__constant__ const uint8_t c_cdc_len[20] = H264_TAB_CDC_LEN;
-__constant__ const uint8_t c_cdc_bits[20] = H264_TAB_CDC_BITS;
-__constant__ const uint8_t c_tz_len[15][16] = H264_TAB_TZ_LEN;
-__constant__ const uint8_t c_tz_bits[15][16] = H264_TAB_TZ_BITS;
-__constant__ const uint8_t c_ctz_len[3][4] = H264_TAB_CTZ_LEN;
-__constant__ const uint8_t c_ctz_bits[3][4] = H264_TAB_CTZ_BITS;
-__constant__ const uint8_t c_run_len[7][16] = H264_TAB_RUN_LEN;
-__constant__ const uint8_t c_run_bits[7][16] = H264_TAB_RUN_BITS;
+// ---- Tables 9-5 .. 9-10 (ITU-T H.264), length and bits of a code in one 16-bit entry: h264_vlc_packed.h ----
+__constant__ const VlcPacked c_vlc = vlc_packed();
 // Table 9-4, inverted for the encoder: coded_block_pattern -> codeNum (inter)
 __constant__ const uint8_t c_cbp2code_inter[48] = H264_TAB_CBP2CODE_INTER;
 
@@ -118,59 +110,64 @@ __device__ __forceinline__ void put_level(S& s, int code, int suffix_len)
     s.put(2 * prefix - 2, (1u << (prefix - 3)) | (unsigned)c);
 }
 
-// residual_block_cavlc(): lv points at scan position 0 of this block's list.  maxc (4, 15 or 16) and nC (-1: chroma DC) are
-// RUN-TIME values: code_slot has one call site, so the lanes of a wave that hold an Intra16x16 DC, a luma, a chroma DC and a
-// chroma AC block walk this code together instead of one block kind after the other.
-// All 16 entries from lv on are read whatever maxc is (they lie inside the macroblock's own levels row for every block kind:
-// the last one is LV_CHROMA_AC + 7 * 16 + 1 + 15 < LV_STRIDE) and the ones from maxc on are masked out.
+// entry i (0 .. 15) of a block of 16 levels held in eight registers: a select on i >> 1, then the half
+__device__ __forceinline__ int level_at(const uint32_t (&w)[8], int i)
+{
+    const int k = i >> 1;
+    const uint32_t a = k & 1 ? w[1] : w[0], b = k & 1 ? w[3] : w[2], c = k & 1 ? w[5] : w[4], d = k & 1 ? w[7] : w[6];
+    const uint32_t ab = k & 2 ? b : a, cd = k & 2 ? d : c, x = k & 4 ? cd : ab;
+    return (int)(int16_t)(i & 1 ? x >> 16 : x);
+}
+
+// residual_block_cavlc(): w holds the aligned 32 bytes of `levels` the block lies in, and its list starts at entry `first` of
+// them (0; 1 for the AC lists, which leave out the DC position; 4 for the second chroma DC block).  maxc (4, 15 or 16) and nC
+// (-1: chroma DC) are RUN-TIME values: code_slot has one call site, so the lanes of a wave that hold an Intra16x16 DC, a luma,
+// a chroma DC and a chroma AC block walk this code together instead of one block kind after the other.
+// Nothing here loads a level: code_slot fetched the block with everything else it needs.  The two table entries that depend
+// on the block's shape alone (coeff_token, total_zeros) are requested together; the run_before codes follow one by one.
 template <class S>
-__device__ __forceinline__ void cavlc_block(S& s, const int16_t* lv, int maxc, int nC)
+__device__ __forceinline__ void cavlc_block(S& s, const uint32_t (&w)[8], int first, int maxc, int nC)
 {
     unsigned nzm = 0;
 #pragma unroll
-    for (int i = 0; i < 16; i++) nzm |= (unsigned)(lv[i] != 0) << i;
-    nzm &= (1u << maxc) - 1u;
+    for (int k = 0; k < 8; k++) nzm |= (unsigned)((w[k] & 0xFFFFu) != 0u) << (2 * k) | (unsigned)((w[k] >> 16) != 0u) << (2 * k + 1);
+    nzm = (nzm >> first) & ((1u << maxc) - 1u);
     const bool cdc = nC == -1;
     const int tc = __popc(nzm);
     // the (up to three) trailing ones, highest frequency first, and their trailing_ones_sign_flags: one walk, one put
     unsigned m = nzm, signs = 0;
     int t1 = 0;
     while (m && t1 < 3) {
-        const int i = 31 - __clz((int)m), v = lv[i];
+        const int i = 31 - __clz((int)m), v = level_at(w, first + i);
         if (v != 1 && v != -1) break;
         signs = (signs << 1) | (v < 0 ? 1u : 0u);
         t1++; m &= ~(1u << i);
     }
-    {   // coeff_token: Table 9-5, the column by nC (one load from the selected table, not a branch per table)
-        const int tab = nC < 2 ? 0 : nC < 4 ? 1 : nC < 8 ? 2 : 3;
-        const uint8_t* const tl = cdc ? c_cdc_len : c_ct_len[tab];
-        const uint8_t* const tb = cdc ? c_cdc_bits : c_ct_bits[tab];
-        s.put(tl[4 * tc + t1], tb[4 * tc + t1]);
-    }
+    const int top = 31 - __clz((int)nzm);   // (-1 without coefficients)
+    const int tz = top + 1 - tc;
+    const bool has_tz = tc != 0 && tc < maxc;
+    // coeff_token: Table 9-5, the column by nC.  total_zeros: Table 9-9 (a) for chroma DC (tc <= 3 there), Tables 9-7 / 9-8 otherwise
+    const int tab = nC < 2 ? 0 : nC < 4 ? 1 : nC < 8 ? 2 : 3;
+    const unsigned e_ct = c_vlc.e[(cdc ? VLC_CDC : VLC_CT + 68 * tab) + 4 * tc + t1];
+    const unsigned e_tz = c_vlc.e[has_tz ? (cdc ? VLC_CTZ + 4 * (tc - 1) : VLC_TZ + 16 * (tc - 1)) + tz : 0];
+    s.put((int)(e_ct & 255u), e_ct >> 8);
     if (!tc) return;
     s.put(t1, signs);
     int suffix_len = (tc > 10 && t1 < 3) ? 1 : 0;
-    bool first = true;
+    bool first_level = true;
     while (m) {
         const int i = 31 - __clz((int)m);
         m &= ~(1u << i);
-        const int lvl = lv[i];
+        const int lvl = level_at(w, first + i);
         int code = lvl > 0 ? 2 * lvl - 2 : -2 * lvl - 1;
-        if (first && t1 < 3) code -= 2;
-        first = false;
+        if (first_level && t1 < 3) code -= 2;
+        first_level = false;
         put_level(s, code, suffix_len);
         if (suffix_len == 0) suffix_len = 1;
         if (iabs(lvl) > (3 << (suffix_len - 1)) && suffix_len < 6) suffix_len++;
     }
-    const int top = 31 - __clz((int)nzm);
-    if (tc < maxc) {
-        const int tz = top + 1 - tc;
-        {   // total_zeros: Table 9-9 (a) for chroma DC (tc <= 3 here), Tables 9-7 / 9-8 otherwise
-            const int e = cdc ? 4 * (tc - 1) + tz : 16 * (tc - 1) + tz;
-            const uint8_t* const tl = cdc ? &c_ctz_len[0][0] : &c_tz_len[0][0];
-            const uint8_t* const tb = cdc ? &c_ctz_bits[0][0] : &c_tz_bits[0][0];
-            s.put(tl[e], tb[e]);
-        }
+    if (has_tz) {
+        s.put((int)(e_tz & 255u), e_tz >> 8);
         int zl = tz;
         m = nzm;
         int hi = top;
@@ -180,23 +177,20 @@ __device__ __forceinline__ void cavlc_block(S& s, const int16_t* lv, int maxc, i
             m &= ~(1u << lo);
             const int run = hi - lo - 1;
             const int t = (zl > 7 ? 7 : zl) - 1;
-            s.put(c_run_len[t][run], c_run_bits[t][run]);
+            const unsigned e = c_vlc.e[VLC_RUN + 16 * t + run];
+            s.put((int)(e & 255u), e >> 8);
             zl -= run;
             hi = lo;
         }
     }
 }
 
-// nC of a block (9.2.1) from the TotalCoeff of the block to its left (nA) and above it (nB).  The caller names each of them as
-// an entry of tc[]: `in` when the neighbour lies in this macroblock (x > 0 / y > 0), `out` in the macroblock to the left /
-// above otherwise (top: the macroblock above is in this slice).  One body for luma and chroma blocks.
-__device__ __forceinline__ int nc_block(const MbInfo* m, int mx, bool top, int mbw, bool a_in, int ia_in, int ia_out, bool b_in, int ib_in, int ib_out)
+// nC of a block (9.2.1) from the TotalCoeff of the block to its left (nA) and above it (nB); a_ok / b_ok: that block exists
+// (in this macroblock, in the macroblock to the left, or in the macroblock above when that one is in this slice)
+__device__ __forceinline__ int nc_from(bool a_ok, int nA, bool b_ok, int nB)
 {
-    int nA = -1, nB = -1;
-    if (a_in || mx > 0) nA = (a_in ? m : m - 1)->tc[a_in ? ia_in : ia_out];
-    if (b_in || top) nB = (b_in ? m : m - mbw)->tc[b_in ? ib_in : ib_out];
-    if (nA >= 0 && nB >= 0) return (nA + nB + 1) >> 1;
-    return nA >= 0 ? nA : (nB >= 0 ? nB : 0);
+    if (a_ok && b_ok) return (nA + nB + 1) >> 1;
+    return a_ok ? nA : (b_ok ? nB : 0);
 }
 
 struct CavlcParams {
@@ -295,23 +289,105 @@ __device__ __forceinline__ unsigned pcm_sample(const CavlcParams& C, int comp, i
 }
 
 // slot: 0 header, 1 Intra16x16 DC, 2..17 luma blkIdx 0..15, 18/19 chroma DC, 20..27 chroma AC
+//
+// Two round trips to memory instead of a chain of dependent ones (type, then cbp, then the neighbours' TotalCoeff, then every
+// level by itself).  The FIRST asks, unconditionally and at addresses clamped into the macroblock's own data where a neighbour
+// is missing, for everything small that can be addressed from (mbi, slot) alone:
+//   - the word of the macroblock's MbInfo that holds type, i16_mode, chroma_mode and cbp;
+//   - the two neighbour bytes the slot looks at: tc[] of the blocks to the left of and above a luma or chroma AC block (in this
+//     macroblock, in the one to the left or in the one above), or - slot 0 - the types of the macroblocks to the left and above
+//     (the Intra4x4 mode prediction asks for them).  The byte's place in the 32-byte record is known here, so the record
+//     itself is not fetched: picking tc[i] out of eight registers by a run-time i would cost more than the byte's address;
+//   - slot 0: prevcoded[mbi], the eight mvd, the sixteen Intra4x4 modes of the macroblock, of its left and of its upper one
+//     (on an IDR picture prevcoded and mvd hold what an earlier picture left, or nothing: both buffers exist whatever the
+//     picture type, and the values are used under p_slice and for inter macroblocks only).
+// The SECOND, only where type and cbp say that the slot has a block: the aligned 32 bytes of `levels` the block lies in
+// (LV_LUMA + 16 b, LV_CHROMA_AC + 16 k and LV_CHROMA_DC are multiples of eight entries, a macroblock's row is 832 bytes): two
+// 16-byte loads, which end inside the row for every slot (the last: LV_CHROMA_AC + 7 * 16 + 16 <= LV_STRIDE).  Asking for them
+// in the first trip as well - 832 bytes per macroblock whatever the pattern says - made the P count pass and static content
+// slower: most blocks of a P picture are left out by the pattern, and a P_Skip macroblock has none.
+struct MbWord {   // MbInfo bytes 4..7
+    uint32_t v;
+    __device__ __forceinline__ int type() const { return (int)(v & 255u); }
+    __device__ __forceinline__ int i16_mode() const { return (int)((v >> 8) & 255u); }
+    __device__ __forceinline__ unsigned chroma_mode() const { return (v >> 16) & 255u; }
+    __device__ __forceinline__ int cbp() const { return (int)(v >> 24); }
+};
+static_assert(offsetof(MbInfo, type) == 4 && offsetof(MbInfo, i16_mode) == 5 && offsetof(MbInfo, chroma_mode) == 6 && offsetof(MbInfo, cbp) == 7 && offsetof(MbInfo, tc) == 8, "MbWord, code_slot");
+// byte k (a constant after unrolling) of sixteen bytes
+__device__ __forceinline__ int byte_of(const uint4& v, int k)
+{
+    const uint32_t w = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
+    return (int)((w >> (8 * (k & 3))) & 255u);
+}
+
 template <class S>
 __device__ __forceinline__ void code_slot(S& s, const CavlcParams& C, int mbi, int slot)
 {
-    const MbInfo* m = C.mb + mbi;
-    if (m->type == MB_PSKIP) return;
     const int my = C.mbdiv.row(mbi), mx = mbi - my * C.mbw;
     const int srow = C.sl.row_in_slice(my);
     const bool top = srow != 0;
-    const int16_t* lv = C.levels + (size_t)mbi * LV_STRIDE;
-    const int cbpl = m->cbp & 15, cbpc = m->cbp >> 4;
-    const bool i16 = m->type == MB_I16;
-    if (m->type == MB_IPCM) {
+    // ---- what the slot is, as far as that needs no data: its level block and its two neighbour bytes ----
+    const int left = mx > 0 ? -(int)sizeof(MbInfo) : 0, up = top ? -(int)sizeof(MbInfo) * C.mbw : 0;   // (0: missing, the macroblock itself instead)
+    int lvoff = 0;                                       // first entry of the aligned block in the macroblock's row
+    int oa = left + (int)offsetof(MbInfo, type), ob = up + (int)offsetof(MbInfo, type);   // neighbour bytes, from this macroblock's record
+    bool a_ok = false, b_ok = false;
+    if (slot >= 1 && slot < 18) {
+        // slot 1: Intra16x16 DC (nC of blkIdx 0); slots 2..17: blkIdx 0..15
+        const int b = slot == 1 ? 0 : slot - 2, x = blk_x(b), y = blk_y(b);
+        lvoff = slot == 1 ? LV_LUMA_DC : LV_LUMA + b * 16;
+        oa = (int)offsetof(MbInfo, tc) + (x > 0 ? xy2blk(x - 1, y) : left + xy2blk(3, y));
+        ob = (int)offsetof(MbInfo, tc) + (y > 0 ? xy2blk(x, y - 1) : up + xy2blk(x, 3));
+        a_ok = x > 0 || mx > 0;
+        b_ok = y > 0 || top;
+    } else if (slot < 20) {
+        if (slot >= 18) lvoff = LV_CHROMA_DC;
+    } else if (slot < 28) {
+        const int k = slot - 20, base = 16 + (k >> 2) * 4, x = k & 1, y = (k >> 1) & 1;
+        lvoff = LV_CHROMA_AC + k * 16;
+        oa = (int)offsetof(MbInfo, tc) + (x > 0 ? base + 2 * y : left + base + 2 * y + 1);
+        ob = (int)offsetof(MbInfo, tc) + (y > 0 ? base + x : up + base + 2 + x);
+        a_ok = x > 0 || mx > 0;
+        b_ok = y > 0 || top;
+    }
+    // ---- the first trip ----
+    const uint8_t* const rec = (const uint8_t*)(C.mb + mbi);
+    const MbWord m = {*(const uint32_t*)(rec + offsetof(MbInfo, type))};
+    const int nA = rec[oa], nB = rec[ob];
+    int prev = -1;
+    uint4 mvd = make_uint4(0, 0, 0, 0), am = mvd, am_left = mvd, am_up = mvd;
+    if (slot == 0) {
+        prev = C.prevcoded[mbi];
+        mvd = *(const uint4*)(C.mvd + 8 * (size_t)mbi);
+        const uint8_t* const a = C.aux + (size_t)mbi * 16;
+        am = *(const uint4*)a;
+        am_left = *(const uint4*)(a + (mx > 0 ? -16 : 0));
+        am_up = *(const uint4*)(a + (top ? -16 * C.mbw : 0));
+    }
+    if (m.type() == MB_PSKIP) return;
+    const int cbpl = m.cbp() & 15, cbpc = m.cbp() >> 4;
+    const bool i16 = m.type() == MB_I16;
+    // ---- the second trip: the slot's levels, where it has a block (requested here, in front of the header's code) ----
+    bool has_block = false;
+    if (m.type() != MB_IPCM) {
+        if (slot >= 1 && slot < 18) has_block = slot == 1 ? i16 : (cbpl & (1 << ((slot - 2) >> 2))) != 0;
+        else if (slot == 18 || slot == 19) has_block = cbpc != 0;
+        else if (slot >= 20 && slot < 28) has_block = cbpc == 2;
+    }
+    uint4 lv0 = make_uint4(0, 0, 0, 0), lv1 = lv0;
+    if (has_block) {
+        const uint4* const lvp = (const uint4*)(C.levels + (size_t)mbi * LV_STRIDE + lvoff);
+        lv0 = lvp[0];
+        lv1 = lvp[1];
+    }
+    const uint32_t w[8] = {lv0.x, lv0.y, lv0.z, lv0.w, lv1.x, lv1.y, lv1.z, lv1.w};
+    // ---- registers only from here on (the samples of an I_PCM macroblock and Table 9-4 apart) ----
+    if (m.type() == MB_IPCM) {
         // 7.3.5: mb_type I_PCM (slot 0; the alignment zero bits after it are left to the zeroed buffer, k_bit_scan and the
         // write pass place the samples on the next byte boundary), then 384 samples, 16 per slot: slots 1..16 the luma rows,
         // 17..20 Cb (two rows each), 21..24 Cr
         if (slot == 0) {
-            if (C.p_slice) put_ue(s, (unsigned)(mbi - 1 - max(C.prevcoded[mbi], (my - srow) * C.mbw - 1)));
+            if (C.p_slice) put_ue(s, (unsigned)(mbi - 1 - max(prev, (my - srow) * C.mbw - 1)));
             put_ue(s, C.p_slice ? 30u : 25u);
         } else if (slot <= 24) {
             const int comp = slot <= 16 ? 0 : (slot <= 20 ? 1 : 2);
@@ -332,79 +408,75 @@ __device__ __forceinline__ void code_slot(S& s, const CavlcParams& C, int mbi, i
     if (slot == 0) {
         if (C.p_slice) {
             // mb_skip_run: the P_Skip macroblocks right before this one, counted from the slice's first macroblock
-            put_ue(s, (unsigned)(mbi - 1 - max(C.prevcoded[mbi], (my - srow) * C.mbw - 1)));
+            put_ue(s, (unsigned)(mbi - 1 - max(prev, (my - srow) * C.mbw - 1)));
         }
-        if (m->type == MB_I4) {
+        if (m.type() == MB_I4) {
             // I_NxN (7.3.5.1): the sixteen Intra4x4 modes against their predictions (8.3.1.1: the smaller of the left and upper
             // blocks' modes; DC when such a neighbour is not an Intra4x4 macroblock, or missing), then chroma mode and coded_block_pattern
-            const uint8_t* am = C.aux + (size_t)mbi * 16;
+            // (slot 0: nA / nB are the types of the macroblocks to the left and above.  Unrolled: every mode is a constant byte of
+            // a register)
             put_ue(s, C.p_slice ? 5u : 0u);
             if (C.t8x8) s.put(1, 0u);   // transform_size_8x8_flag: Intra4x4, not Intra8x8
-#pragma unroll 1
+#pragma unroll
             for (int k = 0; k < 16; k++) {
                 const int x = blk_x(k), y = blk_y(k);
                 int mA, mB;
                 bool dc_only = false;
-                if (x > 0) mA = am[xy2blk(x - 1, y)];
+                if (x > 0) mA = byte_of(am, xy2blk(x - 1, y));
                 else if (mx == 0) { dc_only = true; mA = 2; }
-                else mA = (m - 1)->type == MB_I4 ? (am - 16)[xy2blk(3, y)] : 2;
-                if (y > 0) mB = am[xy2blk(x, y - 1)];
+                else mA = nA == MB_I4 ? byte_of(am_left, xy2blk(3, y)) : 2;
+                if (y > 0) mB = byte_of(am, xy2blk(x, y - 1));
                 else if (!top) { dc_only = true; mB = 2; }
-                else mB = (m - C.mbw)->type == MB_I4 ? (am - 16 * C.mbw)[xy2blk(x, 3)] : 2;
-                const int pm = dc_only ? 2 : min(mA, mB), mode = am[k];
+                else mB = nB == MB_I4 ? byte_of(am_up, xy2blk(x, 3)) : 2;
+                const int pm = dc_only ? 2 : min(mA, mB), mode = byte_of(am, k);
                 if (mode == pm) s.put(1, 1u);
                 else s.put(4, (unsigned)(mode < pm ? mode : mode - 1));   // prev_intra4x4_pred_mode_flag = 0, rem_intra4x4_pred_mode
             }
-            put_ue(s, m->chroma_mode);
-            put_ue(s, c_cbp2code_intra[m->cbp]);
-            if (m->cbp) put_se(s, 0);
+            put_ue(s, m.chroma_mode());
+            put_ue(s, c_cbp2code_intra[m.cbp()]);
+            if (m.cbp()) put_se(s, 0);
         } else if (i16) {
-            const unsigned t = 1u + m->i16_mode + 4u * (unsigned)cbpc + (cbpl ? 12u : 0u);
+            const unsigned t = 1u + m.i16_mode() + 4u * (unsigned)cbpc + (cbpl ? 12u : 0u);
             put_ue(s, C.p_slice ? 5u + t : t);
-            put_ue(s, m->chroma_mode);
+            put_ue(s, m.chroma_mode());
             put_se(s, 0);
         } else {
             // 7.3.5.1 / 7.3.5.2: mb_type (0 P_L0_16x16, 1 P_L0_L0_16x8, 2 P_L0_L0_8x16, 3 P_8x8 with four sub_mb_type P_L0_8x8),
             // every partition's ref_idx_l0, then every partition's mvd_l0 (k_mvpred left them in coding order)
-            const int shape = m->type >= MB_P16X8 ? m->type - MB_P16X8 + 1 : 0, nparts = shape == 0 ? 1 : (shape == 3 ? 4 : 2);
+            const int shape = m.type() >= MB_P16X8 ? m.type() - MB_P16X8 + 1 : 0, nparts = shape == 0 ? 1 : (shape == 3 ? 4 : 2);
             put_ue(s, (unsigned)shape);
             if (shape == 3) s.put(4, 15u);   // four times ue(0)
             for (int k = 0; k < nparts; k++) {
-                if (C.nref == 2) s.put(1, m->chroma_mode ? 0u : 1u);   // ref_idx_l0, te(v): with two pictures the inverted bit (9.1)
-                else if (C.nref > 2) put_ue(s, m->chroma_mode);
+                if (C.nref == 2) s.put(1, m.chroma_mode() ? 0u : 1u);   // ref_idx_l0, te(v): with two pictures the inverted bit (9.1)
+                else if (C.nref > 2) put_ue(s, m.chroma_mode());
             }
-            for (int k = 0; k < nparts; k++) {
-                put_se(s, C.mvd[8 * mbi + 2 * k]);
-                put_se(s, C.mvd[8 * mbi + 2 * k + 1]);
-            }
-            put_ue(s, c_cbp2code_inter[m->cbp]);
-            if (C.t8x8 && cbpl) s.put(1, m->i16_mode & 1u);   // transform_size_8x8_flag (High profile, luma coefficients present)
-            if (m->cbp) put_se(s, 0);
+            const uint32_t vd[4] = {mvd.x, mvd.y, mvd.z, mvd.w};   // (x, y) of partition k: the halves of word k
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (k < nparts) {
+                    put_se(s, (int)(int16_t)(vd[k] & 0xFFFFu));
+                    put_se(s, (int)(int16_t)(vd[k] >> 16));
+                }
+            put_ue(s, c_cbp2code_inter[m.cbp()]);
+            if (C.t8x8 && cbpl) s.put(1, m.i16_mode() & 1u);   // transform_size_8x8_flag (High profile, luma coefficients present)
+            if (m.cbp()) put_se(s, 0);
         }
     }
     // Slots 1..27: what this lane's block is - nothing is coded here.  Lanes of one wave hold all four block kinds, and a wave
     // runs divergent paths one after the other, so the coder itself follows once, after the branches have rejoined.
-    bool has_block = false;
-    const int16_t* blk = lv;
-    int maxc = 16, nC = 0;
+    int first = 0, maxc = 16, nC = nc_from(a_ok, nA, b_ok, nB);
     if (slot >= 1 && slot < 18) {
-        // slot 1: Intra16x16 DC (nC of blkIdx 0); slots 2..17: blkIdx 0..15, Intra16x16 AC (scan positions 1..15) or a whole luma block
-        const int b = slot == 1 ? 0 : slot - 2, x = blk_x(b), y = blk_y(b);
-        has_block = slot == 1 ? i16 : (cbpl & (1 << (b >> 2))) != 0;
+        // slot 1: Intra16x16 DC; slots 2..17: Intra16x16 AC (scan positions 1..15) or a whole luma block
         const bool ac = i16 && slot != 1;
-        blk = lv + (slot == 1 ? LV_LUMA_DC : LV_LUMA + b * 16 + (ac ? 1 : 0));
+        first = ac ? 1 : 0;
         maxc = ac ? 15 : 16;
-        if (has_block) nC = nc_block(m, mx, top, C.mbw, x > 0, xy2blk(x - 1, y), xy2blk(3, y), y > 0, xy2blk(x, y - 1), xy2blk(x, 3));
     } else if (slot < 20) {
-        if (slot >= 18) { has_block = cbpc != 0; blk = lv + LV_CHROMA_DC + (slot - 18) * 4; maxc = 4; nC = -1; }
+        if (slot >= 18) { first = (slot - 18) * 4; maxc = 4; nC = -1; }
     } else if (slot < 28) {
-        const int k = slot - 20, base = 16 + (k >> 2) * 4, x = k & 1, y = (k >> 1) & 1;
-        has_block = cbpc == 2;
-        blk = lv + LV_CHROMA_AC + k * 16 + 1;
+        first = 1;
         maxc = 15;
-        if (has_block) nC = nc_block(m, mx, top, C.mbw, x > 0, base + 2 * y, base + 2 * y + 1, y > 0, base + x, base + 2 + x);
     }
-    if (has_block) cavlc_block(s, blk, maxc, nC);
+    if (has_block) cavlc_block(s, w, first, maxc, nC);
 }
 
 // boundary strengths of every macroblock for the loop filter (lane = macroblock, edge segment).  Its own small
