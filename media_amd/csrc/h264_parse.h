@@ -839,7 +839,11 @@ private:
                 int px, py;
                 predict(mx, my, x4, y4, w4, h4, r, px, py, mbpart);
                 const int dx = br.se(), dy = br.se();
-                if (dx < -8192 || dx > 8191 || dy < -8192 || dy > 8191) { fail("mvd_l0 out of range"); return false; }
+                // A.3.1 bounds the VECTOR (-2048 .. 2047.75 samples horizontally at every level), not the difference: a predictor at
+                // one limit and a vector at the other make |mvd_l0| 16383.  What is refused here is what the arithmetic and the
+                // int16 arrays cannot hold: the predictor is a stored vector, so a difference beyond the distance between two
+                // storable vectors cannot lead to one (and px + dx stays far inside an int), then the vector itself
+                if (dx < -32768 || dx > 32767 || dy < -32768 || dy > 32767) { fail("mvd_l0 out of range"); return false; }
                 const int vx = px + dx, vy = py + dy;
                 if (vx < -16384 || vx > 16383 || vy < -16384 || vy > 16383) { fail("motion vector out of range"); return false; }
                 set_vectors(mx, my, x4, y4, w4, h4, vx, vy);

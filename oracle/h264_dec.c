@@ -275,6 +275,7 @@ struct h264o_dec {
     int slice_idc[256], slice_oa[256], slice_ob[256];
     int cur_is_ref, cur_frame_num, cur_is_idr, cur_pps_id;
     int max_mb_bits, max_level_prefix;
+    int stat[H264O_DSTAT_COUNT];   /* h264o_dec_stat, of the picture being decoded */
     char err[200];
 };
 
@@ -314,6 +315,16 @@ int h264o_dec_mb_kind(const h264o_dec *d, int addr) { return addr >= 0 && addr <
 int h264o_dec_mb_qp(const h264o_dec *d, int addr) { return addr >= 0 && addr < d->mbw * d->mbh ? d->mb[addr].qp : -1; }   /* QP_Y (0 for I_PCM) */
 int h264o_dec_max_mb_bits(const h264o_dec *d) { return d->max_mb_bits; }
 int h264o_dec_max_level_prefix(const h264o_dec *d) { return d->max_level_prefix; }
+int h264o_dec_stat(const h264o_dec *d, int which) { return which >= 0 && which < H264O_DSTAT_COUNT ? d->stat[which] : -1; }
+/* the statistics of the decoder whose picture is being decoded: the scaling and transform functions below are plain functions of
+ * their arguments, so they find it here */
+static __thread int *g_stat;
+static inline int trk(int v)   /* an intermediate of 8.5.10 - 8.5.13: its magnitude is noted, it is passed on unchanged */
+{
+    if (g_stat) { const int a = v < 0 ? -(v + 1) : v;   /* (-2^15 is inside the range, 2^15 is not: -v - 1 puts both ends at 2^15 - 1) */
+                  if (a > g_stat[H264O_DSTAT_MAX_INTERMEDIATE]) g_stat[H264O_DSTAT_MAX_INTERMEDIATE] = a; }
+    return v;
+}
 int h264o_dec_mb_mv(const h264o_dec *d, int addr, int blk4, int *mvx, int *mvy, int *ref)
 {
     if (addr < 0 || addr >= d->mbw * d->mbh || blk4 < 0 || blk4 > 15) return -1;
@@ -453,7 +464,7 @@ static int residual_block(h264o_dec *d, bitr *b, int nC, int max_coeff, int *coe
     int level[16];
     int suffixLength = (total > 10 && t1s < 3) ? 1 : 0;   /* 9.2.2 */
     for (int i = 0; i < total; i++) {
-        if (i < t1s) { level[i] = 1 - 2 * (int)rd_bit(b); continue; }
+        if (i < t1s) { level[i] = 1 - 2 * (int)rd_bit(b); if (!d->stat[H264O_DSTAT_MAX_LEVEL]) d->stat[H264O_DSTAT_MAX_LEVEL] = 1; continue; }
         int level_prefix = 0;                              /* 9.2.2.1 */
         while (!rd_bit(b)) { if (++level_prefix > 25 || b->err) { b->err = 1; return 0; } }
         if (level_prefix > d->max_level_prefix) d->max_level_prefix = level_prefix;
@@ -464,6 +475,7 @@ static int residual_block(h264o_dec *d, bitr *b, int nC, int max_coeff, int *coe
         if (level_prefix >= 16) levelCode += (1 << (level_prefix - 3)) - 4096;
         if (i == t1s && t1s < 3) levelCode += 2;
         level[i] = (levelCode % 2 == 0) ? (levelCode + 2) >> 1 : (-levelCode - 1) >> 1;
+        if (abs(level[i]) > d->stat[H264O_DSTAT_MAX_LEVEL]) d->stat[H264O_DSTAT_MAX_LEVEL] = abs(level[i]);
         if (suffixLength == 0) suffixLength = 1;
         if (abs(level[i]) > (3 << (suffixLength - 1)) && suffixLength < 6) suffixLength++;
     }
@@ -555,8 +567,8 @@ static void scale4x4(const int c[4][4], int qp, int keep_dc, int dcval, int dd[4
         for (int j = 0; j < 4; j++) {
             if (keep_dc && i == 0 && j == 0) { dd[0][0] = dcval; continue; }
             const int ls = level_scale4(qp % 6, i, j);
-            if (qp >= 24) dd[i][j] = (c[i][j] * ls) << (qp / 6 - 4);
-            else dd[i][j] = (c[i][j] * ls + (1 << (3 - qp / 6))) >> (4 - qp / 6);
+            if (qp >= 24) dd[i][j] = trk((c[i][j] * ls) << (qp / 6 - 4));
+            else dd[i][j] = trk((c[i][j] * ls + (1 << (3 - qp / 6))) >> (4 - qp / 6));
         }
 }
 /* 8.5.12.2 */
@@ -564,14 +576,14 @@ static void inverse4x4(const int dd[4][4], int r[4][4])
 {
     int f[4][4], h[4][4];
     for (int i = 0; i < 4; i++) {
-        const int e0 = dd[i][0] + dd[i][2], e1 = dd[i][0] - dd[i][2];
-        const int e2 = (dd[i][1] >> 1) - dd[i][3], e3 = dd[i][1] + (dd[i][3] >> 1);
-        f[i][0] = e0 + e3; f[i][1] = e1 + e2; f[i][2] = e1 - e2; f[i][3] = e0 - e3;
+        const int e0 = trk(dd[i][0] + dd[i][2]), e1 = trk(dd[i][0] - dd[i][2]);
+        const int e2 = trk((dd[i][1] >> 1) - dd[i][3]), e3 = trk(dd[i][1] + (dd[i][3] >> 1));
+        f[i][0] = trk(e0 + e3); f[i][1] = trk(e1 + e2); f[i][2] = trk(e1 - e2); f[i][3] = trk(e0 - e3);
     }
     for (int j = 0; j < 4; j++) {
-        const int g0 = f[0][j] + f[2][j], g1 = f[0][j] - f[2][j];
-        const int g2 = (f[1][j] >> 1) - f[3][j], g3 = f[1][j] + (f[3][j] >> 1);
-        h[0][j] = g0 + g3; h[1][j] = g1 + g2; h[2][j] = g1 - g2; h[3][j] = g0 - g3;
+        const int g0 = trk(f[0][j] + f[2][j]), g1 = trk(f[0][j] - f[2][j]);
+        const int g2 = trk((f[1][j] >> 1) - f[3][j]), g3 = trk(f[1][j] + (f[3][j] >> 1));
+        h[0][j] = trk(g0 + g3); h[1][j] = trk(g1 + g2); h[2][j] = trk(g1 - g2); h[3][j] = trk(g0 - g3);
     }
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) r[i][j] = (h[i][j] + 32) >> 6;
@@ -579,14 +591,14 @@ static void inverse4x4(const int dd[4][4], int r[4][4])
 /* 8.5.13: 8x8 scaling + inverse transform */
 static void one_d8(const int in[8], int out[8])
 {
-    const int a0 = in[0] + in[4], a1 = -in[3] + in[5] - in[7] - (in[7] >> 1);
-    const int a2 = in[0] - in[4], a3 = in[1] + in[7] - in[3] - (in[3] >> 1);
-    const int a4 = (in[2] >> 1) - in[6], a5 = -in[1] + in[7] + in[5] + (in[5] >> 1);
-    const int a6 = in[2] + (in[6] >> 1), a7 = in[3] + in[5] + in[1] + (in[1] >> 1);
-    const int b0 = a0 + a6, b1 = a1 + (a7 >> 2), b2 = a2 + a4, b3 = a3 + (a5 >> 2);
-    const int b4 = a2 - a4, b5 = (a3 >> 2) - a5, b6 = a0 - a6, b7 = a7 - (a1 >> 2);
-    out[0] = b0 + b7; out[1] = b2 + b5; out[2] = b4 + b3; out[3] = b6 + b1;
-    out[4] = b6 - b1; out[5] = b4 - b3; out[6] = b2 - b5; out[7] = b0 - b7;
+    const int a0 = trk(in[0] + in[4]), a1 = trk(-in[3] + in[5] - in[7] - (in[7] >> 1));
+    const int a2 = trk(in[0] - in[4]), a3 = trk(in[1] + in[7] - in[3] - (in[3] >> 1));
+    const int a4 = trk((in[2] >> 1) - in[6]), a5 = trk(-in[1] + in[7] + in[5] + (in[5] >> 1));
+    const int a6 = trk(in[2] + (in[6] >> 1)), a7 = trk(in[3] + in[5] + in[1] + (in[1] >> 1));
+    const int b0 = trk(a0 + a6), b1 = trk(a1 + (a7 >> 2)), b2 = trk(a2 + a4), b3 = trk(a3 + (a5 >> 2));
+    const int b4 = trk(a2 - a4), b5 = trk((a3 >> 2) - a5), b6 = trk(a0 - a6), b7 = trk(a7 - (a1 >> 2));
+    out[0] = trk(b0 + b7); out[1] = trk(b2 + b5); out[2] = trk(b4 + b3); out[3] = trk(b6 + b1);
+    out[4] = trk(b6 - b1); out[5] = trk(b4 - b3); out[6] = trk(b2 - b5); out[7] = trk(b0 - b7);
 }
 static void scale_inverse8x8(const int c[8][8], int qp, int r[8][8])
 {
@@ -594,8 +606,8 @@ static void scale_inverse8x8(const int c[8][8], int qp, int r[8][8])
     for (int i = 0; i < 8; i++)
         for (int j = 0; j < 8; j++) {
             const int ls = level_scale8(qp % 6, i, j);
-            if (qp >= 36) dd[i][j] = (c[i][j] * ls) << (qp / 6 - 6);
-            else dd[i][j] = (c[i][j] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+            if (qp >= 36) dd[i][j] = trk((c[i][j] * ls) << (qp / 6 - 6));
+            else dd[i][j] = trk((c[i][j] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6));
         }
     for (int i = 0; i < 8; i++) one_d8(dd[i], g[i]);            /* each row */
     for (int j = 0; j < 8; j++) {                                /* each column */
@@ -814,6 +826,20 @@ static int chroma_sample_interp(const h264o_dec *d, const dpic *r, int pl, int x
 static void inter_pred_part(h264o_dec *d, const dpic *r, int x0, int y0, int w, int h, int mvx, int mvy)
 {
     const int cw = d->cw, cs = cw / 2;
+    {   /* statistics: the vector, and whether every luma sample the prediction reads (the six taps of a fractional position
+         * included) lies outside the picture on one side */
+        int *st = d->stat;
+        if (mvx < st[H264O_DSTAT_MV_X_MIN]) st[H264O_DSTAT_MV_X_MIN] = mvx;
+        if (mvx > st[H264O_DSTAT_MV_X_MAX]) st[H264O_DSTAT_MV_X_MAX] = mvx;
+        if (mvy < st[H264O_DSTAT_MV_Y_MIN]) st[H264O_DSTAT_MV_Y_MIN] = mvy;
+        if (mvy > st[H264O_DSTAT_MV_Y_MAX]) st[H264O_DSTAT_MV_Y_MAX] = mvy;
+        const int xa = x0 + (mvx >> 2) - ((mvx & 3) ? 2 : 0), xb = x0 + w - 1 + (mvx >> 2) + ((mvx & 3) ? 3 : 0);
+        const int ya = y0 + (mvy >> 2) - ((mvy & 3) ? 2 : 0), yb = y0 + h - 1 + (mvy >> 2) + ((mvy & 3) ? 3 : 0);
+        if (xb < 0) st[H264O_DSTAT_OUT_LEFT]++;
+        if (xa > cw - 1) st[H264O_DSTAT_OUT_RIGHT]++;
+        if (yb < 0) st[H264O_DSTAT_OUT_TOP]++;
+        if (ya > d->ch - 1) st[H264O_DSTAT_OUT_BOTTOM]++;
+    }
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) {
             const int xq = 4 * (x0 + x) + mvx, yq = 4 * (y0 + y) + mvy;   /* 8-225 .. 8-228 */
@@ -923,9 +949,9 @@ static int chroma_residual(mbctx *c, int qpy)
         const int qpc = qpc_of(d, qpy, pl);
         /* 8.5.11.1: c = [[c0 c1][c2 c3]] (raster 2x2 = chroma DC scan), f = A c A with A = [[1 1][1 -1]] */
         const int c0 = dc[pl][0], c1 = dc[pl][1], c2 = dc[pl][2], c3 = dc[pl][3];
-        const int f[4] = {c0 + c1 + c2 + c3, c0 - c1 + c2 - c3, c0 + c1 - c2 - c3, c0 - c1 - c2 + c3};
+        const int f[4] = {trk(c0 + c1 + c2 + c3), trk(c0 - c1 + c2 - c3), trk(c0 + c1 - c2 - c3), trk(c0 - c1 - c2 + c3)};
         for (int k = 0; k < 4; k++) {
-            const int dcC = ((f[k] * level_scale4(qpc % 6, 0, 0)) << (qpc / 6)) >> 5;   /* 8.5.11.2 */
+            const int dcC = trk(((f[k] * level_scale4(qpc % 6, 0, 0)) << (qpc / 6)) >> 5);   /* 8.5.11.2 */
             int cc[4][4], dd[4][4], r[4][4];
             memset(cc, 0, sizeof(cc));
             for (int i = 1; i < 16; i++) cc[D_ZZ4[i][1]][D_ZZ4[i][0]] = ac[pl][k][i];
@@ -1022,13 +1048,13 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
         int cm[4][4], t[4][4], f[4][4];
         for (int i = 0; i < 16; i++) cm[D_ZZ4[i][1]][D_ZZ4[i][0]] = dcs[i];
         static const int A4[4][4] = {{1, 1, 1, 1}, {1, 1, -1, -1}, {1, -1, -1, 1}, {1, -1, 1, -1}};
-        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { t[i][j] = 0; for (int k = 0; k < 4; k++) t[i][j] += A4[i][k] * cm[k][j]; }
-        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { f[i][j] = 0; for (int k = 0; k < 4; k++) f[i][j] += t[i][k] * A4[k][j]; }
+        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { t[i][j] = 0; for (int k = 0; k < 4; k++) t[i][j] += A4[i][k] * cm[k][j]; trk(t[i][j]); }
+        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { f[i][j] = 0; for (int k = 0; k < 4; k++) f[i][j] += t[i][k] * A4[k][j]; trk(f[i][j]); }
         const int ls = level_scale4(q % 6, 0, 0);
         for (int k = 0; k < 16; k++) {
             const int bx = blk_x4(k), by = blk_y4(k);
             const int fi = f[by][bx];
-            const int dcY = q >= 36 ? (fi * ls) << (q / 6 - 6) : (fi * ls + (1 << (5 - q / 6))) >> (6 - q / 6);
+            const int dcY = trk(q >= 36 ? (fi * ls) << (q / 6 - 6) : (fi * ls + (1 << (5 - q / 6))) >> (6 - q / 6));
             int cc[4][4], dd[4][4], r[4][4];
             memset(cc, 0, sizeof(cc));
             for (int i = 1; i < 16; i++) cc[D_ZZ4[i][1]][D_ZZ4[i][0]] = acs[k][i];
@@ -1132,7 +1158,9 @@ static int decode_inter_mb(mbctx *c, int mbt /* P mb_type 0..4, -1 = P_Skip */, 
             const struct part *p = &parts[i];
             int px, py;
             predict_mv(d, m, done, mx, my, c->sl, c->addr, p->x, p->y, p->w, p->h, refq[p->q], p->shape, p->idx, &px, &py);
-            const int vx = px + rd_se(b), vy = py + rd_se(b);
+            const int dx = rd_se(b), dy = rd_se(b), vx = px + dx, vy = py + dy;
+            if (abs(dx) > d->stat[H264O_DSTAT_MAX_MVD]) d->stat[H264O_DSTAT_MAX_MVD] = abs(dx);
+            if (abs(dy) > d->stat[H264O_DSTAT_MAX_MVD]) d->stat[H264O_DSTAT_MAX_MVD] = abs(dy);
             for (int y = p->y; y < p->y + p->h; y += 4)
                 for (int x = p->x; x < p->x + p->w; x += 4) {
                     const int bi = 4 * (y >> 2) + (x >> 2);
@@ -1462,6 +1490,7 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
         d->slice_count = 0;
         for (int i = 0; i < nmb; i++) d->mb[i].kind = DMB_NONE;
         d->max_mb_bits = 0; d->max_level_prefix = 0;
+        memset(d->stat, 0, sizeof(d->stat));
         d->cur_is_ref = nal_ref_idc != 0; d->cur_frame_num = frame_num; d->cur_is_idr = nal_type == 5;
         if (nal_type == 5) d->nrefs = 0;   /* 8.2.1: an IDR picture marks all reference pictures unused before it is decoded */
         d->cur_pps_id = (int)pps_id;
@@ -1530,6 +1559,7 @@ int h264o_dec_decode(h264o_dec *d, const uint8_t *data, size_t len)
     int got_pic = 0;
     size_t i = 0;
     d->err[0] = 0;
+    g_stat = d->stat;   /* (set by every call: never read after its decoder is gone) */
     uint8_t *rbsp = (uint8_t *)malloc(len + 8);
     if (!rbsp) return fail(d, "out of memory");
     while (i + 3 <= len) {

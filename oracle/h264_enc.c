@@ -89,6 +89,7 @@ static int se_len(int v)
 /* ------------------------------------------------------------ CAVLC 9.2 */
 /* hit counters of the writer (h264o_enc_hits): the encoder whose slice data is being written, NULL for the stand-alone helpers */
 static __thread h264o_hits *g_hits;
+static __thread int g_i16dc;   /* the block being written is an Intra16x16 DC block (h264o_hits.re_prefix16) */
 #define HIT(expr) do { if (g_hits) { g_hits->expr; } } while (0)
 static void cavlc_block_body(bitw *b, const int16_t *lv, int max_coeff, int nC);
 static void cavlc_block(bitw *b, const int16_t *lv, int max_coeff, int nC)
@@ -135,6 +136,8 @@ static void cavlc_block_body(bitw *b, const int16_t *lv, int max_coeff, int nC)
                 while (c >= (1 << (prefix - 3))) { c -= 1 << (prefix - 3); prefix++; }
                 /* prefix>15 handled per 9.2.2.1: levelCode += (1<<(prefix-3)) - 4096 */
                 if (prefix > 15) c = code - 30 - ((1 << (prefix - 3)) - 4096);
+                if (prefix == 15 && c == 4095) HIT(re_prefix15_max[suffix_len]++);
+                if (prefix >= 16) HIT(re_prefix16[g_i16dc ? 0 : nC == -1 ? 1 : 2]++);
                 bw_put(b, prefix + 1, 1);
                 bw_put(b, prefix - 3, (uint32_t)c);
             }
@@ -146,6 +149,8 @@ static void cavlc_block_body(bitw *b, const int16_t *lv, int max_coeff, int nC)
                 int c = code - (15 << suffix_len), prefix = 15;
                 while (c >= (1 << (prefix - 3))) { c -= 1 << (prefix - 3); prefix++; }
                 if (prefix > 15) c = code - (15 << suffix_len) - ((1 << (prefix - 3)) - 4096);
+                if (prefix == 15 && c == 4095) HIT(re_prefix15_max[suffix_len]++);
+                if (prefix >= 16) HIT(re_prefix16[g_i16dc ? 0 : nC == -1 ? 1 : 2]++);
                 bw_put(b, prefix + 1, 1);
                 bw_put(b, prefix - 3, (uint32_t)c);
             }
@@ -201,6 +206,9 @@ struct randsyn {
     int cur_p, cur_st;   /* the slice whose header is being written: a P slice; slice_type as written */
     int pps_id, init_qp, nref_default, dbf_ctrl;   /* of the picture parameter set every slice of the picture names */
     int no_t8x8;         /* High profile: that PPS says transform_8x8_mode_flag = 0 */
+    /* feature 131072 ("range ends") */
+    int re;              /* vectors are drawn as vectors up to the limits of A.3.1, also where `direct` writes the macroblock */
+    uint32_t rerng;      /* its generator */
 };
 /* one picture parameter set of a random stream (feature 65536 keeps up to four in play) */
 struct rs_pps { int id, init_qp, cqo[2], nref_default, dbf_ctrl, constrained, t8x8; };
@@ -245,6 +253,8 @@ struct h264o_enc {
     int nonref_in_gop, nonref_run;   /* non-reference pictures since the IDR picture; length of the run that is being written */
     int rs_alt, rs_prev_idr;         /* single-slice pictures alternate I / P; the previous picture was an IDR picture */
     int32_t rs_last[8];              /* h264o_enc_random_last */
+    int16_t *re_mv;        /* feature 131072: 32 int16 per macroblock, the vector of every 4x4 block (raster) as written */
+    int8_t *re_ref;        /* ... 4 per macroblock: ref_idx_l0 of the 8x8 quadrants, -1 = intra */
     struct randsyn *rs;   /* h264o_enc_random_picture (decoder-peer tests): syntax the encoder itself never uses; NULL while encoding */
     uint8_t *want_intra;   /* P pictures: 1 = the motion search handed the macroblock to the intra pass; 2 = one of the "nothing
                             * left to code" tests hit: the prediction is the reconstruction, no transform is run (the tests use
@@ -306,6 +316,8 @@ h264o_enc *h264o_enc_create(const h264o_config *cfg)
     e->mvq = (int16_t *)calloc((size_t)e->mbw * e->mbh, 8 * sizeof(int16_t));
     e->pshape = (uint8_t *)calloc((size_t)e->mbw * e->mbh, 1);
     e->mb_bitpos = (uint32_t *)calloc((size_t)e->mbw * e->mbh, sizeof(uint32_t));
+    e->re_mv = (int16_t *)calloc((size_t)e->mbw * e->mbh, 32 * sizeof(int16_t));
+    e->re_ref = (int8_t *)calloc((size_t)e->mbw * e->mbh, 4);
     for (int i = 0; i < e->mbw * e->mbh; i++) e->slice_of[i] = (int16_t)(i / e->mbw / e->slice_rows);
     e->rbsp_cap = ysz * 4 + 65536;
     e->rbsp = (uint8_t *)malloc(e->rbsp_cap);
@@ -324,6 +336,8 @@ void h264o_enc_destroy(h264o_enc *e)
     free(e->mvq);
     free(e->pshape);
     free(e->mb_bitpos);
+    free(e->re_mv);
+    free(e->re_ref);
     free(e->rbsp);
     free(e);
 }
@@ -1253,6 +1267,92 @@ static int nc_chroma(const h264o_enc *e, int mx, int my, int pl, int b)
 
 /* transform_8x8_mode_flag of the picture parameter set in use: 1 under High, but for a PPS of the generator that says 0 */
 static int t8x8_mode(const h264o_enc *e) { return e->cfg.profile_idc == 100 && !(e->rs && e->rs->no_t8x8); }
+
+/* ---- feature 131072 of the random-stream generator: vectors drawn as vectors.  Where the generator writes an inter macroblock
+ * from draws made at writing time (feature 32: partitions down to 4x4, a reference index per partition) the predictor has to be
+ * known on the 4x4 grid: re_mv / re_ref hold what was written, and this is the writer's own statement of 8.4.1.3 / 6.4.11.7
+ * (it shares nothing with oracle/h264_dec.c, which has to arrive at the same vectors from the mvd_l0 written here) ---- */
+enum { RE_MV_XLO = -8192, RE_MV_XHI = 8191, RE_MV_YLO = -2048, RE_MV_YHI = 2047 };   /* A.3.1 at level_idc >= 31, quarter samples */
+typedef struct { int avail, ref, x, y; } re_nb;
+/* the 4x4 block (bx, by) counted from the macroblock's own top-left block (-1 and 4 reach into the neighbours); `done`: the
+ * blocks of this macroblock whose vectors are already written */
+static re_nb re_block(const h264o_enc *e, int mx, int my, const uint8_t done[16], int bx, int by)
+{
+    re_nb n = {0, -1, 0, 0};
+    int nx = mx, ny = my;
+    if (by > 3) return n;
+    if (bx >= 0 && bx <= 3 && by >= 0) {
+        if (!done[4 * by + bx]) return n;   /* later in decoding order */
+    } else {
+        if (by >= 0 && bx > 3) return n;    /* the macroblock to the right */
+        nx = mx + (bx < 0 ? -1 : bx > 3 ? 1 : 0);
+        ny = my + (by < 0 ? -1 : 0);
+        if (!mb_avail(e, mx, my, nx, ny)) return n;
+        bx &= 3; by &= 3;
+    }
+    const size_t a = (size_t)ny * e->mbw + nx;
+    n.avail = 1;
+    n.ref = e->re_ref[4 * a + 2 * (by >> 1) + (bx >> 1)];
+    if (n.ref >= 0) { n.x = e->re_mv[32 * a + 2 * (4 * by + bx)]; n.y = e->re_mv[32 * a + 2 * (4 * by + bx) + 1]; }
+    return n;
+}
+/* predictor of the partition of bw x bh blocks at (bx, by); shape 1: a 16x8 partition, 2: an 8x16 partition (directional rules),
+ * 0: any other; skip (16x16 geometry, ref 0) receives the P_Skip vector of 8.4.1.1 */
+static mv_t re_predict(const h264o_enc *e, int mx, int my, const uint8_t done[16], int bx, int by, int bw, int ref, int shape, mv_t *skip)
+{
+    const re_nb A = re_block(e, mx, my, done, bx - 1, by);
+    re_nb B = re_block(e, mx, my, done, bx, by - 1), C = re_block(e, mx, my, done, bx + bw, by - 1);
+    mv_t p;
+    if (!C.avail) C = re_block(e, mx, my, done, bx - 1, by - 1);
+    if (skip && (!A.avail || !B.avail || (A.ref == 0 && !A.x && !A.y) || (B.ref == 0 && !B.x && !B.y))) { skip->x = skip->y = 0; skip = NULL; }
+    if (shape == 1 && by == 0 && B.ref == ref) { p.x = (int16_t)B.x; p.y = (int16_t)B.y; return p; }
+    if (shape == 1 && by != 0 && A.ref == ref) { p.x = (int16_t)A.x; p.y = (int16_t)A.y; return p; }
+    if (shape == 2 && bx == 0 && A.ref == ref) { p.x = (int16_t)A.x; p.y = (int16_t)A.y; return p; }
+    if (shape == 2 && bx != 0 && C.ref == ref) { p.x = (int16_t)C.x; p.y = (int16_t)C.y; return p; }
+    if (!B.avail && !C.avail && A.avail) { B = A; C = A; }
+    const int same = (A.ref == ref) + (B.ref == ref) + (C.ref == ref);
+    if (same == 1) {
+        const re_nb *s = A.ref == ref ? &A : B.ref == ref ? &B : &C;
+        p.x = (int16_t)s->x; p.y = (int16_t)s->y;
+    } else { p.x = (int16_t)med3(A.x, B.x, C.x); p.y = (int16_t)med3(A.y, B.y, C.y); }
+    if (skip) *skip = p;
+    return p;
+}
+static void re_store(h264o_enc *e, int mx, int my, uint8_t done[16], int bx, int by, int bw, int bh, int vx, int vy)
+{
+    int16_t *v = e->re_mv + ((size_t)my * e->mbw + mx) * 32;
+    for (int y = by; y < by + bh; y++)
+        for (int x = bx; x < bx + bw; x++) { v[2 * (4 * y + x)] = (int16_t)vx; v[2 * (4 * y + x) + 1] = (int16_t)vy; done[4 * y + x] = 1; }
+}
+/* one vector: mostly near its predictor, one in ten anywhere in the range A.3.1 allows, one in ten with one or both components
+ * exactly at a limit - every second time the limit on the other side of the predictor */
+static int re_limit(uint32_t *s, int pred, int lo, int hi) { return rs_below(s, 2) ? (pred < 0 ? hi : lo) : rs_below(s, 2) ? lo : hi; }
+static int re_near(uint32_t *s, int pred, int lo, int hi)
+{
+    return clip3(lo, hi, rs_below(s, 3) ? pred + rs_below(s, 9) - 4 : rs_below(s, 321) - 160);
+}
+static mv_t re_draw_vector(h264o_enc *e, uint32_t *s, mv_t pred)
+{
+    const int kind = rs_below(s, 10);
+    int vx, vy;
+    if (kind == 0) { vx = RE_MV_XLO + rs_below(s, RE_MV_XHI - RE_MV_XLO + 1); vy = RE_MV_YLO + rs_below(s, RE_MV_YHI - RE_MV_YLO + 1); }
+    else if (kind == 1) {
+        const int which = 1 + rs_below(s, 3);   /* x, y, both */
+        vx = (which & 1) ? re_limit(s, pred.x, RE_MV_XLO, RE_MV_XHI) : re_near(s, pred.x, RE_MV_XLO, RE_MV_XHI);
+        vy = (which & 2) ? re_limit(s, pred.y, RE_MV_YLO, RE_MV_YHI) : re_near(s, pred.y, RE_MV_YLO, RE_MV_YHI);
+    } else { vx = re_near(s, pred.x, RE_MV_XLO, RE_MV_XHI); vy = re_near(s, pred.y, RE_MV_YLO, RE_MV_YHI); }
+    if (vx == RE_MV_XLO) e->hits.re_mv_limit[0]++;
+    if (vx == RE_MV_XHI) e->hits.re_mv_limit[1]++;
+    if (vy == RE_MV_YLO) e->hits.re_mv_limit[2]++;
+    if (vy == RE_MV_YHI) e->hits.re_mv_limit[3]++;
+    for (int c = 0; c < 2; c++) {
+        const uint32_t d = (uint32_t)abs(c ? vy - pred.y : vx - pred.x);
+        if (d > e->hits.max_mvd) e->hits.max_mvd = d;
+        if (d > 8192) e->hits.re_mvd_over_8192++;
+    }
+    const mv_t v = {(int16_t)vx, (int16_t)vy};
+    return v;
+}
 static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
 {
     const h264o_mbinfo *mb = &e->mb[my * e->mbw + mx];
@@ -1261,6 +1361,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
     const int qpd = e->rs ? e->rs->qpd[my * e->mbw + mx] : 0;   /* mb_qp_delta: 0 for every macroblock the encoder codes */
     const uint64_t mb_at = b->bits;
     e->hits.mb_kind[mb->type]++;
+    if (e->rs && e->rs->re && e->rs->direct && H264O_MB_IS_INTRA(mb->type)) memset(e->re_ref + (size_t)(my * e->mbw + mx) * 4, -1, 4);
     if (mb->type == H264O_MB_IPCM) {   /* 7.3.5: mb_type I_PCM, alignment, 256 + 2 x 64 samples */
         int cw = e->cw, cs = cw / 2;
         bw_ue(b, (uint32_t)(p_slice ? 5 + 25 : 25));
@@ -1306,7 +1407,9 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
         bw_se(b, qpd); /* mb_qp_delta */
         if (b->bits - mb_at > 64) e->hits.long_header_slots++;
         g_hits = &e->hits;
+        g_i16dc = 1;
         cavlc_block(b, lv + H264O_LV_LUMA_DC, 16, nc_luma(e, mx, my, 0));
+        g_i16dc = 0;
     } else {
         /* 7.3.5.1 / 7.3.5.2: mb_type (P_L0_16x16, P_L0_L0_16x8, P_L0_L0_8x16, P_8x8 with four sub_mb_type P_L0_8x8), then
          * every partition's ref_idx_l0, then every partition's mvd_l0 */
@@ -1324,11 +1427,37 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
                     if (sub[k]) all8x8 = 0;
                     bw_ue(b, (uint32_t)sub[k]);
                 }
+            int refk[4] = {0, 0, 0, 0};
             for (int k = 0; k < nparts; k++) {
                 int r = rs_below(rng, e->avail_refs);
+                refk[k] = r;
                 if (e->avail_refs == 2) bw_put(b, 1, r ? 0 : 1);
                 else if (e->avail_refs > 2) bw_ue(b, (uint32_t)r);
             }
+            if (e->rs->re) {   /* feature 131072: every partition's vector is drawn, mvd_l0 is what is left of it */
+                uint8_t done[16] = {0};
+                int8_t *rq = e->re_ref + (size_t)(my * e->mbw + mx) * 4;
+                for (int q = 0; q < 4; q++) rq[q] = (int8_t)refk[shape == 0 ? 0 : shape == 1 ? q >> 1 : shape == 2 ? q & 1 : q];
+                for (int k = 0; k < nparts; k++) {
+                    const int nsub = shape == 3 ? (sub[k] == 0 ? 1 : sub[k] == 3 ? 4 : 2) : 1;
+                    for (int j = 0; j < nsub; j++) {
+                        int bx = 0, by = 0, bw4 = 4, bh4 = 4;
+                        if (shape == 1) { by = 2 * k; bh4 = 2; }
+                        else if (shape == 2) { bx = 2 * k; bw4 = 2; }
+                        else if (shape == 3) {
+                            bx = 2 * (k & 1); by = 2 * (k >> 1); bw4 = bh4 = 2;
+                            if (sub[k] == 1) { by += j; bh4 = 1; }
+                            else if (sub[k] == 2) { bx += j; bw4 = 1; }
+                            else if (sub[k] == 3) { bx += j & 1; by += j >> 1; bw4 = bh4 = 1; }
+                        }
+                        const mv_t p = re_predict(e, mx, my, done, bx, by, bw4, refk[k], shape < 3 ? shape : 0, NULL);
+                        const mv_t v = re_draw_vector(e, &e->rs->rerng, p);
+                        bw_se(b, v.x - p.x);
+                        bw_se(b, v.y - p.y);
+                        re_store(e, mx, my, done, bx, by, bw4, bh4, v.x, v.y);
+                    }
+                }
+            } else
             for (int k = 0; k < nparts; k++) {
                 int nsub = shape == 3 ? (sub[k] == 0 ? 1 : sub[k] == 3 ? 4 : 2) : 1;
                 for (int j = 0; j < nsub; j++)
@@ -1656,6 +1785,182 @@ static int rs_block(uint32_t *s, int16_t *lv, int first, int n, int density, int
     return rs_levels(s, lv, first, n, density, mag);
 }
 
+/* ---- feature 131072: QPs and levels at the ends of their ranges ---- */
+static int re_draw_qp(uint32_t *s, int burst)
+{
+    static const uint8_t ends[7] = {0, 1, 2, 3, 49, 50, 51};
+    if (burst) return rs_below(s, 2);
+    return rs_below(s, 2) ? ends[rs_below(s, 7)] : rs_below(s, 52);
+}
+/* magnitude a scaled by 8.5.12.1 (4x4 residual blocks) / 8.5.13 (8x8) at class `cls` of the position */
+static int64_t re_scaled4(int64_t a, int qp, int cls)
+{
+    const int64_t ls = 16 * o_dequant_v[qp % 6][cls];
+    return qp >= 24 ? (a * ls) << (qp / 6 - 4) : (a * ls + (1 << (3 - qp / 6))) >> (4 - qp / 6);
+}
+static int64_t re_scaled8(int64_t a, int qp, int cls)
+{
+    const int64_t ls = 16 * o_dequant8_v[qp % 6][cls];
+    return qp >= 36 ? (a * ls) << (qp / 6 - 6) : (a * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+}
+/* Bounds on every intermediate of 8.5.10 - 8.5.13, from magnitudes alone.  Each stage of the 4x4 inverse transform adds its
+ * inputs with weights of at most 1, so the sum of the magnitudes of the scaled coefficients of a block bounds whatever it
+ * computes; a DC that comes from a DC transform is bounded the same way by the scaled sum of the magnitudes of the DC levels.
+ * A stage of the 8x8 transform weights an input of odd index by up to 1.5 (a1 = -in3 + in5 - in7 - (in7 >> 1) ...). */
+static int64_t re_bound4(const int16_t *lv, int first, int qp, int64_t dc)   /* 16 levels in zig-zag order; index 0 skipped when first = 1 */
+{
+    int64_t sum = dc;
+    for (int i = first; i < 16; i++) sum += re_scaled4(abs(lv[i]), qp, o_pos_class(o_zigzag4x4[i]));
+    return sum;
+}
+static int64_t re_bound8(const int16_t *lv4, int qp)   /* the four interleaved 16-level lists of one 8x8 block */
+{
+    int64_t sum = 0;
+    for (int k = 0; k < 4; k++)
+        for (int i = 0; i < 16; i++) {
+            if (!lv4[16 * k + i]) continue;
+            const int pos = o_zigzag8x8[4 * i + k], r = pos >> 3, c = pos & 7;
+            sum += re_scaled8(abs(lv4[16 * k + i]), qp, o_pos_class8(pos)) * ((r & 1) ? 3 : 2) * ((c & 1) ? 3 : 2);
+        }
+    return (sum + 3) / 4;
+}
+static int64_t re_dc_luma(const int16_t *dc, int qp)   /* 8.5.10 on the sum of the magnitudes: bounds f and dcY */
+{
+    int64_t f = 0;
+    for (int i = 0; i < 16; i++) f += abs(dc[i]);
+    const int64_t ls = 16 * o_dequant_v[qp % 6][0];
+    const int64_t d = qp >= 36 ? (f * ls) << (qp / 6 - 6) : (f * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+    return d > f ? d : f;
+}
+static int64_t re_dc_chroma(const int16_t *dc, int qpc)   /* 8.5.11 */
+{
+    int64_t f = 0;
+    for (int i = 0; i < 4; i++) f += abs(dc[i]);
+    const int64_t d = ((f * 16 * o_dequant_v[qpc % 6][0]) << (qpc / 6)) >> 5;
+    return d > f ? d : f;
+}
+enum { RE_BOUND = 32000 };   /* 2^15 less room for the roundings of the shifts */
+/* the greatest bound over the blocks of macroblock `mb` at QP_Y qp; t8: its luma is (or, for a P_8x8 macroblock whose
+ * sub-macroblock types are drawn later, may be) transformed 8x8; t4: ... 4x4.  *worst: the level list and the index range the
+ * greatest bound was met in */
+static int64_t re_mb_bound(const h264o_mbinfo *mb, const int16_t *lv, int qp, const int qpc[2], int t4, int t8, const int16_t **worst, int *wfirst, int *wn)
+{
+    int64_t most = 0, v;
+    const int cbpl = mb->cbp & 15, cbpc = mb->cbp >> 4;
+#define RE_TAKE(val, list, f, n) do { v = (val); if (v > most) { most = v; *worst = (list); *wfirst = (f); *wn = (n); } } while (0)
+    if (mb->type == H264O_MB_I16) {
+        const int64_t dc = re_dc_luma(lv + H264O_LV_LUMA_DC, qp);
+        RE_TAKE(dc, lv + H264O_LV_LUMA_DC, 0, 16);
+        if (cbpl)
+            for (int b = 0; b < 16; b++) {   /* (a block without AC levels of its own passes the bound through its DC: that list is named then) */
+                const int16_t *ac = lv + H264O_LV_LUMA + 16 * b;
+                const int64_t own = re_bound4(ac, 1, qp, 0);
+                RE_TAKE(own + dc, own ? ac : lv + H264O_LV_LUMA_DC, own ? 1 : 0, 16);
+            }
+    } else {
+        for (int b8 = 0; b8 < 4; b8++) {
+            if (!(cbpl & (1 << b8))) continue;
+            if (t4) for (int k = 0; k < 4; k++) RE_TAKE(re_bound4(lv + H264O_LV_LUMA + 16 * (4 * b8 + k), 0, qp, 0), lv + H264O_LV_LUMA + 16 * (4 * b8 + k), 0, 16);
+            if (t8) RE_TAKE(re_bound8(lv + H264O_LV_LUMA + 64 * b8, qp), lv + H264O_LV_LUMA + 64 * b8, 0, 64);
+        }
+    }
+    if (cbpc)
+        for (int pl = 0; pl < 2; pl++) {
+            const int64_t dc = re_dc_chroma(lv + H264O_LV_CHROMA_DC + 4 * pl, qpc[pl]);
+            RE_TAKE(dc, lv + H264O_LV_CHROMA_DC + 4 * pl, 0, 4);
+            if (cbpc == 2)
+                for (int k = 0; k < 4; k++) {
+                    const int16_t *ac = lv + H264O_LV_CHROMA_AC + 16 * (4 * pl + k);
+                    const int64_t own = re_bound4(ac, 1, qpc[pl], 0);
+                    RE_TAKE(own + dc, own ? ac : lv + H264O_LV_CHROMA_DC + 4 * pl, own ? 1 : 0, own ? 16 : 4);
+                }
+        }
+#undef RE_TAKE
+    return most;
+}
+/* one large level into the list lv[first .. n - 1] of a block.  kind 0: the largest magnitude level_prefix 15 codes at
+ * suffixLength sl, behind sl levels that walk suffixLength there (the block holds nothing else); 1: exactly +-127 / 128 / 129
+ * at some position, the rest of the block stays; 2: a level of level_prefix 16 alone in its block */
+static void re_place(uint32_t *s, int16_t *lv, int first, int n, int kind)
+{
+    static const int16_t ramp[6] = {2, 4, 7, 13, 25, 49};
+    if (kind == 1) {
+        const int a = 127 + rs_below(s, 3);
+        lv[first + rs_below(s, n - first)] = (int16_t)(rs_below(s, 2) ? -a : a);
+        return;
+    }
+    for (int i = first; i < n; i++) lv[i] = 0;
+    if (kind == 2) {
+        const int a = 2065 + rs_below(s, 4096);   /* coded first in its block, at suffixLength 0: 2065 .. 6160 is what level_prefix 16 holds */
+        lv[first + rs_below(s, n - first)] = (int16_t)(rs_below(s, 2) ? -a : a);
+        return;
+    }
+    int sl = rs_below(s, 7);
+    if (sl > n - first - 1) sl = n - first - 1;
+    const int at = first + (rs_below(s, 2) ? 0 : rs_below(s, n - first - sl));   /* (the first position scales least) */
+    lv[at] = (int16_t)(sl == 0 ? -2064 : -(2048 + (15 << (sl - 1))));
+    for (int i = 0; i < sl; i++) lv[at + sl - i] = (int16_t)(rs_below(s, 2) ? -ramp[i] : ramp[i]);
+}
+/* the large levels of one macroblock (its QP_Y is final), then the bound: while a block passes it, its largest level goes */
+static void re_levels(h264o_enc *e, uint32_t *s, h264o_mbinfo *mb, int16_t *lv, int qp, const int cqo[2], int burst, int direct)
+{
+    if (burst == 2) mb->cbp = 0x2F;   /* every block coded (mb_qp_delta, where none was drawn for the macroblock, is 0) */
+    const int cbpl = mb->cbp & 15, cbpc = mb->cbp >> 4, i16 = mb->type == H264O_MB_I16, high = e->cfg.profile_idc == 100;
+    const int inter = !H264O_MB_IS_INTRA(mb->type);
+    const int t8 = inter && mb->i16_mode && cbpl, t4 = !t8 || (direct && mb->type == H264O_MB_P8X8);
+    int qpc[2];
+    for (int pl = 0; pl < 2; pl++) qpc[pl] = o_chroma_qp[clip3(0, 51, qp + cqo[pl])];
+    if (cbpc) {
+        if (qp + cqo[0] < 0 || qp + cqo[1] < 0) e->hits.re_qpi_below_0++;
+        if (qp + cqo[0] > 51 || qp + cqo[1] > 51) e->hits.re_qpi_above_51++;
+    }
+    /* the lists the stream carries for this macroblock: (offset, first index, length) */
+    int list[32][3], nl = 0;
+    if (i16) { list[nl][0] = H264O_LV_LUMA_DC; list[nl][1] = 0; list[nl++][2] = 16; }
+    for (int b = 0; b < 16; b++)
+        if (cbpl & (1 << (b >> 2))) { list[nl][0] = H264O_LV_LUMA + 16 * b; list[nl][1] = i16; list[nl++][2] = 16; }
+    const int nluma = nl;
+    if (cbpc) for (int pl = 0; pl < 2; pl++) { list[nl][0] = H264O_LV_CHROMA_DC + 4 * pl; list[nl][1] = 0; list[nl++][2] = 4; }
+    if (cbpc == 2) for (int b = 0; b < 8; b++) { list[nl][0] = H264O_LV_CHROMA_AC + 16 * b; list[nl][1] = 1; list[nl++][2] = 16; }
+    const int16_t *worst = NULL;
+    int wfirst = 0, wn = 0;
+    if (burst) {   /* whole blocks of levels just beyond a signed byte */
+        for (int k = 0; k < nl; k++) {
+            if (list[k][2] == 4 || (i16 && k == 0) || (burst == 1 && rs_below(s, 3))) continue;
+            for (int i = list[k][1]; i < 16; i++) { const int a = 127 + rs_below(s, 4); lv[list[k][0] + i] = (int16_t)(rs_below(s, 2) ? -a : a); }
+        }
+    } else if (nl && qp <= 11 && rs_below(s, 2)) {
+        for (int attempt = 0; attempt < 6; attempt++) {
+            /* any list, or - they are few - a DC block: Intra16x16 DC is list 0, the two chroma DC lists follow the luma lists */
+            const int k = rs_below(s, 2) ? rs_below(s, nl) : nluma < nl && (!i16 || rs_below(s, 2)) ? nluma + rs_below(s, 2) : 0;
+            const int dc_blk = (i16 && k == 0) || list[k][2] == 4;
+            const int kind = high && dc_blk && rs_below(s, 2) ? 2 : rs_below(s, 2);
+            int16_t keep[16];
+            memcpy(keep, lv + list[k][0], sizeof(keep[0]) * (size_t)list[k][2]);
+            re_place(s, lv + list[k][0], list[k][1], list[k][2], kind);
+            if (re_mb_bound(mb, lv, qp, qpc, t4, t8, &worst, &wfirst, &wn) <= RE_BOUND) break;
+            memcpy(lv + list[k][0], keep, sizeof(keep[0]) * (size_t)list[k][2]);
+        }
+    }
+    while (re_mb_bound(mb, lv, qp, qpc, t4, t8, &worst, &wfirst, &wn) > RE_BOUND) {
+        int16_t *w = lv + (worst - lv);
+        int at = wfirst;
+        for (int i = wfirst; i < wn; i++) if (abs(w[i]) >= abs(w[at])) at = i;
+        w[at] = 0;
+        e->hits.re_dropped++;
+    }
+    for (int b = 0; b < 16; b++) {
+        int tc = 0;
+        if (cbpl & (1 << (b >> 2))) for (int i = i16; i < 16; i++) tc += lv[H264O_LV_LUMA + 16 * b + i] != 0;
+        mb->tc[b] = (uint8_t)tc;
+    }
+    for (int b = 0; b < 8; b++) {
+        int tc = 0;
+        if (cbpc == 2) for (int i = 1; i < 16; i++) tc += lv[H264O_LV_CHROMA_AC + 16 * b + i] != 0;
+        mb->tc[16 + b] = (uint8_t)tc;
+    }
+}
+
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
                                  int *is_idr, uint8_t *mbqp_out)
 {
@@ -1677,6 +1982,13 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
      * that says which parameter set, reference marking and slice types the picture has; the writers read it from rs. */
     uint32_t prng = (seed ^ 0x5bd1e995u) * 2246822519u + 0x3C6EF372u;
     rs_next(&prng);
+    /* feature 131072 ("range ends"), again with a generator of its own.  Pictures 5 and 9 of every twelve of a stream are the ones
+     * with many and with very many large levels (only where QPs are drawn at all) */
+    const int re = (features & 131072) != 0;
+    uint32_t rerng = (seed ^ 0x7F4A7C15u) * 2891336453u + 0x1B873593u;
+    rs_next(&rerng);
+    const int burst = re && (features & 1) ? (e->frames % 12 == 5 ? 1 : e->frames % 12 == 9 ? 2 : 0) : 0;
+    rs.re = re;
     rs.is_ref = 1;
     if (e->frames == 0) {   /* once per stream */
         e->rs_npps = 0; e->rs_pps_last = -1; e->rs_sps_id = 0; e->rs_crop_l = e->rs_crop_t = 0; e->nonref_run = 0; e->rs_alt = 0;
@@ -1811,6 +2123,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
     if (!rs.dbf_ctrl) { rs.idc = 0; rs.oa = rs.ob = 0; }   /* what a slice header without the filter fields means (7.4.3) */
     const int qlo = 4, qhi = 48;   /* QP_Y range drawn from: wide enough for every row of Tables 8-15 / 8-16 that filters */
     for (int i = 0; i < 256; i++) rs.slice_qp[i] = (features & 1) ? qlo + rs_below(&rng, qhi - qlo + 1) : e->cfg.qp;
+    if (re && (features & 1)) for (int i = 0; i < 256; i++) rs.slice_qp[i] = re_draw_qp(&rerng, burst);
     /* samples of the I_PCM macroblocks */
     for (int p = 0; p < 3; p++) {
         size_t n = (size_t)e->cw * e->ch / (p ? 4 : 1);
@@ -1930,6 +2243,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                     else if (r < 9) { vx = rs_below(&rng, 321) - 160; vy = rs_below(&rng, 321) - 160; }
                     else { vx = rs_below(&rng, 1601) - 800; vy = rs_below(&rng, 1601) - 800; }
                     vx = clip3(-2000, 2000, vx); vy = clip3(-2000, 2000, vy);
+                    if (re) { const mv_t v = re_draw_vector(e, &rerng, p); vx = v.x; vy = v.y; }
                     for (int qy = y0; qy < y0 + h; qy++)
                         for (int qx = x0; qx < x0 + w; qx++) { qv[2 * (2 * qy + qx)] = (int16_t)vx; qv[2 * (2 * qy + qx) + 1] = (int16_t)vy; }
                 }
@@ -1971,13 +2285,14 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             }
             if (carries_delta && (features & 1) && rs_below(&rng, 2)) {
                 int d = rs_below(&rng, 4) ? rs_below(&rng, 9) - 4 : rs_below(&rng, 52) - 26;
-                const int nq = clip3(qlo, qhi, qp + d);
+                const int nq = re ? re_draw_qp(&rerng, burst) : clip3(qlo, qhi, qp + d);
                 d = nq - qp;
                 if (d < -26) d += 52;
                 if (d > 25) d -= 52;
                 rs.qpd[mbi] = (int8_t)d;
                 qp = nq;
             }
+            if (re) re_levels(e, &rerng, mb, lv, qp, rs.cqo, burst, rs.direct);
             if (mbqp_out) mbqp_out[mbi] = (uint8_t)qp;
         }
     if ((features & 4096) && any_pcm && rs.dbf_ctrl) rs.idc = 1;   /* the encoder does not filter a picture that holds an I_PCM macroblock */
@@ -1986,6 +2301,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
     bitw b;
     e->rs = &rs;
     rs.rng = rng;
+    rs.rerng = rerng;
     if (idr) {
         memset(e->rbsp, 0, 256);
         b = (bitw){e->rbsp, e->rbsp_cap, 0};
@@ -2021,6 +2337,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
         else { a1 = a0 + e->slice_rows * e->mbw; if (a1 > nmb) a1 = nmb; }
         b = (bitw){e->rbsp, e->rbsp_cap, 0};
         rs.cur_slice_qp = rs.slice_qp[slice_no & 255];
+        if (re) e->hits.re_slice_qp[rs.cur_slice_qp]++;
         const int p_slice = !slice_is_i[slice_no & 255];
         rs.cur_p = p_slice;
         rs.cur_st = (shape == 0 || shape == 3 ? 5 : 0) + (p_slice ? 0 : 2);
@@ -2031,6 +2348,13 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 const h264o_mbinfo *mb = &e->mb[a];
                 e->mb_bitpos[a] = (uint32_t)b.bits;
                 if (p_slice) {
+                    if (mb->type == H264O_MB_PSKIP && rs.re && rs.direct) {   /* its vector is what later macroblocks are predicted from */
+                        uint8_t done[16] = {0};
+                        mv_t skip;
+                        re_predict(e, mx, my, done, 0, 0, 4, 0, 0, &skip);
+                        memset(e->re_ref + (size_t)a * 4, 0, 4);
+                        re_store(e, mx, my, done, 0, 0, 4, 4, skip.x, skip.y);
+                    }
                     if (mb->type == H264O_MB_PSKIP) { skip_run++; e->hits.mb_kind[H264O_MB_PSKIP]++; continue; }
                     hit_skip_run(e, skip_run, 0, mb);
                     bw_ue(&b, (uint32_t)skip_run);

@@ -143,6 +143,14 @@ typedef struct {
     uint32_t pps_id_used[4];            /* pictures by pic_parameter_set_id 0, 1, 7, 255 */
     uint32_t sps_id_used[3];            /* streams by seq_parameter_set_id 0, 5, 31 */
     uint32_t crop_lt_streams;           /* streams whose SPS crops on the left / top */
+    /* h264o_enc_random_picture with feature 131072 ("range ends") */
+    uint32_t re_slice_qp[52];           /* slices by SliceQP_Y (pic_init_qp_minus26 + slice_qp_delta as written) */
+    uint32_t re_prefix15_max[7];        /* levels of level_prefix 15 whose suffix is all ones, by suffixLength: the largest magnitude it codes */
+    uint32_t re_prefix16[3];            /* levels of level_prefix >= 16 in Intra16x16 DC blocks, in chroma DC blocks, anywhere else */
+    uint32_t re_mv_limit[4];            /* vectors written at -8192, at 8191 (horizontal), at -2048, at 2047 (vertical), quarter samples */
+    uint32_t re_mvd_over_8192;          /* mvd_l0 components of magnitude above 8192 */
+    uint32_t re_qpi_below_0, re_qpi_above_51;   /* macroblocks with chroma residual whose QP_Y + chroma_qp_index_offset (either) is < 0 / > 51 */
+    uint32_t re_dropped;                /* levels the generator took out again because a bound of 8.5 would not have held */
 } h264o_hits;
 const h264o_hits *h264o_enc_hits(const h264o_enc *e);
 void h264o_enc_hits_reset(h264o_enc *e);
@@ -179,7 +187,22 @@ const uint8_t *h264o_enc_p_decision(const h264o_enc *e);
  * with its own pic_init_qp, chroma offsets, num_ref_idx_l0_default_active, deblocking_filter_control_present_flag,
  * constrained_intra_pred_flag and (High) transform_8x8_mode_flag, all sent with the IDR picture, one sent again with new content
  * before some non-IDR pictures, one PPS per picture; and frame cropping on the left and top by 2 or 4 luma samples.
- * These three draw from a generator of their own.  2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
+ * 131072 "range ends": the ends of the QP, level and vector ranges.  With 1: slice and macroblock QPs from 0 .. 51, about half of
+ * them from {0, 1, 2, 3, 49, 50, 51} (mb_qp_delta in its wrapped form; pic_init_qp 26 and slice_qp_delta -26 .. 25 reach SliceQP_Y
+ * 0 and 51).  Vectors are drawn as vectors (with 32: for every partition down to 4x4 and every reference index, predicted by a
+ * statement of 8.4.1.3 on the 4x4 grid of the writer's own; mvd_l0 is whatever results): one partition in ten uniform over the
+ * range A.3.1 allows at the level_idc written (-8192 .. 8191 by -2048 .. 2047 quarter samples), one in ten exactly at a limit -
+ * every second time the limit opposite to the predictor, so |mvd_l0| passes 8192 -, never outside.  Levels: in macroblocks of
+ * QP_Y <= 11 some blocks carry one large level - the largest magnitude level_prefix 15 codes at suffixLength 0 .. 6 (2064, 2063,
+ * 2078, 2108, 2168, 2288, 2528, negative: the suffix is all ones; the levels in front of it walk suffixLength there), exactly
+ * +-127 / +-128 / +-129, and under High in Intra16x16 DC and chroma DC blocks a level of level_prefix 16 (2064 .. 6159 at
+ * suffixLength 0; never 17: a quantiser of 8-bit video makes no level above 6528).  Picture 5 of every 12 of a stream is all
+ * QP_Y 0 / 1 with one block in three full of +-127 .. +-130, picture 9 with every block of every macroblock (the lists of large levels of
+ * a decoder outgrow what they start with, then what they grew to).  Conformance (8.5.10 - 8.5.13): for every block the sum of
+ * the magnitudes of its scaled coefficients (DC from the DC transform of the magnitudes; 8x8: weighted 1.5 per odd row / column)
+ * bounds every intermediate; while it passes 32000 the largest level of the block is taken out again (h264o_hits.re_dropped).
+ * oracle/h264_dec.c measures the intermediates themselves (h264o_dec_stat).
+ * These four draw from generators of their own.  2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
  * macroblock (0 for I_PCM, the value the loop filter uses).  Side information: h264o_enc_mbinfo / _mvq / _mbaux / _levels. */
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
                                  int *is_idr, uint8_t *mbqp_out);
@@ -247,6 +270,15 @@ int h264o_dec_coded_height(const h264o_dec *d);
 const uint8_t *h264o_dec_plane(const h264o_dec *d, int plane); /* coded size, pitch = coded w */
 const char *h264o_dec_error(const h264o_dec *d);
 int h264o_dec_last_slice_type(const h264o_dec *d); /* 0 P, 2 I */
+/* statistics of the last decoded picture (like h264o_dec_max_level_prefix): the greatest magnitude met in scaling, in the inverse
+ * transforms and in the DC transforms (8.5.10 - 8.5.13 demand -2^15 .. 2^15 - 1; -2^15 counts as 2^15 - 1), the greatest |level|,
+ * the greatest |mvd_l0| component, the least and greatest vector components used for prediction (quarter samples; 0 when
+ * nothing was predicted), and per side the number of predicted partitions (P_Skip macroblocks included) all of whose luma
+ * reference samples lie outside the picture */
+enum { H264O_DSTAT_MAX_INTERMEDIATE = 0, H264O_DSTAT_MAX_LEVEL, H264O_DSTAT_MAX_MVD, H264O_DSTAT_MV_X_MIN, H264O_DSTAT_MV_X_MAX,
+       H264O_DSTAT_MV_Y_MIN, H264O_DSTAT_MV_Y_MAX, H264O_DSTAT_OUT_LEFT, H264O_DSTAT_OUT_RIGHT, H264O_DSTAT_OUT_TOP,
+       H264O_DSTAT_OUT_BOTTOM, H264O_DSTAT_COUNT };
+int h264o_dec_stat(const h264o_dec *d, int which);
 int h264o_dec_last_nal_type(const h264o_dec *d);
 
 #ifdef __cplusplus

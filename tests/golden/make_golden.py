@@ -75,6 +75,11 @@ RANDOM_CASES = [
     ("rand_96x80_nonref_slice_types", 96, 80, 66, 2, 3, 16384 | 32768 | 1 | 128, 8),
     ("rand_112x64_parameter_sets_high", 112, 64, 100, 3, 2, 65536 | 32768 | 1 | 4 | 32, 8),
     ("rand_96x80_picture_level_all", 96, 80, 100, 0, 3, 16384 | 32768 | 65536 | 63 | 128 | 256 | 1024, 8),
+    # range ends (131072): QPs 0 .. 51, the largest levels level_prefix 15 / 16 code, vectors at the limits of A.3.1; ten pictures,
+    # so that the stream's picture 5 (many large levels) and picture 9 (very many) are in
+    ("rand_96x80_range_ends_baseline", 96, 80, 66, 0, 3, 131072 | 255, 10),
+    ("rand_112x64_range_ends_high", 112, 64, 100, 2, 3, 131072 | 255, 10),
+    ("rand_48x48_range_ends_main_constrained", 48, 48, 77, 0, 2, 131072 | 255 | 1024, 10),
 ]
 
 

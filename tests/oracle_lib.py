@@ -34,7 +34,10 @@ class Hits(C.Structure):
                 # picture level (random_picture with RAND_NONREF / RAND_SLICE_TYPES / RAND_PARAMETER_SETS)
                 ("nonref_pics", C.c_uint32), ("nonref_run", C.c_uint32 * 4), ("nonref_before_idr", C.c_uint32), ("nonref_after_idr", C.c_uint32),
                 ("slice_shape", C.c_uint32 * 4), ("slice_type_form", C.c_uint32 * 2), ("pps_switches", C.c_uint32), ("pps_resent", C.c_uint32),
-                ("pics_no_dbf_ctrl", C.c_uint32), ("pps_id_used", C.c_uint32 * 4), ("sps_id_used", C.c_uint32 * 3), ("crop_lt_streams", C.c_uint32)]
+                ("pics_no_dbf_ctrl", C.c_uint32), ("pps_id_used", C.c_uint32 * 4), ("sps_id_used", C.c_uint32 * 3), ("crop_lt_streams", C.c_uint32),
+                # random_picture with RAND_RANGE_ENDS
+                ("re_slice_qp", C.c_uint32 * 52), ("re_prefix15_max", C.c_uint32 * 7), ("re_prefix16", C.c_uint32 * 3), ("re_mv_limit", C.c_uint32 * 4),
+                ("re_mvd_over_8192", C.c_uint32), ("re_qpi_below_0", C.c_uint32), ("re_qpi_above_51", C.c_uint32), ("re_dropped", C.c_uint32)]
     MAX_FIELDS = ("max_mvd", "max_skip_run")
 
     def arrays(self):
@@ -117,6 +120,7 @@ def lib():
         for n in ("h264o_dec_max_mb_bits", "h264o_dec_max_level_prefix"):
             getattr(L, n).argtypes = [vp]
         L.h264o_dec_ref_age.argtypes = [vp, C.c_int]
+        L.h264o_dec_stat.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_kind.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_qp.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_mv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -188,6 +192,8 @@ class OracleEncoder:
     RAND_DENSE, RAND_ENCODER_SHAPED, RAND_SATURATE_FIRST_SLICE = 2048, 4096, 8192
     # picture level: non-reference pictures; I and P slices in any non-IDR picture; several parameter sets, left / top cropping
     RAND_NONREF, RAND_SLICE_TYPES, RAND_PARAMETER_SETS = 16384, 32768, 65536
+    # the ends of the QP, level and vector ranges (oracle/h264_oracle.h says what is drawn; tests/range_ends.py holds the cases)
+    RAND_RANGE_ENDS = 131072
     SHAPE_ALL_I, SHAPE_I_THEN_P, SHAPE_P_THEN_I, SHAPE_ALL_P = 0, 1, 2, 3
 
     def random_picture(self, seed, force_idr=False, features=31):
@@ -371,6 +377,13 @@ class OracleDecoder:
     @property
     def max_level_prefix(self):
         return lib().h264o_dec_max_level_prefix(self.h)
+
+    STATS = ("max_intermediate", "max_level", "max_mvd", "mv_x_min", "mv_x_max", "mv_y_min", "mv_y_max",
+             "out_left", "out_right", "out_top", "out_bottom")
+
+    def stats(self):
+        """h264o_dec_stat of the last decoded picture, by name"""
+        return {n: lib().h264o_dec_stat(self.h, i) for i, n in enumerate(self.STATS)}
 
     def close(self):
         if self.h:
