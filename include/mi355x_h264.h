@@ -235,6 +235,39 @@ int64_t mi355x_h264_debug_read(mi355x_h264_encoder *enc, int what, void *dst, si
 int mi355x_h264_debug_code_syntax(mi355x_h264_encoder *enc, const void *mbinfo, const void *levels, const void *mvq,
                                   const void *mbaux, const uint8_t *src_i420, uint8_t **out, uint32_t *out_len, int *frame_type);
 
+/* Guard mode of the library's own device and pinned memory (test hook; media_amd/csrc/dev_mem.h).  Every block an encoder, a stream
+ * hub, a decoder or a decoder group allocates passes one place.  Off (the default): no launch, no copy and no allocation differs.
+ * On: every block of an owner created AFTERWARDS lies between two guard regions of guard_bytes each, filled with a fixed pattern,
+ * and - with poison - every block that is not zeroed by design starts filled with 0xCB instead of what the allocator left.  The
+ * byte counts the library reports (mi355x_h264_dec_group_last_step) stay the caller's bytes.  A store of a kernel that misses its
+ * buffer by less than guard_bytes lands in a guard and is found by the check; a read out of bounds, and a store that misses by
+ * more, are not seen.
+ *   mi355x_h264_debug_mem_guard: the process-wide switch.  guard_bytes: 0 (off) or a multiple of 4096 up to 1 MiB - anything else
+ *     is refused with MI355X_H264_E_ARG and nothing changes.  MI355X_H264_MEM_GUARD=<bytes> and MI355X_H264_MEM_POISON=1 in the
+ *     environment give the setting the library starts with.  _get reads the setting (to put it back).
+ *   mi355x_h264_debug_mem_check / mi355x_h264_stream_debug_mem_check (and the decoder's, mi355x_h264_dec.h): waits for the owner's
+ *     work in flight as its synchronous calls do, compares every guard region with the pattern, and the 256 zeroed bytes behind
+ *     every slot of the reconstruction ring with zero.  Returns the number of damaged regions; *regions = regions examined (two per
+ *     block, one per ring slot and plane); report: the line "examined blocks=<blocks> slack=<ring slack regions>", then one line per
+ *     damaged region, "<block> before|after first=<offset> last=<offset>
+ *     bytes=<damaged bytes>", offsets counted from the block's first byte (before: negative).  The stream form covers the hub's
+ *     own blocks and the shared engine's, and no other stream of the hub may be in a call meanwhile.  An owner created with the
+ *     switch off: MI355X_H264_E_ARG and an error text - "never guarded" is not "intact".
+ *   mi355x_h264_debug_mem_tally: every block is checked once more when it is freed (destroy, a staging buffer that grows, a
+ *     decoder's change of size); the damaged regions found there are counted process-wide: returns the count, reset != 0 clears
+ *     it.  With MI355X_H264_MEM_GUARD_LOG=<file> every damaged region found while freeing is also appended to the file as one
+ *     line of the report's form: a run of a whole suite under the environment variables is clean when the file stays absent.
+ *   mi355x_h264_debug_mem_poke: sets ONE byte of a guard region from the host (hipMemset, or a store for pinned memory: no kernel
+ *     runs), so that a test can see the check report it.  block: the name of a block (the member it was allocated for, as the
+ *     source spells it: "d_slotcode", "S.d_bitbuf", "d_plane_base[0]"; the first of that name) or "#N", block N in allocation
+ *     order ("#0" the first, "#-1" the last).  offset: from the block's first byte, inside a guard region - any other is refused
+ *     with MI355X_H264_E_ARG.  value 0..255, or -1: the pattern's byte is put back. */
+int mi355x_h264_debug_mem_guard(int64_t guard_bytes, int poison);
+int mi355x_h264_debug_mem_guard_get(int64_t *guard_bytes, int *poison);
+int64_t mi355x_h264_debug_mem_tally(int reset);
+int mi355x_h264_debug_mem_check(mi355x_h264_encoder *enc, int *regions, char *report, size_t cap);
+int mi355x_h264_debug_mem_poke(mi355x_h264_encoder *enc, const char *block, int64_t offset, int value);
+
 /* ---- streams (ABI 3): many encoders of one geometry, one picture per call each, sharing one engine ----
  * The reference's operating mode is one VideoEncoder object per cloud-phone stream, each driven by its own thread with one
  * EncodeOneFrame per tick (/root/reference/video_codec/VideoEncoderOpenH264.cpp:304-352).  A stream is such an encoder whose
@@ -300,6 +333,8 @@ int mi355x_h264_stream_coded_height(const mi355x_h264_stream *s);
  * stream, into memory every engine owns anyway).  Off (the default): no launch, no copy and no allocation differs. */
 int64_t mi355x_h264_stream_debug_read(mi355x_h264_stream *s, int what, void *dst, size_t cap);
 int mi355x_h264_stream_debug_keep_pre(mi355x_h264_stream *s, int on);
+/* mi355x_h264_debug_mem_check (above) for the blocks of the stream's hub and of the engine its streams share */
+int mi355x_h264_stream_debug_mem_check(mi355x_h264_stream *s, int *regions, char *report, size_t cap);
 /* Which lockstep step coded the stream's last picture: the step's serial number on the stream's engine (1, 2, ..; steps of
  * one engine are numbered in the order they were gathered), the number of pictures the step carried, this picture's position
  * among them (0 .. pictures - 1: the grid index the indirect kernels saw, not the batch item) and whether it was an IDR

@@ -146,6 +146,16 @@ int mi355x_h264_dec_timing(const mi355x_h264_decoder *dec, uint64_t *pictures, d
 /* mi355x_h264_dec_group_last_step of the group of one stream that the decoder is */
 int mi355x_h264_dec_last_step(const mi355x_h264_decoder *dec, int64_t *out, int n);
 
+/* Guard mode of the library's own memory (mi355x_h264.h, mi355x_h264_debug_mem_guard: the switch and the tally are process-wide and
+ * hold for decoders and groups created afterwards).  Off (the default): no launch, no copy and no allocation differs.  The check
+ * waits as mi355x_h264_dec_group_sync does (and for an armed step's copy), then compares the guards of the picture store's blocks
+ * and the group's own, and the ring's zeroed slack; return value, *regions, report and the poke's arguments as for the encoder.  A
+ * decoder's check is its group's.  Blocks that are dropped and made again (the lists of large levels, output staging, a decoder's
+ * change of coded size) are checked as they are freed: mi355x_h264_debug_mem_tally. */
+int mi355x_h264_dec_debug_mem_check(mi355x_h264_decoder *dec, int *regions, char *report, size_t cap);
+int mi355x_h264_dec_group_debug_mem_check(mi355x_h264_dec_group *g, int *regions, char *report, size_t cap);
+int mi355x_h264_dec_group_debug_mem_poke(mi355x_h264_dec_group *g, const char *block, int64_t offset, int value);
+
 /* the host parser alone (needs no GPU): parse one access unit and read back what it recovered */
 typedef struct mi355x_h264_parser mi355x_h264_parser;
 mi355x_h264_parser *mi355x_h264_parser_create(void);

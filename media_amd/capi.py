@@ -35,6 +35,9 @@ EXPORTS = [
     "mi355x_h264_stream_open_ex",
     "mi355x_h264_quality_enable", "mi355x_h264_quality_read", "mi355x_h264_quality_map",
     "mi355x_h264_stream_quality_enable", "mi355x_h264_stream_last_quality", "mi355x_h264_stream_quality_map",
+    "mi355x_h264_debug_mem_guard", "mi355x_h264_debug_mem_guard_get", "mi355x_h264_debug_mem_tally", "mi355x_h264_debug_mem_check",
+    "mi355x_h264_debug_mem_poke", "mi355x_h264_stream_debug_mem_check", "mi355x_h264_dec_debug_mem_check",
+    "mi355x_h264_dec_group_debug_mem_check", "mi355x_h264_dec_group_debug_mem_poke",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
@@ -145,6 +148,16 @@ def lib():
         L.mi355x_h264_stream_quality_map.argtypes = [vp, vp, C.c_size_t]
         L.mi355x_h264_stream_quality_map.restype = C.c_int64
         L.mi355x_h264_stats_enable.argtypes = [vp, C.c_int]
+        if hasattr(L, "mi355x_h264_debug_mem_guard"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no guard mode)
+            L.mi355x_h264_debug_mem_guard.argtypes = [C.c_int64, C.c_int]
+            L.mi355x_h264_debug_mem_guard_get.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+            L.mi355x_h264_debug_mem_tally.argtypes = [C.c_int]
+            L.mi355x_h264_debug_mem_tally.restype = C.c_int64
+            for name in ("mi355x_h264_debug_mem_check", "mi355x_h264_stream_debug_mem_check", "mi355x_h264_dec_debug_mem_check",
+                         "mi355x_h264_dec_group_debug_mem_check"):
+                getattr(L, name).argtypes = [vp, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+            for name in ("mi355x_h264_debug_mem_poke", "mi355x_h264_dec_group_debug_mem_poke"):
+                getattr(L, name).argtypes = [vp, C.c_char_p, C.c_int64, C.c_int]
         L.mi355x_h264_stats_read.argtypes = [vp, C.POINTER(Stats), C.c_int]
         _lib = L
     return _lib
@@ -152,6 +165,42 @@ def lib():
 
 class EncoderError(RuntimeError):
     rc = 0   # the MI355X_H264_E_* code, where a call returned one
+
+
+# ---- the guard mode of the library's own memory (include/mi355x_h264.h, mi355x_h264_debug_mem_guard) ----
+def mem_guard(guard_bytes, poison=False):
+    """the process-wide switch, for owners created afterwards; returns the setting it replaces, as (guard_bytes, poison)"""
+    was = mem_guard_get()
+    rc = lib().mi355x_h264_debug_mem_guard(int(guard_bytes), int(bool(poison)))
+    if rc != 0:
+        err = EncoderError("mi355x_h264_debug_mem_guard(%d) -> %d" % (guard_bytes, rc))
+        err.rc = rc
+        raise err
+    return was
+
+
+def mem_guard_get():
+    g, p = C.c_int64(), C.c_int()
+    lib().mi355x_h264_debug_mem_guard_get(C.byref(g), C.byref(p))
+    return g.value, bool(p.value)
+
+
+def mem_tally(reset=False):
+    """damaged guard regions found while blocks were freed, process-wide"""
+    return int(lib().mi355x_h264_debug_mem_tally(int(reset)))
+
+
+def _mem_check(fn, handle, last_error):
+    """(damaged regions, regions examined, report lines: "examined blocks=B slack=S", then one per damaged region) of one of the
+    four check calls; raises EncoderError (rc = E_ARG: the
+    owner was created without guards)"""
+    regions, buf = C.c_int(), C.create_string_buffer(1 << 16)
+    n = fn(handle, C.byref(regions), buf, len(buf))
+    if n < 0:
+        err = EncoderError("mem_check -> %d: %s" % (n, last_error()))
+        err.rc = n
+        raise err
+    return n, regions.value, [ln for ln in buf.value.decode().split("\n") if ln]
 
 
 def _planes(f, w, h, strides, nv12=False):
@@ -345,6 +394,14 @@ class Encoder:
             self._check(int(got))
         return m
 
+    def mem_check(self):
+        """(damaged regions, regions examined, report lines): mi355x_h264_debug_mem_check"""
+        return _mem_check(lib().mi355x_h264_debug_mem_check, self.h, self.last_error)
+
+    def mem_poke(self, block, offset, value):
+        """one byte of a guard region set from the host (value -1: put back); returns the call's code"""
+        return lib().mi355x_h264_debug_mem_poke(self.h, block.encode(), int(offset), int(value))
+
     def stats_enable(self, on=True):
         self._check(lib().mi355x_h264_stats_enable(self.h, int(on)))
 
@@ -478,6 +535,10 @@ class Stream:
         if got < 0:
             self._check(int(got))
         return m
+
+    def mem_check(self):
+        """(damaged regions, regions examined, report lines) of the hub's blocks and the shared engine's"""
+        return _mem_check(lib().mi355x_h264_stream_debug_mem_check, self.h, self.last_error)
 
     def last_step(self):
         """the lockstep step that coded this stream's last picture (mi355x_h264_stream_debug_last_step)"""

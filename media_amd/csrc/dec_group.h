@@ -133,13 +133,13 @@ int dg_out_prepare(mi355x_h264_dec_group* g)
     bool ok = true;
     for (int k = 0; k < 2 && ok; k++) {
         if (!o.done[k]) ok = hipEventCreateWithFlags(&o.done[k], hipEventDisableTiming) == hipSuccess;
-        if (ok && !o.h_tabx[k]) ok = g->mem.pinned(&o.h_tabx[k], S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
+        if (ok && !o.h_tabx[k]) ok = DM_PINNED(g->mem, o.h_tabx[k], S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
     }
-    if (ok && !o.d_tabx) ok = g->mem.dev(&o.d_tabx, S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
+    if (ok && !o.d_tabx) ok = DM_DEV(g->mem, o.d_tabx, S * (sizeof(DecPos) + sizeof(DecOutPos)), false) == hipSuccess;
     if (ok && need > o.set_cap) {
         for (int k = 0; k < 2; k++) { if (o.h_set[k]) g->mem.drop(o.h_set[k]); o.h_set[k] = nullptr; }
         o.set_cap = 0;
-        for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&o.h_set[k], need) == hipSuccess;
+        for (int k = 0; k < 2 && ok; k++) ok = DM_PINNED(g->mem, o.h_set[k], need) == hipSuccess;
         if (ok) o.set_cap = need;
     }
     ok = ok && out_reserve(g->mem, o.rd, need, 0) == hipSuccess;
@@ -154,14 +154,14 @@ int dg_create_geometry(mi355x_h264_dec_group* g, int mbw, int mbh)
     const size_t n = (size_t)mbw * mbh * g->nstreams;
     bool ok = pic_store_create(g->store, g->device, mbw, mbh, g->nstreams, 4) == hipSuccess;
     for (int a = 0; a < DG_ARRAYS && ok; a++) {
-        for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_arr[k][a], n * DG_BYTES[a]) == hipSuccess;
-        if (ok && a >= DG_LV8) ok = g->mem.dev(&g->d_arr[a], n * DG_BYTES[a]) == hipSuccess;
+        for (int k = 0; k < 2 && ok; k++) ok = DM_PINNED(g->mem, g->h_arr[k][a], n * DG_BYTES[a]) == hipSuccess;
+        if (ok && a >= DG_LV8) ok = DM_DEV(g->mem, g->d_arr[a], n * DG_BYTES[a], false) == hipSuccess;
     }
-    for (int k = 0; k < 2 && ok; k++) ok = g->mem.pinned(&g->h_tab[k], (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
-    ok = ok && g->mem.dev(&g->d_tab, (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
+    for (int k = 0; k < 2 && ok; k++) ok = DM_PINNED(g->mem, g->h_tab[k], (size_t)g->nstreams * sizeof(DecPos)) == hipSuccess;
+    ok = ok && DM_DEV(g->mem, g->d_tab, (size_t)g->nstreams * sizeof(DecPos), false) == hipSuccess;
     // the lists of large levels at their smallest size, so that the steps of an ordinary stream allocate nothing (dg_step grows them)
-    for (int k = 0; k < 2 && ok; k++) if ((ok = g->mem.pinned(&g->h_big[k], 1024 * sizeof(DecBigLevel)) == hipSuccess)) g->h_big_cap[k] = 1024;
-    if (ok && (ok = g->mem.dev(&g->d_big, 1024 * sizeof(DecBigLevel)) == hipSuccess)) g->d_big_cap = 1024;
+    for (int k = 0; k < 2 && ok; k++) if ((ok = DM_PINNED(g->mem, g->h_big[k], 1024 * sizeof(DecBigLevel)) == hipSuccess)) g->h_big_cap[k] = 1024;
+    if (ok && (ok = DM_DEV(g->mem, g->d_big, 1024 * sizeof(DecBigLevel), false) == hipSuccess)) g->d_big_cap = 1024;
     if (!ok) {
         dg_free_geometry(g);
         return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the arrays of %d streams of %dx%d macroblocks (%s)", g->nstreams, mbw, mbh, t_failed_call);
@@ -370,7 +370,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             g->mem.drop(g->h_big[k]);
             g->h_big[k] = nullptr; g->h_big_cap[k] = 0;
             const size_t cap = nbig * 2 + 1024;
-            HIPCHK(g->err, g->mem.pinned(&g->h_big[k], cap * sizeof(DecBigLevel)));
+            HIPCHK(g->err, DM_PINNED(g->mem, g->h_big[k], cap * sizeof(DecBigLevel)));
             g->h_big_cap[k] = cap;
         }
         if (nbig > g->d_big_cap) {
@@ -378,7 +378,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             g->mem.drop(g->d_big);
             g->d_big = nullptr; g->d_big_cap = 0;
             const size_t cap = nbig * 2 + 1024;
-            HIPCHK(g->err, g->mem.dev(&g->d_big, cap * sizeof(DecBigLevel)));
+            HIPCHK(g->err, DM_DEV(g->mem, g->d_big, cap * sizeof(DecBigLevel), false));
             g->d_big_cap = cap;
         }
         size_t at = 0;

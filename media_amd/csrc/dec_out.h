@@ -44,19 +44,19 @@ struct DecOutBuf {
 hipError_t out_reserve(DevMem& mem, DecOutBuf& b, size_t dev_bytes, size_t host_bytes)
 {
     if (!b.h_tab) {
-        HIPTRY(mem.pinned(&b.h_tab, 64 * sizeof(DecOutPos)));
+        HIPTRY(DM_PINNED(mem, b.h_tab, 64 * sizeof(DecOutPos)));
         HIPTRY(hipHostGetDevicePointer((void**)&b.d_tab, b.h_tab, 0));
     }
     if (dev_bytes > b.d_cap) {
         if (b.d_stage) mem.drop(b.d_stage);
         b.d_stage = nullptr; b.d_cap = 0;
-        HIPTRY(mem.dev(&b.d_stage, dev_bytes));
+        HIPTRY(DM_DEV(mem, b.d_stage, dev_bytes, false));
         b.d_cap = dev_bytes;
     }
     if (host_bytes > b.h_cap) {
         if (b.h_stage) mem.drop(b.h_stage);
         b.h_stage = nullptr; b.h_cap = 0;
-        HIPTRY(mem.pinned(&b.h_stage, host_bytes));
+        HIPTRY(DM_PINNED(mem, b.h_stage, host_bytes));
         b.h_cap = host_bytes;
     }
     return hipSuccess;

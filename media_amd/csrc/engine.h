@@ -585,8 +585,8 @@ hipError_t quality_alloc(mi355x_h264_encoder* e)
     const size_t Gn = (size_t)e->G, part = Gn * e->mbh * SSE_SEGS * 3 * sizeof(unsigned long long), map = Gn * e->nmb * sizeof(uint32_t);
     for (int si = 0; si < e->nslots; si++) {
         Slot& S = e->slots[si];
-        HIPTRY(e->mem.pinned(&S.h_qpart, part));
-        HIPTRY(e->mem.pinned(&S.h_qmap, map));
+        HIPTRY(DM_PINNED(e->mem, S.h_qpart, part));
+        HIPTRY(DM_PINNED(e->mem, S.h_qmap, map));
         memset(S.h_qpart, 0, part);
         memset(S.h_qmap, 0, map);   // (a band instance's kernel stores its own rows only: the others stay 0)
     }
@@ -637,6 +637,7 @@ void destroy_engine(mi355x_h264_encoder* e)
 hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
 {
     DevMem& M = e->mem;
+    M.configure();   // the guard mode of dev_mem.h, as the process-wide switch stands now
     HIPTRY(pic_store_create(*e, e->device, e->mbw, e->mbh, e->G, e->nbuf));
     HIPTRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     // Entropy coding normally runs on a stream of its own beside the loop filter (shorter picture latency).  A process that
@@ -653,24 +654,25 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
     }
     const size_t ysz = (size_t)e->cw * e->ch;
     const size_t Gn = (size_t)e->G, nmb = Gn * e->nmb;   // (nmb: macroblocks of all batch items)
-    for (int p = 0; p < 3; p++) HIPTRY(M.dev(&e->d_pre[p], (p ? e->st_ring_c : e->st_ring_y) * Gn));
+    static const char* const pre_name[3] = {"d_pre[0]", "d_pre[1]", "d_pre[2]"};
+    for (int p = 0; p < 3; p++) HIPTRY(M.dev(&e->d_pre[p], (p ? e->st_ring_c : e->st_ring_y) * Gn, false, pre_name[p]));
     {
         std::vector<QpEntry> qt(52);
         for (int q = 0; q < 52; q++) fill_qp(qt[q].qy, qt[q].qc, qt[q].lambda, qt[q].sad_nz, q);
-        HIPTRY(M.dev(&e->d_qtab, 52 * sizeof(QpEntry)));
+        HIPTRY(DM_DEV(M, e->d_qtab, 52 * sizeof(QpEntry), false));
         HIPTRY(hipMemcpy(e->d_qtab, qt.data(), 52 * sizeof(QpEntry), hipMemcpyHostToDevice));
     }
-    HIPTRY(M.dev(&e->d_mvd, nmb * 8 * sizeof(int16_t)));
-    HIPTRY(M.dev(&e->d_me_total, nmb * sizeof(uint32_t)));
-    HIPTRY(M.dev(&e->d_pmv, nmb * sizeof(int)));
-    HIPTRY(M.dev(&e->d_slotbits, nmb * 32 * sizeof(uint16_t)));
-    HIPTRY(M.dev(&e->d_slotcode, nmb * 32 * sizeof(unsigned long long)));
-    HIPTRY(M.dev(&e->d_mbbits, nmb * sizeof(uint32_t)));
-    HIPTRY(M.dev(&e->d_prevcoded, Gn * (e->nmb + 1) * sizeof(int32_t)));
-    HIPTRY(M.dev(&e->d_me_cost, nmb * sizeof(uint16_t), true));
+    HIPTRY(DM_DEV(M, e->d_mvd, nmb * 8 * sizeof(int16_t), false));
+    HIPTRY(DM_DEV(M, e->d_me_total, nmb * sizeof(uint32_t), false));
+    HIPTRY(DM_DEV(M, e->d_pmv, nmb * sizeof(int), false));
+    HIPTRY(DM_DEV(M, e->d_slotbits, nmb * 32 * sizeof(uint16_t), false));
+    HIPTRY(DM_DEV(M, e->d_slotcode, nmb * 32 * sizeof(unsigned long long), false));
+    HIPTRY(DM_DEV(M, e->d_mbbits, nmb * sizeof(uint32_t), false));
+    HIPTRY(DM_DEV(M, e->d_prevcoded, Gn * (e->nmb + 1) * sizeof(int32_t), false));
+    HIPTRY(DM_DEV(M, e->d_me_cost, nmb * sizeof(uint16_t), true));
     e->frame_bytes = (size_t)e->cfg.width * e->cfg.height * 3 / 2;
-    HIPTRY(M.dev(&e->d_stage, e->frame_bytes + 256));
-    HIPTRY(M.pinned(&e->h_stage, e->frame_bytes + 256));
+    HIPTRY(DM_DEV(M, e->d_stage, e->frame_bytes + 256, false));
+    HIPTRY(DM_PINNED(M, e->h_stage, e->frame_bytes + 256));
     e->bitbuf_cap = ysz * 2 + (1 << 16);
     e->slice_cap = e->bitbuf_cap;
     if (e->nsl > 1) {   // every slice gets room for twice its luma bytes (CAVLC's worst case is about 1.6 times)
@@ -691,10 +693,10 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
     }
     for (int si = 0; si < e->nslots; si++) {
         Slot& S = e->slots[si];
-        HIPTRY(M.dev(&S.d_bitbuf, e->st_bitbuf_bytes * Gn, true));
-        HIPTRY(M.dev(&S.d_info, sizeof(SliceInfo) * Gn * e->nsl));
-        HIPTRY(M.pinned(&S.h_info, sizeof(SliceInfo) * Gn * e->nsl));
-        HIPTRY(M.pinned(&S.h_au, e->st_au * Gn));
+        HIPTRY(DM_DEV(M, S.d_bitbuf, e->st_bitbuf_bytes * Gn, true));
+        HIPTRY(DM_DEV(M, S.d_info, sizeof(SliceInfo) * Gn * e->nsl, false));
+        HIPTRY(DM_PINNED(M, S.h_info, sizeof(SliceInfo) * Gn * e->nsl));
+        HIPTRY(DM_PINNED(M, S.h_au, e->st_au * Gn));
         HIPTRY(sync_create(S.sync, e->stream, e->stream_ec, false));
     }
     HIPTRY(hipDeviceSynchronize());

@@ -95,16 +95,17 @@ void hub_free(Hub* h)
 hipError_t hub_alloc(Hub* h)
 {
     HIPTRY(hipSetDevice(h->cfg.device));
-    HIPTRY(h->mem.dev(&h->d_stage, h->st_stage * h->sched.cap));
-    HIPTRY(h->mem.pinned(&h->h_stage, h->st_stage * h->sched.cap));
+    h->mem.configure();
+    HIPTRY(DM_DEV(h->mem, h->d_stage, h->st_stage * h->sched.cap, false));
+    HIPTRY(DM_PINNED(h->mem, h->h_stage, h->st_stage * h->sched.cap));
     for (auto& cs : h->copy_st) HIPTRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     const char* one = getenv("MI355X_H264_ONE_STREAM");
     for (int ci = 0; ci <= h->sched.nctx_p; ci++) {
         HubCtx& c = h->ctx[ci];
         // (the IDR context has one stream: its row wavefront dominates, nothing to overlap)
         HIPTRY(sync_create(c.sync, nullptr, nullptr, (one && one[0] == '1') || ci == h->sched.nctx_p));
-        HIPTRY(h->mem.pinned(&c.h_tab, HubCtx::TAB_BYTES));
-        HIPTRY(h->mem.dev(&c.d_tab, HubCtx::TAB_BYTES));
+        HIPTRY(DM_PINNED(h->mem, c.h_tab, HubCtx::TAB_BYTES));
+        HIPTRY(DM_DEV(h->mem, c.d_tab, HubCtx::TAB_BYTES, false));
     }
     for (int i = 0; i < h->sched.cap; i++) HIPTRY(hipEventCreateWithFlags(&h->items[i].copied, hipEventDisableTiming));
     return hipSuccess;
@@ -230,7 +231,7 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
         // 1. a host picture goes to the stream's staging slot (RGBA: to its RGBA staging slot, which comes with the hub's first host
         // RGBA picture; the step's conversion launch writes the I420 slot): pinned copy, then the transfer on the item's copy
         // stream; it.copied says when it has arrived
-        const int nopen = h->sched.begin_upload([&] { return in.layout != PIC_RGBA || h->mem.pair(&h->d_rgba, &h->h_rgba, h->st_rgba * h->sched.cap); });
+        const int nopen = h->sched.begin_upload([&] { return in.layout != PIC_RGBA || DM_PAIR(h->mem, h->d_rgba, h->h_rgba, h->st_rgba * h->sched.cap); });
         if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the RGBA staging pictures");
         const size_t off = (size_t)item * (in.layout == PIC_RGBA ? h->st_rgba : h->st_stage);
         uint8_t* const hs = (in.layout == PIC_RGBA ? h->h_rgba : h->h_stage) + off, * const ds = (in.layout == PIC_RGBA ? h->d_rgba : h->d_stage) + off;

@@ -37,6 +37,7 @@ using namespace h264;
 #include "host_framing.h"
 #include "rgba_kernels.h"
 #include "k_dec_out.h"
+#include "dev_mem.h"
 #include "pic_store.h"
 #include "engine.h"
 #include "hub_sched.h"
@@ -110,7 +111,7 @@ int mi355x_h264_encode_rgba(mi355x_h264_encoder* e, const uint8_t* rgba, int str
     NEED(e, stride >= 4 * w, "stride smaller than 4 * width");
     HIPCHK(e->err, hipSetDevice(e->device));
     const size_t n = picture_bytes(PIC_RGBA, w, h);
-    if (!e->mem.pair(&e->d_rgba, &e->h_rgba, n + 256))   // staging for RGBA pictures: comes with the first one
+    if (!DM_PAIR(e->mem, e->d_rgba, e->h_rgba, n + 256))   // staging for RGBA pictures: comes with the first one
         return set_err(e->err, MI355X_H264_E_NOMEM, "no memory for the RGBA staging picture");
     HIPCHK(e->err, stage_picture(HostPicture{PIC_RGBA, {rgba, nullptr, nullptr}, {stride, 0, 0}}, w, h, e->h_rgba, e->d_rgba, e->stream, 1));
     return encode_rgba_from_device(e, e->d_rgba, (size_t)w * 4, out, out_len, frame_type);
@@ -266,7 +267,7 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, co
     NEED(e, e->cfg.band_count <= 1, "not for slice bands over several instances");
     HIPCHK(e->err, hipSetDevice(e->device));
     const size_t src_bytes = e->frame_bytes * (size_t)e->G;
-    if (!e->d_inject_src) HIPCHK(e->err, e->mem.dev(&e->d_inject_src, src_bytes + 256));
+    if (!e->d_inject_src) HIPCHK(e->err, DM_DEV(e->mem, e->d_inject_src, src_bytes + 256, false));
     HIPCHK(e->err, hipMemcpy(e->d_inject_src, src_i420, src_bytes, hipMemcpyHostToDevice));   // k_cavlc reads the I_PCM samples from the source
     const int slot = take_slot(e);
     const Injected inj{mbinfo, levels, mvq, mbaux};
@@ -525,6 +526,7 @@ int mi355x_h264_dec_group_create(int device, int streams, mi355x_h264_dec_group*
     mi355x_h264_dec_group* g = new (std::nothrow) mi355x_h264_dec_group();
     if (!g) return MI355X_H264_E_NOMEM;
     g->device = device; g->nstreams = streams;
+    g->mem.configure(); g->store.mem.configure();   // the guard mode of dev_mem.h, as the process-wide switch stands now
     g->st = new (std::nothrow) DecGroupStream[streams];
     if (!g->st) { delete g; return MI355X_H264_E_NOMEM; }
     if (hipSetDevice(device) != hipSuccess || hipEventCreateWithFlags(&g->up_done[0], hipEventDisableTiming) != hipSuccess ||
@@ -716,6 +718,144 @@ int mi355x_h264_dec_timing(const mi355x_h264_decoder* d, uint64_t* pictures, dou
     if (parse_ms) *parse_ms = d->parse_ms;
     if (gpu_ms) *gpu_ms = d->gpu_ms;
     return MI355X_H264_OK;
+}
+
+// ---- the guard mode of dev_mem.h: the process-wide switch, the tally of the free paths, a check and a poke per kind of owner ----
+namespace {
+
+// the lines of the report into the caller's buffer (cut where it ends, always terminated)
+void mem_report(const std::vector<MemDamage>& found, size_t blocks, int slack, char* report, size_t cap)
+{
+    if (!report || !cap) return;
+    report[0] = 0;
+    const int h = snprintf(report, cap, "examined blocks=%zu slack=%d\n", blocks, slack);
+    if (h < 0 || (size_t)h >= cap) { report[0] = 0; return; }
+    size_t at = (size_t)h;
+    for (const MemDamage& d : found) {
+        const int n = snprintf(report + at, cap - at, "%s\n", d.line().c_str());
+        if (n < 0 || (size_t)n >= cap - at) break;
+        at += (size_t)n;
+    }
+}
+// the check of an owner's lists (store: its ring slack as well); the owner's work has been waited for
+int mem_check_lists(std::initializer_list<const DevMem*> lists, std::initializer_list<const PicStore*> stores, int* regions, char* report, size_t cap)
+{
+    std::vector<MemDamage> found;
+    int looked = 0, slack = 0;
+    size_t blocks = 0;
+    for (const DevMem* m : lists) { if (m->check(found, &looked) < 0) return MI355X_H264_E_HIP; blocks += m->blocks.size(); }
+    for (const PicStore* s : stores) if (store_check_slack(*s, found, &slack) < 0) return MI355X_H264_E_HIP;
+    if (regions) *regions = looked + slack;
+    mem_report(found, blocks, slack, report, cap);   // (what a check finds is the caller's to assert: the log is the free paths')
+    return (int)found.size();
+}
+// block: a name (the first block of that name in the lists, in their order) or "#N" (block N of the lists laid end to end, from
+// the back when N is negative: "#0" the first, "#-1" the last)
+int mem_poke_lists(std::initializer_list<const DevMem*> lists, const char* block, int64_t offset, int value)
+{
+    if (!block) return MI355X_H264_E_ARG;
+    std::vector<std::pair<const DevMem*, const DevMem::Block*>> all;
+    for (const DevMem* m : lists) for (const DevMem::Block& b : m->blocks) all.push_back({m, &b});
+    const std::pair<const DevMem*, const DevMem::Block*>* hit = nullptr;
+    if (block[0] == '#') {
+        long n = atol(block + 1);
+        if (n < 0) n += (long)all.size();
+        if (n >= 0 && n < (long)all.size()) hit = &all[(size_t)n];
+    } else {
+        for (const auto& a : all) if (!strcmp(a.second->name, block)) { hit = &a; break; }
+    }
+    if (!hit) return MI355X_H264_E_ARG;
+    return hit->first->poke(*hit->second, offset, value) ? MI355X_H264_OK : MI355X_H264_E_ARG;
+}
+
+}  // namespace
+
+int mi355x_h264_debug_mem_guard(int64_t guard_bytes, int poison)
+{
+    return mem_guard_set(guard_bytes, poison != 0) ? MI355X_H264_OK : MI355X_H264_E_ARG;
+}
+
+int mi355x_h264_debug_mem_guard_get(int64_t* guard_bytes, int* poison)
+{
+    const MemGuardSetting s = mem_guard_setting();
+    if (guard_bytes) *guard_bytes = (int64_t)s.guard;
+    if (poison) *poison = s.poison;
+    return MI355X_H264_OK;
+}
+
+int64_t mi355x_h264_debug_mem_tally(int reset)
+{
+    std::atomic<unsigned long long>& t = mem_guard_global().tally;
+    return (int64_t)(reset ? t.exchange(0) : t.load());
+}
+
+int mi355x_h264_debug_mem_check(mi355x_h264_encoder* e, int* regions, char* report, size_t cap)
+{
+    if (!e) return MI355X_H264_E_ARG;
+    if (regions) *regions = 0;
+    if (report && cap) report[0] = 0;
+    NEED(e, e->mem.guard, "the encoder was created without guards (mi355x_h264_debug_mem_guard)");
+    HIPCHK(e->err, hipSetDevice(e->device));
+    HIPCHK(e->err, hipStreamSynchronize(e->stream));
+    if (e->stream_ec != e->stream) HIPCHK(e->err, hipStreamSynchronize(e->stream_ec));
+    const int n = mem_check_lists({&e->mem}, {e}, regions, report, cap);
+    return n < 0 ? set_err(e->err, n, "guard check: a copy failed") : n;
+}
+
+int mi355x_h264_debug_mem_poke(mi355x_h264_encoder* e, const char* block, int64_t offset, int value)
+{
+    if (!e) return MI355X_H264_E_ARG;
+    NEED(e, e->mem.guard, "the encoder was created without guards (mi355x_h264_debug_mem_guard)");
+    HIPCHK(e->err, hipSetDevice(e->device));
+    const int rc = mem_poke_lists({&e->mem}, block, offset, value);
+    return rc ? set_err(e->err, rc, "no such block, or the offset is outside its guard regions") : rc;
+}
+
+// the hub's own blocks and the shared engine's; the steps of every stream of the hub are waited for (no stream of it may be in a
+// call of its own meanwhile: the check is a test hook)
+int mi355x_h264_stream_debug_mem_check(mi355x_h264_stream* s, int* regions, char* report, size_t cap)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    if (regions) *regions = 0;
+    if (report && cap) report[0] = 0;
+    Hub* h = s->hub;
+    char (&err)[256] = h->items[s->item].err;
+    if (!h->mem.guard || !h->e->mem.guard) return set_err(err, MI355X_H264_E_ARG, "the stream's hub was created without guards (mi355x_h264_debug_mem_guard)");
+    std::lock_guard<std::mutex> lk(h->launch_mu);
+    HIPCHK(err, hipSetDevice(h->cfg.device));
+    HIPCHK(err, hipDeviceSynchronize());
+    const int n = mem_check_lists({&h->mem, &h->e->mem}, {h->e}, regions, report, cap);
+    return n < 0 ? set_err(err, n, "guard check: a copy failed") : n;
+}
+
+int mi355x_h264_dec_group_debug_mem_check(mi355x_h264_dec_group* g, int* regions, char* report, size_t cap)
+{
+    if (!g) return MI355X_H264_E_ARG;
+    if (regions) *regions = 0;
+    if (report && cap) report[0] = 0;
+    if (!g->mem.guard) return set_err(g->err, MI355X_H264_E_ARG, "the group was created without guards (mi355x_h264_debug_mem_guard)");
+    HIPCHK(g->err, hipSetDevice(g->device));
+    if (const int wrc = dg_wait(g)) return wrc;
+    HIPCHK(g->err, hipStreamSynchronize(g->sync.st));   // (an armed step's copy)
+    const int n = mem_check_lists({&g->store.mem, &g->mem}, {&g->store}, regions, report, cap);
+    return n < 0 ? set_err(g->err, n, "guard check: a copy failed") : n;
+}
+
+int mi355x_h264_dec_group_debug_mem_poke(mi355x_h264_dec_group* g, const char* block, int64_t offset, int value)
+{
+    if (!g) return MI355X_H264_E_ARG;
+    if (!g->mem.guard) return set_err(g->err, MI355X_H264_E_ARG, "the group was created without guards (mi355x_h264_debug_mem_guard)");
+    HIPCHK(g->err, hipSetDevice(g->device));
+    const int rc = mem_poke_lists({&g->store.mem, &g->mem}, block, offset, value);
+    return rc ? set_err(g->err, rc, "no such block, or the offset is outside its guard regions") : rc;
+}
+
+int mi355x_h264_dec_debug_mem_check(mi355x_h264_decoder* d, int* regions, char* report, size_t cap)
+{
+    if (!d) return MI355X_H264_E_ARG;
+    const int rc = mi355x_h264_dec_group_debug_mem_check(d->g, regions, report, cap);
+    if (rc < 0) snprintf(d->err, sizeof(d->err), "%s", d->g->err);   // (E_ARG too: "created without guards" is the group's text)
+    return rc;
 }
 
 // ---- the host parser alone (no GPU): what it recovered from the last access unit, for the CPU tests ----

@@ -2,8 +2,8 @@
 // drives them.  It is the part of the device memory that the encoder engine (engine.h, which IS a store plus what coding a stream
 // takes) and the decoder groups (dec_group.h, which own a store and nothing of the encoder's) share: the reconstruction ring, the
 // per-macroblock arrays the kernels hand each other, the hand-off granules of the row wavefronts, the per-picture flags and the two
-// serial counters.  With it: the owner's list of allocations (DevMem), what a step in flight is launched on and waited for with
-// (StepSync), and the parameter blocks of the kernels as far as they come from a store alone.  A store owns no stream.  Part of the
+// serial counters.  With it: what a step in flight is launched on and waited for with (StepSync), the check of the ring's zeroed
+// slack for the guard mode of the owner's list of allocations (DevMem, dev_mem.h), and the parameter blocks of the kernels as far as they come from a store alone.  A store owns no stream.  Part of the
 // one translation unit mi355x_h264.hip, which includes the kernels before this file.
 #pragma once
 
@@ -12,61 +12,14 @@
         hipError_t _r = (call);                                                                              \
         if (_r != hipSuccess) return set_err((err), MI355X_H264_E_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
     } while (0)
-// for the set-up functions that hand the hipError_t on (their callers undo and translate): the call that failed, for the report
-namespace { thread_local const char* t_failed_call = ""; }
-#define HIPTRY(call)                                                      \
+// for the set-up functions that hand the hipError_t on (their callers undo and translate): t_failed_call (dev_mem.h) names the call
+#define HIPTRY(call)                                                     \
     do {                                                                  \
         hipError_t _r = (call);                                           \
         if (_r != hipSuccess) { t_failed_call = #call; return _r; }       \
     } while (0)
 
 namespace {
-
-// Every device or pinned allocation of an owner (store, engine, hub, decoder group) is registered where it is made and freed in one
-// loop; dev_bytes / pinned_bytes: what the owner holds at the moment.
-struct DevMem {
-    struct Block { void* p; size_t bytes; bool pinned; };
-    std::vector<Block> blocks;
-    size_t dev_bytes = 0, pinned_bytes = 0;
-    template <class T> hipError_t dev(T** p, size_t bytes, bool zero = false)
-    {
-        HIPTRY(hipMalloc((void**)p, bytes));
-        blocks.push_back({*p, bytes, false});
-        dev_bytes += bytes;
-        if (zero) HIPTRY(hipMemset(*p, 0, bytes));
-        return hipSuccess;
-    }
-    template <class T> hipError_t pinned(T** p, size_t bytes)
-    {
-        HIPTRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
-        blocks.push_back({*p, bytes, true});
-        pinned_bytes += bytes;
-        return hipSuccess;
-    }
-    // both halves of a staging pair that comes with its first use: whichever is still missing
-    template <class T> bool pair(T** d, T** h, size_t bytes)
-    {
-        if (!*d && dev(d, bytes) != hipSuccess) *d = nullptr;
-        if (*d && !*h && pinned(h, bytes) != hipSuccess) *h = nullptr;
-        return *d && *h;
-    }
-    // one block back ahead of the others (a staging buffer that has to grow); nothing may be using it any more
-    void drop(void* p)
-    {
-        for (size_t i = 0; i < blocks.size(); i++)
-            if (blocks[i].p == p) {
-                if (blocks[i].pinned) (void)hipHostFree(p); else (void)hipFree(p);
-                (blocks[i].pinned ? pinned_bytes : dev_bytes) -= blocks[i].bytes;
-                blocks.erase(blocks.begin() + (long)i);
-                return;
-            }
-    }
-    void free_all()
-    {
-        for (const Block& b : blocks) { if (b.pinned) (void)hipHostFree(b.p); else (void)hipFree(b.p); }
-        blocks.clear(); dev_bytes = pinned_bytes = 0;
-    }
-};
 
 // What one step in flight needs to be launched and waited for: its stream pair (entropy coding forks to ec), the fork /
 // join events, the event behind its last command and the wavefront kernels' time-out flag (pinned).  An engine slot, a hub
@@ -159,23 +112,60 @@ hipError_t pic_store_create(PicStore& s, int device, int mbw, int mbh, int items
     const size_t Gn = (size_t)items, nmb = Gn * s.nmb;   // (nmb: macroblocks of all items)
     s.st_ring_y = ysz + 256; s.st_ring_c = ysz / 4 + 256;
     s.st_y = s.st_ring_y * nbuf; s.st_c = s.st_ring_c * nbuf;
+    static const char* const plane_name[3] = {"d_plane_base[0]", "d_plane_base[1]", "d_plane_base[2]"};
     for (int p = 0; p < 3; p++) {
-        HIPTRY(M.dev(&s.d_plane_base[p], (p ? s.st_c : s.st_y) * Gn, true));
+        HIPTRY(M.dev(&s.d_plane_base[p], (p ? s.st_c : s.st_y) * Gn, true, plane_name[p]));
         for (int b = 0; b < nbuf; b++) s.d_planes[b][p] = s.d_plane_base[p] + (size_t)b * (p ? s.st_ring_c : s.st_ring_y);
     }
-    HIPTRY(M.dev(&s.d_mb, nmb * sizeof(MbInfo), true));
-    HIPTRY(M.dev(&s.d_levels, nmb * LV_STRIDE * sizeof(int16_t)));
-    HIPTRY(M.dev(&s.d_mvq, nmb * 8 * sizeof(int16_t), true));
-    HIPTRY(M.dev(&s.d_aux, nmb * 16, true));
-    for (unsigned** flag : {&s.d_anybs, &s.d_anypcm, &s.d_anyintra}) HIPTRY(M.dev(flag, Gn * sizeof(unsigned), true));
+    HIPTRY(M.dev(&s.d_mb, nmb * sizeof(MbInfo), true, "d_mb"));
+    HIPTRY(M.dev(&s.d_levels, nmb * LV_STRIDE * sizeof(int16_t), false, "d_levels"));
+    HIPTRY(M.dev(&s.d_mvq, nmb * 8 * sizeof(int16_t), true, "d_mvq"));
+    HIPTRY(M.dev(&s.d_aux, nmb * 16, true, "d_aux"));
+    HIPTRY(M.dev(&s.d_anybs, Gn * sizeof(unsigned), true, "d_anybs"));
+    HIPTRY(M.dev(&s.d_anypcm, Gn * sizeof(unsigned), true, "d_anypcm"));
+    HIPTRY(M.dev(&s.d_anyintra, Gn * sizeof(unsigned), true, "d_anyintra"));
     s.st_handoff = (size_t)s.nmb * 24;
-    HIPTRY(M.dev(&s.d_handoff, Gn * s.st_handoff * sizeof(unsigned long long), true));
-    HIPTRY(M.dev(&s.d_bs, nmb * 32));
+    HIPTRY(M.dev(&s.d_handoff, Gn * s.st_handoff * sizeof(unsigned long long), true, "d_handoff"));
+    HIPTRY(M.dev(&s.d_bs, nmb * 32, false, "d_bs"));
     HIPTRY(hipDeviceSynchronize());
     return hipSuccess;
 }
-// nothing of the owner's may be in flight
-void pic_store_destroy(PicStore& s) { s.mem.free_all(); s = PicStore(); }
+// nothing of the owner's may be in flight.  The store's guard setting (dev_mem.h) stays: it is the owner's, taken at its creation
+void pic_store_destroy(PicStore& s)
+{
+    s.mem.free_all();
+    const size_t guard = s.mem.guard;
+    const bool poison = s.mem.poison;
+    s = PicStore();
+    s.mem.guard = guard; s.mem.poison = poison;
+}
+
+// The 256 bytes behind every ring slot of every item are zeroed at creation and no kernel stores there: inner guards that cost
+// nothing.  With the guard mode on, the check looks at them too: one region per plane, item and slot, reported under the name
+// "ring slack <plane>" with offsets from the plane's first byte.  Returns the damaged regions, -1 when a copy failed
+int store_check_slack(const PicStore& s, std::vector<MemDamage>& found, int* regions)
+{
+    if (!s.mem.guard || !s.made()) return 0;
+    static const char* const name[3] = {"ring slack d_plane_base[0]", "ring slack d_plane_base[1]", "ring slack d_plane_base[2]"};
+    const size_t before = found.size(), slots = (size_t)s.G * s.nbuf;
+    std::vector<uint8_t> tmp(slots * 256);
+    for (int p = 0; p < 3; p++) {
+        const size_t st = p ? s.st_ring_c : s.st_ring_y, used = st - 256;
+        if (hipMemcpy2D(tmp.data(), 256, s.d_plane_base[p] + used, st, 256, slots, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        for (size_t k = 0; k < slots; k++) {
+            MemDamage d{name[p], true, 0, 0, 0};
+            for (size_t i = 0; i < 256; i++)
+                if (tmp[k * 256 + i]) {
+                    const long long off = (long long)(k * st + used + i);
+                    if (!d.count) d.first = off;
+                    d.last = off; d.count++;
+                }
+            if (d.count) found.push_back(d);
+        }
+        if (regions) *regions += (int)slots;
+    }
+    return (int)(found.size() - before);
+}
 
 // ---- the parameter blocks of the kernels, as far as they come from the store alone (the engine's frame_params and submit_step and
 // the decoder groups' dg_step add what is theirs) ----

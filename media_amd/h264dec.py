@@ -3,7 +3,7 @@ a device), `DecoderGroup` (the next pictures of up to 64 streams of one coded si
 recovers from a stream with the side information of the encoder that wrote it)."""
 import ctypes as C
 import numpy as np
-from .capi import lib, EncoderError, MBINFO_DTYPE, LV_STRIDE
+from .capi import lib, EncoderError, MBINFO_DTYPE, LV_STRIDE, _mem_check
 
 E_STREAM = -7
 PIX_I420, PIX_NV12, PIX_NV21, PIX_RGBA = 0, 1, 2, 3   # output layouts (MI355X_H264_PIX_*)
@@ -157,6 +157,10 @@ class Decoder:
         if rc != 0:
             raise EncoderError("dec_sync -> %d: %s" % (rc, lib().mi355x_h264_dec_last_error(self.h).decode()))
 
+    def mem_check(self):
+        """(damaged regions, regions examined, report lines): mi355x_h264_dec_debug_mem_check (the guard mode of mi355x_h264.h)"""
+        return _mem_check(lib().mi355x_h264_dec_debug_mem_check, self.h, lambda: lib().mi355x_h264_dec_last_error(self.h).decode())
+
     def last_step(self):
         """DecoderGroup.last_step() of the group of one stream behind this decoder"""
         v = (C.c_int64 * len(DecoderGroup.STEP))()
@@ -210,6 +214,14 @@ class DecoderGroup:
         if r != 0:
             raise EncoderError("group decode -> %d: %s" % (r, self.error()))
         return [(rc[i], got[i]) for i in range(n)]
+
+    def mem_check(self):
+        """(damaged regions, regions examined, report lines): mi355x_h264_dec_group_debug_mem_check"""
+        return _mem_check(lib().mi355x_h264_dec_group_debug_mem_check, self.h, self.error)
+
+    def mem_poke(self, block, offset, value):
+        """one byte of a guard region set from the host (value -1: put back); returns the call's code"""
+        return lib().mi355x_h264_dec_group_debug_mem_poke(self.h, block.encode(), int(offset), int(value))
 
     def sync(self):
         rc = lib().mi355x_h264_dec_group_sync(self.h)
