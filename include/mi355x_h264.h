@@ -324,6 +324,32 @@ int mi355x_h264_stream_last_me_cost(const mi355x_h264_stream *s, uint32_t *cost)
 const char *mi355x_h264_stream_last_error(const mi355x_h264_stream *s);
 int mi355x_h264_stream_coded_width(const mi355x_h264_stream *s);
 int mi355x_h264_stream_coded_height(const mi355x_h264_stream *s);
+/* Scaled streams (tests/test_gpu_scale.py): pictures of src_width x src_height are resampled on the device to the coded size,
+ * cfg->width x cfg->height, by one launch per lockstep step in front of the first kernel that reads samples
+ * (k_scale_to_i420_step); from there on the picture takes the path of every other stream.  `flags` are those of
+ * mi355x_h264_stream_open_ex (MI355X_H264_STREAM_MULTIREF combines with scaling).  src == (cfg->width, cfg->height) gives exactly
+ * the stream mi355x_h264_stream_open_ex gives, sharing its engine; streams share an engine only with streams of the same source
+ * size.  Refused with MI355X_H264_E_ARG before the device is touched: an odd source size, one outside 16 .. 4096, one smaller than
+ * the coded size or more than 4 times it in either dimension, and everything mi355x_h264_stream_open_ex refuses.
+ * Every mi355x_h264_stream_encode* call of such a stream takes pictures of the SOURCE size (strides are checked against the source
+ * width; the device form takes one tight source picture, read where it lies during the call, nothing copied and nothing waited
+ * for; it may start on any byte - RGBA: on 8 - and is read at full speed from multiples of 16).  MI355X_H264_DBG_SRC returns the
+ * resampled staging picture, width * height * 3 / 2 bytes of I420 for every layout, and the quality report's `src` is that picture.
+ * The arithmetic (this library's own definition; tests/scale.py restates it in numpy).  Area (box) resampling of a plane of
+ * SW x SH samples to W x H, W <= SW <= 4 W and H <= SH <= 4 H:
+ *   - per dimension, result sample x covers [x * SW, (x + 1) * SW) on an axis where source sample i covers [i * W, (i + 1) * W);
+ *     the weight wx(x, i) is the integer length of the overlap.  The weights of one result sample sum to SW, and at most 5 source
+ *     samples are touched;
+ *   - out(x, y) = floor((N + (D >> 1)) / D) with N = sum_j sum_i wx(x, i) * wy(y, j) * src(j, i) and D = SW * SH: the exact
+ *     weighted mean rounded to nearest, halves up (an odd D has no ties).  Nothing is rounded between the horizontal and the
+ *     vertical sum.  N + (D >> 1) < 2^32 up to 4096 x 4096, and the division is exact (a multiplier the host computes per plane);
+ *   - I420: Y is resampled SW x SH -> W x H, U and V each SW/2 x SH/2 -> W/2 x H/2.  NV12: the same, the chroma samples taken from
+ *     the interleaved plane.  RGBA: R, G and B are each resampled as a plane (alpha is ignored), and the resampled picture goes
+ *     through the RGBA arithmetic stated at mi355x_h264_encode_rgba, unchanged.  2 : 1 in both dimensions is (a + b + c + d + 2) >> 2. */
+int mi355x_h264_stream_open_scaled(const mi355x_h264_config *cfg, uint32_t flags, int src_width, int src_height,
+                                   mi355x_h264_stream **out);
+int mi355x_h264_stream_source_width(const mi355x_h264_stream *s);    /* the size of the pictures the calls take: the coded   */
+int mi355x_h264_stream_source_height(const mi355x_h264_stream *s);   /* size for streams that do not scale                   */
 /* Test hooks.  mi355x_h264_stream_debug_read: what mi355x_h264_debug_read gives for an encoder (every MI355X_H264_DBG_* value), of the
  * stream's own batch item after the stream's last picture; returns bytes or < 0.  The stream's calls are synchronous and nothing
  * rewrites a stream's arrays before its next call, so other streams may go on encoding meanwhile.
@@ -376,7 +402,8 @@ int mi355x_h264_stats_read(mi355x_h264_encoder *enc, mi355x_h264_stats *out, int
  * Definition.  Each of the three planes is compared sample by sample, Y, Cb and Cr reported in the order Y, U, V: the
  * difference (src - rec) is squared and summed.
  *   src  the picture the encoder kernels read: for I420 and NV12 input the caller's samples, for RGBA input the I420 staging
- *        picture the conversion kernel (k_rgba_to_i420 / k_rgba_to_i420_step) wrote;
+ *        picture the conversion kernel (k_rgba_to_i420 / k_rgba_to_i420_step) wrote; for a scaled stream
+ *        (mi355x_h264_stream_open_scaled) the resampled I420 staging picture of the coded size, whatever the layout;
  *   rec  the reconstruction that becomes the next reference, after the loop filter; a picture that is not filtered
  *        (disable_deblock, or a picture with an I_PCM macroblock) is compared as it stands.
  * Only display samples count: luma x < width, y < height; chroma x < width / 2, y < height / 2.  The replicated columns and rows of

@@ -32,7 +32,7 @@ EXPORTS = [
     "mi355x_h264_stream_last_error", "mi355x_h264_stream_debug_read", "mi355x_h264_stream_hub_stats",
     "mi355x_h264_stream_encode_device", "mi355x_h264_stream_encode_nv12", "mi355x_h264_stream_encode_rgba",
     "mi355x_h264_debug_code_syntax", "mi355x_h264_stream_debug_keep_pre", "mi355x_h264_stream_debug_last_step",
-    "mi355x_h264_stream_open_ex",
+    "mi355x_h264_stream_open_ex", "mi355x_h264_stream_open_scaled", "mi355x_h264_stream_source_width", "mi355x_h264_stream_source_height",
     "mi355x_h264_quality_enable", "mi355x_h264_quality_read", "mi355x_h264_quality_map",
     "mi355x_h264_stream_quality_enable", "mi355x_h264_stream_last_quality", "mi355x_h264_stream_quality_map",
     "mi355x_h264_debug_mem_guard", "mi355x_h264_debug_mem_guard_get", "mi355x_h264_debug_mem_tally", "mi355x_h264_debug_mem_check",
@@ -119,6 +119,10 @@ def lib():
         L.mi355x_h264_debug_code_syntax.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_open.argtypes = [C.POINTER(Config), C.POINTER(vp)]
         L.mi355x_h264_stream_open_ex.argtypes = [C.POINTER(Config), C.c_uint32, C.POINTER(vp)]
+        if hasattr(L, "mi355x_h264_stream_open_scaled"):   # (an A/B library of an earlier build has no scaled streams)
+            L.mi355x_h264_stream_open_scaled.argtypes = [C.POINTER(Config), C.c_uint32, C.c_int, C.c_int, C.POINTER(vp)]
+            L.mi355x_h264_stream_source_width.argtypes = [vp]
+            L.mi355x_h264_stream_source_height.argtypes = [vp]
         L.mi355x_h264_stream_close.argtypes = [vp]
         L.mi355x_h264_stream_close.restype = None
         L.mi355x_h264_stream_encode.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
@@ -428,10 +432,11 @@ class Stream:
     other streams of the same geometry deliver at about the same time; thread-safe across streams (one thread per stream).
     input_format (INPUT_I420 / INPUT_NV12 / INPUT_RGBA) is the layout of every picture of the stream, from host or device memory.
     refs 2 / 3: that many reference pictures are searched; the stream is opened with mi355x_h264_stream_open_ex (as it is whenever
-    `flags` is given: the flags of that call)"""
+    `flags` is given: the flags of that call).  src_size = (SW, SH): a scaled stream (mi355x_h264_stream_open_scaled) - every encode
+    call takes pictures of SW x SH, which the device resamples to width x height; debug_read(DBG_SRC) is the resampled picture"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
-                 input_format=0, refs=0, flags=None):
+                 input_format=0, refs=0, flags=None, src_size=None):
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
@@ -442,16 +447,19 @@ class Stream:
         if flags is None and refs > 1:
             flags = STREAM_MULTIREF
         self.h = C.c_void_p()
-        if flags is None:
+        if src_size is not None:
+            rc = L.mi355x_h264_stream_open_scaled(C.byref(cfg), flags or 0, int(src_size[0]), int(src_size[1]), C.byref(self.h))
+        elif flags is None:
             rc = L.mi355x_h264_stream_open(C.byref(cfg), C.byref(self.h))
         else:
             rc = L.mi355x_h264_stream_open_ex(C.byref(cfg), flags, C.byref(self.h))
         if rc != 0:
             self.h = None
-            err = EncoderError("mi355x_h264_stream_open%s failed: %d" % ("" if flags is None else "_ex", rc))
+            err = EncoderError("mi355x_h264_stream_open%s failed: %d" % ("_scaled" if src_size is not None else "" if flags is None else "_ex", rc))
             err.rc = rc
             raise err
         self.width, self.height = width, height
+        self.src_width, self.src_height = (width, height) if src_size is None else (int(src_size[0]), int(src_size[1]))   # what the calls take
         self.cw, self.ch = L.mi355x_h264_stream_coded_width(self.h), L.mi355x_h264_stream_coded_height(self.h)
         self.nmb = (self.cw // 16) * (self.ch // 16)
 
@@ -463,7 +471,7 @@ class Stream:
 
     def encode(self, i420, strides=None):
         """host I420; with strides = (y, u, v) in bytes, i420 is the three planes as separate arrays"""
-        ((y, ys), (u, us), (v, vs)), keep = _planes(i420, self.width, self.height, strides)
+        ((y, ys), (u, us), (v, vs)), keep = _planes(i420, self.src_width, self.src_height, strides)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
         self._check(lib().mi355x_h264_stream_encode(self.h, y, ys, u, us, v, vs, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
@@ -476,7 +484,7 @@ class Stream:
 
     def encode_nv12(self, nv12, strides=None):
         """host NV12 (Y plane then interleaved UV); with strides = (y, uv), nv12 is the two planes as separate arrays"""
-        ((y, ys), (uv, uvs)), keep = _planes(nv12, self.width, self.height, strides, nv12=True)
+        ((y, ys), (uv, uvs)), keep = _planes(nv12, self.src_width, self.src_height, strides, nv12=True)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
         self._check(lib().mi355x_h264_stream_encode_nv12(self.h, y, ys, uv, uvs, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
@@ -485,11 +493,15 @@ class Stream:
         """host RGBA (height x width x 4 bytes, or rows `stride` bytes apart)"""
         f = np.ascontiguousarray(rgba, dtype=np.uint8)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.width), C.byref(out), C.byref(n), C.byref(ft)))
+        self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.src_width), C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
     def last_error(self):
         return lib().mi355x_h264_stream_last_error(self.h).decode()
+
+    def source_size(self):
+        """(width, height) of the pictures the calls take (mi355x_h264_stream_source_width / _height)"""
+        return lib().mi355x_h264_stream_source_width(self.h), lib().mi355x_h264_stream_source_height(self.h)
 
     def set_qp(self, qp):
         self._check(lib().mi355x_h264_stream_set_qp(self.h, qp))

@@ -22,6 +22,9 @@ struct HubItem {
     const uint8_t* d_in = nullptr;
     const uint8_t* rgba_src = nullptr;
     size_t rgba_stride = 0;
+    // scaling hubs: the tight source picture (the caller's device picture or the item's source staging slot); the step's scaler
+    // writes the I420 staging slot (RGBA: the item's RGBA staging slot, which the conversion launch then reads)
+    const uint8_t* scale_src = nullptr;
     int rc = 0, frame_type = 0;
     uint8_t* out = nullptr;
     uint32_t out_len = 0;
@@ -31,8 +34,9 @@ struct HubItem {
 struct HubCtx {
     StepSync sync;                   // a stream pair of its own
     // the step's tables, one pinned block and one transfer: [source address per position][itemtab word per position][RGBA hubs:
-    // {address, row stride} of the RGBA picture per position]
-    enum { TAB_SRC = 0, TAB_ITEM = MAX_BATCH * 8, TAB_RGBA = TAB_ITEM + MAX_BATCH * 4, TAB_BYTES = TAB_RGBA + MAX_BATCH * 16 };
+    // {address, row stride}][scaling hubs: ScaleSrc per position]
+    enum { TAB_SRC = 0, TAB_ITEM = MAX_BATCH * 8, TAB_RGBA = TAB_ITEM + MAX_BATCH * 4, TAB_SCALE = TAB_RGBA + MAX_BATCH * 16,
+           TAB_BYTES = TAB_SCALE + MAX_BATCH * (int)sizeof(ScaleSrc) };
     uint8_t* h_tab = nullptr;        // pinned
     uint8_t* d_tab = nullptr;
 };
@@ -52,6 +56,14 @@ struct Hub {
     uint8_t* d_rgba = nullptr;       // [cap] host RGBA pictures on their way to the conversion kernel: allocated with the hub's
     uint8_t* h_rgba = nullptr;       // first one (pinned)
     size_t st_rgba = 0;
+    // scaling hubs (mi355x_h264_stream_open_scaled): pictures arrive sw x sh and the step's scaler resamples them to cfg.width x
+    // cfg.height.  d_src / h_src: [cap] host pictures of the source size on their way to it, allocated with the hub's first one;
+    // RGBA: d_rgba holds the [cap] RESAMPLED RGBA pictures (device only, allocated with the hub)
+    int sw = 0, sh = 0;              // the size of the pictures the calls take (an ordinary hub: cfg.width, cfg.height)
+    bool scaled = false;
+    uint8_t* d_src = nullptr;
+    uint8_t* h_src = nullptr;
+    size_t st_src = 0;
     // uploads: item k on copy stream k % NCOPY.  Two streams fill most of the link (tools/ubench_h2d.hip: 1 stream 32 GB/s, 2: 46-51,
     // 4+: 52-57); HIP streams are a scarce resource on this runtime - beyond about a dozen live streams in the process every launch
     // gets slower (measured: 8 copy streams per hub halved the throughput at 64 streams)
@@ -67,9 +79,10 @@ std::vector<Hub*> g_hubs;
 std::atomic<int> g_streams_open{0};   // over all hubs of the process
 
 // (refs: 0 and 1 are both one reference picture; streams that search more have rings of another size, so engines of their own)
-bool same_geometry(const mi355x_h264_config& a, const mi355x_h264_config& b)
+bool same_geometry(const Hub& hub, const mi355x_h264_config& b, int sw, int sh)
 {
-    return std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
+    const mi355x_h264_config& a = hub.cfg;
+    return hub.sw == sw && hub.sh == sh && std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
            a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
 }
 
@@ -98,6 +111,7 @@ hipError_t hub_alloc(Hub* h)
     h->mem.configure();
     HIPTRY(DM_DEV(h->mem, h->d_stage, h->st_stage * h->sched.cap, false));
     HIPTRY(DM_PINNED(h->mem, h->h_stage, h->st_stage * h->sched.cap));
+    if (h->scaled && h->fmt == MI355X_H264_INPUT_RGBA) HIPTRY(DM_DEV(h->mem, h->d_rgba, h->st_rgba * h->sched.cap, false));
     for (auto& cs : h->copy_st) HIPTRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     const char* one = getenv("MI355X_H264_ONE_STREAM");
     for (int ci = 0; ci <= h->sched.nctx_p; ci++) {
@@ -111,12 +125,13 @@ hipError_t hub_alloc(Hub* h)
     return hipSuccess;
 }
 
-int hub_create(const mi355x_h264_config& cfg, Hub** out)
+int hub_create(const mi355x_h264_config& cfg, int sw, int sh, Hub** out)
 {
     Hub* h = new (std::nothrow) Hub();
     if (!h) return MI355X_H264_E_NOMEM;
     h->cfg = cfg;
     h->fmt = cfg.input_format;
+    h->sw = sw; h->sh = sh; h->scaled = sw != cfg.width || sh != cfg.height;
     const char* ci = getenv("MI355X_H264_HUB_ITEMS");
     h->sched.cap = std::min((int)MAX_BATCH, std::max(1, ci ? atoi(ci) : 32));
     const char* wu = getenv("MI355X_H264_HUB_WINDOW_US");
@@ -133,6 +148,7 @@ int hub_create(const mi355x_h264_config& cfg, Hub** out)
     h->sched.nrefs = h->e->nrefs; h->sched.nbuf = h->e->nbuf;   // (up to 4 ring slots: `cur` fits the itemtab word's two bits)
     h->st_stage = (picture_bytes(PIC_I420, cfg.width, cfg.height) + 255) & ~(size_t)255;
     h->st_rgba = (picture_bytes(PIC_RGBA, cfg.width, cfg.height) + 255) & ~(size_t)255;
+    h->st_src = (picture_bytes(h->fmt, sw, sh) + 255) & ~(size_t)255;
     if (hub_alloc(h) != hipSuccess) { hub_free(h); return MI355X_H264_E_HIP; }
     *out = h;
     return MI355X_H264_OK;
@@ -157,24 +173,40 @@ void hub_run_step(Hub* h, HubStep& T)
         unsigned long long* const h_src = (unsigned long long*)(c.h_tab + HubCtx::TAB_SRC);
         uint32_t* const h_itemtab = (uint32_t*)(c.h_tab + HubCtx::TAB_ITEM);
         RgbaSrc* const h_rgbatab = (RgbaSrc*)(c.h_tab + HubCtx::TAB_RGBA);
+        ScaleSrc* const h_scaletab = (ScaleSrc*)(c.h_tab + HubCtx::TAB_SCALE);
+        const bool scaled = h->scaled;
         for (int k = 0; k < n; k++) {
             const HubItem& it = h->items[pics[k].item];
             h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].nref << 10) | ((uint32_t)pics[k].qp << 16);
             // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
             h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
-            if (rgba) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)it.rgba_src, (unsigned long long)it.rgba_stride};
+            // (a scaling RGBA hub: the conversion reads the item's slot of the resampled RGBA pictures)
+            if (rgba && scaled) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)(h->d_rgba + (size_t)pics[k].item * h->st_rgba), (unsigned long long)h->cfg.width * 4};
+            else if (rgba) h_rgbatab[k] = RgbaSrc{(unsigned long long)(uintptr_t)it.rgba_src, (unsigned long long)it.rgba_stride};
+            if (scaled) h_scaletab[k] = ScaleSrc{(unsigned long long)(uintptr_t)it.scale_src, (uint32_t)(rgba ? 4 * h->sw : h->sw),
+                                                 (uint32_t)(rgba ? 0 : h->fmt == MI355X_H264_INPUT_NV12 ? h->sw : h->sw / 2), (uint32_t)h->fmt, 0};
             if (it.staged && hipStreamWaitEvent(Y.st, it.copied, 0) != hipSuccess) rc = MI355X_H264_E_HIP;
         }
-        const size_t tab_bytes = rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
+        const size_t tab_bytes = scaled ? HubCtx::TAB_SCALE + (size_t)n * sizeof(ScaleSrc) : rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
         if (hipMemcpyAsync(c.d_tab, c.h_tab, tab_bytes, hipMemcpyHostToDevice, Y.st) != hipSuccess) rc = MI355X_H264_E_HIP;
         const unsigned long long* const d_srctab = (const unsigned long long*)(c.d_tab + HubCtx::TAB_SRC);
+        if (rc == MI355X_H264_OK && scaled) {   // one scaling launch for the step: every position, all planes (scale_kernels.h)
+            const int w = h->cfg.width, hh = h->cfg.height, th = scale_tile_rows(h->sh, hh);
+            const ScalePlane PY = scale_plane_make(h->sw, h->sh, w, hh), PC = scale_plane_make(h->sw / 2, h->sh / 2, w / 2, hh / 2);
+            const bool nv12 = h->fmt == MI355X_H264_INPUT_NV12;
+            const int ntx_y = scale_tiles_x(w, rgba ? 4 : 1), ntx_c = rgba ? 0 : scale_tiles_x(w / 2, nv12 ? 2 : 1);
+            hipLaunchKernelGGL(k_scale_to_i420_step, dim3((unsigned)(ntx_y + (nv12 ? 1 : 2) * ntx_c), (unsigned)((hh + th - 1) / th), (unsigned)n), dim3(256), 0, Y.st,
+                               (const ScaleSrc*)(c.d_tab + HubCtx::TAB_SCALE), rgba ? (const unsigned long long*)(c.d_tab + HubCtx::TAB_RGBA) : d_srctab, rgba ? 2 : 1,
+                               PY, PC, ntx_y, ntx_c, th);
+        }
         if (rc == MI355X_H264_OK && rgba) {   // one conversion launch for the step, in front of the first kernel that reads samples
             const int w = h->cfg.width, hh = h->cfg.height;
             hipLaunchKernelGGL(k_rgba_to_i420_step, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(hh / 2), (unsigned)n), dim3(256), 0, Y.st,
                                (const RgbaSrc*)(c.d_tab + HubCtx::TAB_RGBA), d_srctab, w, hh);
         }
         if (rc == MI355X_H264_OK) {
-            St.d_src = nullptr; St.src_item_stride = 0; St.nv12 = h->fmt == MI355X_H264_INPUT_NV12; St.idr = idr; St.n = n;
+            St.d_src = nullptr; St.src_item_stride = 0; St.idr = idr; St.n = n;
+            St.nv12 = h->fmt == MI355X_H264_INPUT_NV12 && !scaled;   // (a scaling hub's staging picture is I420)
             St.items = pics; St.d_itemtab = (const uint32_t*)(c.d_tab + HubCtx::TAB_ITEM); St.d_srctab = d_srctab;
             // entropy coding beside the loop filter shortens a picture's latency; with many streams open the second HIP stream
             // costs more than the overlap brings (64 streams: 10.9 k -> 12.1 k fps on one stream per step)
@@ -214,7 +246,7 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
 {
     Hub* h = s->hub;
     HubItem& it = h->items[s->item];
-    const int w = h->cfg.width, hh = h->cfg.height, item = s->item;
+    const int w = h->sw, hh = h->sh, item = s->item;   // the size of the pictures the calls take: the source size of a scaling hub
     const bool rgba = h->fmt == MI355X_H264_INPUT_RGBA;
     // whatever is refused is refused here, on the host, before anything is queued or launched; the stream stays usable
     auto refuse = [&](const char* why) { return set_err(it.err, MI355X_H264_E_ARG, "%s", why); };
@@ -227,7 +259,18 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
     const uint64_t t_in = now_us();
     const bool staged = in.layout != HUB_IN_DEVICE;
     bool ok = true;
-    if (staged) {
+    if (staged && h->scaled) {
+        // a scaling hub's host picture goes to the stream's source staging slot, which comes with the hub's first host picture; the
+        // step's scaler reads it after it.copied
+        const int nopen = h->sched.begin_upload([&] { return DM_PAIR(h->mem, h->d_src, h->h_src, h->st_src * h->sched.cap); });
+        if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the source staging pictures");
+        const size_t off = (size_t)item * h->st_src;
+        it.d_in = nullptr; it.scale_src = h->d_src + off;
+        ok = stage_picture(in, w, hh, h->h_src + off, h->d_src + off, h->copy_st[item % Hub::NCOPY], in.layout == PIC_I420 && nopen <= 4 ? 4 : 1) == hipSuccess &&
+             hipEventRecord(it.copied, h->copy_st[item % Hub::NCOPY]) == hipSuccess;
+    } else if (h->scaled) {
+        it.d_in = nullptr; it.scale_src = in.p[0];   // read where it lies by the step's scaler, during the call
+    } else if (staged) {
         // 1. a host picture goes to the stream's staging slot (RGBA: to its RGBA staging slot, which comes with the hub's first host
         // RGBA picture; the step's conversion launch writes the I420 slot): pinned copy, then the transfer on the item's copy
         // stream; it.copied says when it has arrived

@@ -36,6 +36,7 @@ using namespace h264;
 
 #include "host_framing.h"
 #include "rgba_kernels.h"
+#include "scale_kernels.h"
 #include "k_dec_out.h"
 #include "dev_mem.h"
 #include "pic_store.h"
@@ -330,7 +331,18 @@ int mi355x_h264_stream_open(const mi355x_h264_config* cfg, mi355x_h264_stream** 
 int mi355x_h264_stream_open_ex(const mi355x_h264_config* cfg, uint32_t flags, mi355x_h264_stream** out)
 {
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
+    return mi355x_h264_stream_open_scaled(cfg, flags, cfg->width, cfg->height, out);
+}
+
+int mi355x_h264_stream_open_scaled(const mi355x_h264_config* cfg, uint32_t flags, int sw, int sh, mi355x_h264_stream** out)
+{
+    if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
     *out = nullptr;
+    if (sw != cfg->width || sh != cfg->height) {   // (the same size: exactly mi355x_h264_stream_open_ex, whatever it makes of the size)
+        if (((sw | sh) & 1) || sw < 16 || sh < 16 || sw > 4096 || sh > 4096) return MI355X_H264_E_ARG;
+        if (cfg->width < 16 || cfg->height < 16 || ((cfg->width | cfg->height) & 1)) return MI355X_H264_E_ARG;
+        if (sw < cfg->width || sh < cfg->height || sw > 4 * cfg->width || sh > 4 * cfg->height) return MI355X_H264_E_ARG;
+    }
     if (flags & ~(uint32_t)MI355X_H264_STREAM_MULTIREF) return MI355X_H264_E_ARG;
     const int max_refs = (flags & MI355X_H264_STREAM_MULTIREF) ? (int)mi355x_h264_encoder::MAX_REFS : 1;
     if (cfg->refs > max_refs || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
@@ -342,9 +354,9 @@ int mi355x_h264_stream_open_ex(const mi355x_h264_config* cfg, uint32_t flags, mi
     std::lock_guard<std::mutex> gl(g_hubs_mu);
     Hub* h = nullptr;
     for (Hub* c : g_hubs)
-        if (same_geometry(c->cfg, *cfg) && c->sched.has_room()) { h = c; break; }
+        if (same_geometry(*c, *cfg, sw, sh) && c->sched.has_room()) { h = c; break; }
     if (!h) {
-        const int rc = hub_create(*cfg, &h);
+        const int rc = hub_create(*cfg, sw, sh, &h);
         if (rc != MI355X_H264_OK) { delete s; return rc; }
         g_hubs.push_back(h);
     }
@@ -408,6 +420,8 @@ int mi355x_h264_stream_last_me_cost(const mi355x_h264_stream* s, uint32_t* cost)
 const char* mi355x_h264_stream_last_error(const mi355x_h264_stream* s) { return s ? s->hub->items[s->item].err : "null stream"; }
 int mi355x_h264_stream_coded_width(const mi355x_h264_stream* s) { return s ? s->hub->e->cw : 0; }
 int mi355x_h264_stream_coded_height(const mi355x_h264_stream* s) { return s ? s->hub->e->ch : 0; }
+int mi355x_h264_stream_source_width(const mi355x_h264_stream* s) { return s ? s->hub->sw : 0; }
+int mi355x_h264_stream_source_height(const mi355x_h264_stream* s) { return s ? s->hub->sh : 0; }
 
 // test hooks: what mi355x_h264_debug_read gives for an engine, for the stream's own batch item after its last picture; the stream's
 // calls are synchronous, so the picture is complete, and nothing rewrites the item's arrays before the stream's next call

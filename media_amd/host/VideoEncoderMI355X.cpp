@@ -82,11 +82,24 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     // variable MI355X_H264_HUB=0) keeps the engine of its own.
     const char *hubEnv = getenv("MI355X_H264_HUB");
     const bool shared = GetStrEncParam("persist.vmi.video.encode.shared") != "0" && !(hubEnv != nullptr && hubEnv[0] == '0');
+    // extension: pictures of srcwidth x srcheight, resampled to the coded size on the device (stream path only)
+    const std::string srcW = GetStrEncParam("persist.vmi.video.encode.srcwidth"), srcH = GetStrEncParam("persist.vmi.video.encode.srcheight");
+    m_srcWidth = m_srcHeight = 0;
+    const int haveSrc = ParseSourceSize(srcW, srcH, s.width, s.height, &m_srcWidth, &m_srcHeight);
+    if (haveSrc < 0) {
+        WARN("source size [%s] x [%s] rejected for %ux%u: pictures are taken at the coded size", srcW.c_str(), srcH.c_str(), s.width, s.height);
+    }
+    if (haveSrc > 0 && !shared) {
+        ERR("source size %dx%d: scaling exists on the stream path only (persist.vmi.video.encode.shared = 0 is set)", m_srcWidth, m_srcHeight);
+        m_srcWidth = m_srcHeight = 0;
+        return false;
+    }
     if (shared) {
         cfg.input_format = m_input;
-        const int rc = mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
+        const int rc = haveSrc > 0 ? mi355x_h264_stream_open_scaled(&cfg, MI355X_H264_STREAM_MULTIREF, m_srcWidth, m_srcHeight, &m_stream)
+                                   : mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
         if (rc != MI355X_H264_OK) {
-            ERR("mi355x_h264_stream_open_ex returned %d", rc);
+            ERR("mi355x_h264_stream_open_%s returned %d", haveSrc > 0 ? "scaled" : "ex", rc);
             m_stream = nullptr;
             return false;
         }
@@ -242,6 +255,28 @@ bool VideoEncoderMI355X::ParsePsnr(const std::string &value) { return value == "
 
 bool VideoEncoderMI355X::ParseInputDevice(const std::string &value) { return value == "device"; }
 
+int VideoEncoderMI355X::ParseSourceSize(const std::string &width, const std::string &height, uint32_t codedWidth, uint32_t codedHeight,
+                                        int32_t *srcWidth, int32_t *srcHeight)
+{
+    if (width.empty() && height.empty()) {
+        return 0;
+    }
+    auto number = [](const std::string &v) {   // 1 .. 5 decimal digits and nothing else; -1 otherwise
+        if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) {
+            return -1;
+        }
+        return atoi(v.c_str());
+    };
+    const int32_t w = number(width), h = number(height);
+    const int64_t cw = codedWidth, ch = codedHeight;
+    if (((w | h) & 1) != 0 || !Within(w, 16, 4096) || !Within(h, 16, 4096) || w < cw || h < ch || w > 4 * cw || h > 4 * ch) {
+        return -1;
+    }
+    *srcWidth = w;
+    *srcHeight = h;
+    return 1;
+}
+
 int VideoEncoderMI355X::EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType)
 {
     if (m_inputDevice) {   // one tight picture in device memory, in the object's layout
@@ -252,19 +287,19 @@ int VideoEncoderMI355X::EncodePicture(const uint8_t *i420, uint8_t **out, uint32
                                                  : mi355x_h264_encode_device(m_engine, i420, out, outLen, frameType);
     }
     if (m_input == MI355X_H264_INPUT_RGBA) {
-        const int stride = static_cast<int>(Active().width) * 4;
+        const int stride = static_cast<int>(SrcWidth()) * 4;
         return m_stream != nullptr ? mi355x_h264_stream_encode_rgba(m_stream, i420, stride, out, outLen, frameType)
                                    : mi355x_h264_encode_rgba(m_engine, i420, stride, out, outLen, frameType);
     }
     if (m_input == MI355X_H264_INPUT_NV12) {
-        const int w = static_cast<int>(Active().width);
-        return m_stream != nullptr ? mi355x_h264_stream_encode_nv12(m_stream, i420, w, i420 + LumaBytes(), w, out, outLen, frameType)
-                                   : mi355x_h264_encode_nv12(m_engine, i420, w, i420 + LumaBytes(), w, out, outLen, frameType);
+        const int w = static_cast<int>(SrcWidth());
+        return m_stream != nullptr ? mi355x_h264_stream_encode_nv12(m_stream, i420, w, i420 + SrcLumaBytes(), w, out, outLen, frameType)
+                                   : mi355x_h264_encode_nv12(m_engine, i420, w, i420 + SrcLumaBytes(), w, out, outLen, frameType);
     }
     // tight I420 exactly as the reference's InitSrcPic lays the planes out (ref :354-365)
-    const int pitch = static_cast<int>(Active().width);
-    const uint8_t *u = i420 + LumaBytes();
-    const uint8_t *v = u + LumaBytes() / 4;
+    const int pitch = static_cast<int>(SrcWidth());
+    const uint8_t *u = i420 + SrcLumaBytes();
+    const uint8_t *v = u + SrcLumaBytes() / 4;
     if (m_stream != nullptr) {
         return mi355x_h264_stream_encode(m_stream, i420, pitch, u, pitch / 2, v, pitch / 2, out, outLen, frameType);
     }

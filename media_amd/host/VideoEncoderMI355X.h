@@ -40,6 +40,12 @@ public:
     // extension key persist.vmi.video.encode.psnr: "1" -> the library's quality report is on (include/mi355x_h264.h, "quality
     // report"), on the stream path and with an engine of its own alike; anything else (or unset) -> off
     static bool ParsePsnr(const std::string &value);
+    // extension keys persist.vmi.video.encode.srcwidth / .srcheight: EncodeOneFrame takes pictures of that size and the device
+    // resamples them to the coded size (include/mi355x_h264.h, "scaled streams").  1: both are decimal numbers, even, 16 .. 4096,
+    // at least the coded size and at most 4 times it (*srcWidth, *srcHeight set); 0: neither key is set; -1: anything else (one
+    // key alone, junk, out of range) - the reference's behaviour, with one WARN line
+    static int ParseSourceSize(const std::string &width, const std::string &height, uint32_t codedWidth, uint32_t codedHeight,
+                               int32_t *srcWidth, int32_t *srcHeight);
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -48,9 +54,12 @@ protected:
     bool EngineReady() const override { return m_engine != nullptr || m_stream != nullptr; }
     bool EngineEncode(const uint8_t *i420, uint8_t **out, uint32_t *outLen) override;
     bool EngineForceIdr() override;
-    uint32_t EnginePictureBytes() const override { return m_input == MI355X_H264_INPUT_RGBA ? LumaBytes() * 4 : LumaBytes() * 3 / 2; }
+    uint32_t EnginePictureBytes() const override { return m_input == MI355X_H264_INPUT_RGBA ? SrcLumaBytes() * 4 : SrcLumaBytes() * 3 / 2; }
 
 private:
+    // the size of the pictures EncodeOneFrame is handed: the source size of a scaled stream, else the coded size
+    uint32_t SrcWidth() const { return m_srcWidth > 0 ? static_cast<uint32_t>(m_srcWidth) : Active().width; }
+    uint32_t SrcLumaBytes() const { return m_srcWidth > 0 ? static_cast<uint32_t>(m_srcWidth) * static_cast<uint32_t>(m_srcHeight) : LumaBytes(); }
     int EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType);
     void RateControlUpdate(uint32_t frameBytes, bool isIdr);
     static int32_t StartQp(uint32_t bitrate, uint32_t fps, uint32_t width, uint32_t height);
@@ -67,6 +76,7 @@ private:
     bool m_sceneDetect = true;         // bEnableSceneChangeDetect = 1 in the reference preset (ref :283)
     uint32_t m_sceneCuts = 0;
     int32_t m_input = MI355X_H264_INPUT_I420;   // layout of the pictures EncodeOneFrame is handed (persist.vmi.video.encode.input)
+    int32_t m_srcWidth = 0, m_srcHeight = 0;    // > 0: the pictures' size (.srcwidth / .srcheight), resampled to the coded size on the device
     bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
     // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
     bool m_psnr = false, m_haveQuality = false;

@@ -28,6 +28,11 @@ uint32_t vc_encode_addr(void *enc, uint64_t addr, uint32_t inSize, uint8_t **out
 // how the two input extension keys read a value (host logic, no device)
 int32_t vc_parse_input_layout(const char *value) { return VideoEncoderMI355X::ParseInputLayout(value != nullptr ? value : ""); }
 int32_t vc_parse_input_device(const char *value) { return VideoEncoderMI355X::ParseInputDevice(value != nullptr ? value : "") ? 1 : 0; }
+// persist.vmi.video.encode.srcwidth / .srcheight at a coded size: 1 (and the size), 0 (neither set) or -1 (rejected)
+int32_t vc_parse_source_size(const char *width, const char *height, uint32_t codedWidth, uint32_t codedHeight, int32_t *srcWidth, int32_t *srcHeight)
+{
+    return VideoEncoderMI355X::ParseSourceSize(width != nullptr ? width : "", height != nullptr ? height : "", codedWidth, codedHeight, srcWidth, srcHeight);
+}
 // persist.vmi.video.encode.refs: 2 or 3 are taken, anything else is one reference picture
 int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
 // persist.vmi.video.encode.psnr: "1" turns the quality report on, anything else leaves it off

@@ -36,6 +36,7 @@ def lib():
         L.vc_parse_input_device.argtypes = [C.c_char_p]
         L.vc_parse_refs.argtypes = [C.c_char_p]
         L.vc_parse_psnr.argtypes = [C.c_char_p]
+        L.vc_parse_source_size.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.vc_last_quality.argtypes = [vp, vp]
         L.vc_debug_ref_counts.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
         L.vc_debug_ref_counts.restype = None
@@ -82,6 +83,15 @@ def parse_psnr(value):
     return bool(lib().vc_parse_psnr(str(value).encode()))
 
 
+def parse_source_size(width, height, coded_width, coded_height):
+    """what persist.vmi.video.encode.srcwidth = width and .srcheight = height select at a coded size: (SW, SH) when both are
+    decimal numbers, even, 16 .. 4096, at least the coded size and at most 4 times it; None when neither key is set; False for
+    anything else (the reference's behaviour, with a WARN line)"""
+    sw, sh = C.c_int32(), C.c_int32()
+    rc = lib().vc_parse_source_size(str(width).encode(), str(height).encode(), coded_width, coded_height, C.byref(sw), C.byref(sh))
+    return (sw.value, sh.value) if rc > 0 else None if rc == 0 else False
+
+
 def ref_counts(nrefs, gop, n, forced=()):
     """the number of reference pictures of each of n pictures of a stream that searches nrefs, IDR every gop pictures and at the
     pictures in `forced` (the rule the engine and the stream hub share; 0 = an IDR picture)"""
@@ -92,7 +102,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None, refs=None, psnr=None, shared=None):
+                   inputmem=None, refs=None, psnr=None, shared=None, srcwidth=None, srcheight=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -111,6 +121,8 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.inputmem", "" if inputmem is None else inputmem)   # device; else host memory
     prop_set("persist.vmi.video.encode.refs", "" if refs is None else refs)               # 2 | 3; else one reference picture
     prop_set("persist.vmi.video.encode.psnr", "" if psnr is None else psnr)               # 1: quality report; else off
+    prop_set("persist.vmi.video.encode.srcwidth", "" if srcwidth is None else srcwidth)   # both set and valid: pictures of that
+    prop_set("persist.vmi.video.encode.srcheight", "" if srcheight is None else srcheight)   # size, resampled to width x height
     if shared is not None:
         prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 

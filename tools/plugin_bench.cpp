@@ -5,13 +5,16 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--refs N] [--psnr] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--refs N] [--psnr] [--src WxH] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
 // --psnr (anywhere on the line): the extension key persist.vmi.video.encode.psnr = 1 - the library's quality report is on, every
 // picture's record is read after its call (outside the latency sample), and the JSON line carries psnr_y / psnr_u / psnr_v: the
 // PSNR of the mean squared error of all pictures of the run, per plane.
+// --src WxH (anywhere on the line): the extension keys persist.vmi.video.encode.srcwidth / .srcheight = W / H - the file holds
+// pictures of W x H, which every object hands over as they are and the device resamples to the coded size (<width> <height> and
+// the geometry keys stay the coded size's).
 // input (optional; without it everything is as above): i420 | nv12 | rgba, with ":device" behind it for pictures in device
 // memory - the extension keys persist.vmi.video.encode.input / .inputmem.  The pictures of the file are converted to the layout
 // on the host before the clock starts; for device memory they are uploaded once, before the clock, and every stream cycles
@@ -50,8 +53,19 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
-    const int w = atoi(argv[2]), h = atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
+    int srcW = 0, srcH = 0;
+    for (int i = 1; i + 1 < argc; i++)   // --src WxH: taken out of the line
+        if (strcmp(argv[i], "--src") == 0) {
+            if (sscanf(argv[i + 1], "%dx%d", &srcW, &srcH) != 2 || srcW < 16 || srcH < 16) { fprintf(stderr, "--src %s: WxH expected\n", argv[i + 1]); return 2; }
+            setenv("PERSIST_VMI_VIDEO_ENCODE_SRCWIDTH", std::to_string(srcW).c_str(), 1);
+            setenv("PERSIST_VMI_VIDEO_ENCODE_SRCHEIGHT", std::to_string(srcH).c_str(), 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--src WxH] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    // (w, h: the size of the pictures in the file and in every call - the source size with --src)
+    const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
     std::vector<uint8_t> pics(fsz * npic);
     FILE *in = fopen(argv[1], "rb");
