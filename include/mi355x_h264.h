@@ -198,7 +198,9 @@ enum {
     MI355X_H264_DBG_RECON_U = 1,
     MI355X_H264_DBG_RECON_V = 2,
     MI355X_H264_DBG_MBINFO = 3,    /* 32 B per macroblock, layout of h264 mbinfo below      */
-    MI355X_H264_DBG_LEVELS = 4,    /* 416 int16 per macroblock                              */
+    MI355X_H264_DBG_LEVELS = 4,    /* 416 int16 per macroblock.  Defined where the picture's syntax reads them (by macroblock type
+                                    * and coded_block_pattern, 7.3.5.3); a part whose pattern bit is clear holds whatever an earlier
+                                    * picture left there */
     MI355X_H264_DBG_PRE_Y = 5,     /* reconstruction before the loop filter (needs          */
     MI355X_H264_DBG_PRE_U = 6,     /*  mi355x_h264_debug_keep_pre(enc, 1))                  */
     MI355X_H264_DBG_PRE_V = 7,

@@ -4,7 +4,26 @@
 //
 // SURVEY.md 8a row a6.2 (inside ISVCEncoder::EncodeFrame, /root/reference/video_codec/VideoEncoderOpenH264.cpp:344).
 // This is the kernel the bench's `roofline` block prices against HBM.  Algorithmic HBM bytes per macroblock:
-// source 384 + prediction 384 in; reconstruction 384 + levels 768 + side info 32 out = 1952.
+// source 384 + prediction 384 in; reconstruction 384 + levels 768 + side info 32 out = 1952.  That is the price of a
+// macroblock whose every part is coded, and an UPPER BOUND on what is moved: only what a later stage reads is stored.
+//
+// What is stored, and what is defined after a picture (k_tq and k_tq8 alike):
+//   - levels: the four 4x4 lists of an 8x8 luma quadrant whose coded_block_pattern bit is set (= some block of it has a
+//     level); the eight chroma DC levels where cbp >> 4 >= 1; the eight chroma AC lists where cbp >> 4 == 2.  These are
+//     exactly the lists k_cavlc asks for (code_slot, second trip).  The levels of every other part are NOT written: they
+//     are left from an earlier picture (or from the allocation) and mean nothing.  Whoever reads `levels` goes by type and
+//     coded_block_pattern first (k_cavlc does; so do the tests' comparisons).
+//   - samples: the four words of a 4x4 block (the eight rows of an 8x8 block) whose inverse transform had a non-zero input:
+//     TotalCoeff != 0, for chroma also a non-zero scaled DC term.  With only zero inputs 8.5.12 returns zeros and the
+//     prediction k_me wrote IS the reconstruction.  Every sample of every macroblock is therefore defined after the kernel.
+//   - MbInfo.tc: a block's byte where it is not 0.  THE TC INVARIANT this relies on: every macroblock this kernel codes had
+//     tc[0..23] zeroed in the same picture by k_me.  In k_me's first launch (rf == 0) every macroblock leaves through
+//     settle() or through the write-out under `better` (always true at rf == 0: prev_total is 0xFFFFFFFF), a macroblock of
+//     any partition shape included, and an intra hand-off follows the write-out: all three store m[0] with words 2, 3 = 0 and
+//     m[1] = 0, that is tc[0..7] and tc[8..23].  A later reference picture's launch stores the same zeros when it is
+//     `better` and nothing of MbInfo when it is not, and nothing else writes MbInfo between k_me and this kernel.  A change
+//     to k_me that keeps any tc byte across pictures must bring the unconditional stores back here.
+//   - MbInfo.cbp of every macroblock coded here; the I_PCM rewrite stores all of its macroblock's samples and bytes itself.
 //
 // What changed against round 1's k_pmb2 (one wave per macroblock pair, lane = (4x4 block, row), column passes over
 // DPP quads, motion compensation in front): the prediction now arrives from k_me, which has every sample of it in LDS
@@ -18,7 +37,11 @@
 //     8 macroblocks x 2 planes x 4 blocks - every pass uses all 64 lanes;
 //   - the quantiser works on signed values, l = (w * mf + (w < 0 ? 2^q - 1 - f : f)) >> q (equal to the
 //     sign / magnitude form of the oracle for every w), with its wave-uniform constants pinned in VGPRs;
-//   - TotalCoeff is counted on the packed int16 level pairs (6 fast operations per pair).
+//   - TotalCoeff is counted on the packed int16 level pairs (6 fast operations per pair);
+//   - the luma SECOND stage (scaling, inverse transform, reconstruction, bit bound) runs once per wave, not once per pass:
+//     both passes keep their packed levels and prediction words, then every lane takes whichever of its two blocks has a
+//     level; a second run only when some lane has two, and none when no lane has any (both wave-uniform, by ballot).  On
+//     the bench content 3 % of the luma blocks have a level.  (The MI355X_AB_TQ_4MB layout keeps the stage per pass.)
 // Macroblocks whose prediction already quantises to nothing (k_me's tests) are not touched at all: k_me has written
 // their side info, and prediction = reconstruction; macroblocks k_me handed to the intra pass are skipped too.
 // I_PCM fallback: every block's levels also give an upper bound on its CAVLC bits (dev_common.h, derivation in
@@ -78,6 +101,46 @@ __device__ __forceinline__ int tq_block(int d[16], const TqConst& K, uint32_t lv
     return (int)((cnt2 & 0xFFFFu) + (cnt2 >> 16));
 }
 
+// the two halves of tq_block<false> apart, for the luma passes of k_tq that run the second half once per wave: residual d[] ->
+// packed zig-zag levels lvp[] (returns TotalCoeff), and packed levels -> decoded residual d[].  The second half starts from the
+// packed int16 pairs, which is exact: |w| <= 36 * 255, mf <= 13107 and a shift of at least 15 keep a luma level below 3 700 in
+// magnitude, far inside 16 bits (the levels array and the entropy coder hold them as int16 anyway)
+__device__ __forceinline__ int tq_forward(int d[16], const TqConst& K, uint32_t lvp[8])
+{
+    fdct4x4(d);
+    int l[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int cls = ((i & 1) & ((i >> 2) & 1)) ? 1 : (((i & 1) | ((i >> 2) & 1)) ? 2 : 0);
+        l[i] = quant_signed(d[i], K.mf[cls], K.f, K.c, K.q);
+    }
+    constexpr int ZZ[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
+    uint32_t cnt2 = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t p = ((uint32_t)l[ZZ[2 * k]] & 0xFFFFu) | ((uint32_t)l[ZZ[2 * k + 1]] << 16);
+        lvp[k] = p;
+        const uint32_t t = p | ((p & 0x7FFF7FFFu) + 0x7FFF7FFFu);
+        cnt2 += (t >> 15) & 0x00010001u;
+    }
+    return (int)((cnt2 & 0xFFFFu) + (cnt2 >> 16));
+}
+__device__ __forceinline__ void tq_inverse(const uint32_t lvp[8], const TqConst& K, int d[16])
+{
+    constexpr int ZZ[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        d[ZZ[2 * k]] = (int)(lvp[k] << 16) >> 16;
+        d[ZZ[2 * k + 1]] = (int)lvp[k] >> 16;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int cls = ((i & 1) & ((i >> 2) & 1)) ? 1 : (((i & 1) | ((i >> 2) & 1)) ? 2 : 0);
+        d[i] = __mul24(d[i], K.dq[cls]);
+    }
+    idct4x4(d);
+}
+
 // prediction row (4 samples in one word) + decoded residual -> reconstructed samples, clipped
 __device__ __forceinline__ uint32_t recon4(uint32_t pred, int r0, int r1, int r2, int r3)
 {
@@ -98,23 +161,23 @@ __device__ __forceinline__ void tq_chroma8(const FrameParams& P, const int first
         const int m8 = lane >> 3, pl = (lane >> 2) & 1, cb = lane & 3, mbi = first + m8;
         bool act = mbi < end;
         if (act) act = mb_to_code(*(const uint16_t*)((const uint8_t*)P.mb + (uint32_t)(mbi * 32 + 4)));
-        int cnz = 0, ldc = 0, bb = 0;
+        int cnz = 0, ldc = 0, bb = 0, dcs = 0;   // dcs: the scaled DC term, input 0 of the block's inverse transform
+        uint8_t* const cplane = pl ? P.rec[2] : P.rec[1];
+        uint32_t p4[4], po[4], lvp[8];
+        int d[16];
         if (act) {
             const int my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
             const int x = 8 * mx + 4 * (cb & 1), y = 8 * my + 4 * (cb >> 1);
-            uint8_t* const cplane = pl ? P.rec[2] : P.rec[1];
-            uint32_t s4[4], p4[4], po[4];
+            uint32_t s4[4];
             po[0] = (uint32_t)__mul24(y, cs) + (uint32_t)x;
 #pragma unroll
             for (int r = 1; r < 4; r++) po[r] = po[r - 1] + (uint32_t)csv;
 #pragma unroll
             for (int r = 0; r < 4; r++) { p4[r] = *(const uint32_t*)(cplane + po[r]); s4[r] = src_chroma4(P, pl, x, y + r); }
-            int d[16];
 #pragma unroll
             for (int r = 0; r < 4; r++)
 #pragma unroll
                 for (int c = 0; c < 4; c++) d[4 * r + c] = (int)((s4[r] >> (8 * c)) & 255u) - (int)((p4[r] >> (8 * c)) & 255u);
-            uint32_t lvp[8];
             // 8.5.11: the four DC terms of the plane (one per lane of the quad) through the 2x2 Hadamard, quantised at q + 1 with
             // offset 2f, transformed back and scaled; lane cb keeps output cb of both transforms
             const int sg1 = (cb & 1) ? -1 : 1, sg2 = (cb & 2) ? -1 : 1;
@@ -126,18 +189,29 @@ __device__ __forceinline__ void tq_chroma8(const FrameParams& P, const int first
             cnz = tq_block<true>(d, K, lvp, [&](int w0) {
                 const int fd = had2x2(w0);
                 ldc = quant_signed(fd, K.mf[0], 2 * K.f, 2 * K.c + 1, K.q + 1);   // 2^(q+1) - 1 - 2 (2f) = 2 c + 1
-                return (had2x2(ldc) * 16 * K.dq[0]) >> 5;
+                return dcs = (had2x2(ldc) * 16 * K.dq[0]) >> 5;
             });
             bb = blk_bits_bound_packed(lvp, cnz);
-            const uint32_t lb = (uint32_t)__mul24(mbi, LV_STRIDE * 2), lo = lb + (uint32_t)((LV_CHROMA_AC + (pl * 4 + cb) * 16) * 2);
-            *(uint4*)((uint8_t*)P.levels + lo) = make_uint4(lvp[0], lvp[1], lvp[2], lvp[3]);
-            *(uint4*)((uint8_t*)P.levels + lo + 16u) = make_uint4(lvp[4], lvp[5], lvp[6], lvp[7]);
-            *(int16_t*)((uint8_t*)P.levels + lb + (uint32_t)((LV_CHROMA_DC + pl * 4 + cb) * 2)) = (int16_t)ldc;
-#pragma unroll
-            for (int r = 0; r < 4; r++) *(uint32_t*)(cplane + po[r]) = recon4(p4[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]);
-            *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 24 + pl * 4 + cb)) = (uint8_t)cnz;   // MbInfo.tc[16 + plane * 4 + block]
         }
         const unsigned long long acm = __ballot(cnz != 0), dcm = __ballot(ldc != 0);
+        // chroma part of coded_block_pattern of this lane's macroblock (its eight lanes agree)
+        const int cbpc = ((acm >> (8 * m8)) & 255ull) ? 2 : (((dcm >> (8 * m8)) & 255ull) ? 1 : 0);
+        // Only what a later stage reads is stored (the header comment): AC levels where the pattern says 2, DC levels where it says
+        // 1 or 2; the samples where the inverse transform had a non-zero input (with none the prediction IS the reconstruction);
+        // the TotalCoeff byte where it is not the 0 that k_me wrote for this picture (tc invariant, header comment)
+        if (act) {
+            const uint32_t lb = (uint32_t)__mul24(mbi, LV_STRIDE * 2), lo = lb + (uint32_t)((LV_CHROMA_AC + (pl * 4 + cb) * 16) * 2);
+            if (cbpc == 2) {
+                *(uint4*)((uint8_t*)P.levels + lo) = make_uint4(lvp[0], lvp[1], lvp[2], lvp[3]);
+                *(uint4*)((uint8_t*)P.levels + lo + 16u) = make_uint4(lvp[4], lvp[5], lvp[6], lvp[7]);
+            }
+            if (cbpc) *(int16_t*)((uint8_t*)P.levels + lb + (uint32_t)((LV_CHROMA_DC + pl * 4 + cb) * 2)) = (int16_t)ldc;
+            if ((cnz | dcs) != 0) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) *(uint32_t*)(cplane + po[r]) = recon4(p4[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]);
+            }
+            if (cnz) *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 24 + pl * 4 + cb)) = (uint8_t)cnz;   // MbInfo.tc[16 + plane * 4 + block]
+        }
         // bit bound of the macroblock: its 8 chroma AC blocks + the two DC blocks (four lanes of a quad each) + the luma part
         unsigned long long pcm;
         {
@@ -153,7 +227,6 @@ __device__ __forceinline__ void tq_chroma8(const FrameParams& P, const int first
             pcm = __ballot(act && (lane & 7) == 0 && MB_HEADER_BOUND + csum + ybnd > MB_BITS_LIMIT);
         }
         if (act && (lane & 7) == 0) {
-            const int cbpc = ((acm >> (8 * m8)) & 255ull) ? 2 : (((dcm >> (8 * m8)) & 255ull) ? 1 : 0);
             *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 7)) = (uint8_t)(cbpl | (cbpc << 4));   // MbInfo.cbp
             if (t8 && cbpl) *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 5)) = 1;                  // transform_size_8x8_flag
         }
@@ -204,12 +277,13 @@ __global__ __launch_bounds__(64) void k_tq(FrameParams P0)
             // MbInfo.type == MB_P16 and i16_mode == 0 (k_me sets i16_mode when nothing is left to code, type MB_I16 for the intra pass)
             if (act) act = mb_to_code(*(const uint16_t*)((const uint8_t*)P.mb + (uint32_t)(mbi * 32 + 4)));
             int nz = 0, bb = 0;
+            // one 32-bit offset per access from a wave-uniform base (global_load saddr form: no 64-bit address arithmetic)
+            uint32_t p4[4], po[4], lvp[8];
+            int d[16];
             if (act) {
                 const int my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
                 const int x = 16 * mx + 4 * blk_x(blk), y = 16 * my + 4 * blk_y(blk);
-                uint32_t s4[4], p4[4];
-                // one 32-bit offset per access from a wave-uniform base (global_load saddr form: no 64-bit address arithmetic)
-                uint32_t po[4];
+                uint32_t s4[4];
                 po[0] = (uint32_t)__mul24(y, P.cw) + (uint32_t)x;
 #pragma unroll
                 for (int r = 1; r < 4; r++) po[r] = po[r - 1] + (uint32_t)cwv;
@@ -226,22 +300,28 @@ __global__ __launch_bounds__(64) void k_tq(FrameParams P0)
                         s4[r] = (uint32_t)src_px(P.src, P.w, P.h, x, y + r) | ((uint32_t)src_px(P.src, P.w, P.h, x + 1, y + r) << 8) |
                                 ((uint32_t)src_px(P.src, P.w, P.h, x + 2, y + r) << 16) | ((uint32_t)src_px(P.src, P.w, P.h, x + 3, y + r) << 24);
                 }
-                int d[16];
 #pragma unroll
                 for (int r = 0; r < 4; r++)
 #pragma unroll
                     for (int c = 0; c < 4; c++) d[4 * r + c] = (int)((s4[r] >> (8 * c)) & 255u) - (int)((p4[r] >> (8 * c)) & 255u);
-                uint32_t lvp[8];
                 nz = tq_block<false>(d, K, lvp, [](int) { return 0; });
                 bb = blk_bits_bound_packed(lvp, nz);
-                const uint32_t lo = (uint32_t)__mul24(mbi, LV_STRIDE * 2) + (uint32_t)((LV_LUMA + blk * 16) * 2);
-                *(uint4*)((uint8_t*)P.levels + lo) = make_uint4(lvp[0], lvp[1], lvp[2], lvp[3]);
-                *(uint4*)((uint8_t*)P.levels + lo + 16u) = make_uint4(lvp[4], lvp[5], lvp[6], lvp[7]);
-#pragma unroll
-                for (int r = 0; r < 4; r++) *(uint32_t*)(P.rec[0] + po[r]) = recon4(p4[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]);
-                *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + blk)) = (uint8_t)nz;   // MbInfo.tc[blk]
             }
             ymask[p] = __ballot(nz != 0);
+            // the sparse stores of the other layout (below): lane = 16 macroblock + blkIdx, and the four blocks of an 8x8 quadrant are
+            // blkIdx 4 q .. 4 q + 3 - the four ballot bits from lane & 0x3C on
+            if (act) {
+                if ((unsigned)(ymask[p] >> (lane & 0x3C)) & 0xFu) {
+                    const uint32_t lo = (uint32_t)__mul24(mbi, LV_STRIDE * 2) + (uint32_t)((LV_LUMA + blk * 16) * 2);
+                    *(uint4*)((uint8_t*)P.levels + lo) = make_uint4(lvp[0], lvp[1], lvp[2], lvp[3]);
+                    *(uint4*)((uint8_t*)P.levels + lo + 16u) = make_uint4(lvp[4], lvp[5], lvp[6], lvp[7]);
+                }
+                if (nz) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) *(uint32_t*)(P.rec[0] + po[r]) = recon4(p4[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]);
+                    *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + blk)) = (uint8_t)nz;   // MbInfo.tc[blk]
+                }
+            }
             ybound[p] = row_sum16_dpp(bb);
         }
     }
@@ -267,16 +347,22 @@ __global__ __launch_bounds__(64) void k_tq(FrameParams P0)
     {
         const TqConst K = tq_consts(P.qy);
         const int my = P.mbdiv.row(act ? mbi : mb0), mx = (act ? mbi : mb0) - my * P.mbw;
+        uint32_t p4s[2][4], lvs[2][8], po0 = 0;
+        int nzs[2] = {0, 0};
 #pragma unroll
         for (int p = 0; p < 2; p++) {
             const int byl = 2 * p + by2, blk = xy2blk(bxl, byl);
-            int nz = 0, bb = 0;
+            int nz = 0;
+            // one 32-bit offset per access from a wave-uniform base (global_load saddr form: no 64-bit address arithmetic)
+            uint32_t* const p4 = p4s[p];
+            uint32_t* const lvp = lvs[p];
+            uint32_t po[4];
+            int d[16];
             if (act) {
                 const int x = 16 * mx + 4 * bxl, y = 16 * my + 4 * byl;
-                uint32_t s4[4], p4[4];
-                // one 32-bit offset per access from a wave-uniform base (global_load saddr form: no 64-bit address arithmetic)
-                uint32_t po[4];
+                uint32_t s4[4];
                 po[0] = (uint32_t)__mul24(y, P.cw) + (uint32_t)x;
+                if (p == 0) po0 = po[0];
 #pragma unroll
                 for (int r = 1; r < 4; r++) po[r] = po[r - 1] + (uint32_t)cwv;
 #pragma unroll
@@ -292,24 +378,55 @@ __global__ __launch_bounds__(64) void k_tq(FrameParams P0)
                         s4[r] = (uint32_t)src_px(P.src, P.w, P.h, x, y + r) | ((uint32_t)src_px(P.src, P.w, P.h, x + 1, y + r) << 8) |
                                 ((uint32_t)src_px(P.src, P.w, P.h, x + 2, y + r) << 16) | ((uint32_t)src_px(P.src, P.w, P.h, x + 3, y + r) << 24);
                 }
-                int d[16];
 #pragma unroll
                 for (int r = 0; r < 4; r++)
 #pragma unroll
                     for (int c = 0; c < 4; c++) d[4 * r + c] = (int)((s4[r] >> (8 * c)) & 255u) - (int)((p4[r] >> (8 * c)) & 255u);
-                uint32_t lvp[8];
-                nz = tq_block<false>(d, K, lvp, [](int) { return 0; });
-                bb = blk_bits_bound_packed(lvp, nz);
+                nz = tq_forward(d, K, lvp);
+            }
+            nzs[p] = nz;
+            ymask[p] = __ballot(nz != 0);
+            // Only what a later stage reads is stored (the header comment).  The levels of all four blocks of an 8x8 quadrant that has
+            // a non-zero block - the bit that becomes coded_block_pattern below; the macroblock's lanes are bits 8 m8 .. 8 m8 + 7 of
+            // the ballot, bit = block row of the pass * 4 + block column, so the quadrant of this lane is columns (bxl & 2), (bxl & 2) + 1
+            // of both rows: 0x33 << (bxl & 2), and 8 m8 + (bxl & 2) = lane & 0x3A
+            if (act && ((unsigned)(ymask[p] >> (lane & 0x3A)) & 0x33u)) {
                 const uint32_t lo = (uint32_t)__mul24(mbi, LV_STRIDE * 2) + (uint32_t)((LV_LUMA + blk * 16) * 2);
                 *(uint4*)((uint8_t*)P.levels + lo) = make_uint4(lvp[0], lvp[1], lvp[2], lvp[3]);
                 *(uint4*)((uint8_t*)P.levels + lo + 16u) = make_uint4(lvp[4], lvp[5], lvp[6], lvp[7]);
-#pragma unroll
-                for (int r = 0; r < 4; r++) *(uint32_t*)(P.rec[0] + po[r]) = recon4(p4[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]);
-                *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + blk)) = (uint8_t)nz;   // MbInfo.tc[blk]
             }
-            ymask[p] = __ballot(nz != 0);
-            ybnd += group_sum8_dpp(bb);
         }
+        // The second stage (scaling, inverse transform, reconstruction, bit bound), once per wave: a lane takes whichever of its two
+        // blocks has a level, from the packed levels and the prediction words both passes kept; a second time only when some lane
+        // has two, not at all when no lane has one (wave-uniform).  It stores the samples and the TotalCoeff byte of a block that
+        // has a level: with none the inverse transform returns zeros and the prediction IS the reconstruction, the byte is the 0
+        // that k_me wrote for this picture (tc invariant, header comment), and the bit bound is the constant 6 of an empty block
+        // (blk_bits_bound_packed).  Pass 1's block lies eight picture rows below pass 0's
+        int bb = (nzs[0] ? 0 : 6) + (nzs[1] ? 0 : 6);
+        const bool has0 = nzs[0] != 0, has1 = nzs[1] != 0;
+        auto second = [&](const bool take1, const bool on) {
+            if (on) {
+                uint32_t L[8], Pp[4];
+#pragma unroll
+                for (int k = 0; k < 8; k++) L[k] = take1 ? lvs[1][k] : lvs[0][k];
+#pragma unroll
+                for (int r = 0; r < 4; r++) Pp[r] = take1 ? p4s[1][r] : p4s[0][r];
+                const int nz = take1 ? nzs[1] : nzs[0];
+                int d[16];
+                tq_inverse(L, K, d);
+                uint32_t o = po0 + (take1 ? 8u * (uint32_t)cwv : 0u);
+#pragma unroll
+                for (int r = 0; r < 4; r++) { *(uint32_t*)(P.rec[0] + o) = recon4(Pp[r], d[4 * r], d[4 * r + 1], d[4 * r + 2], d[4 * r + 3]); o += (uint32_t)cwv; }
+                const int blk = xy2blk(bxl, (take1 ? 2 : 0) + by2);
+                *((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + blk)) = (uint8_t)nz;   // MbInfo.tc[blk]
+                bb += blk_bits_bound_packed(L, nz);
+            }
+        };
+        if (__ballot(has0 | has1)) {
+            second(!has0, has0 | has1);
+            if (__ballot(has0 & has1)) second(true, has0 & has1);
+        }
+        ybnd = group_sum8_dpp(bb);
     }
 
     // ---- chroma of the 8 macroblocks + coded_block_pattern + I_PCM fallback (the same lanes hold the same macroblock) ----
@@ -446,11 +563,14 @@ __global__ __launch_bounds__(64) void k_tq8(FrameParams P0)
                 bb += blk_bits_bound_packed(lvp + 8 * k, tcs[k]);
                 nzany |= tcs[k];
             }
-            const uint32_t lo = (uint32_t)__mul24(mbi, LV_STRIDE * 2) + (uint32_t)((LV_LUMA + b8 * 64) * 2);
+            // the lane's block IS an 8x8 quadrant.  One without levels has its coded_block_pattern bit clear, so nobody reads its four
+            // lists; its four TotalCoeff bytes are the zeros that k_me wrote for this picture (tc invariant, header comment); and it
+            // reconstructs to the prediction: nothing to store
+            if (nzany) {
+                const uint32_t lo = (uint32_t)__mul24(mbi, LV_STRIDE * 2) + (uint32_t)((LV_LUMA + b8 * 64) * 2);
 #pragma unroll
-            for (int j = 0; j < 8; j++) *(uint4*)((uint8_t*)P.levels + lo + 16u * j) = make_uint4(lvp[4 * j], lvp[4 * j + 1], lvp[4 * j + 2], lvp[4 * j + 3]);
-            *(uint32_t*)((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + 4 * b8)) = (uint32_t)tcs[0] | ((uint32_t)tcs[1] << 8) | ((uint32_t)tcs[2] << 16) | ((uint32_t)tcs[3] << 24);   // MbInfo.tc[4 b8 ..]
-            if (nzany) {   // (an 8x8 block without levels reconstructs to the prediction: nothing to store)
+                for (int j = 0; j < 8; j++) *(uint4*)((uint8_t*)P.levels + lo + 16u * j) = make_uint4(lvp[4 * j], lvp[4 * j + 1], lvp[4 * j + 2], lvp[4 * j + 3]);
+                *(uint32_t*)((uint8_t*)P.mb + (uint32_t)(mbi * 32 + 8 + 4 * b8)) = (uint32_t)tcs[0] | ((uint32_t)tcs[1] << 8) | ((uint32_t)tcs[2] << 16) | ((uint32_t)tcs[3] << 24);   // MbInfo.tc[4 b8 ..]
 #pragma unroll
                 for (int r = 0; r < 8; r++) idct8_line<1>(d + 8 * r);
 #pragma unroll
