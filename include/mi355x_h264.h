@@ -373,6 +373,56 @@ int mi355x_h264_stream_debug_last_step(const mi355x_h264_stream *s, uint64_t *se
 int mi355x_h264_stream_hub_stats(const mi355x_h264_stream *s, uint64_t *steps, uint64_t *pictures, uint64_t *max_batch,
                                  int *open_streams);
 
+/* ---- colour description (tests/colour.py restates it; tests/test_colour_oracle.py checks the claims over the whole cube) ----
+ * Which matrix and which range the samples of a stream have, chosen by the caller and written into the sequence parameter set's
+ * VUI.  A stream opened without a description (every call above) is BT.601 studio swing as stated at mi355x_h264_encode_rgba and
+ * says nothing: its SPS has vui_parameters_present_flag = 0 and stays bit for bit what it was.
+ * RGBA ingest, four variants of one form (r, g, b: the rounded 2x2 means; every result clipped to 0..255):
+ *   Y = ((a R + b G + c B + 128) >> 8) + o,  Cb, Cr = ((d r + e g + f b + 128) >> 8) + 128
+ *     variant          Y (a, b, c, o)      Cb (d, e, f)      Cr (d, e, f)
+ *     BT.601 limited   66, 129, 25, 16     -38, -74, 112     112,  -94, -18     (the undescribed arithmetic, unchanged)
+ *     BT.709 limited   47, 157, 16, 16     -26, -86, 112     112, -102, -10
+ *     BT.601 full      77, 150, 29,  0     -43, -85, 128     128, -107, -21
+ *     BT.709 full      54, 183, 19,  0     -29, -99, 128     128, -116, -12
+ * Every chroma row sums to 0 (grey gives 128, 128); the limited forms stay inside 16..235 / 16..240 without the clip; the full
+ * forms reach 256 in chroma (and nothing else leaves 0..255), so the clip is needed there.
+ * The way out (the decoder's RGBA layout, include/mi355x_h264_dec.h) has the matching four:
+ *   c = m (Y - o), d = U - 128, e = V - 128,
+ *   R = clip255((c + rv e + 128) >> 8), G = clip255((c + gu d + gv e + 128) >> 8), B = clip255((c + bu d + 128) >> 8)
+ *     variant          m, o      rv    gu, gv        bu
+ *     BT.601 limited   298, 16   409   -100, -208    516
+ *     BT.709 limited   298, 16   459    -55, -136    541
+ *     BT.601 full      256,  0   359    -88, -183    454
+ *     BT.709 full      256,  0   403    -48, -120    475
+ * The VUI of a described stream, in order: no aspect ratio, no overscan; video_signal_type (video_format 5, video_full_range_flag,
+ * colour_primaries / transfer_characteristics 1 / 1 for BT.709 and 6 / 6 for BT.601, matrix_coefficients = matrix);
+ * chroma_loc_info (both types 1: the 2x2 mean makes centre-sited chroma) for streams of RGBA input only; timing_info
+ * (num_units_in_tick 1, time_scale 2 * fps, fixed_frame_rate_flag 1); no HRD, no pic_struct; bitstream_restriction (vectors over
+ * picture boundaries 1, both denominators 0, both log2_max_mv_length 16, max_num_reorder_frames 0, max_dec_frame_buffering = the
+ * number of reference pictures).
+ * For RGBA input the description selects the conversion; for I420 and NV12 input it only says what the caller's samples are, and
+ * no sample is touched. */
+enum { MI355X_H264_MATRIX_BT709 = 1, MI355X_H264_MATRIX_BT601 = 6 };   /* matrix_coefficients, Table E-5 */
+typedef struct mi355x_h264_colour {
+    uint32_t struct_size;   /* sizeof(mi355x_h264_colour) */
+    int32_t matrix;         /* MI355X_H264_MATRIX_BT709 or MI355X_H264_MATRIX_BT601 */
+    int32_t full_range;     /* 0: studio swing, 1: full range */
+} mi355x_h264_colour;
+/* mi355x_h264_stream_open_scaled plus the description.  A null description gives exactly the mi355x_h264_stream_open_scaled
+ * stream, on its engine.  Streams share an engine only with streams of the same description, and a described stream never shares
+ * one with an undescribed stream, even where both are BT.601 limited: their parameter sets differ.  Refused with MI355X_H264_E_ARG
+ * before the device is touched: a matrix other than the two above, full_range outside 0 / 1, a wrong struct_size, and everything
+ * mi355x_h264_stream_open_scaled refuses.  The description of an open stream cannot be changed. */
+int mi355x_h264_stream_open_colour(const mi355x_h264_config *cfg, uint32_t flags, int src_width, int src_height,
+                                   const mi355x_h264_colour *colour, mi355x_h264_stream **out);
+/* mi355x_h264_create plus the description (a null one: exactly mi355x_h264_create).  mi355x_h264_encode_rgba(_device) converts with
+ * the described variant.  The layout of an encoder's pictures is the call's, not the handle's, so its VUI carries no chroma_loc_info. */
+int mi355x_h264_create_colour(const mi355x_h264_config *cfg, const mi355x_h264_colour *colour, mi355x_h264_encoder **out);
+/* the description the handle was opened with: returns 1 and fills *out, or 0 (undescribed; *out is BT.601 limited, what the
+ * conversion then is), or MI355X_H264_E_ARG for a null argument */
+int mi355x_h264_stream_colour(const mi355x_h264_stream *s, mi355x_h264_colour *out);
+int mi355x_h264_colour_of(const mi355x_h264_encoder *enc, mi355x_h264_colour *out);
+
 /* per-kernel device time accumulated since the last reset, measured with HIP
  * events on the encoder's own stream */
 enum {

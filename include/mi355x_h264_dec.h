@@ -75,7 +75,8 @@ typedef struct {
     int32_t width, height;         /* cropped size */
     int32_t stride, chroma_stride; /* bytes per row (chroma_stride: I420 U / V rows, NV12 / NV21 pair rows; 0 for RGBA) */
     int32_t fresh;                 /* 1: decoded in the step the output belongs to */
-    int32_t reserved;
+    int32_t colour;                /* RGBA: matrix | full_range << 8 of the conversion that was applied to the picture (below, "colour"); 0 for
+                                    * the other layouts.  (The struct keeps its size: this was a reserved field, always 0.) */
     int64_t serial;                /* that step's serial number (mi355x_h264_dec_group_last_step out[0]; single decoder: pictures decoded) */
 } mi355x_h264_dec_out_pic;
 /* the last decoded picture in `layout`.  dst == NULL: fills *pic and returns the bytes needed without touching the GPU.  to_device:
@@ -83,6 +84,28 @@ typedef struct {
  * caller's work on dst must be complete; the call returns when the picture is there.  Returns the bytes used or < 0 (E_ARG: layout, row_align, cap too small, no picture yet) */
 int64_t mi355x_h264_dec_read(mi355x_h264_decoder *dec, int layout, int row_align, void *dst, size_t cap, int to_device,
                              mi355x_h264_dec_out_pic *pic);
+
+/* ---- colour: what the stream says about its samples, and which conversion the RGBA layout applies ----
+ * The parser reads the VUI of every sequence parameter set (E.1.1: aspect ratio with Extended_SAR, overscan, video signal type,
+ * chroma location, timing, both HRD parameter sets, pic_struct, bitstream restriction).  No field of it is needed to decode samples,
+ * so a VUI that is damaged, truncated or out of range NEVER refuses the stream: its fields count as absent, all of them, and the
+ * pictures decode as they do without it.
+ * mi355x_h264_dec_colour: out[8] for the sequence parameter set the last decoded picture was coded under (E_ARG before the first):
+ *   out[0] 1 = a colour description is present, else 0;  out[1] matrix_coefficients, out[2] video_full_range_flag, out[3]
+ *   colour_primaries, out[4] transfer_characteristics (2 = unspecified, 0 for the flag, where the stream does not say);
+ *   out[5] chroma_sample_loc_type_top_field 0..5, or -1;  out[6] pictures per second, time_scale / (2 * num_units_in_tick) rounded,
+ *   or 0;  out[7] max_num_reorder_frames, or -1 (0: every picture may be handed out as soon as it is decoded).
+ * RGBA output applies the variant the stream describes - the four sets of mi355x_h264.h, "colour description" - when its
+ * matrix_coefficients are 1 (BT.709), 5 or 6 (both: the BT.601 numbers), with the range its video_full_range_flag names.  Every
+ * other stream, one without a description included, gets BT.601 limited as stated above.  A group's launch serves streams of
+ * different descriptions at once: the variant belongs to the picture, not to the launch.
+ * mi355x_h264_dec_set_rgba_colour overrides that for the handle's (the group form: the stream's) pictures from the next read or armed
+ * step on, whatever the stream says; NULL: follow the stream again.  E_ARG: a matrix other than MI355X_H264_MATRIX_BT709 / _BT601,
+ * full_range outside 0 / 1, a wrong struct_size, no such stream.
+ * mi355x_h264_dec_out_pic.colour names the variant that WAS applied: MI355X_H264_MATRIX_* | full_range << 8 (a stream that says 5 is
+ * reported as 6, whose numbers it got). */
+int mi355x_h264_dec_colour(const mi355x_h264_decoder *dec, int32_t out[8]);
+int mi355x_h264_dec_set_rgba_colour(mi355x_h264_decoder *dec, const mi355x_h264_colour *colour);
 
 /* ---- decoder groups: the next pictures of up to 64 streams reconstructed in ONE step ----
  * One decoder object per stream costs each picture its own uploads and five to eight launches that fill a fraction of the GPU.  A
@@ -107,6 +130,8 @@ int mi355x_h264_dec_group_sync(mi355x_h264_dec_group *g);
 const char *mi355x_h264_dec_group_last_error(const mi355x_h264_dec_group *g, int stream);
 /* the stream's last decoded picture: as the single decoder's calls of these names */
 int mi355x_h264_dec_group_picture_info(const mi355x_h264_dec_group *g, int stream, int *w, int *h, int *cw, int *ch);
+int mi355x_h264_dec_group_colour(const mi355x_h264_dec_group *g, int stream, int32_t out[8]);
+int mi355x_h264_dec_group_set_rgba_colour(mi355x_h264_dec_group *g, int stream, const mi355x_h264_colour *colour);
 int64_t mi355x_h264_dec_group_read_i420(mi355x_h264_dec_group *g, int stream, uint8_t *dst, size_t cap);
 int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group *g, int stream, void *d_dst, size_t cap);
 int64_t mi355x_h264_dec_group_debug_plane(mi355x_h264_dec_group *g, int stream, int plane, void *dst, size_t cap);
@@ -175,6 +200,10 @@ int mi355x_h264_parser_info(const mi355x_h264_parser *p, int32_t *out, int n);
  * 7 neighbour availability (1 B: bits 0..3 the left, above, above-right, above-left macroblock lies in this slice and was decoded
  *   before; bits 4..7 it may also be used for intra prediction: constrained_intra_pred_flag) */
 int64_t mi355x_h264_parser_read(const mi355x_h264_parser *p, int what, void *dst, size_t cap);
+/* out[8] of mi355x_h264_dec_colour for the sequence parameter set the last slice referred to (before the first: set 0, absent
+ * fields); with n >= 10 also out[8] 1 = the set has a VUI that was read whole and in range, out[9] max_dec_frame_buffering or -1.
+ * Returns the number of values written, or -1 */
+int mi355x_h264_parser_colour(const mi355x_h264_parser *p, int32_t *out, int n);
 
 #ifdef __cplusplus
 }

@@ -38,10 +38,14 @@ EXPORTS = [
     "mi355x_h264_debug_mem_guard", "mi355x_h264_debug_mem_guard_get", "mi355x_h264_debug_mem_tally", "mi355x_h264_debug_mem_check",
     "mi355x_h264_debug_mem_poke", "mi355x_h264_stream_debug_mem_check", "mi355x_h264_dec_debug_mem_check",
     "mi355x_h264_dec_group_debug_mem_check", "mi355x_h264_dec_group_debug_mem_poke",
+    "mi355x_h264_create_colour", "mi355x_h264_stream_open_colour", "mi355x_h264_colour_of", "mi355x_h264_stream_colour",
+    "mi355x_h264_dec_colour", "mi355x_h264_dec_set_rgba_colour", "mi355x_h264_dec_group_colour", "mi355x_h264_dec_group_set_rgba_colour",
+    "mi355x_h264_parser_colour",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
 STREAM_MULTIREF = 1   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
+MATRIX_BT709, MATRIX_BT601 = 1, 6   # MI355X_H264_MATRIX_* (matrix_coefficients, Table E-5)
 
 
 class Config(C.Structure):
@@ -49,6 +53,33 @@ class Config(C.Structure):
                 ("bitrate", C.c_int32), ("gop", C.c_int32), ("profile_idc", C.c_int32), ("rc_mode", C.c_int32),
                 ("qp", C.c_int32), ("device", C.c_int32), ("disable_deblock", C.c_int32),
                 ("batch", C.c_int32), ("input_format", C.c_int32), ("slices", C.c_int32), ("band_index", C.c_int32), ("band_count", C.c_int32), ("refs", C.c_int32), ("search", C.c_int32)]
+
+
+class Colour(C.Structure):
+    """mi355x_h264_colour"""
+    _fields_ = [("struct_size", C.c_uint32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
+
+
+def colour_struct(colour):
+    """a description as the C ABI takes it, from ("bt601" | "bt709", "limited" | "full"), from (matrix code, full_range) or from a
+    Colour; None stays None (no description)"""
+    if colour is None or isinstance(colour, Colour):
+        return colour
+    m, r = colour
+    m = {"bt709": MATRIX_BT709, "bt601": MATRIX_BT601}.get(m, m)
+    r = {"limited": 0, "full": 1}.get(r, r)
+    if isinstance(m, str) or isinstance(r, str):
+        raise ValueError("colour = %r: (\"bt601\" | \"bt709\", \"limited\" | \"full\")" % (colour,))
+    return Colour(C.sizeof(Colour), int(m), int(r))
+
+
+def _colour_read(fn, handle):
+    """what mi355x_h264_colour_of / _stream_colour report: ("bt709", "full"), or None for a handle without a description"""
+    c = Colour()
+    rc = fn(handle, C.byref(c))
+    if rc < 0:
+        raise EncoderError("colour read -> %d" % rc)
+    return ({MATRIX_BT709: "bt709", MATRIX_BT601: "bt601"}[c.matrix], "full" if c.full_range else "limited") if rc else None
 
 
 class Stats(C.Structure):
@@ -163,6 +194,11 @@ def lib():
             for name in ("mi355x_h264_debug_mem_poke", "mi355x_h264_dec_group_debug_mem_poke"):
                 getattr(L, name).argtypes = [vp, C.c_char_p, C.c_int64, C.c_int]
         L.mi355x_h264_stats_read.argtypes = [vp, C.POINTER(Stats), C.c_int]
+        if hasattr(L, "mi355x_h264_create_colour"):   # (an A/B library of an earlier build has no colour descriptions)
+            L.mi355x_h264_create_colour.argtypes = [C.POINTER(Config), C.POINTER(Colour), C.POINTER(vp)]
+            L.mi355x_h264_stream_open_colour.argtypes = [C.POINTER(Config), C.c_uint32, C.c_int, C.c_int, C.POINTER(Colour), C.POINTER(vp)]
+            L.mi355x_h264_colour_of.argtypes = [vp, C.POINTER(Colour)]
+            L.mi355x_h264_stream_colour.argtypes = [vp, C.POINTER(Colour)]
         _lib = L
     return _lib
 
@@ -250,7 +286,9 @@ class Encoder:
     """thin object wrapper; argument meaning follows mi355x_h264_config"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0,
-                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1):
+                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1, colour=None):
+        """colour = ("bt601" | "bt709", "limited" | "full"): the encoder is created with mi355x_h264_create_colour - its SPS carries
+        the description and encode_rgba converts with that variant; None: mi355x_h264_create"""
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
@@ -264,10 +302,15 @@ class Encoder:
         cfg.search = search                                       # 0 exhaustive integer search, 1 seeded by the previous picture's vector (the default)
         self.batch = batch
         self.h = C.c_void_p()
-        rc = L.mi355x_h264_create(C.byref(cfg), C.byref(self.h))
+        if colour is None:
+            rc = L.mi355x_h264_create(C.byref(cfg), C.byref(self.h))
+        else:
+            rc = L.mi355x_h264_create_colour(C.byref(cfg), C.byref(colour_struct(colour)), C.byref(self.h))
         if rc != 0:
             self.h = None
-            raise EncoderError("mi355x_h264_create failed: %d" % rc)
+            err = EncoderError("mi355x_h264_create%s failed: %d" % ("" if colour is None else "_colour", rc))
+            err.rc = rc
+            raise err
         self.width, self.height = width, height
         self.cw, self.ch = L.mi355x_h264_coded_width(self.h), L.mi355x_h264_coded_height(self.h)
         self.nmb = (self.cw // 16) * (self.ch // 16)
@@ -277,6 +320,11 @@ class Encoder:
             err = EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_last_error(self.h).decode()))
             err.rc = rc
             raise err
+
+    @property
+    def colour(self):
+        """the description the encoder was created with, ("bt709", "full") ..., or None"""
+        return _colour_read(lib().mi355x_h264_colour_of, self.h)
 
     def encode(self, i420, strides=None):
         """host I420 (numpy uint8, width*height*3/2) -> (bytes, frame_type); with strides = (y, u, v) in bytes, i420 is the
@@ -433,10 +481,12 @@ class Stream:
     input_format (INPUT_I420 / INPUT_NV12 / INPUT_RGBA) is the layout of every picture of the stream, from host or device memory.
     refs 2 / 3: that many reference pictures are searched; the stream is opened with mi355x_h264_stream_open_ex (as it is whenever
     `flags` is given: the flags of that call).  src_size = (SW, SH): a scaled stream (mi355x_h264_stream_open_scaled) - every encode
-    call takes pictures of SW x SH, which the device resamples to width x height; debug_read(DBG_SRC) is the resampled picture"""
+    call takes pictures of SW x SH, which the device resamples to width x height; debug_read(DBG_SRC) is the resampled picture.
+    colour = ("bt601" | "bt709", "limited" | "full"): a described stream (mi355x_h264_stream_open_colour; combines with src_size
+    and flags): its SPS carries the description, and RGBA pictures are converted with that variant"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
-                 input_format=0, refs=0, flags=None, src_size=None):
+                 input_format=0, refs=0, flags=None, src_size=None, colour=None):
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
@@ -447,7 +497,10 @@ class Stream:
         if flags is None and refs > 1:
             flags = STREAM_MULTIREF
         self.h = C.c_void_p()
-        if src_size is not None:
+        if colour is not None:
+            sw, sh = (width, height) if src_size is None else (int(src_size[0]), int(src_size[1]))
+            rc = L.mi355x_h264_stream_open_colour(C.byref(cfg), flags or 0, sw, sh, C.byref(colour_struct(colour)), C.byref(self.h))
+        elif src_size is not None:
             rc = L.mi355x_h264_stream_open_scaled(C.byref(cfg), flags or 0, int(src_size[0]), int(src_size[1]), C.byref(self.h))
         elif flags is None:
             rc = L.mi355x_h264_stream_open(C.byref(cfg), C.byref(self.h))
@@ -455,7 +508,7 @@ class Stream:
             rc = L.mi355x_h264_stream_open_ex(C.byref(cfg), flags, C.byref(self.h))
         if rc != 0:
             self.h = None
-            err = EncoderError("mi355x_h264_stream_open%s failed: %d" % ("_scaled" if src_size is not None else "" if flags is None else "_ex", rc))
+            err = EncoderError("mi355x_h264_stream_open%s failed: %d" % ("_colour" if colour is not None else "_scaled" if src_size is not None else "" if flags is None else "_ex", rc))
             err.rc = rc
             raise err
         self.width, self.height = width, height
@@ -498,6 +551,11 @@ class Stream:
 
     def last_error(self):
         return lib().mi355x_h264_stream_last_error(self.h).decode()
+
+    @property
+    def colour(self):
+        """the description the stream was opened with, ("bt709", "full") ..., or None"""
+        return _colour_read(lib().mi355x_h264_stream_colour, self.h)
 
     def source_size(self):
         """(width, height) of the pictures the calls take (mi355x_h264_stream_source_width / _height)"""

@@ -25,6 +25,8 @@ struct DecGroupStream {
     int width = 0, height = 0, crop_x = 0, crop_y = 0;
     uint64_t pictures = 0;
     int64_t last_serial = 0;   // serial number of the step that decoded its last picture
+    h264dec::Vui vui;    // of the sequence parameter set its last decoded picture was coded under (mi355x_h264_dec_colour)
+    int rgba_override = -1;   // mi355x_h264_dec_set_rgba_colour: the variant RGBA output applies whatever the stream says; -1: follow the stream
     // the step in hand
     const uint8_t* au = nullptr;
     size_t len = 0;
@@ -92,6 +94,18 @@ int env_int(const char* name, int lo, int hi, int dflt)
 }
 
 void dg_drop_refs(DecGroupStream& s) { s.have_refs = 0; s.parser.lose_refs(); }
+
+// The variant of the RGBA conversion a stream's pictures get (k_dec_out.h, DecOutPos.colour): the override if there is one, else
+// what the stream describes when its matrix_coefficients are 1 (BT.709), 5 or 6 (both have the BT.601 numbers); every other
+// stream, one without a description included, is BT.601 limited as before there were descriptions
+int dg_rgba_variant(const DecGroupStream& s)
+{
+    if (s.rgba_override >= 0) return s.rgba_override;
+    const h264dec::Vui& v = s.vui;
+    if (!v.present || !v.colour || (v.matrix != 1 && v.matrix != 5 && v.matrix != 6)) return 0;
+    return (v.matrix == 1 ? 1 : 0) | (v.full_range ? 2 : 0);
+}
+int dg_out_variant(const DecGroupStream& s, int layout) { return layout == DEC_OUT_RGBA ? dg_rgba_variant(s) : -1; }
 
 // the step in flight has finished; a wavefront that timed out leaves none of the step's pictures usable as a reference
 int dg_wait(mi355x_h264_dec_group* g)
@@ -307,6 +321,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         } catch (const std::exception&) { rc[i] = MI355X_H264_E_NOMEM; dg_drop_refs(s); continue; }
         s.width = pic.width; s.height = pic.height; s.crop_x = 2 * sps.crop_l; s.crop_y = 2 * sps.crop_t;
         s.max_refs = std::max(1, sps.max_refs);
+        s.vui = sps.vui;
         // the table row (dev_common.h DecPos)
         tab = outp ? (DecPos*)g->out.h_tabx[k] : g->h_tab[k];
         DecPos& T = tab[npos];
@@ -338,8 +353,8 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             const OutGeom geo = out_geom(g->out.layout, s.width, s.height, g->out.row_align);
             const size_t off = out_align(obytes, 256);
             otab[npos] = DecOutPos{(uint32_t)i, (uint32_t)s.cur, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
-                                   (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, 0ull};
-            g->out.pics[oset][i] = out_pic((int64_t)off, s.width, s.height, geo, 1, g->step_serial);
+                                   (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, (uint32_t)std::max(0, dg_out_variant(s, g->out.layout)), 0u};
+            g->out.pics[oset][i] = out_pic((int64_t)off, s.width, s.height, geo, 1, g->step_serial, dg_out_variant(s, g->out.layout));
             obytes = off + geo.bytes;
         }
         pos_stream[npos++] = i;
@@ -512,8 +527,8 @@ int64_t dg_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* d
         const OutGeom geo = out_geom(layout, s.width, s.height, row_align);
         const size_t off = out_align(total, 256);
         rows[n++] = DecOutPos{(uint32_t)i, (uint32_t)s.last, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
-                              (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, 0ull};
-        desc[i] = out_pic((int64_t)off, s.width, s.height, geo, s.last_serial == g->step_serial, g->step_serial);
+                              (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, (uint32_t)std::max(0, dg_out_variant(s, layout)), 0u};
+        desc[i] = out_pic((int64_t)off, s.width, s.height, geo, s.last_serial == g->step_serial, g->step_serial, dg_out_variant(s, layout));
         total = off + geo.bytes;
     }
     if (n == 0) return MI355X_H264_E_ARG;

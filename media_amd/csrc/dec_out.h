@@ -24,10 +24,13 @@ OutGeom out_geom(int layout, int w, int h, int row_align)
     else { g.stride = g.cstride = (int)out_align(w, a); g.bytes = (size_t)g.stride * h + (size_t)g.cstride * (h / 2); }
     return g;
 }
-mi355x_h264_dec_out_pic out_pic(int64_t off, int w, int h, const OutGeom& g, int fresh, int64_t serial)
+// variant: of the RGBA conversion that is applied to the picture (k_dec_out.h), -1 for the other layouts; the picture's `colour`
+// names it as matrix | full_range << 8 with the matrix code of the variant's numbers (6 for a stream that says 5)
+mi355x_h264_dec_out_pic out_pic(int64_t off, int w, int h, const OutGeom& g, int fresh, int64_t serial, int variant)
 {
     mi355x_h264_dec_out_pic p{};
     p.offset = off; p.width = w; p.height = h; p.stride = g.stride; p.chroma_stride = g.cstride; p.fresh = fresh; p.serial = serial;
+    p.colour = variant < 0 ? 0 : ((variant & 1) ? MI355X_H264_MATRIX_BT709 : MI355X_H264_MATRIX_BT601) | ((variant >> 1) << 8);
     return p;
 }
 mi355x_h264_dec_out_pic out_no_pic(int64_t serial) { mi355x_h264_dec_out_pic p{}; p.offset = -1; p.serial = serial; return p; }

@@ -69,6 +69,7 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     Slot slots[NSLOT];
     int next_slot = 0;
     StreamShape shape{};                     // what the parameter sets and slice headers are written from
+    ColourDesc colour;                       // the description the engine was created with (mi355x_h264_create_colour, the hub's); none: BT.601 limited, no VUI
     std::vector<uint8_t> sps_pps;            // Annex-B SPS + PPS NALs
     std::vector<std::vector<uint8_t>> esc_buf;  // slow path: escaped access unit, per batch item
     int idr_step = 1;                        // idr_pic_id stride between the batch items
@@ -705,9 +706,11 @@ hipError_t engine_alloc(mi355x_h264_encoder* e, bool hub_engine)
 
 // hub_engine: the engine of a stream hub (hub.h) - one set of output buffers instead of NSLOT, never more than one HIP stream
 // pair of its own (the hub's step contexts bring theirs)
-int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool hub_engine)
+// colour: the stream's description (null: none); chroma_loc: its VUI says where the chroma samples lie (a hub of RGBA input)
+int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool hub_engine, const ColourDesc* colour = nullptr, bool chroma_loc = false)
 {
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
+    if (colour && colour->described && !colour_valid(colour->matrix, colour->full_range)) return MI355X_H264_E_ARG;
     ask_for_hw_queues();   // (here, not only in the store's create: the device count below brings the runtime up)
     *out = nullptr;
     if (cfg->width < 16 || cfg->height < 16 || cfg->width > 4096 || cfg->height > 4096 || ((cfg->width | cfg->height) & 1) ||
@@ -747,7 +750,9 @@ int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool
     if (e->G > MAX_BATCH) { delete e; return MI355X_H264_E_ARG; }
     e->esc_buf.resize((size_t)e->G);
     e->last_me_cost.assign((size_t)e->G, 0);
-    e->shape = StreamShape{cfg->profile_idc, e->level_idc, e->nrefs, e->mbw, e->mbh, cfg->width, cfg->height, e->nsl, cfg->disable_deblock};
+    if (colour) e->colour = *colour;
+    e->shape = StreamShape{cfg->profile_idc, e->level_idc, e->nrefs, e->mbw, e->mbh, cfg->width, cfg->height, e->nsl, cfg->disable_deblock,
+                           e->colour.described, e->colour.matrix, e->colour.full_range, chroma_loc ? 1 : 0, cfg->fps > 0 ? cfg->fps : 30};
     e->sps_pps = build_parameter_sets(e->shape);
     e->diag_mode = getenv("MI355X_H264_DIAG") != nullptr && e->G == 1 && e->b_nsl == e->nsl;
     {
@@ -823,7 +828,7 @@ int encode_one_host(mi355x_h264_encoder* e, const HostPicture& in, int pieces, u
 int encode_rgba_from_device(mi355x_h264_encoder* e, const uint8_t* d_rgba, size_t stride, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
     const int w = e->cfg.width, h = e->cfg.height;
-    hipLaunchKernelGGL(k_rgba_to_i420, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(h / 2)), dim3(256), 0, e->stream, d_rgba, stride, e->d_stage, w, h);
+    launch_rgba_to_i420(e->colour.described ? colour_variant(e->colour.matrix, e->colour.full_range) : 0, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(h / 2)), e->stream, d_rgba, stride, e->d_stage, w, h);
     HIPCHK(e->err, hipGetLastError());
     return encode_one_device(e, e->d_stage, false, out, out_len, frame_type);
 }

@@ -39,8 +39,27 @@ struct MbRec {   // = dev_common.h MbInfo (32 bytes)
 };
 static_assert(sizeof(MbRec) == 32, "MbRec layout");
 
+// vui_parameters() of E.1.1, as far as a client of the decoder asks for it (mi355x_h264_dec_colour).  No field is needed to decode
+// samples: a VUI that is damaged, truncated or out of range counts as absent as a whole (present = false, every field at the value
+// below) and the stream decodes as one without
+struct Vui {
+    bool present = false;
+    bool colour = false;                    // colour_description_present_flag
+    int full_range = 0, primaries = 2, transfer = 2, matrix = 2;   // (2: unspecified)
+    int chroma_loc = -1;                    // chroma_sample_loc_type_top_field 0..5; -1: not signalled
+    uint32_t num_units_in_tick = 0, time_scale = 0;   // 0: no timing_info
+    int reorder = -1, dec_buffering = -1;   // max_num_reorder_frames, max_dec_frame_buffering; -1: no bitstream_restriction
+    // pictures per second of a stream of frames (a tick is a field): time_scale / (2 * num_units_in_tick) rounded; 0: not signalled
+    int fps() const
+    {
+        if (!num_units_in_tick || !time_scale) return 0;
+        const uint64_t f = ((uint64_t)time_scale + num_units_in_tick) / (2ull * num_units_in_tick);
+        return f > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)f;
+    }
+};
 struct Sps {
     bool valid = false;
+    Vui vui;
     int profile_idc = 0, level_idc = 0, log2_max_frame_num = 4, poc_type = 0, log2_max_poc_lsb = 4, max_refs = 1;
     int mbw = 0, mbh = 0, crop_l = 0, crop_r = 0, crop_t = 0, crop_b = 0;
     bool delta_pic_order_always_zero = false;
@@ -71,6 +90,7 @@ public:
     size_t pos() const { return pos_; }
     bool more_data() const { return pos_ < stop_; }
     bool aligned() const { return (pos_ & 7) == 0; }
+    bool past_stop() const { return pos_ > stop_; }   // bits were read from behind the payload's last bit (they read as trailing bits or 0)
     // The payload is followed by PAD zero bytes (the caller's buffer): eight bytes can be loaded at every position up to the
     // end, and bits past the end read as 0.
     enum { PAD = 8 };
@@ -345,11 +365,67 @@ private:
             if (cl + cr >= 8u * (unsigned)s.mbw || ct + cb >= 8u * (unsigned)s.mbh || cl > 4096 || cr > 4096 || ct > 4096 || cb > 4096) { fail("frame cropping larger than the picture"); return false; }
             s.crop_l = (int)cl; s.crop_r = (int)cr; s.crop_t = (int)ct; s.crop_b = (int)cb;
         }
-        // (vui_parameters are not needed to decode samples)
         if (br.bad()) { fail("sequence parameter set damaged"); return false; }
+        // vui_parameters are not needed to decode samples: read from a copy of the reader, and whatever is wrong with them leaves
+        // the parameter set as valid as it is without
+        if (br.more_data()) {
+            BitReader v = br;
+            if (v.u(1)) s.vui = parse_vui(v);
+        }
         s.valid = true;
         sps_[id] = s;
         return true;
+    }
+    // hrd_parameters() of E.1.2, skipped field by field; false: out of range
+    static bool skip_hrd(BitReader& br)
+    {
+        const unsigned cnt = br.ue();   // cpb_cnt_minus1
+        if (cnt > 31) return false;
+        br.u(4); br.u(4);               // bit_rate_scale, cpb_size_scale
+        for (unsigned k = 0; k <= cnt && !br.bad(); k++) { br.ue(); br.ue(); br.u(1); }   // bit_rate_value_minus1, cpb_size_value_minus1, cbr_flag
+        br.u(5); br.u(5); br.u(5); br.u(5);   // initial_cpb_removal_delay_length_minus1, cpb_removal_delay_length_minus1, dpb_output_delay_length_minus1, time_offset_length
+        return !br.bad();
+    }
+    // vui_parameters() of E.1.1 behind vui_parameters_present_flag = 1.  Returns the fields, or Vui() (present = false) when a value
+    // is outside its range or the syntax runs past the payload's last bit
+    static Vui parse_vui(BitReader& br)
+    {
+        Vui v;
+        if (br.u(1)) {   // aspect_ratio_info_present_flag
+            if (br.u(8) == 255) { br.u(16); br.u(16); }   // Extended_SAR: sar_width, sar_height
+        }
+        if (br.u(1)) br.u(1);   // overscan_info_present_flag, overscan_appropriate_flag
+        if (br.u(1)) {   // video_signal_type_present_flag
+            br.u(3);     // video_format
+            v.full_range = (int)br.u(1);
+            v.colour = br.u(1) != 0;
+            if (v.colour) { v.primaries = (int)br.u(8); v.transfer = (int)br.u(8); v.matrix = (int)br.u(8); }
+        }
+        if (br.u(1)) {   // chroma_loc_info_present_flag
+            const unsigned top = br.ue(), bottom = br.ue();
+            if (top > 5 || bottom > 5) return Vui();
+            v.chroma_loc = (int)top;
+        }
+        if (br.u(1)) {   // timing_info_present_flag
+            v.num_units_in_tick = br.u(32); v.time_scale = br.u(32);
+            br.u(1);     // fixed_frame_rate_flag
+            if (!v.num_units_in_tick || !v.time_scale) return Vui();
+        }
+        const bool nal_hrd = br.u(1) != 0;
+        if (nal_hrd && !skip_hrd(br)) return Vui();
+        const bool vcl_hrd = br.u(1) != 0;
+        if (vcl_hrd && !skip_hrd(br)) return Vui();
+        if (nal_hrd || vcl_hrd) br.u(1);   // low_delay_hrd_flag
+        br.u(1);         // pic_struct_present_flag
+        if (br.u(1)) {   // bitstream_restriction_flag
+            br.u(1);     // motion_vectors_over_pic_boundaries_flag
+            const unsigned bytes_denom = br.ue(), bits_denom = br.ue(), lh = br.ue(), lv = br.ue(), reorder = br.ue(), buffering = br.ue();
+            if (bytes_denom > 16 || bits_denom > 16 || lh > 16 || lv > 16 || buffering > 16 || reorder > buffering) return Vui();
+            v.reorder = (int)reorder; v.dec_buffering = (int)buffering;
+        }
+        if (br.bad() || br.past_stop()) return Vui();
+        v.present = true;
+        return v;
     }
     bool parse_pps(BitReader& br)
     {

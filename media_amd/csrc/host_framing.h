@@ -166,7 +166,46 @@ void fill_filter_thresholds(Db& D, int qp)
 }
 
 // what the parameter sets and slice headers of a stream depend on
-struct StreamShape { int profile_idc, level_idc, nrefs, mbw, mbh, width, height, nsl, disable_deblock; };
+// described: the stream carries a colour description (include/mi355x_h264.h, "colour description") and its SPS ends with a VUI;
+// matrix (1 BT.709, 6 BT.601), full_range, chroma_loc (streams of RGBA input: chroma_loc_info is written) and fps are its contents.
+// 0 (every undescribed stream): the SPS is what it was before there were descriptions
+struct StreamShape { int profile_idc, level_idc, nrefs, mbw, mbh, width, height, nsl, disable_deblock, described, matrix, full_range, chroma_loc, fps; };
+
+// A colour description as its owner keeps it, and the variant of the two conversions it selects: 0 BT.601 limited (what an
+// undescribed stream has), 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full
+struct ColourDesc { int described = 0, matrix = 6, full_range = 0; };
+inline bool colour_valid(int matrix, int full_range) { return (matrix == 1 || matrix == 6) && (full_range == 0 || full_range == 1); }
+inline int colour_variant(int matrix, int full_range) { return (matrix == 1 ? 1 : 0) | (full_range ? 2 : 0); }
+inline bool same_colour(const ColourDesc& a, const ColourDesc& b)
+{
+    return a.described == b.described && (!a.described || (a.matrix == b.matrix && a.full_range == b.full_range));
+}
+
+// vui_parameters() of E.1.1 for a described stream, behind vui_parameters_present_flag = 1
+inline void write_vui(HostBits& s, const StreamShape& f)
+{
+    s.put(1, 0);  // aspect_ratio_info_present_flag
+    s.put(1, 0);  // overscan_info_present_flag
+    s.put(1, 1);  // video_signal_type_present_flag
+    s.put(3, 5);  // video_format: unspecified
+    s.put(1, (uint32_t)f.full_range);
+    s.put(1, 1);  // colour_description_present_flag
+    const uint32_t prim = f.matrix == 1 ? 1 : 6;   // BT.709: 1 / 1 / 1; BT.601: 6 / 6 / 6
+    s.put(8, prim); s.put(8, prim); s.put(8, (uint32_t)f.matrix);
+    s.put(1, f.chroma_loc ? 1 : 0);   // chroma_loc_info_present_flag: the 2x2 mean of the RGBA ingest makes centre-sited chroma
+    if (f.chroma_loc) { s.ue(1); s.ue(1); }
+    s.put(1, 1);  // timing_info_present_flag
+    s.put(32, 1); s.put(32, 2u * (uint32_t)f.fps);   // num_units_in_tick, time_scale (a tick is a field)
+    s.put(1, 1);  // fixed_frame_rate_flag
+    s.put(1, 0); s.put(1, 0);   // nal / vcl_hrd_parameters_present_flag
+    s.put(1, 0);  // pic_struct_present_flag
+    s.put(1, 1);  // bitstream_restriction_flag
+    s.put(1, 1);  // motion_vectors_over_pic_boundaries_flag
+    s.ue(0); s.ue(0);     // max_bytes_per_pic_denom, max_bits_per_mb_denom
+    s.ue(16); s.ue(16);   // log2_max_mv_length_horizontal / _vertical
+    s.ue(0);      // max_num_reorder_frames: output order is decoding order, a decoder may hand out every picture at once
+    s.ue((uint32_t)f.nrefs);   // max_dec_frame_buffering
+}
 
 // Annex-B SPS + PPS NAL units
 std::vector<uint8_t> build_parameter_sets(const StreamShape& f)
@@ -189,7 +228,8 @@ std::vector<uint8_t> build_parameter_sets(const StreamShape& f)
     const int cr = (f.mbw * 16 - f.width) / 2, cb = (f.mbh * 16 - f.height) / 2;
     if (cr || cb) { s.put(1, 1); s.ue(0); s.ue((uint32_t)cr); s.ue(0); s.ue((uint32_t)cb); }
     else s.put(1, 0);
-    s.put(1, 0);  // vui_parameters_present_flag
+    if (f.described) { s.put(1, 1); write_vui(s, f); }
+    else s.put(1, 0);  // vui_parameters_present_flag
     s.trailing();
     HostBits p;
     p.ue(0); p.ue(0);

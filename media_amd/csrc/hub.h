@@ -50,6 +50,7 @@ struct Hub {
     HubItem items[MAX_BATCH];
     HubCtx ctx[HUB_MAX_CTX];         // ctx[0 .. nctx_p - 1] take the P steps, ctx[nctx_p] the IDR steps
     int fmt = MI355X_H264_INPUT_I420;   // layout of every picture of this hub's streams (config.input_format)
+    ColourDesc colour;               // the description of every stream of this hub (mi355x_h264_stream_open_colour); the engine's parameter sets carry it
     uint8_t* d_stage = nullptr;      // [cap] pictures the kernels read when the caller's are not read in place: host pictures as handed
     uint8_t* h_stage = nullptr;      // over (tight I420 / NV12; pinned h_stage on their way), RGBA pictures after the conversion (I420)
     size_t st_stage = 0;
@@ -79,10 +80,11 @@ std::vector<Hub*> g_hubs;
 std::atomic<int> g_streams_open{0};   // over all hubs of the process
 
 // (refs: 0 and 1 are both one reference picture; streams that search more have rings of another size, so engines of their own)
-bool same_geometry(const Hub& hub, const mi355x_h264_config& b, int sw, int sh)
+// (colour: the parameter sets are the engine's, so a described stream shares one only with streams of its description)
+bool same_geometry(const Hub& hub, const mi355x_h264_config& b, int sw, int sh, const ColourDesc& colour)
 {
     const mi355x_h264_config& a = hub.cfg;
-    return hub.sw == sw && hub.sh == sh && std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
+    return same_colour(hub.colour, colour) && hub.sw == sw && hub.sh == sh && std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
            a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
 }
 
@@ -125,11 +127,12 @@ hipError_t hub_alloc(Hub* h)
     return hipSuccess;
 }
 
-int hub_create(const mi355x_h264_config& cfg, int sw, int sh, Hub** out)
+int hub_create(const mi355x_h264_config& cfg, int sw, int sh, const ColourDesc& colour, Hub** out)
 {
     Hub* h = new (std::nothrow) Hub();
     if (!h) return MI355X_H264_E_NOMEM;
     h->cfg = cfg;
+    h->colour = colour;
     h->fmt = cfg.input_format;
     h->sw = sw; h->sh = sh; h->scaled = sw != cfg.width || sh != cfg.height;
     const char* ci = getenv("MI355X_H264_HUB_ITEMS");
@@ -143,7 +146,7 @@ int hub_create(const mi355x_h264_config& cfg, int sw, int sh, Hub** out)
     h->sched.nctx_p = std::min((int)HUB_MAX_CTX - 1, std::max(1, nc ? atoi(nc) : 2));
     mi355x_h264_config ec = cfg;
     ec.batch = h->sched.cap; ec.refs = std::max(cfg.refs, 1); ec.band_index = 0; ec.band_count = 0; ec.input_format = MI355X_H264_INPUT_I420;
-    int rc = create_engine(&ec, &h->e, true);
+    int rc = create_engine(&ec, &h->e, true, &h->colour, cfg.input_format == MI355X_H264_INPUT_RGBA);
     if (rc != MI355X_H264_OK) { h->e = nullptr; hub_free(h); return rc; }
     h->sched.nrefs = h->e->nrefs; h->sched.nbuf = h->e->nbuf;   // (up to 4 ring slots: `cur` fits the itemtab word's two bits)
     h->st_stage = (picture_bytes(PIC_I420, cfg.width, cfg.height) + 255) & ~(size_t)255;
@@ -201,8 +204,9 @@ void hub_run_step(Hub* h, HubStep& T)
         }
         if (rc == MI355X_H264_OK && rgba) {   // one conversion launch for the step, in front of the first kernel that reads samples
             const int w = h->cfg.width, hh = h->cfg.height;
-            hipLaunchKernelGGL(k_rgba_to_i420_step, dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(hh / 2), (unsigned)n), dim3(256), 0, Y.st,
-                               (const RgbaSrc*)(c.d_tab + HubCtx::TAB_RGBA), d_srctab, w, hh);
+            launch_rgba_to_i420_step(h->colour.described ? colour_variant(h->colour.matrix, h->colour.full_range) : 0,
+                                     dim3((unsigned)((w / 2 + 255) / 256), (unsigned)(hh / 2), (unsigned)n), Y.st,
+                                     (const RgbaSrc*)(c.d_tab + HubCtx::TAB_RGBA), d_srctab, w, hh);
         }
         if (rc == MI355X_H264_OK) {
             St.d_src = nullptr; St.src_item_stride = 0; St.idr = idr; St.n = n;

@@ -12,7 +12,10 @@
 // RGBA is this build's own definition (the counterpart of oracle/h264_rgba.c, which states the way in): integer BT.601 studio swing,
 //   c = 298 * (Y - 16), d = U - 128, e = V - 128,
 //   R = clip255((c + 409 * e + 128) >> 8), G = clip255((c - 100 * d - 208 * e + 128) >> 8), B = clip255((c + 516 * d + 128) >> 8),
-// the shift arithmetic; the chroma sample of a 2x2 block serves its four pixels (no interpolation).
+// the shift arithmetic; the chroma sample of a 2x2 block serves its four pixels (no interpolation).  That is variant 0 of four
+// (include/mi355x_h264.h, "colour description": c = m (Y - o), and rv, gu, gv, bu in place of 409, -100, -208, 516).  A launch may
+// carry streams of different descriptions, so the variant is the table row's (DecOutPos.colour): a value every lane of the block
+// has from scalar loads, turned into the six coefficients by scalar selects - no table in memory is indexed.
 //
 // Lane map.  The unit of work is one 16-byte chunk of the DESTINATION, aligned to 16 bytes there: lane x of a wave takes chunk
 // 64 * blockIdx.x + x of a row, so a wave's store instruction covers 1 KiB of consecutive destination bytes whatever the row's
@@ -33,8 +36,10 @@ enum { DEC_OUT_I420 = 0, DEC_OUT_NV12 = 1, DEC_OUT_NV21 = 2, DEC_OUT_RGBA = 3, D
 struct DecOutPos {
     uint32_t item, slot, crop_x, crop_y, width, height, stride, cstride;
     unsigned long long off;   // of the picture's first byte inside the destination (a multiple of 256)
-    unsigned long long reserved;
+    uint32_t colour;          // RGBA: the variant of the conversion, 0 BT.601 limited, 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full
+    uint32_t reserved;
 };
+static_assert(sizeof(DecOutPos) == 48, "DecOutPos layout");
 struct DecOutParams {
     const uint8_t* y; const uint8_t* u; const uint8_t* v;   // the store's plane bases (d_plane_base)
     size_t st_y, st_c, st_ring_y, st_ring_c;               // bytes between items / between the ring slots of an item
@@ -64,10 +69,23 @@ __device__ __forceinline__ void load_bytes(const uint8_t* s, uint32_t* out)
 // channels with v_ashr_pk_u8_i32 and takes the upper half of its result for zero, which it was not on the MI355X: the blue byte
 // that is OR-ed in there came out wrong for some samples.
 __device__ __forceinline__ uint32_t clip255_shr8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v)) >> 8; }
-__device__ __forceinline__ uint32_t rgba_pixel(int y, int u, int v)
+// the coefficients of variant v (bit 0: BT.709, bit 1: full range); v is uniform over the block
+struct OutCoef { int m, o, rv, gu, gv, bu; };
+__device__ __forceinline__ OutCoef out_coef(uint32_t v)
 {
-    const int c = 298 * (y - 16), d = u - 128, e = v - 128;
-    return clip255_shr8(c + 409 * e + 128) | (clip255_shr8(c - 100 * d - 208 * e + 128) << 8) | (clip255_shr8(c + 516 * d + 128) << 16) | 0xFF000000u;
+    const bool b709 = (v & 1u) != 0, full = (v & 2u) != 0;
+    OutCoef k;
+    k.m = full ? 256 : 298; k.o = full ? 0 : 16;
+    k.rv = full ? (b709 ? 403 : 359) : (b709 ? 459 : 409);
+    k.gu = full ? (b709 ? -48 : -88) : (b709 ? -55 : -100);
+    k.gv = full ? (b709 ? -120 : -183) : (b709 ? -136 : -208);
+    k.bu = full ? (b709 ? 475 : 454) : (b709 ? 541 : 516);
+    return k;
+}
+__device__ __forceinline__ uint32_t rgba_pixel(const OutCoef& k, int y, int u, int v)
+{
+    const int c = k.m * (y - k.o), d = u - 128, e = v - 128;
+    return clip255_shr8(c + k.rv * e + 128) | (clip255_shr8(c + k.gu * d + k.gv * e + 128) << 8) | (clip255_shr8(c + k.bu * d + 128) << 16) | 0xFF000000u;
 }
 // bytes 0, 1 of a and of b as a0 b0 a1 b1
 __device__ __forceinline__ uint32_t weave(uint32_t a, uint32_t b) { return (a & 0xFFu) | ((b & 0xFFu) << 8) | ((a & 0xFF00u) << 8) | ((b & 0xFF00u) << 16); }
@@ -109,7 +127,7 @@ __device__ __forceinline__ void weave_chunk(const uint8_t* a, const uint8_t* b, 
 
 // a row of w RGBA pixels from its luma row and the chroma rows of its pair of rows; rows start on 8 bytes, so a chunk starts at an
 // even pixel: pixels 0, 1 of it share a chroma sample and so do pixels 2, 3
-__device__ __forceinline__ void rgba_chunk(const uint8_t* ys, const uint8_t* us, const uint8_t* vs, uint8_t* drow, int w, int chunk)
+__device__ __forceinline__ void rgba_chunk(const OutCoef& K, const uint8_t* ys, const uint8_t* us, const uint8_t* vs, uint8_t* drow, int w, int chunk)
 {
     uint8_t* const c = drow - ((uintptr_t)drow & 15) + 16 * (size_t)chunk;
     const int k = (int)(c - drow);   // a multiple of 8
@@ -118,12 +136,12 @@ __device__ __forceinline__ void rgba_chunk(const uint8_t* ys, const uint8_t* us,
     if (x >= 0 && x + 4 <= w) {
         const uint32_t y01 = *(const uint16_t*)(ys + x), y23 = *(const uint16_t*)(ys + x + 2);
         const int u0 = us[x / 2], u1 = us[x / 2 + 1], v0 = vs[x / 2], v1 = vs[x / 2 + 1];
-        *(Q4*)c = Q4{rgba_pixel((int)(y01 & 255u), u0, v0), rgba_pixel((int)(y01 >> 8), u0, v0), rgba_pixel((int)(y23 & 255u), u1, v1), rgba_pixel((int)(y23 >> 8), u1, v1)};
+        *(Q4*)c = Q4{rgba_pixel(K, (int)(y01 & 255u), u0, v0), rgba_pixel(K, (int)(y01 >> 8), u0, v0), rgba_pixel(K, (int)(y23 & 255u), u1, v1), rgba_pixel(K, (int)(y23 >> 8), u1, v1)};
         return;
     }
 #pragma unroll
     for (int i = 0; i < 4; i++)
-        if (x + i >= 0 && x + i < w) *(uint32_t*)(c + 4 * i) = rgba_pixel(ys[x + i], us[(x + i) / 2], vs[(x + i) / 2]);
+        if (x + i >= 0 && x + i < w) *(uint32_t*)(c + 4 * i) = rgba_pixel(K, ys[x + i], us[(x + i) / 2], vs[(x + i) / 2]);
 }
 
 // row R (0 .. rows(layout) - 1, the planes' rows one after the other) of the picture of table row t: the lane's chunk of it
@@ -136,7 +154,7 @@ __device__ __forceinline__ void row_chunk(const DecOutParams& P, const DecOutPos
     uint8_t* const d = P.dst + t.off;
     if constexpr (LAYOUT == DEC_OUT_RGBA) {
         if (R >= h) return;
-        rgba_chunk(ys + (size_t)R * pitch, P.u + coff + (size_t)(R / 2) * (pitch / 2), P.v + coff + (size_t)(R / 2) * (pitch / 2), d + (size_t)R * t.stride, w, chunk);
+        rgba_chunk(out_coef(t.colour), ys + (size_t)R * pitch, P.u + coff + (size_t)(R / 2) * (pitch / 2), P.v + coff + (size_t)(R / 2) * (pitch / 2), d + (size_t)R * t.stride, w, chunk);
     } else {
         if (R < h) { copy_chunk(ys + (size_t)R * pitch, d + (size_t)R * t.stride, w, chunk); return; }
         const int r = R - h;   // chroma row

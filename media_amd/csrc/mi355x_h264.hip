@@ -62,6 +62,30 @@ void mi355x_h264_default_config(mi355x_h264_config* c)
 }
 
 int mi355x_h264_create(const mi355x_h264_config* cfg, mi355x_h264_encoder** out) { return create_engine(cfg, out, false); }
+
+// a caller's description as the owners keep it; false: refused (matrix, range or struct_size)
+static bool colour_take(const mi355x_h264_colour* c, ColourDesc* d)
+{
+    *d = ColourDesc();
+    if (!c) return true;
+    if (c->struct_size != sizeof(mi355x_h264_colour) || !colour_valid(c->matrix, c->full_range)) return false;
+    d->described = 1; d->matrix = c->matrix; d->full_range = c->full_range;
+    return true;
+}
+static int colour_give(const ColourDesc& d, mi355x_h264_colour* out)
+{
+    out->struct_size = sizeof(*out); out->matrix = d.described ? d.matrix : MI355X_H264_MATRIX_BT601; out->full_range = d.described ? d.full_range : 0;
+    return d.described;
+}
+
+int mi355x_h264_create_colour(const mi355x_h264_config* cfg, const mi355x_h264_colour* colour, mi355x_h264_encoder** out)
+{
+    ColourDesc d;
+    if (out) *out = nullptr;
+    if (!colour_take(colour, &d)) return MI355X_H264_E_ARG;
+    return create_engine(cfg, out, false, &d, false);
+}
+int mi355x_h264_colour_of(const mi355x_h264_encoder* e, mi355x_h264_colour* out) { return e && out ? colour_give(e->colour, out) : MI355X_H264_E_ARG; }
 void mi355x_h264_destroy(mi355x_h264_encoder* e) { destroy_engine(e); }
 
 #define NEED(e, cond, what) do { if (!(e)) return MI355X_H264_E_ARG; if (!(cond)) return set_err((e)->err, MI355X_H264_E_ARG, what); } while (0)
@@ -336,8 +360,17 @@ int mi355x_h264_stream_open_ex(const mi355x_h264_config* cfg, uint32_t flags, mi
 
 int mi355x_h264_stream_open_scaled(const mi355x_h264_config* cfg, uint32_t flags, int sw, int sh, mi355x_h264_stream** out)
 {
+    return mi355x_h264_stream_open_colour(cfg, flags, sw, sh, nullptr, out);
+}
+
+int mi355x_h264_stream_colour(const mi355x_h264_stream* s, mi355x_h264_colour* out) { return s && out ? colour_give(s->hub->colour, out) : MI355X_H264_E_ARG; }
+
+int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags, int sw, int sh, const mi355x_h264_colour* colour, mi355x_h264_stream** out)
+{
     if (!cfg || !out || cfg->struct_size != sizeof(mi355x_h264_config)) return MI355X_H264_E_ARG;
     *out = nullptr;
+    ColourDesc desc;
+    if (!colour_take(colour, &desc)) return MI355X_H264_E_ARG;
     if (sw != cfg->width || sh != cfg->height) {   // (the same size: exactly mi355x_h264_stream_open_ex, whatever it makes of the size)
         if (((sw | sh) & 1) || sw < 16 || sh < 16 || sw > 4096 || sh > 4096) return MI355X_H264_E_ARG;
         if (cfg->width < 16 || cfg->height < 16 || ((cfg->width | cfg->height) & 1)) return MI355X_H264_E_ARG;
@@ -354,9 +387,9 @@ int mi355x_h264_stream_open_scaled(const mi355x_h264_config* cfg, uint32_t flags
     std::lock_guard<std::mutex> gl(g_hubs_mu);
     Hub* h = nullptr;
     for (Hub* c : g_hubs)
-        if (same_geometry(*c, *cfg, sw, sh) && c->sched.has_room()) { h = c; break; }
+        if (same_geometry(*c, *cfg, sw, sh, desc) && c->sched.has_room()) { h = c; break; }
     if (!h) {
-        const int rc = hub_create(*cfg, sw, sh, &h);
+        const int rc = hub_create(*cfg, sw, sh, desc, &h);
         if (rc != MI355X_H264_OK) { delete s; return rc; }
         g_hubs.push_back(h);
     }
@@ -622,6 +655,29 @@ int mi355x_h264_dec_group_picture_info(const mi355x_h264_dec_group* g, int strea
     return MI355X_H264_OK;
 }
 
+// out[8] of mi355x_h264_dec_colour from a sequence parameter set's VUI (an absent VUI: the absent values of h264dec::Vui)
+static void vui_report(const h264dec::Vui& v, int32_t* out)
+{
+    out[0] = v.colour ? 1 : 0; out[1] = v.matrix; out[2] = v.full_range; out[3] = v.primaries; out[4] = v.transfer;
+    out[5] = v.chroma_loc; out[6] = v.fps(); out[7] = v.reorder;
+}
+
+int mi355x_h264_dec_group_colour(const mi355x_h264_dec_group* g, int stream, int32_t* out)
+{
+    if (!g || !out || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0) return MI355X_H264_E_ARG;
+    vui_report(g->st[stream].vui, out);
+    return MI355X_H264_OK;
+}
+
+int mi355x_h264_dec_group_set_rgba_colour(mi355x_h264_dec_group* g, int stream, const mi355x_h264_colour* colour)
+{
+    if (!g || stream < 0 || stream >= g->nstreams) return MI355X_H264_E_ARG;
+    ColourDesc d;
+    if (!colour_take(colour, &d)) return MI355X_H264_E_ARG;
+    g->st[stream].rgba_override = d.described ? colour_variant(d.matrix, d.full_range) : -1;
+    return MI355X_H264_OK;
+}
+
 int64_t mi355x_h264_dec_group_read_i420(mi355x_h264_dec_group* g, int stream, uint8_t* dst, size_t cap) { return dg_read(g, stream, dst, cap, false); }
 int64_t mi355x_h264_dec_group_read_i420_device(mi355x_h264_dec_group* g, int stream, void* d_dst, size_t cap) { return dg_read(g, stream, d_dst, cap, true); }
 
@@ -703,6 +759,9 @@ int mi355x_h264_dec_picture_info(const mi355x_h264_decoder* d, int* width, int* 
 {
     return d ? mi355x_h264_dec_group_picture_info(d->g, 0, width, height, coded_width, coded_height) : MI355X_H264_E_ARG;
 }
+
+int mi355x_h264_dec_colour(const mi355x_h264_decoder* d, int32_t* out) { return d ? mi355x_h264_dec_group_colour(d->g, 0, out) : MI355X_H264_E_ARG; }
+int mi355x_h264_dec_set_rgba_colour(mi355x_h264_decoder* d, const mi355x_h264_colour* colour) { return d ? mi355x_h264_dec_group_set_rgba_colour(d->g, 0, colour) : MI355X_H264_E_ARG; }
 
 int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder* d, uint8_t* dst, size_t cap) { return d ? dec_ret(d, dg_read(d->g, 0, dst, cap, false)) : MI355X_H264_E_ARG; }
 int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder* d, void* d_dst, size_t cap) { return d ? dec_ret(d, dg_read(d->g, 0, d_dst, cap, true)) : MI355X_H264_E_ARG; }
@@ -897,6 +956,15 @@ int mi355x_h264_parser_info(const mi355x_h264_parser* p, int32_t* out, int n)
     const int m = n < 17 ? 12 : (n < 20 ? 17 : (n < 21 ? 20 : 21));   // (a caller with an earlier layout's slots gets those)
     memcpy(out, v, (size_t)m * sizeof(int32_t));
     return m;
+}
+int mi355x_h264_parser_colour(const mi355x_h264_parser* p, int32_t* out, int n)
+{
+    if (!p || !out || n < 8) return -1;
+    const h264dec::Vui& v = p->p.sps().vui;
+    vui_report(v, out);
+    if (n < 10) return 8;
+    out[8] = v.present ? 1 : 0; out[9] = v.dec_buffering;
+    return 10;
 }
 // what: 0 MbInfo (32 B / macroblock), 1 quadrant vectors (16 B), 2 Intra4x4 modes (16 B), 3 levels (832 B)
 int64_t mi355x_h264_parser_read(const mi355x_h264_parser* p, int what, void* dst, size_t cap)

@@ -3,7 +3,7 @@ a device), `DecoderGroup` (the next pictures of up to 64 streams of one coded si
 recovers from a stream with the side information of the encoder that wrote it)."""
 import ctypes as C
 import numpy as np
-from .capi import lib, EncoderError, MBINFO_DTYPE, LV_STRIDE, _mem_check
+from .capi import lib, EncoderError, MBINFO_DTYPE, LV_STRIDE, _mem_check, Colour, colour_struct
 
 E_STREAM = -7
 PIX_I420, PIX_NV12, PIX_NV21, PIX_RGBA = 0, 1, 2, 3   # output layouts (MI355X_H264_PIX_*)
@@ -13,10 +13,31 @@ _bound = False
 class OutPic(C.Structure):
     """mi355x_h264_dec_out_pic: where a picture lies in an output (offset -1: the stream has none there)"""
     _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("chroma_stride", C.c_int32),
-                ("fresh", C.c_int32), ("reserved", C.c_int32), ("serial", C.c_int64)]
+                ("fresh", C.c_int32), ("colour", C.c_int32), ("serial", C.c_int64)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        """(colour: matrix | full_range << 8 of the RGBA conversion that was applied; 0 for the other layouts)"""
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+COLOUR = ("described", "matrix", "full_range", "primaries", "transfer", "chroma_loc", "fps", "reorder")   # out[8] of mi355x_h264_dec_colour
+
+
+def _colour_dict(fn, *args):
+    v = (C.c_int32 * 8)()
+    rc = fn(*args, v)
+    if rc != 0:
+        raise EncoderError("colour -> %d (no picture decoded yet?)" % rc)
+    return dict(zip(COLOUR, list(v)))
+
+
+def _set_rgba_colour(fn, colour, *args):
+    c = colour_struct(colour)
+    rc = fn(*args, None if c is None else C.byref(c))
+    if rc != 0:
+        err = EncoderError("set_rgba_colour(%r) -> %d" % (colour, rc))
+        err.rc = rc
+        raise err
 
 
 def _bind():
@@ -57,6 +78,13 @@ def _bind():
     L.mi355x_h264_dec_group_read_all.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.c_int, op]; L.mi355x_h264_dec_group_read_all.restype = C.c_int64
     L.mi355x_h264_dec_group_set_output.argtypes = [vp, C.c_int, C.c_int]
     L.mi355x_h264_dec_group_output.argtypes = [vp, C.c_int, C.POINTER(vp), op]
+    if hasattr(L, "mi355x_h264_dec_colour"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no colour descriptions)
+        i8, cp = C.POINTER(C.c_int32), C.POINTER(Colour)
+        L.mi355x_h264_dec_colour.argtypes = [vp, i8]
+        L.mi355x_h264_dec_set_rgba_colour.argtypes = [vp, cp]
+        L.mi355x_h264_dec_group_colour.argtypes = [vp, C.c_int, i8]
+        L.mi355x_h264_dec_group_set_rgba_colour.argtypes = [vp, C.c_int, cp]
+        L.mi355x_h264_parser_colour.argtypes = [vp, i8, C.c_int]
     _bound = True
     return L
 
@@ -141,6 +169,15 @@ class Decoder:
         if n != need:
             raise EncoderError("dec_read -> %d: %s" % (n, lib().mi355x_h264_dec_last_error(self.h).decode()))
         return buf, dict(pic.as_dict(), bytes=n)
+
+    def colour(self):
+        """what the sequence parameter set of the last picture says (mi355x_h264_dec_colour): a dict of COLOUR"""
+        return _colour_dict(lib().mi355x_h264_dec_colour, self.h)
+
+    def set_rgba_colour(self, colour):
+        """RGBA output applies this variant from the next read on, whatever the stream says: ("bt709", "full") ...; None: follow
+        the stream again"""
+        _set_rgba_colour(lib().mi355x_h264_dec_set_rgba_colour, colour, self.h)
 
     def plane(self, p):
         """coded-size plane p of the last picture"""
@@ -233,6 +270,14 @@ class DecoderGroup:
         if lib().mi355x_h264_dec_group_picture_info(self.h, stream, *[C.byref(x) for x in v]) != 0:
             raise EncoderError("stream %d has decoded no picture yet" % stream)
         return tuple(x.value for x in v)   # width, height, coded width, coded height
+
+    def colour(self, stream):
+        """what the sequence parameter set of the stream's last picture says (mi355x_h264_dec_group_colour): a dict of COLOUR"""
+        return _colour_dict(lib().mi355x_h264_dec_group_colour, self.h, stream)
+
+    def set_rgba_colour(self, stream, colour):
+        """as Decoder.set_rgba_colour, for one stream of the group"""
+        _set_rgba_colour(lib().mi355x_h264_dec_group_set_rgba_colour, colour, self.h, stream)
 
     def read_i420(self, stream):
         w, h, _, _ = self.info(stream)
@@ -342,6 +387,14 @@ class Parser:
         v = (C.c_int32 * 21)()
         lib().mi355x_h264_parser_info(self.h, v, 21)
         return dict(zip(self.INFO, list(v)))
+
+    def colour(self):
+        """what the VUI of the active sequence parameter set says (mi355x_h264_parser_colour): a dict of COLOUR, plus `vui` (1: the
+        set has a VUI that was read whole and in range) and `dec_buffering` (max_dec_frame_buffering or -1)"""
+        v = (C.c_int32 * 10)()
+        if lib().mi355x_h264_parser_colour(self.h, v, 10) != 10:
+            raise EncoderError("parser_colour failed")
+        return dict(zip(COLOUR + ("vui", "dec_buffering"), list(v)))
 
     def vectors4(self):
         """(vectors of the sixteen 4x4 blocks (n, 16, 2), raster order; ref_idx_l0 of the four quadrants (n, 4), 255 = intra)"""

@@ -40,7 +40,23 @@ DecoderRetCode VideoDecoderMI355X::SetDecodeParams(DecodeParamsIndex index, void
         m_writeHeight = p->height;
         m_stride = p->stride;
     }
+    if (index == INDEX_PORT_FORMAT_INFO && decParams != nullptr) {
+        // the out port delivers tight planar 4:2:0 (the default) or tight RGBA, converted as the stream's colour description says
+        const auto *p = static_cast<const PortFormatParams *>(decParams);
+        if (p->port != OUT_PORT || (p->format != PIXEL_FORMAT_YUV_420P && p->format != PIXEL_FORMAT_RGBA_8888)) {
+            ERR("set decode params: port %u format %d is not supported", static_cast<unsigned>(p->port), p->format);
+            return VIDEO_DECODER_SET_DECODE_PARAMS_FAIL;
+        }
+        INFO("set decode params: out port format %d", p->format);
+        m_outFormat = p->format;
+    }
     return VIDEO_DECODER_SUCCESS;
+}
+
+uint32_t VideoDecoderMI355X::ColourChanges(int32_t out[8]) const
+{
+    std::memcpy(out, m_colour, sizeof(m_colour));
+    return m_colourChanges;
 }
 
 DecoderRetCode VideoDecoderMI355X::GetDecodeParams(DecodeParamsIndex index, void *decParams)
@@ -59,7 +75,7 @@ DecoderRetCode VideoDecoderMI355X::GetDecodeParams(DecodeParamsIndex index, void
         case INDEX_PORT_FORMAT_INFO: {   // ref :294-304; the output is tight planar 4:2:0
             auto *p = static_cast<PortFormatParams *>(decParams);
             if (p->port == OUT_PORT) {
-                p->format = PIXEL_FORMAT_YUV_420P;
+                p->format = m_outFormat;
             } else if (p->port == IN_PORT) {
                 p->format = STREAM_FORMAT_AVC;
             } else {
@@ -108,6 +124,7 @@ DecoderRetCode VideoDecoderMI355X::StartDecoder()
     }
     m_stop = false;
     m_pending = false;
+    m_colourChanges = 0;
     INFO("start decoder success");
     return VIDEO_DECODER_SUCCESS;
 }
@@ -136,8 +153,23 @@ DecoderRetCode VideoDecoderMI355X::SendStreamData(uint8_t *buffer, uint32_t fill
         (void) mi355x_h264_dec_picture_info(m_engine, &w, &h, nullptr, nullptr);
         m_frameWidth = static_cast<uint32_t>(w);
         m_frameHeight = static_cast<uint32_t>(h);
-        m_frame.resize(static_cast<size_t>(w) * h * 3 / 2);
-        if (mi355x_h264_dec_read_i420(m_engine, m_frame.data(), m_frame.size()) != static_cast<int64_t>(m_frame.size())) {
+        int32_t colour[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (mi355x_h264_dec_colour(m_engine, colour) == MI355X_H264_OK && (m_colourChanges == 0 || std::memcmp(colour, m_colour, sizeof(colour)) != 0)) {
+            std::memcpy(m_colour, colour, sizeof(colour));
+            m_colourChanges++;
+            INFO("stream colour: description %d matrix %d full_range %d primaries %d transfer %d chroma_loc %d fps %d reorder %d", colour[0],
+                 colour[1], colour[2], colour[3], colour[4], colour[5], colour[6], colour[7]);
+        }
+        int64_t got_bytes;
+        if (m_outFormat == PIXEL_FORMAT_RGBA_8888) {
+            mi355x_h264_dec_out_pic pic{};
+            m_frame.resize(static_cast<size_t>(w) * h * 4);
+            got_bytes = mi355x_h264_dec_read(m_engine, MI355X_H264_PIX_RGBA, 1, m_frame.data(), m_frame.size(), 0, &pic);
+        } else {
+            m_frame.resize(static_cast<size_t>(w) * h * 3 / 2);
+            got_bytes = mi355x_h264_dec_read_i420(m_engine, m_frame.data(), m_frame.size());
+        }
+        if (got_bytes != static_cast<int64_t>(m_frame.size())) {
             ERR("reading the decoded picture failed: %s", mi355x_h264_dec_last_error(m_engine));
             return VIDEO_DECODER_DECODE_FAIL;
         }

@@ -32,6 +32,9 @@ public:
 
     // test hooks
     uint64_t PicturesDecoded() const { return m_pictures; }
+    // what the sequence parameter set of the last picture says (out[8] of mi355x_h264_dec_colour), and how often it has changed
+    // since StartDecoder (the first picture counts: 1)
+    uint32_t ColourChanges(int32_t out[8]) const;
 
 private:
     static constexpr uint32_t kDefaultWidth = 1280, kDefaultHeight = 720;   // the reference adapter's defaults (VideoDecoderNetint.h:34-35)
@@ -41,7 +44,12 @@ private:
     uint32_t m_writeWidth = kDefaultWidth, m_writeHeight = kDefaultHeight;
     int32_t m_stride = static_cast<int32_t>(kDefaultWidth);
     uint64_t m_pictures = 0;
-    std::vector<uint8_t> m_frame;   // the waiting picture, tight I420
+    std::vector<uint8_t> m_frame;   // the waiting picture, tight I420 - or tight RGBA, when the out port was set to PIXEL_FORMAT_RGBA_8888
+    // the out port's format: PIXEL_FORMAT_YUV_420P (the default) or PIXEL_FORMAT_RGBA_8888 (SetDecodeParams, INDEX_PORT_FORMAT_INFO).
+    // RGBA follows the stream's colour description (include/mi355x_h264_dec.h, "colour")
+    int32_t m_outFormat = PIXEL_FORMAT_YUV_420P;
+    int32_t m_colour[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t m_colourChanges = 0;
     uint32_t m_frameWidth = 0, m_frameHeight = 0;
     std::function<void(DecodeEventIndex, uint32_t, void *)> m_eventCallBack;
     std::function<uint32_t(uint8_t*, uint8_t*, const PicInfoParams &, uint32_t)> m_copyFrame;

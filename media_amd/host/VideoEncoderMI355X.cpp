@@ -94,12 +94,21 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
         m_srcWidth = m_srcHeight = 0;
         return false;
     }
+    // extension: matrix and range of the stream's samples, written into the SPS; RGBA pictures are converted with them.  Both paths
+    const std::string colourKey = GetStrEncParam("persist.vmi.video.encode.colour"), rangeKey = GetStrEncParam("persist.vmi.video.encode.range");
+    mi355x_h264_colour colour{};
+    const int haveColour = ParseColour(colourKey, rangeKey, &colour);
+    if (haveColour < 0) {
+        WARN("colour [%s] / range [%s] rejected: the stream carries no colour description", colourKey.c_str(), rangeKey.c_str());
+    }
     if (shared) {
         cfg.input_format = m_input;
-        const int rc = haveSrc > 0 ? mi355x_h264_stream_open_scaled(&cfg, MI355X_H264_STREAM_MULTIREF, m_srcWidth, m_srcHeight, &m_stream)
-                                   : mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
+        const int rc = haveColour > 0 ? mi355x_h264_stream_open_colour(&cfg, MI355X_H264_STREAM_MULTIREF, haveSrc > 0 ? m_srcWidth : cfg.width,
+                                                                       haveSrc > 0 ? m_srcHeight : cfg.height, &colour, &m_stream)
+                       : haveSrc > 0 ? mi355x_h264_stream_open_scaled(&cfg, MI355X_H264_STREAM_MULTIREF, m_srcWidth, m_srcHeight, &m_stream)
+                                     : mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
         if (rc != MI355X_H264_OK) {
-            ERR("mi355x_h264_stream_open_%s returned %d", haveSrc > 0 ? "scaled" : "ex", rc);
+            ERR("mi355x_h264_stream_open_%s returned %d", haveColour > 0 ? "colour" : haveSrc > 0 ? "scaled" : "ex", rc);
             m_stream = nullptr;
             return false;
         }
@@ -113,9 +122,9 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     }
     // (an engine of its own takes RGBA through entry points of their own; its input_format names the layout of device I420 / NV12)
     cfg.input_format = m_input == MI355X_H264_INPUT_NV12 ? MI355X_H264_INPUT_NV12 : MI355X_H264_INPUT_I420;
-    const int rc = mi355x_h264_create(&cfg, &m_engine);
+    const int rc = haveColour > 0 ? mi355x_h264_create_colour(&cfg, &colour, &m_engine) : mi355x_h264_create(&cfg, &m_engine);
     if (rc != MI355X_H264_OK) {
-        ERR("mi355x_h264_create returned %d", rc);
+        ERR("mi355x_h264_create%s returned %d", haveColour > 0 ? "_colour" : "", rc);
         m_engine = nullptr;
         return false;
     }
@@ -252,6 +261,30 @@ int32_t VideoEncoderMI355X::ParseInputLayout(const std::string &value)
 int32_t VideoEncoderMI355X::ParseRefs(const std::string &value) { return value == "2" ? 2 : value == "3" ? 3 : 1; }
 
 bool VideoEncoderMI355X::ParsePsnr(const std::string &value) { return value == "1"; }
+
+int VideoEncoderMI355X::ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out)
+{
+    if (colour.empty() && range.empty()) {
+        return 0;
+    }
+    const bool colourOk = colour.empty() || colour == "bt601" || colour == "bt709";
+    const bool rangeOk = range.empty() || range == "limited" || range == "full";
+    if (!colourOk || !rangeOk) {
+        return -1;
+    }
+    out->struct_size = sizeof(*out);
+    out->matrix = colour == "bt709" ? MI355X_H264_MATRIX_BT709 : MI355X_H264_MATRIX_BT601;
+    out->full_range = range == "full" ? 1 : 0;
+    return 1;
+}
+
+bool VideoEncoderMI355X::Colour(mi355x_h264_colour *out) const
+{
+    if (m_stream != nullptr) {
+        return mi355x_h264_stream_colour(m_stream, out) == 1;
+    }
+    return m_engine != nullptr && mi355x_h264_colour_of(m_engine, out) == 1;
+}
 
 bool VideoEncoderMI355X::ParseInputDevice(const std::string &value) { return value == "device"; }
 

@@ -47,6 +47,14 @@ public:
     static int ParseSourceSize(const std::string &width, const std::string &height, uint32_t codedWidth, uint32_t codedHeight,
                                int32_t *srcWidth, int32_t *srcHeight);
 
+    // extension keys persist.vmi.video.encode.colour ("bt601" | "bt709") and .range ("limited" | "full"): either key present and
+    // valid describes the stream (include/mi355x_h264.h, "colour description"), the other defaulting to bt601 / limited.  1: *out is
+    // the description; 0: neither key is set (no description, the reference's behaviour); -1: a key holds anything else - the
+    // reference's behaviour, with one WARN line
+    static int ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out);
+    // the description the engine was opened with (false: none)
+    bool Colour(mi355x_h264_colour *out) const;
+
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
     bool EngineOpen(const Settings &s) override;

@@ -37,6 +37,35 @@ int32_t vc_parse_source_size(const char *width, const char *height, uint32_t cod
 int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
 // persist.vmi.video.encode.psnr: "1" turns the quality report on, anything else leaves it off
 int32_t vc_parse_psnr(const char *value) { return VideoEncoderMI355X::ParsePsnr(value != nullptr ? value : "") ? 1 : 0; }
+// persist.vmi.video.encode.colour / .range: 1 (and matrix, full_range), 0 (neither set) or -1 (rejected)
+int32_t vc_parse_colour(const char *colour, const char *range, int32_t *matrix, int32_t *fullRange)
+{
+    mi355x_h264_colour c{};
+    const int rc = VideoEncoderMI355X::ParseColour(colour != nullptr ? colour : "", range != nullptr ? range : "", &c);
+    if (rc > 0) { *matrix = c.matrix; *fullRange = c.full_range; }
+    return rc;
+}
+// the description the object's engine was opened with: 1 (and matrix, full_range) or 0
+int32_t vc_colour(void *enc, int32_t *matrix, int32_t *fullRange)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    mi355x_h264_colour c{};
+    if (m == nullptr || !m->Colour(&c)) return 0;
+    *matrix = c.matrix; *fullRange = c.full_range;
+    return 1;
+}
+// The parameter sets (Annex-B SPS + PPS) the library writes for a stream shape, from the host code alone (host_framing.h,
+// build_parameter_sets): shape = the fourteen fields of StreamShape in order.  Returns the bytes, or -1 when cap is too small
+int32_t vc_debug_parameter_sets(const int32_t *shape, uint8_t *dst, int32_t cap)
+{
+    const StreamShape f{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9], shape[10], shape[11], shape[12], shape[13]};
+    const std::vector<uint8_t> ps = build_parameter_sets(f);
+    if (static_cast<size_t>(cap) < ps.size()) return -1;
+    std::memcpy(dst, ps.data(), ps.size());
+    return static_cast<int32_t>(ps.size());
+}
+// level_idc the library picks for a picture of mbs macroblocks at fps (host_framing.h, pick_level; never below 3.2)
+int32_t vc_debug_level(int32_t mbs, int32_t fps) { return std::max(32, pick_level(mbs, fps)); }
 // The one rule for a picture's number of reference pictures (PicSeq::avail_refs, shared by the engine and the stream hub), driven
 // as both drive it: n pictures of a stream that searches nrefs pictures with an IDR every gop; force[i] != 0 forces an IDR at
 // picture i.  out[i] = the count of picture i (0: an IDR picture).

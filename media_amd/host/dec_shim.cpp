@@ -3,6 +3,7 @@
 // SetCopyFrameFunc -> Start -> (SendStreamData, RetrieveFrameData) x N -> Stop -> Destroy.
 #include <cstring>
 #include "VideoDecoder.h"
+#include "VideoDecoderMI355X.h"
 
 extern "C" {
 struct vd_events { uint32_t count, width, height, stride; };
@@ -37,6 +38,19 @@ uint32_t vd_get_port_format(void *dec, uint32_t port, int32_t *format)
     const uint32_t rc = static_cast<VideoDecoder *>(dec)->GetDecodeParams(INDEX_PORT_FORMAT_INFO, &p);
     *format = p.format;
     return rc;
+}
+uint32_t vd_set_port_format(void *dec, uint32_t port, int32_t format)
+{
+    PortFormatParams p;
+    p.port = static_cast<DecoderPort>(port);
+    p.format = format;
+    return static_cast<VideoDecoder *>(dec)->SetDecodeParams(INDEX_PORT_FORMAT_INFO, &p);
+}
+// what the last picture's sequence parameter set says about colour (out8: mi355x_h264_dec_colour) and how often that has changed
+uint32_t vd_colour(void *dec, int32_t *out8)
+{
+    auto *m = dynamic_cast<VideoDecoderMI355X *>(static_cast<VideoDecoder *>(dec));
+    return m != nullptr ? m->ColourChanges(out8) : 0;
 }
 uint32_t vd_get_align(void *dec, uint32_t *out2)
 {

@@ -41,6 +41,11 @@ def lib():
         L.vc_debug_ref_counts.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
         L.vc_debug_ref_counts.restype = None
         L.vc_last_qp.argtypes = [vp]
+        i32p = C.POINTER(C.c_int32)
+        L.vc_parse_colour.argtypes = [C.c_char_p, C.c_char_p, i32p, i32p]
+        L.vc_colour.argtypes = [vp, i32p, i32p]
+        L.vc_debug_parameter_sets.argtypes = [i32p, vp, C.c_int32]
+        L.vc_debug_level.argtypes = [C.c_int32, C.c_int32]
         L.vc_scene_cuts.argtypes = [vp]
         L.vc_scene_cuts.restype = C.c_uint32
         L.vc_debug_recon_y.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -92,6 +97,30 @@ def parse_source_size(width, height, coded_width, coded_height):
     return (sw.value, sh.value) if rc > 0 else None if rc == 0 else False
 
 
+def parse_colour(colour, rng):
+    """what persist.vmi.video.encode.colour = colour and .range = rng select: (matrix code, full_range) when either is set and both
+    are valid ("bt601" | "bt709", "limited" | "full"; the absent one: bt601 / limited); None when neither is set; False for
+    anything else (the reference's behaviour, with a WARN line)"""
+    m, f = C.c_int32(), C.c_int32()
+    rc = lib().vc_parse_colour(str(colour).encode(), str(rng).encode(), C.byref(m), C.byref(f))
+    return (m.value, f.value) if rc > 0 else None if rc == 0 else False
+
+
+def parameter_sets(profile_idc, nrefs, width, height, fps=30, slices=1, disable_deblock=0, colour=None, chroma_loc=False):
+    """the Annex-B SPS + PPS the library writes for such a stream, from the host code alone (media_amd/csrc/host_framing.h through
+    the shim; no device): colour = (matrix code, full_range) for a described stream, chroma_loc for one of RGBA input"""
+    import numpy as np
+    mbw, mbh = (width + 15) // 16, (height + 15) // 16
+    level = lib().vc_debug_level(mbw * mbh, fps)
+    shape = (C.c_int32 * 14)(profile_idc, level, nrefs, mbw, mbh, width, height, slices, disable_deblock,
+                             0 if colour is None else 1, 6 if colour is None else colour[0], 0 if colour is None else colour[1], int(bool(chroma_loc)), fps)
+    buf = np.zeros(512, np.uint8)
+    n = lib().vc_debug_parameter_sets(shape, buf.ctypes.data, buf.size)
+    if n < 0:
+        raise RuntimeError("parameter sets larger than %d bytes" % buf.size)
+    return buf[:n].tobytes()
+
+
 def ref_counts(nrefs, gop, n, forced=()):
     """the number of reference pictures of each of n pictures of a stream that searches nrefs, IDR every gop pictures and at the
     pictures in `forced` (the rule the engine and the stream hub share; 0 = an IDR picture)"""
@@ -102,7 +131,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None, refs=None, psnr=None, shared=None, srcwidth=None, srcheight=None):
+                   inputmem=None, refs=None, psnr=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -123,6 +152,8 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.psnr", "" if psnr is None else psnr)               # 1: quality report; else off
     prop_set("persist.vmi.video.encode.srcwidth", "" if srcwidth is None else srcwidth)   # both set and valid: pictures of that
     prop_set("persist.vmi.video.encode.srcheight", "" if srcheight is None else srcheight)   # size, resampled to width x height
+    prop_set("persist.vmi.video.encode.colour", "" if colour is None else colour)         # bt601 | bt709 } either one set and valid: a
+    prop_set("persist.vmi.video.encode.range", "" if range is None else range)            # limited | full } described stream
     if shared is not None:
         prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 
@@ -176,6 +207,11 @@ class VideoEncoder:
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)
+
+    def colour(self):
+        """(matrix code, full_range) the engine was opened with (persist.vmi.video.encode.colour / .range), or None"""
+        m, f = C.c_int32(), C.c_int32()
+        return (m.value, f.value) if lib().vc_colour(self.h, C.byref(m), C.byref(f)) == 1 else None
 
     def recon_y(self):
         """luma reconstruction of the last picture, coded size (measurement hook)"""

@@ -10,7 +10,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libVideoDecoder.so")
 (SUCCESS, CREATE_FAIL, INIT_FAIL, START_FAIL, DECODE_FAIL, STOP_FAIL, DESTROY_FAIL, RESET_FAIL, GET_PARAMS_FAIL, SET_PARAMS_FAIL,
  SET_FUNC_FAIL, WRITE_OVERFLOW, READ_UNDERFLOW, BAD_PIC_SIZE, EOS) = range(15)
 STREAM_AVC, STREAM_HEVC = 0, 1
-PIXEL_FORMAT_YUV_420P = 1
+PIXEL_FORMAT_RGBA_8888, PIXEL_FORMAT_YUV_420P = 0, 1
+IN_PORT, OUT_PORT = 0, 1
 
 
 class Events(C.Structure):
@@ -31,7 +32,8 @@ def lib():
                            ("vd_start", [vp]), ("vd_stop", [vp]), ("vd_flush", [vp]), ("vd_send", [vp, vp, u32]),
                            ("vd_retrieve", [vp, vp, u32, C.POINTER(u32)]), ("vd_set_pic_info", [vp, u32, u32, C.c_int32]),
                            ("vd_get_pic_info", [vp, C.POINTER(u32)]), ("vd_get_port_format", [vp, u32, C.POINTER(C.c_int32)]),
-                           ("vd_get_align", [vp, C.POINTER(u32)]), ("vd_install_hooks", [vp, C.POINTER(Events)])):
+                           ("vd_get_align", [vp, C.POINTER(u32)]), ("vd_set_port_format", [vp, u32, C.c_int32]),
+                           ("vd_colour", [vp, C.POINTER(C.c_int32)]), ("vd_install_hooks", [vp, C.POINTER(Events)])):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = u32
         L.vd_destroy.argtypes = [vp]
@@ -62,6 +64,16 @@ class PluginDecoder:
     def port_format(self, port):
         f = C.c_int32(-1)
         return lib().vd_get_port_format(self.h, port, C.byref(f)), f.value
+
+    def set_port_format(self, port, fmt):
+        """SetDecodeParams(INDEX_PORT_FORMAT_INFO): the out port takes PIXEL_FORMAT_YUV_420P or PIXEL_FORMAT_RGBA_8888"""
+        return lib().vd_set_port_format(self.h, port, fmt)
+
+    def colour(self):
+        """(what the last picture's sequence parameter set says: the eight values of mi355x_h264_dec_colour, changes since start)"""
+        v = (C.c_int32 * 8)()
+        n = lib().vd_colour(self.h, v)
+        return list(v), n
 
     def align(self):
         v = (C.c_uint32 * 2)()

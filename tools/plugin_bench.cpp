@@ -5,7 +5,7 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--refs N] [--psnr] [--src WxH] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--refs N] [--psnr] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
@@ -15,6 +15,9 @@
 // --src WxH (anywhere on the line): the extension keys persist.vmi.video.encode.srcwidth / .srcheight = W / H - the file holds
 // pictures of W x H, which every object hands over as they are and the device resamples to the coded size (<width> <height> and
 // the geometry keys stay the coded size's).
+// --colour C / --range R (anywhere on the line): the extension keys persist.vmi.video.encode.colour / .range - every object's
+// stream carries that colour description in its SPS, and RGBA pictures are converted with it (include/mi355x_h264.h, "colour
+// description"); the values go to the library as they are, which takes bt601 | bt709 and limited | full.
 // input (optional; without it everything is as above): i420 | nv12 | rgba, with ":device" behind it for pictures in device
 // memory - the extension keys persist.vmi.video.encode.input / .inputmem.  The pictures of the file are converted to the layout
 // on the host before the clock starts; for device memory they are uploaded once, before the clock, and every stream cycles
@@ -63,7 +66,15 @@ int main(int argc, char **argv)
             argc -= 2;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--src WxH] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    for (const char *opt : {"--colour", "--range"})   // --colour C, --range R: taken out of the line
+        for (int i = 1; i + 1 < argc; i++)
+            if (strcmp(argv[i], opt) == 0) {
+                setenv(strcmp(opt, "--colour") == 0 ? "PERSIST_VMI_VIDEO_ENCODE_COLOUR" : "PERSIST_VMI_VIDEO_ENCODE_RANGE", argv[i + 1], 1);
+                for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+                argc -= 2;
+                break;
+            }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     // (w, h: the size of the pictures in the file and in every call - the source size with --src)
     const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
