@@ -490,6 +490,49 @@ int mi355x_h264_stream_quality_enable(mi355x_h264_stream *s, int on);
 int mi355x_h264_stream_last_quality(const mi355x_h264_stream *s, mi355x_h264_quality *out);
 int64_t mi355x_h264_stream_quality_map(mi355x_h264_stream *s, uint32_t *dst, size_t cap);
 
+/* ---- quality report: SSIM per plane and per macroblock, beside the SSE (tests/ssim.py restates this text in numpy) ----
+ * Definition.  src, rec, "display samples" and the plane order Y, U, V are those of the SSE definition above.  A plane is W x H
+ * display samples; the chroma planes are width / 2 x height / 2, which may be odd.
+ * Windows.  A window is 8x8 samples with its origin at (4i, 4j).  It counts when it lies wholly inside the plane's display samples:
+ * 4i + 8 <= W and 4j + 8 <= H, so a plane has (W / 4 - 1) * (H / 4 - 1) windows (integer division): a 16x16 picture has 9 luma
+ * windows and one per chroma plane.  A window is never shortened.  A band instance (band_count > 1) counts the windows whose
+ * origin row lies in its own macroblock rows and whose last row does too: its limit is min(H, 16 * (row0 + rows)) for luma and
+ * min(H / 2, 8 * (row0 + rows)) for chroma.  Windows that straddle two bands belong to nobody: UNLIKE the SSE, the band records do
+ * NOT add up to the single instance's; windows[] says how many were counted.
+ * Per window, all integers, the sums over its 64 samples:
+ *   s1 = sum src, s2 = sum rec, ss = sum (src^2 + rec^2), s12 = sum src * rec
+ *   vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2
+ *   C1 = 416, C2 = 235963   (the usual (0.01 * 255)^2 * 64 and (0.03 * 255)^2 * 64 * 63, rounded)
+ *   l = floor(((2 s1 s2 + C1) << 16) / (s1^2 + s2^2 + C1))      in 0 .. 65536
+ *   c = floor(((2 covar + C2) << 16) / (vars + C2))             in -65535 .. 65536; floor, not truncation: the numerator can be negative
+ *   q = (l * c) >> 16                                           a 64-bit product, an arithmetic shift
+ * Every term before the shifts fits 31 bits, the shifted numerators stay below 2^47, 2 |covar| <= vars.  q / 65536 is within 4.6e-5
+ * of the floating-point SSIM of the window.  Identical windows: 65536, 65536, 65536; constant 100 against constant 110: 65239,
+ * 65536, 65239; constant 0 against 255: 0, 65536, 0; 32 samples of 0 and 32 of 255 against its inverse: 65536, -65305, -65305.
+ * Per picture: sum[3], int64, the sum of q over the plane's windows; windows[3], the window count per plane; a luma map
+ * int32_t [rows][columns of macroblocks], each entry the sum of q of the luma windows whose ORIGIN lies in the macroblock (at
+ * most 16 windows, so an entry stays inside +-2^20), 0 outside a band instance's band; the map adds up to sum[0].  The mean SSIM of a
+ * plane is sum / (65536 * windows): the caller's to compute, as PSNR is.  The device computes, sums and returns no float.
+ * The SSIM record accompanies the SSE record, which carries bytes, QP and type: metrics = MI355X_H264_QUALITY_SSE (exactly what
+ * mi355x_h264_quality_enable(enc, 1) does), SSE | SSIM (both), or 0 (off); SSIM alone and any other bit: MI355X_H264_E_ARG.
+ * mi355x_h264_quality_enable(enc, on) equals _ex(enc, on ? 1 : 0).  With SSIM not asked for nothing differs: no launch, copy,
+ * allocation, byte or record; k_ssim's pinned arrays come with the first enable that asks for it.  On: one more kernel (k_ssim)
+ * behind k_sse, off the chain like it.  MI355X_H264_QUALITY=3 in the environment turns both on when an engine is created.
+ * Records are read like the SSE records and in their order; an injected or refused picture has valid = 0; nothing to read (SSIM was
+ * not on for the last call, no picture yet), null handles and a small cap behave as their SSE counterparts do. */
+enum { MI355X_H264_QUALITY_SSE = 1, MI355X_H264_QUALITY_SSIM = 2 };
+typedef struct mi355x_h264_ssim {
+    int64_t  sum[3];
+    uint64_t windows[3];
+    uint32_t valid, reserved;
+} mi355x_h264_ssim;
+int mi355x_h264_quality_enable_ex(mi355x_h264_encoder *enc, unsigned metrics);
+int mi355x_h264_stream_quality_enable_ex(mi355x_h264_stream *s, unsigned metrics);
+int64_t mi355x_h264_quality_ssim_read(mi355x_h264_encoder *enc, mi355x_h264_ssim *dst, size_t cap);
+int64_t mi355x_h264_quality_ssim_map(mi355x_h264_encoder *enc, int item, int32_t *dst, size_t cap);
+int mi355x_h264_stream_last_ssim(const mi355x_h264_stream *s, mi355x_h264_ssim *out);
+int64_t mi355x_h264_stream_ssim_map(mi355x_h264_stream *s, int32_t *dst, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

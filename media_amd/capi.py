@@ -35,6 +35,8 @@ EXPORTS = [
     "mi355x_h264_stream_open_ex", "mi355x_h264_stream_open_scaled", "mi355x_h264_stream_source_width", "mi355x_h264_stream_source_height",
     "mi355x_h264_quality_enable", "mi355x_h264_quality_read", "mi355x_h264_quality_map",
     "mi355x_h264_stream_quality_enable", "mi355x_h264_stream_last_quality", "mi355x_h264_stream_quality_map",
+    "mi355x_h264_quality_enable_ex", "mi355x_h264_stream_quality_enable_ex", "mi355x_h264_quality_ssim_read", "mi355x_h264_quality_ssim_map",
+    "mi355x_h264_stream_last_ssim", "mi355x_h264_stream_ssim_map",
     "mi355x_h264_debug_mem_guard", "mi355x_h264_debug_mem_guard_get", "mi355x_h264_debug_mem_tally", "mi355x_h264_debug_mem_check",
     "mi355x_h264_debug_mem_poke", "mi355x_h264_stream_debug_mem_check", "mi355x_h264_dec_debug_mem_check",
     "mi355x_h264_dec_group_debug_mem_check", "mi355x_h264_dec_group_debug_mem_poke",
@@ -99,6 +101,27 @@ def psnr(sse, samples):
     if not samples:
         return float("nan")
     return float("inf") if sse == 0 else 10.0 * math.log10(65025.0 * samples / sse)
+
+
+class Ssim(C.Structure):
+    """mi355x_h264_ssim"""
+    _fields_ = [("sum", C.c_int64 * 3), ("windows", C.c_uint64 * 3), ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+QUALITY_SSE, QUALITY_SSIM = 1, 2   # MI355X_H264_QUALITY_*
+
+
+def ssim_mean(total, windows):
+    """sum / (65536 * windows) on the host (nothing compared: nan)"""
+    return total / (65536.0 * windows) if windows else float("nan")
+
+
+def _with_ssim(rec, s):
+    """the SSIM record s (an Ssim) added to the SSE record's dict: `ssim` (Y, U, V means), `ssim_sum`, `ssim_windows`"""
+    tot, win = [int(v) for v in s.sum], [int(v) for v in s.windows]
+    rec["ssim_sum"], rec["ssim_windows"] = tot, win
+    rec["ssim"] = [ssim_mean(a, b) if s.valid else float("nan") for a, b in zip(tot, win)]
+    return rec
 
 
 def _quality_record(q):
@@ -182,6 +205,16 @@ def lib():
         L.mi355x_h264_stream_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355x_h264_stream_quality_map.argtypes = [vp, vp, C.c_size_t]
         L.mi355x_h264_stream_quality_map.restype = C.c_int64
+        if hasattr(L, "mi355x_h264_quality_enable_ex"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no SSIM)
+            L.mi355x_h264_quality_enable_ex.argtypes = [vp, C.c_uint]
+            L.mi355x_h264_stream_quality_enable_ex.argtypes = [vp, C.c_uint]
+            L.mi355x_h264_quality_ssim_read.argtypes = [vp, C.POINTER(Ssim), C.c_size_t]
+            L.mi355x_h264_quality_ssim_read.restype = C.c_int64
+            L.mi355x_h264_quality_ssim_map.argtypes = [vp, C.c_int, vp, C.c_size_t]
+            L.mi355x_h264_quality_ssim_map.restype = C.c_int64
+            L.mi355x_h264_stream_last_ssim.argtypes = [vp, C.POINTER(Ssim)]
+            L.mi355x_h264_stream_ssim_map.argtypes = [vp, vp, C.c_size_t]
+            L.mi355x_h264_stream_ssim_map.restype = C.c_int64
         L.mi355x_h264_stats_enable.argtypes = [vp, C.c_int]
         if hasattr(L, "mi355x_h264_debug_mem_guard"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no guard mode)
             L.mi355x_h264_debug_mem_guard.argtypes = [C.c_int64, C.c_int]
@@ -424,9 +457,14 @@ class Encoder:
     def debug_read(self, what):
         return _debug_read(self, lib().mi355x_h264_debug_read, what)
 
-    def quality_enable(self, on=True):
-        """the quality report (mi355x_h264_quality_enable): SSE per plane and per macroblock of every picture from the next one on"""
-        self._check(lib().mi355x_h264_quality_enable(self.h, int(on)))
+    def quality_enable(self, on=True, ssim=False):
+        """the quality report (mi355x_h264_quality_enable): SSE per plane and per macroblock of every picture from the next one on;
+        ssim: SSIM beside it (mi355x_h264_quality_enable_ex with both metrics)"""
+        if on and ssim:
+            self._check(lib().mi355x_h264_quality_enable_ex(self.h, QUALITY_SSE | QUALITY_SSIM))
+        else:
+            self._check(lib().mi355x_h264_quality_enable(self.h, int(on)))
+        self._ssim = bool(on and ssim)
 
     def quality(self, cap=None):
         """the records of every picture of the last call, in the order of sizes[] (mi355x_h264_quality_read), as dicts with `psnr`
@@ -436,7 +474,21 @@ class Encoder:
         got = lib().mi355x_h264_quality_read(self.h, a, n)
         if got < 0:
             self._check(int(got))
-        return [_quality_record(a[i]) for i in range(got)]
+        recs = [_quality_record(a[i]) for i in range(got)]
+        if getattr(self, "_ssim", False) or os.environ.get("MI355X_H264_QUALITY") == "3":   # (SSIM off: the dictionaries are what they were)
+            b = (Ssim * max(n, 1))()
+            if lib().mi355x_h264_quality_ssim_read(self.h, b, n) == got:
+                recs = [_with_ssim(r, b[i]) for i, r in enumerate(recs)]
+        return recs
+
+    def ssim_map(self, item=0):
+        """the sum of q over the luma windows whose origin lies in the macroblock, of the last picture of batch item `item`: int32
+        (rows, columns)"""
+        m = np.zeros((self.ch // 16, self.cw // 16), np.int32)
+        got = lib().mi355x_h264_quality_ssim_map(self.h, item, m.ctypes.data, m.size)
+        if got < 0:
+            self._check(int(got))
+        return m
 
     def quality_map(self, item=0):
         """SSE per macroblock (all planes added) of the last picture of batch item `item`: uint32 (rows, columns)"""
@@ -588,15 +640,31 @@ class Stream:
         """keep the pre-filter planes of every stream of this stream's engine (mi355x_h264_stream_debug_keep_pre)"""
         self._check(lib().mi355x_h264_stream_debug_keep_pre(self.h, int(on)))
 
-    def quality_enable(self, on=True):
-        """the quality report for every stream of this stream's engine (mi355x_h264_stream_quality_enable)"""
-        self._check(lib().mi355x_h264_stream_quality_enable(self.h, int(on)))
+    def quality_enable(self, on=True, ssim=False):
+        """the quality report for every stream of this stream's engine (mi355x_h264_stream_quality_enable); ssim: SSIM beside the
+        SSE (mi355x_h264_stream_quality_enable_ex with both metrics)"""
+        if on and ssim:
+            self._check(lib().mi355x_h264_stream_quality_enable_ex(self.h, QUALITY_SSE | QUALITY_SSIM))
+        else:
+            self._check(lib().mi355x_h264_stream_quality_enable(self.h, int(on)))
 
     def quality(self):
         """the record of this stream's last picture, `psnr` added; raises EncoderError (rc = E_ARG) when there is none"""
         q = Quality()
         self._check(lib().mi355x_h264_stream_last_quality(self.h, C.byref(q)))
-        return _quality_record(q)
+        rec, s = _quality_record(q), Ssim()
+        # (the switch belongs to the shared engine, so another stream may have asked for SSIM: the record says whether there is one)
+        if lib().mi355x_h264_stream_last_ssim(self.h, C.byref(s)) == 0:
+            rec = _with_ssim(rec, s)
+        return rec
+
+    def ssim_map(self):
+        """the sum of q over the luma windows whose origin lies in the macroblock, of this stream's last picture: int32 (rows, columns)"""
+        m = np.zeros((self.ch // 16, self.cw // 16), np.int32)
+        got = lib().mi355x_h264_stream_ssim_map(self.h, m.ctypes.data, m.size)
+        if got < 0:
+            self._check(int(got))
+        return m
 
     def quality_map(self):
         """SSE per macroblock of this stream's last picture: uint32 (rows, columns)"""

@@ -11,7 +11,8 @@ constexpr int NSLOT = 3;          // access-unit slots in flight
 
 // where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
 struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0;
-                  int quality = 0; };   // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
+                  int quality = 0;      // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
+                  int ssim = 0; };      // the SSIM record accompanies it (compared: k_ssim ran behind k_sse)
 
 struct Slot {
     uint32_t* d_bitbuf = nullptr;   // device slice payload (zeroed before use)
@@ -21,6 +22,8 @@ struct Slot {
     AuLayout lay;                   // of the picture in flight
     unsigned long long* h_qpart = nullptr;   // quality report (pinned, with the first enable): [G][mbh][SSE_SEGS][3] plane sums per wave of k_sse
     uint32_t* h_qmap = nullptr;              //   and [G][nmb] sums per macroblock, stored by k_sse; rows outside the band stay 0
+    long long* h_spart = nullptr;            // SSIM (pinned, with the first enable that asks for it): [G][mbh][SSIM_SEGS][3] plane sums per wave of k_ssim
+    int32_t* h_smap = nullptr;               //   and [G][nmb] luma sums per macroblock, stored by k_ssim; rows outside the band stay 0
     bool busy = false;
     StepSync sync;                  // on the engine's stream pair
     // stats events of this frame: pairs (start, stop, kernel id, launches, mbs)
@@ -90,6 +93,12 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     std::vector<uint8_t> q_have;             // [G] the item has a record
     std::vector<mi355x_h264_quality> q_recs; // the records of the last call, in the order of sizes[]: item g's goes to g * q_mul + q_add
     size_t q_mul = 1, q_add = 0;
+    // SSIM beside the SSE (mi355x_h264_quality_enable_ex with MI355X_H264_QUALITY_SSIM; allocated with the first enable that asks for it)
+    bool ssim_on = false, ssim_ready = false;
+    std::vector<mi355x_h264_ssim> s_item;    // [G] as q_item
+    std::vector<const int32_t*> s_map;       // [G] as q_map
+    std::vector<uint8_t> s_have;             // [G] the item has an SSIM record
+    std::vector<mi355x_h264_ssim> s_recs;    // as q_recs, same order
     char err[256] = {0};
 };
 
@@ -412,6 +421,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
     // kernel when nothing is filtered).  On the second stream, beside the entropy coder and behind the filter's event: the chain to the
     // next picture's k_me (this stream) does not wait for it.  An injected picture's ring holds nothing to compare.
     T.lay.quality = !e->quality_on ? 0 : (T.inj ? 2 : 1);
+    T.lay.ssim = T.lay.quality && e->ssim_on;
     const bool compare = T.lay.quality == 1;
     if (compare) {
         if (fork) {
@@ -419,6 +429,8 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             HIPCHK(e->err, hipStreamWaitEvent(ec, e->q_ready, 0));
         }
         LAUNCH2(ind, k_sse<true>, k_sse<false>, dim3((unsigned)e->b_rows * SSE_SEGS, G), dim3(64), ec, P, S.h_qpart, S.h_qmap);
+        // SSIM: behind k_sse on the same stream and in front of q_done[cur] and `done`, so the three hazards hold for it unchanged
+        if (T.lay.ssim) LAUNCH2(ind, k_ssim<true>, k_ssim<false>, dim3((unsigned)e->b_rows * SSIM_SEGS, G), dim3(64), ec, P, S.h_spart, S.h_smap);
         if (!ind) { HIPCHK(e->err, hipEventRecord(e->q_done[cur], ec)); e->q_done_set[cur] = true; }   // (hazard "ring slot", above)
     }
     if (fork) HIPCHK(e->err, hipStreamWaitEvent(st, Y.entropy_done, 0));   // join: the next picture rewrites MbInfo / levels
@@ -560,13 +572,38 @@ void quality_record(mi355x_h264_encoder* e, const Slot& S, const AuLayout& L, in
     e->q_have[g] = 1;
     const size_t idx = (size_t)g * e->q_mul + e->q_add;
     if (idx < e->q_recs.size()) e->q_recs[idx] = q;
+    if (!e->ssim_ready) return;
+    // the SSIM record beside it (k_ssim left one partial per wave and plane; the window counts follow from the geometry)
+    e->s_map[g] = nullptr;
+    e->s_have[g] = 0;
+    if (!L.ssim) return;
+    mi355x_h264_ssim s{};
+    if (compared) {
+        const long long* part = S.h_spart + ((size_t)g * e->mbh + e->b_row0) * SSIM_SEGS * 3;
+        for (int r = 0; r < e->b_rows * SSIM_SEGS; r++)
+            for (int p = 0; p < 3; p++) s.sum[p] += part[(size_t)r * 3 + p];
+        // windows at (4i, 4j) that lie wholly inside the display samples of the band's rows
+        const int w = e->cfg.width, h = e->cfg.height;
+        const int yl = std::min(h, 16 * (e->b_row0 + e->b_rows)) - 16 * e->b_row0, cl = std::min(h / 2, 8 * (e->b_row0 + e->b_rows)) - 8 * e->b_row0;
+        auto count = [](int span) { return (uint64_t)std::max(0, span / 4 - 1); };
+        s.windows[0] = count(w) * count(yl);
+        s.windows[1] = s.windows[2] = count(w / 2) * count(cl);
+        s.valid = 1;
+        e->s_map[g] = S.h_smap + (size_t)g * e->nmb;
+    }
+    e->s_item[g] = s;
+    e->s_have[g] = 1;
+    if (idx < e->s_recs.size()) e->s_recs[idx] = s;
 }
 
 int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
     const int rc = finish_au(e, S, L, g, out, out_len, frame_type);
     if (L.quality) quality_record(e, S, L, g, rc == MI355X_H264_OK ? *out_len : 0, rc == MI355X_H264_OK && L.quality == 1);
-    else if (!e->q_have.empty()) e->q_have[g] = 0;   // (coded with the switch off: nothing to read for this picture)
+    else {   // (coded with the switch off: nothing to read for this picture)
+        if (!e->q_have.empty()) e->q_have[g] = 0;
+        if (!e->s_have.empty()) e->s_have[g] = 0;
+    }
     return rc;
 }
 
@@ -575,6 +612,8 @@ void quality_begin(mi355x_h264_encoder* e, size_t n, size_t mul, size_t add)
 {
     e->q_recs.clear();
     if (e->quality_on) e->q_recs.resize(n);   // (valid = 0 until the picture is finished)
+    e->s_recs.clear();
+    if (e->quality_on && e->ssim_on) e->s_recs.resize(n);
     e->q_mul = mul; e->q_add = add;
 }
 
@@ -598,13 +637,35 @@ hipError_t quality_alloc(mi355x_h264_encoder* e)
     HIPTRY(hipEventCreateWithFlags(&e->q_ready, hipEventDisableTiming));
     return hipSuccess;
 }
-int quality_set(mi355x_h264_encoder* e, bool on)
+// k_ssim's pinned result arrays, in every slot: with the first enable that asks for SSIM
+hipError_t ssim_alloc(mi355x_h264_encoder* e)
 {
-    if (on) {
-        const hipError_t r = quality_alloc(e);
+    if (e->ssim_ready) return hipSuccess;
+    HIPTRY(hipSetDevice(e->device));
+    const size_t Gn = (size_t)e->G, part = Gn * e->mbh * SSIM_SEGS * 3 * sizeof(long long), map = Gn * e->nmb * sizeof(int32_t);
+    for (int si = 0; si < e->nslots; si++) {
+        Slot& S = e->slots[si];
+        if (!S.h_spart) { HIPTRY(DM_PINNED(e->mem, S.h_spart, part)); memset(S.h_spart, 0, part); }
+        if (!S.h_smap) { HIPTRY(DM_PINNED(e->mem, S.h_smap, map)); memset(S.h_smap, 0, map); }   // (rows outside the band stay 0)
+    }
+    e->s_item.assign(Gn, mi355x_h264_ssim{});
+    e->s_map.assign(Gn, nullptr);
+    e->s_have.assign(Gn, 0);
+    e->ssim_ready = true;
+    return hipSuccess;
+}
+// metrics: MI355X_H264_QUALITY_* bits; 0 off, SSE alone, or both (SSIM alone is refused: its record accompanies the SSE record)
+int quality_set(mi355x_h264_encoder* e, unsigned metrics)
+{
+    if (!quality_metrics_ok(metrics))
+        return set_err(e->err, MI355X_H264_E_ARG, "quality report: metrics must be 0, MI355X_H264_QUALITY_SSE, or SSE | SSIM (the SSIM record accompanies the SSE record)");
+    if (metrics) {
+        hipError_t r = quality_alloc(e);
+        if (r == hipSuccess && (metrics & MI355X_H264_QUALITY_SSIM)) r = ssim_alloc(e);
         if (r != hipSuccess) return set_err(e->err, r == hipErrorOutOfMemory ? MI355X_H264_E_NOMEM : MI355X_H264_E_HIP, "quality report: %s: %s", t_failed_call, hipGetErrorString(r));
     }
-    e->quality_on = on;
+    e->quality_on = metrics != 0;
+    e->ssim_on = (metrics & MI355X_H264_QUALITY_SSIM) != 0;
     return MI355X_H264_OK;
 }
 
@@ -771,9 +832,9 @@ int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool
         destroy_engine(e);
         return r == hipErrorOutOfMemory ? MI355X_H264_E_NOMEM : MI355X_H264_E_HIP;
     }
-    {   // MI355X_H264_QUALITY=1: the quality report is on from the first picture (mi355x_h264_quality_enable)
-        const char* q = getenv("MI355X_H264_QUALITY");
-        if (q && q[0] == '1' && !q[1] && quality_set(e, true) != MI355X_H264_OK) {
+    {   // MI355X_H264_QUALITY=1: the quality report is on from the first picture (mi355x_h264_quality_enable); =3: with SSIM (_enable_ex)
+        const unsigned metrics = quality_env_metrics(getenv("MI355X_H264_QUALITY"));
+        if (metrics && quality_set(e, metrics) != MI355X_H264_OK) {
             fprintf(stderr, "mi355x_h264_create: %s\n", e->err);
             destroy_engine(e);
             return MI355X_H264_E_HIP;

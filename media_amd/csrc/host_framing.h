@@ -296,6 +296,12 @@ inline void pack_picture(const HostPicture& in, int w, int h, uint8_t* dst)
     }
 }
 
+// Quality report: the metrics the switch takes (include/mi355x_h264.h: bit 0 SSE, bit 1 SSIM).  Off, the SSE alone, or both: the
+// SSIM record accompanies the SSE record, so SSIM alone is refused like any other bit.  And what MI355X_H264_QUALITY in the
+// environment turns on when an engine is created: "1" the SSE, "3" both, anything else nothing.
+bool quality_metrics_ok(unsigned metrics) { return metrics == 0 || metrics == 1 || metrics == 3; }
+unsigned quality_env_metrics(const char* v) { return v && (v[0] == '1' || v[0] == '3') && !v[1] ? (unsigned)(v[0] - '0') : 0u; }
+
 int pick_level(int mbs, int fps)
 {
     for (const auto& l : h_levels)

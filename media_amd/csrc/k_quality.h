@@ -97,4 +97,125 @@ __global__ __launch_bounds__(64) void k_sse(FrameParams P0, unsigned long long* 
     }
 }
 
+// ---- SSIM (include/mi355x_h264.h, "quality report: SSIM"): Q16 integers per 8x8 window at every (4i, 4j), per plane and, for
+// luma, per macroblock.  Exact like the SSE: every term is an integer, so the result does not depend on the order of summation.
+//
+// Waves over (macroblock row, segment) as in k_sse, SSIM_SEGS of them to a row.  A lane is one 4x4 BLOCK of a macroblock: lanes 0..24 the 5x5 luma blocks at
+// (4 bx, 4 by) from the macroblock's origin (column 4 and row 4 are the next macroblock's and the next row's first blocks, loaded
+// again rather than handed between waves), lanes 32..40 the 3x3 blocks of Cb, lanes 48..56 those of Cr.  A lane reads its block as four
+// source words (src_luma4 / src_chroma4: in place, from any byte) and four reconstruction words and keeps the block's sums s1, s2,
+// ss, s12 (v_dot4_u32_u8).  A window is 2x2 blocks: the lane of its upper left block fetches the other three (ds_bpermute; s1 and
+// s2 travel in one word) and evaluates it.  A window that does not lie wholly inside the display samples (the band's limit for a
+// band instance) is masked out whole, never shortened; the loads behind it are clamped into the picture, so they stay uniform.
+// The two divisions: the numerators are below 2^47 in magnitude and the divisors between 416 and 2^30, so both are doubles exactly;
+// the quotient is computed in double precision (one correctly rounded division), floored, and then CORRECTED by one step from the
+// integer remainder n - q d (exact in 64 bits).  The rounded quotient is within 1 of the true one, so a single step either way gives
+// the floor whatever the rounding did; nothing rests on the rounding mode.  (The 64-bit integer division is exact as well and was
+// measured slower: DESIGN.md section 8.)
+// Results as in k_sse: plain stores into the step's pinned memory, one int64 triple per wave, map entries in stores of up to 64 words.
+enum { SSIM_C1 = 416, SSIM_C2 = 235963 };
+enum { SSIM_SEGS = 8 };   // waves per macroblock row (measured at 1080p, DESIGN.md section 8: 4, 8 and 16 give 37 / 22 / 16 us for a lone picture and 374 / 296 / 365 us for 32)
+
+// floor(n / d) for |n| < 2^47, 416 <= d < 2^30; the quotient fits 18 bits
+__device__ __forceinline__ int ssim_floor_div(long long n, int d)
+{
+#ifdef SSIM_AB_IDIV   // A/B build (Makefile target `ab`): the 64-bit integer division as the compiler expands it, measured in DESIGN.md section 8
+    const long long t = n / (long long)d;
+    return (int)(n - t * (long long)d < 0 ? t - 1 : t);
+#else
+    int q = (int)floor((double)n / (double)d);
+    const long long r = n - (long long)q * (long long)d;
+    q += r < 0 ? -1 : (r >= (long long)d ? 1 : 0);
+    return q;
+#endif
+}
+
+// the window of four blocks: s = s1 | s2 << 16 (each at most 16 * 255), ss = sum of src^2 + rec^2, s12 = sum of src * rec
+__device__ __forceinline__ int ssim_window(uint32_t s, uint32_t ss, uint32_t s12)
+{
+    const int s1 = (int)(s & 0xFFFFu), s2 = (int)(s >> 16);
+    const int vars = 64 * (int)ss - s1 * s1 - s2 * s2;
+    const int covar = 64 * (int)s12 - s1 * s2;
+    const int l = ssim_floor_div((long long)(2 * s1 * s2 + SSIM_C1) << 16, s1 * s1 + s2 * s2 + SSIM_C1);
+    const int c = ssim_floor_div((long long)(2 * covar + SSIM_C2) * 65536, vars + SSIM_C2);
+    return (int)(((long long)l * (long long)c) >> 16);
+}
+
+// part: [item][mbh][SSIM_SEGS][3] plane sums (Y, U, V) of the windows whose origin lies in a wave's part of a macroblock row;
+// map: [item][mbh * mbw] the sum of the luma windows whose origin lies in the macroblock
+template <bool IND>
+__global__ __launch_bounds__(64) void k_ssim(FrameParams P0, long long* __restrict__ part, int32_t* __restrict__ map)
+{
+    const int lane = threadIdx.x, pos = blockIdx.y;
+    const FrameParams P = batch_view<IND>(P0, pos);
+    const int g = batch_item<IND>(P0.itemtab, pos);
+    const int seg = (int)blockIdx.x % SSIM_SEGS;
+    const int my = P.band.row0 + (int)blockIdx.x / SSIM_SEGS;
+    if (my >= P.mbh) return;
+    const int per = (P.mbw + SSIM_SEGS - 1) / SSIM_SEGS, mx0 = seg * per, mx1 = min(P.mbw, mx0 + per);
+    const bool luma = lane < 32;
+    const int pl = (lane >> 4) & 1;                          // chroma lanes: 32..47 Cb, 48..63 Cr
+    const int idx = luma ? lane : (lane & 15), nb = luma ? 5 : 3;
+    const bool live = idx < nb * nb;                         // (the other lanes load block 0 again and count nothing)
+    const int bx = live ? idx % nb : 0, by = live ? idx / nb : 0;
+    const int mbs = luma ? 16 : 8;                           // samples of a macroblock per axis
+    const int pw = luma ? P.w : P.w / 2, ph = luma ? P.h : P.h / 2, pitch = luma ? P.cw : P.cw / 2, prow = luma ? P.ch : P.ch / 2;
+    const int lim = min(ph, mbs * (P.band.row0 + P.band.rows));   // a band instance: its own rows (no window straddles two bands)
+    const int y0 = mbs * my + 4 * by;                        // first row of the block
+    const bool rowok = live && bx < nb - 1 && by < nb - 1 && y0 + 8 <= lim;
+    const uint8_t* const rbase = luma ? P.rec[0] : rec_chroma(P, pl);   // (never P.rec[lane-dependent])
+    const int o1 = lane + 1, o2 = lane + nb, o3 = lane + nb + 1;        // the blocks to the right, below and below right
+    int32_t* const mrow = map + (size_t)g * P.st_mb + (size_t)my * P.mbw;
+    // the eight words of a block: rows y0 .. y0 + 3 at column x of its plane
+    auto load = [&](int mx, uint32_t (&a)[4], uint32_t (&b)[4]) {
+        const int x = mbs * mx + 4 * bx, xr = min(x, pitch - 4);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int y = y0 + r;
+            a[r] = luma ? src_luma4(P, x, y) : src_chroma4(P, pl, x, y);
+            b[r] = *(const uint32_t*)(rbase + (size_t)min(y, prow - 1) * pitch + xr);
+        }
+    };
+    int acc = 0;     // this lane's windows: a wave has at most mbw / 4 + 1 macroblocks of 65536 at most each
+    int mine = 0;    // lane l keeps the map entry of the wave's macroblock 64 k + l
+    uint32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    if (mx0 < mx1) load(mx0, a, b);
+    for (int mx = mx0; mx < mx1; mx++) {
+        // the next macroblock's words are asked for before this one's are summed (the last iteration reads its own again)
+        uint32_t na[4], nb4[4];
+        load(mx + 1 < mx1 ? mx + 1 : mx, na, nb4);
+        uint32_t s1 = 0, s2 = 0, ss = 0, s12 = 0;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            s1 = __builtin_amdgcn_udot4(a[r], 0x01010101u, s1, false);
+            s2 = __builtin_amdgcn_udot4(b[r], 0x01010101u, s2, false);
+            ss = __builtin_amdgcn_udot4(a[r], a[r], __builtin_amdgcn_udot4(b[r], b[r], ss, false), false);
+            s12 = __builtin_amdgcn_udot4(a[r], b[r], s12, false);
+        }
+        uint32_t s = s1 | (s2 << 16);
+        s += (uint32_t)__shfl((int)s, o1) + (uint32_t)__shfl((int)s, o2) + (uint32_t)__shfl((int)s, o3);   // (halves of at most 65280: no carry)
+        ss += (uint32_t)__shfl((int)ss, o1) + (uint32_t)__shfl((int)ss, o2) + (uint32_t)__shfl((int)ss, o3);
+        s12 += (uint32_t)__shfl((int)s12, o1) + (uint32_t)__shfl((int)s12, o2) + (uint32_t)__shfl((int)s12, o3);
+        const bool counts = rowok && mbs * mx + 4 * bx + 8 <= pw;
+        const int q = counts ? ssim_window(s, ss, s12) : 0;
+        acc += q;
+        const int r16 = row_sum16_dpp(luma ? q : 0);
+        const int tot = __builtin_amdgcn_readlane(r16, 0) + __builtin_amdgcn_readlane(r16, 16);   // at most 16 * 65536 in magnitude
+        const int k = mx - mx0;
+        if (lane == (k & 63)) mine = tot;
+        if ((k & 63) == 63 || mx == mx1 - 1) {
+            if (lane <= (k & 63)) mrow[mx0 + (k & ~63) + lane] = mine;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) { a[r] = na[r]; b[r] = nb4[r]; }
+    }
+    const int t16 = row_sum16_dpp(acc);
+    const long long ty = (long long)__builtin_amdgcn_readlane(t16, 0) + (long long)__builtin_amdgcn_readlane(t16, 16);
+    const long long tu = __builtin_amdgcn_readlane(t16, 32), tv = __builtin_amdgcn_readlane(t16, 48);
+    if (lane == 0) {
+        long long* o = part + (((size_t)g * P.mbh + my) * SSIM_SEGS + seg) * 3;
+        o[0] = ty; o[1] = tu; o[2] = tv;
+    }
+}
+
 }  // namespace h264

@@ -327,7 +327,31 @@ int mi355x_h264_stats_read(mi355x_h264_encoder* e, mi355x_h264_stats* out, int r
 int mi355x_h264_quality_enable(mi355x_h264_encoder* e, int on)
 {
     if (!e) return MI355X_H264_E_ARG;
-    return quality_set(e, on != 0);
+    return quality_set(e, on != 0 ? MI355X_H264_QUALITY_SSE : 0u);
+}
+
+int mi355x_h264_quality_enable_ex(mi355x_h264_encoder* e, unsigned metrics)
+{
+    if (!e) return MI355X_H264_E_ARG;
+    return quality_set(e, metrics);
+}
+
+int64_t mi355x_h264_quality_ssim_read(mi355x_h264_encoder* e, mi355x_h264_ssim* dst, size_t cap)
+{
+    NEED(e, dst, "null argument");
+    NEED(e, !e->s_recs.empty(), "no quality SSIM records: SSIM was not enabled for the last call, or there has been no picture yet");
+    NEED(e, cap >= e->s_recs.size(), "room for fewer records than the last call made");
+    memcpy(dst, e->s_recs.data(), e->s_recs.size() * sizeof(mi355x_h264_ssim));
+    return (int64_t)e->s_recs.size();
+}
+
+int64_t mi355x_h264_quality_ssim_map(mi355x_h264_encoder* e, int item, int32_t* dst, size_t cap)
+{
+    NEED(e, dst && item >= 0 && item < e->G, "null argument or no such item");
+    NEED(e, !e->s_recs.empty() && e->s_have[item] && e->s_map[item], "no quality SSIM map: nothing was compared for the item's last picture");
+    NEED(e, cap >= (size_t)e->nmb, "room for fewer entries than the picture has macroblocks");
+    memcpy(dst, e->s_map[item], (size_t)e->nmb * sizeof(int32_t));
+    return (int64_t)e->nmb;
 }
 
 int64_t mi355x_h264_quality_read(mi355x_h264_encoder* e, mi355x_h264_quality* dst, size_t cap)
@@ -400,6 +424,7 @@ int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags
     it.copied = ev;
     g_streams_open.fetch_add(1);
     if (!h->e->q_have.empty()) h->e->q_have[idx] = 0;   // (quality report: the item's record was the stream's before this one)
+    if (!h->e->s_have.empty()) h->e->s_have[idx] = 0;
     s->hub = h; s->item = idx;
     *out = s;
     return MI355X_H264_OK;
@@ -504,14 +529,41 @@ int mi355x_h264_stream_debug_keep_pre(mi355x_h264_stream* s, int on)
 }
 
 // the quality report of all streams of this stream's engine (engine.h, submit_step), and this stream's last record and map
-int mi355x_h264_stream_quality_enable(mi355x_h264_stream* s, int on)
+int mi355x_h264_stream_quality_enable_ex(mi355x_h264_stream* s, unsigned metrics)
 {
     if (!s) return MI355X_H264_E_ARG;
     if (hipSetDevice(s->hub->cfg.device) != hipSuccess) return set_err(s->hub->items[s->item].err, MI355X_H264_E_HIP, "hipSetDevice");
     std::lock_guard<std::mutex> lk(s->hub->launch_mu);   // (a step's leader reads the switch while it launches, and the records when it finishes)
-    const int rc = quality_set(s->hub->e, on != 0);
+    const int rc = quality_set(s->hub->e, metrics);
     if (rc != MI355X_H264_OK) snprintf(s->hub->items[s->item].err, sizeof(s->hub->items[s->item].err), "%s", s->hub->e->err);
     return rc;
+}
+int mi355x_h264_stream_quality_enable(mi355x_h264_stream* s, int on) { return mi355x_h264_stream_quality_enable_ex(s, on != 0 ? MI355X_H264_QUALITY_SSE : 0u); }
+
+int mi355x_h264_stream_last_ssim(const mi355x_h264_stream* s, mi355x_h264_ssim* out)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    Hub* h = s->hub;
+    if (!out) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->launch_mu);
+    if (h->e->s_have.empty() || !h->e->s_have[s->item])
+        return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "no quality SSIM record: SSIM was not enabled for the stream's last picture, or there has been no picture yet");
+    *out = h->e->s_item[s->item];
+    return MI355X_H264_OK;
+}
+
+int64_t mi355x_h264_stream_ssim_map(mi355x_h264_stream* s, int32_t* dst, size_t cap)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    Hub* h = s->hub;
+    const mi355x_h264_encoder* e = h->e;
+    if (!dst) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->launch_mu);
+    if (e->s_have.empty() || !e->s_have[s->item] || !e->s_map[s->item])
+        return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "no quality SSIM map: nothing was compared for the stream's last picture");
+    if (cap < (size_t)e->nmb) return set_err(h->items[s->item].err, MI355X_H264_E_ARG, "room for fewer entries than the picture has macroblocks");
+    memcpy(dst, e->s_map[s->item], (size_t)e->nmb * sizeof(int32_t));   // (as mi355x_h264_stream_quality_map: nothing rewrites this before the stream's next picture)
+    return (int64_t)e->nmb;
 }
 
 int mi355x_h264_stream_last_quality(const mi355x_h264_stream* s, mi355x_h264_quality* out)

@@ -74,8 +74,14 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     // LastFrameQuality() and one log line per GOP.  The switch of a shared engine holds for all its streams and ends with it:
     // an object without the key leaves it as it finds it and reads nothing
     m_psnr = ParsePsnr(GetStrEncParam("persist.vmi.video.encode.psnr"));
-    m_haveQuality = false;
+    // extension: "1" = the report is on with both metrics, SSIM beside the SSE ("quality report: SSIM"), with or without .psnr:
+    // LastFrameSsim() and a log line of its own per GOP.  (An object with .psnr alone that opens a stream of the same shared
+    // engine later sets the switch to the SSE alone for all of them; this object then reads no SSIM record and writes no line.)
+    m_ssim = ParseSsim(GetStrEncParam("persist.vmi.video.encode.ssim"));
+    m_haveQuality = m_haveSsim = false;
     m_gopPictures = 0;
+    m_gopSsimPictures = 0;
+    const unsigned metrics = m_ssim ? (MI355X_H264_QUALITY_SSE | MI355X_H264_QUALITY_SSIM) : MI355X_H264_QUALITY_SSE;
     // One engine per object (mi355x_h264_create) costs every picture its own launch sequence.  The default is a STREAM of the
     // shared engine: the pictures that the encoder objects of one process hand over at about the same time are coded in one
     // lockstep step (include/mi355x_h264.h, "streams"; same bitstream).  persist.vmi.video.encode.shared = 0 (or the environment
@@ -112,7 +118,7 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
             m_stream = nullptr;
             return false;
         }
-        if (m_psnr && mi355x_h264_stream_quality_enable(m_stream, 1) != MI355X_H264_OK) {
+        if ((m_psnr || m_ssim) && mi355x_h264_stream_quality_enable_ex(m_stream, metrics) != MI355X_H264_OK) {
             ERR("quality report: %s", mi355x_h264_stream_last_error(m_stream));
             mi355x_h264_stream_close(m_stream);
             m_stream = nullptr;
@@ -128,7 +134,7 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
         m_engine = nullptr;
         return false;
     }
-    if (m_psnr && mi355x_h264_quality_enable(m_engine, 1) != MI355X_H264_OK) {
+    if ((m_psnr || m_ssim) && mi355x_h264_quality_enable_ex(m_engine, metrics) != MI355X_H264_OK) {
         ERR("quality report: %s", mi355x_h264_last_error(m_engine));
         mi355x_h264_destroy(m_engine);
         m_engine = nullptr;
@@ -145,12 +151,28 @@ void VideoEncoderMI355X::QualityAfterPicture(bool isIdr)
     const int rc = m_stream != nullptr ? mi355x_h264_stream_last_quality(m_stream, &q)
                                        : (mi355x_h264_quality_read(m_engine, &q, 1) == 1 ? MI355X_H264_OK : MI355X_H264_E_ARG);
     m_haveQuality = rc == MI355X_H264_OK;
+    m_haveSsim = false;
     if (!m_haveQuality) {
         return;
     }
     m_lastQuality = q;
     if (isIdr) {
         QualityLogGop();
+    }
+    if (m_ssim) {
+        mi355x_h264_ssim s{};
+        m_haveSsim = m_stream != nullptr ? mi355x_h264_stream_last_ssim(m_stream, &s) == MI355X_H264_OK
+                                         : mi355x_h264_quality_ssim_read(m_engine, &s, 1) == 1;
+        if (m_haveSsim) {
+            m_lastSsim = s;
+            if (s.valid != 0) {
+                for (int p = 0; p < 3; p++) {
+                    m_gopSsimSum[p] += s.sum[p];
+                    m_gopSsimWindows[p] += s.windows[p];
+                }
+                m_gopSsimPictures++;
+            }
+        }
     }
     if (q.valid != 0) {
         for (int p = 0; p < 3; p++) {
@@ -166,7 +188,7 @@ void VideoEncoderMI355X::QualityAfterPicture(bool isIdr)
 // (10 log10(255^2 samples / SSE) over the sums; computed here, on the host - the library reports integers only)
 void VideoEncoderMI355X::QualityLogGop()
 {
-    if (m_gopPictures != 0) {
+    if (m_gopPictures != 0 && m_psnr) {
         double db[3];
         for (int p = 0; p < 3; p++) {
             db[p] = m_gopSse[p] != 0 ? 10.0 * std::log10(65025.0 * static_cast<double>(m_gopSamples[p]) / static_cast<double>(m_gopSse[p])) : INFINITY;
@@ -179,14 +201,36 @@ void VideoEncoderMI355X::QualityLogGop()
     }
     m_gopBytes = 0;
     m_gopPictures = 0;
+    // a line of its own: the mean SSIM Y / U / V of the GOP, sum / (65536 windows) over the GOP's sums (computed here, on the host)
+    if (m_gopSsimPictures != 0) {
+        double mean[3];
+        for (int p = 0; p < 3; p++) {
+            mean[p] = m_gopSsimWindows[p] != 0 ? static_cast<double>(m_gopSsimSum[p]) / (65536.0 * static_cast<double>(m_gopSsimWindows[p])) : NAN;
+        }
+        INFO("GOP of %u pictures: mean SSIM Y %.4f U %.4f V %.4f", m_gopSsimPictures, mean[0], mean[1], mean[2]);
+    }
+    for (int p = 0; p < 3; p++) {
+        m_gopSsimSum[p] = 0;
+        m_gopSsimWindows[p] = 0;
+    }
+    m_gopSsimPictures = 0;
 }
 
 bool VideoEncoderMI355X::LastFrameQuality(mi355x_h264_quality *out) const
 {
-    if (!m_psnr || !m_haveQuality || out == nullptr) {
+    if ((!m_psnr && !m_ssim) || !m_haveQuality || out == nullptr) {
         return false;
     }
     *out = m_lastQuality;
+    return true;
+}
+
+bool VideoEncoderMI355X::LastFrameSsim(mi355x_h264_ssim *out) const
+{
+    if (!m_ssim || !m_haveSsim || out == nullptr) {
+        return false;
+    }
+    *out = m_lastSsim;
     return true;
 }
 
@@ -261,6 +305,8 @@ int32_t VideoEncoderMI355X::ParseInputLayout(const std::string &value)
 int32_t VideoEncoderMI355X::ParseRefs(const std::string &value) { return value == "2" ? 2 : value == "3" ? 3 : 1; }
 
 bool VideoEncoderMI355X::ParsePsnr(const std::string &value) { return value == "1"; }
+
+bool VideoEncoderMI355X::ParseSsim(const std::string &value) { return value == "1"; }
 
 int VideoEncoderMI355X::ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out)
 {
@@ -367,7 +413,7 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
             m_stream != nullptr ? mi355x_h264_stream_last_error(m_stream) : mi355x_h264_last_error(m_engine));
         return false;
     }
-    if (m_psnr) {
+    if (m_psnr || m_ssim) {
         QualityAfterPicture(frameType == MI355X_H264_FRAME_IDR);
     }
     RateControlUpdate(*outLen, frameType == MI355X_H264_FRAME_IDR);
@@ -376,7 +422,7 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
 
 void VideoEncoderMI355X::EngineClose()
 {
-    if (m_psnr && (m_engine != nullptr || m_stream != nullptr)) {
+    if ((m_psnr || m_ssim) && (m_engine != nullptr || m_stream != nullptr)) {
         QualityLogGop();
     }
     if (m_engine != nullptr) {

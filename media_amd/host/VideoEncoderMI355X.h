@@ -27,6 +27,8 @@ public:
     // quality report of the last picture that went out (extension key persist.vmi.video.encode.psnr = 1; after a scene-change
     // re-code: of the IDR picture).  false: the key is off or there has been no picture
     bool LastFrameQuality(mi355x_h264_quality *out) const;
+    // its SSIM record (extension key persist.vmi.video.encode.ssim = 1).  false: the key is off or there is no record
+    bool LastFrameSsim(mi355x_h264_ssim *out) const;
     // measurement hook (bench.py reads the reconstruction for PSNR): luma reconstruction of the last picture, coded size
     int64_t ReadReconY(void *dst, size_t cap, int32_t *codedWidth, int32_t *codedHeight);
     bool Shared() const { return m_stream != nullptr; }
@@ -40,6 +42,9 @@ public:
     // extension key persist.vmi.video.encode.psnr: "1" -> the library's quality report is on (include/mi355x_h264.h, "quality
     // report"), on the stream path and with an engine of its own alike; anything else (or unset) -> off
     static bool ParsePsnr(const std::string &value);
+    // extension key persist.vmi.video.encode.ssim: "1" -> the quality report is on with both metrics (SSE and SSIM), with or
+    // without .psnr, on both paths; anything else (or unset) -> what .psnr says
+    static bool ParseSsim(const std::string &value);
     // extension keys persist.vmi.video.encode.srcwidth / .srcheight: EncodeOneFrame takes pictures of that size and the device
     // resamples them to the coded size (include/mi355x_h264.h, "scaled streams").  1: both are decimal numbers, even, 16 .. 4096,
     // at least the coded size and at most 4 times it (*srcWidth, *srcHeight set); 0: neither key is set; -1: anything else (one
@@ -89,6 +94,12 @@ private:
     // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
     bool m_psnr = false, m_haveQuality = false;
     mi355x_h264_quality m_lastQuality{};
+    // SSIM beside it (persist.vmi.video.encode.ssim = 1)
+    bool m_ssim = false, m_haveSsim = false;
+    mi355x_h264_ssim m_lastSsim{};
+    int64_t m_gopSsimSum[3] = {0, 0, 0};
+    uint64_t m_gopSsimWindows[3] = {0, 0, 0};
+    uint32_t m_gopSsimPictures = 0;
     uint64_t m_gopSse[3] = {0, 0, 0}, m_gopSamples[3] = {0, 0, 0}, m_gopBytes = 0;
     uint32_t m_gopPictures = 0;
 };

@@ -37,6 +37,12 @@ int32_t vc_parse_source_size(const char *width, const char *height, uint32_t cod
 int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
 // persist.vmi.video.encode.psnr: "1" turns the quality report on, anything else leaves it off
 int32_t vc_parse_psnr(const char *value) { return VideoEncoderMI355X::ParsePsnr(value != nullptr ? value : "") ? 1 : 0; }
+// persist.vmi.video.encode.ssim: "1" turns the quality report on with both metrics, anything else leaves it as .psnr says
+int32_t vc_parse_ssim(const char *value) { return VideoEncoderMI355X::ParseSsim(value != nullptr ? value : "") ? 1 : 0; }
+// the library's own rules (host_framing.h, shared with the engine): is `metrics` a value mi355x_h264_quality_enable_ex takes, and
+// what MI355X_H264_QUALITY = value turns on when an engine is created (MI355X_H264_QUALITY_* bits)
+int32_t vc_debug_quality_metrics_ok(uint32_t metrics) { return quality_metrics_ok(metrics) ? 1 : 0; }
+uint32_t vc_debug_quality_env(const char *value) { return quality_env_metrics(value); }
 // persist.vmi.video.encode.colour / .range: 1 (and matrix, full_range), 0 (neither set) or -1 (rejected)
 int32_t vc_parse_colour(const char *colour, const char *range, int32_t *matrix, int32_t *fullRange)
 {
@@ -93,6 +99,12 @@ int32_t vc_last_quality(void *enc, mi355x_h264_quality *out)
 {
     auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
     return m != nullptr && m->LastFrameQuality(out) ? 0 : -1;
+}
+// the SSIM record (mi355x_h264_ssim) of the last picture that went out (persist.vmi.video.encode.ssim = 1); 0, or -1 when there is none
+int32_t vc_last_ssim(void *enc, mi355x_h264_ssim *out)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    return m != nullptr && m->LastFrameSsim(out) ? 0 : -1;
 }
 uint32_t vc_scene_cuts(void *enc)
 {

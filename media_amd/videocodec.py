@@ -36,6 +36,11 @@ def lib():
         L.vc_parse_input_device.argtypes = [C.c_char_p]
         L.vc_parse_refs.argtypes = [C.c_char_p]
         L.vc_parse_psnr.argtypes = [C.c_char_p]
+        L.vc_parse_ssim.argtypes = [C.c_char_p]
+        L.vc_last_ssim.argtypes = [vp, vp]
+        L.vc_debug_quality_metrics_ok.argtypes = [C.c_uint32]
+        L.vc_debug_quality_env.argtypes = [C.c_char_p]
+        L.vc_debug_quality_env.restype = C.c_uint32
         L.vc_parse_source_size.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.vc_last_quality.argtypes = [vp, vp]
         L.vc_debug_ref_counts.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
@@ -81,6 +86,21 @@ def parse_input_device(value):
 def parse_refs(value):
     """what persist.vmi.video.encode.refs = value selects: 2 or 3 reference pictures, else 1"""
     return lib().vc_parse_refs(str(value).encode())
+
+
+def parse_ssim(value):
+    """does persist.vmi.video.encode.ssim = value turn the quality report on with both metrics?  "1" only"""
+    return bool(lib().vc_parse_ssim(str(value).encode()))
+
+
+def quality_metrics_ok(metrics):
+    """does mi355x_h264_quality_enable_ex take `metrics`?  (the library's own rule, no device)"""
+    return bool(lib().vc_debug_quality_metrics_ok(metrics))
+
+
+def quality_env(value):
+    """the metrics MI355X_H264_QUALITY = value turns on when an engine is created (None: the variable is not set)"""
+    return int(lib().vc_debug_quality_env(None if value is None else str(value).encode()))
 
 
 def parse_psnr(value):
@@ -131,7 +151,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None, refs=None, psnr=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None):
+                   inputmem=None, refs=None, psnr=None, ssim=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -150,6 +170,7 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.inputmem", "" if inputmem is None else inputmem)   # device; else host memory
     prop_set("persist.vmi.video.encode.refs", "" if refs is None else refs)               # 2 | 3; else one reference picture
     prop_set("persist.vmi.video.encode.psnr", "" if psnr is None else psnr)               # 1: quality report; else off
+    prop_set("persist.vmi.video.encode.ssim", "" if ssim is None else ssim)               # 1: the report with SSIM beside the SSE
     prop_set("persist.vmi.video.encode.srcwidth", "" if srcwidth is None else srcwidth)   # both set and valid: pictures of that
     prop_set("persist.vmi.video.encode.srcheight", "" if srcheight is None else srcheight)   # size, resampled to width x height
     prop_set("persist.vmi.video.encode.colour", "" if colour is None else colour)         # bt601 | bt709 } either one set and valid: a
@@ -204,6 +225,15 @@ class VideoEncoder:
         if lib().vc_last_quality(self.h, C.byref(q)) != 0:
             return None
         return capi._quality_record(q)
+
+    def last_ssim(self):
+        """the SSIM record of the last picture that went out (persist.vmi.video.encode.ssim = 1) as a dict of `ssim`, `ssim_sum`,
+        `ssim_windows` and `valid`, or None when there is none"""
+        from media_amd import capi
+        s = capi.Ssim()
+        if lib().vc_last_ssim(self.h, C.byref(s)) != 0:
+            return None
+        return capi._with_ssim({"valid": bool(s.valid)}, s)
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)

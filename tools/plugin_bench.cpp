@@ -5,10 +5,13 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--refs N] [--psnr] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
+// --ssim (anywhere on the line): the extension key persist.vmi.video.encode.ssim = 1 - the report is on with both metrics, every
+// picture's SSIM record is read after its call (outside the latency sample), and the JSON line carries ssim_y / ssim_u / ssim_v:
+// sum / (65536 windows) over all pictures of the run, per plane.
 // --psnr (anywhere on the line): the extension key persist.vmi.video.encode.psnr = 1 - the library's quality report is on, every
 // picture's record is read after its call (outside the latency sample), and the JSON line carries psnr_y / psnr_u / psnr_v: the
 // PSNR of the mean squared error of all pictures of the run, per plane.
@@ -37,6 +40,7 @@
 #include "mi355x_h264.h"
 
 extern "C" int32_t vc_last_quality(void *enc, mi355x_h264_quality *out);   // media_amd/host/capi_shim.cpp
+extern "C" int32_t vc_last_ssim(void *enc, mi355x_h264_ssim *out);
 
 int main(int argc, char **argv)
 {
@@ -74,7 +78,16 @@ int main(int argc, char **argv)
                 argc -= 2;
                 break;
             }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    bool ssim = false;
+    for (int i = 1; i < argc; i++)   // --ssim: taken out of the line
+        if (strcmp(argv[i], "--ssim") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_SSIM", "1", 1);
+            ssim = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     // (w, h: the size of the pictures in the file and in every call - the source size with --src)
     const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
@@ -143,7 +156,8 @@ int main(int argc, char **argv)
         std::vector<std::vector<double>> lat(S);
         std::vector<uint64_t> bytes(S, 0);
         std::atomic<int> failures{0};
-        std::vector<uint64_t> sse((size_t)S * 3, 0), samples((size_t)S * 3, 0);
+        std::vector<uint64_t> sse((size_t)S * 3, 0), samples((size_t)S * 3, 0), windows((size_t)S * 3, 0);
+        std::vector<int64_t> qsum((size_t)S * 3, 0);
         auto work = [&](int k) {
             lat[k].reserve(frames);
             for (int i = 0; i < frames; i++) {
@@ -158,6 +172,9 @@ int main(int argc, char **argv)
                 mi355x_h264_quality q;
                 if (psnr && rc == VIDEO_ENCODER_SUCCESS && vc_last_quality(encs[k], &q) == 0 && q.valid)
                     for (int p = 0; p < 3; p++) { sse[(size_t)k * 3 + p] += q.sse[p]; samples[(size_t)k * 3 + p] += q.samples[p]; }
+                mi355x_h264_ssim sq;
+                if (ssim && rc == VIDEO_ENCODER_SUCCESS && vc_last_ssim(encs[k], &sq) == 0 && sq.valid)
+                    for (int p = 0; p < 3; p++) { qsum[(size_t)k * 3 + p] += sq.sum[p]; windows[(size_t)k * 3 + p] += sq.windows[p]; }
             }
         };
         std::vector<std::thread> ths;
@@ -171,7 +188,7 @@ int main(int argc, char **argv)
         for (int k = 0; k < S; k++) { all.insert(all.end(), lat[k].begin(), lat[k].end()); total += bytes[k]; }
         std::sort(all.begin(), all.end());
         const size_t n = all.size();
-        char q[160] = "";
+        char q[320] = "";
         if (psnr) {
             double db[3];
             for (int p = 0; p < 3; p++) {
@@ -180,6 +197,16 @@ int main(int argc, char **argv)
                 db[p] = m == 0 ? 0.0 : (e == 0 ? 999.0 : 10.0 * std::log10(65025.0 * (double)m / (double)e));   // (999: no error at all)
             }
             snprintf(q, sizeof(q), ",\"psnr_y\":%.3f,\"psnr_u\":%.3f,\"psnr_v\":%.3f", db[0], db[1], db[2]);
+        }
+        if (ssim) {
+            double mean[3];
+            for (int p = 0; p < 3; p++) {
+                int64_t t = 0; uint64_t m = 0;
+                for (int k = 0; k < S; k++) { t += qsum[(size_t)k * 3 + p]; m += windows[(size_t)k * 3 + p]; }
+                mean[p] = m == 0 ? 0.0 : (double)t / (65536.0 * (double)m);
+            }
+            const size_t at = strlen(q);
+            snprintf(q + at, sizeof(q) - at, ",\"ssim_y\":%.5f,\"ssim_u\":%.5f,\"ssim_v\":%.5f", mean[0], mean[1], mean[2]);
         }
         printf("{\"streams\":%d,\"fps_aggregate\":%.1f,\"fps_per_stream\":%.1f,\"latency_ms_p50\":%.3f,\"latency_ms_p99\":%.3f,\"bytes_per_picture\":%.1f,"
                "\"bitrate_achieved\":%.0f,\"pictures\":%zu,\"encode_failures\":%d%s}\n",
