@@ -48,10 +48,10 @@ int mi355x_h264_dec_decode(mi355x_h264_decoder *dec, const uint8_t *au, size_t l
 /* wait until the picture launched by the last decode call is complete */
 int mi355x_h264_dec_sync(mi355x_h264_decoder *dec);
 
-/* cropped and coded size of the last decoded picture (INDEX_PIC_INFO, VideoDecoder.h:57) */
+/* cropped and coded size of the last decoded picture (INDEX_PIC_INFO, VideoDecoder.h:57); the native size, whatever output size is set */
 int mi355x_h264_dec_picture_info(const mi355x_h264_decoder *dec, int *width, int *height, int *coded_width, int *coded_height);
 
-/* the last decoded picture as tight I420 (Y, U, V planes of the cropped size) into host / device memory; returns bytes or < 0
+/* the last decoded picture as tight I420 (Y, U, V planes of the cropped size - never of an output size) into host / device memory; returns bytes or < 0
  * (RetrieveFrameData, VideoDecoderNetint.cpp:640, PIXEL_FORMAT_YUV_420P) */
 int64_t mi355x_h264_dec_read_i420(mi355x_h264_decoder *dec, uint8_t *dst, size_t cap);
 int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder *dec, void *d_dst, size_t cap);
@@ -72,7 +72,7 @@ int64_t mi355x_h264_dec_read_i420_device(mi355x_h264_decoder *dec, void *d_dst, 
 #define MI355X_H264_PIX_RGBA 3
 typedef struct {
     int64_t offset;                /* of the picture inside the output; -1: the stream has no picture in this output */
-    int32_t width, height;         /* cropped size */
+    int32_t width, height;         /* size delivered: the cropped size, or the output size set (below, "output size") */
     int32_t stride, chroma_stride; /* bytes per row (chroma_stride: I420 U / V rows, NV12 / NV21 pair rows; 0 for RGBA) */
     int32_t fresh;                 /* 1: decoded in the step the output belongs to */
     int32_t colour;                /* RGBA: matrix | full_range << 8 of the conversion that was applied to the picture (below, "colour"); 0 for
@@ -165,8 +165,33 @@ int mi355x_h264_dec_group_set_output(mi355x_h264_dec_group *g, int layout, int r
  * that took no part in that step.  E_ARG: unarmed, or fewer than back + 1 armed steps so far */
 int mi355x_h264_dec_group_output(mi355x_h264_dec_group *g, int back, const uint8_t **data, mi355x_h264_dec_out_pic *pics);
 
+/* ---- output size: pictures resampled on the GPU to a requested size (media_amd/csrc/k_dec_out_scale.h) ----
+ * A decoder, or a stream of a group, may have an output size (W, H).  The picture delivered in layout L is then exactly what the
+ * unscaled call delivers in L, with the same row_align and the same colour variant, for a decoded picture whose cropped I420 planes
+ * are the area-resampled planes: Y resampled from the cropped size (w, h) to (W, H), Cb and Cr each from (w / 2, h / 2) to
+ * (W / 2, H / 2).  The arithmetic is that of mi355x_h264.h, "scaled streams": integer overlap weights, and one exact division
+ * floor((N + (D >> 1)) / D) per sample; nothing is rounded between the horizontal and the vertical sums.  RGBA resamples the three
+ * planes first and converts then: the chroma sample of a 2x2 block of the RESULT serves its four pixels.  A dimension with W == w is
+ * the identity by this arithmetic.
+ * set_output_size: (0, 0) = the native size again; stream = -1: every stream of the group.  E_ARG, before the device is touched: an
+ * odd value, a value outside 2..4096, exactly one of the two values 0, no such stream.  The setting holds from the next dec_read /
+ * read_all call and from the next armed step on; the same picture may be read again and again at different sizes (a rendition
+ * ladder from one decode).  Output buffers sized for the native picture always suffice.
+ * Whether a picture can be resampled is checked when it is delivered: W <= w <= 4 W and H <= h <= 4 H must hold (no upscaling, no
+ * ratio above 4).  Otherwise dec_read returns E_ARG and last_error names both sizes; in read_all and in an armed step that stream's
+ * pics[i].offset is -1 and mi355x_h264_dec_group_last_error(g, i) says why, while the other streams are delivered (read_all: E_ARG
+ * when no stream is deliverable, as for "no stream has a picture").
+ * mi355x_h264_dec_out_pic.width / height / stride / chroma_stride describe the picture DELIVERED, and dst == NULL sizing follows
+ * them.  A call none of whose streams has an output size makes the launch it always made; a call with at least one makes ONE launch
+ * of the resampling kernel for all its pictures (the others pass through ratio 1), and the transfers the unscaled call makes.
+ * Left at the native size: _picture_info, _read_i420(_device), _group_read_i420(_device), debug_plane. */
+int mi355x_h264_dec_set_output_size(mi355x_h264_decoder *dec, int width, int height);
+int mi355x_h264_dec_output_size(const mi355x_h264_decoder *dec, int *width, int *height);
+int mi355x_h264_dec_group_set_output_size(mi355x_h264_dec_group *g, int stream, int width, int height);
+int mi355x_h264_dec_group_output_size(const mi355x_h264_dec_group *g, int stream, int *width, int *height);
+
 /* ---- test / measurement hooks ---- */
-int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 */
+int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 (never resampled) */
 int mi355x_h264_dec_timing(const mi355x_h264_decoder *dec, uint64_t *pictures, double *parse_ms, double *gpu_ms);
 /* mi355x_h264_dec_group_last_step of the group of one stream that the decoder is */
 int mi355x_h264_dec_last_step(const mi355x_h264_decoder *dec, int64_t *out, int n);

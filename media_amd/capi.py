@@ -43,6 +43,7 @@ EXPORTS = [
     "mi355x_h264_create_colour", "mi355x_h264_stream_open_colour", "mi355x_h264_colour_of", "mi355x_h264_stream_colour",
     "mi355x_h264_dec_colour", "mi355x_h264_dec_set_rgba_colour", "mi355x_h264_dec_group_colour", "mi355x_h264_dec_group_set_rgba_colour",
     "mi355x_h264_parser_colour",
+    "mi355x_h264_dec_set_output_size", "mi355x_h264_dec_output_size", "mi355x_h264_dec_group_set_output_size", "mi355x_h264_dec_group_output_size",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*

@@ -27,6 +27,7 @@ struct DecGroupStream {
     int64_t last_serial = 0;   // serial number of the step that decoded its last picture
     h264dec::Vui vui;    // of the sequence parameter set its last decoded picture was coded under (mi355x_h264_dec_colour)
     int rgba_override = -1;   // mi355x_h264_dec_set_rgba_colour: the variant RGBA output applies whatever the stream says; -1: follow the stream
+    int out_w = 0, out_h = 0; // mi355x_h264_dec_group_set_output_size: the size its pictures are delivered at; 0, 0: their own
     // the step in hand
     const uint8_t* au = nullptr;
     size_t len = 0;
@@ -66,9 +67,10 @@ struct mi355x_h264_dec_group {
     int intra_slots = 32, filter_slots = 32;   // pictures the row wavefronts hold at a time (the rest are walked to)
     int64_t step_serial = 0, last[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (last_step's out[11] / out[12] are the DevMem totals)
     double last_ms[2] = {0, 0};          // the last step's parse and launch time, untruncated (last[5] / last[6] are whole microseconds)
-    // output (k_dec_out.h).  rd: read_all's table and staging; its device staging buffer also serves the armed steps (everything
+    // output (k_dec_out.h, k_dec_out_scale.h).  rd: read_all's table and staging; its device staging buffer also serves the armed steps (everything
     // is ordered on the group's stream).  Armed: the step's table of output positions lies behind its DecPos rows in tables of
-    // their own (h_tabx / d_tabx: DecPos [streams], then DecOutPos [streams]), so that one transfer carries both.
+    // their own (h_tabx / d_tabx: DecPos [streams], then DecOutPos or - a stream has an output size - DecOutScalePos [streams]), so that
+    // one transfer carries both.
     struct Out {
         DecOutBuf rd;
         bool armed = false, ready = false;
@@ -106,6 +108,25 @@ int dg_rgba_variant(const DecGroupStream& s)
     return (v.matrix == 1 ? 1 : 0) | (v.full_range ? 2 : 0);
 }
 int dg_out_variant(const DecGroupStream& s, int layout) { return layout == DEC_OUT_RGBA ? dg_rgba_variant(s) : -1; }
+
+// The size stream s's last picture is delivered at: its own, or the output size set.  false: the picture cannot be resampled to
+// that size; the stream's report says so with both sizes, and the call delivers the other streams
+bool dg_out_size(DecGroupStream& s, int& W, int& H)
+{
+    W = s.out_w ? s.out_w : s.width; H = s.out_w ? s.out_h : s.height;
+    if (!s.out_w || out_size_serves(s.width, s.height, W, H)) return true;
+    snprintf(s.err, sizeof(s.err), "output size %dx%d cannot be made from a picture of %dx%d: W <= w <= 4 W and H <= h <= 4 H must hold", W, H, s.width, s.height);
+    return false;
+}
+// one more row of a call's table: stream i's picture in ring slot `slot`, delivered at W x H at byte `off`
+void dg_out_row(OutCall& c, const DecGroupStream& s, int i, int slot, int W, int H, const OutGeom& geo, size_t off, int layout)
+{
+    c.rows[c.n] = DecOutPos{(uint32_t)i, (uint32_t)slot, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)W, (uint32_t)H,
+                            (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, (uint32_t)std::max(0, dg_out_variant(s, layout)), 0u};
+    c.src[c.n][0] = s.width; c.src[c.n][1] = s.height;
+    c.scaled |= s.out_w != 0;
+    c.n++;
+}
 
 // the step in flight has finished; a wavefront that timed out leaves none of the step's pictures usable as a reference
 int dg_wait(mi355x_h264_dec_group* g)
@@ -147,9 +168,9 @@ int dg_out_prepare(mi355x_h264_dec_group* g)
     bool ok = true;
     for (int k = 0; k < 2 && ok; k++) {
         if (!o.done[k]) ok = hipEventCreateWithFlags(&o.done[k], hipEventDisableTiming) == hipSuccess;
-        if (ok && !o.h_tabx[k]) ok = DM_PINNED(g->mem, o.h_tabx[k], S * (sizeof(DecPos) + sizeof(DecOutPos))) == hipSuccess;
+        if (ok && !o.h_tabx[k]) ok = DM_PINNED(g->mem, o.h_tabx[k], S * (sizeof(DecPos) + sizeof(DecOutScalePos))) == hipSuccess;
     }
-    if (ok && !o.d_tabx) ok = DM_DEV(g->mem, o.d_tabx, S * (sizeof(DecPos) + sizeof(DecOutPos)), false) == hipSuccess;
+    if (ok && !o.d_tabx) ok = DM_DEV(g->mem, o.d_tabx, S * (sizeof(DecPos) + sizeof(DecOutScalePos)), false) == hipSuccess;
     if (ok && need > o.set_cap) {
         for (int k = 0; k < 2; k++) { if (o.h_set[k]) g->mem.drop(o.h_set[k]); o.h_set[k] = nullptr; }
         o.set_cap = 0;
@@ -269,7 +290,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     // which of the parsed pictures this step takes, and the table row of each
     int pos_stream[DEC_GROUP_MAX_STREAMS], npos = 0;
     DecPos* tab = nullptr;
-    DecOutPos* otab = nullptr;          // armed: the output positions, behind the DecPos rows
+    OutCall ocall;                      // armed: the output positions
     const bool outp = g->out.armed;
     const int oset = g->out.count ? g->out.cur ^ 1 : 0;
     size_t obytes = 0;
@@ -349,17 +370,21 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         nbig += pic.big.size();
         if (outp) {
             if (npos == 0) for (int x = 0; x < S; x++) g->out.pics[oset][x] = out_no_pic(g->step_serial);
-            otab = (DecOutPos*)(g->out.h_tabx[k] + (size_t)S * sizeof(DecPos));
-            const OutGeom geo = out_geom(g->out.layout, s.width, s.height, g->out.row_align);
-            const size_t off = out_align(obytes, 256);
-            otab[npos] = DecOutPos{(uint32_t)i, (uint32_t)s.cur, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
-                                   (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, (uint32_t)std::max(0, dg_out_variant(s, g->out.layout)), 0u};
-            g->out.pics[oset][i] = out_pic((int64_t)off, s.width, s.height, geo, 1, g->step_serial, dg_out_variant(s, g->out.layout));
-            obytes = off + geo.bytes;
+            int W, H;
+            if (dg_out_size(s, W, H)) {   // (else: no picture of this stream in the output, and its report says why)
+                const OutGeom geo = out_geom(g->out.layout, W, H, g->out.row_align);
+                const size_t off = out_align(obytes, 256);
+                dg_out_row(ocall, s, i, s.cur, W, H, geo, off, g->out.layout);
+                g->out.pics[oset][i] = out_pic((int64_t)off, W, H, geo, 1, g->step_serial, dg_out_variant(s, g->out.layout));
+                obytes = off + geo.bytes;
+            }
         }
         pos_stream[npos++] = i;
     }
     if (npos == 0) return MI355X_H264_OK;
+    // (armed: the output positions lie behind the DecPos rows and travel with them)
+    uint8_t* const otab = outp ? g->out.h_tabx[k] + (size_t)S * sizeof(DecPos) : nullptr;
+    const size_t otab_bytes = outp ? out_fill(ocall, otab) : 0;
 
     PicStore* const ps = &g->store;
     hipStream_t st = g->sync.st;
@@ -374,9 +399,8 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         HIPCHK(g->err, hipMemcpyAsync(g->d_arr[a] + off, g->h_arr[k][a] + off, bytes, hipMemcpyHostToDevice, st));
         transfers++;
     }
-    // (armed: the output positions lie behind the DecPos rows and travel with them)
     const DecPos* const d_tab = outp ? (const DecPos*)g->out.d_tabx : g->d_tab;
-    const size_t tab_bytes = outp ? (size_t)S * sizeof(DecPos) + (size_t)npos * sizeof(DecOutPos) : (size_t)npos * sizeof(DecPos);
+    const size_t tab_bytes = outp ? (size_t)S * sizeof(DecPos) + otab_bytes : (size_t)npos * sizeof(DecPos);
     HIPCHK(g->err, hipMemcpyAsync((void*)d_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
     transfers++;
     if (nbig) {   // the streams' large levels as one list, the indices counted from item 0
@@ -458,11 +482,14 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     if (outp) {
         // behind the loop filter, and ahead of the next step on this stream, which may write the very ring slot (a non-reference
         // picture leaves `cur` where it was): the step's pictures into the staging buffer, and that into the pinned set
-        HIPCHK(g->err, launch_dec_out(ps, g->out.layout, otab, (const DecOutPos*)(g->out.d_tabx + (size_t)S * sizeof(DecPos)), npos, g->out.rd.d_stage, st));
-        HIPCHK(g->err, hipMemcpyAsync(g->out.h_set[oset], g->out.rd.d_stage, obytes, hipMemcpyDeviceToHost, st));
+        // (a step none of whose pictures can be delivered at the size asked for makes neither: its set says "no picture" for all)
+        if (ocall.n) {
+            HIPCHK(g->err, out_launch(ps, g->out.layout, ocall, otab, g->out.d_tabx + (size_t)S * sizeof(DecPos), g->out.rd.d_stage, st));
+            HIPCHK(g->err, hipMemcpyAsync(g->out.h_set[oset], g->out.rd.d_stage, obytes, hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(g->err, hipEventRecord(g->out.done[oset], st));
         g->out.cur = oset; g->out.count = std::min(2, g->out.count + 1);
-        g->last[7] = 1; g->last[8] = 1;
+        g->last[7] = g->last[8] = ocall.n ? 1 : 0;
     }
     g->busy = true;
     g->nflight = npos;
@@ -516,21 +543,22 @@ int64_t dg_read(mi355x_h264_dec_group* g, int stream, void* dst, size_t cap, boo
 int64_t dg_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* dst, size_t cap, bool to_device, mi355x_h264_dec_out_pic* pics)
 {
     if (!g || !pics || !out_args_ok(layout, row_align)) return MI355X_H264_E_ARG;
-    DecOutPos rows[DEC_GROUP_MAX_STREAMS];
+    OutCall call;
     mi355x_h264_dec_out_pic desc[DEC_GROUP_MAX_STREAMS];
-    int n = 0;
     size_t total = 0;
     for (int i = 0; i < g->nstreams; i++) {
-        const DecGroupStream& s = g->st[i];
+        DecGroupStream& s = g->st[i];
         desc[i] = out_no_pic(g->step_serial);
         if (s.last < 0) continue;
-        const OutGeom geo = out_geom(layout, s.width, s.height, row_align);
+        int W, H;
+        if (!dg_out_size(s, W, H)) continue;   // (its report says why; the others are delivered)
+        const OutGeom geo = out_geom(layout, W, H, row_align);
         const size_t off = out_align(total, 256);
-        rows[n++] = DecOutPos{(uint32_t)i, (uint32_t)s.last, (uint32_t)s.crop_x, (uint32_t)s.crop_y, (uint32_t)s.width, (uint32_t)s.height,
-                              (uint32_t)geo.stride, (uint32_t)geo.cstride, (unsigned long long)off, (uint32_t)std::max(0, dg_out_variant(s, layout)), 0u};
-        desc[i] = out_pic((int64_t)off, s.width, s.height, geo, s.last_serial == g->step_serial, g->step_serial, dg_out_variant(s, layout));
+        dg_out_row(call, s, i, s.last, W, H, geo, off, layout);
+        desc[i] = out_pic((int64_t)off, W, H, geo, s.last_serial == g->step_serial, g->step_serial, dg_out_variant(s, layout));
         total = off + geo.bytes;
     }
+    const int n = call.n;
     if (n == 0) return MI355X_H264_E_ARG;
     if (dst && (cap < total || (to_device && ((uintptr_t)dst & 15)))) return MI355X_H264_E_ARG;
     memcpy(pics, desc, (size_t)g->nstreams * sizeof(desc[0]));
@@ -543,9 +571,9 @@ int64_t dg_read_all(mi355x_h264_dec_group* g, int layout, int row_align, void* d
     DecOutBuf& b = g->out.rd;
     if (out_reserve(g->mem, b, to_device ? 0 : total, to_device ? 0 : total) != hipSuccess)
         return set_err(g->err, MI355X_H264_E_NOMEM, "memory for the output staging (%s)", t_failed_call);
-    memcpy(b.h_tab, rows, (size_t)n * sizeof(DecOutPos));
+    out_fill(call, b.h_tab);
     g->last[9] = g->last[10] = 0;
-    HIPCHK(g->err, launch_dec_out(ps, layout, rows, b.d_tab, n, to_device ? (uint8_t*)dst : b.d_stage, st));
+    HIPCHK(g->err, out_launch(ps, layout, call, b.h_tab, b.d_tab, to_device ? (uint8_t*)dst : b.d_stage, st));
     g->last[9] = 1;
     if (!to_device) { HIPCHK(g->err, hipMemcpyAsync(b.h_stage, b.d_stage, total, hipMemcpyDeviceToHost, st)); g->last[10] = 1; }
     HIPCHK(g->err, hipStreamSynchronize(st));

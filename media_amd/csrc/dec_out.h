@@ -1,5 +1,6 @@
-// media_amd/csrc/dec_out.h -- host side of k_dec_out.h: the geometry of a picture in a layout (include/mi355x_h264_dec.h states the
-// packing), the table and staging buffers of the read calls, and the ONE launch that serves them (dec_group.h).
+// media_amd/csrc/dec_out.h -- host side of k_dec_out.h and k_dec_out_scale.h: the geometry of a picture in a layout
+// (include/mi355x_h264_dec.h states the packing), the output size of a stream, the table and staging buffers of the read calls,
+// and the ONE launch that serves them (dec_group.h).
 #pragma once
 
 namespace {
@@ -35,11 +36,32 @@ mi355x_h264_dec_out_pic out_pic(int64_t off, int w, int h, const OutGeom& g, int
 }
 mi355x_h264_dec_out_pic out_no_pic(int64_t serial) { mi355x_h264_dec_out_pic p{}; p.offset = -1; p.serial = serial; return p; }
 
+// ---- output size (include/mi355x_h264_dec.h, "output size"; k_dec_out_scale.h) ----
+// what set_output_size takes: (0, 0) = the native size, else both even and 2..4096
+bool out_size_ok(int W, int H)
+{
+    if (W == 0 && H == 0) return true;
+    return W >= 2 && W <= 4096 && H >= 2 && H <= 4096 && !(W & 1) && !(H & 1);
+}
+// a picture of w x h can be resampled to W x H: no upscaling, no ratio above 4
+bool out_size_serves(int w, int h, int W, int H) { return W <= w && w <= 4 * W && H <= h && h <= 4 * H; }
+// the scaled form of a table row whose width / height are the RESULT size, for a cropped picture of w x h.  The tile height: as many
+// result rows as SC_ROWS source rows serve (scale_tile_rows), even, so that a tile's chroma rows are its own
+DecOutScalePos out_scale_pos(const DecOutPos& o, int w, int h)
+{
+    DecOutScalePos t{};
+    t.o = o;
+    t.y = scale_plane_make(w, h, (int)o.width, (int)o.height);
+    t.c = scale_plane_make(w / 2, h / 2, (int)o.width / 2, (int)o.height / 2);
+    t.th = (uint32_t)std::min((int)DOS_TH, scale_tile_rows(h, (int)o.height) & ~1);
+    return t;
+}
+
 // what the read calls of a decoder or a group own, made with the first call that needs it: the position table in pinned memory
 // (the kernel reads it in place: a read call makes no transfer for it) and the staging pair of the host form
 struct DecOutBuf {
-    DecOutPos* h_tab = nullptr;   // [DEC_GROUP_MAX_STREAMS]
-    const DecOutPos* d_tab = nullptr;   // the same memory as the device addresses it
+    uint8_t* h_tab = nullptr;     // [DEC_GROUP_MAX_STREAMS] rows: DecOutPos, or DecOutScalePos when a position of the call is scaled
+    const uint8_t* d_tab = nullptr;     // the same memory as the device addresses it
     uint8_t* d_stage = nullptr; size_t d_cap = 0;
     uint8_t* h_stage = nullptr; size_t h_cap = 0;
 };
@@ -47,7 +69,7 @@ struct DecOutBuf {
 hipError_t out_reserve(DevMem& mem, DecOutBuf& b, size_t dev_bytes, size_t host_bytes)
 {
     if (!b.h_tab) {
-        HIPTRY(DM_PINNED(mem, b.h_tab, 64 * sizeof(DecOutPos)));
+        HIPTRY(DM_PINNED(mem, b.h_tab, 64 * sizeof(DecOutScalePos)));
         HIPTRY(hipHostGetDevicePointer((void**)&b.d_tab, b.h_tab, 0));
     }
     if (dev_bytes > b.d_cap) {
@@ -87,6 +109,51 @@ hipError_t launch_dec_out(const PicStore* s, int layout, const DecOutPos* rows, 
         default: hipLaunchKernelGGL(k_dec_out<DEC_OUT_RGBA>, grid, block, 0, st, P); break;
     }
     return hipGetLastError();
+}
+
+// the same for a call with at least one scaled position: ONE launch of k_dec_out_scaled for all n rows
+hipError_t launch_dec_out_scaled(const PicStore* s, int layout, const DecOutScalePos* rows, const DecOutScalePos* d_tab, int n, uint8_t* dst, hipStream_t st)
+{
+    int tx = 1, ty = 1;
+    for (int i = 0; i < n; i++) {
+        tx = std::max(tx, ((int)rows[i].o.width + DOS_TW - 1) / DOS_TW);
+        ty = std::max(ty, ((int)rows[i].o.height + (int)rows[i].th - 1) / (int)rows[i].th);
+    }
+    DecOutParams P{};
+    P.y = s->d_plane_base[0]; P.u = s->d_plane_base[1]; P.v = s->d_plane_base[2];
+    P.st_y = s->st_y; P.st_c = s->st_c; P.st_ring_y = s->st_ring_y; P.st_ring_c = s->st_ring_c;
+    P.pitch = s->cw; P.dst = dst; P.tab = nullptr;
+    const dim3 grid((unsigned)tx, (unsigned)ty, (unsigned)n), block(256);
+    switch (layout) {
+        case DEC_OUT_I420: hipLaunchKernelGGL(k_dec_out_scaled<DEC_OUT_I420>, grid, block, 0, st, P, d_tab); break;
+        case DEC_OUT_NV12: hipLaunchKernelGGL(k_dec_out_scaled<DEC_OUT_NV12>, grid, block, 0, st, P, d_tab); break;
+        case DEC_OUT_NV21: hipLaunchKernelGGL(k_dec_out_scaled<DEC_OUT_NV21>, grid, block, 0, st, P, d_tab); break;
+        default: hipLaunchKernelGGL(k_dec_out_scaled<DEC_OUT_RGBA>, grid, block, 0, st, P, d_tab); break;
+    }
+    return hipGetLastError();
+}
+
+// What a call delivers, as its table is made: rows[] with width / height = the size DELIVERED, src[] the cropped size of each picture,
+// scaled = at least one stream of the call has an output size.  out_fill writes the table the kernel reads into `tab` (pinned: read
+// in place, or sent along with the step's position table) and returns its bytes; out_launch makes the ONE launch from that table:
+// k_dec_out as ever when no position is scaled, else k_dec_out_scaled for all of them (native positions: ratio 1)
+struct OutCall {
+    DecOutPos rows[DEC_GROUP_MAX_STREAMS];
+    int src[DEC_GROUP_MAX_STREAMS][2];
+    int n = 0;
+    bool scaled = false;
+};
+size_t out_fill(const OutCall& c, uint8_t* tab)
+{
+    if (!c.scaled) { memcpy(tab, c.rows, (size_t)c.n * sizeof(DecOutPos)); return (size_t)c.n * sizeof(DecOutPos); }
+    DecOutScalePos* const t = (DecOutScalePos*)tab;
+    for (int i = 0; i < c.n; i++) t[i] = out_scale_pos(c.rows[i], c.src[i][0], c.src[i][1]);
+    return (size_t)c.n * sizeof(DecOutScalePos);
+}
+hipError_t out_launch(const PicStore* s, int layout, const OutCall& c, const uint8_t* tab, const uint8_t* d_tab, uint8_t* dst, hipStream_t st)
+{
+    if (!c.scaled) return launch_dec_out(s, layout, c.rows, (const DecOutPos*)d_tab, c.n, dst, st);
+    return launch_dec_out_scaled(s, layout, (const DecOutScalePos*)tab, (const DecOutScalePos*)d_tab, c.n, dst, st);
 }
 
 }  // namespace

@@ -38,6 +38,7 @@ using namespace h264;
 #include "rgba_kernels.h"
 #include "scale_kernels.h"
 #include "k_dec_out.h"
+#include "k_dec_out_scale.h"
 #include "dev_mem.h"
 #include "pic_store.h"
 #include "engine.h"
@@ -765,6 +766,21 @@ int64_t mi355x_h264_dec_group_read_all(mi355x_h264_dec_group* g, int layout, int
 int mi355x_h264_dec_group_set_output(mi355x_h264_dec_group* g, int layout, int row_align) { return dg_set_output(g, layout, row_align); }
 int mi355x_h264_dec_group_output(mi355x_h264_dec_group* g, int back, const uint8_t** data, mi355x_h264_dec_out_pic* pics) { return dg_output(g, back, data, pics); }
 
+// the size a stream's pictures are delivered at (k_dec_out_scale.h); nothing on the device is touched: the next call's table says it
+int mi355x_h264_dec_group_set_output_size(mi355x_h264_dec_group* g, int stream, int width, int height)
+{
+    if (!g || stream < -1 || stream >= g->nstreams || !out_size_ok(width, height)) return MI355X_H264_E_ARG;
+    for (int i = 0; i < g->nstreams; i++)
+        if (stream == -1 || stream == i) { g->st[i].out_w = width; g->st[i].out_h = height; }
+    return MI355X_H264_OK;
+}
+int mi355x_h264_dec_group_output_size(const mi355x_h264_dec_group* g, int stream, int* width, int* height)
+{
+    if (!g || !width || !height || stream < 0 || stream >= g->nstreams) return MI355X_H264_E_ARG;
+    *width = g->st[stream].out_w; *height = g->st[stream].out_h;
+    return MI355X_H264_OK;
+}
+
 // ---- the decoder peer (decoder.h): a group of one stream, every call forwarded with stream 0 ----
 
 int mi355x_h264_dec_create(int device, mi355x_h264_decoder** out)
@@ -825,8 +841,14 @@ int64_t mi355x_h264_dec_read(mi355x_h264_decoder* d, int layout, int row_align, 
     if (!d) return MI355X_H264_E_ARG;
     const int64_t n = dec_ret(d, dg_read_all(d->g, layout, row_align, dst, cap, to_device != 0, pic));
     if (n >= 0) { pic->fresh = 1; pic->serial = (int64_t)d->g->st[0].pictures; }
+    // (refused for the output size: the stream's report names both sizes)
+    int W, H;
+    if (n == MI355X_H264_E_ARG && pic && out_args_ok(layout, row_align) && d->g->st[0].last >= 0 && !dg_out_size(d->g->st[0], W, H)) snprintf(d->err, sizeof(d->err), "%s", d->g->st[0].err);
     return n;
 }
+
+int mi355x_h264_dec_set_output_size(mi355x_h264_decoder* d, int width, int height) { return d ? mi355x_h264_dec_group_set_output_size(d->g, 0, width, height) : MI355X_H264_E_ARG; }
+int mi355x_h264_dec_output_size(const mi355x_h264_decoder* d, int* width, int* height) { return d ? mi355x_h264_dec_group_output_size(d->g, 0, width, height) : MI355X_H264_E_ARG; }
 
 // coded-size planes of the last picture (test hook: compared with the oracle decoder's planes)
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder* d, int plane, void* dst, size_t cap)

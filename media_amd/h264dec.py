@@ -85,8 +85,29 @@ def _bind():
         L.mi355x_h264_dec_group_colour.argtypes = [vp, C.c_int, i8]
         L.mi355x_h264_dec_group_set_rgba_colour.argtypes = [vp, C.c_int, cp]
         L.mi355x_h264_parser_colour.argtypes = [vp, i8, C.c_int]
+    if hasattr(L, "mi355x_h264_dec_set_output_size"):   # (likewise: an earlier build delivers at the native size only)
+        L.mi355x_h264_dec_set_output_size.argtypes = [vp, C.c_int, C.c_int]
+        L.mi355x_h264_dec_output_size.argtypes = [vp, ip, ip]
+        L.mi355x_h264_dec_group_set_output_size.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        L.mi355x_h264_dec_group_output_size.argtypes = [vp, C.c_int, ip, ip]
     _bound = True
     return L
+
+
+def _set_output_size(fn, w, h, *args):
+    rc = fn(*args, int(w), int(h))
+    if rc != 0:
+        err = EncoderError("set_output_size(%r, %r) -> %d (even, 2..4096, or 0, 0 for the native size)" % (w, h, rc))
+        err.rc = rc
+        raise err
+
+
+def _output_size(fn, *args):
+    w, h = C.c_int(0), C.c_int(0)
+    rc = fn(*args, C.byref(w), C.byref(h))
+    if rc != 0:
+        raise EncoderError("output_size -> %d" % rc)
+    return w.value, h.value
 
 
 def _tensor_ready(tensor):
@@ -158,7 +179,9 @@ class Decoder:
         pic = OutPic()
         need = lib().mi355x_h264_dec_read(self.h, layout, row_align, None, 0, 0, C.byref(pic))
         if need < 0:
-            raise EncoderError("dec_read(layout %d, row_align %d) -> %d" % (layout, row_align, need))
+            err = EncoderError("dec_read(layout %d, row_align %d) -> %d: %s" % (layout, row_align, need, lib().mi355x_h264_dec_last_error(self.h).decode()))
+            err.rc = need
+            raise err
         if device_tensor is None:
             buf = np.empty(need, np.uint8)
             n = lib().mi355x_h264_dec_read(self.h, layout, row_align, buf.ctypes.data, buf.nbytes, 0, C.byref(pic))
@@ -169,6 +192,15 @@ class Decoder:
         if n != need:
             raise EncoderError("dec_read -> %d: %s" % (n, lib().mi355x_h264_dec_last_error(self.h).decode()))
         return buf, dict(pic.as_dict(), bytes=n)
+
+    def set_output_size(self, w, h):
+        """pictures are delivered by read() at w x h, resampled on the GPU, from the next read on (the same picture may be read
+        at several sizes); 0, 0: at their own size again.  info(), i420() and plane() stay at the native size"""
+        _set_output_size(lib().mi355x_h264_dec_set_output_size, w, h, self.h)
+
+    def output_size(self):
+        """(w, h) as set; (0, 0): the native size"""
+        return _output_size(lib().mi355x_h264_dec_output_size, self.h)
 
     def colour(self):
         """what the sequence parameter set of the last picture says (mi355x_h264_dec_colour): a dict of COLOUR"""
@@ -278,6 +310,14 @@ class DecoderGroup:
     def set_rgba_colour(self, stream, colour):
         """as Decoder.set_rgba_colour, for one stream of the group"""
         _set_rgba_colour(lib().mi355x_h264_dec_group_set_rgba_colour, colour, self.h, stream)
+
+    def set_output_size(self, stream, w, h):
+        """as Decoder.set_output_size, for one stream of the group (stream = -1: for every stream): what read_all() and the armed
+        output() deliver.  A stream whose picture cannot be resampled to its size has offset -1 there, and error(stream) says why"""
+        _set_output_size(lib().mi355x_h264_dec_group_set_output_size, w, h, self.h, stream)
+
+    def output_size(self, stream):
+        return _output_size(lib().mi355x_h264_dec_group_output_size, self.h, stream)
 
     def read_i420(self, stream):
         w, h, _, _ = self.info(stream)

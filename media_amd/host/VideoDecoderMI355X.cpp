@@ -4,8 +4,10 @@
  */
 #define LOG_TAG "VideoDecoderMI355X"
 #include "VideoDecoderMI355X.h"
+#include <cstdlib>
 #include <cstring>
 #include "MediaLog.h"
+#include "Property.h"
 
 VideoDecoderMI355X::~VideoDecoderMI355X()
 {
@@ -53,6 +55,40 @@ DecoderRetCode VideoDecoderMI355X::SetDecodeParams(DecodeParamsIndex index, void
     return VIDEO_DECODER_SUCCESS;
 }
 
+int VideoDecoderMI355X::ParseOutputSize(const std::string &width, const std::string &height, int32_t *outWidth, int32_t *outHeight)
+{
+    if (width.empty() && height.empty()) {
+        return 0;
+    }
+    auto number = [](const std::string &v) {   // 1 .. 5 decimal digits and nothing else; -1 otherwise
+        if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) {
+            return -1;
+        }
+        return atoi(v.c_str());
+    };
+    const int32_t w = number(width), h = number(height);
+    if (w < 2 || h < 2 || w > 4096 || h > 4096 || ((w | h) & 1) != 0) {
+        return -1;
+    }
+    *outWidth = w;
+    *outHeight = h;
+    return 1;
+}
+
+void VideoDecoderMI355X::ReadOutputSizeKeys()
+{
+    const std::string w = GetStrEncParam("persist.vmi.video.decode.outwidth"), h = GetStrEncParam("persist.vmi.video.decode.outheight");
+    m_outWidth = m_outHeight = 0;
+    m_nativeWarnWidth = m_nativeWarnHeight = 0;
+    const int have = ParseOutputSize(w, h, &m_outWidth, &m_outHeight);
+    if (have < 0) {
+        WARN("outwidth '%s' / outheight '%s' rejected (both must be set: decimal, even, 2..4096): frames keep their own size", w.c_str(), h.c_str());
+        m_outWidth = m_outHeight = 0;
+    } else if (have > 0) {
+        INFO("frames are delivered at %dx%d, resampled on the device", m_outWidth, m_outHeight);
+    }
+}
+
 uint32_t VideoDecoderMI355X::ColourChanges(int32_t out[8]) const
 {
     std::memcpy(out, m_colour, sizeof(m_colour));
@@ -67,9 +103,11 @@ DecoderRetCode VideoDecoderMI355X::GetDecodeParams(DecodeParamsIndex index, void
     switch (index) {
         case INDEX_PIC_INFO: {   // ref :287-293
             auto *p = static_cast<PicInfoParams *>(decParams);
-            p->width = m_writeWidth;
-            p->stride = static_cast<int32_t>(m_writeWidth);
-            p->height = p->scanLines = m_writeHeight;
+            // (with an output size asked for: the size frames are delivered at, once one has been)
+            const bool delivered = m_outWidth > 0 && m_frameWidth > 0;
+            p->width = delivered ? m_frameWidth : m_writeWidth;
+            p->stride = static_cast<int32_t>(p->width);
+            p->height = p->scanLines = delivered ? m_frameHeight : m_writeHeight;
             break;
         }
         case INDEX_PORT_FORMAT_INFO: {   // ref :294-304; the output is tight planar 4:2:0
@@ -125,6 +163,8 @@ DecoderRetCode VideoDecoderMI355X::StartDecoder()
     m_stop = false;
     m_pending = false;
     m_colourChanges = 0;
+    m_frameWidth = m_frameHeight = 0;
+    ReadOutputSizeKeys();
     INFO("start decoder success");
     return VIDEO_DECODER_SUCCESS;
 }
@@ -151,6 +191,21 @@ DecoderRetCode VideoDecoderMI355X::SendStreamData(uint8_t *buffer, uint32_t fill
     if (got) {
         int w = 0, h = 0;
         (void) mi355x_h264_dec_picture_info(m_engine, &w, &h, nullptr, nullptr);
+        // the size asked for, where this picture can be resampled to it (no upscaling, no ratio above 4); else its own
+        bool scaled = m_outWidth > 0;
+        if (scaled && !(m_outWidth <= w && w <= 4 * m_outWidth && m_outHeight <= h && h <= 4 * m_outHeight)) {
+            scaled = false;
+            if (m_nativeWarnWidth != static_cast<uint32_t>(w) || m_nativeWarnHeight != static_cast<uint32_t>(h)) {
+                WARN("pictures of %dx%d cannot be resampled to %dx%d: delivered at their own size", w, h, m_outWidth, m_outHeight);
+                m_nativeWarnWidth = static_cast<uint32_t>(w);
+                m_nativeWarnHeight = static_cast<uint32_t>(h);
+            }
+        }
+        (void) mi355x_h264_dec_set_output_size(m_engine, scaled ? m_outWidth : 0, scaled ? m_outHeight : 0);
+        if (scaled) {
+            w = m_outWidth;
+            h = m_outHeight;
+        }
         m_frameWidth = static_cast<uint32_t>(w);
         m_frameHeight = static_cast<uint32_t>(h);
         int32_t colour[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -165,6 +220,10 @@ DecoderRetCode VideoDecoderMI355X::SendStreamData(uint8_t *buffer, uint32_t fill
             mi355x_h264_dec_out_pic pic{};
             m_frame.resize(static_cast<size_t>(w) * h * 4);
             got_bytes = mi355x_h264_dec_read(m_engine, MI355X_H264_PIX_RGBA, 1, m_frame.data(), m_frame.size(), 0, &pic);
+        } else if (scaled) {   // (tight I420 is the I420 layout at row_align 1)
+            mi355x_h264_dec_out_pic pic{};
+            m_frame.resize(static_cast<size_t>(w) * h * 3 / 2);
+            got_bytes = mi355x_h264_dec_read(m_engine, MI355X_H264_PIX_I420, 1, m_frame.data(), m_frame.size(), 0, &pic);
         } else {
             m_frame.resize(static_cast<size_t>(w) * h * 3 / 2);
             got_bytes = mi355x_h264_dec_read_i420(m_engine, m_frame.data(), m_frame.size());

@@ -7,6 +7,7 @@
 #ifndef VIDEO_DECODER_MI355X_H
 #define VIDEO_DECODER_MI355X_H
 
+#include <string>
 #include <vector>
 #include "VideoDecoder.h"
 #include "mi355x_h264_dec.h"
@@ -35,6 +36,10 @@ public:
     // what the sequence parameter set of the last picture says (out[8] of mi355x_h264_dec_colour), and how often it has changed
     // since StartDecoder (the first picture counts: 1)
     uint32_t ColourChanges(int32_t out[8]) const;
+    // extension keys persist.vmi.video.decode.outwidth / .outheight: frames are delivered at that size, resampled on the device
+    // (include/mi355x_h264_dec.h, "output size").  Both decimal, even and 2..4096: 1 and the size; neither set: 0; anything else
+    // (one key alone, junk): -1, and the caller keeps the native size.  Parsed as VideoEncoderMI355X parses .srcwidth / .srcheight
+    static int ParseOutputSize(const std::string &width, const std::string &height, int32_t *outWidth, int32_t *outHeight);
 
 private:
     static constexpr uint32_t kDefaultWidth = 1280, kDefaultHeight = 720;   // the reference adapter's defaults (VideoDecoderNetint.h:34-35)
@@ -50,7 +55,10 @@ private:
     int32_t m_outFormat = PIXEL_FORMAT_YUV_420P;
     int32_t m_colour[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t m_colourChanges = 0;
-    uint32_t m_frameWidth = 0, m_frameHeight = 0;
+    uint32_t m_frameWidth = 0, m_frameHeight = 0;   // of the waiting picture as delivered
+    int32_t m_outWidth = 0, m_outHeight = 0;       // > 0: the size asked for with .outwidth / .outheight (read by StartDecoder)
+    uint32_t m_nativeWarnWidth = 0, m_nativeWarnHeight = 0;   // the native size the last "cannot be resampled" WARN line named
+    void ReadOutputSizeKeys();
     std::function<void(DecodeEventIndex, uint32_t, void *)> m_eventCallBack;
     std::function<uint32_t(uint8_t*, uint8_t*, const PicInfoParams &, uint32_t)> m_copyFrame;
 };

@@ -4,8 +4,16 @@
 #include <cstring>
 #include "VideoDecoder.h"
 #include "VideoDecoderMI355X.h"
+#include "Property.h"
 
 extern "C" {
+// the property store of this library (media_amd/host/Property.h)
+void vd_prop_set(const char *key, const char *text) { SetEncParam(key, text != nullptr ? text : ""); }
+// persist.vmi.video.decode.outwidth / .outheight: 1 (and the size), 0 (neither set) or -1 (rejected)
+int32_t vd_parse_output_size(const char *width, const char *height, int32_t *outWidth, int32_t *outHeight)
+{
+    return VideoDecoderMI355X::ParseOutputSize(width != nullptr ? width : "", height != nullptr ? height : "", outWidth, outHeight);
+}
 struct vd_events { uint32_t count, width, height, stride; };
 
 uint32_t vd_create(void **dec) { return CreateVideoDecoder(reinterpret_cast<VideoDecoder **>(dec)); }

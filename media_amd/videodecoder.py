@@ -38,8 +38,26 @@ def lib():
             getattr(L, name).restype = u32
         L.vd_destroy.argtypes = [vp]
         L.vd_destroy.restype = None
+        L.vd_prop_set.argtypes = [C.c_char_p, C.c_char_p]
+        L.vd_prop_set.restype = None
+        L.vd_parse_output_size.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.vd_parse_output_size.restype = C.c_int32
         _lib = L
     return _lib
+
+
+def parse_output_size(width, height):
+    """what persist.vmi.video.decode.outwidth = width and .outheight = height select: (W, H) when both are decimal, even and
+    2..4096; None when neither is set; False for anything else (one WARN line, frames keep their own size)"""
+    w, h = C.c_int32(0), C.c_int32(0)
+    rc = lib().vd_parse_output_size(str(width).encode(), str(height).encode(), C.byref(w), C.byref(h))
+    return None if rc == 0 else ((w.value, h.value) if rc > 0 else False)
+
+
+def set_output_size(width=None, height=None):
+    """the two keys as StartDecoder reads them (None: unset)"""
+    lib().vd_prop_set(b"persist.vmi.video.decode.outwidth", b"" if width is None else str(width).encode())
+    lib().vd_prop_set(b"persist.vmi.video.decode.outheight", b"" if height is None else str(height).encode())
 
 
 class PluginDecoder:

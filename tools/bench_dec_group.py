@@ -5,11 +5,14 @@ access units.  Both forms run interleaved, --repeat times each, in one process, 
     each   every stream's picture with read_i420(k), one after the other (the objects: i420() on each stream's thread)
     all    all pictures of a step with one read_all() (--layout, to the host)
     armed  set_output() once; per step decode(t + 1), then output(back=1): the pictures of step t, copied while t + 1 was parsed
+--out-size WxH (with all / armed) adds a third form, group_scaled: the same group with every stream's output size set
+(mi355x_h264_dec_group_set_output_size), interleaved with the other forms in the same run; --no-objects leaves the objects out.
 The objects know `none` and read every picture back in all other modes.  Prints one JSON line per (S, form, read) with median and
 min / max fps, and for the group the host's parse / launch time per picture (mi355x_h264_dec_group_last_step).  Kernel times: run it
 once under `rocprofv3 --kernel-trace --stats -- python tools/bench_dec_group.py --streams 16 --repeat 1 --read armed`.
 
-    python tools/bench_dec_group.py [--streams 1,4,16,32] [--pictures 60] [--repeat 3] [--read none,each] [--layout i420]"""
+    python tools/bench_dec_group.py [--streams 1,4,16,32] [--pictures 60] [--repeat 3] [--read none,each] [--layout i420]
+                                    [--out-size 480x270] [--no-objects]"""
 import argparse
 import json
 import os
@@ -33,9 +36,11 @@ def make_stream(n):
 LAYOUTS = {"i420": 0, "nv12": 1, "nv21": 2, "rgba": 3}
 
 
-def run_group(aus, S, read, layout=0):
+def run_group(aus, S, read, layout=0, out_size=None):
     from media_amd import h264dec
     g = h264dec.DecoderGroup(S)
+    if out_size:
+        g.set_output_size(-1, *out_size)
     parse_us = launch_us = 0
     dst = None  # read_all's destination
     taken = 0   # bytes looked at, so that no mode gets away with not touching its pictures
@@ -102,20 +107,30 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--read", default="none,each", help="read modes, comma-separated: none, each, all, armed")
     ap.add_argument("--layout", default="i420", choices=sorted(LAYOUTS), help="of the modes all and armed")
+    ap.add_argument("--out-size", default="", help="WxH: also run the group with this output size for every stream (modes all and armed)")
+    ap.add_argument("--no-objects", action="store_true", help="leave out the S Decoder objects")
     a = ap.parse_args()
     modes = a.read.split(",")
     assert all(m in ("none", "each", "all", "armed") for m in modes), modes
+    out_size = tuple(int(x) for x in a.out_size.split("x")) if a.out_size else None
+    assert out_size is None or (len(out_size) == 2 and all(m in ("all", "armed") for m in modes)), "--out-size WxH goes with --read all|armed"
     aus = make_stream(a.pictures)
     for S in [int(x) for x in a.streams.split(",")]:
         for read in modes:
-            runs = {"group": [], "objects": []}
+            forms = ["group"] + (["group_scaled"] if out_size else []) + ([] if a.no_objects else ["objects"])
+            runs = {form: [] for form in forms}
             extra = {}
             for _ in range(a.repeat):
-                for form, fn in (("group", run_group), ("objects", run_objects)):
-                    fps, extra[form] = fn(aus, S, read, LAYOUTS[a.layout]) if form == "group" else fn(aus, S, read)
+                for form in forms:
+                    if form == "objects":
+                        fps, extra[form] = run_objects(aus, S, read)
+                    else:
+                        fps, extra[form] = run_group(aus, S, read, LAYOUTS[a.layout], out_size if form == "group_scaled" else None)
                     runs[form].append(fps)
-            for form in ("group", "objects"):
+            for form in forms:
                 v = runs[form]
+                if form == "group_scaled":
+                    extra[form]["out_size"] = a.out_size
                 print(json.dumps(dict({"streams": S, "form": form, "read_back": read != "none", "read": read, "layout": a.layout if read in ("all", "armed") else "i420", "pictures_per_stream": a.pictures, "fps_median": round(statistics.median(v), 1),
                                        "fps_min": round(min(v), 1), "fps_max": round(max(v), 1), "runs": [round(x, 1) for x in v]}, **extra[form])), flush=True)
 
