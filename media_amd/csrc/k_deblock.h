@@ -183,9 +183,12 @@ __global__ __launch_bounds__(64) void k_deblock_diag(DbParams D, int s)
 // 24 granules per macroblock, each ONE aligned 8-byte agent-scope relaxed atomic
 // store of {tag = picture serial, 4 samples}; the consumer re-reads its granules
 // with agent-scope atomic loads (L1-bypassing) until every tag matches.  No fence,
-// no separate flag, no drain.  Each sample of the picture has exactly one writer:
+// no separate flag, no drain.  Each sample of the picture has at most one writer:
 // a row stores rows 0..11 of its macroblocks (0..5 chroma), the row below stores
-// rows 12..15 (6..7) after its own top-edge filter; the last row stores all 16.
+// rows 12..15 (6..7) after its own top-edge filter - where it filters that edge;
+// where it does not, nothing is handed down or waited for and the row stores all
+// 16 itself, as the last row does everywhere.  A macroblock the filter cannot have
+// changed is not stored at all (db_hands_down, db_dirty further down).
 // Everything a macroblock needs from HBM (its samples, MbInfo, granules) is
 // requested one macroblock ahead, so an iteration is LDS/VALU work only.
 // Every spin is bounded; a timeout sets *err and the grid still drains.
@@ -434,21 +437,39 @@ __device__ __forceinline__ void db_store_apron(const DbParams& D, uint8_t* const
 // -DDB_AB_COUNT (measurement build, make ab): what the macroblock steps wait on.  Per wave in registers, added once at the wave's
 // end with vector atomic adds: iterations that have a wait, those whose prefetched tag was stale, those still stale at the first
 // look (the same number since the re-request left), spin passes.  The host reads and clears the four words with mi355x_h264_db_counts().
-struct DbCount { unsigned iters, stale, still_stale, spins; };
+// Since the sparse hand-off four more.  Three are counted per row (a wave of the pair form counts each of its rows; lanes 0 and 32
+// add) and are the picture's own, whatever the form: macroblocks with a filtered top edge (an apron to take, through LDS or after a
+// wait), macroblocks whose stores were skipped (clean), sets of bottom rows handed down (granules or ring slots).  The fourth is the
+// wave's: iterations in which no row of the wave has an edge to filter, a macroblock to store or rows to hand down (the row form
+// counts its macroblock iterations, the pair form all of them).  mi355x_h264_db_counts2() reads all eight; tools/db_sparsity.py
+// restates them from the oracle's macroblock records.
+struct DbCount { unsigned iters, stale, still_stale, spins, top_on, idle, skipped, published; };
+#define DB_COUNT_ZERO {0, 0, 0, 0, 0, 0, 0, 0}
 #ifdef DB_AB_COUNT
-__device__ unsigned g_db_count[4];
-__device__ __forceinline__ void db_count_flush(const DbCount& c, const int lane)
+__device__ unsigned g_db_count[8];
+__device__ __forceinline__ void db_count_flush(const DbCount& c, const int lane, const bool two_rows)
 {
     if (lane == 0 && c.iters) {
         atomicAdd(&g_db_count[0], c.iters); atomicAdd(&g_db_count[1], c.stale);
         atomicAdd(&g_db_count[2], c.still_stale); atomicAdd(&g_db_count[3], c.spins);
+    }
+    if (lane == 0) atomicAdd(&g_db_count[5], c.idle);
+    if (lane == 0 || (two_rows && lane == 32)) {
+        atomicAdd(&g_db_count[4], c.top_on); atomicAdd(&g_db_count[6], c.skipped); atomicAdd(&g_db_count[7], c.published);
     }
 }
 }  // namespace h264
 extern "C" __attribute__((visibility("default"))) int mi355x_h264_db_counts(unsigned out[4], int clear)
 {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h264::g_db_count), 4 * sizeof(unsigned)) != hipSuccess) return -1;
-    const unsigned zero[4] = {0, 0, 0, 0};
+    const unsigned zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (all eight: one set of counters)
+    if (clear && hipMemcpyToSymbol(HIP_SYMBOL(h264::g_db_count), zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+extern "C" __attribute__((visibility("default"))) int mi355x_h264_db_counts2(unsigned out[8], int clear)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h264::g_db_count), 8 * sizeof(unsigned)) != hipSuccess) return -1;
+    const unsigned zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (clear && hipMemcpyToSymbol(HIP_SYMBOL(h264::g_db_count), zero, sizeof(zero)) != hipSuccess) return -1;
     return 0;
 }
@@ -469,7 +490,7 @@ namespace h264 {
 __device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64* const addr, const unsigned serial, bool& timed_out, DbCount& cnt)
 {
     const bool stale = __ballot(need && (unsigned)(g >> 32) != serial) != 0ull;
-    DB_COUNT(cnt.iters++; if (stale) { cnt.stale++; cnt.still_stale++; })
+    DB_COUNT(if (__ballot(need) != 0ull) { cnt.iters++; if (stale) { cnt.stale++; cnt.still_stale++; } })
     if (timed_out || !stale) return;
     unsigned spins = 0;
     do {
@@ -479,6 +500,22 @@ __device__ __forceinline__ void db_wait_tags(const bool need, u64& g, const u64*
     } while (__ballot(need && (unsigned)(g >> 32) != serial) != 0ull);
     DB_COUNT(cnt.spins += spins;)
 }
+// The hand-off and the stores happen only where the picture needs them.  Both tests are uniform over the lanes of a row.
+//   db_hands_down: macroblock (x, r) hands its bottom rows (12..15 / 6..7) to the row below exactly where that row filters its top
+//     edge there: below_top = bS word (dir 1, edge 0) of macroblock (x, r + 1), any segment.  The row below decides its wait, its top
+//     apron and the apron's store by the SAME word of the SAME array (its own b1.x), which k_bs / k_dec_bs_pos wrote before the
+//     launch: a wait exists only where a publish does.  Elsewhere row r stores the rows itself, and db_horizontal with edge 0
+//     skipped (or run with bS 0 beside the pair's other row: no sample changes) makes no use of tile rows -4..-1.
+//   db_dirty: a macroblock's samples can differ from the picture's - the filter works in place - only when one of its own eight
+//     edge groups has a strength, or the left edge of its right neighbour (nb0; none behind the last macroblock), or the top edge
+//     below (then the rows it can change travel down and are stored there).  A clean macroblock stores nothing.  A strength whose
+//     alpha / beta test fails on every line still counts as dirty: conservative, and known without looking at a sample.
+// SAFETY of the sparse hand-off: the set of waits is a subset of the waits of the form that handed every macroblock down; every
+// wait that remains is answered by a publish decided from the same memory word; there is no new spin and no fence, and the bounded
+// spin with its timed_out path (db_wait_tags) is as it was.  Every sample of the picture keeps at most one writer.
+__device__ __forceinline__ bool db_hands_down(const bool last_row, const uint32_t below_top) { return !last_row && below_top != 0; }
+__device__ __forceinline__ bool db_dirty(const uint32_t own, const bool have_right, const uint4 nb0) { return own != 0 || (have_right && nb0.x != 0); }
+__device__ __forceinline__ uint32_t db_any(const uint4 b0, const uint4 b1) { return b0.x | b0.y | b0.z | b0.w | b1.x | b1.y | b1.z | b1.w; }
 
 // ===========================================================================
 // Row form: one wave per macroblock row; all 64 lanes move samples (one luma dword each), lanes 0..31 filter.
@@ -533,7 +570,9 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     uint32_t pf_y = 0, pf_c = 0;
     uint4 pf_b0 = {0, 0, 0, 0}, pf_b1 = pf_b0;
     u64 pf_g = 0;
+    uint32_t pf_tn = 0;   // top-edge strengths of the macroblock BELOW (its bS word dir 1, edge 0): does that row take our bottom rows?
     const int grow = first_row ? my : my - 1;      // a first row reads (and ignores) its own slots
+    const int trow = last_row ? my : my + 1;       // (a last row hands nothing down and ignores the word)
     const int glane = lane < 24 ? lane : lane - 24 < 24 ? lane - 24 : lane - 48;
     const int last_mx = D.mbw - 1;
     auto prefetch = [&](int mx) {   // mx clamped by the caller into 0 .. mbw - 1
@@ -542,10 +581,11 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
         const uint4* b = (const uint4*)(bsw + ((size_t)my * D.mbw + mx) * 8);
         pf_b0 = b[0]; pf_b1 = b[1];
         pf_g = AT_LOAD(handoff + ((size_t)grow * D.mbw + mx) * 24 + glane);
+        pf_tn = bsw[((size_t)trow * D.mbw + mx) * 8 + 4];
         if (PERMB) pf_q = (uint32_t)D.mbqp[(size_t)my * D.mbw + mx] | ((uint32_t)D.mbqp[(size_t)grow * D.mbw + mx] << 8);
     };
     auto consume = [&]() {   // forces the waits for the prefetched registers to sit here
-        asm volatile("" : "+v"(pf_y), "+v"(pf_c), "+v"(pf_g));
+        asm volatile("" : "+v"(pf_y), "+v"(pf_c), "+v"(pf_g), "+v"(pf_tn));
         asm volatile("" : "+v"(pf_b0.x), "+v"(pf_b0.y), "+v"(pf_b0.z), "+v"(pf_b0.w));
         asm volatile("" : "+v"(pf_b1.x), "+v"(pf_b1.y), "+v"(pf_b1.z), "+v"(pf_b1.w));
         if (PERMB) asm volatile("" : "+v"(pf_q));
@@ -555,7 +595,8 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
     uint32_t cur_y = pf_y, cur_c = pf_c, cur_q = pf_q;
     uint4 b0 = pf_b0, b1 = pf_b1;
     u64 g = pf_g;
-    DbCount cnt = {0, 0, 0, 0};
+    uint32_t tn = pf_tn, prev_tn = 0, prev_own = 0;   // prev_*: of macroblock mx - 1, which store_prev serves
+    DbCount cnt = DB_COUNT_ZERO;
 
     // the previous macroblock is final with respect to this row once the current one's LEFT edge has been filtered (its
     // other vertical edges and its horizontal edges do not touch it): store / publish it.  Issued between the left edge and
@@ -566,11 +607,13 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
         if (mx > 0) {
             const int pmx = mx - 1;
             const int co = have_cur ? -16 : 0, cco = have_cur ? -8 : 0;  // after the last macroblock there was no shift
-            const int nrow = last_row ? 16 : 12, ncrow = last_row ? 8 : 6;
-            if (yr < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr, co + yc4));
-            if (lane < 32 && cr_l < ncrow)
+            const bool down = db_hands_down(last_row, prev_tn), dirty = db_dirty(prev_own, have_cur, b0);
+            const int nrow = down ? 12 : 16, ncrow = down ? 6 : 8;
+            DB_COUNT(if (!dirty) cnt.skipped++; if (down) cnt.published++;)
+            if (dirty && yr < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr, co + yc4));
+            if (dirty && lane < 32 && cr_l < ncrow)
                 *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = dw(db_c(s_y, cpl_l, cr_l, cco + cc4));
-            if (!last_row && lane < 24)
+            if (down && lane < 24)
                 AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + lane, ((u64)R.serial << 32) | db_bottom_dword(s_y, lane, have_cur));
         }
     };
@@ -608,7 +651,13 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             db_inner_vertical<BS4>(L, px, b0, v_on, thr);
             // the top apron is needed from here on and not before (the vertical edges touch rows 0..15 only): wait until
             // every granule of the macroblock above carries this picture's tag
-            if (!first_row) {
+            // every granule of the macroblock above carries this picture's tag - where the top edge is filtered: only then has the
+            // row above handed its bottom rows down (db_hands_down, from the same word), and only then does edge 0 of
+            // db_horizontal look at rows -4..-1
+            const bool top_on = !first_row && b1.x != 0;
+            DB_COUNT(if (top_on) cnt.top_on++;
+                     if (!db_any(b0, b1) && !(mx > 0 && (db_hands_down(last_row, prev_tn) || db_dirty(prev_own, true, b0)))) cnt.idle++;)
+            if (top_on) {
                 db_wait_tags(lane < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out, cnt);
                 db_put_apron(s_y, lane, (uint32_t)g);
             }
@@ -618,14 +667,15 @@ __device__ __forceinline__ void deblock_rows_picture(const DbRowParams& R, const
             wave_sync();
             consume();   // the next macroblock's data has arrived; nothing below waits for memory any more
             // 6. the top apron (rows 12..15 / 6..7 of the macroblock above) is final: store it
-            if (!first_row) db_store_apron(D, s_y, lane, mx, my);
+            if (top_on) db_store_apron(D, s_y, lane, mx, my);
         }
         if (!have_cur) store_prev(mx, false);   // after the last macroblock of the row
-        cur_y = pf_y; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; cur_q = pf_q;
+        prev_tn = tn; prev_own = db_any(b0, b1);
+        cur_y = pf_y; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; cur_q = pf_q; tn = pf_tn;
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;  // pinned host word, read after the picture's event
-    DB_COUNT(db_count_flush(cnt, lane);)
+    DB_COUNT(db_count_flush(cnt, lane, false);)
 }
 // The kernels: workgroup (row, y) filters its row of pictures y, y + gridDim.y, ... of the step's R.npic pictures.  A launch whose
 // pictures nearly all return at once - the stream hub's bS 4 launch on P steps of content without intra macroblocks - is made with
@@ -707,6 +757,10 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
     uint32_t pf_y0 = 0, pf_y1 = 0, pf_c = 0;
     uint4 pf_b0 = {0, 0, 0, 0}, pf_b1 = pf_b0;
     u64 pf_g = 0;
+    uint32_t pf_tn = 0;   // top-edge strengths of the macroblock below this lane's row, as in the row form.  (For the upper row that is
+                          // the lower half's b1.x of the same iteration; the load is issued for all 64 lanes either way, so both rows
+                          // take the word the same way and no lane is read across.)
+    const int trow = last_row ? my : my + 1;
     // only the upper row reads global granules (those of the row above it); a first row and the lanes of the lower row read
     // and ignore row A's own slots - never row -1
     const int grow = (first_row || half == 1) ? rowA : rowA - 1;
@@ -719,9 +773,10 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
         const uint4* b = (const uint4*)(bsw + ((size_t)my * D.mbw + mx) * 8);
         pf_b0 = b[0]; pf_b1 = b[1];
         pf_g = AT_LOAD(handoff + ((size_t)grow * D.mbw + mx) * 24 + glane);
+        pf_tn = bsw[((size_t)trow * D.mbw + mx) * 8 + 4];
     };
     auto consume = [&]() {
-        asm volatile("" : "+v"(pf_y0), "+v"(pf_y1), "+v"(pf_c), "+v"(pf_g));
+        asm volatile("" : "+v"(pf_y0), "+v"(pf_y1), "+v"(pf_c), "+v"(pf_g), "+v"(pf_tn));
         asm volatile("" : "+v"(pf_b0.x), "+v"(pf_b0.y), "+v"(pf_b0.z), "+v"(pf_b0.w));
         asm volatile("" : "+v"(pf_b1.x), "+v"(pf_b1.y), "+v"(pf_b1.z), "+v"(pf_b1.w));
     };
@@ -730,20 +785,24 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
     uint32_t cur_y0 = pf_y0, cur_y1 = pf_y1, cur_c = pf_c;
     uint4 b0 = pf_b0, b1 = pf_b1;
     u64 g = pf_g;
-    DbCount cnt = {0, 0, 0, 0};
+    uint32_t tn = pf_tn, prev_tn = 0, prev_own = 0;   // prev_*: of macroblock mx - 1, which store_prev serves
+    DbCount cnt = DB_COUNT_ZERO;
 
-    // the previous macroblock of this lane's row is final for the row: rows 0..11 (all 16 of a last row) to the picture, rows
-    // 12..15 handed down - the upper row into the LDS ring, the lower row as global granules for the next pair
+    // the previous macroblock of this lane's row is final for the row: what the filter can have changed of it goes to the picture,
+    // rows 12..15 are handed down where the row below filters its top edge (db_hands_down) - the upper row into the LDS ring, the
+    // lower row as global granules for the next pair - and go to the picture with the rest where it does not
     auto store_prev = [&](const int mx, const bool have_cur) {
         if (mx > 0 && live) {
             const int pmx = mx - 1;
             const int co = have_cur ? -16 : 0, cco = have_cur ? -8 : 0;
-            const int nrow = last_row ? 16 : 12, ncrow = last_row ? 8 : 6;
-            *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0, co + yc4));
-            if (yr0 + 8 < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0 + 8) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0 + 8, co + yc4));
-            if (cr_l < ncrow)
+            const bool down = db_hands_down(last_row, prev_tn), dirty = db_dirty(prev_own, have_cur, b0);
+            const int nrow = down ? 12 : 16, ncrow = down ? 6 : 8;
+            DB_COUNT(if (!dirty) cnt.skipped++; if (down) cnt.published++;)
+            if (dirty) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0, co + yc4));
+            if (dirty && yr0 + 8 < nrow) *(uint32_t*)(D.pl[0] + (size_t)(16 * my + yr0 + 8) * D.cw + 16 * pmx + yc4) = dw(db_y(s_y, yr0 + 8, co + yc4));
+            if (dirty && cr_l < ncrow)
                 *(uint32_t*)((cpl_l ? D.pl[2] : D.pl[1]) + (size_t)(8 * my + cr_l) * cs + 8 * pmx + cc4) = dw(db_c(s_y, cpl_l, cr_l, cco + cc4));
-            if (!last_row && hl < 24) {
+            if (down && hl < 24) {
                 const uint32_t v = db_bottom_dword(s_y, hl, have_cur);
                 if (half == 0) s_ring[pmx & 1][hl] = v;
                 else AT_STORE(handoff + ((size_t)my * D.mbw + pmx) * 24 + hl, ((u64)R.serial << 32) | v);
@@ -784,19 +843,24 @@ __device__ __forceinline__ void deblock_pairs_picture(const DbRowParams& R, cons
         wave_sync();   // (the ring slot written above is read by the other half's lanes)
         // top apron, needed by the horizontal edges only: the upper row waits for the previous pair's granules, the lower row
         // takes the ring slot the upper row has just filled
-        db_wait_tags(have_cur && !from_lds && !first_row && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out, cnt);
-        if (have_cur && !first_row && hl < 24) db_put_apron(s_y, hl, from_lds ? s_ring[mx & 1][hl] : (uint32_t)g);
+        // - each where its top edge is filtered, which is where the row above has handed anything down
+        const bool top_on = have_cur && !first_row && b1.x != 0;
+        DB_COUNT(if (top_on) cnt.top_on++;
+                 if (__ballot(in_range && ((have_cur && db_any(b0, b1) != 0) || (mx > 0 && (db_hands_down(last_row, prev_tn) || db_dirty(prev_own, have_cur, b0))))) == 0ull) cnt.idle++;)
+        db_wait_tags(top_on && !from_lds && hl < 24, g, handoff + ((size_t)grow * D.mbw + mx) * 24 + glane, R.serial, timed_out, cnt);
+        if (top_on && hl < 24) db_put_apron(s_y, hl, from_lds ? s_ring[mx & 1][hl] : (uint32_t)g);
         wave_sync();
         db_horizontal<BS4>(L, b1, h_on, thr, thr);
         wave_sync();
         consume();
         // the top apron (rows 12..15 / 6..7 of the macroblock above) is final: store it
-        if (have_cur && !first_row && hl < 24) db_store_apron(D, s_y, hl, mx, my);
-        if (mx + 1 >= 0 && mx + 1 <= last_mx) { cur_y0 = pf_y0; cur_y1 = pf_y1; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; }
+        if (top_on && hl < 24) db_store_apron(D, s_y, hl, mx, my);
+        if (have_cur) { prev_tn = tn; prev_own = db_any(b0, b1); }
+        if (mx + 1 >= 0 && mx + 1 <= last_mx) { cur_y0 = pf_y0; cur_y1 = pf_y1; cur_c = pf_c; b0 = pf_b0; b1 = pf_b1; g = pf_g; tn = pf_tn; }
         wave_sync();
     }
     if (timed_out && lane == 0) *R.err = 1u;
-    DB_COUNT(db_count_flush(cnt, lane);)
+    DB_COUNT(db_count_flush(cnt, lane, true);)
 }
 template <bool BS4, bool IND = false>
 __global__ __launch_bounds__(64) void k_deblock_pairs(DbRowParams R)
