@@ -108,7 +108,13 @@ struct FrameParams {
     // per batch item, value = pic_serial when raised by a kernel of this picture (never cleared: the serial changes):
     unsigned* anypcm;    //   the picture holds an I_PCM macroblock (it is then not loop-filtered: slice header idc 1)
     unsigned* anyintra;  //   P picture: the motion search handed macroblocks to the intra pass (k_pintra_rows, bS 3 / 4 edges)
+    unsigned* stepintra; //   ONE word of the step (no batch stride): some P picture of it has macroblocks for the intra pass.  k_me raises
+                         //   it beside anyintra; a wave of the encoder's own intra pass asks it first and walks the pictures only then
     unsigned pic_serial;
+    // the GPU's motion-search lock (engine.h, k_turn_acquire), where this step's search took it and k_tq follows: its first wave gives
+    // it back (k_tq.h tq_turn_release).  Null in every other launch.
+    unsigned* turn_lock;
+    unsigned turn_id;
     SliceRows sl;        // slices of the picture: bands of sl.rows macroblock rows (sl.rows = mbh: one slice)
     Band band;           // the rows this instance encodes; grids cover the band, coordinates stay those of the picture
     MbDiv mbdiv;         // macroblock index / mbw

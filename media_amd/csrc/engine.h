@@ -108,12 +108,32 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
 // coding, row wavefronts) run in the issue slots the other's motion search leaves.  Left to themselves the instances settle in
 // whatever phase their first steps put them - search beside filter (good), or search beside search and filter beside filter (2 - 5 %
 // less, run by run: section 7 of DESIGN.md).  A lock word in device memory per GPU keeps the searches apart: a one-wave kernel in
-// front of a search takes it (compare-and-swap, sleeping between tries), a one-thread kernel behind the search gives it back.
+// front of a search takes it (compare-and-swap, sleeping between tries), and behind the search it is given back: by the first wave
+// of k_tq, the kernel that follows the search on the same stream (k_tq.h tq_turn_release: the lock and the id travel in its
+// FrameParams; a launch of its own for that one compare-and-swap cost a kernel boundary on every P step's chain), or - High profile,
+// where k_tq8 follows - by the one-thread kernel k_turn_release in front of k_tq8 (the release from inside k_tq8 measured SLOWER
+// than the launch, in every run: DESIGN.md section 11).
 // Whoever comes first goes first - no order is imposed, so an engine in its IDR step, or gone, holds nobody up (an ORDER between the
 // engines' searches, by events or by counters, follows the order in which the host threads happened to queue them and left one
-// instance idle for 1.4 ms of every step) - and the holder's search is already queued behind its acquire, so the lock is always given
-// back; the wait gives up after TURN_TIMEOUT_US all the same.
+// instance idle for 1.4 ms of every step) - and the holder's search and the release behind it (k_turn_release, or the k_tq that
+// carries the lock) are queued right behind its acquire, in the same submit_step and with no early return between them, so the
+// lock is always given back; the wait gives up after TURN_TIMEOUT_US all the same.
 // ---------------------------------------------------------------------------------------------------------------
+// -DTURN_AB_COUNT (measurement build, make ab): acquires that ended by the time-out instead of by getting the lock - a release that
+// went missing would show here; the host reads and clears the word with mi355x_h264_turn_timeouts().
+#ifdef TURN_AB_COUNT
+__device__ unsigned g_turn_timeouts;
+extern "C" __attribute__((visibility("default"))) int mi355x_h264_turn_timeouts(unsigned* out, int clear)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_turn_timeouts), sizeof(unsigned)) != hipSuccess) return -1;
+    const unsigned zero = 0;
+    if (clear && hipMemcpyToSymbol(HIP_SYMBOL(g_turn_timeouts), &zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+#define TURN_COUNT_TIMEOUT() atomicAdd(&g_turn_timeouts, 1u)
+#else
+#define TURN_COUNT_TIMEOUT() ((void)0)
+#endif
 __global__ void k_turn_acquire(unsigned* lock, unsigned id, int timeout_us)
 {
     if (threadIdx.x) return;
@@ -121,7 +141,7 @@ __global__ void k_turn_acquire(unsigned* lock, unsigned id, int timeout_us)
     for (;;) {
         unsigned expect = 0u;
         if (__hip_atomic_compare_exchange_strong(lock, &expect, id, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        if (wall_clock64() - t0 > (long long)timeout_us * 100) { __hip_atomic_store(lock, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+        if (wall_clock64() - t0 > (long long)timeout_us * 100) { TURN_COUNT_TIMEOUT(); __hip_atomic_store(lock, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
         __builtin_amdgcn_s_sleep(16);
     }
 }
@@ -259,16 +279,17 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         HIPCHK(e->err, hipMemcpyAsync(e->d_mvq, T.inj->mvq, n * 8 * sizeof(int16_t), hipMemcpyHostToDevice, st));
         HIPCHK(e->err, hipMemcpyAsync(e->d_aux, T.inj->mbaux, n * 16, hipMemcpyHostToDevice, st));
         HIPCHK(e->err, hipMemsetAsync(e->d_me_cost, 0, n * sizeof(uint16_t), st));
-        unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {};
+        unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {}, stepintra = 0;
         const MbInfo* m = (const MbInfo*)T.inj->mbinfo;
         for (int g = 0; g < T.n; g++)
             for (int i = 0; i < e->nmb; i++) {
                 const int type = m[(size_t)g * e->nmb + i].type;
                 if (type == MB_IPCM) anypcm[g] = pic_serial;
-                if (!idr && mb_is_intra_host(type)) anyintra[g] = pic_serial;
+                if (!idr && mb_is_intra_host(type)) anyintra[g] = stepintra = pic_serial;
             }
         HIPCHK(e->err, hipMemcpyAsync(e->d_anypcm, anypcm, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
         HIPCHK(e->err, hipMemcpyAsync(e->d_anyintra, anyintra, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIPCHK(e->err, hipMemcpyAsync(e->d_stepintra, &stepintra, sizeof(unsigned), hipMemcpyHostToDevice, st));
         HIPCHK(e->err, hipStreamSynchronize(st));   // (the flag arrays live on this stack)
     } else if (idr) {
         StatScope sc(e, &S, MI355X_H264_K_INTRA, (uint32_t)(e->diag_mode ? e->mbw + e->mbh - 1 : 1), (uint32_t)(e->b_nmb * T.n), st);
@@ -296,19 +317,26 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
                 for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
                 LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
             } }
-          if (turns) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
+          // the lock goes back with the first wave of the k_tq that follows on this stream (k_tq.h tq_turn_release); in front of k_tq8
+          // by a launch of its own
+          if (turns && e->cfg.profile_idc == 100) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
+          else if (turns) { P.turn_lock = g_turns.d_lock[e->device]; P.turn_id = (unsigned)e->me_turn; }
         }
         { StatScope sc(e, &S, MI355X_H264_K_PMB, 1, (uint32_t)(e->b_nmb * T.n), st);
           if (e->cfg.profile_idc == 100) LAUNCH2(ind, k_tq8<true>, k_tq8<false>, dim3((e->b_nmb + 15) / 16, G), dim3(64), st, P);   // High: 8x8 transform, sixteen macroblocks per wave
-          else LAUNCH2(ind, k_tq<true>, k_tq<false>, dim3((e->b_nmb + 7) / 8, G), dim3(64), st, P); }   // one wave per eight macroblocks
+          else LAUNCH2(ind, k_tq<true>, k_tq<false>, dim3((e->b_nmb + 7) / 8, G), dim3(64), st, P);   // one wave per eight macroblocks
+          P.turn_lock = nullptr; }   // (given back: no later launch of the step carries it)
         {   // macroblocks the motion search handed to the intra pass (returns at once when there are none)
             const IntraRowParams R = intra_row_params(e, P, Y.h_err, (int)G);
-            // Their grids hold ONE picture at a time (the workgroups walk the step's pictures) while the recent P pictures had next to
+            // The grid holds ONE picture at a time (the workgroups walk the step's pictures) while the recent P pictures had next to
             // no intra macroblocks, all of them once they have: see k_pintra_rows.  MI355X_H264_PINTRA_SLOTS fixes the number.
             static const int pslots_env = getenv("MI355X_H264_PINTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_PINTRA_SLOTS"))) : 0;
             const unsigned pslots = std::min(G, pslots_env ? (unsigned)pslots_env : (e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u));
-            LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3(std::min((e->b_nmb + 3) / 4, (int)I4_MARKED_WAVES), pslots), dim3(64), st, P, (int)G);
-            LAUNCH2(ind, (k_pintra_rows<false, true>), (k_pintra_rows<false, false>), dim3(e->b_rows, pslots), dim3(64), st, R);
+            if (ind) {   // the stream hub: Intra4x4 or Intra16x16 and the block modes of the marked macroblocks first, then the rows
+                hipLaunchKernelGGL(k_i4_decide<true>, dim3(std::min((e->b_nmb + 3) / 4, (int)I4_MARKED_WAVES), pslots), dim3(64), 0, st, P, (int)G);
+                hipLaunchKernelGGL((k_pintra_rows<false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
+            } else   // the encoder's own batches: ONE launch, the row waves decide as they go, and one load when the step has nothing for them
+                hipLaunchKernelGGL((k_pintra_rows<false, false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
         }
     }
     // entropy coding: slice headers per position

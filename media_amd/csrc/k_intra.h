@@ -697,12 +697,19 @@ __global__ __launch_bounds__(128) void k_intra_rows(IntraRowParams R)
 // ===========================================================================
 // DEC (the decoder peer): the intra macroblocks are those of intra type in the MbInfo the host parser filled (every macroblock
 // of an I picture); they are reconstructed from the given modes and levels, and the pictures are those of a decoder group's step.
-template <bool DEC, bool IND = false>
+// DECIDE (the encoder's own lockstep steps): the whole intra pass of a P step is this ONE launch.  Intra4x4-or-16x16 and the block
+// modes of a marked macroblock (k_intra4.h i4_decide_mb, from the source alone) are chosen by the row wave just before it codes
+// the macroblock - no launch of k_i4_decide's marked form in front - and a wave first asks the STEP's flag (FrameParams::stepintra):
+// on a step none of whose pictures has a marked macroblock, which is nearly every step, it returns after that one load and
+// does not walk the pictures' own flags, a chain of dependent scalar loads as long as the step has pictures.
+template <bool DEC, bool IND = false, bool DECIDE = false>
 __global__ __launch_bounds__(64) void k_pintra_rows(IntraRowParams R)
 {
     static_assert(!DEC || IND, "the decoder's pictures are positions of a decoder group's table");
+    static_assert(!DECIDE || (!DEC && !IND), "the encoder's own steps only");
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x;
+    if constexpr (DECIDE) { if (*R.p.stepintra != R.p.pic_serial) return; }
     __shared__ IntraLds S;
     bool tab_ready = false;   // the Intra4x4 address table is built by the first macroblock that needs this wave: most rows of most P pictures have none
     bool timed_out = false;
@@ -751,6 +758,26 @@ __global__ __launch_bounds__(64) void k_pintra_rows(IntraRowParams R)
         while (todo) {
             const int mx = base + __ffsll((long long)todo) - 1;
             todo &= todo - 1;
+            bool dec_i4 = false;
+            uint32_t dec_aux = 0u;
+            if constexpr (DECIDE) {
+                // First of all, while nothing else of the macroblock is held: all four 16-lane rows decide it.  Its type is stored by
+                // intra_mb_core, the modes here (the entropy coder reads them), and both are handed on in registers: lanes 0..3
+                // take the four modes of blkIdx 4 lane .. 4 lane + 3, as they would load them
+                const int mbi = my * P.mbw + mx;
+                int dl = lane;
+                asm volatile("" : "+v"(dl));   // (what the decision derives from the lane is computed here, not kept across the walk)
+                const I4Choice c = i4_decide_mb(P, mbi, dl);
+                dec_i4 = c.use_i4;
+                if (dl < 16) P.aux[(size_t)mbi * 16 + xy2blk(dl & 3, dl >> 2)] = (uint8_t)c.mode;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int b = 4 * (dl & 3) + k;
+                    dec_aux |= (uint32_t)__shfl((int)c.mode, 4 * blk_y(b) + blk_x(b)) << (8 * k);
+                }
+                if (lane >= 4) dec_aux = 0u;
+                asm volatile("" : "+v"(dec_aux));   // (nothing of the macroblock's coding is started above this line)
+            }
             if (!DEC) load_src_mb(P, mx, my, S.src, S.srcc, lane);
             // left column + corner sources
             if (mx > 0) {
@@ -806,8 +833,13 @@ __global__ __launch_bounds__(64) void k_pintra_rows(IntraRowParams R)
             wave_sync();
             {
                 const int mbi = my * P.mbw + mx;
-                const bool use_i4 = ((const uint8_t*)(P.mb + mbi))[4] == MB_I4;
-                const uint32_t auxw = lane < 4 ? *(const uint32_t*)(P.aux + (size_t)mbi * 16 + 4 * lane) : 0u;
+                bool use_i4;
+                uint32_t auxw = 0u;
+                if constexpr (DECIDE) { use_i4 = dec_i4; auxw = dec_aux; }
+                else {
+                    use_i4 = ((const uint8_t*)(P.mb + mbi))[4] == MB_I4;
+                    if (lane < 4) auxw = *(const uint32_t*)(P.aux + (size_t)mbi * 16 + 4 * lane);
+                }
                 if (!tab_ready) { i4_lds_init(S.i4, lane); tab_ready = true; wave_sync(); }
                 intra_mb_core<DEC>(P, mx, my, S, lane, __builtin_amdgcn_readfirstlane((int)use_i4) != 0, auxw);
             }

@@ -994,6 +994,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                 m[1] = make_uint4(0u, 0u, 0u, 0u);
                 P.me_cost[mbi] = (uint16_t)(0x8000u | (best_cost < 16383u ? best_cost : 16383u));   // bit 15: for k_pintra_rows
                 *P.anyintra = P.pic_serial;
+                *P.stepintra = P.pic_serial;
             }
             return;
         }

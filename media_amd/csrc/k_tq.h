@@ -252,10 +252,22 @@ __device__ __forceinline__ void tq_chroma8(const FrameParams& P, const int first
         }
 }
 
+// The motion-search lock of the GPU goes back here (engine.h, k_turn_acquire): stream order puts this launch behind the whole of the
+// step's k_me, so its first wave does what a one-thread launch between the two did - one compare-and-swap by one lane, not waited for.
+// k_tq only: in front of k_tq8 the launch of its own stays (measured: DESIGN.md section 11).
+__device__ __forceinline__ void tq_turn_release(const FrameParams& P0)
+{
+    if (P0.turn_lock != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        unsigned expect = P0.turn_id;
+        (void)__hip_atomic_compare_exchange_strong(P0.turn_lock, &expect, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 template <bool IND = false>
 __global__ __launch_bounds__(64) void k_tq(FrameParams P0)
 {
     __builtin_amdgcn_s_setprio(2);   // short and on the way to the loop filter: ahead of another stream's motion search
+    if constexpr (!IND) tq_turn_release(P0);
     const FrameParams P = batch_view<IND>(P0, blockIdx.y);
     const int lane = threadIdx.x;
     const int nmb = P.mbw * P.band.rows, mb0 = P.band.row0 * P.mbw, end = mb0 + nmb;

@@ -92,6 +92,7 @@ struct PicStore {
     unsigned* d_anybs = nullptr;             // [G] picture serial when any boundary strength is non-zero
     unsigned* d_anypcm = nullptr;            // [G] == pic_serial: the picture holds an I_PCM macroblock (not loop-filtered)
     unsigned* d_anyintra = nullptr;          // [G] == pic_serial: P picture with macroblocks for the intra pass
+    unsigned* d_stepintra = nullptr;         // one word == pic_serial: some P picture of the step has macroblocks for the intra pass
     unsigned long long* d_handoff = nullptr; // row-to-row hand-off of the wavefront kernels
     uint32_t* d_bs = nullptr;                // boundary strengths, 32 B per macroblock
     unsigned serial = 0;                     // of the wavefront launches
@@ -124,6 +125,7 @@ hipError_t pic_store_create(PicStore& s, int device, int mbw, int mbh, int items
     HIPTRY(M.dev(&s.d_anybs, Gn * sizeof(unsigned), true, "d_anybs"));
     HIPTRY(M.dev(&s.d_anypcm, Gn * sizeof(unsigned), true, "d_anypcm"));
     HIPTRY(M.dev(&s.d_anyintra, Gn * sizeof(unsigned), true, "d_anyintra"));
+    HIPTRY(M.dev(&s.d_stepintra, sizeof(unsigned), true, "d_stepintra"));
     s.st_handoff = (size_t)s.nmb * 24;
     HIPTRY(M.dev(&s.d_handoff, Gn * s.st_handoff * sizeof(unsigned long long), true, "d_handoff"));
     HIPTRY(M.dev(&s.d_bs, nmb * 32, false, "d_bs"));
@@ -178,7 +180,7 @@ FrameParams store_frame_params(PicStore* s)   // takes the next picture serial
     P.mb = s->d_mb; P.levels = s->d_levels; P.mvq = s->d_mvq; P.aux = s->d_aux;
     P.st_y = s->st_y; P.st_c = s->st_c; P.st_mb = s->nmb;
     P.mbdiv.inv = recip32(s->mbw);
-    P.anypcm = s->d_anypcm; P.anyintra = s->d_anyintra; P.pic_serial = next_nonzero(s->pic_serial);
+    P.anypcm = s->d_anypcm; P.anyintra = s->d_anyintra; P.stepintra = s->d_stepintra; P.pic_serial = next_nonzero(s->pic_serial);
     return P;
 }
 IntraRowParams intra_row_params(PicStore* s, const FrameParams& P, unsigned* h_err, int npic)   // takes the next wavefront serial
