@@ -181,6 +181,28 @@ int mi355x_h264_set_qp(mi355x_h264_encoder *enc, int qp);
  * sharded over several encoder instances / GPUs (instance i of G: next = i, step = G) the
  * concatenated output equals the serial stream byte for byte. */
 int mi355x_h264_set_idr_pic_id(mi355x_h264_encoder *enc, int next, int step);
+/* ---- temporal layers: every second P picture non-reference and droppable ----
+ * Number the pictures of a GOP from the IDR picture at position 0; config.gop counts all pictures, and a forced IDR picture
+ * restarts at position 0.
+ *   Layer 0, the even positions: what pictures are without layers, except that "the previous picture" everywhere means the
+ *     previous LAYER-0 picture - the reference pictures and their count, frame_num, the ring slot, and the per-macroblock
+ *     previous-picture vector of the motion search (seed, rate predictor, "nothing left to code" tests).
+ *   Layer 1, the odd positions: a P picture that is no reference picture.  nal_ref_idc is 0, its slice header has no
+ *     dec_ref_pic_marking(), its frame_num is PrevRefFrameNum + 1 (7.4.3; the next layer-0 picture carries the same).  It refers to
+ *     what a reference picture in its place would refer to, with the same num_ref_idx override and the same search seeds, and is
+ *     reconstructed and filtered like any picture - into the ring slot the next layer-0 picture overwrites.  After it, ring
+ *     position, frame_num, reference count and motion state are what the layer-0 picture before it left.
+ * The picture QP follows one rule for both layers; SPS and PPS do not change by a bit (POC type 2 allows non-reference pictures
+ * that do not follow each other), so two-layer and ordinary streams of one geometry share an engine and a lockstep step.  A stream
+ * with its nal_ref_idc 0 NAL units removed is the stream an encoder with gop = ceil(gop / 2) writes for the layer-0 pictures alone,
+ * byte for byte.  A stream that does not ask for layers is not changed in any way.  frame_type is MI355X_H264_FRAME_P for a
+ * layer-1 picture; the layer is read with the two _last_temporal_id calls (0 or 1, of the last finished picture).
+ * A refused or failed picture of either layer forces an IDR picture next, as ever.
+ * mi355x_h264_set_temporal_layers: 1 or 2, before the encoder's first picture only.  MI355X_H264_E_ARG, before the device is touched:
+ * another count, a band instance (band_count > 1: the halo exchange is the caller's) with 2, a call after the first picture; and
+ * mi355x_h264_debug_code_syntax on a two-layer encoder.  Streams: MI355X_H264_STREAM_TEMPORAL2 in the flags of the open calls. */
+int mi355x_h264_set_temporal_layers(mi355x_h264_encoder *enc, int layers);
+int mi355x_h264_last_temporal_id(const mi355x_h264_encoder *enc);
 /* Scene-change statistic of the last finished picture, one value per batch item: the sum over the
  * macroblocks that went through motion search of min(final SATD-based motion cost, 16383); 0 for IDR
  * pictures.  The plugin class compares it with a threshold and re-codes the picture as IDR
@@ -292,8 +314,11 @@ int mi355x_h264_stream_open(const mi355x_h264_config *cfg, mi355x_h264_stream **
  * honoured (with refs <= 1 the stream is an ordinary one and shares the engine of mi355x_h264_stream_open streams of its geometry).
  * Unknown flag bits, refs > 3, band_count > 1 and batch > 1 return MI355X_H264_E_ARG before the device is touched.  Every other
  * stream call works unchanged on the stream. */
-enum { MI355X_H264_STREAM_MULTIREF = 1 };   /* cfg->refs 2 / 3 is honoured */
+enum { MI355X_H264_STREAM_MULTIREF = 1,     /* cfg->refs 2 / 3 is honoured */
+       MI355X_H264_STREAM_TEMPORAL2 = 8 };  /* two temporal layers (above, "temporal layers"); in _open_ex, _open_scaled and _open_colour.
+                                             * (Bits 1 and 2 stay unknown bits: callers and tests rely on their being refused.) */
 int mi355x_h264_stream_open_ex(const mi355x_h264_config *cfg, uint32_t flags, mi355x_h264_stream **out);
+int mi355x_h264_stream_last_temporal_id(const mi355x_h264_stream *s);   /* temporal layer of the stream's last finished picture */
 void mi355x_h264_stream_close(mi355x_h264_stream *s);
 int mi355x_h264_stream_encode(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *u, int u_stride,
                               const uint8_t *v, int v_stride, uint8_t **out, uint32_t *out_len, int *frame_type);

@@ -44,10 +44,11 @@ EXPORTS = [
     "mi355x_h264_dec_colour", "mi355x_h264_dec_set_rgba_colour", "mi355x_h264_dec_group_colour", "mi355x_h264_dec_group_set_rgba_colour",
     "mi355x_h264_parser_colour",
     "mi355x_h264_dec_set_output_size", "mi355x_h264_dec_output_size", "mi355x_h264_dec_group_set_output_size", "mi355x_h264_dec_group_output_size",
+    "mi355x_h264_set_temporal_layers", "mi355x_h264_last_temporal_id", "mi355x_h264_stream_last_temporal_id",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
-STREAM_MULTIREF = 1   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
+STREAM_MULTIREF, STREAM_TEMPORAL2 = 1, 8   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
 MATRIX_BT709, MATRIX_BT601 = 1, 6   # MI355X_H264_MATRIX_* (matrix_coefficients, Table E-5)
 
 
@@ -217,6 +218,10 @@ def lib():
             L.mi355x_h264_stream_ssim_map.argtypes = [vp, vp, C.c_size_t]
             L.mi355x_h264_stream_ssim_map.restype = C.c_int64
         L.mi355x_h264_stats_enable.argtypes = [vp, C.c_int]
+        if hasattr(L, "mi355x_h264_set_temporal_layers"):
+            L.mi355x_h264_set_temporal_layers.argtypes = [vp, C.c_int]
+            L.mi355x_h264_last_temporal_id.argtypes = [vp]
+            L.mi355x_h264_stream_last_temporal_id.argtypes = [vp]
         if hasattr(L, "mi355x_h264_debug_mem_guard"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no guard mode)
             L.mi355x_h264_debug_mem_guard.argtypes = [C.c_int64, C.c_int]
             L.mi355x_h264_debug_mem_guard_get.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int)]
@@ -320,10 +325,16 @@ class Encoder:
     """thin object wrapper; argument meaning follows mi355x_h264_config"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0,
-                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1, colour=None):
+                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1, colour=None, temporal_layers=1):
         """colour = ("bt601" | "bt709", "limited" | "full"): the encoder is created with mi355x_h264_create_colour - its SPS carries
-        the description and encode_rgba converts with that variant; None: mi355x_h264_create"""
+        the description and encode_rgba converts with that variant; None: mi355x_h264_create.
+        temporal_layers = 2: every second P picture is a non-reference picture (mi355x_h264_set_temporal_layers)"""
         L = lib()
+        self.h = None
+        if temporal_layers not in (1, 2) or (temporal_layers == 2 and band_count > 1):   # (refused before the device is touched)
+            err = EncoderError("temporal_layers: 1 or 2, and 2 not on a band instance")
+            err.rc = E_ARG
+            raise err
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
         cfg.width, cfg.height, cfg.qp, cfg.gop, cfg.fps = width, height, qp, gop, fps
@@ -348,12 +359,27 @@ class Encoder:
         self.width, self.height = width, height
         self.cw, self.ch = L.mi355x_h264_coded_width(self.h), L.mi355x_h264_coded_height(self.h)
         self.nmb = (self.cw // 16) * (self.ch // 16)
+        if temporal_layers != 1:
+            try:
+                self.set_temporal_layers(temporal_layers)
+            except EncoderError:
+                self.close()
+                raise
 
     def _check(self, rc):
         if rc != 0:
             err = EncoderError("rc=%d: %s" % (rc, lib().mi355x_h264_last_error(self.h).decode()))
             err.rc = rc
             raise err
+
+    def set_temporal_layers(self, layers):
+        """1 or 2, before the first picture (mi355x_h264_set_temporal_layers)"""
+        self._check(lib().mi355x_h264_set_temporal_layers(self.h, int(layers)))
+
+    @property
+    def last_temporal_id(self):
+        """temporal layer (0 / 1) of the last finished picture"""
+        return lib().mi355x_h264_last_temporal_id(self.h)
 
     @property
     def colour(self):
@@ -536,10 +562,12 @@ class Stream:
     `flags` is given: the flags of that call).  src_size = (SW, SH): a scaled stream (mi355x_h264_stream_open_scaled) - every encode
     call takes pictures of SW x SH, which the device resamples to width x height; debug_read(DBG_SRC) is the resampled picture.
     colour = ("bt601" | "bt709", "limited" | "full"): a described stream (mi355x_h264_stream_open_colour; combines with src_size
-    and flags): its SPS carries the description, and RGBA pictures are converted with that variant"""
+    and flags): its SPS carries the description, and RGBA pictures are converted with that variant.
+    temporal_layers = 2: MI355X_H264_STREAM_TEMPORAL2 joins the flags - every second P picture is a non-reference picture; any other
+    value but 1 is refused here (the flag has no way to carry it)"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
-                 input_format=0, refs=0, flags=None, src_size=None, colour=None):
+                 input_format=0, refs=0, flags=None, src_size=None, colour=None, temporal_layers=1):
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
@@ -549,6 +577,12 @@ class Stream:
         cfg.refs = refs
         if flags is None and refs > 1:
             flags = STREAM_MULTIREF
+        if temporal_layers not in (1, 2):
+            err = EncoderError("temporal_layers: 1 or 2")
+            err.rc = E_ARG
+            raise err
+        if temporal_layers == 2:
+            flags = (flags or 0) | STREAM_TEMPORAL2
         self.h = C.c_void_p()
         if colour is not None:
             sw, sh = (width, height) if src_size is None else (int(src_size[0]), int(src_size[1]))
@@ -604,6 +638,11 @@ class Stream:
 
     def last_error(self):
         return lib().mi355x_h264_stream_last_error(self.h).decode()
+
+    @property
+    def last_temporal_id(self):
+        """temporal layer (0 / 1) of the stream's last finished picture"""
+        return lib().mi355x_h264_stream_last_temporal_id(self.h)
 
     @property
     def colour(self):

@@ -88,6 +88,9 @@ struct FrameParams {
     int nref;               // reference pictures available to this picture (1 .. config.refs); indirect launches: the position's own
     int rf, rf_last;        // k_me runs once per reference picture: ref_idx_l0 of this launch (ref = its planes), and of the last launch
                             // (indirect launches: of the position's last launch, nref - 1)
+    int me;                 // k_me, temporal layers: ME_PARK / ME_SEED_PARK of the picture (0: every picture of a one-layer stream);
+                            // indirect launches: the position's own, from the itemtab word.  (Here it fills the four bytes in front
+                            // of the pointer below: no other field moves, every other kernel reads its arguments where it did)
     uint32_t* me_total;     // per macroblock: best motion cost + lambda * bits(ref_idx_l0) so far, 0 = settled without a search
     int* pmv;               // per macroblock: the previous picture's vector (rate predictor), parked by the first launch
     MbInfo* mb;
@@ -142,13 +145,20 @@ struct FrameParams {
     const DecPos* dectab;
 };
 
+// Temporal layers, the two wave-uniform facts k_me takes about its picture (host_framing.h, PicSeq::me_facts):
+//   ME_PARK       a layer-1 picture: the previous-picture vector word it read is kept in pmv, because its own vectors replace it in MbInfo
+//   ME_SEED_PARK  a layer-0 P picture of a two-layer stream: the word comes from pmv, where the layer-1 picture in front of it kept
+//                 what the previous LAYER-0 picture left
+enum { ME_PARK = 1, ME_SEED_PARK = 2 };
+
 // itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 10..11 the reference pictures the position's
-// picture has (1..3 in a P step: min(config.refs, pictures since the stream's IDR); 0 in an IDR step), 16..21 QP
-struct ItemRef { int item, cur, nref, qp; };
+// picture has (1..3 in a P step: reference pictures since the stream's IDR, at most config.refs; 0 in an IDR step), 12..13 ME_PARK /
+// ME_SEED_PARK of the position's picture, 16..21 QP
+struct ItemRef { int item, cur, nref, qp, me; };
 __device__ __forceinline__ ItemRef item_ref(const uint32_t* itemtab, int pos)
 {
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)itemtab[pos]);   // uniform: a scalar load
-    return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 10) & 3u), (int)((w >> 16) & 63u)};
+    return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 10) & 3u), (int)((w >> 16) & 63u), (int)((w >> 12) & 3u)};
 }
 // srctab entry of a position: wave-uniform like the itemtab word, a scalar load of its own (it depends on the position alone, so
 // it is issued beside the itemtab word, not behind it)
@@ -199,7 +209,7 @@ __device__ __forceinline__ FrameParams batch_view(FrameParams P, int pos)
         const int rf = P.rf;
 #pragma unroll
         for (int p = 0; p < 3; p++) P.ref[p] = rf == 0 ? P.refs[0][p] : (rf == 1 ? P.refs[1][p] : P.refs[2][p]);
-        P.nref = it.nref; P.rf_last = it.nref - 1;
+        P.nref = it.nref; P.rf_last = it.nref - 1; P.me = it.me;
         const int g = it.item;
         P.src = src;
         P.mb += (size_t)g * P.st_mb;

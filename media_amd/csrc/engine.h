@@ -11,6 +11,7 @@ constexpr int NSLOT = 3;          // access-unit slots in flight
 
 // where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
 struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0;
+                  int layer = 0;        // temporal layer of the picture (the stream hub: of the position, with nal_hdr - hub.h sets both per picture)
                   int quality = 0;      // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
                   int ssim = 0; };      // the SSIM record accompanies it (compared: k_ssim ran behind k_sse)
 
@@ -55,7 +56,8 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     int pair_min_batch = 8;                  // (MI355X_H264_PAIR_FILTER=N sets it, 0 turns the pair form off)
     int16_t* d_mvd = nullptr;
     uint32_t* d_me_total = nullptr;          // [G][nmb] best motion cost so far over the reference pictures (k_me, one launch each)
-    int* d_pmv = nullptr;                    // [G][nmb] the previous picture's vectors, parked for the later launches
+    int* d_pmv = nullptr;                    // [G][nmb] the previous picture's vectors, parked for the later launches - and, temporal layers, by a layer-1 picture for the layer-0 picture behind it
+    int last_layer = 0;                      // temporal layer of the last finished picture (mi355x_h264_last_temporal_id)
     uint16_t* d_slotbits = nullptr;
     unsigned long long* d_slotcode = nullptr;
     uint32_t* d_mbbits = nullptr;
@@ -250,6 +252,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         for (int r = 0; r < mi355x_h264_encoder::MAX_REFS; r++) P.refs[r][p] = e->d_planes[(cur + e->nbuf - 1 - std::min(r, e->nrefs - 1)) % e->nbuf][p];
         P.ref[p] = P.refs[0][p];
     }
+    P.me = ind ? 0 : e->seq.me_facts(idr);   // (temporal layers; indirect launches: the position's own, from the itemtab word)
     P.itemtab = T.d_itemtab; P.srctab = T.d_srctab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
     P.st_src = T.src_item_stride; P.sl = e->sl;
     P.band.row0 = e->b_row0; P.band.rows = e->b_rows;
@@ -262,8 +265,9 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
 
     // (the payload buffers of the items were left zeroed by the k_pack of their previous use)
 
-    // Quality report, hazard "ring slot": this picture's first kernels write ring slot `cur`, which the k_sse of the picture coded
-    // nbuf pictures ago read on the second stream.  In mi355x_h264_encode_gops_device / _batch_device no host wait lies between the
+    // Quality report, hazard "ring slot": this picture's first kernels write ring slot `cur`, which the k_sse of the picture that
+    // wrote it last read on the second stream - nbuf pictures ago, or, behind a layer-1 picture, the picture just before.  The event
+    // is the slot's, so either way the wait below is the one that matters.  In mi355x_h264_encode_gops_device / _batch_device no host wait lies between the
     // two, so the rewrite is ordered behind that comparison by its event.  (Indirect steps: a stream's call returns only after the
     // host has waited for its step's `done`, which lies behind the step's k_sse - the host wait is the order.)
     if (!ind && e->q_done_set[cur]) {
@@ -346,9 +350,10 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         const int fn = ind ? T.items[g].frame_num : e->seq.frame_num, qp = ind ? T.items[g].qp : e->qp;
         const int id = ind ? T.items[g].idr_id : ((e->seq.idr_id + g * e->idr_step) & 0xFF);
         const int nact = ind ? T.items[g].nref : avail_refs(e, idr);
-        H.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, false, fn, qp, nact, &hdr);
+        const bool nonref = (ind ? T.items[g].layer : e->seq.layer()) != 0;
+        H.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, false, fn, qp, nact, &hdr, nonref);
         H.bits[g] = hdr;
-        Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, true, fn, qp, nact, &hdr);
+        Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, true, fn, qp, nact, &hdr, nonref);
         Hpcm.bits[g] = hdr;
     }
     // entropy coding needs only levels / MbInfo, the loop filter the reconstruction and the boundary strengths
@@ -392,7 +397,8 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         // with several slices: the payload of slice s at s * slice_cap, the access unit is put together by finish_item
         const size_t pre = (idr ? e->sps_pps.size() : 0) + 5;
         const size_t pad = (16 - (pre & 15)) & 15;
-        T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr, idr ? ((3 << 5) | 5) : ((2 << 5) | 1)};
+        const int layer = ind ? 0 : e->seq.layer();   // (indirect: hub.h gives every position its own)
+        T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr, slice_nal_hdr(idr, layer), layer};
         LAUNCH2(ind, k_pack<true>, k_pack<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, (uint8_t*)S.d_bitbuf, e->st_bitbuf_bytes, S.h_au + T.lay.payload_off, e->st_au,
                 (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
     }
@@ -539,6 +545,7 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
         e->p_intra_x16 = (3 * e->p_intra_x16 + 16 * (searched - tq_coded)) / 4;
     }
     if (frame_type) *frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
+    e->last_layer = L.layer;
     std::vector<uint8_t>& eb = e->esc_buf[g];
     if (e->nsl > 1) {
         // several slices: one NAL unit each, put together here (the payloads lie slice_cap apart in the pinned buffer)
@@ -953,7 +960,7 @@ enum { HALO_MB_ROWS = 2 };   // 32 luma rows: the search reaches 16 rows + 0.75 
 // rows [r0, r1) of the newest reconstruction <-> a packed block (Y rows, then U rows, then V rows)
 int halo_copy(mi355x_h264_encoder* e, int r0, int r1, void* d_blk, bool to_block)
 {
-    const int last = (e->seq.cur + e->nbuf - 1) % e->nbuf;
+    const int last = e->seq.last_slot(e->nbuf);
     uint8_t* blk = (uint8_t*)d_blk;
     for (int p = 0; p < 3; p++) {
         const size_t pitch = p ? e->cw / 2 : e->cw, rows_per_mb = p ? 8 : 16;

@@ -27,25 +27,41 @@ int set_err(char (&err)[N], int code, const char* fmt, ...)
 
 // Where a stream stands in its picture sequence: the engine keeps one (its batch items move in lockstep), the stream hub
 // one per stream.
+// Temporal layers (include/mi355x_h264.h, "temporal layers"): with layers = 2 the pictures at odd positions of a GOP are layer 1 -
+// P pictures nobody refers to.  frame_in_gop is the POSITION in the GOP (every picture counts: next_is_idr, layer); refs_in_gop
+// counts the reference pictures since the IDR picture (avail_refs).  After a layer-1 picture cur, frame_num and refs_in_gop are what
+// the layer-0 picture before it left: it is reconstructed into the ring slot the next layer-0 picture overwrites and carries that
+// picture's frame_num (PrevRefFrameNum + 1, 7.4.3).  layers = 1: the two counts move together and every picture is layer 0.
 struct PicSeq {
     int cur = 0;                 // ring slot the next picture is reconstructed into
     int frame_in_gop = 0, frame_num = 0, idr_id = 0, force_idr = 0;
     long frames = 0;
+    int layers = 1, refs_in_gop = 0;
+    int last_cur = -1;           // ring slot of the last picture that went out (-1: none yet)
     bool next_is_idr(int gop) const { return force_idr || frames == 0 || frame_in_gop >= gop; }
-    void begin(bool idr) { if (idr) { frame_in_gop = 0; frame_num = 0; force_idr = 0; } }
+    void begin(bool idr) { if (idr) { frame_in_gop = 0; refs_in_gop = 0; frame_num = 0; force_idr = 0; } }
+    // of the picture begun: its layer, and the two facts k_me takes (dev_common.h ME_PARK, ME_SEED_PARK)
+    int layer() const { return layers == 2 ? (frame_in_gop & 1) : 0; }
+    int me_facts(bool idr) const { return layers != 2 || idr ? 0 : layer() ? 1 : 2; }
     // reference pictures the picture begun has, of a stream that searches nrefs: those coded since the stream's last IDR picture
     // (0, 1, 2, .. up to nrefs).  The one rule of the engine and the stream hub: a forced IDR restarts it with begin()
-    int avail_refs(bool idr, int nrefs) const { return idr ? 0 : std::min(nrefs, frame_in_gop); }
+    int avail_refs(bool idr, int nrefs) const { return idr ? 0 : std::min(nrefs, refs_in_gop); }
+    // the slot of the last picture that went out (before the first: the slot behind cur, as ever)
+    int last_slot(int nbuf) const { return last_cur >= 0 ? last_cur : (cur + nbuf - 1) % nbuf; }
     // the picture went out: idr_step = what an IDR picture adds to idr_pic_id (the engine: its stride times the batch)
     void advance(bool idr, int nbuf, int idr_step)
     {
-        cur = (cur + 1) % nbuf; frame_num = (frame_num + 1) & 255; frame_in_gop++; frames++;
+        last_cur = cur;
+        if (!layer()) { cur = (cur + 1) % nbuf; frame_num = (frame_num + 1) & 255; refs_in_gop++; }
+        frame_in_gop++; frames++;
         if (idr) idr_id = (idr_id + idr_step) & 0xFF;
     }
 };
 // one picture of an indirect step (engine.h, Step): the batch item it belongs to and that stream's state for the picture
-// (nref: PicSeq::avail_refs)
-struct ItemPic { int item, cur, qp, frame_num, idr_id, nref; };
+// (nref: PicSeq::avail_refs; layer, me: PicSeq::layer, me_facts)
+struct ItemPic { int item, cur, qp, frame_num, idr_id, nref, layer, me; };
+// first byte of a slice NAL unit: nal_ref_idc 3 for an IDR picture, 2 for a P picture others refer to, 0 for a layer-1 picture
+inline int slice_nal_hdr(bool idr, int layer) { return idr ? ((3 << 5) | 5) : layer ? 1 : ((2 << 5) | 1); }
 
 // ---- host tables (ITU-T H.264 Table 8-15, A-1; quantiser of the reference model) ----
 const uint8_t h_chroma_qp[52] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,
@@ -251,7 +267,8 @@ std::vector<uint8_t> build_parameter_sets(const StreamShape& f)
 // slice_header() of 7.3.3 for this build's fixed choices, from slice_type on (first_mb_in_slice differs per slice and
 // is written by k_bit_scan); returns bit count (< 64).
 // frame_num, qp, nact (num_ref_idx_l0_active of a P slice): the picture's own - one per batch item in the stream hub's steps
-int build_slice_header(const StreamShape& f, bool idr, int idr_id, bool no_filter, int frame_num, int qp, int nact, uint64_t* bits)
+// nonref: a layer-1 picture (nal_ref_idc 0) - its header has no dec_ref_pic_marking()
+int build_slice_header(const StreamShape& f, bool idr, int idr_id, bool no_filter, int frame_num, int qp, int nact, uint64_t* bits, bool nonref = false)
 {
     HostBits h;
     h.ue(idr ? 7 : 5);
@@ -262,7 +279,7 @@ int build_slice_header(const StreamShape& f, bool idr, int idr_id, bool no_filte
         if (nact != f.nrefs) { h.put(1, 1); h.ue((uint32_t)nact - 1); } else h.put(1, 0);
         h.put(1, 0);   // ref_pic_list_modification_flag_l0
     }
-    if (idr) { h.put(1, 0); h.put(1, 0); } else h.put(1, 0);
+    if (idr) { h.put(1, 0); h.put(1, 0); } else if (!nonref) h.put(1, 0);   // dec_ref_pic_marking(): nal_ref_idc != 0 only
     h.se(qp - 26);
     no_filter = no_filter || f.disable_deblock;            // (a picture with an I_PCM macroblock is not filtered)
     h.ue(no_filter ? 1 : f.nsl > 1 ? 2 : 0);   // several slices: no filtering across slice edges, the bands stay independent

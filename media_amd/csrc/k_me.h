@@ -205,8 +205,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     // the vector this macroblock had in the previous picture (0 after an IDR): stand-in for the motion vector predictor
     // in the rate term of the search; final before the launch, so every macroblock stays independent
     // (with several reference pictures the first launch parks it in P.pmv: MbInfo is rewritten by then)
-    const int pmw = __builtin_amdgcn_readfirstlane(P.rf == 0 ? *(const int*)(P.mb + mbi) : P.pmv[mbi]);
-    if (P.rf == 0 && P.rf_last > 0 && lane == 0) P.pmv[mbi] = pmw;
+    // Temporal layers: "the previous picture" is the previous LAYER-0 picture.  A layer-1 picture (ME_PARK) reads that picture's word
+    // from MbInfo like any other and parks it; the layer-0 picture behind it (ME_SEED_PARK) takes the parked word, because MbInfo holds
+    // the layer-1 picture's vectors by then.  The same value in the same array as the multi-reference park, so the two uses agree
+    const int pmw = __builtin_amdgcn_readfirstlane(P.rf == 0 && !(P.me & ME_SEED_PARK) ? *(const int*)(P.mb + mbi) : P.pmv[mbi]);
+    if (P.rf == 0 && (P.rf_last > 0 || (P.me & ME_PARK)) && lane == 0) P.pmv[mbi] = pmw;
     const int pmx = (int)(int16_t)(pmw & 0xFFFF), pmy = pmw >> 16;
     load_src_mb(P, mx, my, s_src, s_srcc, lane);
     // Several reference pictures (config.refs, BASELINE.json configs[4]: 3): ONE LAUNCH PER REFERENCE PICTURE, P.ref = the

@@ -212,6 +212,18 @@ int mi355x_h264_last_me_cost(const mi355x_h264_encoder* e, uint32_t* cost)
 
 int mi355x_h264_set_qp(mi355x_h264_encoder* e, int qp) { if (!e || qp < 10 || qp > 51) return MI355X_H264_E_ARG; e->qp = qp; return MI355X_H264_OK; }
 
+// ---- temporal layers (host_framing.h, PicSeq; k_me.h) ----
+int mi355x_h264_set_temporal_layers(mi355x_h264_encoder* e, int layers)
+{
+    NEED(e, layers == 1 || layers == 2, "temporal layers: 1 or 2");
+    NEED(e, layers == 1 || e->cfg.band_count <= 1, "temporal layers: not on a band instance (the halo exchange is the caller's)");
+    NEED(e, e->seq.frames == 0, "temporal layers: before the first picture only");
+    e->seq.layers = layers;
+    return MI355X_H264_OK;
+}
+int mi355x_h264_last_temporal_id(const mi355x_h264_encoder* e) { return e ? e->last_layer : MI355X_H264_E_ARG; }
+int mi355x_h264_stream_last_temporal_id(const mi355x_h264_stream* s) { return s ? s->hub->sched.last_layer(s->item) : MI355X_H264_E_ARG; }
+
 int mi355x_h264_set_idr_pic_id(mi355x_h264_encoder* e, int next, int step)
 {
     if (!e) return MI355X_H264_E_ARG;
@@ -264,7 +276,7 @@ int64_t mi355x_h264_debug_read(mi355x_h264_encoder* e, int what, void* dst, size
     const void* src = nullptr;
     size_t n = 0;
     const size_t ysz = (size_t)e->cw * e->ch;
-    const int last = (e->seq.cur + e->nbuf - 1) % e->nbuf;  // picture finished by the last encode
+    const int last = e->seq.last_slot(e->nbuf);  // picture finished by the last encode (a layer-1 picture leaves seq.cur where it was)
     switch (what) {
         case MI355X_H264_DBG_RECON_Y: case MI355X_H264_DBG_RECON_U: case MI355X_H264_DBG_RECON_V:
             src = e->d_planes[last][what]; n = what ? ysz / 4 : ysz; break;
@@ -291,6 +303,7 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, co
 {
     NEED(e, mbinfo && levels && mvq && mbaux && src_i420 && out && out_len, "null argument");
     NEED(e, e->cfg.band_count <= 1, "not for slice bands over several instances");
+    NEED(e, e->seq.layers == 1, "not for an encoder with two temporal layers");
     HIPCHK(e->err, hipSetDevice(e->device));
     const size_t src_bytes = e->frame_bytes * (size_t)e->G;
     if (!e->d_inject_src) HIPCHK(e->err, DM_DEV(e->mem, e->d_inject_src, src_bytes + 256, false));
@@ -401,7 +414,7 @@ int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags
         if (cfg->width < 16 || cfg->height < 16 || ((cfg->width | cfg->height) & 1)) return MI355X_H264_E_ARG;
         if (sw < cfg->width || sh < cfg->height || sw > 4 * cfg->width || sh > 4 * cfg->height) return MI355X_H264_E_ARG;
     }
-    if (flags & ~(uint32_t)MI355X_H264_STREAM_MULTIREF) return MI355X_H264_E_ARG;
+    if (flags & ~(uint32_t)(MI355X_H264_STREAM_MULTIREF | MI355X_H264_STREAM_TEMPORAL2)) return MI355X_H264_E_ARG;
     const int max_refs = (flags & MI355X_H264_STREAM_MULTIREF) ? (int)mi355x_h264_encoder::MAX_REFS : 1;
     if (cfg->refs > max_refs || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
     if (cfg->input_format != MI355X_H264_INPUT_I420 && cfg->input_format != MI355X_H264_INPUT_NV12 && cfg->input_format != MI355X_H264_INPUT_RGBA)
@@ -418,7 +431,7 @@ int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags
         if (rc != MI355X_H264_OK) { delete s; return rc; }
         g_hubs.push_back(h);
     }
-    const int idx = h->sched.open(cfg->qp, cfg->gop);   // (there is room: opens and closes are serialised by g_hubs_mu)
+    const int idx = h->sched.open(cfg->qp, cfg->gop, (flags & MI355X_H264_STREAM_TEMPORAL2) ? 2 : 1);   // (there is room: opens and closes are serialised by g_hubs_mu)
     HubItem& it = h->items[idx];
     hipEvent_t ev = it.copied;
     it = HubItem();

@@ -107,12 +107,24 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     if (haveColour < 0) {
         WARN("colour [%s] / range [%s] rejected: the stream carries no colour description", colourKey.c_str(), rangeKey.c_str());
     }
+    // extension: "2" = two temporal layers, the odd pictures of a GOP non-reference and droppable.  Both paths
+    const std::string layersKey = GetStrEncParam("persist.vmi.video.encode.temporallayers");
+    bool layersJunk = false;
+    m_temporalLayers = ParseTemporalLayers(layersKey, &layersJunk);
+    m_lastTemporalId = -1;
+    if (layersJunk) {
+        WARN("temporal layers [%s] rejected: one layer", layersKey.c_str());
+    }
     if (shared) {
         cfg.input_format = m_input;
-        const int rc = haveColour > 0 ? mi355x_h264_stream_open_colour(&cfg, MI355X_H264_STREAM_MULTIREF, haveSrc > 0 ? m_srcWidth : cfg.width,
+        uint32_t flags = MI355X_H264_STREAM_MULTIREF;
+        if (m_temporalLayers == 2) {
+            flags |= MI355X_H264_STREAM_TEMPORAL2;
+        }
+        const int rc = haveColour > 0 ? mi355x_h264_stream_open_colour(&cfg, flags, haveSrc > 0 ? m_srcWidth : cfg.width,
                                                                        haveSrc > 0 ? m_srcHeight : cfg.height, &colour, &m_stream)
-                       : haveSrc > 0 ? mi355x_h264_stream_open_scaled(&cfg, MI355X_H264_STREAM_MULTIREF, m_srcWidth, m_srcHeight, &m_stream)
-                                     : mi355x_h264_stream_open_ex(&cfg, MI355X_H264_STREAM_MULTIREF, &m_stream);
+                       : haveSrc > 0 ? mi355x_h264_stream_open_scaled(&cfg, flags, m_srcWidth, m_srcHeight, &m_stream)
+                                     : mi355x_h264_stream_open_ex(&cfg, flags, &m_stream);
         if (rc != MI355X_H264_OK) {
             ERR("mi355x_h264_stream_open_%s returned %d", haveColour > 0 ? "colour" : haveSrc > 0 ? "scaled" : "ex", rc);
             m_stream = nullptr;
@@ -136,6 +148,12 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     }
     if ((m_psnr || m_ssim) && mi355x_h264_quality_enable_ex(m_engine, metrics) != MI355X_H264_OK) {
         ERR("quality report: %s", mi355x_h264_last_error(m_engine));
+        mi355x_h264_destroy(m_engine);
+        m_engine = nullptr;
+        return false;
+    }
+    if (m_temporalLayers == 2 && mi355x_h264_set_temporal_layers(m_engine, 2) != MI355X_H264_OK) {
+        ERR("temporal layers: %s", mi355x_h264_last_error(m_engine));
         mi355x_h264_destroy(m_engine);
         m_engine = nullptr;
         return false;
@@ -306,6 +324,14 @@ int32_t VideoEncoderMI355X::ParseRefs(const std::string &value) { return value =
 
 bool VideoEncoderMI355X::ParsePsnr(const std::string &value) { return value == "1"; }
 
+int32_t VideoEncoderMI355X::ParseTemporalLayers(const std::string &value, bool *junk)
+{
+    if (junk != nullptr) {
+        *junk = !(value.empty() || value == "1" || value == "2");
+    }
+    return value == "2" ? 2 : 1;
+}
+
 bool VideoEncoderMI355X::ParseSsim(const std::string &value) { return value == "1"; }
 
 int VideoEncoderMI355X::ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out)
@@ -413,6 +439,7 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
             m_stream != nullptr ? mi355x_h264_stream_last_error(m_stream) : mi355x_h264_last_error(m_engine));
         return false;
     }
+    m_lastTemporalId = m_stream != nullptr ? mi355x_h264_stream_last_temporal_id(m_stream) : mi355x_h264_last_temporal_id(m_engine);
     if (m_psnr || m_ssim) {
         QualityAfterPicture(frameType == MI355X_H264_FRAME_IDR);
     }

@@ -59,6 +59,13 @@ public:
     static int ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out);
     // the description the engine was opened with (false: none)
     bool Colour(mi355x_h264_colour *out) const;
+    // extension key persist.vmi.video.encode.temporallayers: "2" -> two temporal layers, every second P picture a non-reference
+    // picture a forwarder may drop (include/mi355x_h264.h, "temporal layers"), on both paths; unset or "1" -> 1, the reference
+    // preset's iTemporalLayerNum; anything else -> 1 with *junk set (the reference's behaviour, with one WARN line).  The rate
+    // controller sees every picture as it does with one layer
+    static int32_t ParseTemporalLayers(const std::string &value, bool *junk);
+    // temporal layer (0 / 1) of the last picture that went out; -1 before the first
+    int32_t LastTemporalId() const { return m_lastTemporalId; }
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -91,6 +98,7 @@ private:
     int32_t m_input = MI355X_H264_INPUT_I420;   // layout of the pictures EncodeOneFrame is handed (persist.vmi.video.encode.input)
     int32_t m_srcWidth = 0, m_srcHeight = 0;    // > 0: the pictures' size (.srcwidth / .srcheight), resampled to the coded size on the device
     bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
+    int32_t m_temporalLayers = 1, m_lastTemporalId = -1;   // .temporallayers; the layer of the last picture that went out
     // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
     bool m_psnr = false, m_haveQuality = false;
     mi355x_h264_quality m_lastQuality{};

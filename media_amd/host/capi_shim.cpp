@@ -34,6 +34,19 @@ int32_t vc_parse_source_size(const char *width, const char *height, uint32_t cod
     return VideoEncoderMI355X::ParseSourceSize(width != nullptr ? width : "", height != nullptr ? height : "", codedWidth, codedHeight, srcWidth, srcHeight);
 }
 // persist.vmi.video.encode.refs: 2 or 3 are taken, anything else is one reference picture
+// persist.vmi.video.encode.temporallayers: 1 or 2; *junk = the value is none the key takes (one WARN line, one layer)
+int32_t vc_parse_temporal_layers(const char *value, int32_t *junk)
+{
+    bool j = false;
+    const int32_t n = VideoEncoderMI355X::ParseTemporalLayers(value != nullptr ? value : "", &j);
+    if (junk != nullptr) *junk = j ? 1 : 0;
+    return n;
+}
+int32_t vc_last_temporal_id(void *enc)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    return m != nullptr ? m->LastTemporalId() : -1;
+}
 int32_t vc_parse_refs(const char *value) { return VideoEncoderMI355X::ParseRefs(value != nullptr ? value : ""); }
 // persist.vmi.video.encode.psnr: "1" turns the quality report on, anything else leaves it off
 int32_t vc_parse_psnr(const char *value) { return VideoEncoderMI355X::ParsePsnr(value != nullptr ? value : "") ? 1 : 0; }

@@ -35,6 +35,8 @@ def lib():
         L.vc_parse_input_layout.argtypes = [C.c_char_p]
         L.vc_parse_input_device.argtypes = [C.c_char_p]
         L.vc_parse_refs.argtypes = [C.c_char_p]
+        L.vc_parse_temporal_layers.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
+        L.vc_last_temporal_id.argtypes = [vp]
         L.vc_parse_psnr.argtypes = [C.c_char_p]
         L.vc_parse_ssim.argtypes = [C.c_char_p]
         L.vc_last_ssim.argtypes = [vp, vp]
@@ -86,6 +88,14 @@ def parse_input_device(value):
 def parse_refs(value):
     """what persist.vmi.video.encode.refs = value selects: 2 or 3 reference pictures, else 1"""
     return lib().vc_parse_refs(str(value).encode())
+
+
+def parse_temporal_layers(value):
+    """what persist.vmi.video.encode.temporallayers = value selects: (layers, is the value junk?) - 2 for "2", 1 for "1" and for
+    the unset key, 1 with the junk mark (one WARN line) for anything else"""
+    junk = C.c_int32()
+    n = lib().vc_parse_temporal_layers(str(value).encode(), C.byref(junk))
+    return n, bool(junk.value)
 
 
 def parse_ssim(value):
@@ -151,7 +161,8 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
-                   inputmem=None, refs=None, psnr=None, ssim=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None):
+                   inputmem=None, refs=None, psnr=None, ssim=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None,
+                   temporallayers=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -175,6 +186,7 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.srcheight", "" if srcheight is None else srcheight)   # size, resampled to width x height
     prop_set("persist.vmi.video.encode.colour", "" if colour is None else colour)         # bt601 | bt709 } either one set and valid: a
     prop_set("persist.vmi.video.encode.range", "" if range is None else range)            # limited | full } described stream
+    prop_set("persist.vmi.video.encode.temporallayers", "" if temporallayers is None else temporallayers)   # 2: two temporal layers
     if shared is not None:
         prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 
@@ -234,6 +246,10 @@ class VideoEncoder:
         if lib().vc_last_ssim(self.h, C.byref(s)) != 0:
             return None
         return capi._with_ssim({"valid": bool(s.valid)}, s)
+
+    def last_temporal_id(self):
+        """temporal layer (0 / 1) of the last picture that went out (persist.vmi.video.encode.temporallayers = 2); -1 before the first"""
+        return lib().vc_last_temporal_id(self.h)
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)

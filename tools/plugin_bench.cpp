@@ -5,10 +5,13 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
+// --temporal N (anywhere on the line): the extension key persist.vmi.video.encode.temporallayers = N - with 2 every second P picture
+// of a GOP is a non-reference picture (include/mi355x_h264.h, "temporal layers"); every picture's layer is read after its call
+// (outside the latency sample), and the JSON line carries pictures_l0 / pictures_l1 and bytes_l0 / bytes_l1.
 // --ssim (anywhere on the line): the extension key persist.vmi.video.encode.ssim = 1 - the report is on with both metrics, every
 // picture's SSIM record is read after its call (outside the latency sample), and the JSON line carries ssim_y / ssim_u / ssim_v:
 // sum / (65536 windows) over all pictures of the run, per plane.
@@ -41,12 +44,22 @@
 
 extern "C" int32_t vc_last_quality(void *enc, mi355x_h264_quality *out);   // media_amd/host/capi_shim.cpp
 extern "C" int32_t vc_last_ssim(void *enc, mi355x_h264_ssim *out);
+extern "C" int32_t vc_last_temporal_id(void *enc);
 
 int main(int argc, char **argv)
 {
     for (int i = 1; i + 1 < argc; i++)   // --refs N: taken out of the line, the rest is positional
         if (strcmp(argv[i], "--refs") == 0) {
             setenv("PERSIST_VMI_VIDEO_ENCODE_REFS", argv[i + 1], 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    bool temporal = false;
+    for (int i = 1; i + 1 < argc; i++)   // --temporal N: taken out of the line
+        if (strcmp(argv[i], "--temporal") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_TEMPORALLAYERS", argv[i + 1], 1);
+            temporal = true;
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2;
             break;
@@ -87,7 +100,7 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     // (w, h: the size of the pictures in the file and in every call - the source size with --src)
     const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
@@ -158,6 +171,7 @@ int main(int argc, char **argv)
         std::atomic<int> failures{0};
         std::vector<uint64_t> sse((size_t)S * 3, 0), samples((size_t)S * 3, 0), windows((size_t)S * 3, 0);
         std::vector<int64_t> qsum((size_t)S * 3, 0);
+        std::vector<uint64_t> lpics((size_t)S * 2, 0), lbytes((size_t)S * 2, 0);   // per temporal layer
         auto work = [&](int k) {
             lat[k].reserve(frames);
             for (int i = 0; i < frames; i++) {
@@ -169,6 +183,10 @@ int main(int argc, char **argv)
                 lat[k].push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
                 if (rc != VIDEO_ENCODER_SUCCESS) failures++;
                 else bytes[k] += n;
+                if (temporal && rc == VIDEO_ENCODER_SUCCESS) {
+                    const int tid = vc_last_temporal_id(encs[k]) == 1 ? 1 : 0;
+                    lpics[(size_t)k * 2 + tid]++; lbytes[(size_t)k * 2 + tid] += n;
+                }
                 mi355x_h264_quality q;
                 if (psnr && rc == VIDEO_ENCODER_SUCCESS && vc_last_quality(encs[k], &q) == 0 && q.valid)
                     for (int p = 0; p < 3; p++) { sse[(size_t)k * 3 + p] += q.sse[p]; samples[(size_t)k * 3 + p] += q.samples[p]; }
@@ -188,7 +206,14 @@ int main(int argc, char **argv)
         for (int k = 0; k < S; k++) { all.insert(all.end(), lat[k].begin(), lat[k].end()); total += bytes[k]; }
         std::sort(all.begin(), all.end());
         const size_t n = all.size();
-        char q[320] = "";
+        char q[480] = "";
+        if (temporal) {
+            uint64_t np[2] = {0, 0}, nb[2] = {0, 0};
+            for (int k = 0; k < S; k++)
+                for (int l = 0; l < 2; l++) { np[l] += lpics[(size_t)k * 2 + l]; nb[l] += lbytes[(size_t)k * 2 + l]; }
+            snprintf(q, sizeof(q), ",\"pictures_l0\":%llu,\"pictures_l1\":%llu,\"bytes_l0\":%llu,\"bytes_l1\":%llu", (unsigned long long)np[0],
+                     (unsigned long long)np[1], (unsigned long long)nb[0], (unsigned long long)nb[1]);
+        }
         if (psnr) {
             double db[3];
             for (int p = 0; p < 3; p++) {
@@ -196,7 +221,8 @@ int main(int argc, char **argv)
                 for (int k = 0; k < S; k++) { e += sse[(size_t)k * 3 + p]; m += samples[(size_t)k * 3 + p]; }
                 db[p] = m == 0 ? 0.0 : (e == 0 ? 999.0 : 10.0 * std::log10(65025.0 * (double)m / (double)e));   // (999: no error at all)
             }
-            snprintf(q, sizeof(q), ",\"psnr_y\":%.3f,\"psnr_u\":%.3f,\"psnr_v\":%.3f", db[0], db[1], db[2]);
+            const size_t at = strlen(q);
+            snprintf(q + at, sizeof(q) - at, ",\"psnr_y\":%.3f,\"psnr_u\":%.3f,\"psnr_v\":%.3f", db[0], db[1], db[2]);
         }
         if (ssim) {
             double mean[3];
