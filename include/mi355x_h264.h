@@ -203,6 +203,32 @@ int mi355x_h264_set_idr_pic_id(mi355x_h264_encoder *enc, int next, int step);
  * mi355x_h264_debug_code_syntax on a two-layer encoder.  Streams: MI355X_H264_STREAM_TEMPORAL2 in the flags of the open calls. */
 int mi355x_h264_set_temporal_layers(mi355x_h264_encoder *enc, int layers);
 int mi355x_h264_last_temporal_id(const mi355x_h264_encoder *enc);
+/* ---- intra refresh: a moving all-intra slice band, recovery without an IDR picture ----
+ * An encoder or stream with config.slices = n (2 .. 32, and the picture really has n bands: every band two macroblock rows or more)
+ * and intra refresh on codes IDR pictures as ever.  Let p = 1, 2, ... count the P pictures since the last IDR picture and
+ * k = (p - 1) mod n.  In that P picture
+ *   band k is ALL INTRA: every macroblock of it goes to the intra pass without a motion search.  It stays a P slice (mb_type 5..,
+ *     every mb_skip_run 0);
+ *   bands j < k are CLEAN: the prediction of their macroblocks reads no sample below luma row L = 16 * row_end(k - 1) - 1 of the
+ *     reference picture, luma and chroma, under the reads of 8.4.2.2.1 / 8.4.2.2.2.  For a partition at luma row y0 of height hp
+ *     with vertical vector vy (quarter samples) the last luma row read is y0 + floor(vy / 4) + hp - 1, plus 3 when vy % 4 != 0, and
+ *     is <= L; the last chroma row read is y0 / 2 + floor(vy / 8) + hp / 2 - 1, plus 1 when vy % 8 != 0, and is <= (L + 1) / 2 - 1;
+ *   bands j > k are unrestricted.
+ * Slices neither predict, filter nor code across their edges, so a decoder that starts at an access unit with k = 0 (or lost
+ * pictures before it) has every sample right from the picture with k = n - 1 on, band j from the picture with k = j on.  The access
+ * unit with k = 0 starts with a recovery point SEI (NAL type 6, nal_ref_idc 0, payload type 6): recovery_frame_cnt = n - 1,
+ * exact_match_flag 1, broken_link_flag 0, changing_slice_group_idc 0.  IDR pictures come as before - by config.gop, on force_idr,
+ * on a scene change, after a failed picture - and each restarts p.  A forced macroblock adds 0 to the scene-change statistic.
+ * With refresh off nothing differs from an encoder without it.
+ * mi355x_h264_set_intra_refresh: on = 0 / 1, before the encoder's first picture only.  MI355X_H264_E_ARG, before the device is
+ * touched: slices outside 2 .. 32 or a picture that does not divide into that many bands, refs > 1, two temporal layers (either
+ * order of the two calls), a band instance (band_count > 1), a call after the first picture; and mi355x_h264_debug_code_syntax on
+ * such an encoder.  Streams: MI355X_H264_STREAM_INTRA_REFRESH in the flags of the open calls, refused on the same grounds.
+ * The two _last_refresh_band calls give k of the last finished picture, -1 for an IDR picture or with refresh off.
+ * Not built: the decoder peer joining at a recovery point (it waits for an IDR picture), refresh with several reference pictures
+ * or temporal layers, column refresh, rate control aware of the intra band. */
+int mi355x_h264_set_intra_refresh(mi355x_h264_encoder *enc, int on);
+int mi355x_h264_last_refresh_band(const mi355x_h264_encoder *enc);
 /* Scene-change statistic of the last finished picture, one value per batch item: the sum over the
  * macroblocks that went through motion search of min(final SATD-based motion cost, 16383); 0 for IDR
  * pictures.  The plugin class compares it with a threshold and re-codes the picture as IDR
@@ -315,8 +341,11 @@ int mi355x_h264_stream_open(const mi355x_h264_config *cfg, mi355x_h264_stream **
  * Unknown flag bits, refs > 3, band_count > 1 and batch > 1 return MI355X_H264_E_ARG before the device is touched.  Every other
  * stream call works unchanged on the stream. */
 enum { MI355X_H264_STREAM_MULTIREF = 1,     /* cfg->refs 2 / 3 is honoured */
-       MI355X_H264_STREAM_TEMPORAL2 = 8 };  /* two temporal layers (above, "temporal layers"); in _open_ex, _open_scaled and _open_colour.
+       MI355X_H264_STREAM_TEMPORAL2 = 8,    /* two temporal layers (above, "temporal layers"); in _open_ex, _open_scaled and _open_colour.
                                              * (Bits 1 and 2 stay unknown bits: callers and tests rely on their being refused.) */
+       MI355X_H264_STREAM_INTRA_REFRESH = 32 };   /* intra refresh over the cfg->slices bands (above, "intra refresh"); in the same three
+                                                   * calls.  (Bit 4 stays an unknown bit too.) */
+int mi355x_h264_stream_last_refresh_band(const mi355x_h264_stream *s);   /* all-intra band of the stream's last finished picture, -1: none */
 int mi355x_h264_stream_open_ex(const mi355x_h264_config *cfg, uint32_t flags, mi355x_h264_stream **out);
 int mi355x_h264_stream_last_temporal_id(const mi355x_h264_stream *s);   /* temporal layer of the stream's last finished picture */
 void mi355x_h264_stream_close(mi355x_h264_stream *s);

@@ -45,10 +45,11 @@ EXPORTS = [
     "mi355x_h264_parser_colour",
     "mi355x_h264_dec_set_output_size", "mi355x_h264_dec_output_size", "mi355x_h264_dec_group_set_output_size", "mi355x_h264_dec_group_output_size",
     "mi355x_h264_set_temporal_layers", "mi355x_h264_last_temporal_id", "mi355x_h264_stream_last_temporal_id",
+    "mi355x_h264_set_intra_refresh", "mi355x_h264_last_refresh_band", "mi355x_h264_stream_last_refresh_band",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
-STREAM_MULTIREF, STREAM_TEMPORAL2 = 1, 8   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
+STREAM_MULTIREF, STREAM_TEMPORAL2, STREAM_INTRA_REFRESH = 1, 8, 32   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
 MATRIX_BT709, MATRIX_BT601 = 1, 6   # MI355X_H264_MATRIX_* (matrix_coefficients, Table E-5)
 
 
@@ -222,6 +223,10 @@ def lib():
             L.mi355x_h264_set_temporal_layers.argtypes = [vp, C.c_int]
             L.mi355x_h264_last_temporal_id.argtypes = [vp]
             L.mi355x_h264_stream_last_temporal_id.argtypes = [vp]
+        if hasattr(L, "mi355x_h264_set_intra_refresh"):
+            L.mi355x_h264_set_intra_refresh.argtypes = [vp, C.c_int]
+            L.mi355x_h264_last_refresh_band.argtypes = [vp]
+            L.mi355x_h264_stream_last_refresh_band.argtypes = [vp]
         if hasattr(L, "mi355x_h264_debug_mem_guard"):   # (an A/B library of an earlier build, MI355X_H264_LIB, has no guard mode)
             L.mi355x_h264_debug_mem_guard.argtypes = [C.c_int64, C.c_int]
             L.mi355x_h264_debug_mem_guard_get.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int)]
@@ -325,12 +330,18 @@ class Encoder:
     """thin object wrapper; argument meaning follows mi355x_h264_config"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0,
-                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1, colour=None, temporal_layers=1):
+                 bitrate=5000000, rc_mode=0, batch=1, input_format=0, slices=0, band_index=0, band_count=0, refs=0, search=1, colour=None, temporal_layers=1,
+                 intra_refresh=False):
         """colour = ("bt601" | "bt709", "limited" | "full"): the encoder is created with mi355x_h264_create_colour - its SPS carries
         the description and encode_rgba converts with that variant; None: mi355x_h264_create.
-        temporal_layers = 2: every second P picture is a non-reference picture (mi355x_h264_set_temporal_layers)"""
+        temporal_layers = 2: every second P picture is a non-reference picture (mi355x_h264_set_temporal_layers).
+        intra_refresh: the `slices` bands are coded all intra in turn, one per P picture (mi355x_h264_set_intra_refresh)"""
         L = lib()
         self.h = None
+        if intra_refresh and (not 2 <= slices <= 32 or refs > 1 or temporal_layers != 1 or band_count > 1):   # (before the device is touched)
+            err = EncoderError("intra_refresh: slices 2 .. 32, one reference picture, one temporal layer, no band instance")
+            err.rc = E_ARG
+            raise err
         if temporal_layers not in (1, 2) or (temporal_layers == 2 and band_count > 1):   # (refused before the device is touched)
             err = EncoderError("temporal_layers: 1 or 2, and 2 not on a band instance")
             err.rc = E_ARG
@@ -365,6 +376,21 @@ class Encoder:
             except EncoderError:
                 self.close()
                 raise
+        if intra_refresh:
+            try:
+                self.set_intra_refresh(True)
+            except EncoderError:
+                self.close()
+                raise
+
+    def set_intra_refresh(self, on):
+        """before the first picture, on an encoder with slices = 2 .. 32 (mi355x_h264_set_intra_refresh)"""
+        self._check(lib().mi355x_h264_set_intra_refresh(self.h, 1 if on else 0))
+
+    @property
+    def last_refresh_band(self):
+        """the all-intra band k of the last finished picture; -1 for an IDR picture or with refresh off"""
+        return lib().mi355x_h264_last_refresh_band(self.h)
 
     def _check(self, rc):
         if rc != 0:
@@ -567,7 +593,9 @@ class Stream:
     value but 1 is refused here (the flag has no way to carry it)"""
 
     def __init__(self, width, height, qp=26, gop=30, fps=30, profile_idc=66, device=0, disable_deblock=0, slices=0, search=1,
-                 input_format=0, refs=0, flags=None, src_size=None, colour=None, temporal_layers=1):
+                 input_format=0, refs=0, flags=None, src_size=None, colour=None, temporal_layers=1,
+                 intra_refresh=False):
+        """intra_refresh: MI355X_H264_STREAM_INTRA_REFRESH joins the flags - the `slices` bands are coded all intra in turn"""
         L = lib()
         cfg = Config()
         L.mi355x_h264_default_config(C.byref(cfg))
@@ -583,6 +611,8 @@ class Stream:
             raise err
         if temporal_layers == 2:
             flags = (flags or 0) | STREAM_TEMPORAL2
+        if intra_refresh:
+            flags = (flags or 0) | STREAM_INTRA_REFRESH
         self.h = C.c_void_p()
         if colour is not None:
             sw, sh = (width, height) if src_size is None else (int(src_size[0]), int(src_size[1]))
@@ -643,6 +673,11 @@ class Stream:
     def last_temporal_id(self):
         """temporal layer (0 / 1) of the stream's last finished picture"""
         return lib().mi355x_h264_stream_last_temporal_id(self.h)
+
+    @property
+    def last_refresh_band(self):
+        """the all-intra band k of the stream's last finished picture; -1 for an IDR picture or with refresh off"""
+        return lib().mi355x_h264_stream_last_refresh_band(self.h)
 
     @property
     def colour(self):

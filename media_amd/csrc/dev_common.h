@@ -61,6 +61,8 @@ struct SliceRows {
     __device__ __forceinline__ int row_in_slice(int my) const { return my - (int)__umulhi((unsigned)my, inv) * rows; }
     // 6.4.4: the macroblocks above belong to another slice (or lie outside the picture) on a slice's first row
     __device__ __forceinline__ bool has_top(int my) const { return row_in_slice(my) != 0; }
+    // the band row my lies in (rows >= 2: inv is a reciprocal)
+    __device__ __forceinline__ int slice_of(int my) const { return (int)__umulhi((unsigned)my, inv); }
 };
 
 // macroblock index -> (mx, my) without a runtime division (a float reciprocal sequence of ~20 instructions, per lane in the
@@ -150,10 +152,14 @@ struct FrameParams {
 //   ME_SEED_PARK  a layer-0 P picture of a two-layer stream: the word comes from pmv, where the layer-1 picture in front of it kept
 //                 what the previous LAYER-0 picture left
 enum { ME_PARK = 1, ME_SEED_PARK = 2 };
+// Intra refresh (host_framing.h, PicSeq::refresh_band): the band k of the picture that is coded all intra travels as k + 1 (0: none)
+// beside them - direct launches in bits 8..13 of FrameParams::me, indirect launches in bits 22..27 of the position's itemtab word.
+// Only k_me<IND, true> reads it (k_me.h, me_refresh_band); the engines of refresh streams alone launch that form.
+enum { ME_RFR_SHIFT = 8, ITEM_RFR_SHIFT = 22, RFR_MASK = 63 };
 
 // itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 10..11 the reference pictures the position's
 // picture has (1..3 in a P step: reference pictures since the stream's IDR, at most config.refs; 0 in an IDR step), 12..13 ME_PARK /
-// ME_SEED_PARK of the position's picture, 16..21 QP
+// ME_SEED_PARK of the position's picture, 16..21 QP, 22..27 intra refresh band + 1 (above)
 struct ItemRef { int item, cur, nref, qp, me; };
 __device__ __forceinline__ ItemRef item_ref(const uint32_t* itemtab, int pos)
 {

@@ -12,6 +12,7 @@ constexpr int NSLOT = 3;          // access-unit slots in flight
 // where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
 struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0;
                   int layer = 0;        // temporal layer of the picture (the stream hub: of the position, with nal_hdr - hub.h sets both per picture)
+                  int rband = -1;       // intra refresh: the picture's all-intra band, -1 for none (the stream hub: the position's, as layer)
                   int quality = 0;      // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
                   int ssim = 0; };      // the SSIM record accompanies it (compared: k_ssim ran behind k_sse)
 
@@ -58,6 +59,7 @@ struct mi355x_h264_encoder : PicStore {      // (G: the lockstep batch, closed G
     uint32_t* d_me_total = nullptr;          // [G][nmb] best motion cost so far over the reference pictures (k_me, one launch each)
     int* d_pmv = nullptr;                    // [G][nmb] the previous picture's vectors, parked for the later launches - and, temporal layers, by a layer-1 picture for the layer-0 picture behind it
     int last_layer = 0;                      // temporal layer of the last finished picture (mi355x_h264_last_temporal_id)
+    std::vector<int> last_rband;             // per batch item: all-intra band of its last finished picture, -1 none (mi355x_h264_last_refresh_band)
     uint16_t* d_slotbits = nullptr;
     unsigned long long* d_slotcode = nullptr;
     uint32_t* d_mbbits = nullptr;
@@ -253,6 +255,8 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         P.ref[p] = P.refs[0][p];
     }
     P.me = ind ? 0 : e->seq.me_facts(idr);   // (temporal layers; indirect launches: the position's own, from the itemtab word)
+    const bool rfr = e->shape.refresh != 0;   // intra refresh: the other form of k_me, and the picture's band beside the facts
+    if (rfr && !ind) P.me |= (e->seq.refresh_band(idr) + 1) << ME_RFR_SHIFT;
     P.itemtab = T.d_itemtab; P.srctab = T.d_srctab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
     P.st_src = T.src_item_stride; P.sl = e->sl;
     P.band.row0 = e->b_row0; P.band.rows = e->b_rows;
@@ -319,7 +323,8 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             for (int r = 0; r < P.nref; r++) {   // (indirect: P.nref = the most any position has; no launch places a wave that has nothing to do)
                 Q.rf = r;
                 for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
-                LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
+                if (rfr) LAUNCH2(ind, (k_me<true, true>), (k_me<false, true>), dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
+                else LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
             } }
           // the lock goes back with the first wave of the k_tq that follows on this stream (k_tq.h tq_turn_release); in front of k_tq8
           // by a launch of its own
@@ -399,6 +404,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         const size_t pad = (16 - (pre & 15)) & 15;
         const int layer = ind ? 0 : e->seq.layer();   // (indirect: hub.h gives every position its own)
         T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr, slice_nal_hdr(idr, layer), layer};
+        T.lay.rband = ind ? -1 : e->seq.refresh_band(idr);
         LAUNCH2(ind, k_pack<true>, k_pack<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, (uint8_t*)S.d_bitbuf, e->st_bitbuf_bytes, S.h_au + T.lay.payload_off, e->st_au,
                 (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
     }
@@ -546,11 +552,17 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
     }
     if (frame_type) *frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
     e->last_layer = L.layer;
+    e->last_rband[g] = L.rband;
     std::vector<uint8_t>& eb = e->esc_buf[g];
     if (e->nsl > 1) {
         // several slices: one NAL unit each, put together here (the payloads lie slice_cap apart in the pinned buffer)
-        eb.resize(need);
         size_t pos = 0;
+        if (L.rband == 0) {   // intra refresh: the access unit that starts a cycle opens with the recovery point SEI
+            eb.clear();
+            append_recovery_point_sei(eb, e->nsl);   // (n = the stream's slices)
+            pos = eb.size();
+        }
+        eb.resize(need + pos);
         if (L.idr && e->b_sl0 == 0) { memcpy(eb.data(), e->sps_pps.data(), e->sps_pps.size()); pos = e->sps_pps.size(); }   // parameter sets go with the first band
         for (int sl = 0; sl < e->b_nsl; sl++) {
             const SliceInfo& si = info[sl];
@@ -846,9 +858,10 @@ int create_engine(const mi355x_h264_config* cfg, mi355x_h264_encoder** out, bool
     if (e->G > MAX_BATCH) { delete e; return MI355X_H264_E_ARG; }
     e->esc_buf.resize((size_t)e->G);
     e->last_me_cost.assign((size_t)e->G, 0);
+    e->last_rband.assign((size_t)e->G, -1);
     if (colour) e->colour = *colour;
     e->shape = StreamShape{cfg->profile_idc, e->level_idc, e->nrefs, e->mbw, e->mbh, cfg->width, cfg->height, e->nsl, cfg->disable_deblock,
-                           e->colour.described, e->colour.matrix, e->colour.full_range, chroma_loc ? 1 : 0, cfg->fps > 0 ? cfg->fps : 30};
+                           e->colour.described, e->colour.matrix, e->colour.full_range, chroma_loc ? 1 : 0, cfg->fps > 0 ? cfg->fps : 30, 0};
     e->sps_pps = build_parameter_sets(e->shape);
     e->diag_mode = getenv("MI355X_H264_DIAG") != nullptr && e->G == 1 && e->b_nsl == e->nsl;
     {

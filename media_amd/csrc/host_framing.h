@@ -32,6 +32,9 @@ int set_err(char (&err)[N], int code, const char* fmt, ...)
 // counts the reference pictures since the IDR picture (avail_refs).  After a layer-1 picture cur, frame_num and refs_in_gop are what
 // the layer-0 picture before it left: it is reconstructed into the ring slot the next layer-0 picture overwrites and carries that
 // picture's frame_num (PrevRefFrameNum + 1, 7.4.3).  layers = 1: the two counts move together and every picture is layer 0.
+// Intra refresh (include/mi355x_h264.h, "intra refresh"): refresh_n = n bands (0: off), and p, the count of P pictures since the
+// last IDR picture, is the position frame_in_gop of the picture begun - refresh needs one layer, so every picture counts, and
+// whatever makes an IDR picture (gop, force_idr, a scene change, a failed picture) restarts it with begin().
 struct PicSeq {
     int cur = 0;                 // ring slot the next picture is reconstructed into
     int frame_in_gop = 0, frame_num = 0, idr_id = 0, force_idr = 0;
@@ -43,6 +46,10 @@ struct PicSeq {
     // of the picture begun: its layer, and the two facts k_me takes (dev_common.h ME_PARK, ME_SEED_PARK)
     int layer() const { return layers == 2 ? (frame_in_gop & 1) : 0; }
     int me_facts(bool idr) const { return layers != 2 || idr ? 0 : layer() ? 1 : 2; }
+    int refresh_n = 0;           // intra refresh: the number of bands (the stream's slices), 0 = off
+    int refresh_p() const { return frame_in_gop; }   // of the picture begun: 1, 2, .. for the P pictures since the IDR picture
+    // the band of the picture begun that is coded all intra: k = (p - 1) mod n; -1 for an IDR picture or with refresh off
+    int refresh_band(bool idr) const { return refresh_n < 2 || idr || refresh_p() < 1 ? -1 : (refresh_p() - 1) % refresh_n; }
     // reference pictures the picture begun has, of a stream that searches nrefs: those coded since the stream's last IDR picture
     // (0, 1, 2, .. up to nrefs).  The one rule of the engine and the stream hub: a forced IDR restarts it with begin()
     int avail_refs(bool idr, int nrefs) const { return idr ? 0 : std::min(nrefs, refs_in_gop); }
@@ -57,9 +64,17 @@ struct PicSeq {
         if (idr) idr_id = (idr_id + idr_step) & 0xFF;
     }
 };
+// Intra refresh wants n = 2 .. 32 bands and the picture to have exactly that many: the bands the engine makes of `slices` for a
+// picture of mbh macroblock rows (create_engine's rule: ceil(mbh / slices) rows each, at least two), 0 for a count out of range
+inline int refresh_bands(int mbh, int slices)
+{
+    if (slices < 2 || slices > 32) return 0;
+    const int n = std::min(slices, std::max(1, mbh / 2)), rows = (mbh + n - 1) / n;
+    return (mbh + rows - 1) / rows;
+}
 // one picture of an indirect step (engine.h, Step): the batch item it belongs to and that stream's state for the picture
-// (nref: PicSeq::avail_refs; layer, me: PicSeq::layer, me_facts)
-struct ItemPic { int item, cur, qp, frame_num, idr_id, nref, layer, me; };
+// (nref: PicSeq::avail_refs; layer, me: PicSeq::layer, me_facts; rband: PicSeq::refresh_band)
+struct ItemPic { int item, cur, qp, frame_num, idr_id, nref, layer, me, rband; };
 // first byte of a slice NAL unit: nal_ref_idc 3 for an IDR picture, 2 for a P picture others refer to, 0 for a layer-1 picture
 inline int slice_nal_hdr(bool idr, int layer) { return idr ? ((3 << 5) | 5) : layer ? 1 : ((2 << 5) | 1); }
 
@@ -140,6 +155,23 @@ void append_nal(std::vector<uint8_t>& au, int ref_idc, int type, const HostBits&
     au.insert(au.end(), esc.begin(), esc.begin() + n);
 }
 
+// Recovery point SEI (D.1.7 / D.2.7) in front of the access unit that starts a refresh cycle (band 0 all intra): NAL type 6,
+// nal_ref_idc 0, one message of payload type 6 - recovery_frame_cnt = n - 1 (after the n pictures of the cycle every band has been
+// coded intra once and predicted from refreshed rows only), exact_match_flag 1, broken_link_flag 0, changing_slice_group_idc 0.
+// Appended to `au` with its start code, through nal_escape like every NAL unit.
+inline void append_recovery_point_sei(std::vector<uint8_t>& au, int n)
+{
+    HostBits pl;
+    pl.ue((uint32_t)n - 1); pl.put(1, 1); pl.put(1, 0); pl.put(2, 0);
+    if (pl.nbits & 7) pl.trailing();   // sei_payload(): bit_equal_to_one, then zero bits up to the byte boundary
+    HostBits b;
+    b.put(8, 6);                            // payloadType
+    b.put(8, (uint32_t)pl.bytes.size());    // payloadSize
+    for (uint8_t v : pl.bytes) b.put(8, v);
+    b.trailing();
+    append_nal(au, 0, 6, b);
+}
+
 template <class Quant>
 void fill_quant(Quant& q, int qp)
 {
@@ -185,7 +217,9 @@ void fill_filter_thresholds(Db& D, int qp)
 // described: the stream carries a colour description (include/mi355x_h264.h, "colour description") and its SPS ends with a VUI;
 // matrix (1 BT.709, 6 BT.601), full_range, chroma_loc (streams of RGBA input: chroma_loc_info is written) and fps are its contents.
 // 0 (every undescribed stream): the SPS is what it was before there were descriptions
-struct StreamShape { int profile_idc, level_idc, nrefs, mbw, mbh, width, height, nsl, disable_deblock, described, matrix, full_range, chroma_loc, fps; };
+// refresh: intra refresh is on (nsl bands).  No byte of the parameter sets or slice headers depends on it; it is here because the
+// engine of such a stream launches another form of k_me, so it shares no engine with an ordinary stream of nsl slices (hub.h)
+struct StreamShape { int profile_idc, level_idc, nrefs, mbw, mbh, width, height, nsl, disable_deblock, described, matrix, full_range, chroma_loc, fps, refresh; };
 
 // A colour description as its owner keeps it, and the variant of the two conversions it selects: 0 BT.601 limited (what an
 // undescribed stream has), 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full

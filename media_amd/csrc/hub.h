@@ -81,10 +81,11 @@ std::atomic<int> g_streams_open{0};   // over all hubs of the process
 
 // (refs: 0 and 1 are both one reference picture; streams that search more have rings of another size, so engines of their own)
 // (colour: the parameter sets are the engine's, so a described stream shares one only with streams of its description)
-bool same_geometry(const Hub& hub, const mi355x_h264_config& b, int sw, int sh, const ColourDesc& colour)
+// (refresh: a hub of intra refresh streams launches the other form of k_me - never shared with ordinary streams of as many slices)
+bool same_geometry(const Hub& hub, const mi355x_h264_config& b, int sw, int sh, const ColourDesc& colour, bool refresh)
 {
     const mi355x_h264_config& a = hub.cfg;
-    return same_colour(hub.colour, colour) && hub.sw == sw && hub.sh == sh && std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
+    return (hub.e->shape.refresh != 0) == refresh && same_colour(hub.colour, colour) && hub.sw == sw && hub.sh == sh && std::max(a.refs, 1) == std::max(b.refs, 1) && a.width == b.width && a.height == b.height && a.fps == b.fps && a.profile_idc == b.profile_idc && a.device == b.device &&
            a.disable_deblock == b.disable_deblock && a.slices == b.slices && a.search == b.search && a.input_format == b.input_format;
 }
 
@@ -127,7 +128,7 @@ hipError_t hub_alloc(Hub* h)
     return hipSuccess;
 }
 
-int hub_create(const mi355x_h264_config& cfg, int sw, int sh, const ColourDesc& colour, Hub** out)
+int hub_create(const mi355x_h264_config& cfg, int sw, int sh, const ColourDesc& colour, bool refresh, Hub** out)
 {
     Hub* h = new (std::nothrow) Hub();
     if (!h) return MI355X_H264_E_NOMEM;
@@ -148,6 +149,7 @@ int hub_create(const mi355x_h264_config& cfg, int sw, int sh, const ColourDesc& 
     ec.batch = h->sched.cap; ec.refs = std::max(cfg.refs, 1); ec.band_index = 0; ec.band_count = 0; ec.input_format = MI355X_H264_INPUT_I420;
     int rc = create_engine(&ec, &h->e, true, &h->colour, cfg.input_format == MI355X_H264_INPUT_RGBA);
     if (rc != MI355X_H264_OK) { h->e = nullptr; hub_free(h); return rc; }
+    h->e->shape.refresh = refresh ? 1 : 0;   // (no byte of the parameter sets depends on it: set behind their making)
     h->sched.nrefs = h->e->nrefs; h->sched.nbuf = h->e->nbuf;   // (up to 4 ring slots: `cur` fits the itemtab word's two bits)
     h->st_stage = (picture_bytes(PIC_I420, cfg.width, cfg.height) + 255) & ~(size_t)255;
     h->st_rgba = (picture_bytes(PIC_RGBA, cfg.width, cfg.height) + 255) & ~(size_t)255;
@@ -180,7 +182,8 @@ void hub_run_step(Hub* h, HubStep& T)
         const bool scaled = h->scaled;
         for (int k = 0; k < n; k++) {
             const HubItem& it = h->items[pics[k].item];
-            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].nref << 10) | ((uint32_t)pics[k].me << 12) | ((uint32_t)pics[k].qp << 16);
+            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].nref << 10) | ((uint32_t)pics[k].me << 12) | ((uint32_t)pics[k].qp << 16) |
+                           ((uint32_t)(pics[k].rband + 1) << ITEM_RFR_SHIFT);
             // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
             h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
             // (a scaling RGBA hub: the conversion reads the item's slot of the resampled RGBA pictures)
@@ -233,6 +236,7 @@ void hub_run_step(Hub* h, HubStep& T)
         if (rc == MI355X_H264_OK) {
             AuLayout L = St.lay;   // (the layer is the position's: streams of both kinds share the step)
             L.layer = pics[k].layer; L.nal_hdr = slice_nal_hdr(idr, L.layer);
+            L.rband = pics[k].rband;   // (intra refresh: the streams of a step stand at different bands)
             it.rc = finish_item(e, e->slots[0], L, pics[k].item, &it.out, &it.out_len, &it.frame_type);
             if (it.rc != MI355X_H264_OK) snprintf(it.err, sizeof(it.err), "%s", e->err);
             if (St.lay.quality) e->q_item[pics[k].item].qp = (uint32_t)pics[k].qp;   // (the position's own QP, not the engine's)

@@ -45,6 +45,7 @@ struct HubSched {
         int qp = 26, gop = 30;
         int last_cur = 0;            // ring slot of the last finished picture
         int last_layer = 0;          // and its temporal layer
+        int last_rband = -1;         // and its all-intra band (intra refresh; -1: an IDR picture, or refresh off)
         uint64_t step_serial = 0;    // the step that took the stream's last picture: its number on this hub (1, 2, ..), how many
         int step_n = 0, step_pos = 0;   // pictures it carried, this picture's position in it, and its type (test hook:
         bool step_idr = false;       // mi355x_h264_stream_debug_last_step)
@@ -58,7 +59,7 @@ struct HubSched {
     size_t p_share() const { return std::max<size_t>(1, ((size_t)nopen + nctx_p) / (nctx_p + 1)); }
 
     bool has_room() { std::lock_guard<std::mutex> lk(mu); return nopen < cap; }
-    int open(int qp, int gop, int layers = 1)
+    int open(int qp, int gop, int layers = 1, int refresh_n = 0)   // refresh_n: bands of an intra refresh stream, 0 = an ordinary one
     {
         std::lock_guard<std::mutex> lk(mu);
         int idx = 0;
@@ -66,6 +67,7 @@ struct HubSched {
         if (idx >= cap) return -1;
         items[idx] = Item();
         items[idx].open = true; items[idx].qp = qp; items[idx].gop = gop; items[idx].seq.layers = layers;
+        items[idx].seq.refresh_n = refresh_n;
         nopen++;
         return idx;
     }
@@ -83,6 +85,7 @@ struct HubSched {
     void set_idr_pic_id(int item, int next) { std::lock_guard<std::mutex> lk(mu); items[item].seq.idr_id = next & 0xFF; }
     int last_cur(int item) { std::lock_guard<std::mutex> lk(mu); return items[item].last_cur; }
     int last_layer(int item) { std::lock_guard<std::mutex> lk(mu); return items[item].last_layer; }
+    int last_rband(int item) { std::lock_guard<std::mutex> lk(mu); return items[item].last_rband; }
     void last_step(int item, uint64_t* serial, int* n, int* pos, int* idr)
     {
         std::lock_guard<std::mutex> lk(mu);
@@ -139,7 +142,7 @@ struct HubSched {
             for (int k = 0; k < T.n; k++) {
                 Item& b = items[q[k]];
                 b.seq.begin(idr);
-                T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id, b.seq.avail_refs(idr, nrefs), b.seq.layer(), b.seq.me_facts(idr)};
+                T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id, b.seq.avail_refs(idr, nrefs), b.seq.layer(), b.seq.me_facts(idr), b.seq.refresh_band(idr)};
                 T.rc[k] = 0;
             }
             // positions by their number of reference pictures, most first (queue order within a number): the motion search of
@@ -158,7 +161,7 @@ struct HubSched {
             lk.lock();
             for (int k = 0; k < T.n; k++) {
                 Item& b = items[T.picks[k].item];
-                if (T.rc[k] == 0) { b.last_cur = b.seq.cur; b.last_layer = T.picks[k].layer; b.seq.advance(idr, nbuf, 1); }
+                if (T.rc[k] == 0) { b.last_cur = b.seq.cur; b.last_layer = T.picks[k].layer; b.last_rband = T.picks[k].rband; b.seq.advance(idr, nbuf, 1); }
                 else b.seq.force_idr = 1;   // the picture is missing from the stream (or not to be trusted): the next one must not refer to it
                                             // (a layer-1 picture nobody refers to: one rule for both layers all the same)
                 b.done = true;

@@ -594,7 +594,9 @@ struct SliceInfo {       // lives in pinned host memory, written by the device
     uint32_t epb_count;  // positions needing an emulation prevention byte
     uint32_t error;
     uint32_t me_cost;    // scene-change statistic gathered by k_me (0 for IDR pictures)
-    uint32_t searched;   // P slices: macroblocks k_me searched (its "nothing left to code" tests settled the others: me_cost 0)
+    uint32_t searched;   // P slices: macroblocks k_me searched (its "nothing left to code" tests settled the others: me_cost 0).
+                         // Intra refresh: the forced band's macroblocks (me_cost 0x8000) count here too, though their waves return in
+                         // front of the search - they cancel in tq_coded, so k_tq's count is right and k_me's is high by one band a picture
     uint32_t tq_coded;   // of those, the ones k_tq / k_tq8 coded (not handed to the intra pass: me_cost bit 15)
     uint32_t pad[1];
 };

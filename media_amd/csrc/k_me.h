@@ -171,7 +171,26 @@ __device__ __forceinline__ uint32_t chroma_pred4_half(const uint8_t* cp, int cs2
 #ifndef ME_WAVES_MIN
 #define ME_WAVES_MIN 6
 #endif
-template <bool IND = false>
+// RFR = true: the form for streams with intra refresh (include/mi355x_h264.h, "intra refresh"), launched by their engines alone.
+// The picture's band k (me_refresh_band) is not searched at all: its waves hand every macroblock to the intra pass and return in
+// front of their first load.  A wave of a band above it (a clean band) carries one wave-uniform bound `dymax` on the vertical
+// integer displacement dy, such that no prediction reads a reference row below L = 16 * row_end(k - 1) - 1:
+//   the integer winner has by + dy + 18 <= L - the sub-sample stage and the partitions stay within 0.75 samples of it, so the last
+//   row they read is at most by + 15 + dy + 3 (six-tap filter), and the last chroma row by / 2 + 8 + floor((4 dy + 3) / 8) <= (L + 1) / 2 - 1;
+//   a "nothing left to code" hit is integer and nothing refines it, so it needs by + dy + 15 <= L only (dy <= dymax + 3; the zero
+//   vector always passes: by + 15 <= L in every clean band);
+//   the seeded test takes a previous vector beyond the bound as "not a strict minimum" and leaves neighbours beyond it out, as it
+//   leaves out those beyond the search range; the exhaustive pass prices rows beyond it so that they never win (rows -16 .. -3
+//   are within the bound for every macroblock, so a winner exists).
+// Bands below k are searched as ever.  RFR = false compiles to what it was: every use of the bound is behind `if constexpr`.
+template <bool IND, bool RFR>
+__device__ __forceinline__ int me_refresh_band(const FrameParams& P0, const FrameParams& P)
+{
+    if constexpr (!RFR) return -1;
+    else if constexpr (IND) return (int)(((uint32_t)__builtin_amdgcn_readfirstlane((int)P0.itemtab[blockIdx.y]) >> ITEM_RFR_SHIFT) & RFR_MASK) - 1;
+    else return ((P.me >> ME_RFR_SHIFT) & RFR_MASK) - 1;
+}
+template <bool IND = false, bool RFR = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN, 8))) void k_me(FrameParams P0)
 {
     if (AB_PRIO_ME) __builtin_amdgcn_s_setprio(AB_PRIO_ME);
@@ -186,6 +205,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
 #endif
     const int mbi = P.band.row0 * P.mbw + xcd_mb_index(blockIdx.x, P.mbw * P.band.rows), my = P.mbdiv.row(mbi), mx = mbi - my * P.mbw;
     const int bx = 16 * mx, by = 16 * my;
+    int dymax = ME_R;   // RFR, clean bands: the integer winner's dy is at most this (others: no bound, the range ends at ME_R - 1)
+    if constexpr (RFR) {
+        const int rk = me_refresh_band<IND, RFR>(P0, P), band = P.sl.slice_of(my);
+        if (band == rk) {
+            // the refresh band: Intra16x16 or Intra4x4 by the intra pass, as section 5 hands a macroblock over - the MB_I16 word with
+            // the zeroed tc[], bit 15 of me_cost.  The cost beside it is 0: a forced macroblock says nothing about the content, so it
+            // adds nothing to the scene-change statistic (k_bit_scan sums bits 0..14).  No inter prediction is written
+            if (lane == 0) {
+                uint4* m = (uint4*)(P.mb + mbi);
+                m[0] = make_uint4(0u, (uint32_t)MB_I16, 0u, 0u);
+                m[1] = make_uint4(0u, 0u, 0u, 0u);
+                *(uint4*)(P.mvq + (size_t)mbi * 8) = make_uint4(0u, 0u, 0u, 0u);
+                P.me_cost[mbi] = (uint16_t)0x8000u;
+                *P.anyintra = P.pic_serial;
+                *P.stepintra = P.pic_serial;
+            }
+            return;
+        }
+        if (band < rk) dymax = min(ME_R, 16 * rk * P.sl.rows - 1 - 18 - by);   // L - 18 - by, at least -3
+    }
 
     __shared__ __attribute__((aligned(16))) uint32_t s_win[ME_WS * ME_WDW];  // 56 x 56 bytes
     __shared__ __attribute__((aligned(16))) uint8_t s_src[256];
@@ -409,7 +448,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
             if (why == 0) { settle(0, 0, ry, rc); return; }
         }
         const int rvx = ((pmx + 2) >> 2) * 4, rvy = ((pmy + 2) >> 2) * 4;   // the previous vector rounded to integer samples
-        if ((rvx | rvy) != 0) {   // wave-uniform
+        if ((rvx | rvy) != 0 && (!RFR || (rvy >> 2) <= dymax + 3)) {   // wave-uniform (RFR: an integer hit may read down to row L)
             // luma: integer displacement inside the window; chroma: 1/8-sample bilinear (8.4.2.2.2) at fractions 0 or 4 (averages),
             // samples clamped at the picture edge exactly as motion compensation does - fetched (ten global loads) only once
             // the luma block sums have let the wave through
@@ -436,7 +475,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
     bool seeded = false;
     if (P.search == 1) {
         const int sx = (pmx + 2) >> 2, sy = (pmy + 2) >> 2;
-        if (sx >= -ME_R && sx < ME_R && sy >= -ME_R && sy < ME_R) {   // wave-uniform
+        if (sx >= -ME_R && sx < ME_R && sy >= -ME_R && sy < ME_R && (!RFR || sy <= dymax)) {   // wave-uniform
             const int g = lane >> 4, j = lane & 15;
             const int dyc = sy - 1 + (g < 3 ? g : 0);
             const uint4 sv = *(const uint4*)(s_src + 16 * j);
@@ -458,7 +497,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
                     const int dx = sx - 1 + k, dy = sy - 1 + gy;
                     const unsigned sad = (unsigned)__builtin_amdgcn_readlane(sad3[k], 16 * gy);
                     const unsigned key = ((sad + (unsigned)(P.lambda * (se_len(4 * dx - pmx) + se_len(4 * dy - pmy)))) << 10) | (unsigned)(((dy + ME_R) << 5) | (dx + ME_R));
-                    const bool inr = dx >= -ME_R && dx < ME_R && dy >= -ME_R && dy < ME_R;
+                    const bool inr = dx >= -ME_R && dx < ME_R && dy >= -ME_R && dy < ME_R && (!RFR || dy <= dymax);
                     if (gy == 1 && k == 1) ckey = key;
                     else if (inr && key < nmin) nmin = key;
                 }
@@ -473,7 +512,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ME_WAVES_MIN
         const int dxi = lane & 31, half = lane >> 5;
         const int col = dxi + ME_AP, cdw = col >> 2, sh = col & 3;
         // motion-vector cost and candidate index of every dy, shifted into key position: one table per macroblock
-        if (lane < 32) s_ytab[lane] = ((uint32_t)__mul24(P.lambda, se_len(4 * (lane - ME_R) - pmy)) << 10) | ((uint32_t)lane << 5);
+        // (RFR: a row beyond the bound gets bits 30..31 in place of its cost - above every key a row within the bound can have:
+        // SAD + cost < 2^17, so such keys lie below 2^27 - and neither the bound of pass 1 nor pass 2 ever takes it)
+        if (lane < 32) s_ytab[lane] = (RFR && lane - ME_R > dymax ? 0xC0000000u : ((uint32_t)__mul24(P.lambda, se_len(4 * (lane - ME_R) - pmy)) << 10)) | ((uint32_t)lane << 5);
         // the source macroblock is wave-uniform: keep its 64 dwords in SGPRs (v_sad_u8 takes one scalar operand).
         // Macroblocks inside the picture read it with scalar loads straight from the source picture.
         uint32_t srow[16][4];

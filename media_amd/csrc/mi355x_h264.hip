@@ -217,12 +217,32 @@ int mi355x_h264_set_temporal_layers(mi355x_h264_encoder* e, int layers)
 {
     NEED(e, layers == 1 || layers == 2, "temporal layers: 1 or 2");
     NEED(e, layers == 1 || e->cfg.band_count <= 1, "temporal layers: not on a band instance (the halo exchange is the caller's)");
+    NEED(e, layers == 1 || !e->shape.refresh, "temporal layers: not with intra refresh");
     NEED(e, e->seq.frames == 0, "temporal layers: before the first picture only");
     e->seq.layers = layers;
     return MI355X_H264_OK;
 }
 int mi355x_h264_last_temporal_id(const mi355x_h264_encoder* e) { return e ? e->last_layer : MI355X_H264_E_ARG; }
 int mi355x_h264_stream_last_temporal_id(const mi355x_h264_stream* s) { return s ? s->hub->sched.last_layer(s->item) : MI355X_H264_E_ARG; }
+
+// ---- intra refresh (host_framing.h, PicSeq::refresh_band; k_me.h, the RFR form) ----
+int mi355x_h264_set_intra_refresh(mi355x_h264_encoder* e, int on)
+{
+    NEED(e, on == 0 || on == 1, "intra refresh: 0 or 1");
+    NEED(e, e->seq.frames == 0, "intra refresh: before the first picture only");
+    if (on) {
+        NEED(e, e->cfg.slices >= 2 && e->cfg.slices <= 32, "intra refresh: an encoder with slices = 2 .. 32");
+        NEED(e, refresh_bands(e->mbh, e->cfg.slices) == e->cfg.slices, "intra refresh: the picture does not divide into that many bands of two rows or more");
+        NEED(e, e->cfg.refs <= 1, "intra refresh: one reference picture");
+        NEED(e, e->seq.layers == 1, "intra refresh: one temporal layer");
+        NEED(e, e->cfg.band_count <= 1, "intra refresh: not on a band instance");
+    }
+    e->shape.refresh = on;
+    e->seq.refresh_n = on ? e->nsl : 0;
+    return MI355X_H264_OK;
+}
+int mi355x_h264_last_refresh_band(const mi355x_h264_encoder* e) { return e ? e->last_rband[0] : MI355X_H264_E_ARG; }
+int mi355x_h264_stream_last_refresh_band(const mi355x_h264_stream* s) { return s ? s->hub->sched.last_rband(s->item) : MI355X_H264_E_ARG; }
 
 int mi355x_h264_set_idr_pic_id(mi355x_h264_encoder* e, int next, int step)
 {
@@ -304,6 +324,7 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, co
     NEED(e, mbinfo && levels && mvq && mbaux && src_i420 && out && out_len, "null argument");
     NEED(e, e->cfg.band_count <= 1, "not for slice bands over several instances");
     NEED(e, e->seq.layers == 1, "not for an encoder with two temporal layers");
+    NEED(e, !e->shape.refresh, "not for an encoder with intra refresh");
     HIPCHK(e->err, hipSetDevice(e->device));
     const size_t src_bytes = e->frame_bytes * (size_t)e->G;
     if (!e->d_inject_src) HIPCHK(e->err, DM_DEV(e->mem, e->d_inject_src, src_bytes + 256, false));
@@ -414,7 +435,11 @@ int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags
         if (cfg->width < 16 || cfg->height < 16 || ((cfg->width | cfg->height) & 1)) return MI355X_H264_E_ARG;
         if (sw < cfg->width || sh < cfg->height || sw > 4 * cfg->width || sh > 4 * cfg->height) return MI355X_H264_E_ARG;
     }
-    if (flags & ~(uint32_t)(MI355X_H264_STREAM_MULTIREF | MI355X_H264_STREAM_TEMPORAL2)) return MI355X_H264_E_ARG;
+    if (flags & ~(uint32_t)(MI355X_H264_STREAM_MULTIREF | MI355X_H264_STREAM_TEMPORAL2 | MI355X_H264_STREAM_INTRA_REFRESH)) return MI355X_H264_E_ARG;
+    const bool refresh = (flags & MI355X_H264_STREAM_INTRA_REFRESH) != 0;
+    // intra refresh: 2..32 bands of two rows or more that the picture really divides into, one reference picture, one layer
+    if (refresh && ((flags & MI355X_H264_STREAM_TEMPORAL2) || cfg->refs > 1 || cfg->slices < 2 || refresh_bands((cfg->height + 15) / 16, cfg->slices) != cfg->slices))
+        return MI355X_H264_E_ARG;
     const int max_refs = (flags & MI355X_H264_STREAM_MULTIREF) ? (int)mi355x_h264_encoder::MAX_REFS : 1;
     if (cfg->refs > max_refs || cfg->band_count > 1 || cfg->batch > 1) return MI355X_H264_E_ARG;
     if (cfg->input_format != MI355X_H264_INPUT_I420 && cfg->input_format != MI355X_H264_INPUT_NV12 && cfg->input_format != MI355X_H264_INPUT_RGBA)
@@ -425,13 +450,13 @@ int mi355x_h264_stream_open_colour(const mi355x_h264_config* cfg, uint32_t flags
     std::lock_guard<std::mutex> gl(g_hubs_mu);
     Hub* h = nullptr;
     for (Hub* c : g_hubs)
-        if (same_geometry(*c, *cfg, sw, sh, desc) && c->sched.has_room()) { h = c; break; }
+        if (same_geometry(*c, *cfg, sw, sh, desc, refresh) && c->sched.has_room()) { h = c; break; }
     if (!h) {
-        const int rc = hub_create(*cfg, sw, sh, desc, &h);
+        const int rc = hub_create(*cfg, sw, sh, desc, refresh, &h);
         if (rc != MI355X_H264_OK) { delete s; return rc; }
         g_hubs.push_back(h);
     }
-    const int idx = h->sched.open(cfg->qp, cfg->gop, (flags & MI355X_H264_STREAM_TEMPORAL2) ? 2 : 1);   // (there is room: opens and closes are serialised by g_hubs_mu)
+    const int idx = h->sched.open(cfg->qp, cfg->gop, (flags & MI355X_H264_STREAM_TEMPORAL2) ? 2 : 1, refresh ? cfg->slices : 0);   // (there is room: opens and closes are serialised by g_hubs_mu)
     HubItem& it = h->items[idx];
     hipEvent_t ev = it.copied;
     it = HubItem();

@@ -115,11 +115,28 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     if (layersJunk) {
         WARN("temporal layers [%s] rejected: one layer", layersKey.c_str());
     }
+    // extension: "n" (2..32) = intra refresh over n slice bands (include/mi355x_h264.h, "intra refresh"); it sets slices = n.  Both
+    // paths.  Junk, or a conflict with .slices, .refs or .temporallayers (or a picture that has no n bands): one WARN line and the
+    // stream the other keys describe
+    const std::string refreshKey = GetStrEncParam("persist.vmi.video.encode.intrarefresh");
+    bool refreshWarn = false;
+    m_intraRefresh = ParseIntraRefresh(refreshKey, cfg.slices, cfg.refs, m_temporalLayers, s.height, &refreshWarn);
+    m_lastRefreshBand = -1;
+    if (refreshWarn) {
+        WARN("intra refresh [%s] rejected (2..32 bands the picture divides into, the same .slices or none, one reference picture, one layer): off",
+             refreshKey.c_str());
+    }
+    if (m_intraRefresh > 0) {
+        cfg.slices = m_intraRefresh;
+    }
     if (shared) {
         cfg.input_format = m_input;
         uint32_t flags = MI355X_H264_STREAM_MULTIREF;
         if (m_temporalLayers == 2) {
             flags |= MI355X_H264_STREAM_TEMPORAL2;
+        }
+        if (m_intraRefresh > 0) {
+            flags |= MI355X_H264_STREAM_INTRA_REFRESH;
         }
         const int rc = haveColour > 0 ? mi355x_h264_stream_open_colour(&cfg, flags, haveSrc > 0 ? m_srcWidth : cfg.width,
                                                                        haveSrc > 0 ? m_srcHeight : cfg.height, &colour, &m_stream)
@@ -154,6 +171,12 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     }
     if (m_temporalLayers == 2 && mi355x_h264_set_temporal_layers(m_engine, 2) != MI355X_H264_OK) {
         ERR("temporal layers: %s", mi355x_h264_last_error(m_engine));
+        mi355x_h264_destroy(m_engine);
+        m_engine = nullptr;
+        return false;
+    }
+    if (m_intraRefresh > 0 && mi355x_h264_set_intra_refresh(m_engine, 1) != MI355X_H264_OK) {
+        ERR("intra refresh: %s", mi355x_h264_last_error(m_engine));
         mi355x_h264_destroy(m_engine);
         m_engine = nullptr;
         return false;
@@ -332,6 +355,33 @@ int32_t VideoEncoderMI355X::ParseTemporalLayers(const std::string &value, bool *
     return value == "2" ? 2 : 1;
 }
 
+int32_t VideoEncoderMI355X::ParseIntraRefresh(const std::string &value, int32_t slices, int32_t refs, int32_t layers, uint32_t height, bool *warn)
+{
+    if (warn != nullptr) {
+        *warn = false;
+    }
+    if (value.empty()) {
+        return 0;
+    }
+    int32_t n = 0;
+    bool ok = value.size() <= 2 && value[0] != '0';
+    for (char ch : value) {
+        ok = ok && ch >= '0' && ch <= '9';
+        n = n * 10 + (ch - '0');
+    }
+    ok = ok && n >= 2 && n <= 32;
+    if (ok) {   // the bands the engine makes of n slices: ceil(rows / n) macroblock rows each, two at least
+        const int32_t mbh = (static_cast<int32_t>(height) + 15) / 16;
+        const int32_t m = std::min(n, std::max(1, mbh / 2)), rows = (mbh + m - 1) / m;
+        ok = (mbh + rows - 1) / rows == n;
+    }
+    ok = ok && (slices == 0 || slices == n) && refs <= 1 && layers == 1;
+    if (!ok && warn != nullptr) {
+        *warn = true;
+    }
+    return ok ? n : 0;
+}
+
 bool VideoEncoderMI355X::ParseSsim(const std::string &value) { return value == "1"; }
 
 int VideoEncoderMI355X::ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out)
@@ -440,6 +490,7 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
         return false;
     }
     m_lastTemporalId = m_stream != nullptr ? mi355x_h264_stream_last_temporal_id(m_stream) : mi355x_h264_last_temporal_id(m_engine);
+    m_lastRefreshBand = m_stream != nullptr ? mi355x_h264_stream_last_refresh_band(m_stream) : mi355x_h264_last_refresh_band(m_engine);
     if (m_psnr || m_ssim) {
         QualityAfterPicture(frameType == MI355X_H264_FRAME_IDR);
     }

@@ -66,6 +66,13 @@ public:
     static int32_t ParseTemporalLayers(const std::string &value, bool *junk);
     // temporal layer (0 / 1) of the last picture that went out; -1 before the first
     int32_t LastTemporalId() const { return m_lastTemporalId; }
+    // extension key persist.vmi.video.encode.intrarefresh: "n" (decimal, 2..32) -> intra refresh over n slice bands, which sets
+    // slices = n (include/mi355x_h264.h, "intra refresh"), on both paths; unset -> 0, off.  Anything else, a picture of `height`
+    // that has no n bands of two macroblock rows, a .slices of another count (slices: the parsed key, 0 unset), refs > 1 or two
+    // temporal layers -> 0 with *warn set (one WARN line, the stream the other keys describe)
+    static int32_t ParseIntraRefresh(const std::string &value, int32_t slices, int32_t refs, int32_t layers, uint32_t height, bool *warn);
+    // the all-intra band of the last picture that went out; -1 for an IDR picture, with refresh off and before the first
+    int32_t LastRefreshBand() const { return m_lastRefreshBand; }
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -98,6 +105,7 @@ private:
     int32_t m_input = MI355X_H264_INPUT_I420;   // layout of the pictures EncodeOneFrame is handed (persist.vmi.video.encode.input)
     int32_t m_srcWidth = 0, m_srcHeight = 0;    // > 0: the pictures' size (.srcwidth / .srcheight), resampled to the coded size on the device
     bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
+    int32_t m_intraRefresh = 0, m_lastRefreshBand = -1;     // .intrarefresh (bands, 0 off); the band of the last picture that went out
     int32_t m_temporalLayers = 1, m_lastTemporalId = -1;   // .temporallayers; the layer of the last picture that went out
     // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
     bool m_psnr = false, m_haveQuality = false;

@@ -42,6 +42,19 @@ int32_t vc_parse_temporal_layers(const char *value, int32_t *junk)
     if (junk != nullptr) *junk = j ? 1 : 0;
     return n;
 }
+// persist.vmi.video.encode.intrarefresh: the bands (0: off); *warn = junk or a conflict with the other keys (one WARN line)
+int32_t vc_parse_intra_refresh(const char *value, int32_t slices, int32_t refs, int32_t layers, uint32_t height, int32_t *warn)
+{
+    bool w = false;
+    const int32_t n = VideoEncoderMI355X::ParseIntraRefresh(value != nullptr ? value : "", slices, refs, layers, height, &w);
+    if (warn != nullptr) *warn = w ? 1 : 0;
+    return n;
+}
+int32_t vc_last_refresh_band(void *enc)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    return m != nullptr ? m->LastRefreshBand() : -1;
+}
 int32_t vc_last_temporal_id(void *enc)
 {
     auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
@@ -77,7 +90,7 @@ int32_t vc_colour(void *enc, int32_t *matrix, int32_t *fullRange)
 // build_parameter_sets): shape = the fourteen fields of StreamShape in order.  Returns the bytes, or -1 when cap is too small
 int32_t vc_debug_parameter_sets(const int32_t *shape, uint8_t *dst, int32_t cap)
 {
-    const StreamShape f{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9], shape[10], shape[11], shape[12], shape[13]};
+    const StreamShape f{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9], shape[10], shape[11], shape[12], shape[13], 0};
     const std::vector<uint8_t> ps = build_parameter_sets(f);
     if (static_cast<size_t>(cap) < ps.size()) return -1;
     std::memcpy(dst, ps.data(), ps.size());

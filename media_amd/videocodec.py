@@ -37,6 +37,8 @@ def lib():
         L.vc_parse_refs.argtypes = [C.c_char_p]
         L.vc_parse_temporal_layers.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
         L.vc_last_temporal_id.argtypes = [vp]
+        L.vc_parse_intra_refresh.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]
+        L.vc_last_refresh_band.argtypes = [vp]
         L.vc_parse_psnr.argtypes = [C.c_char_p]
         L.vc_parse_ssim.argtypes = [C.c_char_p]
         L.vc_last_ssim.argtypes = [vp, vp]
@@ -96,6 +98,14 @@ def parse_temporal_layers(value):
     junk = C.c_int32()
     n = lib().vc_parse_temporal_layers(str(value).encode(), C.byref(junk))
     return n, bool(junk.value)
+
+
+def parse_intra_refresh(value, slices=0, refs=0, layers=1, height=1080):
+    """what persist.vmi.video.encode.intrarefresh = value selects beside the other keys: (bands, one WARN line?) - n for a decimal
+    2..32 the picture divides into that conflicts with nothing, 0 for the unset key, 0 with the mark for anything else"""
+    warn = C.c_int32()
+    n = lib().vc_parse_intra_refresh(str(value).encode(), slices, refs, layers, height, C.byref(warn))
+    return n, bool(warn.value)
 
 
 def parse_ssim(value):
@@ -162,7 +172,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
                    inputmem=None, refs=None, psnr=None, ssim=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None,
-                   temporallayers=None):
+                   temporallayers=None, intrarefresh=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -187,6 +197,7 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.colour", "" if colour is None else colour)         # bt601 | bt709 } either one set and valid: a
     prop_set("persist.vmi.video.encode.range", "" if range is None else range)            # limited | full } described stream
     prop_set("persist.vmi.video.encode.temporallayers", "" if temporallayers is None else temporallayers)   # 2: two temporal layers
+    prop_set("persist.vmi.video.encode.intrarefresh", "" if intrarefresh is None else intrarefresh)       # n: intra refresh, n bands
     if shared is not None:
         prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 
@@ -250,6 +261,10 @@ class VideoEncoder:
     def last_temporal_id(self):
         """temporal layer (0 / 1) of the last picture that went out (persist.vmi.video.encode.temporallayers = 2); -1 before the first"""
         return lib().vc_last_temporal_id(self.h)
+
+    def last_refresh_band(self):
+        """the all-intra band of the last picture that went out (persist.vmi.video.encode.intrarefresh = n); -1: none"""
+        return lib().vc_last_refresh_band(self.h)
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)

@@ -15,6 +15,30 @@
 
 int main(int argc, char** argv)
 {
+    // intra refresh:  pic_seq_harness refresh N GOP SCRIPT  - one line per picture: idr p k sei-bytes-in-hex ('-' where the access unit
+    // has none); SCRIPT as above.  pic_seq_harness bands MBH SLICES - refresh_bands().  tests/test_intra_refresh_host.py
+    if (argc == 5 && !strcmp(argv[1], "refresh")) {
+        const int n = atoi(argv[2]), gop = atoi(argv[3]);
+        PicSeq seq;
+        seq.refresh_n = n;
+        for (const char* p = argv[4]; *p; p++) {
+            if (*p == 'I') seq.force_idr = 1;
+            const bool idr = seq.next_is_idr(gop);
+            seq.begin(idr);
+            const int k = seq.refresh_band(idr);
+            printf("%d %d %d ", idr ? 1 : 0, idr ? 0 : seq.refresh_p(), k);
+            if (k == 0) {
+                std::vector<uint8_t> au;
+                append_recovery_point_sei(au, n);
+                for (uint8_t v : au) printf("%02x", v);
+            } else putchar('-');
+            putchar('\n');
+            if (*p == 'F') seq.force_idr = 1;
+            else seq.advance(idr, 2, 1);
+        }
+        return 0;
+    }
+    if (argc == 4 && !strcmp(argv[1], "bands")) { printf("%d\n", refresh_bands(atoi(argv[2]), atoi(argv[3]))); return 0; }
     if (argc != 7) { fprintf(stderr, "usage: %s LAYERS GOP REFS SLICES QP SCRIPT\n", argv[0]); return 2; }
     const int layers = atoi(argv[1]), gop = atoi(argv[2]), nrefs = std::max(1, atoi(argv[3])), nsl = std::max(1, atoi(argv[4])), qp = atoi(argv[5]);
     const char* script = argv[6];

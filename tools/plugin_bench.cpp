@@ -5,13 +5,16 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
 // --temporal N (anywhere on the line): the extension key persist.vmi.video.encode.temporallayers = N - with 2 every second P picture
 // of a GOP is a non-reference picture (include/mi355x_h264.h, "temporal layers"); every picture's layer is read after its call
 // (outside the latency sample), and the JSON line carries pictures_l0 / pictures_l1 and bytes_l0 / bytes_l1.
+// --intra-refresh N (anywhere on the line): the extension key persist.vmi.video.encode.intrarefresh = N - N slice bands, one of them
+// all intra in every P picture (include/mi355x_h264.h, "intra refresh").  Compare with a run that sets
+// PERSIST_VMI_VIDEO_ENCODE_SLICES=N instead: the same slices without the refresh.
 // --ssim (anywhere on the line): the extension key persist.vmi.video.encode.ssim = 1 - the report is on with both metrics, every
 // picture's SSIM record is read after its call (outside the latency sample), and the JSON line carries ssim_y / ssim_u / ssim_v:
 // sum / (65536 windows) over all pictures of the run, per plane.
@@ -64,6 +67,13 @@ int main(int argc, char **argv)
             argc -= 2;
             break;
         }
+    for (int i = 1; i + 1 < argc; i++)   // --intra-refresh N: taken out of the line
+        if (strcmp(argv[i], "--intra-refresh") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_INTRAREFRESH", argv[i + 1], 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     bool psnr = false;
     for (int i = 1; i < argc; i++)   // --psnr: taken out of the line
         if (strcmp(argv[i], "--psnr") == 0) {
@@ -100,7 +110,7 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     // (w, h: the size of the pictures in the file and in every call - the source size with --src)
     const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
