@@ -225,8 +225,9 @@ int mi355x_h264_last_temporal_id(const mi355x_h264_encoder *enc);
  * order of the two calls), a band instance (band_count > 1), a call after the first picture; and mi355x_h264_debug_code_syntax on
  * such an encoder.  Streams: MI355X_H264_STREAM_INTRA_REFRESH in the flags of the open calls, refused on the same grounds.
  * The two _last_refresh_band calls give k of the last finished picture, -1 for an IDR picture or with refresh off.
- * Not built: the decoder peer joining at a recovery point (it waits for an IDR picture), refresh with several reference pictures
- * or temporal layers, column refresh, rate control aware of the intra band. */
+ * The decoder peer recovers as promised here: mi355x_h264_dec.h, "loss mode".
+ * Not built: the encoder repeating SPS / PPS at recovery points (a receiver that joins needs them from elsewhere), refresh with
+ * several reference pictures or temporal layers, column refresh, rate control aware of the intra band. */
 int mi355x_h264_set_intra_refresh(mi355x_h264_encoder *enc, int on);
 int mi355x_h264_last_refresh_band(const mi355x_h264_encoder *enc);
 /* Scene-change statistic of the last finished picture, one value per batch item: the sum over the

@@ -190,6 +190,67 @@ int mi355x_h264_dec_output_size(const mi355x_h264_decoder *dec, int *width, int 
 int mi355x_h264_dec_group_set_output_size(mi355x_h264_dec_group *g, int stream, int width, int height);
 int mi355x_h264_dec_group_output_size(const mi355x_h264_dec_group *g, int stream, int *width, int *height);
 
+/* ---- loss mode: conceal lost slices and pictures, join at a recovery point, and know when pictures are exact again ----
+ * A decoder, or a stream of a group, has a loss mode.  MI355X_H264_LOSS_STRICT (0, the default) is everything said above: a picture
+ * whose slices leave a hole, a frame_num that does not follow, a P picture with nothing held are refused, and the stream waits for an
+ * IDR picture.  MI355X_H264_LOSS_CONCEAL (1) decodes on.  The mode may be set at any time between calls; E_ARG for another mode, no
+ * such stream, a null handle.  Strict and concealing streams share a group and its steps; a stream left strict keeps every refusal,
+ * message, launch, copy and allocation it had.
+ *
+ * Concealment is not normative; this is the library's definition: WHAT IS MISSING IS DECODED AS IF AN ALL-P_SKIP SLICE HAD ARRIVED IN
+ * ITS PLACE, so that any conforming decoder fed the stream with those slices put in produces the same samples.
+ *   Missing or damaged slice.  A hole in the macroblock addresses - from the address behind the last received slice (0 at the start
+ *   of the picture) to the next received slice's first_mb_in_slice, or to the end of the picture - is filled.  A slice NAL unit that
+ *   does not parse, in its header or anywhere in its data, is dropped WHOLE and its extent becomes such a hole (so does a slice that
+ *   runs on into the next one).  The fill stands for ONE P slice of exactly those macroblocks: one mb_skip_run; the picture parameter
+ *   set, reference list and deblocking parameters of the picture's received slices; slice QP = that of the preceding slice in
+ *   decoding order (the last slice of the previous picture if the hole comes first; pic_init_qp if there is no previous picture).  By
+ *   8.4.1.1 every vector of such a slice is (0, 0) with ref_idx 0: a copy from the newest reference picture, loop-filtered or not
+ *   exactly as the standard says for that slice.  The host writes the per-macroblock arrays for those macroblocks and they go through
+ *   the step's ordinary launches: a partly received picture costs no launch.  An access unit with slices none of which is usable
+ *   yields got_picture = 0 and counts as a lost picture; so does an IDR picture with a hole (a P slice cannot stand in one).  A slice
+ *   that names a parameter set the stream has not delivered, and whatever is wrong outside slice NAL units, is refused as in strict
+ *   mode; a refused stream joins again (below) with its next picture.
+ *   Missing reference pictures.  g = (frame_num - PrevRefFrameNum - 1) mod MaxFrameNum > 0: each of the g missing pictures stands for
+ *   an all-skip picture, a copy of the newest held picture.  Nothing is output for them and no step is run: the reference list entry of
+ *   age a (the missing pictures counted) means the held picture of real age max(0, a - g), and min(held + g, max_num_ref_frames)
+ *   pictures are held afterwards.  A P picture behind a lost IDR picture falls under the same rule; lost non-reference pictures leave
+ *   no gap.
+ *   Joining.  A concealing stream that holds parameter sets (fed as an access unit of SPS + PPS, which decode accepts with
+ *   got_picture = 0) and no reference picture decodes a picture that is no IDR picture against reference pictures whose samples are
+ *   all 128, Y, U and V, and holds max_num_ref_frames of them.  A group without a coded size takes that picture's.  The grey pictures
+ *   are written by one store-only launch (media_amd/csrc/k_dec_ring.h) per step for all its joining streams, ahead of reconstruction:
+ *   mi355x_h264_dec_group_last_step out[2] is one higher in such a step and in no other.
+ *
+ * The damage map: a byte per macroblock of the last picture, raster order; bit 0 TAINTED = its samples may differ from the lossless
+ * decode, bit 1 CONCEALED = it was filled in in this picture.  The rules are conservative (a clean macroblock IS exact; a tainted one
+ * may be) and work on whole macroblocks (media_amd/csrc/dec_loss.h):
+ *   a concealed macroblock is tainted; every macroblock of a grey or stand-in picture is tainted; I_PCM is clean;
+ *   an inter partition taints its macroblock if a tainted macroblock of the picture it refers to overlaps the rectangle it reads -
+ *   the block plus the six-tap margins (2 before, 3 behind) where the vector component is fractional (8.4.2.2.1), the chroma block
+ *   plus one sample where it has a fraction (8.4.2.2.2), clamped to the picture;
+ *   an intra macroblock is tainted if a neighbour A, B, C or D that its prediction may read - in its slice, and intra where
+ *   constrained_intra_pred_flag says so - is tainted;
+ *   then, in decoding order, a filtered left or top macroblock edge taints both its macroblocks if either is tainted:
+ *   disable_deblocking_filter_idc 1 filters none, 2 none across a slice edge;
+ *   an IDR picture whose slices were all received is therefore clean.
+ * mi355x_h264_dec_damage out[6]: [0] tainted macroblocks of the last picture (0: it is exact), [1] macroblocks concealed in it, [2]
+ * reference pictures stood in for before it (g), [3] recovery_frame_cnt of a recovery point SEI (payload type 6) in its access unit,
+ * else -1 (read in both modes; a damaged SEI never refuses a stream), [4] pictures decoded since the stream's last loss, join or
+ * refusal (the picture of the loss counts 0), [5] 1 = the stream joined without an IDR picture and has not been clean since.
+ * mi355x_h264_dec_damage_map: the map into dst[cap], returns its bytes (E_ARG: no picture yet, cap too small).  A strict stream
+ * reports a clean picture.  One exception keeps the report sound across a change of mode: a stream that has decoded in conceal mode
+ * keeps its maps going after it is set to strict again (its reference pictures may still be tainted), and both calls go on reporting
+ * them, until its group's coded size changes.  An access unit with more than 32 damaged slices is refused as in strict mode. */
+#define MI355X_H264_LOSS_STRICT 0
+#define MI355X_H264_LOSS_CONCEAL 1
+int mi355x_h264_dec_set_loss_mode(mi355x_h264_decoder *dec, int mode);
+int mi355x_h264_dec_damage(const mi355x_h264_decoder *dec, int32_t out[6]);
+int64_t mi355x_h264_dec_damage_map(const mi355x_h264_decoder *dec, uint8_t *dst, size_t cap);
+int mi355x_h264_dec_group_set_loss_mode(mi355x_h264_dec_group *g, int stream, int mode);
+int mi355x_h264_dec_group_damage(const mi355x_h264_dec_group *g, int stream, int32_t out[6]);
+int64_t mi355x_h264_dec_group_damage_map(const mi355x_h264_dec_group *g, int stream, uint8_t *dst, size_t cap);
+
 /* ---- test / measurement hooks ---- */
 int64_t mi355x_h264_dec_debug_plane(mi355x_h264_decoder *dec, int plane, void *dst, size_t cap);   /* coded-size plane 0..2 (never resampled) */
 int mi355x_h264_dec_timing(const mi355x_h264_decoder *dec, uint64_t *pictures, double *parse_ms, double *gpu_ms);
@@ -225,6 +286,11 @@ int mi355x_h264_parser_info(const mi355x_h264_parser *p, int32_t *out, int n);
  * 7 neighbour availability (1 B: bits 0..3 the left, above, above-right, above-left macroblock lies in this slice and was decoded
  *   before; bits 4..7 it may also be used for intra prediction: constrained_intra_pred_flag) */
 int64_t mi355x_h264_parser_read(const mi355x_h264_parser *p, int what, void *dst, size_t cap);
+/* the parser's half of the loss mode (above): in MI355X_H264_LOSS_CONCEAL parse fills holes, takes frame_num gaps and joins in;
+ * parser_read what = 8 then gives 1 B / macroblock, 1 = filled in.  parser_loss out[5] for the last access unit: macroblocks filled in,
+ * g, 1 = the picture joined, recovery_frame_cnt or -1 (both modes), 1 = it held slices but no usable picture (parse returned 0) */
+int mi355x_h264_parser_set_loss_mode(mi355x_h264_parser *p, int mode);
+int mi355x_h264_parser_loss(const mi355x_h264_parser *p, int32_t out[5]);
 /* out[8] of mi355x_h264_dec_colour for the sequence parameter set the last slice referred to (before the first: set 0, absent
  * fields); with n >= 10 also out[8] 1 = the set has a VUI that was read whole and in range, out[9] max_dec_frame_buffering or -1.
  * Returns the number of values written, or -1 */

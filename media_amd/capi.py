@@ -46,6 +46,9 @@ EXPORTS = [
     "mi355x_h264_dec_set_output_size", "mi355x_h264_dec_output_size", "mi355x_h264_dec_group_set_output_size", "mi355x_h264_dec_group_output_size",
     "mi355x_h264_set_temporal_layers", "mi355x_h264_last_temporal_id", "mi355x_h264_stream_last_temporal_id",
     "mi355x_h264_set_intra_refresh", "mi355x_h264_last_refresh_band", "mi355x_h264_stream_last_refresh_band",
+    "mi355x_h264_dec_set_loss_mode", "mi355x_h264_dec_damage", "mi355x_h264_dec_damage_map",
+    "mi355x_h264_dec_group_set_loss_mode", "mi355x_h264_dec_group_damage", "mi355x_h264_dec_group_damage_map",
+    "mi355x_h264_parser_set_loss_mode", "mi355x_h264_parser_loss",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*

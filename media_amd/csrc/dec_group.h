@@ -28,6 +28,16 @@ struct DecGroupStream {
     h264dec::Vui vui;    // of the sequence parameter set its last decoded picture was coded under (mi355x_h264_dec_colour)
     int rgba_override = -1;   // mi355x_h264_dec_set_rgba_colour: the variant RGBA output applies whatever the stream says; -1: follow the stream
     int out_w = 0, out_h = 0; // mi355x_h264_dec_group_set_output_size: the size its pictures are delivered at; 0, 0: their own
+    // loss mode (include/mi355x_h264_dec.h, "loss mode"; the arithmetic: dec_loss.h).  0: strict, nothing below is touched but `since`
+    // - unless the stream HAS concealed (taint is not empty): the maps then go on in strict mode too, until the geometry goes
+    int loss = 0;
+    bool virt = false;        // its reference pictures are the ring slots of `refs` (a gap or a join since the last IDR picture);
+                              // false: the ring's plain rotation, age a in slot cur - 1 - a
+    dec_loss::RefSlots refs;
+    std::vector<uint8_t> taint;   // [ring slot][macroblock]: the damage maps, made with the first picture decoded in conceal mode
+    int tainted = 0, concealed = 0, gap = 0, recovery = -1;   // of its last picture (mi355x_h264_dec_damage out[0..3])
+    int64_t since = 0;        // pictures decoded since its last loss, join or refusal
+    bool joined = false;      // joined without an IDR picture and not clean since
     // the step in hand
     const uint8_t* au = nullptr;
     size_t len = 0;
@@ -95,7 +105,40 @@ int env_int(const char* name, int lo, int hi, int dflt)
     return std::min(hi, std::max(lo, atoi(v)));
 }
 
-void dg_drop_refs(DecGroupStream& s) { s.have_refs = 0; s.parser.lose_refs(); }
+void dg_drop_refs(DecGroupStream& s) { s.have_refs = 0; s.since = 0; s.parser.lose_refs(); }
+
+// RefPicList0 entry r of the picture in hand as a ring slot, and whether that entry is a stand-in picture (dec_loss.h)
+int dg_ref_age(const DecGroupStream& s, const h264dec::Picture& pic, int r)
+{
+    return std::min(r < pic.num_ref_active ? pic.ref_age[r] : r, std::max(0, s.have_refs - 1));
+}
+int dg_ref_slot(const DecGroupStream& s, const h264dec::Picture& pic, int r, int nbuf)
+{
+    const int age = dg_ref_age(s, pic, r);
+    return s.virt ? s.refs.slot[age] : (s.cur + nbuf - 1 - age) % nbuf;
+}
+
+// the damage map of the picture in hand into the slot it is written to, and the stream's report (conceal mode only)
+void dg_damage(DecGroupStream& s, const h264dec::Picture& pic, int nbuf)
+{
+    const size_t nmb = (size_t)pic.mbw * pic.mbh;
+    if (s.taint.size() != nmb * nbuf) s.taint.assign(nmb * nbuf, 0);
+    dec_loss::TaintPic t;
+    t.mbw = pic.mbw; t.mbh = pic.mbh;
+    t.type = &pic.mb[0].type; t.type_stride = sizeof(h264dec::MbRec);
+    t.mv4 = pic.mv4.data(); t.refq = pic.refq.data(); t.avail = pic.mbavail.data();
+    t.concealed = pic.concealed.empty() ? nullptr : pic.concealed.data();
+    t.deblock_idc = pic.deblock_idc;
+    for (int r = 0; r < 3; r++) {
+        const bool standin = s.have_refs < 1 || (s.virt && s.refs.standin[dg_ref_age(s, pic, r)]);
+        t.ref[r] = standin ? nullptr : s.taint.data() + (size_t)dg_ref_slot(s, pic, r, nbuf) * nmb;
+    }
+    s.tainted = dec_loss::taint_picture(t, s.taint.data() + (size_t)s.cur * nmb, &s.concealed);
+    s.gap = pic.gap;
+    if (pic.joined) s.joined = true;
+    if (s.tainted == 0) s.joined = false;
+    if (pic.joined || pic.gap > 0 || s.concealed > 0) s.since = -1;   // (the picture of a loss counts 0: dg_step adds one)
+}
 
 // The variant of the RGBA conversion a stream's pictures get (k_dec_out.h, DecOutPos.colour): the override if there is one, else
 // what the stream describes when its matrix_coefficients are 1 (BT.709), 5 or 6 (both have the BT.601 numbers); every other
@@ -214,7 +257,7 @@ int dg_drop_geometry(mi355x_h264_dec_group* g)
     HIPCHK(g->err, hipStreamSynchronize(g->sync.st));
     g->sched.in_flight[0] = g->sched.in_flight[1] = false;
     dg_free_geometry(g);
-    for (int i = 0; i < g->nstreams; i++) { dg_drop_refs(g->st[i]); g->st[i].cur = 0; g->st[i].last = -1; }
+    for (int i = 0; i < g->nstreams; i++) { dg_drop_refs(g->st[i]); g->st[i].cur = 0; g->st[i].last = -1; g->st[i].virt = false; g->st[i].taint.clear(); }
     return MI355X_H264_OK;
 }
 
@@ -294,12 +337,12 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
     const bool outp = g->out.armed;
     const int oset = g->out.count ? g->out.cur ^ 1 : 0;
     size_t obytes = 0;
-    bool any_inter = false, any_intra = false, any_plain = false, any_bs4 = false;
+    bool any_inter = false, any_intra = false, any_plain = false, any_bs4 = false, any_join = false;
     size_t nbig = 0;
     for (int j = 0; j < njobs; j++) {
         const int i = jobs[j];
         DecGroupStream& s = g->st[i];
-        if (s.prc == 0) continue;
+        if (s.prc == 0) { if (s.parser.lost()) s.since = 0; continue; }   // (conceal mode: a picture none of whose slices could be used)
         if (s.prc == -2) { snprintf(s.err, sizeof(s.err), "out of host memory while parsing the access unit"); dg_drop_refs(s); rc[i] = MI355X_H264_E_NOMEM; continue; }
         if (s.prc < 0) { snprintf(s.err, sizeof(s.err), "%s", s.parser.error().c_str()); dg_drop_refs(s); rc[i] = MI355X_H264_E_STREAM; continue; }
         const h264dec::Picture& pic = s.parser.picture();
@@ -311,7 +354,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             }
         }
         if (!g->store.made()) {
-            if (!pic.idr) { rc[i] = dg_stream_fail(s, "the stream must start with an IDR picture"); continue; }
+            if (!pic.idr && !(s.loss && pic.joined)) { rc[i] = dg_stream_fail(s, "the stream must start with an IDR picture"); continue; }
             if (const int crc = dg_create_geometry(g, pic.mbw, pic.mbh)) {
                 for (int jj = 0; jj < njobs; jj++) dg_drop_refs(g->st[jobs[jj]]);
                 return crc;
@@ -328,7 +371,22 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
             rc[i] = dg_stream_fail(s, "coded size %dx%d differs from the group's %dx%d", 16 * pic.mbw, 16 * pic.mbh, ps->cw, ps->ch);
             continue;
         }
-        if (pic.idr) s.have_refs = 0;
+        if (pic.idr) { s.have_refs = 0; s.virt = false; }
+        uint32_t w6 = 0;
+        if (s.loss && !pic.idr) {
+            const int cap = std::min(std::max(1, sps.max_refs), ps->nbuf - 1);
+            if (pic.joined) {
+                // a join: every reference picture is ONE grey picture, in the slot behind the one being written (k_dec_ring.h makes it)
+                const int grey = (s.cur + ps->nbuf - 1) % ps->nbuf;
+                s.refs.join(grey); s.virt = true; s.have_refs = cap;
+                w6 = 1u | (1u << (4 + grey));
+            } else if (pic.gap > 0 && s.have_refs > 0) {
+                // a frame_num gap: the missing pictures are copies of the newest held picture; no step is run for them
+                if (!s.virt) { s.refs.from_ring(s.cur, s.have_refs, ps->nbuf); s.virt = true; }
+                s.refs.gap(pic.gap);
+                s.have_refs = dec_loss::refs_after_gap(s.have_refs, pic.gap, cap);
+            }
+        }
         if (pic.has_inter && (s.have_refs < 1 || pic.num_ref_active > s.have_refs)) {
             rc[i] = dg_stream_fail(s, "a P picture refers to %d reference pictures, %d are held", pic.num_ref_active, s.have_refs);
             continue;
@@ -351,8 +409,7 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         uint32_t w0 = (uint32_t)i | ((uint32_t)s.cur << 8) | ((uint32_t)std::max(1, s.have_refs) << 16);
         for (int r = 0; r < 3; r++) {
             // RefPicList0 entry r = the reference picture decoded ref_age[r] + 1 reference pictures ago (ring slot cur - 1 - age)
-            const int age = std::min(r < pic.num_ref_active ? pic.ref_age[r] : r, std::max(0, s.have_refs - 1));
-            w0 |= (uint32_t)((s.cur + ps->nbuf - 1 - age) % ps->nbuf) << (10 + 2 * r);
+            w0 |= (uint32_t)dg_ref_slot(s, pic, r, ps->nbuf) << (10 + 2 * r);
         }
         w0 |= (pic.has_inter ? 1u << 24 : 0u) | (pic.has_intra ? 1u << 25 : 0u) | (filtered ? 1u << 26 : 0u) | (pic.deblock_idc == 0 ? 1u << 27 : 0u);
         T.w[0] = w0;
@@ -365,6 +422,12 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         const int frows = (pic.deblock_idc == 0 || pic.slice_rows < 0) ? ps->mbh : rows;
         T.w[2] = (uint32_t)rows; T.w[3] = recip32(rows);
         T.w[4] = (uint32_t)frows; T.w[5] = recip32(frows);
+        T.w[6] = w6;
+        any_join |= w6 != 0;   // (only now: a joining picture that was refused above makes no launch)
+        s.recovery = pic.recovery;
+        // the maps go on while they exist: a stream that concealed once and is strict again still refers to what it concealed
+        if (s.loss || !s.taint.empty()) dg_damage(s, pic, ps->nbuf);
+        else { s.tainted = s.concealed = s.gap = 0; s.joined = false; }
         any_inter |= pic.has_inter; any_intra |= pic.has_intra;
         if (filtered) { if (pic.has_intra) any_bs4 = true; else any_plain = true; }
         nbig += pic.big.size();
@@ -434,6 +497,14 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
 
     const dim3 wave(64);
     const unsigned NP = (unsigned)npos;
+    if (any_join) {   // the grey reference pictures of the positions that join, ahead of everything that reads them
+        DecRingFill F{};
+        for (int p = 0; p < 3; p++) F.base[p] = ps->d_plane_base[p];
+        F.st_y = ps->st_y; F.st_c = ps->st_c; F.st_ring_y = ps->st_ring_y; F.st_ring_c = ps->st_ring_c;
+        F.vec_y = (unsigned)(nmb * 16); F.nbuf = ps->nbuf;
+        hipLaunchKernelGGL(k_dec_ring_fill, dim3((F.vec_y + 255) / 256, 3, NP), dim3(256), 0, st, F, d_tab);
+        launches++;
+    }
     {
         const int words = (int)(nmb * (LV_STRIDE / 4));
         hipLaunchKernelGGL(k_dec_widen_pos, dim3((words + 255) / 256, NP), dim3(256), 0, st, (const uint32_t*)g->d_arr[DG_LV8], (const MbInfo*)ps->d_mb, ps->d_levels, (int)nmb,
@@ -501,10 +572,15 @@ int dg_step(mi355x_h264_dec_group* g, const uint8_t* const* aus, const size_t* l
         s.last = s.cur;
         s.last_serial = g->step_serial;
         s.parser.commit();
-        if (is_ref) {   // sliding window (8.2.5.3)
+        if (is_ref && !s.virt) {   // sliding window (8.2.5.3)
             s.cur = (s.cur + 1) % ps->nbuf;
             s.have_refs = std::min(s.have_refs + 1, std::min(s.max_refs, ps->nbuf - 1));
+        } else if (is_ref) {       // the same window over the list of slots: the next picture goes to a slot no held picture lies in
+            s.refs.push(s.cur, false);
+            s.have_refs = std::min(s.have_refs + 1, std::min(s.max_refs, ps->nbuf - 1));
+            s.cur = s.refs.next_free(s.cur, s.have_refs, ps->nbuf);
         }
+        s.since++;
         s.pictures++;
         got[i] = 1;
     }

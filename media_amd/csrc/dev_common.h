@@ -249,6 +249,8 @@ __device__ __forceinline__ int batch_item(const uint32_t* itemtab, int pos)
 //   w[1]  four signed bytes: chroma_qp_index_offset, second_chroma_qp_index_offset, FilterOffsetA, FilterOffsetB
 //   w[2], w[3]  SliceRows of the intra wavefront (bands of whole rows, else the picture's height)
 //   w[4], w[5]  SliceRows of the loop filter (the picture's height with idc 0 or slices that are no bands)
+//   w[6]  conceal mode (k_dec_ring.h): bit 0 the position joins without an IDR picture, bits 4..7 the ring slots of its item that
+//         k_dec_ring_fill makes grey ahead of reconstruction; 0 for every other position.  w[7] is not used
 struct DecPos { uint32_t w[8]; };
 struct DecPosRef {
     int item, cur, ref[3], nref;

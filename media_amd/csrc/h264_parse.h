@@ -17,6 +17,9 @@
 // slices of any shape in raster order (bands of whole rows decode as independent wavefronts); disable_deblocking_filter_idc
 // 0 / 1 / 2 (one value per picture).
 // Anything else is refused with a message naming the syntax element (never decoded wrongly).
+// Conceal mode (set_conceal; include/mi355x_h264_dec.h, "loss mode"; the arithmetic: dec_loss.h) is opt-in: macroblocks no usable
+// slice covers are parsed as if an all-P_Skip slice had arrived for them, a frame_num gap enters the list of reference pictures, and
+// a P picture that finds none held joins.  Without it every refusal and message is what it was.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -26,6 +29,7 @@
 #include <string>
 #include <vector>
 #include "h264_vlc_tables.h"
+#include "dec_loss.h"
 
 namespace h264dec {
 
@@ -212,6 +216,12 @@ struct Picture {
     std::vector<int8_t> levels8;
     struct Big { uint32_t idx; int32_t val; };
     std::vector<Big> big;
+    // conceal mode (Parser::set_conceal; include/mi355x_h264_dec.h, "loss mode") - all of it at these values in strict mode
+    std::vector<uint8_t> concealed;   // per macroblock, 1: no received slice covered it, it was filled in as P_Skip (empty in strict mode)
+    int nconcealed = 0;               // how many
+    int gap = 0;                      // reference pictures missing in front of this picture (frame_num gap)
+    bool joined = false;              // no reference picture was held: the picture refers to grey pictures
+    int recovery = -1;                // recovery_frame_cnt of a recovery point SEI in the access unit (both modes), else -1
 };
 
 class Parser {
@@ -219,6 +229,12 @@ public:
     const std::string& error() const { return err_; }
     void set_error(const std::string& e) { err_ = e; }
     const Picture& picture() const { return pic_; }
+    // conceal mode: what is missing from a picture is parsed as if an all-P_Skip slice had arrived in its place, a frame_num gap and a
+    // first picture that is no IDR picture are taken in (Picture::gap, ::joined) instead of being refused.  lost(): the last access unit
+    // held slices but none was usable (or it was an IDR picture with a hole, which nothing can fill): parse returned 0
+    void set_conceal(bool on) { conceal_ = on; }
+    bool conceal() const { return conceal_; }
+    bool lost() const { return lost_; }
     const Sps& sps() const { return sps_[active_sps_]; }
 
     // one access unit (Annex B).  Returns 1: a picture is ready in picture(); 0: no slice in it (parameter sets only); -1: error().
@@ -236,6 +252,7 @@ public:
     void commit()
     {
         if (pic_.idr) dpb_fn_.clear();
+        prev_pic_qp_ = pic_last_qp_;
         if (pic_.is_ref) {
             dpb_fn_.insert(dpb_fn_.begin(), cur_frame_num_);
             const size_t cap = (size_t)(sps().max_refs > 0 ? sps().max_refs : 1);
@@ -246,11 +263,32 @@ public:
     void lose_refs() { dpb_fn_.clear(); prev_ref_fn_ = -1; }
 
 private:
+    // conceal mode: a slice NAL unit that does not parse is dropped WHOLE - the access unit is scanned again without it, from the
+    // list of reference pictures as it stood, so that nothing the damaged slice wrote stays - and its extent becomes a hole
     int parse_access_unit_(const uint8_t* au, size_t len)
+    {
+        lost_ = false;
+        dropped_.clear();
+        if (!conceal_) return scan_access_unit(au, len);
+        const std::vector<int> dpb = dpb_fn_;
+        const int prev = prev_ref_fn_;
+        for (;;) {
+            const int rc = scan_access_unit(au, len);
+            if (rc != -3) return rc;
+            // (every drop costs a scan of the access unit: an access unit of many broken slices is not worth that, and is refused)
+            if (dropped_.size() > MAX_DROPS) return fail("more than %d damaged slices in one access unit", (int)MAX_DROPS);
+            dpb_fn_ = dpb;
+            prev_ref_fn_ = prev;
+        }
+    }
+    // 1, 0, -1 as parse_access_unit; -3: a slice was put on the list of dropped NAL units, scan again
+    int scan_access_unit(const uint8_t* au, size_t len)
     {
         err_.clear();
         bool have_pic = false;
         int next_mb = 0;
+        nal_index_ = 0; drop_nal_ = -1; fatal_ = false; saw_slice_ = false; idr_hole_ = false;
+        au_gap_ = 0; au_joined_ = false; au_recovery_ = -1; au_last_qp_ = -1; last_slice_nal_ = -1; last_slice_first_ = -1;
         size_t i = 0;
         while (i + 3 < len) {
             // next start code
@@ -259,11 +297,24 @@ private:
             size_t e = s;
             while (e + 2 < len && !(au[e] == 0 && au[e + 1] == 0 && (au[e + 2] == 1 || (au[e + 2] == 0 && e + 3 < len && au[e + 3] == 1)))) e++;
             if (e + 2 >= len) e = len;
-            if (s < e && !nal(au + s, e - s, have_pic, next_mb)) return -1;
+            if (s < e && !nal(au + s, e - s, have_pic, next_mb)) {
+                if (!conceal_ || fatal_ || drop_nal_ < 0) return -1;
+                dropped_.push_back(drop_nal_);
+                return -3;
+            }
+            nal_index_++;
             i = e;
         }
-        if (!have_pic) return 0;
+        if (!have_pic) { lost_ = conceal_ && saw_slice_; return 0; }
+        if (conceal_) {   // what no slice covered, up to the end of the picture
+            const dec_loss::Hole h = dec_loss::hole_before(next_mb, pic_.mbw * pic_.mbh, pic_.mbw * pic_.mbh);
+            if (h.to > h.from) fill_hole(h.from, h.to);
+            next_mb = h.to;
+        }
+        if (idr_hole_) { lost_ = true; return 0; }
         if (next_mb != pic_.mbw * pic_.mbh) return fail("picture incomplete: slices cover %d of %d macroblocks", next_mb, pic_.mbw * pic_.mbh);
+        pic_.gap = au_gap_; pic_.joined = au_joined_; pic_.recovery = au_recovery_;
+        pic_last_qp_ = au_last_qp_;
         // bands of slice_rows rows only if every band start was seen (a last slice longer than the others is "any shape")
         if (pic_.slice_rows > 0 && pic_.slices != (pic_.mbh + pic_.slice_rows - 1) / pic_.slice_rows) pic_.slice_rows = -1;
         return 1;
@@ -283,6 +334,17 @@ private:
     std::vector<int> dpb_fn_;
     int cur_frame_num_ = 0;
     int prev_ref_fn_ = -1;   // frame_num of the previous reference picture (PrevRefFrameNum, 7.4.3); -1: none held
+    // conceal mode, and the scan of the access unit in hand
+    bool conceal_ = false, lost_ = false, fatal_ = false, saw_slice_ = false, idr_hole_ = false, au_joined_ = false;
+    enum { MAX_DROPS = 32 };
+    std::vector<int> dropped_;                  // NAL units (by their number in the access unit) dropped as damaged, at most MAX_DROPS + 1
+    int pic_sps_id_ = 0;                        // sequence parameter set of the picture in hand
+    int nal_index_ = 0, drop_nal_ = -1;         // the NAL unit in hand; the one to drop when it fails (the slice before it, if that overran)
+    int last_slice_nal_ = -1, last_slice_first_ = -1;
+    int au_gap_ = 0, au_recovery_ = -1;
+    int au_last_qp_ = -1;                       // slice QP of the preceding slice of this picture (received or filled in); -1: none yet
+    int pic_last_qp_ = -1, prev_pic_qp_ = -1;   // of the last slice of the picture parsed / of the previous picture taken in (commit)
+    int pic_pps_id_ = 0;                        // picture parameter set of the picture's received slices
 
     int fail(const char* fmt, int a = 0, int b = 0)
     {
@@ -294,7 +356,8 @@ private:
     bool nal(const uint8_t* p, size_t n, bool& have_pic, int& next_mb)
     {
         const int hdr = p[0], ref_idc = (hdr >> 5) & 3, type = hdr & 31;
-        if (hdr & 0x80) { fail("forbidden_zero_bit set"); return false; }
+        fatal_ = !(type == 1 || type == 5);   // (conceal mode drops damaged slices; whatever else fails refuses the access unit)
+        if (hdr & 0x80) { fatal_ = true; fail("forbidden_zero_bit set"); return false; }
         // emulation prevention (7.4.1.1): 00 00 03 -> 00 00
         rbsp_.resize(n + BitReader::PAD);
         size_t m = 0;
@@ -308,9 +371,93 @@ private:
         BitReader br(rbsp_.data(), m);
         if (type == 7) return parse_sps(br);
         if (type == 8) return parse_pps(br);
-        if (type == 1 || type == 5) return parse_slice(br, type == 5, ref_idc, have_pic, next_mb);
+        if (type == 1 || type == 5) {
+            saw_slice_ = true;
+            if (conceal_) {
+                for (const int d : dropped_) if (d == nal_index_) return true;   // a hole
+                drop_nal_ = nal_index_;
+            }
+            return parse_slice(br, type == 5, ref_idc, have_pic, next_mb);
+        }
+        if (type == 6) { parse_sei(rbsp_.data(), m); return true; }
         if (type == 2 || type == 3 || type == 4) { fail("data partitioning (nal_unit_type %d) is not supported", type); return false; }
         return true;   // SEI, AUD, end of sequence, filler ...: nothing to decode
+    }
+
+    // sei_rbsp (7.3.2.3): the recovery point message (payload type 6, D.1.7) is read for its recovery_frame_cnt; nothing here is
+    // needed to decode samples, so whatever is wrong with it is passed over
+    void parse_sei(const uint8_t* p, size_t n)
+    {
+        size_t i = 0;
+        while (i + 2 <= n) {
+            unsigned type = 0, size = 0;
+            while (i < n && p[i] == 0xFF) { type += 255; i++; }
+            if (i >= n) return;
+            type += p[i++];
+            while (i < n && p[i] == 0xFF) { size += 255; i++; }
+            if (i >= n) return;
+            size += p[i++];
+            if (size > n - i) return;
+            if (type == 6 && size > 0) {
+                uint8_t buf[8 + BitReader::PAD] = {0};
+                const size_t k = size < 8 ? size : 8;
+                memcpy(buf, p + i, k);
+                BitReader br(buf, k);
+                const unsigned cnt = br.ue();
+                if (!br.bad() && cnt < 65536u) au_recovery_ = (int)cnt;
+            }
+            i += size;
+            if (i < n && p[i] == 0x80) return;   // rbsp_trailing_bits
+        }
+    }
+
+    // ---- conceal mode ----
+    // the slice at first_mb starts here: bands of equal height (the last may be shorter): slice k starts at row k * slice_rows;
+    // anything else is "any shape"
+    void note_slice_start(int first_mb)
+    {
+        if (first_mb == 0) { pic_.slices = 1; pic_.slice_rows = 0; return; }
+        if (pic_.slices == 1 && first_mb % pic_.mbw == 0) pic_.slice_rows = first_mb / pic_.mbw;
+        if (pic_.slice_rows <= 0 || first_mb != pic_.slices * pic_.slice_rows * pic_.mbw) pic_.slice_rows = -1;
+        pic_.slices++;
+    }
+    // a P slice and no reference picture held: the stream joins here.  The list of reference pictures is what a decoder would hold
+    // that had decoded the pictures in front (frame_num - 1, - 2, ...); the decoder makes them grey pictures
+    void join_refs(const Sps& sps, int frame_num)
+    {
+        const int mask = (1 << sps.log2_max_frame_num) - 1, cap = sps.max_refs > 0 ? sps.max_refs : 1;
+        dpb_fn_.clear();
+        for (int k = 1; k <= cap; k++) dpb_fn_.push_back((frame_num - k) & mask);
+        au_joined_ = true;
+    }
+    // macroblocks [from, to) as ONE P slice that is one mb_skip_run, under the picture's parameter set, with the slice QP of the
+    // preceding slice (the last slice of the previous picture when the hole is the first thing in the picture; with no previous
+    // picture either, pic_init_qp).  By 8.4.1.1 every vector is (0, 0) with ref_idx 0: skip_mb finds that by itself, the
+    // neighbours outside the fill being in other slices
+    void fill_hole(int from, int to)
+    {
+        if (pic_.idr) { idr_hole_ = true; return; }   // (a P slice cannot stand in an IDR picture: the picture counts as lost)
+        if (from < 0 || to > (int)pic_.mb.size() || pic_.concealed.size() != pic_.mb.size()) return;   // never outside the picture's arrays
+        const Pps& pps = pps_[pic_pps_id_];
+        const Sps& sps = sps_[pic_sps_id_];
+        if (dpb_fn_.empty()) join_refs(sps, cur_frame_num_);
+        if (!pic_.num_ref_active) {
+            int list[4];
+            uint8_t none[BitReader::PAD] = {0};
+            BitReader br(none, 0);
+            pic_.num_ref_active = pps.num_ref_default < 3 ? pps.num_ref_default : 3;
+            ref_list(br, sps, cur_frame_num_, pic_.num_ref_active, false, list);
+            for (int r = 0; r < 3; r++) pic_.ref_age[r] = list[r];
+        }
+        note_slice_start(from);
+        slice_first_ = from; slice_type_ = 0; num_ref_ = pic_.num_ref_active; constrained_ = pps.constrained_intra;
+        qp_ = slice_qp_ = au_last_qp_ >= 0 ? au_last_qp_ : (prev_pic_qp_ >= 0 ? prev_pic_qp_ : pps.pic_init_qp);
+        au_last_qp_ = qp_;
+        for (int addr = from; addr < to; addr++) {
+            skip_mb(addr % pic_.mbw, addr / pic_.mbw);
+            pic_.concealed[(size_t)addr] = 1;
+        }
+        pic_.nconcealed += to - from;
     }
 
     bool parse_sps(BitReader& br)
@@ -670,11 +817,32 @@ private:
         if (st > 4) st -= 5;
         if (st != 0 && st != 2) { fail("slice_type %d (only I and P)", st); return false; }
         const unsigned pps_id = br.ue();
-        if (pps_id > 255 || !pps_[pps_id].valid || !sps_[pps_[pps_id].sps_id].valid) { fail("slice refers to a missing parameter set"); return false; }
+        if (pps_id > 255 || !pps_[pps_id].valid || !sps_[pps_[pps_id].sps_id].valid) { fatal_ = true; fail("slice refers to a missing parameter set"); return false; }
         const Pps& pps = pps_[pps_id];
+        // (conceal mode fills holes by the picture's own size: a slice under another sequence parameter set, or under one that was
+        // replaced by another size since the picture began, is damage and is dropped)
+        if (conceal_ && have_pic && (pps.sps_id != pic_sps_id_ || sps_[pps.sps_id].mbw != pic_.mbw || sps_[pps.sps_id].mbh != pic_.mbh)) {
+            fail("slice under another sequence parameter set than its picture's");
+            return false;
+        }
         active_sps_ = pps.sps_id;
         const Sps& sps = sps_[active_sps_];
         const int frame_num = (int)br.u(sps.log2_max_frame_num);
+        if (conceal_ && !idr && !br.bad()) {
+            // the first slice of the picture says whether reference pictures went missing in front of it (they enter the list as
+            // 8.2.5.2 has it, by frame_num alone); a P slice that finds no reference picture held joins
+            if (!have_pic && !dpb_fn_.empty()) {
+                const int g = dec_loss::frame_num_gap(frame_num, prev_ref_fn_, sps.log2_max_frame_num);
+                const size_t cap = (size_t)(sps.max_refs > 0 ? sps.max_refs : 1);
+                for (int k = g < 4 ? 0 : g - 4; k < g; k++) dpb_fn_.insert(dpb_fn_.begin(), (prev_ref_fn_ + 1 + k) & ((1 << sps.log2_max_frame_num) - 1));
+                if (dpb_fn_.size() > cap) dpb_fn_.resize(cap);
+                au_gap_ = g;
+                // the gap is taken in ONCE: PrevRefFrameNum is now the last stand-in's (8.2.5.2), so that a non-reference picture
+                // here, which does not move it, leaves no gap for the picture behind it to find again
+                if (g > 0) prev_ref_fn_ = (frame_num - 1) & ((1 << sps.log2_max_frame_num) - 1);
+            }
+            if (st == 0 && dpb_fn_.empty()) join_refs(sps, frame_num);
+        }
         if (idr) br.ue();               // idr_pic_id
         if (sps.poc_type == 0) {
             br.u(sps.log2_max_poc_lsb);
@@ -711,12 +879,14 @@ private:
         }
         if (br.bad() || qp < 0 || qp > 51 || idc > 2 || num_ref < 1 || num_ref > 3) { fail("slice header damaged"); return false; }
 
+        const int nmb_pic = have_pic ? pic_.mbw * pic_.mbh : sps.mbw * sps.mbh;   // (a picture keeps the size it began with)
+        if (conceal_ && first_mb >= nmb_pic) { fail("first_mb_in_slice %d past the picture", first_mb); return false; }
         if (!have_pic) {   // first slice of the picture
-            if (first_mb != 0) { fail("first slice of the access unit starts at macroblock %d", first_mb); return false; }
+            if (first_mb != 0 && !conceal_) { fail("first slice of the access unit starts at macroblock %d", first_mb); return false; }
             // 7.4.3 without gaps_in_frame_num: an IDR picture has frame_num 0, every other picture PrevRefFrameNum + 1.  Anything
             // else means a reference picture went missing between the two: predicting from the ring would use the wrong pictures
             if (idr && frame_num != 0) { fail("frame_num %d in an IDR picture", frame_num); return false; }
-            if (!idr && prev_ref_fn_ >= 0 && frame_num != ((prev_ref_fn_ + 1) & ((1 << sps.log2_max_frame_num) - 1))) {
+            if (!conceal_ && !idr && prev_ref_fn_ >= 0 && frame_num != ((prev_ref_fn_ + 1) & ((1 << sps.log2_max_frame_num) - 1))) {
                 fail("frame_num %d does not follow the previous reference picture's %d: a picture is missing", frame_num, prev_ref_fn_);
                 return false;
             }
@@ -740,13 +910,22 @@ private:
             pic_.aux.assign(n * 16, 0);
             pic_.levels8.assign(n * L_STRIDE, 0);
             pic_.big.clear();
+            pic_.gap = 0; pic_.joined = false; pic_.recovery = -1; pic_.nconcealed = 0;
+            if (conceal_) pic_.concealed.assign(n, 0); else pic_.concealed.clear();
+            pic_pps_id_ = (int)pps_id; pic_sps_id_ = pps.sps_id;
             have_pic = true;
+            const dec_loss::Hole h = dec_loss::hole_before(0, first_mb, nmb_pic);
+            if (h.to > h.from) {   // (conceal mode) the picture starts with a hole
+                pic_.slices = 0;
+                fill_hole(h.from, h.to);
+                note_slice_start(first_mb);
+            }
         } else {
-            if (first_mb != next_mb) { fail("slices out of order (first_mb_in_slice %d, expected %d)", first_mb, next_mb); return false; }
-            // bands of equal height (the last may be shorter): slice k starts at row k * slice_rows; anything else is "any shape"
-            if (pic_.slices == 1 && first_mb % pic_.mbw == 0) pic_.slice_rows = first_mb / pic_.mbw;
-            if (pic_.slice_rows <= 0 || first_mb != pic_.slices * pic_.slice_rows * pic_.mbw) pic_.slice_rows = -1;
-            pic_.slices++;
+            if (conceal_ && first_mb < next_mb && first_mb > last_slice_first_) drop_nal_ = last_slice_nal_;   // the slice before this one ran on into it
+            if (first_mb != next_mb && !(conceal_ && first_mb > next_mb)) { fail("slices out of order (first_mb_in_slice %d, expected %d)", first_mb, next_mb); return false; }
+            const dec_loss::Hole h = dec_loss::hole_before(next_mb, first_mb, nmb_pic);
+            if (h.to > h.from) fill_hole(h.from, h.to);
+            note_slice_start(first_mb);
             if (qp != pic_.qp) pic_.one_qp = false;
             if (idc != pic_.deblock_idc) { fail("disable_deblocking_filter_idc differs between slices"); return false; }
             if (oa != pic_.filter_oa || ob != pic_.filter_ob) { fail("deblocking filter offsets differ between slices"); return false; }
@@ -755,6 +934,7 @@ private:
             if (st == 0 && !pic_.num_ref_active) { pic_.num_ref_active = num_ref; for (int r = 0; r < 3; r++) pic_.ref_age[r] = list[r]; }
             else if (st == 0 && (list[0] != pic_.ref_age[0] || list[1] != pic_.ref_age[1] || list[2] != pic_.ref_age[2])) { fail("reference picture lists differ between slices"); return false; }
         }
+        drop_nal_ = nal_index_; last_slice_nal_ = nal_index_; last_slice_first_ = first_mb; au_last_qp_ = qp;
         slice_first_ = first_mb; slice_type_ = st; slice_qp_ = qp; num_ref_ = num_ref;
         qp_ = qp;   // QP_Y,PRED of the slice's first macroblock (7.4.5)
         constrained_ = pps.constrained_intra;

@@ -28,6 +28,7 @@
 #include "k_me.h"
 #include "k_tq.h"
 #include "k_dec.h"
+#include "k_dec_ring.h"
 #include "k_quality.h"
 #include "h264_parse.h"
 #include "../../include/mi355x_h264_dec.h"
@@ -819,6 +820,35 @@ int mi355x_h264_dec_group_output_size(const mi355x_h264_dec_group* g, int stream
     return MI355X_H264_OK;
 }
 
+// ---- loss mode (dec_group.h, dec_loss.h): the switch, and what the host knows about the damage in a stream's last picture ----
+int mi355x_h264_dec_group_set_loss_mode(mi355x_h264_dec_group* g, int stream, int mode)
+{
+    if (!g || stream < 0 || stream >= g->nstreams || mode < MI355X_H264_LOSS_STRICT || mode > MI355X_H264_LOSS_CONCEAL) return MI355X_H264_E_ARG;
+    DecGroupStream& s = g->st[stream];
+    s.loss = mode;
+    s.parser.set_conceal(mode == MI355X_H264_LOSS_CONCEAL);
+    return MI355X_H264_OK;
+}
+int mi355x_h264_dec_group_damage(const mi355x_h264_dec_group* g, int stream, int32_t* out)
+{
+    if (!g || !out || stream < 0 || stream >= g->nstreams) return MI355X_H264_E_ARG;
+    const DecGroupStream& s = g->st[stream];
+    const bool c = s.loss != 0 || !s.taint.empty();   // (a stream that has concealed keeps its maps, whatever its mode is now)
+    out[0] = c ? s.tainted : 0; out[1] = c ? s.concealed : 0; out[2] = c ? s.gap : 0; out[3] = s.last < 0 ? -1 : s.recovery;
+    out[4] = (int32_t)std::min<int64_t>(s.since, 0x7FFFFFFF); out[5] = c && s.joined ? 1 : 0;
+    return MI355X_H264_OK;
+}
+int64_t mi355x_h264_dec_group_damage_map(const mi355x_h264_dec_group* g, int stream, uint8_t* dst, size_t cap)
+{
+    if (!g || !dst || stream < 0 || stream >= g->nstreams || g->st[stream].last < 0) return MI355X_H264_E_ARG;
+    const DecGroupStream& s = g->st[stream];
+    const size_t nmb = (size_t)g->store.nmb;
+    if (cap < nmb) return MI355X_H264_E_ARG;
+    if (s.taint.size() == nmb * (size_t)g->store.nbuf) memcpy(dst, s.taint.data() + (size_t)s.last * nmb, nmb);
+    else memset(dst, 0, nmb);
+    return (int64_t)nmb;
+}
+
 // ---- the decoder peer (decoder.h): a group of one stream, every call forwarded with stream 0 ----
 
 int mi355x_h264_dec_create(int device, mi355x_h264_decoder** out)
@@ -884,6 +914,10 @@ int64_t mi355x_h264_dec_read(mi355x_h264_decoder* d, int layout, int row_align, 
     if (n == MI355X_H264_E_ARG && pic && out_args_ok(layout, row_align) && d->g->st[0].last >= 0 && !dg_out_size(d->g->st[0], W, H)) snprintf(d->err, sizeof(d->err), "%s", d->g->st[0].err);
     return n;
 }
+
+int mi355x_h264_dec_set_loss_mode(mi355x_h264_decoder* d, int mode) { return d ? mi355x_h264_dec_group_set_loss_mode(d->g, 0, mode) : MI355X_H264_E_ARG; }
+int mi355x_h264_dec_damage(const mi355x_h264_decoder* d, int32_t* out) { return d ? mi355x_h264_dec_group_damage(d->g, 0, out) : MI355X_H264_E_ARG; }
+int64_t mi355x_h264_dec_damage_map(const mi355x_h264_decoder* d, uint8_t* dst, size_t cap) { return d ? mi355x_h264_dec_group_damage_map(d->g, 0, dst, cap) : MI355X_H264_E_ARG; }
 
 int mi355x_h264_dec_set_output_size(mi355x_h264_decoder* d, int width, int height) { return d ? mi355x_h264_dec_group_set_output_size(d->g, 0, width, height) : MI355X_H264_E_ARG; }
 int mi355x_h264_dec_output_size(const mi355x_h264_decoder* d, int* width, int* height) { return d ? mi355x_h264_dec_group_output_size(d->g, 0, width, height) : MI355X_H264_E_ARG; }
@@ -1069,6 +1103,19 @@ int mi355x_h264_parser_info(const mi355x_h264_parser* p, int32_t* out, int n)
     memcpy(out, v, (size_t)m * sizeof(int32_t));
     return m;
 }
+int mi355x_h264_parser_set_loss_mode(mi355x_h264_parser* p, int mode)
+{
+    if (!p || mode < MI355X_H264_LOSS_STRICT || mode > MI355X_H264_LOSS_CONCEAL) return MI355X_H264_E_ARG;
+    p->p.set_conceal(mode == MI355X_H264_LOSS_CONCEAL);
+    return MI355X_H264_OK;
+}
+int mi355x_h264_parser_loss(const mi355x_h264_parser* p, int32_t* out)
+{
+    if (!p || !out) return MI355X_H264_E_ARG;
+    const h264dec::Picture& c = p->p.picture();
+    out[0] = c.nconcealed; out[1] = c.gap; out[2] = c.joined ? 1 : 0; out[3] = c.recovery; out[4] = p->p.lost() ? 1 : 0;
+    return MI355X_H264_OK;
+}
 int mi355x_h264_parser_colour(const mi355x_h264_parser* p, int32_t* out, int n)
 {
     if (!p || !out || n < 8) return -1;
@@ -1106,6 +1153,7 @@ int64_t mi355x_h264_parser_read(const mi355x_h264_parser* p, int what, void* dst
         case 5: src = c.mv4.data(); n = c.mv4.size() * sizeof(int16_t); break;
         case 6: src = c.refq.data(); n = c.refq.size(); break;
         case 7: src = c.mbavail.data(); n = c.mbavail.size(); break;
+        case 8: src = c.concealed.data(); n = c.concealed.size(); break;
         default: return -1;
     }
     if (cap < n) return -1;

@@ -90,8 +90,54 @@ def _bind():
         L.mi355x_h264_dec_output_size.argtypes = [vp, ip, ip]
         L.mi355x_h264_dec_group_set_output_size.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.mi355x_h264_dec_group_output_size.argtypes = [vp, C.c_int, ip, ip]
+    if hasattr(L, "mi355x_h264_dec_set_loss_mode"):   # (likewise: an earlier build is strict)
+        i6 = C.POINTER(C.c_int32)
+        L.mi355x_h264_dec_set_loss_mode.argtypes = [vp, C.c_int]
+        L.mi355x_h264_dec_damage.argtypes = [vp, i6]
+        L.mi355x_h264_dec_damage_map.argtypes = [vp, vp, sz]; L.mi355x_h264_dec_damage_map.restype = C.c_int64
+        L.mi355x_h264_dec_group_set_loss_mode.argtypes = [vp, C.c_int, C.c_int]
+        L.mi355x_h264_dec_group_damage.argtypes = [vp, C.c_int, i6]
+        L.mi355x_h264_dec_group_damage_map.argtypes = [vp, C.c_int, vp, sz]; L.mi355x_h264_dec_group_damage_map.restype = C.c_int64
+        L.mi355x_h264_parser_set_loss_mode.argtypes = [vp, C.c_int]
+        L.mi355x_h264_parser_loss.argtypes = [vp, i6]
     _bound = True
     return L
+
+
+LOSS_STRICT, LOSS_CONCEAL = 0, 1   # MI355X_H264_LOSS_*
+TAINTED, CONCEALED = 1, 2          # the bits of a damage-map byte
+DAMAGE = ("tainted", "concealed", "gap", "recovery_frame_cnt", "since_loss", "joined")   # out[6] of mi355x_h264_dec_damage
+
+
+def _loss_mode(mode):
+    m = {"strict": LOSS_STRICT, "conceal": LOSS_CONCEAL}.get(mode, mode)
+    if isinstance(m, str):
+        raise ValueError("loss = %r: \"strict\" | \"conceal\"" % (mode,))
+    return int(m)
+
+
+def _set_loss_mode(fn, mode, *args):
+    rc = fn(*args, _loss_mode(mode))
+    if rc != 0:
+        err = EncoderError("set_loss_mode(%r) -> %d" % (mode, rc))
+        err.rc = rc
+        raise err
+
+
+def _damage(fn, *args):
+    v = (C.c_int32 * 6)()
+    rc = fn(*args, v)
+    if rc != 0:
+        raise EncoderError("damage -> %d" % rc)
+    return dict(zip(DAMAGE, list(v)))
+
+
+def _damage_map(fn, mbw, mbh, *args):
+    a = np.empty((mbh, mbw), np.uint8)
+    n = fn(*args, a.ctypes.data, a.nbytes)
+    if n != a.nbytes:
+        raise EncoderError("damage_map -> %d" % n)
+    return a
 
 
 def _set_output_size(fn, w, h, *args):
@@ -128,12 +174,27 @@ class StreamError(EncoderError):
 
 
 class Decoder:
-    def __init__(self, device=0):
+    def __init__(self, device=0, loss="strict"):
         L = _bind()
         self.h = C.c_void_p()
         rc = L.mi355x_h264_dec_create(device, C.byref(self.h))
         if rc != 0:
             raise EncoderError("mi355x_h264_dec_create -> %d (no HIP device? there is no CPU reconstruction path)" % rc)
+        if _loss_mode(loss) != LOSS_STRICT:
+            self.set_loss_mode(loss)
+
+    def set_loss_mode(self, mode):
+        """"strict" (refuse what is damaged or missing, wait for an IDR picture) or "conceal" (include/mi355x_h264_dec.h, "loss mode")"""
+        _set_loss_mode(lib().mi355x_h264_dec_set_loss_mode, mode, self.h)
+
+    def damage(self):
+        """what is known about the last picture: a dict of DAMAGE (tainted == 0: the picture is exact)"""
+        return _damage(lib().mi355x_h264_dec_damage, self.h)
+
+    def damage_map(self):
+        """(mbh, mbw) bytes of the last picture: TAINTED | CONCEALED per macroblock"""
+        _, _, cw, ch = self.info()
+        return _damage_map(lib().mi355x_h264_dec_damage_map, cw // 16, ch // 16, self.h)
 
     def close(self):
         if self.h:
@@ -248,13 +309,32 @@ class DecoderGroup:
     STEP = ("serial", "pictures", "launches", "transfers", "parse_threads", "parse_us", "launch_us", "output_launches", "output_transfers",
             "read_launches", "read_transfers", "device_bytes", "pinned_bytes")
 
-    def __init__(self, streams, device=0):
+    def __init__(self, streams, device=0, loss=None):
+        """loss: None (every stream strict), one mode for all streams, or a list with one mode per stream"""
         L = _bind()
         self.h = C.c_void_p()
         self.streams = streams
         rc = L.mi355x_h264_dec_group_create(device, streams, C.byref(self.h))
         if rc != 0:
             raise EncoderError("mi355x_h264_dec_group_create(%d streams) -> %d" % (streams, rc))
+        if loss is not None:
+            modes = [loss] * streams if isinstance(loss, (str, int)) else list(loss)
+            if len(modes) != streams:
+                raise EncoderError("loss: %d modes for %d streams" % (len(modes), streams))
+            for i, m in enumerate(modes):
+                if _loss_mode(m) != LOSS_STRICT:
+                    self.set_loss_mode(i, m)
+
+    def set_loss_mode(self, stream, mode):
+        """as Decoder.set_loss_mode, for one stream of the group"""
+        _set_loss_mode(lib().mi355x_h264_dec_group_set_loss_mode, mode, self.h, stream)
+
+    def damage(self, stream):
+        return _damage(lib().mi355x_h264_dec_group_damage, self.h, stream)
+
+    def damage_map(self, stream):
+        _, _, cw, ch = self.info(stream)
+        return _damage_map(lib().mi355x_h264_dec_group_damage_map, cw // 16, ch // 16, self.h, stream)
 
     def close(self):
         if self.h:
@@ -415,6 +495,23 @@ class Parser:
             self.close()
         except Exception:
             pass
+
+    LOSS = ("concealed", "gap", "joined", "recovery_frame_cnt", "lost")
+
+    def set_loss_mode(self, mode):
+        _set_loss_mode(lib().mi355x_h264_parser_set_loss_mode, mode, self.h)
+
+    def loss(self):
+        """what the conceal mode did to the last access unit (mi355x_h264_parser_loss): a dict of LOSS"""
+        v = (C.c_int32 * 5)()
+        if lib().mi355x_h264_parser_loss(self.h, v) != 0:
+            raise EncoderError("parser_loss failed")
+        return dict(zip(self.LOSS, list(v)))
+
+    def concealed(self):
+        """1 per macroblock of the last picture that was filled in (conceal mode)"""
+        i = self.info()
+        return self._read(8, np.empty(i["mbw"] * i["mbh"], np.uint8))
 
     def parse(self, au):
         buf = (C.c_uint8 * len(au)).from_buffer_copy(au)

@@ -75,6 +75,32 @@ int VideoDecoderMI355X::ParseOutputSize(const std::string &width, const std::str
     return 1;
 }
 
+int VideoDecoderMI355X::ParseLossMode(const std::string &value, int32_t *mode)
+{
+    if (value.empty()) {
+        return 0;
+    }
+    if (value != "0" && value != "1") {
+        return -1;
+    }
+    *mode = value == "1" ? MI355X_H264_LOSS_CONCEAL : MI355X_H264_LOSS_STRICT;
+    return 1;
+}
+
+void VideoDecoderMI355X::ReadLossModeKey()
+{
+    const std::string v = GetStrEncParam("persist.vmi.video.decode.lossmode");
+    m_lossMode = MI355X_H264_LOSS_STRICT;
+    m_inexact = false;
+    if (ParseLossMode(v, &m_lossMode) < 0) {
+        WARN("lossmode '%s' rejected (0: strict, 1: conceal): the decoder stays strict", v.c_str());
+        m_lossMode = MI355X_H264_LOSS_STRICT;
+    } else if (m_lossMode == MI355X_H264_LOSS_CONCEAL) {
+        INFO("lost slices and pictures are concealed; the decoder joins at any picture");
+    }
+    (void) mi355x_h264_dec_set_loss_mode(m_engine, m_lossMode);
+}
+
 void VideoDecoderMI355X::ReadOutputSizeKeys()
 {
     const std::string w = GetStrEncParam("persist.vmi.video.decode.outwidth"), h = GetStrEncParam("persist.vmi.video.decode.outheight");
@@ -165,6 +191,7 @@ DecoderRetCode VideoDecoderMI355X::StartDecoder()
     m_colourChanges = 0;
     m_frameWidth = m_frameHeight = 0;
     ReadOutputSizeKeys();
+    ReadLossModeKey();
     INFO("start decoder success");
     return VIDEO_DECODER_SUCCESS;
 }
@@ -214,6 +241,14 @@ DecoderRetCode VideoDecoderMI355X::SendStreamData(uint8_t *buffer, uint32_t fill
             m_colourChanges++;
             INFO("stream colour: description %d matrix %d full_range %d primaries %d transfer %d chroma_loc %d fps %d reorder %d", colour[0],
                  colour[1], colour[2], colour[3], colour[4], colour[5], colour[6], colour[7]);
+        }
+        if (m_lossMode == MI355X_H264_LOSS_CONCEAL) {
+            int32_t damage[6] = {0, 0, 0, -1, 0, 0};
+            (void) mi355x_h264_dec_damage(m_engine, damage);
+            if (damage[0] == 0 && m_inexact) {
+                INFO("pictures are exact again");
+            }
+            m_inexact = damage[0] != 0;
         }
         int64_t got_bytes;
         if (m_outFormat == PIXEL_FORMAT_RGBA_8888) {

@@ -40,6 +40,10 @@ public:
     // (include/mi355x_h264_dec.h, "output size").  Both decimal, even and 2..4096: 1 and the size; neither set: 0; anything else
     // (one key alone, junk): -1, and the caller keeps the native size.  Parsed as VideoEncoderMI355X parses .srcwidth / .srcheight
     static int ParseOutputSize(const std::string &width, const std::string &height, int32_t *outWidth, int32_t *outHeight);
+    // extension key persist.vmi.video.decode.lossmode: 0 strict (the default), 1 conceal (include/mi355x_h264_dec.h, "loss mode").
+    // Returns 1 (and the mode), 0 (not set) or -1 (rejected: anything but "0" and "1")
+    static int ParseLossMode(const std::string &value, int32_t *mode);
+    bool Inexact() const { return m_inexact; }   // conceal mode: the last picture may differ from the lossless decode
 
 private:
     static constexpr uint32_t kDefaultWidth = 1280, kDefaultHeight = 720;   // the reference adapter's defaults (VideoDecoderNetint.h:34-35)
@@ -56,9 +60,12 @@ private:
     int32_t m_colour[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t m_colourChanges = 0;
     uint32_t m_frameWidth = 0, m_frameHeight = 0;   // of the waiting picture as delivered
+    int32_t m_lossMode = 0;                        // the loss mode asked for with .lossmode (read by StartDecoder)
+    bool m_inexact = false;                        // the last picture had tainted macroblocks: one INFO line when that ends
     int32_t m_outWidth = 0, m_outHeight = 0;       // > 0: the size asked for with .outwidth / .outheight (read by StartDecoder)
     uint32_t m_nativeWarnWidth = 0, m_nativeWarnHeight = 0;   // the native size the last "cannot be resampled" WARN line named
     void ReadOutputSizeKeys();
+    void ReadLossModeKey();
     std::function<void(DecodeEventIndex, uint32_t, void *)> m_eventCallBack;
     std::function<uint32_t(uint8_t*, uint8_t*, const PicInfoParams &, uint32_t)> m_copyFrame;
 };

@@ -14,6 +14,10 @@ int32_t vd_parse_output_size(const char *width, const char *height, int32_t *out
 {
     return VideoDecoderMI355X::ParseOutputSize(width != nullptr ? width : "", height != nullptr ? height : "", outWidth, outHeight);
 }
+// persist.vmi.video.decode.lossmode: 1 (and the mode), 0 (not set) or -1 (rejected)
+int32_t vd_parse_loss_mode(const char *value, int32_t *mode) { return VideoDecoderMI355X::ParseLossMode(value != nullptr ? value : "", mode); }
+// conceal mode: 1 when the last picture handed out may differ from the lossless decode
+int32_t vd_inexact(void *dec) { return static_cast<VideoDecoderMI355X *>(static_cast<VideoDecoder *>(dec))->Inexact() ? 1 : 0; }
 struct vd_events { uint32_t count, width, height, stride; };
 
 uint32_t vd_create(void **dec) { return CreateVideoDecoder(reinterpret_cast<VideoDecoder **>(dec)); }

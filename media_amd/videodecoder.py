@@ -42,8 +42,26 @@ def lib():
         L.vd_prop_set.restype = None
         L.vd_parse_output_size.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.vd_parse_output_size.restype = C.c_int32
+        if hasattr(L, "vd_parse_loss_mode"):
+            L.vd_parse_loss_mode.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
+            L.vd_parse_loss_mode.restype = C.c_int32
+            L.vd_inexact.argtypes = [C.c_void_p]
+            L.vd_inexact.restype = C.c_int32
         _lib = L
     return _lib
+
+
+def parse_loss_mode(value):
+    """what persist.vmi.video.decode.lossmode = value selects: 0 (strict) or 1 (conceal); None when it is not set; False for
+    anything but "0" and "1" (one WARN line, the decoder stays strict)"""
+    m = C.c_int32(0)
+    rc = lib().vd_parse_loss_mode(str(value).encode(), C.byref(m))
+    return None if rc == 0 else (m.value if rc > 0 else False)
+
+
+def set_loss_mode(value=None):
+    """the key as StartDecoder reads it (None: unset)"""
+    lib().vd_prop_set(b"persist.vmi.video.decode.lossmode", b"" if value is None else str(value).encode())
 
 
 def parse_output_size(width, height):
@@ -68,6 +86,7 @@ class PluginDecoder:
 
     def create_decoder(self, fmt=STREAM_AVC): return lib().vd_create_decoder(self.h, fmt)
     def init(self): return lib().vd_init(self.h)
+    def inexact(self): return bool(lib().vd_inexact(self.h))
     def install_hooks(self): return lib().vd_install_hooks(self.h, C.byref(self.events))
     def start(self): return lib().vd_start(self.h)
     def stop(self): return lib().vd_stop(self.h)
