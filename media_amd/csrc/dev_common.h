@@ -11,6 +11,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "item_word.h"
+
 // wave priorities of the entropy-coding kernels and of the motion search (row wavefronts run at 3, the transform at 2).
 // A/B builds (media_amd/csrc/Makefile target `ab`) may swap them: -DAB_PRIO_EC=0 -DAB_PRIO_ME=1
 #ifndef AB_PRIO_EC
@@ -147,24 +149,11 @@ struct FrameParams {
     const DecPos* dectab;
 };
 
-// Temporal layers, the two wave-uniform facts k_me takes about its picture (host_framing.h, PicSeq::me_facts):
-//   ME_PARK       a layer-1 picture: the previous-picture vector word it read is kept in pmv, because its own vectors replace it in MbInfo
-//   ME_SEED_PARK  a layer-0 P picture of a two-layer stream: the word comes from pmv, where the layer-1 picture in front of it kept
-//                 what the previous LAYER-0 picture left
-enum { ME_PARK = 1, ME_SEED_PARK = 2 };
-// Intra refresh (host_framing.h, PicSeq::refresh_band): the band k of the picture that is coded all intra travels as k + 1 (0: none)
-// beside them - direct launches in bits 8..13 of FrameParams::me, indirect launches in bits 22..27 of the position's itemtab word.
-// Only k_me<IND, true> reads it (k_me.h, me_refresh_band); the engines of refresh streams alone launch that form.
-enum { ME_RFR_SHIFT = 8, ITEM_RFR_SHIFT = 22, RFR_MASK = 63 };
-
-// itemtab word: bits 0..7 batch item, 8..9 ring slot of the picture being coded, 10..11 the reference pictures the position's
-// picture has (1..3 in a P step: reference pictures since the stream's IDR, at most config.refs; 0 in an IDR step), 12..13 ME_PARK /
-// ME_SEED_PARK of the position's picture, 16..21 QP, 22..27 intra refresh band + 1 (above)
-struct ItemRef { int item, cur, nref, qp, me; };
+// The itemtab word of a position, FrameParams::me of a direct launch and the facts they carry (ME_PARK, ME_SEED_PARK, the intra refresh
+// band) are laid out in item_word.h, which the host's packing shares
 __device__ __forceinline__ ItemRef item_ref(const uint32_t* itemtab, int pos)
 {
-    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)itemtab[pos]);   // uniform: a scalar load
-    return ItemRef{(int)(w & 0xFFu), (int)((w >> 8) & 3u), (int)((w >> 10) & 3u), (int)((w >> 16) & 63u), (int)((w >> 12) & 3u)};
+    return item_unpack((uint32_t)__builtin_amdgcn_readfirstlane((int)itemtab[pos]));   // uniform: a scalar load
 }
 // srctab entry of a position: wave-uniform like the itemtab word, a scalar load of its own (it depends on the position alone, so
 // it is issued beside the itemtab word, not behind it)

@@ -9,11 +9,10 @@ namespace {
 
 constexpr int NSLOT = 3;          // access-unit slots in flight
 
-// where an access unit lies in a slot's h_au: offset of its first byte and of the slice payload; its type
-struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false; int nal_hdr = 0;
-                  int layer = 0;        // temporal layer of the picture (the stream hub: of the position, with nal_hdr - hub.h sets both per picture)
-                  int rband = -1;       // intra refresh: the picture's all-intra band, -1 for none (the stream hub: the position's, as layer)
-                  int quality = 0;      // quality report of the picture: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
+// where the access units of a step lie in a slot's h_au: offset of the first byte and of the slice payload; their type; and the
+// step's quality report.  What is the picture's own (layer, QP, refresh band) is in its ItemPic
+struct AuLayout { size_t au_start = 0, payload_off = 0; bool idr = false;
+                  int quality = 0;      // quality report of the step's pictures: 0 off, 1 compared (k_sse ran), 2 on but nothing to compare
                   int ssim = 0; };      // the SSIM record accompanies it (compared: k_ssim ran behind k_sse)
 
 struct Slot {
@@ -22,6 +21,7 @@ struct Slot {
     SliceInfo* h_info = nullptr;    // pinned
     uint8_t* h_au = nullptr;        // pinned access unit buffer
     AuLayout lay;                   // of the picture in flight
+    ItemPic pics[MAX_BATCH];        // and its records, one per batch item (direct steps; the stream hub's are the gathered step's)
     unsigned long long* h_qpart = nullptr;   // quality report (pinned, with the first enable): [G][mbh][SSE_SEGS][3] plane sums per wave of k_sse
     uint32_t* h_qmap = nullptr;              //   and [G][nmb] sums per macroblock, stored by k_sse; rows outside the band stay 0
     long long* h_spart = nullptr;            // SSIM (pinned, with the first enable that asks for it): [G][mbh][SSIM_SEGS][3] plane sums per wave of k_ssim
@@ -195,20 +195,21 @@ struct StatScope {
 };
 
 // ---- one lockstep step: which pictures, where from, on which streams ----
-// Direct (items == nullptr): the n = e->G batch items of the encoder, one QP, one ring position, consecutive idr_pic_ids - the
-// closed-GOP batch of mi355x_h264_encode_gops_device and the single-picture calls.  Indirect (the stream hub below): position k
-// of the grid is picture items[k] - its own batch item, ring slot, QP, frame_num and idr_pic_id; the kernels are the IND = true
-// instantiations and read d_itemtab, and the source picture of position k lies at d_srctab[k] (d_src is not used) - wherever that is: a
-// slot of the hub's staging array or the caller's own device memory.  A step holds pictures of ONE type (IDR or P): the two run
-// different kernels.  A P step's positions are ordered by their pictures' number of reference pictures (ItemPic.nref, most
-// first): k_me's launch for reference picture r covers the positions that have it, the first ones.
+// Position k of the grid is picture items[k]: its batch item, ring slot, QP, frame_num, idr_pic_id, reference count, layer and
+// refresh band (ItemPic, made by PicSeq::pic), whoever brings the step.  Direct (d_itemtab == nullptr): the n = e->G batch items of the
+// encoder in their order, one stream state, consecutive idr_pic_ids - the closed-GOP batch of mi355x_h264_encode_gops_device and the
+// single-picture calls; the kernels find item g at g strides.  Indirect (the stream hub below): the kernels are the IND = true
+// instantiations and read each position's facts from d_itemtab (item_word.h), and the source picture of position k lies at
+// d_srctab[k] (d_src is not used) - wherever that is: a slot of the hub's staging array or the caller's own device memory.  A step
+// holds pictures of ONE type (IDR or P): the two run different kernels.  A P step's positions are ordered by their pictures' number
+// of reference pictures (ItemPic.nref, most first): k_me's launch for reference picture r covers the positions that have it, the first ones.
 // mi355x_h264_debug_code_syntax: the decisions of the step's pictures come from the host (arrays of n items) instead of the
 // decision and reconstruction kernels
 struct Injected { const void* mbinfo; const void* levels; const void* mvq; const void* mbaux; };
 struct Step {
     const uint8_t* d_src = nullptr; size_t src_item_stride = 0; bool nv12 = false; bool idr = false;
     int n = 1;
-    const ItemPic* items = nullptr;
+    const ItemPic* items = nullptr;   // [n]
     const uint32_t* d_itemtab = nullptr;
     const unsigned long long* d_srctab = nullptr;
     const StepSync* sync = nullptr;   // streams, events and the time-out flag of the step
@@ -232,43 +233,275 @@ FrameParams frame_params(mi355x_h264_encoder* e)   // takes the next picture ser
     return P;
 }
 
-int submit_step(mi355x_h264_encoder* e, Step& T)
+// ---- the stages of a step, in the order submit_step calls them.  A stage queues its launches on the stream it names; the events
+// between the two streams are submit_step's alone.  ind: the IND = true kernels run (device tables exist) ----
+
+// The step's FrameParams (takes the next picture serial) and me_pos[r] = the positions that have reference picture r, k_me's grid
+// for it (the kernels take each position's own count from its itemtab word).  Refuses positions out of the order of their counts
+int step_frame_params(mi355x_h264_encoder* e, const Step& T, FrameParams& P, int* me_pos)
 {
-    Slot& S = *T.slot;
-    const bool idr = T.idr, ind = T.items != nullptr;
-    const int cur = e->seq.cur;
-    FrameParams P = frame_params(e);
+    const bool idr = T.idr, ind = T.d_itemtab != nullptr;
+    P = frame_params(e);
     P.src = T.d_src; P.src_nv12 = T.nv12 ? 1 : 0; P.w = e->cfg.width; P.h = e->cfg.height;
-    // indirect: me_pos[r] = positions that have reference picture r (the kernels take each position's own count from the itemtab word)
-    int me_pos[mi355x_h264_encoder::MAX_REFS] = {0, 0, 0};
-    if (ind)
-        for (int k = 0; k < T.n; k++) {
-            const int nr = T.items[k].nref;
-            if (nr < (idr ? 0 : 1) || nr > (idr ? 0 : e->nrefs) || (k > 0 && nr > T.items[k - 1].nref))
-                return set_err(e->err, MI355X_H264_E_INTERNAL, "step position %d: %d reference pictures (after %d)", k, nr, k ? T.items[k - 1].nref : 0);
-            for (int r = 0; r < nr; r++) me_pos[r]++;
-        }
-    P.nref = ind ? (idr ? 1 : T.items[0].nref) : std::max(1, avail_refs(e, idr));
+    for (int k = 0; k < T.n; k++) {
+        const int nr = T.items[k].nref;
+        if (nr < (idr ? 0 : 1) || nr > (idr ? 0 : e->nrefs) || (k > 0 && nr > T.items[k - 1].nref))
+            return set_err(e->err, MI355X_H264_E_INTERNAL, "step position %d: %d reference pictures (after %d)", k, nr, k ? T.items[k - 1].nref : 0);
+        for (int r = 0; r < nr; r++) me_pos[r]++;
+    }
+    P.nref = std::max(1, T.items[0].nref);   // the most any position has
+    const int cur = ind ? 0 : T.items[0].cur;   // direct: the ring slot every item writes (indirect: plane bases; the position's slot is in its word)
     for (int p = 0; p < 3; p++) {
         P.rec[p] = ind ? e->d_plane_base[p] : e->d_planes[cur][p];
         for (int r = 0; r < mi355x_h264_encoder::MAX_REFS; r++) P.refs[r][p] = e->d_planes[(cur + e->nbuf - 1 - std::min(r, e->nrefs - 1)) % e->nbuf][p];
         P.ref[p] = P.refs[0][p];
     }
-    P.me = ind ? 0 : e->seq.me_facts(idr);   // (temporal layers; indirect launches: the position's own, from the itemtab word)
-    const bool rfr = e->shape.refresh != 0;   // intra refresh: the other form of k_me, and the picture's band beside the facts
-    if (rfr && !ind) P.me |= (e->seq.refresh_band(idr) + 1) << ME_RFR_SHIFT;
+    // (temporal layers, and intra refresh: the other form of k_me and the picture's band; indirect launches: the position's own word)
+    P.me = ind ? 0 : me_word(T.items[0], e->shape.refresh != 0);
     P.itemtab = T.d_itemtab; P.srctab = T.d_srctab; P.qtab = e->d_qtab; P.st_ring_y = e->st_ring_y; P.st_ring_c = e->st_ring_c; P.nbuf = e->nbuf;
     P.st_src = T.src_item_stride; P.sl = e->sl;
     P.band.row0 = e->b_row0; P.band.rows = e->b_rows;
-    const unsigned pic_serial = P.pic_serial;
-    const unsigned G = (unsigned)T.n;
     fill_qp(P.qy, P.qc, P.lambda, P.sad_nz, e->qp);   // (indirect launches take these from qtab by the item's own QP)
     P.search = e->cfg.search;
+    return MI355X_H264_OK;
+}
+
+// mi355x_h264_debug_code_syntax: the arrays k_i4_decide / k_intra_rows / k_me / k_tq / k_pintra_rows would have left, and the flags
+// they would have raised
+int step_inject(mi355x_h264_encoder* e, const Step& T, const FrameParams& P)
+{
+    hipStream_t st = T.sync->st;
+    const size_t n = (size_t)T.n * e->nmb;
+    HIPCHK(e->err, hipMemcpyAsync(e->d_mb, T.inj->mbinfo, n * sizeof(MbInfo), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemcpyAsync(e->d_levels, T.inj->levels, n * LV_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemcpyAsync(e->d_mvq, T.inj->mvq, n * 8 * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemcpyAsync(e->d_aux, T.inj->mbaux, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemsetAsync(e->d_me_cost, 0, n * sizeof(uint16_t), st));
+    unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {}, stepintra = 0;
+    const MbInfo* m = (const MbInfo*)T.inj->mbinfo;
+    for (int g = 0; g < T.n; g++)
+        for (int i = 0; i < e->nmb; i++) {
+            const int type = m[(size_t)g * e->nmb + i].type;
+            if (type == MB_IPCM) anypcm[g] = P.pic_serial;
+            if (!T.idr && mb_is_intra_host(type)) anyintra[g] = stepintra = P.pic_serial;
+        }
+    HIPCHK(e->err, hipMemcpyAsync(e->d_anypcm, anypcm, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemcpyAsync(e->d_anyintra, anyintra, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipMemcpyAsync(e->d_stepintra, &stepintra, sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(e->err, hipStreamSynchronize(st));   // (the flag arrays live on this stack)
+    return MI355X_H264_OK;
+}
+
+// IDR pictures: decide, then the row wavefront
+void step_recon_idr(mi355x_h264_encoder* e, const Step& T, const FrameParams& P)
+{
+    const bool ind = T.d_itemtab != nullptr;
+    const unsigned G = (unsigned)T.n;
+    hipStream_t st = T.sync->st;
+    StatScope sc(e, T.slot, MI355X_H264_K_INTRA, (uint32_t)(e->diag_mode ? e->mbw + e->mbh - 1 : 1), (uint32_t)(e->b_nmb * T.n), st);
+    LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3((e->b_nmb + 3) / 4, G), dim3(64), st, P, 0);   // Intra4x4 or Intra16x16, and the block modes: from the source alone
+    if (e->diag_mode && !ind) {
+        for (int s = 0; s < e->mbw + e->mbh - 1; s++) {
+            const int ymin = std::max(0, s - e->mbw + 1), ymax = std::min(e->mbh - 1, s);
+            hipLaunchKernelGGL(k_intra_diag, dim3(ymax - ymin + 1, G), dim3(64), 0, st, P, s);
+        }
+        return;
+    }
+    const IntraRowParams R = intra_row_params(e, P, T.sync->h_err, (int)G);
+    // MI355X_H264_INTRA_SLOTS: pictures the row wavefront holds at a time (k_intra_rows)
+    static const int slots = getenv("MI355X_H264_INTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_INTRA_SLOTS"))) : 24;
+    LAUNCH2(ind, k_intra_rows<true>, k_intra_rows<false>, dim3(e->b_rows, std::min(G, (unsigned)slots)), dim3(128), st, R);
+}
+
+// P pictures: the motion search behind the GPU's lock (one launch per reference picture), transform and quantisation, the intra pass.
+// (P: the lock travels in it for the launch of k_tq alone)
+void step_recon_p(mi355x_h264_encoder* e, const Step& T, FrameParams& P, const int* me_pos)
+{
+    const bool ind = T.d_itemtab != nullptr, rfr = e->shape.refresh != 0;
+    const unsigned G = (unsigned)T.n;
+    hipStream_t st = T.sync->st;
+    const bool turns = g_turns_on && !ind && e->me_turn > 0 && T.n >= TURN_MIN_BATCH;
+    if (turns) hipLaunchKernelGGL(k_turn_acquire, dim3(1), dim3(64), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn, (int)TURN_TIMEOUT_US);
+    { StatScope sc(e, T.slot, MI355X_H264_K_ME, (uint32_t)P.nref, (uint32_t)(e->b_nmb * T.n), st);
+      FrameParams Q = P;   // one launch per reference picture (config.refs): Q.ref = the planes of ref_idx_l0 = Q.rf
+      Q.rf_last = P.nref - 1;
+      for (int r = 0; r < P.nref; r++) {   // (over the positions that have the picture: no launch places a wave that has nothing to do)
+          Q.rf = r;
+          for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
+          if (rfr) LAUNCH2(ind, (k_me<true, true>), (k_me<false, true>), dim3(e->b_nmb, (unsigned)me_pos[r]), dim3(64), st, Q);
+          else LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, (unsigned)me_pos[r]), dim3(64), st, Q);
+      } }
+    // the lock goes back with the first wave of the k_tq that follows on this stream (k_tq.h tq_turn_release); in front of k_tq8
+    // by a launch of its own
+    if (turns && e->cfg.profile_idc == 100) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
+    else if (turns) { P.turn_lock = g_turns.d_lock[e->device]; P.turn_id = (unsigned)e->me_turn; }
+    { StatScope sc(e, T.slot, MI355X_H264_K_PMB, 1, (uint32_t)(e->b_nmb * T.n), st);
+      if (e->cfg.profile_idc == 100) LAUNCH2(ind, k_tq8<true>, k_tq8<false>, dim3((e->b_nmb + 15) / 16, G), dim3(64), st, P);   // High: 8x8 transform, sixteen macroblocks per wave
+      else LAUNCH2(ind, k_tq<true>, k_tq<false>, dim3((e->b_nmb + 7) / 8, G), dim3(64), st, P);   // one wave per eight macroblocks
+      P.turn_lock = nullptr; }   // (given back: no later launch of the step carries it)
+    // macroblocks the motion search handed to the intra pass (returns at once when there are none)
+    const IntraRowParams R = intra_row_params(e, P, T.sync->h_err, (int)G);
+    // The grid holds ONE picture at a time (the workgroups walk the step's pictures) while the recent P pictures had next to
+    // no intra macroblocks, all of them once they have: see k_pintra_rows.  MI355X_H264_PINTRA_SLOTS fixes the number.
+    static const int pslots_env = getenv("MI355X_H264_PINTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_PINTRA_SLOTS"))) : 0;
+    const unsigned pslots = std::min(G, pslots_env ? (unsigned)pslots_env : (e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u));
+    if (ind) {   // the stream hub: Intra4x4 or Intra16x16 and the block modes of the marked macroblocks first, then the rows
+        hipLaunchKernelGGL(k_i4_decide<true>, dim3(std::min((e->b_nmb + 3) / 4, (int)I4_MARKED_WAVES), pslots), dim3(64), 0, st, P, (int)G);
+        hipLaunchKernelGGL((k_pintra_rows<false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
+    } else   // the encoder's own batches: ONE launch, the row waves decide as they go, and one load when the step has nothing for them
+        hipLaunchKernelGGL((k_pintra_rows<false, false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
+}
+
+// slice headers per position, from the pictures' records (Hpcm: of a picture with an I_PCM macroblock, which is not filtered)
+void step_headers(mi355x_h264_encoder* e, const Step& T, HdrBatch& H, HdrBatch& Hpcm)
+{
+    for (int g = 0; g < T.n; g++) {
+        const ItemPic& pic = T.items[g];
+        uint64_t hdr = 0;
+        H.len[g] = (unsigned char)build_slice_header(e->shape, T.idr, pic.idr_id, false, pic.frame_num, pic.qp, pic.nref, &hdr, pic.layer != 0);
+        H.bits[g] = hdr;
+        Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, T.idr, pic.idr_id, true, pic.frame_num, pic.qp, pic.nref, &hdr, pic.layer != 0);
+        Hpcm.bits[g] = hdr;
+    }
+}
+
+// what the entropy coder's kernels and k_bs take
+CavlcParams step_cavlc_params(mi355x_h264_encoder* e, const Step& T, const FrameParams& P)
+{
+    CavlcParams C{};
+    C.mb = e->d_mb; C.levels = e->d_levels; C.mvd = e->d_mvd; C.mbw = e->mbw; C.nmb = e->nmb; C.p_slice = T.idr ? 0 : 1; C.t8x8 = e->cfg.profile_idc == 100 ? 1 : 0;
+    C.nref = T.d_itemtab ? 0 : T.items[0].nref; C.sl = e->sl;   // (indirect launches: the position's own, from the itemtab word)
+    C.mb_first = e->b_row0 * e->mbw; C.mb_end = C.mb_first + e->b_nmb;
+    C.slice_cap = (unsigned)e->slice_cap;
+    C.mbdiv = P.mbdiv;
+    C.slotbits = e->d_slotbits; C.slotcode = e->d_slotcode; C.mbbits = e->d_mbbits; C.bitbuf = T.slot->d_bitbuf;
+    C.bs = (uint8_t*)e->d_bs; C.prevcoded = e->d_prevcoded;
+    C.st_mb = e->nmb; C.st_bitbuf = e->st_bitbuf_bytes / 4;
+    C.aux = e->d_aux; C.mvq = e->d_mvq;
+    C.src = T.d_src; C.w = e->cfg.width; C.h = e->cfg.height; C.src_nv12 = T.nv12 ? 1 : 0; C.st_src = T.src_item_stride;
+    C.itemtab = T.d_itemtab; C.srctab = T.d_srctab;
+    return C;
+}
+
+// the boundary strengths, a small launch in front of the fork (the diagonal debug form of the filter reads them too); returns the
+// serial the loop filter of this picture will run under, 0 with the filter off
+unsigned step_bs(mi355x_h264_encoder* e, const Step& T, const CavlcParams& C)
+{
+    if (e->cfg.disable_deblock) return 0;
+    const unsigned db_serial = next_nonzero(e->serial);
+    LAUNCH2(T.d_itemtab != nullptr, k_bs<true>, k_bs<false>, dim3(std::min((e->b_nmb + 1) / 2, (int)BS_WAVES), (unsigned)T.n), dim3(64), T.sync->st, C, e->d_anybs, db_serial);
+    return db_serial;
+}
+
+// entropy coding on ec, k_mvpred through k_pack, and where the access units will lie (T.lay)
+void step_entropy(mi355x_h264_encoder* e, Step& T, const FrameParams& P, const CavlcParams& C, const HdrBatch& H, const HdrBatch& Hpcm, hipStream_t ec)
+{
+    const bool idr = T.idr, ind = T.d_itemtab != nullptr;
+    const unsigned G = (unsigned)T.n;
+    Slot& S = *T.slot;
+    StatScope sc(e, &S, MI355X_H264_K_CAVLC, 4, (uint32_t)(e->b_nmb * T.n), ec);
+    const int grid = (e->b_nmb + 1) / 2;
+    if (!idr) {
+        LAUNCH2(ind, k_mvpred<true>, k_mvpred<false>, dim3((e->b_nmb + 63) / 64, G), dim3(64), ec, P);   // vectors + coded_block_pattern are final: mvd, P_Skip
+        LAUNCH2(ind, k_skip_scan<true>, k_skip_scan<false>, dim3(G), dim3(256), ec, C);
+    }
+    LAUNCH2(ind, (k_cavlc<false, true>), (k_cavlc<false, false>), dim3(grid, G), dim3(64), ec, C);
+    LAUNCH2(ind, k_bit_scan<true>, k_bit_scan<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, C, H, Hpcm, (const unsigned*)e->d_anypcm, P.pic_serial, S.d_info, e->d_me_cost,
+            e->b_nsl, e->b_sl0, (unsigned)e->slice_cap);
+    LAUNCH2(ind, (k_cavlc<true, true>), (k_cavlc<true, false>), dim3(grid, G), dim3(64), ec, C);
+    // access unit layout in the pinned buffer: [pad][SPS PPS (IDR only)][00 00 00 01 hdr][payload...];
+    // with several slices: the payload of slice s at s * slice_cap, the access unit is put together by finish_item
+    const size_t pre = (idr ? e->sps_pps.size() : 0) + 5;
+    const size_t pad = (16 - (pre & 15)) & 15;
+    T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr};
+    LAUNCH2(ind, k_pack<true>, k_pack<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, (uint8_t*)S.d_bitbuf, e->st_bitbuf_bytes, S.h_au + T.lay.payload_off, e->st_au,
+            (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
+}
+
+// debug (keep_pre): a copy of every picture's reconstruction before the loop filter
+int step_keep_pre(mi355x_h264_encoder* e, const Step& T)
+{
+    hipStream_t st = T.sync->st;
+    if (!T.d_itemtab && !T.inj)
+        for (int p = 0; p < 3; p++) {   // (the items' planes lie nbuf ring slots apart: one row of the 2-D copy per item)
+            const size_t ring = p ? e->st_ring_c : e->st_ring_y;
+            HIPCHK(e->err, hipMemcpy2DAsync(e->d_pre[p], ring, e->d_planes[T.items[0].cur][p], p ? e->st_c : e->st_y, ring, (size_t)e->G, hipMemcpyDeviceToDevice, st));
+        }
+    if (T.d_itemtab)   // (mi355x_h264_stream_debug_keep_pre: every position's picture, from its item's own ring slot to its item's copy)
+        for (int k = 0; k < T.n; k++)
+            for (int p = 0; p < 3; p++) {
+                const size_t ring = p ? e->st_ring_c : e->st_ring_y;
+                HIPCHK(e->err, hipMemcpyAsync(e->d_pre[p] + (size_t)T.items[k].item * ring,
+                                              e->d_plane_base[p] + (size_t)T.items[k].item * (p ? e->st_c : e->st_y) + (size_t)T.items[k].cur * ring, ring,
+                                              hipMemcpyDeviceToDevice, st));
+            }
+    return MI355X_H264_OK;
+}
+
+// the loop filter, on the step's first stream
+void step_filter(mi355x_h264_encoder* e, const Step& T, unsigned pic_serial, unsigned db_serial)
+{
+    const bool idr = T.idr, ind = T.d_itemtab != nullptr;
+    const unsigned G = (unsigned)T.n;
+    hipStream_t st = T.sync->st;
+    const int steps = e->mbw + 2 * (e->mbh - 1);
+    StatScope sc(e, T.slot, MI355X_H264_K_DEBLOCK, (uint32_t)(e->diag_mode ? steps : 1), (uint32_t)(e->b_nmb * T.n), st);
+    const DbParams D = db_params(e, ind ? e->d_plane_base : e->d_planes[T.items[0].cur], e->sl, e->qp);   // (indirect launches look the item's own QP up on the device)
+    if (e->diag_mode && !ind) {
+        for (int s = 0; s < steps; s++) {
+            const int ymin = std::max(0, (s - (e->mbw - 1) + 1) >> 1), ymax = std::min(e->mbh - 1, s >> 1);
+            if (ymax < ymin) continue;
+            hipLaunchKernelGGL(k_deblock_diag, dim3(ymax - ymin + 1), dim3(64), 0, st, D, s);
+        }
+        return;
+    }
+    DbRowParams R = db_row_params(e, D, T.sync->h_err, db_serial, pic_serial, e->b_row0, (int)G);
+    R.itemtab = T.d_itemtab; R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c;
+    // two macroblock rows per wave (k_deblock_pairs) for lockstep batches of pictures of one slice; else one row per wave
+    const bool pairs = e->pair_filter && T.n >= e->pair_min_batch && e->nsl == 1 && e->b_rows == e->mbh;
+    const unsigned grid_x = pairs ? (unsigned)((e->b_rows + 1) / 2) : (unsigned)e->b_rows;
+    auto filter = [&](bool bs4, unsigned at_a_time) {   // (bs4 = false: the stream hub's P steps only)
+        const dim3 grid(grid_x, std::min(G, at_a_time));
+        if (pairs) { if (bs4) LAUNCH2(ind, (k_deblock_pairs<true, true>), (k_deblock_pairs<true, false>), grid, dim3(64), st, R);
+                     else hipLaunchKernelGGL((k_deblock_pairs<false, true>), grid, dim3(64), 0, st, R); }
+        else { if (bs4) LAUNCH2(ind, (k_deblock_rows<true, false, true>), (k_deblock_rows<true, false, false>), grid, dim3(64), st, R);
+               else hipLaunchKernelGGL((k_deblock_rows<false, false, true>), grid, dim3(64), 0, st, R); }
+    };
+    if (idr) { R.need_intra = 0; filter(true, G); }
+    else if (!ind) {   // P pictures: ONE launch, every picture resident and taken in the form it needs (k_deblock_rows_p)
+        R.need_intra = 0;
+        if (pairs) hipLaunchKernelGGL(k_deblock_pairs_p, dim3(grid_x, G), dim3(64), 0, st, R);
+        else hipLaunchKernelGGL(k_deblock_rows_p, dim3(grid_x, G), dim3(64), 0, st, R);
+    } else {   // P pictures of the stream hub: the form without the bS 4 filter, or - when the picture has intra macroblocks - the one with it
+        // (while the recent P pictures had next to none, the second launch holds one picture at a time: see k_deblock_rows)
+        R.need_intra = -1; filter(false, G);
+        R.need_intra = 1; filter(true, e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u);
+    }
+}
+
+// the quality report's comparisons on ec: k_sse, and k_ssim behind it on the same stream
+void step_quality(mi355x_h264_encoder* e, const Step& T, const FrameParams& P, hipStream_t ec)
+{
+    const bool ind = T.d_itemtab != nullptr;
+    const unsigned G = (unsigned)T.n;
+    LAUNCH2(ind, k_sse<true>, k_sse<false>, dim3((unsigned)e->b_rows * SSE_SEGS, G), dim3(64), ec, P, T.slot->h_qpart, T.slot->h_qmap);
+    if (T.lay.ssim) LAUNCH2(ind, k_ssim<true>, k_ssim<false>, dim3((unsigned)e->b_rows * SSIM_SEGS, G), dim3(64), ec, P, T.slot->h_spart, T.slot->h_smap);
+}
+
+// One lockstep step: the stages in order, and everything that orders the step's two streams - st carries reconstruction and loop
+// filter (the chain to the next picture's motion search), ec entropy coding and the quality report beside them.
+// (the payload buffers of the items were left zeroed by the k_pack of their previous use)
+int submit_step(mi355x_h264_encoder* e, Step& T)
+{
     const StepSync& Y = *T.sync;
-    hipStream_t st = Y.st;
-
-    // (the payload buffers of the items were left zeroed by the k_pack of their previous use)
-
+    const bool ind = T.d_itemtab != nullptr;
+    hipStream_t st = Y.st, ec = T.one_stream ? st : Y.ec;
+    const bool fork = ec != st;
+    const int cur = T.items[0].cur;   // (direct steps: the ring slot every item writes)
+    FrameParams P;
+    int me_pos[mi355x_h264_encoder::MAX_REFS] = {0, 0, 0};
+    int rc = step_frame_params(e, T, P, me_pos);
+    if (rc) return rc;
     // Quality report, hazard "ring slot": this picture's first kernels write ring slot `cur`, which the k_sse of the picture that
     // wrote it last read on the second stream - nbuf pictures ago, or, behind a layer-1 picture, the picture just before.  The event
     // is the slot's, so either way the wait below is the one that matters.  In mi355x_h264_encode_gops_device / _batch_device no host wait lies between the
@@ -278,185 +511,24 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
         HIPCHK(e->err, hipStreamWaitEvent(st, e->q_done[cur], 0));
         e->q_done_set[cur] = false;
     }
-
-    if (T.inj) {
-        // the arrays k_i4_decide / k_intra_rows / k_me / k_tq / k_pintra_rows would have left, and the flags they would have raised
-        const size_t n = (size_t)T.n * e->nmb;
-        HIPCHK(e->err, hipMemcpyAsync(e->d_mb, T.inj->mbinfo, n * sizeof(MbInfo), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemcpyAsync(e->d_levels, T.inj->levels, n * LV_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemcpyAsync(e->d_mvq, T.inj->mvq, n * 8 * sizeof(int16_t), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemcpyAsync(e->d_aux, T.inj->mbaux, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemsetAsync(e->d_me_cost, 0, n * sizeof(uint16_t), st));
-        unsigned anypcm[MAX_BATCH] = {}, anyintra[MAX_BATCH] = {}, stepintra = 0;
-        const MbInfo* m = (const MbInfo*)T.inj->mbinfo;
-        for (int g = 0; g < T.n; g++)
-            for (int i = 0; i < e->nmb; i++) {
-                const int type = m[(size_t)g * e->nmb + i].type;
-                if (type == MB_IPCM) anypcm[g] = pic_serial;
-                if (!idr && mb_is_intra_host(type)) anyintra[g] = stepintra = pic_serial;
-            }
-        HIPCHK(e->err, hipMemcpyAsync(e->d_anypcm, anypcm, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemcpyAsync(e->d_anyintra, anyintra, (size_t)T.n * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipMemcpyAsync(e->d_stepintra, &stepintra, sizeof(unsigned), hipMemcpyHostToDevice, st));
-        HIPCHK(e->err, hipStreamSynchronize(st));   // (the flag arrays live on this stack)
-    } else if (idr) {
-        StatScope sc(e, &S, MI355X_H264_K_INTRA, (uint32_t)(e->diag_mode ? e->mbw + e->mbh - 1 : 1), (uint32_t)(e->b_nmb * T.n), st);
-        LAUNCH2(ind, k_i4_decide<true>, k_i4_decide<false>, dim3((e->b_nmb + 3) / 4, G), dim3(64), st, P, 0);   // Intra4x4 or Intra16x16, and the block modes: from the source alone
-        if (e->diag_mode && !ind) {
-            for (int s = 0; s < e->mbw + e->mbh - 1; s++) {
-                const int ymin = std::max(0, s - e->mbw + 1), ymax = std::min(e->mbh - 1, s);
-                hipLaunchKernelGGL(k_intra_diag, dim3(ymax - ymin + 1, G), dim3(64), 0, st, P, s);
-            }
-        } else {
-            const IntraRowParams R = intra_row_params(e, P, Y.h_err, (int)G);
-            {   // MI355X_H264_INTRA_SLOTS: pictures the row wavefront holds at a time (k_intra_rows)
-                static const int slots = getenv("MI355X_H264_INTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_INTRA_SLOTS"))) : 24;
-                LAUNCH2(ind, k_intra_rows<true>, k_intra_rows<false>, dim3(e->b_rows, std::min(G, (unsigned)slots)), dim3(128), st, R);
-            }
-        }
-    } else {
-        { const bool turns = g_turns_on && !ind && e->me_turn > 0 && T.n >= TURN_MIN_BATCH;
-          if (turns) hipLaunchKernelGGL(k_turn_acquire, dim3(1), dim3(64), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn, (int)TURN_TIMEOUT_US);
-          { StatScope sc(e, &S, MI355X_H264_K_ME, (uint32_t)P.nref, (uint32_t)(e->b_nmb * T.n), st);
-            FrameParams Q = P;   // one launch per reference picture (config.refs): Q.ref = the planes of ref_idx_l0 = Q.rf
-            Q.rf_last = P.nref - 1;
-            for (int r = 0; r < P.nref; r++) {   // (indirect: P.nref = the most any position has; no launch places a wave that has nothing to do)
-                Q.rf = r;
-                for (int p = 0; p < 3; p++) Q.ref[p] = P.refs[r][p];
-                if (rfr) LAUNCH2(ind, (k_me<true, true>), (k_me<false, true>), dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
-                else LAUNCH2(ind, k_me<true>, k_me<false>, dim3(e->b_nmb, ind ? (unsigned)me_pos[r] : G), dim3(64), st, Q);
-            } }
-          // the lock goes back with the first wave of the k_tq that follows on this stream (k_tq.h tq_turn_release); in front of k_tq8
-          // by a launch of its own
-          if (turns && e->cfg.profile_idc == 100) hipLaunchKernelGGL(k_turn_release, dim3(1), dim3(1), 0, st, g_turns.d_lock[e->device], (unsigned)e->me_turn);
-          else if (turns) { P.turn_lock = g_turns.d_lock[e->device]; P.turn_id = (unsigned)e->me_turn; }
-        }
-        { StatScope sc(e, &S, MI355X_H264_K_PMB, 1, (uint32_t)(e->b_nmb * T.n), st);
-          if (e->cfg.profile_idc == 100) LAUNCH2(ind, k_tq8<true>, k_tq8<false>, dim3((e->b_nmb + 15) / 16, G), dim3(64), st, P);   // High: 8x8 transform, sixteen macroblocks per wave
-          else LAUNCH2(ind, k_tq<true>, k_tq<false>, dim3((e->b_nmb + 7) / 8, G), dim3(64), st, P);   // one wave per eight macroblocks
-          P.turn_lock = nullptr; }   // (given back: no later launch of the step carries it)
-        {   // macroblocks the motion search handed to the intra pass (returns at once when there are none)
-            const IntraRowParams R = intra_row_params(e, P, Y.h_err, (int)G);
-            // The grid holds ONE picture at a time (the workgroups walk the step's pictures) while the recent P pictures had next to
-            // no intra macroblocks, all of them once they have: see k_pintra_rows.  MI355X_H264_PINTRA_SLOTS fixes the number.
-            static const int pslots_env = getenv("MI355X_H264_PINTRA_SLOTS") ? std::max(1, atoi(getenv("MI355X_H264_PINTRA_SLOTS"))) : 0;
-            const unsigned pslots = std::min(G, pslots_env ? (unsigned)pslots_env : (e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u));
-            if (ind) {   // the stream hub: Intra4x4 or Intra16x16 and the block modes of the marked macroblocks first, then the rows
-                hipLaunchKernelGGL(k_i4_decide<true>, dim3(std::min((e->b_nmb + 3) / 4, (int)I4_MARKED_WAVES), pslots), dim3(64), 0, st, P, (int)G);
-                hipLaunchKernelGGL((k_pintra_rows<false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
-            } else   // the encoder's own batches: ONE launch, the row waves decide as they go, and one load when the step has nothing for them
-                hipLaunchKernelGGL((k_pintra_rows<false, false, true>), dim3(e->b_rows, pslots), dim3(64), 0, st, R);
-        }
-    }
-    // entropy coding: slice headers per position
+    // reconstruction on st (or, mi355x_h264_debug_code_syntax, what it would have left)
+    if (T.inj) { rc = step_inject(e, T, P); if (rc) return rc; }
+    else if (T.idr) step_recon_idr(e, T, P);
+    else step_recon_p(e, T, P, me_pos);
     HdrBatch H{}, Hpcm{};
-    for (int g = 0; g < T.n; g++) {
-        uint64_t hdr = 0;
-        const int fn = ind ? T.items[g].frame_num : e->seq.frame_num, qp = ind ? T.items[g].qp : e->qp;
-        const int id = ind ? T.items[g].idr_id : ((e->seq.idr_id + g * e->idr_step) & 0xFF);
-        const int nact = ind ? T.items[g].nref : avail_refs(e, idr);
-        const bool nonref = (ind ? T.items[g].layer : e->seq.layer()) != 0;
-        H.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, false, fn, qp, nact, &hdr, nonref);
-        H.bits[g] = hdr;
-        Hpcm.len[g] = (unsigned char)build_slice_header(e->shape, idr, id, true, fn, qp, nact, &hdr, nonref);
-        Hpcm.bits[g] = hdr;
-    }
-    // entropy coding needs only levels / MbInfo, the loop filter the reconstruction and the boundary strengths
-    // (a small launch of its own on this stream): the two run side by side and the filter never waits for the coder
-    hipStream_t ec = T.one_stream ? st : Y.ec;
-    CavlcParams C{};
-    C.mb = e->d_mb; C.levels = e->d_levels; C.mvd = e->d_mvd; C.mbw = e->mbw; C.nmb = e->nmb; C.p_slice = idr ? 0 : 1; C.t8x8 = e->cfg.profile_idc == 100 ? 1 : 0;
-    C.nref = ind ? 0 : avail_refs(e, idr); C.sl = e->sl;   // (indirect launches: the position's own, from the itemtab word)
-    C.mb_first = e->b_row0 * e->mbw; C.mb_end = C.mb_first + e->b_nmb;
-    C.slice_cap = (unsigned)e->slice_cap;
-    C.mbdiv = P.mbdiv;
-    C.slotbits = e->d_slotbits; C.slotcode = e->d_slotcode; C.mbbits = e->d_mbbits; C.bitbuf = S.d_bitbuf;
-    C.bs = (uint8_t*)e->d_bs; C.prevcoded = e->d_prevcoded;
-    C.st_mb = e->nmb; C.st_bitbuf = e->st_bitbuf_bytes / 4;
-    C.aux = e->d_aux; C.mvq = e->d_mvq;
-    C.src = T.d_src; C.w = e->cfg.width; C.h = e->cfg.height; C.src_nv12 = T.nv12 ? 1 : 0; C.st_src = T.src_item_stride;
-    C.itemtab = T.d_itemtab; C.srctab = T.d_srctab;
-    const int cavlc_grid = (e->b_nmb + 1) / 2;
-    unsigned db_serial = 0;
-    if (!e->cfg.disable_deblock) {   // (the diagonal debug form of the filter reads the strengths too)
-        db_serial = next_nonzero(e->serial);   // the serial the loop filter of this picture will run under
-        LAUNCH2(ind, k_bs<true>, k_bs<false>, dim3(std::min(cavlc_grid, (int)BS_WAVES), G), dim3(64), st, C, e->d_anybs, db_serial);
-    }
-    const bool fork = ec != st;
+    step_headers(e, T, H, Hpcm);
+    const CavlcParams C = step_cavlc_params(e, T, P);
+    const unsigned db_serial = step_bs(e, T, C);
+    // entropy coding needs only levels / MbInfo, the loop filter the reconstruction and the boundary strengths: the two run side by
+    // side and the filter never waits for the coder
     if (fork) {
         HIPCHK(e->err, hipEventRecord(Y.recon_ready, st));
         HIPCHK(e->err, hipStreamWaitEvent(ec, Y.recon_ready, 0));
     }
-    {
-        StatScope sc(e, &S, MI355X_H264_K_CAVLC, 4, (uint32_t)(e->b_nmb * T.n), ec);
-        const int grid = cavlc_grid;
-        if (!idr) {
-            LAUNCH2(ind, k_mvpred<true>, k_mvpred<false>, dim3((e->b_nmb + 63) / 64, G), dim3(64), ec, P);   // vectors + coded_block_pattern are final: mvd, P_Skip
-            LAUNCH2(ind, k_skip_scan<true>, k_skip_scan<false>, dim3(G), dim3(256), ec, C);
-        }
-        LAUNCH2(ind, (k_cavlc<false, true>), (k_cavlc<false, false>), dim3(grid, G), dim3(64), ec, C);
-        LAUNCH2(ind, k_bit_scan<true>, k_bit_scan<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, C, H, Hpcm, (const unsigned*)e->d_anypcm, pic_serial, S.d_info, e->d_me_cost,
-                e->b_nsl, e->b_sl0, (unsigned)e->slice_cap);
-        LAUNCH2(ind, (k_cavlc<true, true>), (k_cavlc<true, false>), dim3(grid, G), dim3(64), ec, C);
-        // access unit layout in the pinned buffer: [pad][SPS PPS (IDR only)][00 00 00 01 hdr][payload...];
-        // with several slices: the payload of slice s at s * slice_cap, the access unit is put together by finish_item
-        const size_t pre = (idr ? e->sps_pps.size() : 0) + 5;
-        const size_t pad = (16 - (pre & 15)) & 15;
-        const int layer = ind ? 0 : e->seq.layer();   // (indirect: hub.h gives every position its own)
-        T.lay = AuLayout{pad, e->nsl > 1 ? 0 : pad + pre, idr, slice_nal_hdr(idr, layer), layer};
-        T.lay.rband = ind ? -1 : e->seq.refresh_band(idr);
-        LAUNCH2(ind, k_pack<true>, k_pack<false>, dim3(G * (unsigned)e->b_nsl), dim3(SCAN_NT), ec, (uint8_t*)S.d_bitbuf, e->st_bitbuf_bytes, S.h_au + T.lay.payload_off, e->st_au,
-                (const SliceInfo*)S.d_info, S.h_info, e->b_nsl, e->b_sl0, (unsigned)e->slice_cap, T.d_itemtab);
-    }
+    step_entropy(e, T, P, C, H, Hpcm, ec);
     if (fork) HIPCHK(e->err, hipEventRecord(Y.entropy_done, ec));
-    if (e->keep_pre && !ind && !T.inj)
-        for (int p = 0; p < 3; p++) {   // (the items' planes lie nbuf ring slots apart: one row of the 2-D copy per item)
-            const size_t ring = p ? e->st_ring_c : e->st_ring_y;
-            HIPCHK(e->err, hipMemcpy2DAsync(e->d_pre[p], ring, e->d_planes[cur][p], p ? e->st_c : e->st_y, ring, (size_t)e->G, hipMemcpyDeviceToDevice, st));
-        }
-    if (e->keep_pre && ind)   // (mi355x_h264_stream_debug_keep_pre: every position's picture, from its item's own ring slot to its item's copy)
-        for (int k = 0; k < T.n; k++)
-            for (int p = 0; p < 3; p++) {
-                const size_t ring = p ? e->st_ring_c : e->st_ring_y;
-                HIPCHK(e->err, hipMemcpyAsync(e->d_pre[p] + (size_t)T.items[k].item * ring,
-                                              e->d_plane_base[p] + (size_t)T.items[k].item * (p ? e->st_c : e->st_y) + (size_t)T.items[k].cur * ring, ring,
-                                              hipMemcpyDeviceToDevice, st));
-            }
-    if (!e->cfg.disable_deblock && !T.inj) {
-        const int steps = e->mbw + 2 * (e->mbh - 1);
-        StatScope sc(e, &S, MI355X_H264_K_DEBLOCK, (uint32_t)(e->diag_mode ? steps : 1), (uint32_t)(e->b_nmb * T.n), st);
-        const DbParams D = db_params(e, ind ? e->d_plane_base : e->d_planes[cur], e->sl, e->qp);   // (indirect launches look the item's own QP up on the device)
-        if (e->diag_mode && !ind) {
-            for (int s = 0; s < steps; s++) {
-                const int ymin = std::max(0, (s - (e->mbw - 1) + 1) >> 1), ymax = std::min(e->mbh - 1, s >> 1);
-                if (ymax < ymin) continue;
-                hipLaunchKernelGGL(k_deblock_diag, dim3(ymax - ymin + 1), dim3(64), 0, st, D, s);
-            }
-        } else {
-            DbRowParams R = db_row_params(e, D, Y.h_err, db_serial, pic_serial, e->b_row0, (int)G);
-            R.itemtab = T.d_itemtab; R.st_ring_y = e->st_ring_y; R.st_ring_c = e->st_ring_c;
-            // two macroblock rows per wave (k_deblock_pairs) for lockstep batches of pictures of one slice; else one row per wave
-            const bool pairs = e->pair_filter && T.n >= e->pair_min_batch && e->nsl == 1 && e->b_rows == e->mbh;
-            const unsigned grid_x = pairs ? (unsigned)((e->b_rows + 1) / 2) : (unsigned)e->b_rows;
-            auto filter = [&](bool bs4, unsigned at_a_time) {   // (bs4 = false: the stream hub's P steps only)
-                const dim3 grid(grid_x, std::min(G, at_a_time));
-                if (pairs) { if (bs4) LAUNCH2(ind, (k_deblock_pairs<true, true>), (k_deblock_pairs<true, false>), grid, dim3(64), st, R);
-                             else hipLaunchKernelGGL((k_deblock_pairs<false, true>), grid, dim3(64), 0, st, R); }
-                else { if (bs4) LAUNCH2(ind, (k_deblock_rows<true, false, true>), (k_deblock_rows<true, false, false>), grid, dim3(64), st, R);
-                       else hipLaunchKernelGGL((k_deblock_rows<false, false, true>), grid, dim3(64), 0, st, R); }
-            };
-            if (idr) { R.need_intra = 0; filter(true, G); }
-            else if (!ind) {   // P pictures: ONE launch, every picture resident and taken in the form it needs (k_deblock_rows_p)
-                R.need_intra = 0;
-                if (pairs) hipLaunchKernelGGL(k_deblock_pairs_p, dim3(grid_x, G), dim3(64), 0, st, R);
-                else hipLaunchKernelGGL(k_deblock_rows_p, dim3(grid_x, G), dim3(64), 0, st, R);
-            } else {   // P pictures of the stream hub: the form without the bS 4 filter, or - when the picture has intra macroblocks - the one with it
-                // (while the recent P pictures had next to none, the second launch holds one picture at a time: see k_deblock_rows)
-                R.need_intra = -1; filter(false, G);
-                R.need_intra = 1; filter(true, e->p_intra_x16 > 16u * PINTRA_SPARSE_MBS ? G : 1u);
-            }
-        }
-    }
+    if (e->keep_pre) { rc = step_keep_pre(e, T); if (rc) return rc; }
+    if (!e->cfg.disable_deblock && !T.inj) step_filter(e, T, P.pic_serial, db_serial);
     // Quality report: source against the reconstruction that is now final (behind the loop filter; behind the last reconstruction
     // kernel when nothing is filtered).  On the second stream, beside the entropy coder and behind the filter's event: the chain to the
     // next picture's k_me (this stream) does not wait for it.  An injected picture's ring holds nothing to compare.
@@ -468,9 +540,7 @@ int submit_step(mi355x_h264_encoder* e, Step& T)
             HIPCHK(e->err, hipEventRecord(e->q_ready, st));
             HIPCHK(e->err, hipStreamWaitEvent(ec, e->q_ready, 0));
         }
-        LAUNCH2(ind, k_sse<true>, k_sse<false>, dim3((unsigned)e->b_rows * SSE_SEGS, G), dim3(64), ec, P, S.h_qpart, S.h_qmap);
-        // SSIM: behind k_sse on the same stream and in front of q_done[cur] and `done`, so the three hazards hold for it unchanged
-        if (T.lay.ssim) LAUNCH2(ind, k_ssim<true>, k_ssim<false>, dim3((unsigned)e->b_rows * SSIM_SEGS, G), dim3(64), ec, P, S.h_spart, S.h_smap);
+        step_quality(e, T, P, ec);   // (k_ssim in front of q_done[cur] and `done` like k_sse: the three hazards hold for it unchanged)
         if (!ind) { HIPCHK(e->err, hipEventRecord(e->q_done[cur], ec)); e->q_done_set[cur] = true; }   // (hazard "ring slot", above)
     }
     if (fork) HIPCHK(e->err, hipStreamWaitEvent(st, Y.entropy_done, 0));   // join: the next picture rewrites MbInfo / levels
@@ -491,8 +561,10 @@ int submit(mi355x_h264_encoder* e, const uint8_t* d_src, size_t src_item_stride,
     const bool idr = e->seq.next_is_idr(e->cfg.gop) || (e->after_injected && !inj);
     e->seq.begin(idr);
     e->after_injected = inj != nullptr;
+    for (int g = 0; g < e->G; g++) S.pics[g] = batch_item_pic(e->seq.pic(0, e->qp, idr, e->nrefs), g, e->idr_step);
     Step T;
     T.d_src = d_src; T.src_item_stride = src_item_stride; T.nv12 = nv12; T.idr = idr; T.n = e->G;
+    T.items = S.pics;
     e->last_src = d_src;
     T.sync = &S.sync;
     T.slot = &S;
@@ -526,9 +598,10 @@ int wait_slot(mi355x_h264_encoder* e, int slot_idx)
     return rc;
 }
 
-// finish the access unit of batch item g on the host: S = the buffers it was written to, L = where and of which type
-int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
+// finish the access unit of picture `pic` on the host: S = the buffers it was written to, L = where and of which type
+int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, const ItemPic& pic, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
+    const int g = pic.item, nal_hdr = slice_nal_hdr(L.idr, pic.layer);
     uint8_t* base = S.h_au + (size_t)g * e->st_au;
     const SliceInfo* const info = S.h_info + (size_t)g * e->b_nsl;   // one per slice of this instance's band
     for (int sl = 0; sl < e->b_nsl; sl++)
@@ -551,13 +624,13 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
         e->p_intra_x16 = (3 * e->p_intra_x16 + 16 * (searched - tq_coded)) / 4;
     }
     if (frame_type) *frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
-    e->last_layer = L.layer;
-    e->last_rband[g] = L.rband;
+    e->last_layer = pic.layer;
+    e->last_rband[g] = pic.rband;
     std::vector<uint8_t>& eb = e->esc_buf[g];
     if (e->nsl > 1) {
         // several slices: one NAL unit each, put together here (the payloads lie slice_cap apart in the pinned buffer)
         size_t pos = 0;
-        if (L.rband == 0) {   // intra refresh: the access unit that starts a cycle opens with the recovery point SEI
+        if (pic.rband == 0) {   // intra refresh: the access unit that starts a cycle opens with the recovery point SEI
             eb.clear();
             append_recovery_point_sei(eb, e->nsl);   // (n = the stream's slices)
             pos = eb.size();
@@ -568,7 +641,7 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
             const SliceInfo& si = info[sl];
             const uint8_t* pay = base + (size_t)(e->b_sl0 + sl) * e->slice_cap;
             uint8_t* o = eb.data() + pos;
-            o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 1; o[4] = (uint8_t)L.nal_hdr;
+            o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 1; o[4] = (uint8_t)nal_hdr;
             pos += 5;
             if (si.epb_count == 0) { memcpy(eb.data() + pos, pay, si.total_bytes); pos += si.total_bytes; }
             else pos += nal_escape(pay, si.total_bytes, eb.data() + pos);
@@ -581,7 +654,7 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
     uint8_t* au = base + L.au_start;
     size_t pos = 0;
     if (L.idr) { memcpy(au, e->sps_pps.data(), e->sps_pps.size()); pos = e->sps_pps.size(); }
-    au[pos++] = 0; au[pos++] = 0; au[pos++] = 0; au[pos++] = 1; au[pos++] = (uint8_t)L.nal_hdr;
+    au[pos++] = 0; au[pos++] = 0; au[pos++] = 0; au[pos++] = 1; au[pos++] = (uint8_t)nal_hdr;
     if (info->epb_count == 0) {
         *out = au;
         *out_len = (uint32_t)(pos + info->total_bytes);
@@ -595,12 +668,13 @@ int finish_au(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t
     return MI355X_H264_OK;
 }
 
-// the quality record of item g's picture: the rows of the band added up (k_sse left one partial per wave and plane).  A
+// the quality record of picture `pic`: the rows of the band added up (k_sse left one partial per wave and plane).  A
 // picture that was refused (E_OVERFLOW) or injected has a record with valid = 0
-void quality_record(mi355x_h264_encoder* e, const Slot& S, const AuLayout& L, int g, uint32_t bytes, bool compared)
+void quality_record(mi355x_h264_encoder* e, const Slot& S, const AuLayout& L, const ItemPic& pic, uint32_t bytes, bool compared)
 {
+    const int g = pic.item;
     mi355x_h264_quality q{};
-    q.bytes = bytes; q.qp = (uint32_t)e->qp; q.frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
+    q.bytes = bytes; q.qp = (uint32_t)pic.qp; q.frame_type = L.idr ? MI355X_H264_FRAME_IDR : MI355X_H264_FRAME_P;
     e->q_map[g] = nullptr;
     if (compared) {
         const unsigned long long* part = S.h_qpart + ((size_t)g * e->mbh + e->b_row0) * SSE_SEGS * 3;
@@ -643,10 +717,11 @@ void quality_record(mi355x_h264_encoder* e, const Slot& S, const AuLayout& L, in
     if (idx < e->s_recs.size()) e->s_recs[idx] = s;
 }
 
-int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, int g, uint8_t** out, uint32_t* out_len, int* frame_type)
+int finish_item(mi355x_h264_encoder* e, Slot& S, const AuLayout& L, const ItemPic& pic, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
-    const int rc = finish_au(e, S, L, g, out, out_len, frame_type);
-    if (L.quality) quality_record(e, S, L, g, rc == MI355X_H264_OK ? *out_len : 0, rc == MI355X_H264_OK && L.quality == 1);
+    const int rc = finish_au(e, S, L, pic, out, out_len, frame_type);
+    const int g = pic.item;
+    if (L.quality) quality_record(e, S, L, pic, rc == MI355X_H264_OK ? *out_len : 0, rc == MI355X_H264_OK && L.quality == 1);
     else {   // (coded with the switch off: nothing to read for this picture)
         if (!e->q_have.empty()) e->q_have[g] = 0;
         if (!e->s_have.empty()) e->s_have[g] = 0;
@@ -719,7 +794,7 @@ int quality_set(mi355x_h264_encoder* e, unsigned metrics)
 int collect(mi355x_h264_encoder* e, int slot_idx, uint8_t** out, uint32_t* out_len, int* frame_type)
 {
     const int rc = wait_slot(e, slot_idx);
-    return rc ? rc : finish_item(e, e->slots[slot_idx], e->slots[slot_idx].lay, 0, out, out_len, frame_type);
+    return rc ? rc : finish_item(e, e->slots[slot_idx], e->slots[slot_idx].lay, e->slots[slot_idx].pics[0], out, out_len, frame_type);
 }
 
 void destroy_engine(mi355x_h264_encoder* e)

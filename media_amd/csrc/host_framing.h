@@ -11,6 +11,8 @@
 #include <cstring>
 #include <vector>
 
+#include "item_word.h"   // ItemPic
+
 namespace {
 
 // floor(2^32 / n) + 1: x / n = mulhi(x, inv) for the ranges dev_common.h states (SliceRows, MbDiv); n = 1 has no 32-bit
@@ -43,7 +45,7 @@ struct PicSeq {
     int last_cur = -1;           // ring slot of the last picture that went out (-1: none yet)
     bool next_is_idr(int gop) const { return force_idr || frames == 0 || frame_in_gop >= gop; }
     void begin(bool idr) { if (idr) { frame_in_gop = 0; refs_in_gop = 0; frame_num = 0; force_idr = 0; } }
-    // of the picture begun: its layer, and the two facts k_me takes (dev_common.h ME_PARK, ME_SEED_PARK)
+    // of the picture begun: its layer, and the two facts k_me takes (item_word.h ME_PARK, ME_SEED_PARK)
     int layer() const { return layers == 2 ? (frame_in_gop & 1) : 0; }
     int me_facts(bool idr) const { return layers != 2 || idr ? 0 : layer() ? 1 : 2; }
     int refresh_n = 0;           // intra refresh: the number of bands (the stream's slices), 0 = off
@@ -53,6 +55,11 @@ struct PicSeq {
     // reference pictures the picture begun has, of a stream that searches nrefs: those coded since the stream's last IDR picture
     // (0, 1, 2, .. up to nrefs).  The one rule of the engine and the stream hub: a forced IDR restarts it with begin()
     int avail_refs(bool idr, int nrefs) const { return idr ? 0 : std::min(nrefs, refs_in_gop); }
+    // the record of the picture begun (engine.h, Step): batch item `item` of a stream that codes at qp and searches nrefs pictures
+    ItemPic pic(int item, int qp, bool idr, int nrefs) const
+    {
+        return ItemPic{item, cur, qp, frame_num, idr_id, avail_refs(idr, nrefs), layer(), me_facts(idr), refresh_band(idr)};
+    }
     // the slot of the last picture that went out (before the first: the slot behind cur, as ever)
     int last_slot(int nbuf) const { return last_cur >= 0 ? last_cur : (cur + nbuf - 1) % nbuf; }
     // the picture went out: idr_step = what an IDR picture adds to idr_pic_id (the engine: its stride times the batch)
@@ -72,9 +79,9 @@ inline int refresh_bands(int mbh, int slices)
     const int n = std::min(slices, std::max(1, mbh / 2)), rows = (mbh + n - 1) / n;
     return (mbh + rows - 1) / rows;
 }
-// one picture of an indirect step (engine.h, Step): the batch item it belongs to and that stream's state for the picture
-// (nref: PicSeq::avail_refs; layer, me: PicSeq::layer, me_facts; rband: PicSeq::refresh_band)
-struct ItemPic { int item, cur, qp, frame_num, idr_id, nref, layer, me, rband; };
+// the record of item g of a direct batch, from item 0's: the items move in lockstep and differ in their idr_pic_id alone, which
+// steps by the engine's stride (mi355x_h264_set_idr_pic_id) and wraps at 256
+inline ItemPic batch_item_pic(ItemPic p, int g, int idr_step) { p.item = g; p.idr_id = (p.idr_id + g * idr_step) & 0xFF; return p; }
 // first byte of a slice NAL unit: nal_ref_idc 3 for an IDR picture, 2 for a P picture others refer to, 0 for a layer-1 picture
 inline int slice_nal_hdr(bool idr, int layer) { return idr ? ((3 << 5) | 5) : layer ? 1 : ((2 << 5) | 1); }
 

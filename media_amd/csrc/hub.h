@@ -182,8 +182,9 @@ void hub_run_step(Hub* h, HubStep& T)
         const bool scaled = h->scaled;
         for (int k = 0; k < n; k++) {
             const HubItem& it = h->items[pics[k].item];
-            h_itemtab[k] = (uint32_t)pics[k].item | ((uint32_t)pics[k].cur << 8) | ((uint32_t)pics[k].nref << 10) | ((uint32_t)pics[k].me << 12) | ((uint32_t)pics[k].qp << 16) |
-                           ((uint32_t)(pics[k].rband + 1) << ITEM_RFR_SHIFT);
+            bool bad = false;
+            h_itemtab[k] = item_word(pics[k], &bad);
+            if (bad) rc = set_err(e->err, MI355X_H264_E_INTERNAL, "step position %d: a fact of the picture does not fit the itemtab word", k);
             // the picture the kernels read: the caller's own (read where it lies), or the item's staging slot
             h_src[k] = (unsigned long long)(uintptr_t)(it.d_in ? it.d_in : h->d_stage + (size_t)pics[k].item * h->st_stage);
             // (a scaling RGBA hub: the conversion reads the item's slot of the resampled RGBA pictures)
@@ -234,12 +235,8 @@ void hub_run_step(Hub* h, HubStep& T)
         HubItem& it = h->items[pics[k].item];
         it.rc = rc;
         if (rc == MI355X_H264_OK) {
-            AuLayout L = St.lay;   // (the layer is the position's: streams of both kinds share the step)
-            L.layer = pics[k].layer; L.nal_hdr = slice_nal_hdr(idr, L.layer);
-            L.rband = pics[k].rband;   // (intra refresh: the streams of a step stand at different bands)
-            it.rc = finish_item(e, e->slots[0], L, pics[k].item, &it.out, &it.out_len, &it.frame_type);
+            it.rc = finish_item(e, e->slots[0], St.lay, pics[k], &it.out, &it.out_len, &it.frame_type);
             if (it.rc != MI355X_H264_OK) snprintf(it.err, sizeof(it.err), "%s", e->err);
-            if (St.lay.quality) e->q_item[pics[k].item].qp = (uint32_t)pics[k].qp;   // (the position's own QP, not the engine's)
         } else snprintf(it.err, sizeof(it.err), "%s", errtxt);
         T.rc[k] = it.rc;
     }

@@ -142,7 +142,7 @@ struct HubSched {
             for (int k = 0; k < T.n; k++) {
                 Item& b = items[q[k]];
                 b.seq.begin(idr);
-                T.picks[k] = ItemPic{q[k], b.seq.cur, b.qp, b.seq.frame_num, b.seq.idr_id, b.seq.avail_refs(idr, nrefs), b.seq.layer(), b.seq.me_facts(idr), b.seq.refresh_band(idr)};
+                T.picks[k] = b.seq.pic(q[k], b.qp, idr, nrefs);
                 T.rc[k] = 0;
             }
             // positions by their number of reference pictures, most first (queue order within a number): the motion search of

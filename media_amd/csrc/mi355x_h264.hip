@@ -191,7 +191,7 @@ int mi355x_h264_encode_gops_device(mi355x_h264_encoder* e, const void* d_frames,
             int r = wait_slot(e, slot);
             for (int g = 0; g < G && !r; g++) {
                 uint8_t* p = nullptr; uint32_t n = 0;
-                r = finish_item(e, e->slots[slot], e->slots[slot].lay, g, &p, &n, nullptr);
+                r = finish_item(e, e->slots[slot], e->slots[slot].lay, e->slots[slot].pics[g], &p, &n, nullptr);
                 if (r) break;
                 if (gop_bytes[g] + n > out_cap_per_gop) return set_err(e->err, MI355X_H264_E_OVERFLOW, "gop output buffer too small");
                 memcpy(host_out + (size_t)g * out_cap_per_gop + gop_bytes[g], p, n);
@@ -340,7 +340,7 @@ int mi355x_h264_debug_code_syntax(mi355x_h264_encoder* e, const void* mbinfo, co
     char first[sizeof(e->err)] = {0};
     for (int g = 0; g < e->G; g++) {   // every item is finished, whatever became of the ones before it
         out[g] = nullptr; out_len[g] = 0;
-        const int r = finish_item(e, e->slots[slot], e->slots[slot].lay, g, &out[g], &out_len[g], frame_type);
+        const int r = finish_item(e, e->slots[slot], e->slots[slot].lay, e->slots[slot].pics[g], &out[g], &out_len[g], frame_type);
         if (r) { out[g] = nullptr; out_len[g] = 0; }
         if (r && !rc) { rc = r; memcpy(first, e->err, sizeof(first)); }
     }
