@@ -276,6 +276,8 @@ struct h264o_dec {
     int cur_is_ref, cur_frame_num, cur_is_idr, cur_pps_id;
     int max_mb_bits, max_level_prefix;
     int stat[H264O_DSTAT_COUNT];   /* h264o_dec_stat, of the picture being decoded */
+    uint32_t dbf[H264O_DBF_COUNT]; /* h264o_dec_dbf, of the picture being decoded */
+    int slice_qp[256];             /* SliceQP_Y per slice (for the statistics only) */
     char err[200];
 };
 
@@ -316,6 +318,8 @@ int h264o_dec_mb_qp(const h264o_dec *d, int addr) { return addr >= 0 && addr < d
 int h264o_dec_max_mb_bits(const h264o_dec *d) { return d->max_mb_bits; }
 int h264o_dec_max_level_prefix(const h264o_dec *d) { return d->max_level_prefix; }
 int h264o_dec_stat(const h264o_dec *d, int which) { return which >= 0 && which < H264O_DSTAT_COUNT ? d->stat[which] : -1; }
+const uint32_t *h264o_dec_dbf(const h264o_dec *d) { return d->dbf; }
+int h264o_dec_dbf_count(void) { return H264O_DBF_COUNT; }
 /* the statistics of the decoder whose picture is being decoded: the scaling and transform functions below are plain functions of
  * their arguments, so they find it here */
 static __thread int *g_stat;
@@ -1250,11 +1254,25 @@ static int decode_inter_mb(mbctx *c, int mbt /* P mb_type 0..4, -1 = P_Skip */, 
 
 /* ------------------------------------------------------------------ 8.7 deblocking filter */
 /* 8.7.2.3 / 8.7.2.4: one line of samples; p[i] = pix[-(i+1) * step], q[i] = pix[i * step] */
-static void filter_samples(uint8_t *pix, int step, int bS, int chroma, int chromaEdge, int indexA, int alpha, int beta)
+/* `st` (h264o_dec_dbf) only takes notes: nothing read from it, no sample depends on it */
+static void filter_samples(uint8_t *pix, int step, int bS, int chroma, int chromaEdge, int indexA, int indexB, int alpha, int beta, uint32_t *st)
 {
     (void)chromaEdge;
     const int p0 = pix[-step], p1 = pix[-2 * step], q0 = pix[0], q1 = pix[step];
+    uint8_t before[6];
+    for (int i = 0; i < 6; i++) before[i] = (chroma && (i == 0 || i == 5)) ? 0 : pix[(i - 3) * step];
+#define TAB(t, idx) st[H264O_DBF_TABLE(t, chroma, bS, idx)]++
+#define CELL(c) st[H264O_DBF_CELL(c, chroma, bS)]++
+    TAB(H264O_DBT_A_EVAL, indexA);
+    {
+        const int fa = abs(p0 - q0) < alpha, fp = abs(p1 - p0) < beta, fq = abs(q1 - q0) < beta;
+        if (!fa && fp && fq) CELL(H264O_DBC_REJ_ALPHA);
+        if (fa && !fp && fq) CELL(H264O_DBC_REJ_P);
+        if (fa && fp && !fq) CELL(H264O_DBC_REJ_Q);
+    }
     if (!(bS != 0 && abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta)) return;   /* filterSamplesFlag 8-468 */
+    TAB(H264O_DBT_A_FILT, indexA);
+    TAB(H264O_DBT_B_FILT, indexB);
     if (bS < 4) {
         const int tc0 = D_TC0[bS - 1][indexA];
         int tc, ap = 0, aq = 0, p2 = 0, q2 = 0;
@@ -1262,19 +1280,39 @@ static void filter_samples(uint8_t *pix, int step, int bS, int chroma, int chrom
             p2 = pix[-3 * step]; q2 = pix[2 * step];
             ap = abs(p2 - p0); aq = abs(q2 - q0);
             tc = tc0 + (ap < beta ? 1 : 0) + (aq < beta ? 1 : 0);
+            if (ap < beta) TAB(H264O_DBT_B_AP, indexB);
+            if (aq < beta) TAB(H264O_DBT_B_AQ, indexB);
+            CELL(H264O_DBC_APAQ_00 + 2 * (ap < beta) + (aq < beta));
         } else tc = tc0 + 1;
-        const int delta = clip3i(-tc, tc, ((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3));
+        const int raw = ((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3);
+        const int delta = clip3i(-tc, tc, raw);
+        CELL(raw < -tc ? H264O_DBC_DELTA_CLIP_NEG : raw > tc ? H264O_DBC_DELTA_CLIP_POS : raw ? H264O_DBC_DELTA_UNCLIPPED : H264O_DBC_DELTA_ZERO);
+        if (p0 + delta < 0) CELL(H264O_DBC_CLIP1_P0_AT_0);
+        if (p0 + delta > 255) CELL(H264O_DBC_CLIP1_P0_AT_255);
+        if (q0 - delta < 0) CELL(H264O_DBC_CLIP1_Q0_AT_0);
+        if (q0 - delta > 255) CELL(H264O_DBC_CLIP1_Q0_AT_255);
         pix[-step] = (uint8_t)clip1y(p0 + delta);
         pix[0] = (uint8_t)clip1y(q0 - delta);
         if (!chroma) {
-            if (ap < beta) pix[-2 * step] = (uint8_t)(p1 + clip3i(-tc0, tc0, (p2 + ((p0 + q0 + 1) >> 1) - (p1 << 1)) >> 1));
-            if (aq < beta) pix[step] = (uint8_t)(q1 + clip3i(-tc0, tc0, (q2 + ((p0 + q0 + 1) >> 1) - (q1 << 1)) >> 1));
+            if (ap < beta) {
+                const int r = (p2 + ((p0 + q0 + 1) >> 1) - (p1 << 1)) >> 1;
+                CELL(r < -tc0 ? H264O_DBC_P1_CLIP_NEG : r > tc0 ? H264O_DBC_P1_CLIP_POS : H264O_DBC_P1_UNCLIPPED);
+                pix[-2 * step] = (uint8_t)(p1 + clip3i(-tc0, tc0, r));
+            }
+            if (aq < beta) {
+                const int r = (q2 + ((p0 + q0 + 1) >> 1) - (q1 << 1)) >> 1;
+                CELL(r < -tc0 ? H264O_DBC_Q1_CLIP_NEG : r > tc0 ? H264O_DBC_Q1_CLIP_POS : H264O_DBC_Q1_UNCLIPPED);
+                pix[step] = (uint8_t)(q1 + clip3i(-tc0, tc0, r));
+            }
         }
     } else {
         if (!chroma) {
             const int p2 = pix[-3 * step], q2 = pix[2 * step], p3 = pix[-4 * step], q3 = pix[3 * step];
             const int ap = abs(p2 - p0), aq = abs(q2 - q0);
             const int small = abs(p0 - q0) < ((alpha >> 2) + 2);
+            if (ap < beta) TAB(H264O_DBT_B_AP, indexB);
+            if (aq < beta) TAB(H264O_DBT_B_AQ, indexB);
+            if (small) CELL(H264O_DBC_STRONG_00 + 2 * (ap < beta) + (aq < beta)); else CELL(H264O_DBC_STRONG_FALSE);
             if (ap < beta && small) {
                 pix[-step] = (uint8_t)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
                 pix[-2 * step] = (uint8_t)((p2 + p1 + p0 + q0 + 2) >> 2);
@@ -1290,6 +1328,10 @@ static void filter_samples(uint8_t *pix, int step, int bS, int chroma, int chrom
             pix[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
         }
     }
+    for (int i = 0; i < 6; i++)
+        if (!(chroma && (i == 0 || i == 5)) && before[i] != pix[(i - 3) * step]) { TAB(H264O_DBT_A_CHANGED, indexA); break; }
+#undef TAB
+#undef CELL
 }
 static int is_intra(const dmb *m) { return m->kind == DMB_I4 || m->kind == DMB_I16 || m->kind == DMB_IPCM; }
 /* 8.7.2.1 for frame macroblocks of P / I slices: p-side 4x4 block bp of mp, q-side bq of mq (raster indices) */
@@ -1311,11 +1353,12 @@ static void deblock_picture(h264o_dec *d)
             const dmb *mq = &d->mb[my * mbw + mx];
             const int idc = d->slice_idc[mq->slice & 255], oa = d->slice_oa[mq->slice & 255], ob = d->slice_ob[mq->slice & 255];
             if (idc == 1) continue;
+            uint32_t *cx = d->dbf + H264O_DBF_CTX;
             /* 8.7: filterLeftMbEdgeFlag / filterTopMbEdgeFlag */
             int fleft = mx > 0, ftop = my > 0;
             if (idc == 2) {
-                if (fleft && d->mb[my * mbw + mx - 1].slice != mq->slice) fleft = 0;
-                if (ftop && d->mb[(my - 1) * mbw + mx].slice != mq->slice) ftop = 0;
+                if (fleft && d->mb[my * mbw + mx - 1].slice != mq->slice) { fleft = 0; cx[H264O_DBX_IDC2_SLICE_EDGE_ALONE]++; }
+                if (ftop && d->mb[(my - 1) * mbw + mx].slice != mq->slice) { ftop = 0; cx[H264O_DBX_IDC2_SLICE_EDGE_ALONE]++; }
             }
             for (int dir = 0; dir < 2; dir++)        /* vertical edges (left to right) first, then horizontal (top to bottom) */
                 for (int e = 0; e < 4; e++) {
@@ -1329,16 +1372,28 @@ static void deblock_picture(h264o_dec *d)
                         else { bq = 4 * e + blk; bp = e ? bq - 4 : 12 + blk; }
                         const int bS = derive_bS(mp, bp, mq, bq, e == 0);
                         if (!bS) continue;
+                        cx[H264O_DBX_EDGE + 4 * dir + e]++;
+                        if (e == 0) {   /* contexts of a macroblock edge, per line with bS != 0 */
+                            if (mp->qp != mq->qp) {
+                                cx[dir == 0 ? H264O_DBX_LEFT_QP_DIFF : H264O_DBX_TOP_QP_DIFF]++;
+                                if ((mp->qp + mq->qp) & 1) cx[dir == 0 ? H264O_DBX_LEFT_QP_ODD : H264O_DBX_TOP_QP_ODD]++;
+                            }
+                            if (mp->kind == DMB_IPCM) cx[H264O_DBX_PCM_P]++;
+                            if (mq->kind == DMB_IPCM) cx[H264O_DBX_PCM_Q]++;
+                            if (mp->slice != mq->slice && idc == 0 && d->slice_qp[mp->slice & 255] != d->slice_qp[mq->slice & 255]) cx[H264O_DBX_IDC0_SLICE_EDGE_QP_DIFF]++;
+                            if (mp->t8x8 != mq->t8x8) cx[H264O_DBX_T8_BESIDE_4X4]++;
+                        }
                         {   /* luma */
                             const int qpav = (mp->qp + mq->qp + 1) >> 1;
                             const int indexA = clip3i(0, 51, qpav + oa), indexB = clip3i(0, 51, qpav + ob);
                             uint8_t *pix = dir == 0 ? Y + (size_t)(16 * my + k) * cw + 16 * mx + 4 * e : Y + (size_t)(16 * my + 4 * e) * cw + 16 * mx + k;
-                            filter_samples(pix, dir == 0 ? 1 : cw, bS, 0, 0, indexA, D_ALPHA[indexA], D_BETA[indexB]);
+                            filter_samples(pix, dir == 0 ? 1 : cw, bS, 0, 0, indexA, indexB, D_ALPHA[indexA], D_BETA[indexB], d->dbf);
                         }
                         /* chroma (4:2:0): edges 0 and 2 of the luma grid are chroma edges 0 and 4; chroma sample k/2 takes the
                          * bS of the luma sample position 2 * (k/2) (8.7.2: "bS of the corresponding luma edge") */
                         if (!(e & 1) && !(k & 1)) {
                             const int kc = k >> 1, ec = 2 * e;   /* chroma sample offset of the edge: 0 or 4 */
+                            int idxa_cb = 0;
                             for (int pl = 0; pl < 2; pl++) {
                                 const int qpp = mp->kind == DMB_IPCM ? qpc_of(d, 0, pl) : qpc_of(d, mp->qp, pl);
                                 const int qpq = mq->kind == DMB_IPCM ? qpc_of(d, 0, pl) : qpc_of(d, mq->qp, pl);
@@ -1346,7 +1401,14 @@ static void deblock_picture(h264o_dec *d)
                                 const int indexA = clip3i(0, 51, qpav + oa), indexB = clip3i(0, 51, qpav + ob);
                                 uint8_t *C = d->cur.pl[1 + pl];
                                 uint8_t *pix = dir == 0 ? C + (size_t)(8 * my + kc) * cs + 8 * mx + ec : C + (size_t)(8 * my + ec) * cs + 8 * mx + kc;
-                                filter_samples(pix, dir == 0 ? 1 : cs, bS, 1, 1, indexA, D_ALPHA[indexA], D_BETA[indexB]);
+                                if (pl == 0) idxa_cb = indexA; else if (idxa_cb != indexA) cx[H264O_DBX_CBCR_DIFF]++;
+                                for (int sd = 0; sd < 2; sd++) {   /* qPI of either side clipped (8.5.8); an I_PCM side has QP_Y 0 */
+                                    const dmb *ms = sd ? mq : mp;
+                                    const int qpi = (ms->kind == DMB_IPCM ? 0 : ms->qp) + d->cqp_off[pl];
+                                    if (qpi < 0) cx[H264O_DBX_QPI_CLIP_0]++;
+                                    if (qpi > 51) cx[H264O_DBX_QPI_CLIP_51]++;
+                                }
+                                filter_samples(pix, dir == 0 ? 1 : cs, bS, 1, 1, indexA, indexB, D_ALPHA[indexA], D_BETA[indexB], d->dbf);
                             }
                         }
                     }
@@ -1491,6 +1553,7 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
         for (int i = 0; i < nmb; i++) d->mb[i].kind = DMB_NONE;
         d->max_mb_bits = 0; d->max_level_prefix = 0;
         memset(d->stat, 0, sizeof(d->stat));
+        memset(d->dbf, 0, sizeof(d->dbf));
         d->cur_is_ref = nal_ref_idc != 0; d->cur_frame_num = frame_num; d->cur_is_idr = nal_type == 5;
         if (nal_type == 5) d->nrefs = 0;   /* 8.2.1: an IDR picture marks all reference pictures unused before it is decoded */
         d->cur_pps_id = (int)pps_id;
@@ -1505,7 +1568,7 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
     }
     if (d->slice_count >= 256) return fail(d, "more than 256 slices");
     const int sl = d->slice_count++;
-    d->slice_idc[sl] = idc; d->slice_oa[sl] = oa; d->slice_ob[sl] = ob;
+    d->slice_idc[sl] = idc; d->slice_oa[sl] = oa; d->slice_ob[sl] = ob; d->slice_qp[sl] = qp;
     d->slice_type = st;
     d->nal_type = nal_type;
     if (st == 0 && d->nrefs < 1) return fail(d, "P slice without a reference picture");

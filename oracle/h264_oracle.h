@@ -280,6 +280,35 @@ enum { H264O_DSTAT_MAX_INTERMEDIATE = 0, H264O_DSTAT_MAX_LEVEL, H264O_DSTAT_MAX_
        H264O_DSTAT_OUT_BOTTOM, H264O_DSTAT_COUNT };
 int h264o_dec_stat(const h264o_dec *d, int which);
 int h264o_dec_last_nal_type(const h264o_dec *d);
+/* what the loop filter (8.7) did to the last decoded picture: h264o_dec_dbf() is an array of H264O_DBF_COUNT counters, the filter's
+ * own account (the decode does not read it).  kind: 0 luma, 1 chroma; bS 1..4.
+ *   tables, H264O_DBF_TABLE(t, kind, bS, index 0..51): by indexA the lines evaluated (bS != 0), filtered (filterSamplesFlag) and
+ *     those where a sample changed; by indexB the lines filtered and, luma, those of them with ap < beta / with aq < beta
+ *   branch cells, H264O_DBF_CELL(c, kind, bS), lines: rejected by the alpha test alone / the p-side / the q-side beta test alone;
+ *     luma bS < 4 the four (ap < beta, aq < beta) combinations (APAQ_00 + 2 * ap + aq); delta clipped at -tc, at +tc, unclipped
+ *     and non-zero, zero; the p1 / q1 corrections clipped at -tc0, at +tc0, unclipped; Clip1 active on p0 + delta / q0 - delta at
+ *     0 and at 255; luma bS 4 the strong test true with each (ap, aq) combination, and false
+ *   contexts, H264O_DBF_CTX + c, lines with bS != 0 of a macroblock edge (IDC2_SLICE_EDGE_ALONE: macroblock edges): qPp != qPq at
+ *     a left / top edge and, among those, qPp + qPq odd; an I_PCM macroblock on the p / q side; a chroma line whose Cb and Cr
+ *     indexA differ; a side's qPI clipped at 0 / at 51; an edge between slices left alone under idc 2, and one filtered under idc 0
+ *     whose slices have different SliceQP_Y; transform_size_8x8_flag differing across the edge; EDGE + 4 * dir + e: lines of
+ *     (direction, edge 0..3) */
+enum { H264O_DBT_A_EVAL = 0, H264O_DBT_A_FILT, H264O_DBT_A_CHANGED, H264O_DBT_B_FILT, H264O_DBT_B_AP, H264O_DBT_B_AQ, H264O_DBT_COUNT };
+enum { H264O_DBC_REJ_ALPHA = 0, H264O_DBC_REJ_P, H264O_DBC_REJ_Q, H264O_DBC_APAQ_00, H264O_DBC_APAQ_01, H264O_DBC_APAQ_10, H264O_DBC_APAQ_11,
+       H264O_DBC_DELTA_CLIP_NEG, H264O_DBC_DELTA_CLIP_POS, H264O_DBC_DELTA_UNCLIPPED, H264O_DBC_DELTA_ZERO,
+       H264O_DBC_P1_CLIP_NEG, H264O_DBC_P1_CLIP_POS, H264O_DBC_P1_UNCLIPPED, H264O_DBC_Q1_CLIP_NEG, H264O_DBC_Q1_CLIP_POS, H264O_DBC_Q1_UNCLIPPED,
+       H264O_DBC_CLIP1_P0_AT_0, H264O_DBC_CLIP1_P0_AT_255, H264O_DBC_CLIP1_Q0_AT_0, H264O_DBC_CLIP1_Q0_AT_255,
+       H264O_DBC_STRONG_00, H264O_DBC_STRONG_01, H264O_DBC_STRONG_10, H264O_DBC_STRONG_11, H264O_DBC_STRONG_FALSE, H264O_DBC_COUNT };
+enum { H264O_DBX_LEFT_QP_DIFF = 0, H264O_DBX_TOP_QP_DIFF, H264O_DBX_LEFT_QP_ODD, H264O_DBX_TOP_QP_ODD, H264O_DBX_PCM_P, H264O_DBX_PCM_Q,
+       H264O_DBX_CBCR_DIFF, H264O_DBX_QPI_CLIP_0, H264O_DBX_QPI_CLIP_51, H264O_DBX_IDC2_SLICE_EDGE_ALONE, H264O_DBX_IDC0_SLICE_EDGE_QP_DIFF,
+       H264O_DBX_T8_BESIDE_4X4, H264O_DBX_EDGE, H264O_DBX_COUNT = H264O_DBX_EDGE + 8 };
+#define H264O_DBF_TABLE(t, kind, bS, idx) ((((t) * 2 + (kind)) * 4 + (bS) - 1) * 52 + (idx))
+#define H264O_DBF_CELLS (H264O_DBT_COUNT * 2 * 4 * 52)
+#define H264O_DBF_CELL(c, kind, bS) (H264O_DBF_CELLS + ((c) * 2 + (kind)) * 4 + (bS) - 1)
+#define H264O_DBF_CTX (H264O_DBF_CELLS + H264O_DBC_COUNT * 2 * 4)
+#define H264O_DBF_COUNT (H264O_DBF_CTX + H264O_DBX_COUNT)
+const uint32_t *h264o_dec_dbf(const h264o_dec *d);
+int h264o_dec_dbf_count(void);
 
 #ifdef __cplusplus
 }

@@ -18,43 +18,13 @@ import numpy as np
 import intra_refresh as ir
 import temporal as tl
 from temporal import Bits, pack, ue_bits, se_bits, escape, unescape, nal_units, annexb
+from slice_header import FN_BITS, Hdr, read_header, bits_of as _bits, rbsp as _rbsp
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dec_loss_streams.json")
-FN_BITS = 8
 TAINTED, CONCEALED = 1, 2
 
 
 # ---------------------------------------------------------------- slice headers of this encoder's streams
-
-Hdr = namedtuple("Hdr", "nal first_mb slice_type frame_num fn_pos idr ref_idc nact qp idc oa ob")
-
-
-def read_header(nal):
-    """slice_header() of a slice NAL unit (header byte first) as this encoder and the oracle write it"""
-    r = Bits(unescape(nal[1:])[:24])
-    idr, ref_idc = (nal[0] & 31) == 5, (nal[0] >> 5) & 3
-    first, st = r.ue(), r.ue()
-    assert r.ue() == 0, "pic_parameter_set_id"
-    fn_pos = r.p
-    fn = r.u(FN_BITS)
-    nact = None
-    if idr:
-        r.ue()
-    if st % 5 == 0:
-        if r.u(1):
-            nact = r.ue() + 1
-        assert r.u(1) == 0, "ref_pic_list_modification_flag_l0"
-    if ref_idc:
-        r.u(2 if idr else 1)
-    k = r.ue()
-    qp = 26 + ((k + 1) // 2 if k & 1 else -(k // 2))
-    idc = r.ue()
-    oa = ob = 0
-    if idc != 1:
-        k = r.ue(); oa = (k + 1) // 2 if k & 1 else -(k // 2)
-        k = r.ue(); ob = (k + 1) // 2 if k & 1 else -(k // 2)
-    return Hdr(nal[0], first, st, fn, fn_pos, idr, ref_idc, nact, qp, idc, oa, ob)
-
 
 def skip_slice(first_mb, count, frame_num, ref_idc, nact, qp, idc, oa=0, ob=0):
     """the NAL unit of ONE P slice of `count` macroblocks from first_mb on, all P_Skip: slice_header (7.3.3), slice_data (7.3.4) =
@@ -81,17 +51,6 @@ def rewrite_frame_num(nal, frame_num):
     bits = np.unpackbits(np.frombuffer(rbsp, np.uint8)).tolist()
     bits[h.fn_pos:h.fn_pos + FN_BITS] = [(frame_num >> k) & 1 for k in range(FN_BITS - 1, -1, -1)]
     return bytes([nal[0]]) + escape(pack(bits))
-
-
-def _bits(nal):
-    return np.unpackbits(np.frombuffer(unescape(nal[1:]), np.uint8)).tolist()
-
-
-def _rbsp(nal_hdr, bits):
-    """bits up to and including the stop bit, aligned anew"""
-    stop = len(bits) - 1 - bits[::-1].index(1)
-    b = bits[:stop + 1]
-    return bytes([nal_hdr]) + escape(pack(b + [0] * (-len(b) % 8)))
 
 
 def renumber_sps(nal, sps_id):

@@ -121,6 +121,8 @@ def lib():
             getattr(L, n).argtypes = [vp]
         L.h264o_dec_ref_age.argtypes = [vp, C.c_int]
         L.h264o_dec_stat.argtypes = [vp, C.c_int]
+        L.h264o_dec_dbf.restype = vp
+        L.h264o_dec_dbf.argtypes = [vp]
         L.h264o_dec_mb_kind.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_qp.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_mv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -385,6 +387,12 @@ class OracleDecoder:
         """h264o_dec_stat of the last decoded picture, by name"""
         return {n: lib().h264o_dec_stat(self.h, i) for i, n in enumerate(self.STATS)}
 
+    def dbf(self):
+        """h264o_dec_dbf of the last decoded picture: a Dbf (a copy)"""
+        n = lib().h264o_dec_dbf_count()
+        assert n == Dbf.COUNT, "oracle/h264_oracle.h and Dbf disagree about H264O_DBF_COUNT"
+        return Dbf(np.ctypeslib.as_array(C.cast(lib().h264o_dec_dbf(self.h), C.POINTER(C.c_uint32)), shape=(n,)).astype(np.int64))
+
     def close(self):
         if self.h:
             lib().h264o_dec_destroy(self.h)
@@ -392,3 +400,25 @@ class OracleDecoder:
 
     def __del__(self):
         self.close()
+
+
+class Dbf:
+    """the loop filter's account of one picture, or the sum of several (oracle/h264_oracle.h, H264O_DBF_*): tables[name] is
+    (kind 0 luma / 1 chroma, bS - 1, index 0..51), cells[name] is (kind, bS - 1), ctx[name] a number"""
+    TABLES = ("a_eval", "a_filt", "a_changed", "b_filt", "b_ap", "b_aq")
+    CELLS = ("rej_alpha", "rej_p", "rej_q", "apaq_00", "apaq_01", "apaq_10", "apaq_11", "delta_clip_neg", "delta_clip_pos", "delta_unclipped",
+             "delta_zero", "p1_clip_neg", "p1_clip_pos", "p1_unclipped", "q1_clip_neg", "q1_clip_pos", "q1_unclipped", "clip1_p0_at_0",
+             "clip1_p0_at_255", "clip1_q0_at_0", "clip1_q0_at_255", "strong_00", "strong_01", "strong_10", "strong_11", "strong_false")
+    CTX = ("left_qp_diff", "top_qp_diff", "left_qp_odd", "top_qp_odd", "pcm_p", "pcm_q", "cbcr_diff", "qpi_clip_0", "qpi_clip_51",
+           "idc2_slice_edge_alone", "idc0_slice_edge_qp_diff", "t8_beside_4x4") + tuple("edge_%d_%d" % (d, e) for d in range(2) for e in range(4))
+    COUNT = len(TABLES) * 416 + len(CELLS) * 8 + len(CTX)
+
+    def __init__(self, flat=None):
+        self.flat = np.zeros(self.COUNT, np.int64) if flat is None else flat
+        nt, nc = len(self.TABLES) * 416, len(self.CELLS) * 8
+        self.tables = dict(zip(self.TABLES, self.flat[:nt].reshape(len(self.TABLES), 2, 4, 52)))
+        self.cells = dict(zip(self.CELLS, self.flat[nt:nt + nc].reshape(len(self.CELLS), 2, 4)))
+        self.ctx = dict(zip(self.CTX, self.flat[nt + nc:]))
+
+    def __add__(self, other):
+        return Dbf(self.flat + other.flat)
