@@ -374,6 +374,53 @@ int mi355x_h264_stream_encode_nv12(mi355x_h264_stream *s, const uint8_t *y, int 
                                    uint8_t **out, uint32_t *out_len, int *frame_type);
 int mi355x_h264_stream_encode_rgba(mi355x_h264_stream *s, const uint8_t *rgba, int stride, uint8_t **out, uint32_t *out_len,
                                    int *frame_type);
+/* Damage tiles (tests/test_gpu_damage.py; media_amd/csrc/damage.h, k_patch.h; restated in tests/damage.py): a host call that
+ * transfers only the tiles of the picture that differ from the stream's previous picture.  The access units, the reconstruction
+ * and the quality records are byte for byte those of the ordinary call with the picture that is encoded (below).
+ *   Grid: tiles of 64 x 16 luma samples at multiples of (64, 16) over the SOURCE picture (mi355x_h264_stream_source_width x
+ *     _height); tile index = row of tiles * tiles per row + column.  Tiles at the right and bottom edge are partial.  A tile's
+ *     bytes: I420 64 x 16 Y, then 32 x 8 U, then 32 x 8 V (1536); NV12 64 x 16 Y, then 64 x 8 of the interleaved plane (1536);
+ *     RGBA 64 x 16 x 4 (4096).
+ *   Damage set, caller rectangles {x, y, w, h} in luma samples: every tile a rectangle touches after clipping to the picture; an
+ *     empty rectangle or one wholly outside adds nothing; n == 0: nothing changed.  n < 0 (other than the sentinel), n > 0 with
+ *     null rects, rects with the sentinel, or a negative w / h: MI355X_H264_E_ARG, and the stream stays as it was.
+ *   Damage set, n == MI355X_H264_DAMAGE_DETECT with null rects: every tile with at least one byte inside the picture that differs
+ *     from the previous picture (the library compares while it copies; the caller's stride padding is never read).
+ *   The picture that is encoded: the stream's previous picture with the damaged tiles replaced from the caller's picture.  With
+ *     detect that is exactly the caller's picture; with rectangles that miss a change it is the stated composition, not the
+ *     caller's picture.
+ *   Slot validity: every stream has a flag "the staging slot holds the previous picture".  A host call (ordinary or damage) that
+ *     succeeded sets it; it is clear at open, after every mi355x_h264_stream_encode_device call and after any call that failed
+ *     behind the argument checks (its upload or its step may have left the slot half written).  A call refused with
+ *     MI355X_H264_E_ARG changes nothing.  With the flag clear a damage call is an ordinary whole upload of the caller's picture,
+ *     whatever its rectangles say - the first picture of a stream always goes whole.
+ *   Payload: 16-byte header {uint32 magic "DAMG", layout, tiles, bytes per tile}, the tiles' uint32 indices in ascending order,
+ *     zeros up to a multiple of 16, the tiles at their full nominal size (bytes of a partial tile outside the picture are
+ *     unspecified and never stored): payload = ((16 + 4 * tiles + 15) & ~15) + tiles * bytes per tile.  It goes over the link in
+ *     ONE transfer, and one kernel launch per step (k_patch_step) writes the tiles of all its pictures into their slots.
+ *   Fallback: the call goes patched when 0 < payload < the tight picture's bytes (w * h * 3 / 2, RGBA w * h * 4); with payload >=
+ *     picture the picture that is encoded goes whole in one transfer; with no damaged tile nothing is transferred or patched and
+ *     the picture is encoded from the slot as it is.
+ * The ordinary calls are untouched: they transfer whole pictures.  Not on the direct mi355x_h264_encode* path or the batch calls. */
+typedef struct mi355x_h264_rect { int32_t x, y, w, h; } mi355x_h264_rect;
+#define MI355X_H264_DAMAGE_DETECT (-0x44414D47)   /* as n, with null rects: the library finds the damage */
+enum { MI355X_H264_UPLOAD_WHOLE = 0,      /* the whole picture went over the link                                      */
+       MI355X_H264_UPLOAD_PATCHED = 1,    /* a payload of damaged tiles                                                */
+       MI355X_H264_UPLOAD_NOTHING = 2,    /* no tile was damaged: nothing went                                         */
+       MI355X_H264_UPLOAD_IN_PLACE = 3 }; /* mi355x_h264_stream_encode_device: the picture was read where it lay       */
+int mi355x_h264_stream_encode_damage(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *u, int u_stride,
+                                     const uint8_t *v, int v_stride, const mi355x_h264_rect *rects, int n,
+                                     uint8_t **out, uint32_t *out_len, int *frame_type);
+int mi355x_h264_stream_encode_nv12_damage(mi355x_h264_stream *s, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride,
+                                          const mi355x_h264_rect *rects, int n, uint8_t **out, uint32_t *out_len, int *frame_type);
+int mi355x_h264_stream_encode_rgba_damage(mi355x_h264_stream *s, const uint8_t *rgba, int stride, const mi355x_h264_rect *rects, int n,
+                                          uint8_t **out, uint32_t *out_len, int *frame_type);
+/* The stream's last picture that got past the argument checks: bytes put on the link for it; damaged tiles (a whole upload
+ * that had no damage set - an ordinary call, or a damage call on an invalid slot - counts every tile; in place: 0); tiles of the
+ * grid; MI355X_H264_UPLOAD_*.  Any pointer may be null.  Before the first picture: 0, 0, the grid, WHOLE. */
+int mi355x_h264_stream_last_upload(const mi355x_h264_stream *s, uint64_t *bytes, uint32_t *tiles, uint32_t *tiles_total, int *mode);
+/* test hook: k_patch_step launches of the stream's engine so far, and the tiles they wrote */
+int mi355x_h264_stream_debug_patch_stats(const mi355x_h264_stream *s, uint64_t *launches, uint64_t *tiles);
 int mi355x_h264_stream_set_qp(mi355x_h264_stream *s, int qp);            /* as mi355x_h264_set_qp            */
 int mi355x_h264_stream_force_idr(mi355x_h264_stream *s);                 /* as mi355x_h264_force_idr         */
 int mi355x_h264_stream_set_idr_pic_id(mi355x_h264_stream *s, int next);  /* idr_pic_id of the next IDR       */

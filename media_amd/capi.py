@@ -49,11 +49,16 @@ EXPORTS = [
     "mi355x_h264_dec_set_loss_mode", "mi355x_h264_dec_damage", "mi355x_h264_dec_damage_map",
     "mi355x_h264_dec_group_set_loss_mode", "mi355x_h264_dec_group_damage", "mi355x_h264_dec_group_damage_map",
     "mi355x_h264_parser_set_loss_mode", "mi355x_h264_parser_loss",
+    "mi355x_h264_stream_encode_damage", "mi355x_h264_stream_encode_nv12_damage", "mi355x_h264_stream_encode_rgba_damage",
+    "mi355x_h264_stream_last_upload", "mi355x_h264_stream_debug_patch_stats",
 ]
 E_ARG, E_OVERFLOW = -1, -5   # MI355X_H264_E_*
 INPUT_I420, INPUT_NV12, INPUT_RGBA = 0, 1, 2   # MI355X_H264_INPUT_*
 STREAM_MULTIREF, STREAM_TEMPORAL2, STREAM_INTRA_REFRESH = 1, 8, 32   # MI355X_H264_STREAM_* (mi355x_h264_stream_open_ex)
 MATRIX_BT709, MATRIX_BT601 = 1, 6   # MI355X_H264_MATRIX_* (matrix_coefficients, Table E-5)
+DAMAGE_DETECT = -0x44414D47   # MI355X_H264_DAMAGE_DETECT
+UPLOAD_WHOLE, UPLOAD_PATCHED, UPLOAD_NOTHING, UPLOAD_IN_PLACE = range(4)   # MI355X_H264_UPLOAD_*
+UPLOAD_NAMES = ["whole", "patched", "nothing", "in_place"]
 
 
 class Config(C.Structure):
@@ -61,6 +66,21 @@ class Config(C.Structure):
                 ("bitrate", C.c_int32), ("gop", C.c_int32), ("profile_idc", C.c_int32), ("rc_mode", C.c_int32),
                 ("qp", C.c_int32), ("device", C.c_int32), ("disable_deblock", C.c_int32),
                 ("batch", C.c_int32), ("input_format", C.c_int32), ("slices", C.c_int32), ("band_index", C.c_int32), ("band_count", C.c_int32), ("refs", C.c_int32), ("search", C.c_int32)]
+
+
+class Rect(C.Structure):
+    """mi355x_h264_rect"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+def _damage_args(damage):
+    """(rects pointer or None, n, what to keep alive) of Stream.encode*(damage=...): "detect", or a sequence of (x, y, w, h)"""
+    if isinstance(damage, str):
+        if damage != "detect":
+            raise ValueError("damage: None, \"detect\" or a list of (x, y, w, h)")
+        return None, DAMAGE_DETECT, None
+    rects = (Rect * max(1, len(damage)))(*[Rect(*[int(v) for v in r]) for r in damage])
+    return (rects if len(damage) else None), len(damage), rects
 
 
 class Colour(C.Structure):
@@ -189,6 +209,13 @@ def lib():
         L.mi355x_h264_stream_encode_device.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_encode_nv12.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.mi355x_h264_stream_encode_rgba.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        if hasattr(L, "mi355x_h264_stream_encode_damage"):
+            tail = [C.POINTER(Rect), C.c_int, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+            L.mi355x_h264_stream_encode_damage.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int] + tail
+            L.mi355x_h264_stream_encode_nv12_damage.argtypes = [vp, vp, C.c_int, vp, C.c_int] + tail
+            L.mi355x_h264_stream_encode_rgba_damage.argtypes = [vp, vp, C.c_int] + tail
+            L.mi355x_h264_stream_last_upload.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+            L.mi355x_h264_stream_debug_patch_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mi355x_h264_stream_set_qp.argtypes = [vp, C.c_int]
         L.mi355x_h264_stream_force_idr.argtypes = [vp]
         L.mi355x_h264_stream_set_idr_pic_id.argtypes = [vp, C.c_int]
@@ -642,12 +669,32 @@ class Stream:
             err.rc = rc
             raise err
 
-    def encode(self, i420, strides=None):
-        """host I420; with strides = (y, u, v) in bytes, i420 is the three planes as separate arrays"""
+    def encode(self, i420, strides=None, damage=None):
+        """host I420; with strides = (y, u, v) in bytes, i420 is the three planes as separate arrays.  damage (here and on the NV12
+        and RGBA forms): None - the ordinary call, the whole picture; "detect" or [(x, y, w, h), ...] - the damage call
+        (mi355x_h264_stream_encode_damage): only the tiles that changed are transferred"""
         ((y, ys), (u, us), (v, vs)), keep = _planes(i420, self.src_width, self.src_height, strides)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode(self.h, y, ys, u, us, v, vs, C.byref(out), C.byref(n), C.byref(ft)))
+        if damage is None:
+            self._check(lib().mi355x_h264_stream_encode(self.h, y, ys, u, us, v, vs, C.byref(out), C.byref(n), C.byref(ft)))
+        else:
+            rects, nr, keep2 = _damage_args(damage)
+            self._check(lib().mi355x_h264_stream_encode_damage(self.h, y, ys, u, us, v, vs, rects, nr, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
+
+    @property
+    def last_upload(self):
+        """what the stream's last picture put on the link (mi355x_h264_stream_last_upload): bytes, damaged tiles, the grid's
+        tiles, mode ("whole" / "patched" / "nothing" / "in_place")"""
+        b, t, tt, m = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int()
+        self._check(lib().mi355x_h264_stream_last_upload(self.h, C.byref(b), C.byref(t), C.byref(tt), C.byref(m)))
+        return {"bytes": b.value, "tiles": t.value, "tiles_total": tt.value, "mode": UPLOAD_NAMES[m.value]}
+
+    def patch_stats(self):
+        """k_patch_step launches of this stream's engine so far and the tiles they wrote (mi355x_h264_stream_debug_patch_stats)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(lib().mi355x_h264_stream_debug_patch_stats(self.h, C.byref(a), C.byref(b)))
+        return {"launches": a.value, "tiles": b.value}
 
     def encode_device(self, dev_ptr):
         """one tight picture in the stream's layout, in device memory of the stream's device; read in place"""
@@ -655,18 +702,26 @@ class Stream:
         self._check(lib().mi355x_h264_stream_encode_device(self.h, C.c_void_p(dev_ptr), C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
-    def encode_nv12(self, nv12, strides=None):
+    def encode_nv12(self, nv12, strides=None, damage=None):
         """host NV12 (Y plane then interleaved UV); with strides = (y, uv), nv12 is the two planes as separate arrays"""
         ((y, ys), (uv, uvs)), keep = _planes(nv12, self.src_width, self.src_height, strides, nv12=True)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode_nv12(self.h, y, ys, uv, uvs, C.byref(out), C.byref(n), C.byref(ft)))
+        if damage is None:
+            self._check(lib().mi355x_h264_stream_encode_nv12(self.h, y, ys, uv, uvs, C.byref(out), C.byref(n), C.byref(ft)))
+        else:
+            rects, nr, keep2 = _damage_args(damage)
+            self._check(lib().mi355x_h264_stream_encode_nv12_damage(self.h, y, ys, uv, uvs, rects, nr, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
-    def encode_rgba(self, rgba, stride=None):
+    def encode_rgba(self, rgba, stride=None, damage=None):
         """host RGBA (height x width x 4 bytes, or rows `stride` bytes apart)"""
         f = np.ascontiguousarray(rgba, dtype=np.uint8)
         out, n, ft = C.c_void_p(), C.c_uint32(), C.c_int()
-        self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.src_width), C.byref(out), C.byref(n), C.byref(ft)))
+        if damage is None:
+            self._check(lib().mi355x_h264_stream_encode_rgba(self.h, f.ctypes.data, int(stride or 4 * self.src_width), C.byref(out), C.byref(n), C.byref(ft)))
+        else:
+            rects, nr, keep2 = _damage_args(damage)
+            self._check(lib().mi355x_h264_stream_encode_rgba_damage(self.h, f.ctypes.data, int(stride or 4 * self.src_width), rects, nr, C.byref(out), C.byref(n), C.byref(ft)))
         return C.string_at(out.value, n.value), ft.value
 
     def last_error(self):

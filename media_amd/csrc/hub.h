@@ -25,6 +25,16 @@ struct HubItem {
     // scaling hubs: the tight source picture (the caller's device picture or the item's source staging slot); the step's scaler
     // writes the I420 staging slot (RGBA: the item's RGBA staging slot, which the conversion launch then reads)
     const uint8_t* scale_src = nullptr;
+    // damage tiles (damage.h).  slot_valid: the stream's staging slot and its pinned twin hold the stream's last picture - set by a
+    // host call that succeeded, clear at open, after a device-form call and after a call that failed (a failed upload or step
+    // leaves the twin written and the slot partly or not: they may differ).  patch_tiles: tiles of this call's payload, which the
+    // step's patch launch writes into the slot (0: none).  up_*: mi355x_h264_stream_last_upload.  mark: scratch, one byte per tile
+    bool slot_valid = false;
+    uint32_t patch_tiles = 0;
+    uint64_t up_bytes = 0;
+    uint32_t up_tiles = 0;
+    int up_mode = damage::MODE_WHOLE;
+    std::vector<uint8_t> mark;
     int rc = 0, frame_type = 0;
     uint8_t* out = nullptr;
     uint32_t out_len = 0;
@@ -34,9 +44,9 @@ struct HubItem {
 struct HubCtx {
     StepSync sync;                   // a stream pair of its own
     // the step's tables, one pinned block and one transfer: [source address per position][itemtab word per position][RGBA hubs:
-    // {address, row stride}][scaling hubs: ScaleSrc per position]
+    // {address, row stride}][scaling hubs: ScaleSrc per position][steps with damage tiles: PatchSrc per picture that has some]
     enum { TAB_SRC = 0, TAB_ITEM = MAX_BATCH * 8, TAB_RGBA = TAB_ITEM + MAX_BATCH * 4, TAB_SCALE = TAB_RGBA + MAX_BATCH * 16,
-           TAB_BYTES = TAB_SCALE + MAX_BATCH * (int)sizeof(ScaleSrc) };
+           TAB_PATCH = TAB_SCALE + MAX_BATCH * (int)sizeof(ScaleSrc), TAB_BYTES = TAB_PATCH + MAX_BATCH * (int)sizeof(PatchSrc) };
     uint8_t* h_tab = nullptr;        // pinned
     uint8_t* d_tab = nullptr;
 };
@@ -65,6 +75,11 @@ struct Hub {
     uint8_t* d_src = nullptr;
     uint8_t* h_src = nullptr;
     size_t st_src = 0;
+    // damage tiles: [cap] payloads (damage.h: header, tile indices, tiles) on their way to the step's patch launch, st_src apart (a
+    // payload that goes is smaller than the picture); allocated with the hub's first damage call
+    uint8_t* d_patch = nullptr;
+    uint8_t* h_patch = nullptr;
+    std::atomic<uint64_t> patch_launches{0}, patch_tiles{0};   // k_patch_step launches of this hub and the tiles they wrote (test hook)
     // uploads: item k on copy stream k % NCOPY.  Two streams fill most of the link (tools/ubench_h2d.hip: 1 stream 32 GB/s, 2: 46-51,
     // 4+: 52-57); HIP streams are a scarce resource on this runtime - beyond about a dozen live streams in the process every launch
     // gets slower (measured: 8 copy streams per hub halved the throughput at 64 streams)
@@ -180,6 +195,9 @@ void hub_run_step(Hub* h, HubStep& T)
         RgbaSrc* const h_rgbatab = (RgbaSrc*)(c.h_tab + HubCtx::TAB_RGBA);
         ScaleSrc* const h_scaletab = (ScaleSrc*)(c.h_tab + HubCtx::TAB_SCALE);
         const bool scaled = h->scaled;
+        PatchSrc* const h_patchtab = (PatchSrc*)(c.h_tab + HubCtx::TAB_PATCH);
+        int npatch = 0;
+        uint32_t patch_most = 0, patch_sum = 0;
         for (int k = 0; k < n; k++) {
             const HubItem& it = h->items[pics[k].item];
             bool bad = false;
@@ -193,10 +211,21 @@ void hub_run_step(Hub* h, HubStep& T)
             if (scaled) h_scaletab[k] = ScaleSrc{(unsigned long long)(uintptr_t)it.scale_src, (uint32_t)(rgba ? 4 * h->sw : h->sw),
                                                  (uint32_t)(rgba ? 0 : h->fmt == MI355X_H264_INPUT_NV12 ? h->sw : h->sw / 2), (uint32_t)h->fmt, 0};
             if (it.staged && hipStreamWaitEvent(Y.st, it.copied, 0) != hipSuccess) rc = MI355X_H264_E_HIP;
+            if (it.staged && it.patch_tiles) {   // the picture came as damage tiles: they go into the slot the upload would have filled
+                const size_t item = (size_t)pics[k].item;
+                uint8_t* const slot = scaled ? h->d_src + item * h->st_src : rgba ? h->d_rgba + item * h->st_rgba : h->d_stage + item * h->st_stage;
+                h_patchtab[npatch++] = PatchSrc{(unsigned long long)(uintptr_t)(h->d_patch + item * h->st_src), (unsigned long long)(uintptr_t)slot,
+                                                it.patch_tiles, (uint32_t)h->fmt, (uint32_t)h->sw, (uint32_t)h->sh};
+                patch_most = std::max(patch_most, it.patch_tiles); patch_sum += it.patch_tiles;
+            }
         }
-        const size_t tab_bytes = scaled ? HubCtx::TAB_SCALE + (size_t)n * sizeof(ScaleSrc) : rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
+        const size_t tab_bytes = npatch ? HubCtx::TAB_PATCH + (size_t)npatch * sizeof(PatchSrc) : scaled ? HubCtx::TAB_SCALE + (size_t)n * sizeof(ScaleSrc) : rgba ? HubCtx::TAB_RGBA + (size_t)n * sizeof(RgbaSrc) : HubCtx::TAB_ITEM + (size_t)n * sizeof(uint32_t);
         if (hipMemcpyAsync(c.d_tab, c.h_tab, tab_bytes, hipMemcpyHostToDevice, Y.st) != hipSuccess) rc = MI355X_H264_E_HIP;
         const unsigned long long* const d_srctab = (const unsigned long long*)(c.d_tab + HubCtx::TAB_SRC);
+        if (rc == MI355X_H264_OK && npatch) {   // one patch launch for the step (k_patch.h), behind the `copied` waits and in front of every reader of a slot
+            hipLaunchKernelGGL(k_patch_step, dim3((patch_most + 3) / 4, (unsigned)npatch), dim3(256), 0, Y.st, (const PatchSrc*)(c.d_tab + HubCtx::TAB_PATCH));
+            h->patch_launches++; h->patch_tiles += patch_sum;
+        }
         if (rc == MI355X_H264_OK && scaled) {   // one scaling launch for the step: every position, all planes (scale_kernels.h)
             const int w = h->cfg.width, hh = h->cfg.height, th = scale_tile_rows(h->sh, hh);
             const ScalePlane PY = scale_plane_make(h->sw, h->sh, w, hh), PC = scale_plane_make(h->sw / 2, h->sh / 2, w / 2, hh / 2);
@@ -249,7 +278,12 @@ struct mi355x_h264_stream { Hub* hub; int item; };
 
 namespace {
 
-int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint32_t* out_len, int* frame_type)
+// a damage call's request: rects[0 .. n - 1], or n == MI355X_H264_DAMAGE_DETECT with null rects
+struct DamageReq { const mi355x_h264_rect* rects; int n; };
+static_assert(sizeof(mi355x_h264_rect) == sizeof(damage::Rect), "the ABI's rectangle is damage.h's");
+
+// dmg: null for the ordinary calls, which transfer the whole picture
+int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint32_t* out_len, int* frame_type, const DamageReq* dmg = nullptr)
 {
     Hub* h = s->hub;
     HubItem& it = h->items[s->item];
@@ -262,14 +296,52 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
     if (in.layout == PIC_NV12 && (in.stride[0] < w || in.stride[1] < w)) return refuse("stride smaller than width");
     if (in.layout == PIC_RGBA && in.stride[0] < 4 * w) return refuse("stride smaller than 4 * width");
     if (in.layout == HUB_IN_DEVICE && rgba && ((uintptr_t)in.p[0] & 7) != 0) return refuse("RGBA picture not aligned to 8 bytes");
+    const bool detect = dmg && dmg->n == MI355X_H264_DAMAGE_DETECT;
+    if (dmg && detect && dmg->rects) return refuse("damage: MI355X_H264_DAMAGE_DETECT takes no rectangles");
+    if (dmg && !detect) {
+        it.mark.clear();
+        if (!damage::rects_to_tiles(w, hh, (const damage::Rect*)dmg->rects, dmg->n, it.mark))
+            return refuse("damage: a negative count, a count without rectangles, or a rectangle of negative width or height");
+    }
     if (hipSetDevice(h->cfg.device) != hipSuccess) return set_err(it.err, MI355X_H264_E_HIP, "hipSetDevice");
     const uint64_t t_in = now_us();
     const bool staged = in.layout != HUB_IN_DEVICE;
     bool ok = true;
-    if (staged && h->scaled) {
+    it.patch_tiles = 0;
+    it.up_bytes = staged ? picture_bytes(in.layout, w, hh) : 0; it.up_tiles = staged ? (uint32_t)damage::tiles_total(w, hh) : 0;
+    it.up_mode = staged ? damage::MODE_WHOLE : damage::MODE_IN_PLACE;
+    // the payload pair comes with the hub's first damage call, valid slot or not (under the scheduler's lock, as the other pairs)
+    auto patch_pair = [&] { return !dmg || DM_PAIR(h->mem, h->d_patch, h->h_patch, h->st_src * h->sched.cap); };
+    if (staged && dmg && it.slot_valid) {
+        // 0. a damage call on a valid slot: the slot and its pinned twin hold the stream's last picture (the stream's calls are
+        // synchronous: every reader of the slot finished before the last call returned).  The damaged tiles go into the twin, which
+        // then holds the picture that is encoded; over the link goes the payload (damage.h) for the step's patch launch, or the
+        // twin whole when the payload would not be smaller, or nothing.
+        const int nopen = h->sched.begin_upload(patch_pair);
+        if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the damage payloads");
+        const size_t st = h->scaled ? h->st_src : rgba ? h->st_rgba : h->st_stage, off = (size_t)item * st;
+        uint8_t* const hs = (h->scaled ? h->h_src : rgba ? h->h_rgba : h->h_stage) + off, * const ds = (h->scaled ? h->d_src : rgba ? h->d_rgba : h->d_stage) + off;
+        hipStream_t cs = h->copy_st[item % Hub::NCOPY];
+        const damage::Picture pic{in.layout, {in.p[0], in.p[1], in.p[2]}, {in.stride[0], in.stride[1], in.stride[2]}};
+        if (detect) damage::detect_and_copy(pic, w, hh, hs, it.mark);
+        else damage::copy_tiles(pic, w, hh, it.mark, hs);
+        const size_t ntiles = damage::count_tiles(it.mark);
+        it.d_in = nullptr;
+        if (h->scaled) it.scale_src = ds;
+        else if (rgba) { it.rgba_src = ds; it.rgba_stride = (size_t)w * 4; }
+        it.up_tiles = (uint32_t)ntiles; it.up_mode = damage::upload_mode(in.layout, w, hh, ntiles);
+        if (it.up_mode == damage::MODE_PATCHED) {
+            uint8_t* const hp = h->h_patch + (size_t)item * h->st_src;
+            it.up_bytes = damage::pack_payload(in.layout, w, hh, hs, it.mark, hp);
+            it.patch_tiles = (uint32_t)ntiles;
+            ok = hipMemcpyAsync(h->d_patch + (size_t)item * h->st_src, hp, it.up_bytes, hipMemcpyHostToDevice, cs) == hipSuccess && hipEventRecord(it.copied, cs) == hipSuccess;
+        } else if (it.up_mode == damage::MODE_WHOLE) {
+            ok = hipMemcpyAsync(ds, hs, it.up_bytes, hipMemcpyHostToDevice, cs) == hipSuccess && hipEventRecord(it.copied, cs) == hipSuccess;
+        } else it.up_bytes = 0;   // nothing changed: no transfer, no patch; the step waits for the slot's last transfer, long arrived
+    } else if (staged && h->scaled) {
         // a scaling hub's host picture goes to the stream's source staging slot, which comes with the hub's first host picture; the
         // step's scaler reads it after it.copied
-        const int nopen = h->sched.begin_upload([&] { return DM_PAIR(h->mem, h->d_src, h->h_src, h->st_src * h->sched.cap); });
+        const int nopen = h->sched.begin_upload([&] { return DM_PAIR(h->mem, h->d_src, h->h_src, h->st_src * h->sched.cap) && patch_pair(); });
         if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the source staging pictures");
         const size_t off = (size_t)item * h->st_src;
         it.d_in = nullptr; it.scale_src = h->d_src + off;
@@ -281,7 +353,7 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
         // 1. a host picture goes to the stream's staging slot (RGBA: to its RGBA staging slot, which comes with the hub's first host
         // RGBA picture; the step's conversion launch writes the I420 slot): pinned copy, then the transfer on the item's copy
         // stream; it.copied says when it has arrived
-        const int nopen = h->sched.begin_upload([&] { return in.layout != PIC_RGBA || DM_PAIR(h->mem, h->d_rgba, h->h_rgba, h->st_rgba * h->sched.cap); });
+        const int nopen = h->sched.begin_upload([&] { return (in.layout != PIC_RGBA || DM_PAIR(h->mem, h->d_rgba, h->h_rgba, h->st_rgba * h->sched.cap)) && patch_pair(); });
         if (nopen < 0) return set_err(it.err, MI355X_H264_E_NOMEM, "no memory for the RGBA staging pictures");
         const size_t off = (size_t)item * (in.layout == PIC_RGBA ? h->st_rgba : h->st_stage);
         uint8_t* const hs = (in.layout == PIC_RGBA ? h->h_rgba : h->h_stage) + off, * const ds = (in.layout == PIC_RGBA ? h->d_rgba : h->d_stage) + off;
@@ -302,7 +374,8 @@ int hub_encode(mi355x_h264_stream* s, const HostPicture& in, uint8_t** out, uint
     const uint64_t t_q = now_us();
     // 2. queue the picture; lead a step or wait for the one that takes it
     h->us_upload += t_q - t_in;
-    if (!h->sched.encode(item, staged, ok, [&](HubStep& T) { hub_run_step(h, T); })) return set_err(it.err, MI355X_H264_E_HIP, "upload of the picture failed");
+    if (!h->sched.encode(item, staged, ok, [&](HubStep& T) { hub_run_step(h, T); })) { it.slot_valid = false; return set_err(it.err, MI355X_H264_E_HIP, "upload of the picture failed"); }
+    it.slot_valid = staged && it.rc == MI355X_H264_OK;
     h->us_total += now_us() - t_in;
     *out = it.out; *out_len = it.out_len;
     if (frame_type) *frame_type = it.frame_type;

@@ -1,7 +1,7 @@
 // media_amd/csrc/mi355x_h264.hip -- the C ABI of include/mi355x_h264.h and include/mi355x_h264_dec.h.  The library is this ONE
 // translation unit: the kernels (k_*.h, rgba_kernels.h), host_framing.h (parameter sets, slice header, NAL escaping, tables; no
 // HIP), pic_store.h (what encoder and decoder share: ring, per-macroblock arrays, flags), engine.h (mi355x_h264_encoder),
-// hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side), dec_group.h
+// hub_sched.h + hub.h (the stream hub: scheduling without HIP, device side; damage.h + k_patch.h: its damage tiles), dec_group.h
 // (decoder groups) and decoder.h (the decoder peer: a group of one stream).  Every entry point below checks its arguments and
 // calls into one of them.  There is no CPU encode path:
 // without a HIP device create() fails.
@@ -38,6 +38,8 @@ using namespace h264;
 #include "host_framing.h"
 #include "rgba_kernels.h"
 #include "scale_kernels.h"
+#include "damage.h"
+#include "k_patch.h"
 #include "k_dec_out.h"
 #include "k_dec_out_scale.h"
 #include "dev_mem.h"
@@ -501,6 +503,51 @@ int mi355x_h264_stream_encode_rgba(mi355x_h264_stream* s, const uint8_t* rgba, i
 {
     if (!s || !rgba || !out || !out_len) return MI355X_H264_E_ARG;
     return hub_encode(s, HostPicture{PIC_RGBA, {rgba, nullptr, nullptr}, {stride, 0, 0}}, out, out_len, frame_type);
+}
+
+// damage tiles (hub.h, damage.h): the host calls with a damage set; every refusal leaves the stream as it was
+int mi355x_h264_stream_encode_damage(mi355x_h264_stream* s, const uint8_t* y, int ys, const uint8_t* u, int us, const uint8_t* v, int vs,
+                                     const mi355x_h264_rect* rects, int n, uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !y || !u || !v || !out || !out_len) return MI355X_H264_E_ARG;
+    const DamageReq d{rects, n};
+    return hub_encode(s, HostPicture{PIC_I420, {y, u, v}, {ys, us, vs}}, out, out_len, frame_type, &d);
+}
+
+int mi355x_h264_stream_encode_nv12_damage(mi355x_h264_stream* s, const uint8_t* y, int ys, const uint8_t* uv, int uvs, const mi355x_h264_rect* rects, int n,
+                                          uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !y || !uv || !out || !out_len) return MI355X_H264_E_ARG;
+    const DamageReq d{rects, n};
+    return hub_encode(s, HostPicture{PIC_NV12, {y, uv, nullptr}, {ys, uvs, 0}}, out, out_len, frame_type, &d);
+}
+
+int mi355x_h264_stream_encode_rgba_damage(mi355x_h264_stream* s, const uint8_t* rgba, int stride, const mi355x_h264_rect* rects, int n,
+                                          uint8_t** out, uint32_t* out_len, int* frame_type)
+{
+    if (!s || !rgba || !out || !out_len) return MI355X_H264_E_ARG;
+    const DamageReq d{rects, n};
+    return hub_encode(s, HostPicture{PIC_RGBA, {rgba, nullptr, nullptr}, {stride, 0, 0}}, out, out_len, frame_type, &d);
+}
+
+// (the stream's calls are synchronous and only they write the item's record: read without the hub's lock, as last_error is)
+int mi355x_h264_stream_last_upload(const mi355x_h264_stream* s, uint64_t* bytes, uint32_t* tiles, uint32_t* tiles_total, int* mode)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    const HubItem& it = s->hub->items[s->item];
+    if (bytes) *bytes = it.up_bytes;
+    if (tiles) *tiles = it.up_tiles;
+    if (tiles_total) *tiles_total = (uint32_t)damage::tiles_total(s->hub->sw, s->hub->sh);
+    if (mode) *mode = it.up_mode;
+    return MI355X_H264_OK;
+}
+
+int mi355x_h264_stream_debug_patch_stats(const mi355x_h264_stream* s, uint64_t* launches, uint64_t* tiles)
+{
+    if (!s) return MI355X_H264_E_ARG;
+    if (launches) *launches = s->hub->patch_launches.load();
+    if (tiles) *tiles = s->hub->patch_tiles.load();
+    return MI355X_H264_OK;
 }
 
 int mi355x_h264_stream_encode_device(mi355x_h264_stream* s, const void* d_pic, uint8_t** out, uint32_t* out_len, int* frame_type)

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include "MediaLog.h"
 #include "Property.h"
+#include "../csrc/damage.h"   // the key's parser (plain C++)
 
 namespace {
 bool Within(int32_t v, int32_t lo, int32_t hi) { return v >= lo && v <= hi; }
@@ -128,6 +129,23 @@ bool VideoEncoderMI355X::EngineOpen(const Settings &s)
     }
     if (m_intraRefresh > 0) {
         cfg.slices = m_intraRefresh;
+    }
+    // extension: "detect" = host pictures go through the damage calls, which transfer only the tiles that changed (include/
+    // mi355x_h264.h, "damage tiles"); the bytes of the stream are those of whole pictures.  Stream path and host memory only
+    const std::string damageKey = GetStrEncParam("persist.vmi.video.encode.damage");
+    const int32_t damage = ParseDamage(damageKey);
+    if (damage < 0) {
+        WARN("damage [%s] rejected (off | detect): off", damageKey.c_str());
+        SetEncParam("persist.vmi.video.encode.damage", "off");
+    }
+    m_damageDetect = damage > 0;
+    m_haveNextDamage = false;
+    m_damageInfoSaid = false;
+    if (m_damageDetect && (!shared || m_inputDevice)) {
+        INFO("damage detect: %s - whole pictures as without the key", !shared ? "an engine of its own has no staging slot to patch (persist.vmi.video.encode.shared = 0)"
+                                                                             : "pictures in device memory are read in place, nothing is transferred");
+        m_damageDetect = false;
+        m_damageInfoSaid = true;
     }
     if (shared) {
         cfg.input_format = m_input;
@@ -384,6 +402,28 @@ int32_t VideoEncoderMI355X::ParseIntraRefresh(const std::string &value, int32_t 
 
 bool VideoEncoderMI355X::ParseSsim(const std::string &value) { return value == "1"; }
 
+int32_t VideoEncoderMI355X::ParseDamage(const std::string &value) { return damage::parse_mode_key(value.c_str()); }
+
+bool VideoEncoderMI355X::SetNextDamage(const Rect *rects, int n)
+{
+    if (n < 0 || (n > 0 && rects == nullptr)) {
+        return false;
+    }
+    for (int i = 0; i < n; i++) {
+        if (rects[i].w < 0 || rects[i].h < 0) {
+            return false;
+        }
+    }
+    m_nextDamage.assign(rects, rects + n);
+    m_haveNextDamage = true;
+    return true;
+}
+
+bool VideoEncoderMI355X::LastUpload(uint64_t *bytes, uint32_t *tiles, uint32_t *tilesTotal, int *mode) const
+{
+    return m_stream != nullptr && mi355x_h264_stream_last_upload(m_stream, bytes, tiles, tilesTotal, mode) == MI355X_H264_OK;
+}
+
 int VideoEncoderMI355X::ParseColour(const std::string &colour, const std::string &range, mi355x_h264_colour *out)
 {
     if (colour.empty() && range.empty()) {
@@ -435,11 +475,35 @@ int VideoEncoderMI355X::ParseSourceSize(const std::string &width, const std::str
 int VideoEncoderMI355X::EncodePicture(const uint8_t *i420, uint8_t **out, uint32_t *outLen, int *frameType)
 {
     if (m_inputDevice) {   // one tight picture in device memory, in the object's layout
+        if (m_haveNextDamage && !m_damageInfoSaid) {
+            INFO("SetNextDamage: pictures in device memory are read in place, nothing is transferred");
+            m_damageInfoSaid = true;
+        }
         if (m_stream != nullptr) {
             return mi355x_h264_stream_encode_device(m_stream, i420, out, outLen, frameType);
         }
         return m_input == MI355X_H264_INPUT_RGBA ? mi355x_h264_encode_rgba_device(m_engine, i420, out, outLen, frameType)
                                                  : mi355x_h264_encode_device(m_engine, i420, out, outLen, frameType);
+    }
+    // damage tiles: the rectangles of SetNextDamage, else what the key says; stream path only (EngineOpen has said so for the key)
+    const bool useDamage = m_stream != nullptr && (m_haveNextDamage || m_damageDetect);
+    if (m_haveNextDamage && m_stream == nullptr && !m_damageInfoSaid) {
+        INFO("SetNextDamage: an engine of its own has no staging slot to patch - whole pictures");
+        m_damageInfoSaid = true;
+    }
+    const mi355x_h264_rect *rects = m_haveNextDamage && !m_nextDamage.empty() ? m_nextDamage.data() : nullptr;
+    const int nrects = m_haveNextDamage ? static_cast<int>(m_nextDamage.size()) : MI355X_H264_DAMAGE_DETECT;
+    if (useDamage && m_input == MI355X_H264_INPUT_RGBA) {
+        return mi355x_h264_stream_encode_rgba_damage(m_stream, i420, static_cast<int>(SrcWidth()) * 4, rects, nrects, out, outLen, frameType);
+    }
+    if (useDamage && m_input == MI355X_H264_INPUT_NV12) {
+        const int w = static_cast<int>(SrcWidth());
+        return mi355x_h264_stream_encode_nv12_damage(m_stream, i420, w, i420 + SrcLumaBytes(), w, rects, nrects, out, outLen, frameType);
+    }
+    if (useDamage) {
+        const int pitch = static_cast<int>(SrcWidth());
+        const uint8_t *u = i420 + SrcLumaBytes();
+        return mi355x_h264_stream_encode_damage(m_stream, i420, pitch, u, pitch / 2, u + SrcLumaBytes() / 4, pitch / 2, rects, nrects, out, outLen, frameType);
     }
     if (m_input == MI355X_H264_INPUT_RGBA) {
         const int stride = static_cast<int>(SrcWidth()) * 4;
@@ -484,6 +548,7 @@ bool VideoEncoderMI355X::EngineEncode(const uint8_t *i420, uint8_t **out, uint32
             m_sceneCuts++;
         }
     }
+    m_haveNextDamage = false;   // (SetNextDamage holds for this picture alone, its re-code included)
     if (rc != MI355X_H264_OK) {
         ERR("EncodeOneFrame: engine returned %d (%s)", rc,
             m_stream != nullptr ? mi355x_h264_stream_last_error(m_stream) : mi355x_h264_last_error(m_engine));

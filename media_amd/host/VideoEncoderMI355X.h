@@ -8,6 +8,8 @@
 #ifndef VIDEO_ENCODER_MI355X_H
 #define VIDEO_ENCODER_MI355X_H
 
+#include <vector>
+
 #include "PropertyDrivenEncoder.h"
 #include "mi355x_h264.h"
 
@@ -73,6 +75,21 @@ public:
     static int32_t ParseIntraRefresh(const std::string &value, int32_t slices, int32_t refs, int32_t layers, uint32_t height, bool *warn);
     // the all-intra band of the last picture that went out; -1 for an IDR picture, with refresh off and before the first
     int32_t LastRefreshBand() const { return m_lastRefreshBand; }
+    // extension key persist.vmi.video.encode.damage: "detect" -> every host picture goes through the damage call of its layout with
+    // MI355X_H264_DAMAGE_DETECT (include/mi355x_h264.h, "damage tiles": only the tiles that changed are transferred, the bytes of
+    // the stream are the same); "off", unset or empty -> 0, whole pictures; anything else -> -1: one WARN line, "off" is written
+    // back to the key and whole pictures go.  An engine of its own (.shared = 0) and pictures in device memory (.inputmem = device)
+    // have no staging slot to patch: whole pictures (device: none) go as before and one INFO line says so
+    static int32_t ParseDamage(const std::string &value);
+    // The rectangles of the NEXT EncodeOneFrame only, in luma samples of the picture that call is handed: it goes through the damage
+    // call with them (n = 0: nothing changed), whatever the key says; a scene-change re-code of that picture takes them again.  The
+    // picture that is encoded is the previous one with the tiles the rectangles touch replaced - rectangles that miss a change
+    // are the caller's affair.  false: n < 0, n > 0 without rectangles or a negative width / height - nothing was set.  On a path
+    // that cannot use damage the next picture goes whole and one INFO line says so
+    using Rect = mi355x_h264_rect;
+    bool SetNextDamage(const Rect *rects, int n);
+    // test hook: mi355x_h264_stream_last_upload of the object's stream; false with an engine of its own
+    bool LastUpload(uint64_t *bytes, uint32_t *tiles, uint32_t *tilesTotal, int *mode) const;
 
 protected:
     const char *BackendName() const override { return "MI355X HIP"; }
@@ -106,6 +123,8 @@ private:
     int32_t m_srcWidth = 0, m_srcHeight = 0;    // > 0: the pictures' size (.srcwidth / .srcheight), resampled to the coded size on the device
     bool m_inputDevice = false;                 // inputData is an address in the object's device's memory (.inputmem = device)
     int32_t m_intraRefresh = 0, m_lastRefreshBand = -1;     // .intrarefresh (bands, 0 off); the band of the last picture that went out
+    bool m_damageDetect = false, m_haveNextDamage = false, m_damageInfoSaid = false;   // .damage = detect; SetNextDamage holds for one picture
+    std::vector<mi355x_h264_rect> m_nextDamage;
     int32_t m_temporalLayers = 1, m_lastTemporalId = -1;   // .temporallayers; the layer of the last picture that went out
     // quality report (persist.vmi.video.encode.psnr = 1): the last picture's record and the sums of the GOP being coded
     bool m_psnr = false, m_haveQuality = false;

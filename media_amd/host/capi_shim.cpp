@@ -55,6 +55,24 @@ int32_t vc_last_refresh_band(void *enc)
     auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
     return m != nullptr ? m->LastRefreshBand() : -1;
 }
+// persist.vmi.video.encode.damage: 1 detect, 0 off / unset, -1 rejected (one WARN line, "off" written back)
+int32_t vc_parse_damage(const char *value) { return VideoEncoderMI355X::ParseDamage(value != nullptr ? value : ""); }
+// VideoEncoderMI355X::SetNextDamage; rects = n * {x, y, w, h} int32.  1: set, 0: refused, -1: not this backend
+int32_t vc_set_next_damage(void *enc, const int32_t *rects, int32_t n)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    if (m == nullptr) return -1;
+    return m->SetNextDamage(reinterpret_cast<const VideoEncoderMI355X::Rect *>(rects), n) ? 1 : 0;
+}
+// VideoEncoderMI355X::LastUpload: 0 (and the four values) or -1 (an engine of its own)
+int32_t vc_last_upload(void *enc, uint64_t *bytes, uint32_t *tiles, uint32_t *tilesTotal, int32_t *mode)
+{
+    auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));
+    int md = 0;
+    if (m == nullptr || !m->LastUpload(bytes, tiles, tilesTotal, &md)) return -1;
+    *mode = md;
+    return 0;
+}
 int32_t vc_last_temporal_id(void *enc)
 {
     auto *m = dynamic_cast<VideoEncoderMI355X *>(static_cast<VideoEncoder *>(enc));

@@ -39,6 +39,9 @@ def lib():
         L.vc_last_temporal_id.argtypes = [vp]
         L.vc_parse_intra_refresh.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]
         L.vc_last_refresh_band.argtypes = [vp]
+        L.vc_parse_damage.argtypes = [C.c_char_p]
+        L.vc_set_next_damage.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
+        L.vc_last_upload.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.vc_parse_psnr.argtypes = [C.c_char_p]
         L.vc_parse_ssim.argtypes = [C.c_char_p]
         L.vc_last_ssim.argtypes = [vp, vp]
@@ -108,6 +111,12 @@ def parse_intra_refresh(value, slices=0, refs=0, layers=1, height=1080):
     return n, bool(warn.value)
 
 
+def parse_damage(value):
+    """what persist.vmi.video.encode.damage = value selects: 1 for "detect", 0 for "off" and the unset key, -1 for anything else (one
+    WARN line, "off" written back)"""
+    return lib().vc_parse_damage(str(value).encode())
+
+
 def parse_ssim(value):
     """does persist.vmi.video.encode.ssim = value turn the quality report on with both metrics?  "1" only"""
     return bool(lib().vc_parse_ssim(str(value).encode()))
@@ -172,7 +181,7 @@ def ref_counts(nrefs, gop, n, forced=()):
 
 def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="baseline", fmt=3, qp=None, slices=None, input=None,
                    inputmem=None, refs=None, psnr=None, ssim=None, shared=None, srcwidth=None, srcheight=None, colour=None, range=None,
-                   temporallayers=None, intrarefresh=None):
+                   temporallayers=None, intrarefresh=None, damage=None):
     """fill the property store the way a 'video' mode cloud phone would"""
     prop_set("ro.vmi.demo.video.encode.format", fmt)
     prop_set("ro.sys.vmi.cloudphone", "video")
@@ -198,6 +207,7 @@ def set_video_mode(width, height, fps=30, bitrate=5000000, gop=30, profile="base
     prop_set("persist.vmi.video.encode.range", "" if range is None else range)            # limited | full } described stream
     prop_set("persist.vmi.video.encode.temporallayers", "" if temporallayers is None else temporallayers)   # 2: two temporal layers
     prop_set("persist.vmi.video.encode.intrarefresh", "" if intrarefresh is None else intrarefresh)       # n: intra refresh, n bands
+    prop_set("persist.vmi.video.encode.damage", "" if damage is None else damage)                         # detect: damage tiles; else off
     if shared is not None:
         prop_set("persist.vmi.video.encode.shared", shared)                               # 0: an engine of its own; else a stream
 
@@ -265,6 +275,20 @@ class VideoEncoder:
     def last_refresh_band(self):
         """the all-intra band of the last picture that went out (persist.vmi.video.encode.intrarefresh = n); -1: none"""
         return lib().vc_last_refresh_band(self.h)
+
+    def set_next_damage(self, rects):
+        """VideoEncoderMI355X::SetNextDamage: [(x, y, w, h), ...] for the next picture only; True when taken"""
+        flat = [int(v) for r in rects for v in r]
+        arr = (C.c_int32 * max(1, len(flat)))(*flat)
+        return lib().vc_set_next_damage(self.h, arr if rects else None, len(rects)) == 1
+
+    def last_upload(self):
+        """mi355x_h264_stream_last_upload of the object's stream as capi.Stream.last_upload gives it; None with an engine of its own"""
+        from media_amd import capi
+        b, t, tt, m = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        if lib().vc_last_upload(self.h, C.byref(b), C.byref(t), C.byref(tt), C.byref(m)) != 0:
+            return None
+        return {"bytes": b.value, "tiles": t.value, "tiles_total": tt.value, "mode": capi.UPLOAD_NAMES[m.value]}
 
     def scene_cuts(self):
         return lib().vc_scene_cuts(self.h)

@@ -5,8 +5,17 @@
 // (media_amd/lib/plugin_bench, recipe in media_amd/host/Makefile).  Configuration reaches the library through the property
 // store, seeded from environment variables as in tests/boundary/ref_header_caller.cpp.
 //
-// usage: plugin_bench [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
+// usage: plugin_bench [--damage detect] [--static-share P] [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] <i420 file with N pictures> <width> <height> <N> <frames per stream> <S1,S2,...> [input]
 // prints one JSON object per S on its own line.
+// --damage detect (anywhere on the line): the extension key persist.vmi.video.encode.damage = detect - every host picture goes through
+// the damage call, which transfers only the tiles that changed (include/mi355x_h264.h, "damage tiles").  With or without it the JSON
+// line carries upload_bytes_per_picture, link_gbps and damaged_tiles_per_picture / tiles_total from every picture's
+// mi355x_h264_stream_last_upload (read after its call, outside the latency sample).
+// --static-share P (anywhere on the line; host pictures only): content option - every stream keeps a picture of its own, and each
+// picture differs from the stream's last one only inside a window of consecutive tiles (64 x 16, raster order, wrapping) that covers
+// 100 - P % of the grid and moves by half its length per picture; inside the window the bytes come from the next picture of the
+// file, the rest is byte-identical.  The window is copied before the call's clock starts but inside the run's, with and without
+// --damage alike.
 // --refs N (anywhere on the line): the extension key persist.vmi.video.encode.refs = N - 2 or 3 reference pictures are searched
 // (every object a stream of a shared engine that keeps N + 1 reconstructions per stream); without it the key is left as found.
 // --temporal N (anywhere on the line): the extension key persist.vmi.video.encode.temporallayers = N - with 2 every second P picture
@@ -44,16 +53,34 @@
 #include <cmath>
 #include "VideoCodecApi.h"
 #include "mi355x_h264.h"
+#include "../media_amd/csrc/damage.h"   // the tile grid (plain C++)
 
 extern "C" int32_t vc_last_quality(void *enc, mi355x_h264_quality *out);   // media_amd/host/capi_shim.cpp
 extern "C" int32_t vc_last_ssim(void *enc, mi355x_h264_ssim *out);
 extern "C" int32_t vc_last_temporal_id(void *enc);
+extern "C" int32_t vc_last_upload(void *enc, uint64_t *bytes, uint32_t *tiles, uint32_t *tilesTotal, int32_t *mode);
 
 int main(int argc, char **argv)
 {
     for (int i = 1; i + 1 < argc; i++)   // --refs N: taken out of the line, the rest is positional
         if (strcmp(argv[i], "--refs") == 0) {
             setenv("PERSIST_VMI_VIDEO_ENCODE_REFS", argv[i + 1], 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    for (int i = 1; i + 1 < argc; i++)   // --damage detect: taken out of the line
+        if (strcmp(argv[i], "--damage") == 0) {
+            setenv("PERSIST_VMI_VIDEO_ENCODE_DAMAGE", argv[i + 1], 1);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    int staticShare = -1;
+    for (int i = 1; i + 1 < argc; i++)   // --static-share P: taken out of the line
+        if (strcmp(argv[i], "--static-share") == 0) {
+            staticShare = atoi(argv[i + 1]);
+            if (staticShare < 0 || staticShare > 100) { fprintf(stderr, "--static-share %s: 0 .. 100 expected\n", argv[i + 1]); return 2; }
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2;
             break;
@@ -110,7 +137,7 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s [--damage detect] [--static-share P] [--intra-refresh N] [--temporal N] [--refs N] [--psnr] [--ssim] [--src WxH] [--colour bt601|bt709] [--range limited|full] in.i420 w h pictures frames_per_stream S1,S2,... [i420|nv12|rgba[:device]]\n", argv[0]); return 2; }
     // (w, h: the size of the pictures in the file and in every call - the source size with --src)
     const int w = srcW > 0 ? srcW : atoi(argv[2]), h = srcW > 0 ? srcH : atoi(argv[3]), npic = atoi(argv[4]), frames = atoi(argv[5]);
     size_t fsz = (size_t)w * h * 3 / 2;
@@ -150,6 +177,9 @@ int main(int argc, char **argv)
         fsz = nsz;
         base = pics.data();
     }
+    if (device && staticShare >= 0) { fprintf(stderr, "--static-share makes host pictures\n"); return 2; }
+    const int dlayout = layout == "rgba" ? damage::LAYOUT_RGBA : layout == "nv12" ? damage::LAYOUT_NV12 : damage::LAYOUT_I420;
+    const int ntiles = damage::tiles_total(w, h), nwin = staticShare < 0 ? 0 : (int)(((int64_t)ntiles * (100 - staticShare) + 50) / 100);
     if (device) {   // upload once, before the clock
         void *hip = dlopen("libamdhip64.so", RTLD_NOW | RTLD_GLOBAL);
         auto dmalloc = hip ? reinterpret_cast<int (*)(void **, size_t)>(dlsym(hip, "hipMalloc")) : nullptr;
@@ -182,10 +212,24 @@ int main(int argc, char **argv)
         std::vector<uint64_t> sse((size_t)S * 3, 0), samples((size_t)S * 3, 0), windows((size_t)S * 3, 0);
         std::vector<int64_t> qsum((size_t)S * 3, 0);
         std::vector<uint64_t> lpics((size_t)S * 2, 0), lbytes((size_t)S * 2, 0);   // per temporal layer
+        std::vector<uint64_t> upBytes(S, 0), upTiles(S, 0);
+        // --static-share: every stream's own picture, as the warm-up call left it in the library
+        std::vector<std::vector<uint8_t>> own(staticShare >= 0 ? S : 0);
+        for (int k = 0; k < (int)own.size(); k++) own[k].assign(base + fsz * (size_t)(k % npic), base + fsz * (size_t)(k % npic) + fsz);
         auto work = [&](int k) {
             lat[k].reserve(frames);
+            std::vector<uint8_t> mark;
             for (int i = 0; i < frames; i++) {
                 const uint8_t *f = base + fsz * (size_t)((k + 1 + i) % npic);   // (the pool holds frames + S + 1 pictures: no wrap)
+                if (staticShare >= 0) {   // the window's tiles from the pool's picture into the stream's own
+                    mark.assign((size_t)ntiles, 0);
+                    const int start = nwin ? (int)(((int64_t)i * (nwin / 2 + 1) + 7 * k) % ntiles) : 0;
+                    for (int t = 0; t < nwin; t++) mark[(size_t)((start + t) % ntiles)] = 1;
+                    const size_t ysz = (size_t)w * h;
+                    const damage::Picture src{dlayout, {f, f + ysz, f + ysz + ysz / 4}, {dlayout == damage::LAYOUT_RGBA ? 4 * w : w, dlayout == damage::LAYOUT_I420 ? w / 2 : w, w / 2}};
+                    damage::copy_tiles(src, w, h, mark, own[k].data());
+                    f = own[k].data();
+                }
                 uint8_t *au = nullptr;
                 uint32_t n = 0;
                 const auto t0 = std::chrono::steady_clock::now();
@@ -193,6 +237,8 @@ int main(int argc, char **argv)
                 lat[k].push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
                 if (rc != VIDEO_ENCODER_SUCCESS) failures++;
                 else bytes[k] += n;
+                uint64_t ub = 0; uint32_t ut = 0, utt = 0; int32_t um = 0;
+                if (rc == VIDEO_ENCODER_SUCCESS && vc_last_upload(encs[k], &ub, &ut, &utt, &um) == 0) { upBytes[k] += ub; upTiles[k] += ut; }
                 if (temporal && rc == VIDEO_ENCODER_SUCCESS) {
                     const int tid = vc_last_temporal_id(encs[k]) == 1 ? 1 : 0;
                     lpics[(size_t)k * 2 + tid]++; lbytes[(size_t)k * 2 + tid] += n;
@@ -216,12 +262,19 @@ int main(int argc, char **argv)
         for (int k = 0; k < S; k++) { all.insert(all.end(), lat[k].begin(), lat[k].end()); total += bytes[k]; }
         std::sort(all.begin(), all.end());
         const size_t n = all.size();
-        char q[480] = "";
+        char q[720] = "";
+        {
+            uint64_t ub = 0, ut = 0;
+            for (int k = 0; k < S; k++) { ub += upBytes[k]; ut += upTiles[k]; }
+            snprintf(q, sizeof(q), ",\"upload_bytes_per_picture\":%.1f,\"link_gbps\":%.3f,\"damaged_tiles_per_picture\":%.1f,\"tiles_total\":%d,\"static_share\":%d",
+                     (double)ub / n, (double)ub / dt / 1e9, (double)ut / n, ntiles, staticShare);
+        }
         if (temporal) {
             uint64_t np[2] = {0, 0}, nb[2] = {0, 0};
             for (int k = 0; k < S; k++)
                 for (int l = 0; l < 2; l++) { np[l] += lpics[(size_t)k * 2 + l]; nb[l] += lbytes[(size_t)k * 2 + l]; }
-            snprintf(q, sizeof(q), ",\"pictures_l0\":%llu,\"pictures_l1\":%llu,\"bytes_l0\":%llu,\"bytes_l1\":%llu", (unsigned long long)np[0],
+            const size_t at = strlen(q);
+            snprintf(q + at, sizeof(q) - at, ",\"pictures_l0\":%llu,\"pictures_l1\":%llu,\"bytes_l0\":%llu,\"bytes_l1\":%llu", (unsigned long long)np[0],
                      (unsigned long long)np[1], (unsigned long long)nb[0], (unsigned long long)nb[1]);
         }
         if (psnr) {
