@@ -544,6 +544,12 @@ class Parser:
         i = self.info()
         return self._read(4, np.empty(i["mbw"] * i["mbh"], np.uint8))
 
+    def mbavail(self):
+        """per macroblock of the last picture: the neighbours left, above, above-right, above-left in its slice (bits 0..3) and usable
+        for intra prediction (bits 4..7)"""
+        i = self.info()
+        return self._read(7, np.empty(i["mbw"] * i["mbh"], np.uint8))
+
     def _read(self, what, arr):
         n = lib().mi355x_h264_parser_read(self.h, what, arr.ctypes.data, arr.nbytes)
         if n != arr.nbytes:

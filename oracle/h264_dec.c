@@ -242,6 +242,7 @@ typedef struct {
     int8_t refidx[4];      /* per 8x8 quadrant, -1 = not inter */
     int32_t refpic[4];     /* identity of the reference picture per quadrant (8.7.2.1 compares pictures, not indices) */
     uint16_t bits;         /* bits of macroblock_layer() (A.3.1 limit 3200) */
+    uint8_t avail;         /* h264o_dec_mb_avail: the neighbouring macroblocks as this one found them (for tests; nothing reads it) */
 } dmb;
 
 typedef struct { uint8_t *pl[3]; int frame_num; int32_t id; } dpic;
@@ -277,6 +278,7 @@ struct h264o_dec {
     int max_mb_bits, max_level_prefix;
     int stat[H264O_DSTAT_COUNT];   /* h264o_dec_stat, of the picture being decoded */
     uint32_t dbf[H264O_DBF_COUNT]; /* h264o_dec_dbf, of the picture being decoded */
+    uint32_t pred[H264O_PRED_COUNT];   /* h264o_dec_pred, of the picture being decoded */
     int slice_qp[256];             /* SliceQP_Y per slice (for the statistics only) */
     char err[200];
 };
@@ -315,14 +317,30 @@ int h264o_dec_last_nal_type(const h264o_dec *d) { return d->nal_type; }
  * macroblock_layer() in bits (A.3.1: <= 3200), the largest level_prefix met (A.2: <= 15 outside the High profiles) */
 int h264o_dec_mb_kind(const h264o_dec *d, int addr) { return addr >= 0 && addr < d->mbw * d->mbh ? d->mb[addr].kind : -1; }
 int h264o_dec_mb_qp(const h264o_dec *d, int addr) { return addr >= 0 && addr < d->mbw * d->mbh ? d->mb[addr].qp : -1; }   /* QP_Y (0 for I_PCM) */
+/* the neighbouring macroblocks (bit 0 left, 1 top, 2 top-right, 3 top-left) as macroblock `addr` of the last picture found them: available
+ * (6.4.8: in the picture, in its slice, decoded before it), and in bits 4..7 available for intra prediction as well (with
+ * constrained_intra_pred_flag an inter macroblock is not) - of an intra macroblock: the very values its prediction used */
+int h264o_dec_mb_avail(const h264o_dec *d, int addr) { return addr >= 0 && addr < d->mbw * d->mbh ? d->mb[addr].avail : -1; }
+/* the intra prediction modes of macroblock `addr` of the last picture: which 0..15 Intra4x4PredMode of the 4x4 block at raster position
+ * `which`, 16 Intra16x16PredMode, 17 intra_chroma_pred_mode */
+int h264o_dec_mb_intra_mode(const h264o_dec *d, int addr, int which)
+{
+    if (addr < 0 || addr >= d->mbw * d->mbh || which < 0 || which > 17) return -1;
+    return which < 16 ? d->mb[addr].i4mode[which] : which == 16 ? d->mb[addr].i16_mode : d->mb[addr].chroma_mode;
+}
 int h264o_dec_max_mb_bits(const h264o_dec *d) { return d->max_mb_bits; }
 int h264o_dec_max_level_prefix(const h264o_dec *d) { return d->max_level_prefix; }
 int h264o_dec_stat(const h264o_dec *d, int which) { return which >= 0 && which < H264O_DSTAT_COUNT ? d->stat[which] : -1; }
 const uint32_t *h264o_dec_dbf(const h264o_dec *d) { return d->dbf; }
 int h264o_dec_dbf_count(void) { return H264O_DBF_COUNT; }
+const uint32_t *h264o_dec_pred(const h264o_dec *d) { return d->pred; }
+int h264o_dec_pred_count(void) { return H264O_PRED_COUNT; }
 /* the statistics of the decoder whose picture is being decoded: the scaling and transform functions below are plain functions of
  * their arguments, so they find it here */
 static __thread int *g_stat;
+/* the prediction account (h264o_dec_pred) of that decoder: the sample interpolation and the plane predictors note Clip1 there.  Notes
+ * only: nothing is read from it */
+static __thread uint32_t *g_pred;
 static inline int trk(int v)   /* an intermediate of 8.5.10 - 8.5.13: its magnitude is noted, it is passed on unchanged */
 {
     if (g_stat) { const int a = v < 0 ? -(v + 1) : v;   /* (-2^15 is inside the range, 2^15 is not: -v - 1 puts both ends at 2^15 - 1) */
@@ -727,7 +745,11 @@ static int intra16x16_pred(int mode, int have_top, int have_left, int have_tl, c
         int H = 0, V = 0;
         for (int k = 0; k <= 7; k++) { H += (k + 1) * (P(8 + k, -1) - P(6 - k, -1)); V += (k + 1) * (P(-1, 8 + k) - P(-1, 6 - k)); }
         const int a = 16 * (P(-1, 15) + P(15, -1)), bb = (5 * H + 32) >> 6, c = (5 * V + 32) >> 6;
-        for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) out[16 * y + x] = (uint8_t)clip1y((a + bb * (x - 7) + c * (y - 7) + 16) >> 5);
+        for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) {
+            const int v = (a + bb * (x - 7) + c * (y - 7) + 16) >> 5;
+            if (g_pred && (v < 0 || v > 255)) g_pred[H264O_PRED_PLANE_CLIP + (v > 255)]++;
+            out[16 * y + x] = (uint8_t)clip1y(v);
+        }
     } else return -1;
     return 0;
 }
@@ -739,6 +761,7 @@ static int intra_chroma_pred(int mode, int have_top, int have_left, int have_tl,
             for (int bx = 0; bx < 2; bx++) {
                 int st = 0, sl = 0, v;
                 for (int k = 0; k < 4; k++) { if (have_top) st += P(4 * bx + k, -1); if (have_left) sl += P(-1, 4 * by + k); }
+                if (g_pred) g_pred[H264O_PRED_IC_DC + (2 * by + bx) * 4 + 2 * (have_left != 0) + (have_top != 0)]++;
                 if ((bx == 0 && by == 0) || (bx == 1 && by == 1)) {
                     if (have_top && have_left) v = (st + sl + 4) >> 3;
                     else if (have_left) v = (sl + 2) >> 2;
@@ -766,7 +789,11 @@ static int intra_chroma_pred(int mode, int have_top, int have_left, int have_tl,
         int H = 0, V = 0;
         for (int k = 0; k <= 3; k++) { H += (k + 1) * (P(4 + k, -1) - P(2 - k, -1)); V += (k + 1) * (P(-1, 4 + k) - P(-1, 2 - k)); }
         const int a = 16 * (P(-1, 7) + P(7, -1)), bb = (34 * H + 32) >> 6, c = (34 * V + 32) >> 6;
-        for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) out[8 * y + x] = (uint8_t)clip1y((a + bb * (x - 3) + c * (y - 3) + 16) >> 5);
+        for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) {
+            const int v = (a + bb * (x - 3) + c * (y - 3) + 16) >> 5;
+            if (g_pred && (v < 0 || v > 255)) g_pred[H264O_PRED_PLANE_CLIP + 2 + (v > 255)]++;
+            out[8 * y + x] = (uint8_t)clip1y(v);
+        }
     } else return -1;
     return 0;
 #undef P
@@ -792,13 +819,25 @@ static int luma_sample_interp(const h264o_dec *d, const dpic *r, int x, int y, i
 {
     const int G = ref_luma(d, r, x, y);
     if (xF == 0 && yF == 0) return G;
-    const int b = clip1y((b1_at(d, r, x, y) + 16) >> 5);       /* between G and H (right neighbour) */
-    const int h = clip1y((h1_at(d, r, x, y) + 16) >> 5);       /* between G and M (below)            */
+    const int rb = (b1_at(d, r, x, y) + 16) >> 5, b = clip1y(rb);       /* between G and H (right neighbour) */
+    const int rh = (h1_at(d, r, x, y) + 16) >> 5, h = clip1y(rh);       /* between G and M (below)            */
     const int j1 = tap(b1_at(d, r, x, y - 2), b1_at(d, r, x, y - 1), b1_at(d, r, x, y), b1_at(d, r, x, y + 1), b1_at(d, r, x, y + 2), b1_at(d, r, x, y + 3));
-    const int j = clip1y((j1 + 512) >> 10);
-    const int s = clip1y((b1_at(d, r, x, y + 1) + 16) >> 5);   /* b of the row below        */
-    const int m = clip1y((h1_at(d, r, x + 1, y) + 16) >> 5);   /* h of the column to the right */
+    const int rj = (j1 + 512) >> 10, j = clip1y(rj);
+    const int rs = (b1_at(d, r, x, y + 1) + 16) >> 5, s = clip1y(rs);   /* b of the row below        */
+    const int rm = (h1_at(d, r, x + 1, y) + 16) >> 5, m = clip1y(rm);   /* h of the column to the right */
     const int H = ref_luma(d, r, x + 1, y), M = ref_luma(d, r, x, y + 1);
+    if (g_pred) {   /* the account: Clip1 active on the intermediates this position uses (-1: none of that type) */
+        const int pos = 4 * yF + xF;
+        const int ub = (pos == 1 || pos == 2 || pos == 3 || pos == 5 || pos == 6 || pos == 7) ? rb : (pos == 13 || pos == 14 || pos == 15) ? rs : -1;
+        const int uh = (pos == 4 || pos == 8 || pos == 12 || pos == 5 || pos == 9 || pos == 13) ? rh : (pos == 7 || pos == 11 || pos == 15) ? rm : -1;
+        const int hasb = pos != 4 && pos != 8 && pos != 12 && pos != 9 && pos != 10 && pos != 11;
+        const int hash = pos != 1 && pos != 2 && pos != 3 && pos != 6 && pos != 10 && pos != 14;
+        const int hasj = pos == 6 || pos == 9 || pos == 10 || pos == 11 || pos == 14;
+        uint32_t *c = g_pred + H264O_PRED_L_CLIP + pos * 6;
+        if (hasb && (ub < 0 || ub > 255)) c[0 + (ub > 255)]++;
+        if (hash && (uh < 0 || uh > 255)) c[2 + (uh > 255)]++;
+        if (hasj && (rj < 0 || rj > 255)) c[4 + (rj > 255)]++;
+    }
     switch (4 * yF + xF) {
         case 1: return (G + b + 1) >> 1;   /* a */
         case 2: return b;
@@ -827,9 +866,77 @@ static int chroma_sample_interp(const h264o_dec *d, const dpic *r, int pl, int x
     return ((8 - xF) * (8 - yF) * A + xF * (8 - yF) * B + (8 - xF) * yF * C + xF * yF * D + 32) >> 6;
 }
 /* inter prediction of one partition (x0, y0, w, h in luma samples relative to the picture) */
-static void inter_pred_part(h264o_dec *d, const dpic *r, int x0, int y0, int w, int h, int mvx, int mvy)
+/* the account: the relation of the window lo .. hi to 0 .. n - 1 goes to rel[6]; rows or columns outside, for the crossing relations,
+ * to cross[side][4]; returns bit 0: crosses the low edge, bit 1: the high edge */
+static int pred_axis(uint32_t *rel, uint32_t *cross, int lo, int hi, int n)
+{
+    int r, sides = 0;
+    if (hi < 0) r = H264O_PRR_BEYOND_LOW;
+    else if (lo > n - 1) r = H264O_PRR_BEYOND_HIGH;
+    else if (lo < 0 && hi > n - 1) { r = H264O_PRR_CROSS_BOTH; sides = 3; }
+    else if (lo < 0) { r = H264O_PRR_CROSS_LOW; sides = 1; }
+    else if (hi > n - 1) { r = H264O_PRR_CROSS_HIGH; sides = 2; }
+    else r = H264O_PRR_INSIDE;
+    rel[r]++;
+    if (sides & 1) cross[(-lo > 4 ? 4 : -lo) - 1]++;
+    if (sides & 2) cross[4 + (hi - (n - 1) > 4 ? 4 : hi - (n - 1)) - 1]++;
+    return sides;
+}
+static void pred_note_inter(h264o_dec *d, int x0, int y0, int w, int h, int mvx, int mvy, int shape, int ref)
+{
+    uint32_t *pa = d->pred;
+    const int cw = d->cw, ch = d->ch, xF = mvx & 3, yF = mvy & 3;
+    pa[H264O_PRED_L_SHAPE + (shape * 4 + yF) * 4 + xF]++;
+    if (ref >= 0 && ref < 3) pa[H264O_PRED_L_REF + (ref * 4 + yF) * 4 + xF]++;
+    const int xa = x0 + (mvx >> 2) - (xF ? 2 : 0), xb = x0 + w - 1 + (mvx >> 2) + (xF ? 3 : 0);
+    const int ya = y0 + (mvy >> 2) - (yF ? 2 : 0), yb = y0 + h - 1 + (mvy >> 2) + (yF ? 3 : 0);
+    const int sx = pred_axis(pa + H264O_PRED_L_REL + (0 * 4 + xF) * 6, pa + H264O_PRED_L_CROSS + (0 * 4 + xF) * 8, xa, xb, cw);
+    const int sy = pred_axis(pa + H264O_PRED_L_REL + (1 * 4 + yF) * 6, pa + H264O_PRED_L_CROSS + (1 * 4 + yF) * 8, ya, yb, ch);
+    if (xF && yF)
+        for (int ys = 0; ys < 2; ys++)
+            for (int xs = 0; xs < 2; xs++) if (((sx >> xs) & 1) && ((sy >> ys) & 1)) pa[H264O_PRED_L_CORNER + 2 * ys + xs]++;
+    for (int by = 0; by < h; by += 4)
+        for (int bx = 0; bx < w; bx += 4) {
+            const int X = x0 + bx + (mvx >> 2), lo = X - (xF ? 2 : 0), hi = X + 3 + (xF ? 3 : 0);
+            if (ref >= 0 && ref < 3) pa[H264O_PRED_B_REF + (ref * 4 + yF) * 4 + xF]++;
+            if (lo >= 0 && hi <= cw - 1) {
+                pa[H264O_PRED_B_ALIGN + (X & 3) * 4 + xF]++;
+                if (xF) pa[H264O_PRED_B_RDIST + (cw - 1 - hi > 4 ? 4 : cw - 1 - hi)]++;
+            }
+        }
+    const int cxF = mvx & 7, cyF = mvy & 7, cs = cw / 2, chh = ch / 2;
+    pa[H264O_PRED_C_FRAC + cyF * 8 + cxF]++;
+    const int cxa = x0 / 2 + (mvx >> 3), cxb = cxa + w / 2 - 1 + (cxF ? 1 : 0), cya = y0 / 2 + (mvy >> 3), cyb = cya + h / 2 - 1 + (cyF ? 1 : 0);
+    const int csx = pred_axis(pa + H264O_PRED_C_REL + (0 * 2 + (cxF != 0)) * 6, pa + H264O_PRED_C_CROSS + (0 * 2 + (cxF != 0)) * 8, cxa, cxb, cs);
+    pred_axis(pa + H264O_PRED_C_REL + (1 * 2 + (cyF != 0)) * 6, pa + H264O_PRED_C_CROSS + (1 * 2 + (cyF != 0)) * 8, cya, cyb, chh);
+    if (cxF && !csx && cxa >= 0 && cxb <= cs - 1) pa[H264O_PRED_C_RDIST + (cs - cxb > 8 ? 8 : cs - cxb) - 1]++;
+}
+/* the account: the horizontally adjacent pairs of 4x4 luma blocks of every 8x8 quadrant of an inter macroblock, by how their vectors
+ * differ as chroma vectors (units of 1/8 sample) */
+static void pred_note_pairs(h264o_dec *d, const dmb *m, int mx, int my)
+{
+    const int cs = d->cw / 2, chh = d->ch / 2;
+    for (int q = 0; q < 4; q++)
+        for (int r = 0; r < 2; r++) {
+            const int bx = 2 * (q & 1), by = 2 * (q >> 1) + r, bi = 4 * by + bx;
+            const int16_t *a = m->mv[bi], *b = m->mv[bi + 1];
+            if (a[0] == b[0] && a[1] == b[1]) { d->pred[H264O_PRED_C_PAIR]++; continue; }
+            d->pred[H264O_PRED_C_PAIR + (((a[0] >> 3) != (b[0] >> 3) || (a[1] >> 3) != (b[1] >> 3)) ? 1 : 2)]++;
+            int in[2];
+            for (int k = 0; k < 2; k++) {
+                const int16_t *v = k ? b : a;
+                const int xa = 8 * mx + 2 * (bx + k) + (v[0] >> 3), xb = xa + 1 + ((v[0] & 7) ? 1 : 0);
+                const int ya = 8 * my + 2 * by + (v[1] >> 3), yb = ya + 1 + ((v[1] & 7) ? 1 : 0);
+                in[k] = xa >= 0 && xb <= cs - 1 && ya >= 0 && yb <= chh - 1;
+            }
+            if (in[0] != in[1]) d->pred[H264O_PRED_C_PAIR_MIXED]++;
+        }
+}
+/* shape: H264O_PRS_*, ref: ref_idx_l0 (for the account alone) */
+static void inter_pred_part(h264o_dec *d, const dpic *r, int x0, int y0, int w, int h, int mvx, int mvy, int shape, int ref)
 {
     const int cw = d->cw, cs = cw / 2;
+    pred_note_inter(d, x0, y0, w, h, mvx, mvy, shape, ref);
     {   /* statistics: the vector, and whether every luma sample the prediction reads (the six taps of a fractional position
          * included) lies outside the picture on one side */
         int *st = d->stat;
@@ -976,6 +1083,7 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
     uint8_t *Y = d->cur.pl[0] + (size_t)16 * my * cw + 16 * mx;
     const dmb *mA = mb_at(d, mx - 1, my, c->sl, c->addr), *mB = mb_at(d, mx, my - 1, c->sl, c->addr);
     const dmb *mC = mb_at(d, mx + 1, my - 1, c->sl, c->addr), *mD = mb_at(d, mx - 1, my - 1, c->sl, c->addr);
+    const dmb *const raw[4] = {mA, mB, mD, mC};   /* (the account: before constrained_intra_pred_flag is applied) */
     if (d->constrained_intra) {
         /* 8.3.1.1 / 8.3.1.2 / 8.3.3 / 8.3.4: with constrained_intra_pred_flag a macroblock coded in Inter prediction mode is "not
          * available" for intra prediction (nor for the derivation of Intra4x4PredMode) */
@@ -985,6 +1093,19 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
         if (mD && (mD->kind == DMB_INTER || mD->kind == DMB_SKIP)) mD = NULL;
     }
     for (int i = 0; i < 4; i++) { m->refidx[i] = -1; m->refpic[i] = -1; }
+    m->avail = (uint8_t)((raw[0] ? 1 : 0) | (raw[1] ? 2 : 0) | (raw[3] ? 4 : 0) | (raw[2] ? 8 : 0) | (mA ? 16 : 0) | (mB ? 32 : 0) | (mC ? 64 : 0) | (mD ? 128 : 0));
+    /* the account: why each neighbouring macroblock is or is not available for intra prediction (0 left, 1 top, 2 top-left, 3 top-right),
+     * and the sides the predictions of this macroblock read (`used`, same bits) */
+    const dmb *const fin[4] = {mA, mB, mD, mC};
+    static const int8_t NBX[4] = {-1, 0, -1, 1}, NBY[4] = {0, -1, -1, -1};
+    int rsn[4], used = 0;
+    for (int s = 0; s < 4; s++) {
+        const int nx = mx + NBX[s], ny = my + NBY[s];
+        if (nx < 0 || ny < 0 || nx >= d->mbw || ny >= d->mbh) rsn[s] = H264O_PRN_OUTSIDE;
+        else if (!raw[s]) rsn[s] = H264O_PRN_OTHER_SLICE;
+        else if (!fin[s]) rsn[s] = H264O_PRN_CONSTRAINED_INTER;
+        else rsn[s] = fin[s]->kind == DMB_IPCM ? H264O_PRN_IPCM_MB : (fin[s]->kind == DMB_INTER || fin[s]->kind == DMB_SKIP) ? H264O_PRN_INTER_MB : H264O_PRN_INTRA_MB;
+    }
     if (mbt == 25) { /* I_PCM, 7.3.5 + 8.3.5 */
         m->kind = DMB_IPCM;
         while (b->pos & 7) if (rd_bit(b)) return fail(d, "pcm_alignment_zero_bit != 0");
@@ -1047,6 +1168,8 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
         if (b->err) return fail(d, "residual parse error (Intra16x16)");
         uint8_t pred[256];
         if (intra16x16_pred(m->i16_mode, mB != NULL, mA != NULL, mD != NULL, Y, cw, pred)) return fail(d, "Intra16x16 mode uses unavailable neighbours");
+        d->pred[H264O_PRED_I16 + m->i16_mode * 8 + (mA != NULL) + 2 * (mB != NULL) + 4 * (mD != NULL)]++;
+        used |= m->i16_mode == 0 ? 2 : m->i16_mode == 1 ? 1 : m->i16_mode == 2 ? 3 : 7;
         for (int y = 0; y < 16; y++) memcpy(Y + y * cw, pred + 16 * y, 16);
         /* 8.5.10: c = 4x4 of DC levels (inverse zig-zag), f = A c A, A rows 1111 / 11-1-1 / 1-1-11 / 1-11-1 */
         int cm[4][4], t[4][4], f[4][4];
@@ -1092,6 +1215,22 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
             uint8_t pred[16];
             uint8_t *p = Y + 4 * by * cw + 4 * bx;
             if (intra4x4_pred(m->i4mode[4 * by + bx], have_top, have_left, have_tl, have_tr, p, cw, pred)) return fail(d, "Intra4x4 mode uses unavailable neighbours");
+            {   /* the account */
+                const int mode = m->i4mode[4 * by + bx];
+                uint32_t *pa = d->pred;
+                pa[H264O_PRED_I4 + mode * 16 + have_left + 2 * have_top + 4 * have_tl + 8 * have_tr]++;
+                /* where each neighbouring block lies: -1 this macroblock, -2 not yet decoded, else the side of the neighbouring macroblock */
+                const int wl = bx > 0 ? -1 : 0, wt = by > 0 ? -1 : 1, wtl = (bx > 0 && by > 0) ? -1 : bx > 0 ? 1 : by > 0 ? 0 : 2;
+                const int wtr = by == 0 ? (bx < 3 ? 1 : 3) : have_tr ? -1 : -2;
+                const int where[4] = {wl, wt, wtl, wtr};
+                for (int s = 0; s < 4; s++)
+                    pa[H264O_PRED_I4_NB + s * 8 + (where[s] == -1 ? H264O_PRN_SAME_MB : where[s] == -2 ? H264O_PRN_NOT_YET_DECODED : rsn[where[s]])]++;
+                if (wtr == -2) pa[H264O_PRED_I4_TR_NYD + k]++;
+                if ((mode == 3 || mode == 7) && have_top) pa[H264O_PRED_I4_TR + 2 * (mode == 7) + have_tr]++;
+                /* neighbouring blocks the mode reads: bit 0 left, 1 top, 2 top-left, 3 top-right (a substituted top-right is not read) */
+                static const uint8_t READS[9] = {2, 1, 3, 10, 7, 7, 7, 10, 1};
+                for (int s = 0; s < 4; s++) if (((READS[mode] >> s) & 1) && where[s] >= 0) used |= 1 << where[s];
+            }
             for (int y = 0; y < 4; y++) memcpy(p + y * cw, pred + 4 * y, 4);
             if (tc) {
                 int cc[4][4], dd[4][4], r[4][4];
@@ -1102,6 +1241,10 @@ static int decode_intra_mb(mbctx *c, int mbt /* I-slice mb_type */, int *qp)
             }
         }
     }
+    d->pred[H264O_PRED_IC + m->chroma_mode * 8 + (mA != NULL) + 2 * (mB != NULL) + 4 * (mD != NULL)]++;
+    used |= m->chroma_mode == 0 ? 3 : m->chroma_mode == 1 ? 1 : m->chroma_mode == 2 ? 2 : 7;
+    for (int s = 0; s < 4; s++)
+        if (((used >> s) & 1) && rsn[s] == H264O_PRN_INTER_MB) d->pred[H264O_PRED_IBI + 2 * s + (fin[s]->cbp != 0)]++;
     for (int pl = 0; pl < 2; pl++) {
         uint8_t pc[64];
         uint8_t *C = d->cur.pl[1 + pl] + (size_t)8 * my * cs + 8 * mx;
@@ -1121,6 +1264,11 @@ static int decode_inter_mb(mbctx *c, int mbt /* P mb_type 0..4, -1 = P_Skip */, 
     uint8_t done[16];
     memset(done, 0, sizeof(done));
     m->kind = mbt < 0 ? DMB_SKIP : DMB_INTER;
+    for (int s = 0; s < 4; s++) {   /* (an inter macroblock uses bits 0..3 alone, through neighbour_blk) */
+        static const int8_t NX[4] = {-1, 0, 1, -1}, NY[4] = {0, -1, -1, -1};
+        const dmb *n = mb_at(d, mx + NX[s], my + NY[s], c->sl, c->addr);
+        if (n) m->avail |= (uint8_t)((1 << s) | ((!d->constrained_intra || n->kind == DMB_I4 || n->kind == DMB_I16 || n->kind == DMB_IPCM) ? 16 << s : 0));
+    }
     /* partition geometry: list of (x, y, w, h, quadrant-for-ref, shape, partidx) */
     struct part { int x, y, w, h, q, shape, idx; } parts[16];
     int np = 0, sub[4] = {0, 0, 0, 0};
@@ -1193,7 +1341,8 @@ static int decode_inter_mb(mbctx *c, int mbt /* P mb_type 0..4, -1 = P_Skip */, 
         const dpic *r = ref_of(d, 0, nactive);
         if (!r) return fail(d, "P_Skip without a reference picture");
         m->refpic[0] = m->refpic[1] = m->refpic[2] = m->refpic[3] = r->id;
-        inter_pred_part(d, r, 16 * mx, 16 * my, 16, 16, m->mv[0][0], m->mv[0][1]);
+        pred_note_pairs(d, m, mx, my);
+        inter_pred_part(d, r, 16 * mx, 16 * my, 16, 16, m->mv[0][0], m->mv[0][1], H264O_PRS_SKIP, 0);
         return 0;
     }
     for (int s = 0; s < 4; s++) {
@@ -1201,10 +1350,13 @@ static int decode_inter_mb(mbctx *c, int mbt /* P mb_type 0..4, -1 = P_Skip */, 
         if (!r) return fail(d, "reference index without a picture");
         m->refpic[s] = r->id;
     }
+    pred_note_pairs(d, m, mx, my);
     for (int i = 0; i < np; i++) {
         const struct part *p = &parts[i];
         const int bi = 4 * (p->y >> 2) + (p->x >> 2);
-        inter_pred_part(d, ref_of(d, m->refidx[p->q], nactive), 16 * mx + p->x, 16 * my + p->y, p->w, p->h, m->mv[bi][0], m->mv[bi][1]);
+        const int shape = p->w == 16 ? (p->h == 16 ? H264O_PRS_16X16 : H264O_PRS_16X8) : p->w == 8 ? (p->h == 16 ? H264O_PRS_8X16 : p->h == 8 ? H264O_PRS_8X8 : H264O_PRS_8X4)
+                        : (p->h == 8 ? H264O_PRS_4X8 : H264O_PRS_4X4);
+        inter_pred_part(d, ref_of(d, m->refidx[p->q], nactive), 16 * mx + p->x, 16 * my + p->y, p->w, p->h, m->mv[bi][0], m->mv[bi][1], shape, m->refidx[p->q]);
     }
     /* residual */
     const int q = *qp;
@@ -1554,6 +1706,7 @@ static int decode_slice(h264o_dec *d, bitr *b, int nal_type, int nal_ref_idc)
         d->max_mb_bits = 0; d->max_level_prefix = 0;
         memset(d->stat, 0, sizeof(d->stat));
         memset(d->dbf, 0, sizeof(d->dbf));
+        memset(d->pred, 0, sizeof(d->pred));
         d->cur_is_ref = nal_ref_idc != 0; d->cur_frame_num = frame_num; d->cur_is_idr = nal_type == 5;
         if (nal_type == 5) d->nrefs = 0;   /* 8.2.1: an IDR picture marks all reference pictures unused before it is decoded */
         d->cur_pps_id = (int)pps_id;
@@ -1623,6 +1776,7 @@ int h264o_dec_decode(h264o_dec *d, const uint8_t *data, size_t len)
     size_t i = 0;
     d->err[0] = 0;
     g_stat = d->stat;   /* (set by every call: never read after its decoder is gone) */
+    g_pred = d->pred;
     uint8_t *rbsp = (uint8_t *)malloc(len + 8);
     if (!rbsp) return fail(d, "out of memory");
     while (i + 3 <= len) {

@@ -209,6 +209,9 @@ struct randsyn {
     /* feature 131072 ("range ends") */
     int re;              /* vectors are drawn as vectors up to the limits of A.3.1, also where `direct` writes the macroblock */
     uint32_t rerng;      /* its generator */
+    /* feature 262144 ("prediction cells", with 32) */
+    int pc;              /* vectors are drawn so that the windows of 8.4.2.2 lie at the picture's edges (`re` is set with it: the writer keeps the 4x4 grid) */
+    uint32_t pcrng;      /* its generator */
 };
 /* one picture parameter set of a random stream (feature 65536 keeps up to four in play) */
 struct rs_pps { int id, init_qp, cqo[2], nref_default, dbf_ctrl, constrained, t8x8; };
@@ -1353,6 +1356,39 @@ static mv_t re_draw_vector(h264o_enc *e, uint32_t *s, mv_t pred)
     const mv_t v = {(int16_t)vx, (int16_t)vy};
     return v;
 }
+/* feature 262144: one component of the vector of a partition whose first sample is `pos` and which is n samples long, in a picture
+ * of `size` samples on that axis.  One in eight near the predictor, one in eight small; otherwise a fraction is drawn, and one end of
+ * the window 8.4.2.2.1 reads for it (n samples; with a fraction two more in front and three behind) is put 0 .. 5 samples inside or
+ * 1 .. 8 outside one edge of the picture: the near end (the window crosses the edge by that much, or lies that far inside), or the far end
+ * (the window lies beyond the edge, or all but a few samples of it do); a window longer than the picture is put across both edges
+ * every second time */
+static int pc_axis(uint32_t *s, int pos, int n, int size, int pred)
+{
+    const int k = rs_below(s, 8);
+    if (k == 0) return pred + rs_below(s, 9) - 4;
+    if (k == 1) return rs_below(s, 65) - 32;
+    const int frac = rs_below(s, 4), front = frac ? 2 : 0, back = frac ? 3 : 0, off = rs_below(s, 14) - 5;
+    int x;   /* where the partition's first sample comes from, full samples */
+    /* a window longer than the picture (16 samples and a fraction in a picture of 16): every second time across both edges */
+    if (n + front + back > size + 1 && rs_below(s, 2)) return 4 * (size - n - back + 1 + rs_below(s, n + front + back - size - 1) - pos) + frac;
+    switch (rs_below(s, 4)) {
+        case 0: x = -off + front; break;                              /* the window starts at -off */
+        case 1: x = size - 1 + off - back - (n - 1); break;           /* ... ends at size - 1 + off */
+        case 2: x = off - back - (n - 1); break;                      /* ... ends at off: about the low edge */
+        default: x = size - 1 + off + front; break;                   /* ... starts at size - 1 + off: about the high edge */
+    }
+    return 4 * (x - pos) + frac;
+}
+static mv_t pc_draw_vector(h264o_enc *e, uint32_t *s, int mx, int my, int bx, int by, int bw, int bh, mv_t pred)
+{
+    const mv_t v = {(int16_t)clip3(RE_MV_XLO, RE_MV_XHI, pc_axis(s, 16 * mx + 4 * bx, 4 * bw, e->cw, pred.x)),
+                    (int16_t)clip3(RE_MV_YLO, RE_MV_YHI, pc_axis(s, 16 * my + 4 * by, 4 * bh, e->ch, pred.y))};
+    for (int c = 0; c < 2; c++) {
+        const uint32_t d = (uint32_t)abs(c ? v.y - pred.y : v.x - pred.x);
+        if (d > e->hits.max_mvd) e->hits.max_mvd = d;
+    }
+    return v;
+}
 static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
 {
     const h264o_mbinfo *mb = &e->mb[my * e->mbw + mx];
@@ -1451,7 +1487,7 @@ static void write_mb(h264o_enc *e, bitw *b, int mx, int my, int p_slice)
                             else if (sub[k] == 3) { bx += j & 1; by += j >> 1; bw4 = bh4 = 1; }
                         }
                         const mv_t p = re_predict(e, mx, my, done, bx, by, bw4, refk[k], shape < 3 ? shape : 0, NULL);
-                        const mv_t v = re_draw_vector(e, &e->rs->rerng, p);
+                        const mv_t v = e->rs->pc ? pc_draw_vector(e, &e->rs->pcrng, mx, my, bx, by, bw4, bh4, p) : re_draw_vector(e, &e->rs->rerng, p);
                         bw_se(b, v.x - p.x);
                         bw_se(b, v.y - p.y);
                         re_store(e, mx, my, done, bx, by, bw4, bh4, v.x, v.y);
@@ -1901,7 +1937,35 @@ static void re_place(uint32_t *s, int16_t *lv, int first, int n, int kind)
     lv[at] = (int16_t)(sl == 0 ? -2064 : -(2048 + (15 << (sl - 1))));
     for (int i = 0; i < sl; i++) lv[at + sl - i] = (int16_t)(rs_below(s, 2) ? -ramp[i] : ramp[i]);
 }
-/* the large levels of one macroblock (its QP_Y is final), then the bound: while a block passes it, its largest level goes */
+/* the bound of 8.5.10 - 8.5.13 on one macroblock (its QP_Y is final): while a block passes it, its largest level goes */
+static void re_enforce_bound(h264o_enc *e, h264o_mbinfo *mb, int16_t *lv, int qp, const int cqo[2], int direct)
+{
+    const int cbpl = mb->cbp & 15, cbpc = mb->cbp >> 4, i16 = mb->type == H264O_MB_I16;
+    const int inter = !H264O_MB_IS_INTRA(mb->type);
+    const int t8 = inter && mb->i16_mode && cbpl, t4 = !t8 || (direct && mb->type == H264O_MB_P8X8);
+    int qpc[2];
+    for (int pl = 0; pl < 2; pl++) qpc[pl] = o_chroma_qp[clip3(0, 51, qp + cqo[pl])];
+    const int16_t *worst = NULL;
+    int wfirst = 0, wn = 0;
+    while (re_mb_bound(mb, lv, qp, qpc, t4, t8, &worst, &wfirst, &wn) > RE_BOUND) {
+        int16_t *w = lv + (worst - lv);
+        int at = wfirst;
+        for (int i = wfirst; i < wn; i++) if (abs(w[i]) >= abs(w[at])) at = i;
+        w[at] = 0;
+        e->hits.re_dropped++;
+    }
+    for (int b = 0; b < 16; b++) {
+        int tc = 0;
+        if (cbpl & (1 << (b >> 2))) for (int i = i16; i < 16; i++) tc += lv[H264O_LV_LUMA + 16 * b + i] != 0;
+        mb->tc[b] = (uint8_t)tc;
+    }
+    for (int b = 0; b < 8; b++) {
+        int tc = 0;
+        if (cbpc == 2) for (int i = 1; i < 16; i++) tc += lv[H264O_LV_CHROMA_AC + 16 * b + i] != 0;
+        mb->tc[16 + b] = (uint8_t)tc;
+    }
+}
+/* the large levels of one macroblock (its QP_Y is final), then the bound */
 static void re_levels(h264o_enc *e, uint32_t *s, h264o_mbinfo *mb, int16_t *lv, int qp, const int cqo[2], int burst, int direct)
 {
     if (burst == 2) mb->cbp = 0x2F;   /* every block coded (mb_qp_delta, where none was drawn for the macroblock, is 0) */
@@ -1942,23 +2006,7 @@ static void re_levels(h264o_enc *e, uint32_t *s, h264o_mbinfo *mb, int16_t *lv, 
             memcpy(lv + list[k][0], keep, sizeof(keep[0]) * (size_t)list[k][2]);
         }
     }
-    while (re_mb_bound(mb, lv, qp, qpc, t4, t8, &worst, &wfirst, &wn) > RE_BOUND) {
-        int16_t *w = lv + (worst - lv);
-        int at = wfirst;
-        for (int i = wfirst; i < wn; i++) if (abs(w[i]) >= abs(w[at])) at = i;
-        w[at] = 0;
-        e->hits.re_dropped++;
-    }
-    for (int b = 0; b < 16; b++) {
-        int tc = 0;
-        if (cbpl & (1 << (b >> 2))) for (int i = i16; i < 16; i++) tc += lv[H264O_LV_LUMA + 16 * b + i] != 0;
-        mb->tc[b] = (uint8_t)tc;
-    }
-    for (int b = 0; b < 8; b++) {
-        int tc = 0;
-        if (cbpc == 2) for (int i = 1; i < 16; i++) tc += lv[H264O_LV_CHROMA_AC + 16 * b + i] != 0;
-        mb->tc[16 + b] = (uint8_t)tc;
-    }
+    re_enforce_bound(e, mb, lv, qp, cqo, direct);
 }
 
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
@@ -1988,7 +2036,12 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
     uint32_t rerng = (seed ^ 0x7F4A7C15u) * 2891336453u + 0x1B873593u;
     rs_next(&rerng);
     const int burst = re && (features & 1) ? (e->frames % 12 == 5 ? 1 : e->frames % 12 == 9 ? 2 : 0) : 0;
-    rs.re = re;
+    /* feature 262144 ("prediction cells", with 32), once more with a generator of its own */
+    const int pc = (features & 262144) && (features & 32);
+    uint32_t pcrng = (seed ^ 0x2545F491u) * 3266489917u + 0x68E31DA4u;
+    rs_next(&pcrng);
+    rs.re = re || pc;
+    rs.pc = pc;
     rs.is_ref = 1;
     if (e->frames == 0) {   /* once per stream */
         e->rs_npps = 0; e->rs_pps_last = -1; e->rs_sps_id = 0; e->rs_crop_l = e->rs_crop_t = 0; e->nonref_run = 0; e->rs_alt = 0;
@@ -2170,6 +2223,11 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
             if (islice) type = kind < 45 ? H264O_MB_I4 : kind < 90 ? H264O_MB_I16 : H264O_MB_IPCM;
             else type = kind < 22 ? H264O_MB_PSKIP : kind < 44 ? H264O_MB_P16 : kind < 54 ? H264O_MB_P16X8 : kind < 64 ? H264O_MB_P8X16
                       : kind < 76 ? H264O_MB_P8X8 : kind < 85 ? H264O_MB_I16 : kind < 94 ? H264O_MB_I4 : H264O_MB_IPCM;
+            if (pc && !islice) {   /* four in ten macroblocks of a P slice intra; more of the inter ones split into quadrants */
+                const int k = rs_below(&pcrng, 100);
+                type = k < 16 ? H264O_MB_PSKIP : k < 26 ? H264O_MB_P16 : k < 33 ? H264O_MB_P16X8 : k < 40 ? H264O_MB_P8X16 : k < 58 ? H264O_MB_P8X8
+                     : k < 75 ? H264O_MB_I16 : k < 95 ? H264O_MB_I4 : H264O_MB_IPCM;
+            }
             if (type == H264O_MB_IPCM && !(features & 8)) type = H264O_MB_I16;
             if (mbi >= skip_from && mbi < skip_to && !islice) type = H264O_MB_PSKIP;
             const int saturate = (features & 8192) && my < e->slice_rows && mbi % 8 < 3;
@@ -2293,6 +2351,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
                 qp = nq;
             }
             if (re) re_levels(e, &rerng, mb, lv, qp, rs.cqo, burst, rs.direct);
+            else if (pc) re_enforce_bound(e, mb, lv, qp, rs.cqo, rs.direct);   /* (conforming to 8.5 whatever the QP draws) */
             if (mbqp_out) mbqp_out[mbi] = (uint8_t)qp;
         }
     if ((features & 4096) && any_pcm && rs.dbf_ctrl) rs.idc = 1;   /* the encoder does not filter a picture that holds an I_PCM macroblock */
@@ -2302,6 +2361,7 @@ int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int
     e->rs = &rs;
     rs.rng = rng;
     rs.rerng = rerng;
+    rs.pcrng = pcrng;
     if (idr) {
         memset(e->rbsp, 0, 256);
         b = (bitw){e->rbsp, e->rbsp_cap, 0};

@@ -202,7 +202,13 @@ const uint8_t *h264o_enc_p_decision(const h264o_enc *e);
  * the magnitudes of its scaled coefficients (DC from the DC transform of the magnitudes; 8x8: weighted 1.5 per odd row / column)
  * bounds every intermediate; while it passes 32000 the largest level of the block is taken out again (h264o_hits.re_dropped).
  * oracle/h264_dec.c measures the intermediates themselves (h264o_dec_stat).
- * These four draw from generators of their own.  2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
+ * 262144 "prediction cells" (with 32): the vector of every partition is drawn per component - one in eight near its predictor, one in
+ * eight within +-8 samples, otherwise with a fraction drawn evenly and one end of the window 8.4.2.2.1 reads for it put 0 .. 5 samples
+ * inside or 1 .. 8 outside one edge of the picture (either end of the window about either edge) -, and of the macroblocks of a P slice 17 %
+ * are Intra16x16, 20 % Intra4x4, 5 % I_PCM, 16 % P_Skip and 18 % P_8x8 (intra prediction modes are drawn evenly over what availability allows
+ * anyway); levels are taken out
+ * again as under 131072 while a block passes the bound of 8.5.  oracle/h264_dec.c says which cells of its prediction account (h264o_dec_pred) that reaches.
+ * These five draw from generators of their own.  2048, 4096 and 8192 draw only when set: streams of every other feature value stay what they were.  mbqp_out (one byte per macroblock, may be NULL) receives QP_Y of every
  * macroblock (0 for I_PCM, the value the loop filter uses).  Side information: h264o_enc_mbinfo / _mvq / _mbaux / _levels. */
 int64_t h264o_enc_random_picture(h264o_enc *e, uint32_t seed, int force_idr, int features, uint8_t *out, size_t out_cap,
                                  int *is_idr, uint8_t *mbqp_out);
@@ -309,6 +315,46 @@ enum { H264O_DBX_LEFT_QP_DIFF = 0, H264O_DBX_TOP_QP_DIFF, H264O_DBX_LEFT_QP_ODD,
 #define H264O_DBF_COUNT (H264O_DBF_CTX + H264O_DBX_COUNT)
 const uint32_t *h264o_dec_dbf(const h264o_dec *d);
 int h264o_dec_dbf_count(void);
+/* what the prediction (8.3, 8.4.2.2) of the last decoded picture was made of: h264o_dec_pred() is an array of H264O_PRED_COUNT counters,
+ * the decoder's own account (the decode does not read it).  Every cell is defined by sample coordinates against the picture and by
+ * the availability of 6.4.x.  W, H: the picture's width and height in samples of the plane in question.
+ * inter luma, per predicted partition (P_Skip: one of 16x16): xFrac = mvx & 3, yFrac = mvy & 3; on the horizontal axis the window is
+ * the columns 8.4.2.2.1 reads, xInt .. xInt + w - 1, with xFrac != 0 xInt - 2 .. xInt + w + 2 (the vertical axis alike), and its
+ * relation to 0 .. W - 1 is one of H264O_PRR_*
+ *   L_SHAPE [shape H264O_PRS_*][yFrac][xFrac];  L_REF [ref_idx_l0 0..2][yFrac][xFrac];  L_REL [axis 0 x / 1 y][fraction on it][relation]
+ *   L_CROSS [axis][fraction][side 0 low / 1 high][columns or rows outside: 1, 2, 3, 4 and more] for the crossing relations (CROSS_BOTH
+ *     counts on both sides);  L_CORNER [y side][x side]: both fractions non-zero and the window crosses an edge on either axis
+ * inter luma, per 4x4 block of a partition: B_REF [ref_idx_l0][yFrac][xFrac] (its sum: the inter 4x4 blocks of the picture); the
+ *   block's own window horizontally inside: B_ALIGN [xInt & 3][xFrac], and with xFrac != 0 B_RDIST [W - 1 - its last column: 0..3, 4 and more]
+ * inter luma, per predicted sample: L_CLIP [4 * yFrac + xFrac][intermediate 0 b-type (b, s) / 1 h-type (h, m) / 2 j][Clip1 active at 0 / at 255],
+ *   of the intermediates Table 8-12 uses for that position
+ * inter chroma, per predicted partition: xFracC = mvx & 7, xIntC = x / 2 + (mvx >> 3), window xIntC .. xIntC + w / 2 - 1 (+ 1 with xFracC != 0)
+ *   C_FRAC [yFracC][xFracC];  C_REL [axis][fraction zero / non-zero][relation];  C_CROSS [axis][zero / non-zero][side][samples outside 1, 2, 3, 4 and more]
+ *   C_RDIST [samples from the window's last column to the picture's last one, both counted: 1..7, 8 and more], xFracC != 0 and the window horizontally inside
+ *   per horizontally adjacent pair of 4x4 luma blocks of one 8x8 quadrant: C_PAIR [0 the same vector / 1 mv >> 3 differs on an axis / 2 only mv & 7 differs],
+ *   C_PAIR_MIXED: differing pairs with the 2x2 chroma window of one block inside the picture and the other's not
+ * Intra4x4, per block: I4 [Intra4x4PredMode][left | top << 1 | top-left << 2 | top-right << 3 as 8.3.1.2 has them before substitution];
+ *   I4_NB [neighbour 0 left, 1 top, 2 top-left, 3 top-right][H264O_PRN_*];  I4_TR_NYD [blkIdx]: top-right not yet decoded;
+ *   I4_TR [0 mode 3 / 1 mode 7][0 top-right substituted by p[3, -1] / 1 real]
+ * I16, IC [mode][left | top << 1 | top-left << 2] per macroblock (IC: intra_chroma_pred_mode);  IC_DC [chroma4x4BlkIdx][left][top] per plane with
+ *   mode 0 (8.3.4);  PLANE_CLIP [0 luma / 1 chroma][Clip1 active at 0 / at 255] per sample of a plane-mode prediction
+ * IBI [side 0 left, 1 top, 2 top-left, 3 top-right][coded_block_pattern of the neighbour 0 / non-zero]: intra macroblocks whose prediction
+ *   reads samples of an inter macroblock on that side */
+enum { H264O_PRS_SKIP = 0, H264O_PRS_16X16, H264O_PRS_16X8, H264O_PRS_8X16, H264O_PRS_8X8, H264O_PRS_8X4, H264O_PRS_4X8, H264O_PRS_4X4 };
+enum { H264O_PRR_INSIDE = 0, H264O_PRR_CROSS_LOW, H264O_PRR_CROSS_HIGH, H264O_PRR_BEYOND_LOW, H264O_PRR_BEYOND_HIGH, H264O_PRR_CROSS_BOTH };
+enum { H264O_PRN_OUTSIDE = 0, H264O_PRN_OTHER_SLICE, H264O_PRN_NOT_YET_DECODED, H264O_PRN_CONSTRAINED_INTER, H264O_PRN_SAME_MB, H264O_PRN_INTRA_MB,
+       H264O_PRN_IPCM_MB, H264O_PRN_INTER_MB };
+enum { H264O_PRED_L_SHAPE = 0, H264O_PRED_L_REF = H264O_PRED_L_SHAPE + 8 * 16, H264O_PRED_L_REL = H264O_PRED_L_REF + 3 * 16,
+       H264O_PRED_L_CROSS = H264O_PRED_L_REL + 2 * 4 * 6, H264O_PRED_L_CORNER = H264O_PRED_L_CROSS + 2 * 4 * 2 * 4, H264O_PRED_B_REF = H264O_PRED_L_CORNER + 4,
+       H264O_PRED_B_ALIGN = H264O_PRED_B_REF + 3 * 16, H264O_PRED_B_RDIST = H264O_PRED_B_ALIGN + 16, H264O_PRED_L_CLIP = H264O_PRED_B_RDIST + 5,
+       H264O_PRED_C_FRAC = H264O_PRED_L_CLIP + 16 * 3 * 2, H264O_PRED_C_REL = H264O_PRED_C_FRAC + 64, H264O_PRED_C_CROSS = H264O_PRED_C_REL + 2 * 2 * 6,
+       H264O_PRED_C_RDIST = H264O_PRED_C_CROSS + 2 * 2 * 2 * 4, H264O_PRED_C_PAIR = H264O_PRED_C_RDIST + 8, H264O_PRED_C_PAIR_MIXED = H264O_PRED_C_PAIR + 3,
+       H264O_PRED_I4 = H264O_PRED_C_PAIR_MIXED + 1, H264O_PRED_I4_NB = H264O_PRED_I4 + 9 * 16, H264O_PRED_I4_TR_NYD = H264O_PRED_I4_NB + 4 * 8,
+       H264O_PRED_I4_TR = H264O_PRED_I4_TR_NYD + 16, H264O_PRED_I16 = H264O_PRED_I4_TR + 4, H264O_PRED_IC = H264O_PRED_I16 + 4 * 8,
+       H264O_PRED_IC_DC = H264O_PRED_IC + 4 * 8, H264O_PRED_PLANE_CLIP = H264O_PRED_IC_DC + 16, H264O_PRED_IBI = H264O_PRED_PLANE_CLIP + 4,
+       H264O_PRED_COUNT = H264O_PRED_IBI + 8 };
+const uint32_t *h264o_dec_pred(const h264o_dec *d);
+int h264o_dec_pred_count(void);
 
 #ifdef __cplusplus
 }

@@ -123,8 +123,12 @@ def lib():
         L.h264o_dec_stat.argtypes = [vp, C.c_int]
         L.h264o_dec_dbf.restype = vp
         L.h264o_dec_dbf.argtypes = [vp]
+        L.h264o_dec_pred.restype = vp
+        L.h264o_dec_pred.argtypes = [vp]
         L.h264o_dec_mb_kind.argtypes = [vp, C.c_int]
         L.h264o_dec_mb_qp.argtypes = [vp, C.c_int]
+        L.h264o_dec_mb_avail.argtypes = [vp, C.c_int]
+        L.h264o_dec_mb_intra_mode.argtypes = [vp, C.c_int, C.c_int]
         L.h264o_dec_mb_mv.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint)
         L.h264o_dec_table_coeff_token.argtypes = [C.c_int, C.c_int, C.c_int, ip, up]
@@ -196,6 +200,8 @@ class OracleEncoder:
     RAND_NONREF, RAND_SLICE_TYPES, RAND_PARAMETER_SETS = 16384, 32768, 65536
     # the ends of the QP, level and vector ranges (oracle/h264_oracle.h says what is drawn; tests/range_ends.py holds the cases)
     RAND_RANGE_ENDS = 131072
+    # windows of the inter prediction at the picture's edges, many intra macroblocks in P slices (with RAND_SUBPARTS; tests/pred_cells.py)
+    RAND_PRED_CELLS = 262144
     SHAPE_ALL_I, SHAPE_I_THEN_P, SHAPE_P_THEN_I, SHAPE_ALL_P = 0, 1, 2, 3
 
     def random_picture(self, seed, force_idr=False, features=31):
@@ -367,6 +373,16 @@ class OracleDecoder:
         n = (lib().h264o_dec_coded_width(self.h) // 16) * (lib().h264o_dec_coded_height(self.h) // 16)
         return np.array([lib().h264o_dec_mb_qp(self.h, i) for i in range(n)], dtype=np.int32)
 
+    def mb_avail(self):
+        """per macroblock: its neighbours left, top, top-right, top-left available (bits 0..3) and available for intra prediction (bits 4..7)"""
+        n = (lib().h264o_dec_coded_width(self.h) // 16) * (lib().h264o_dec_coded_height(self.h) // 16)
+        return np.array([lib().h264o_dec_mb_avail(self.h, i) for i in range(n)], dtype=np.uint8)
+
+    def mb_intra_modes(self):
+        """per macroblock: Intra4x4PredMode of its sixteen 4x4 blocks (raster order), Intra16x16PredMode, intra_chroma_pred_mode"""
+        n = (lib().h264o_dec_coded_width(self.h) // 16) * (lib().h264o_dec_coded_height(self.h) // 16)
+        return np.array([[lib().h264o_dec_mb_intra_mode(self.h, i, k) for k in range(18)] for i in range(n)], dtype=np.uint8)
+
     def mb_mv(self, addr, blk4=0):
         x, y, r = C.c_int(0), C.c_int(0), C.c_int(0)
         lib().h264o_dec_mb_mv(self.h, addr, blk4, C.byref(x), C.byref(y), C.byref(r))
@@ -392,6 +408,12 @@ class OracleDecoder:
         n = lib().h264o_dec_dbf_count()
         assert n == Dbf.COUNT, "oracle/h264_oracle.h and Dbf disagree about H264O_DBF_COUNT"
         return Dbf(np.ctypeslib.as_array(C.cast(lib().h264o_dec_dbf(self.h), C.POINTER(C.c_uint32)), shape=(n,)).astype(np.int64))
+
+    def pred(self):
+        """h264o_dec_pred of the last decoded picture: a Pred (a copy)"""
+        n = lib().h264o_dec_pred_count()
+        assert n == Pred.COUNT, "oracle/h264_oracle.h and Pred disagree about H264O_PRED_COUNT"
+        return Pred(np.ctypeslib.as_array(C.cast(lib().h264o_dec_pred(self.h), C.POINTER(C.c_uint32)), shape=(n,)).astype(np.int64))
 
     def close(self):
         if self.h:
@@ -422,3 +444,31 @@ class Dbf:
 
     def __add__(self, other):
         return Dbf(self.flat + other.flat)
+
+
+class Pred:
+    """the prediction account of one picture, or the sum of several (oracle/h264_oracle.h, H264O_PRED_*, says what every cell counts):
+    p["name"] is the section as an array of its shape, in the header's order"""
+    SHAPES = ("skip", "16x16", "16x8", "8x16", "8x8", "8x4", "4x8", "4x4")
+    RELATIONS = ("inside", "cross_low", "cross_high", "beyond_low", "beyond_high", "cross_both")
+    REASONS = ("outside", "other_slice", "not_yet_decoded", "constrained_inter", "same_mb", "intra_mb", "ipcm_mb", "inter_mb")
+    SIDES = ("left", "top", "top_left", "top_right")
+    SECTIONS = (("l_shape", (8, 4, 4)), ("l_ref", (3, 4, 4)), ("l_rel", (2, 4, 6)), ("l_cross", (2, 4, 2, 4)), ("l_corner", (2, 2)),
+                ("b_ref", (3, 4, 4)), ("b_align", (4, 4)), ("b_rdist", (5,)), ("l_clip", (16, 3, 2)), ("c_frac", (8, 8)), ("c_rel", (2, 2, 6)),
+                ("c_cross", (2, 2, 2, 4)), ("c_rdist", (8,)), ("c_pair", (3,)), ("c_pair_mixed", (1,)), ("i4", (9, 16)), ("i4_nb", (4, 8)),
+                ("i4_tr_nyd", (16,)), ("i4_tr", (2, 2)), ("i16", (4, 8)), ("ic", (4, 8)), ("ic_dc", (4, 2, 2)), ("plane_clip", (2, 2)), ("ibi", (4, 2)))
+    COUNT = sum(int(np.prod(shape)) for _, shape in SECTIONS)
+
+    def __init__(self, flat=None):
+        self.flat = np.zeros(self.COUNT, np.int64) if flat is None else flat
+        self.sections, at = {}, 0
+        for name, shape in self.SECTIONS:
+            n = int(np.prod(shape))
+            self.sections[name] = self.flat[at:at + n].reshape(shape)
+            at += n
+
+    def __getitem__(self, name):
+        return self.sections[name]
+
+    def __add__(self, other):
+        return Pred(self.flat + other.flat)
